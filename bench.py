@@ -12,6 +12,13 @@ touching the GPU, and exits with their status.  The per-GPU work is fixed (weak
 scaling), `value` is the whole-job aggregate; `ranks_seen` is an RCCL
 all-reduce of ones.  WORLD_SIZE != --gpus is an error.
 
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed
+step returned to its caller -- loss.npy, and the model's variables (after the
+update) and gradients, each concatenated in reference creation order
+(variables.npy, gradients.npy) -- as float32.  Inputs and initial weights are
+seeded, so two builds run with the same arguments can be compared file for
+file.
+
 Extra objects on the JSON line:
   roofline     - the dominant kernel (gemm_nn3_kernel: the skip-sum /
                  post-processing fp32 MFMA GEMMs and their data gradients),
@@ -122,6 +129,26 @@ def cpu_model():
 def log(msg):
     sys.stderr.write('[bench] %s\n' % msg)
     sys.stderr.flush()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """Write each of `arrays` ({name: array}) flattened to out_dir/<name>.npy
+    in float32.  When they hold more than `cap` bytes in all, an array larger
+    than its share of `cap` is cut to a sample of its elements at indices
+    fixed by a seeded generator, the same on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+            for k, v in arrays.items()}
+    share = (cap // max(len(flat), 1) - 4096) // 4   # 4096: room for the header
+    over = sum(a.nbytes for a in flat.values()) > cap
+    for name, a in flat.items():
+        if over and a.size > share:
+            idx = np.random.default_rng(0).choice(a.size, share, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(params, T, max_seconds=20.0, max_steps=20):
@@ -524,7 +551,12 @@ def main():
                          '(default: both schedules, value from the faster)')
     ap.add_argument('--no-secondary', action='store_true',
                     help='skip the forward-only and fast-generation figures')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the last timed step\'s loss, variables and '
+                         'gradients to DIR/<name>.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # run plainly: start the N ranks ourselves.  Nothing in this process
@@ -654,6 +686,15 @@ def main():
     log('warm-up done, timing %d steps' % args.steps)
     net._gemm_events = None          # the headline loop is un-instrumented
     dt, loss = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        # before the instrumented pass below steps the model again
+        dump_outputs(args.dump_outputs, {
+            'loss': loss.detach().cpu().numpy(),
+            'variables': torch.cat([v.reshape(-1) for _, v in
+                                    net.named_variables()]).cpu().numpy(),
+            'gradients': torch.cat([v.reshape(-1) for _, v in
+                                    net.named_variables(net.gradients)]).cpu().numpy()})
+        log('outputs of the last timed step written to %s' % args.dump_outputs)
     isteps = max(1, min(5, args.steps))
     events, ar_us = instrumented(isteps)
     ranks_seen = 1

@@ -135,11 +135,13 @@ def test_train_histogram_summaries(hip_lib, tmp_path, params):
     assert z['layer0_filter/counts'].sum() == 2 * 32 * 32
 
 
-def test_bench_line_carries_the_contract(hip_lib):
+def test_bench_line_carries_the_contract(hip_lib, tmp_path):
     """`python bench.py` (small shape): ONE JSON line with the driver's keys,
     the roofline object measured live (NN GEMMs + the TN GEMMs beside them),
     the whole-step fraction, the CPU baseline with its core count and CPU
-    model, and the secondary figures (GC step, B = 1 step, fast generation)."""
+    model, and the secondary figures (GC step, B = 1 step, fast generation);
+    --dump-outputs writes the last timed step's loss, variables and
+    gradients."""
     import json
     import subprocess
     import sys
@@ -148,7 +150,8 @@ def test_bench_line_carries_the_contract(hip_lib):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'),
                         '--steps', '2', '--warmup', '1', '--batch', '2',
-                        '--samples', '4000'], env=env, stdout=subprocess.PIPE,
+                        '--samples', '4000', '--dump-outputs', str(tmp_path / 'out')],
+                       env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
@@ -183,3 +186,13 @@ def test_bench_line_carries_the_contract(hip_lib):
     for k in ('forward_only_samples_per_s', 'fastgen_us_per_sample',
               'gc_ms_per_step', 'b1_ms_per_step'):
         assert sec[k] > 0, k
+    from util import O, DEFAULT, cfg_with, flat_named
+    got = {k: np.load(str(tmp_path / 'out' / (k + '.npy')))
+           for k in ('loss', 'variables', 'gradients')}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got['loss'].tolist() == [float(np.float32(r['config']['final_loss']))]
+    n = sum(np.asarray(a).size for _, a in flat_named(
+        O.create_variables(cfg_with(DEFAULT, batch_size=2))))
+    assert got['variables'].size == got['gradients'].size == n
+    assert np.isfinite(got['variables']).all() and np.isfinite(got['gradients']).all()
+    assert np.abs(got['gradients']).max() > 0

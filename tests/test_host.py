@@ -155,3 +155,24 @@ def test_bench_synthetic_clips():
     assert np.array_equal(a[0], b[0]) and np.abs(a).max() <= 1.0
     assert len(np.unique(O.mu_law_encode(a, 256))) > 100
     assert bench.host_cores() >= 1
+
+
+def test_bench_dump_outputs_float32_and_capped(tmp_path):
+    """bench.py --dump-outputs: each array flattened to <name>.npy in float32;
+    over the size cap, a sample at fixed indices that stays under it."""
+    import bench
+    rng = np.random.default_rng(5)
+    arrays = {'loss': np.float64(2.5), 'variables': rng.standard_normal(10000)}
+    bench.dump_outputs(str(tmp_path / 'all'), arrays)
+    got = {k: np.load(str(tmp_path / 'all' / (k + '.npy'))) for k in arrays}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got['loss'].tolist() == [2.5]
+    assert np.array_equal(got['variables'], arrays['variables'].astype(np.float32))
+    cap = 2 * (4096 + 4 * 1000)      # two arrays: 1000 elements each
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays, cap=cap)
+    files = [str(tmp_path / d / 'variables.npy') for d in ('a', 'b')]
+    a, b = np.load(files[0]), np.load(files[1])
+    assert a.size == 1000 and np.array_equal(a, b)
+    assert np.isin(a, arrays['variables'].astype(np.float32)).all()
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / 'a').iterdir()) <= cap
