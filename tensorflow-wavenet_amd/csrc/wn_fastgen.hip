@@ -321,12 +321,14 @@ __global__ __launch_bounds__(FG_THREADS, 1) void fastgen_kernel(FastGen g) {
         // temperature: exp(log(p)/tau - logsumexp) in float64, then inverse
         // CDF with a counter-based uniform (np.random.choice equivalent)
         // (sampling weights proportional to exp(log(p)/tau); at tau == 1
-        // that is p itself, no transcendental needed)
+        // that is p itself, no transcendental needed; a probability of 0 --
+        // float32 underflow -- has weight exactly 0 at any tau, as
+        // np.log(0) = -inf gives it in the reference)
         const double tau = (double)g.temperature;
         if (g.temperature != 1.0f) {
           double mx = -1e300;
           for (int q = lane; q < Q; q += 64) {
-            const double lp = log(pd[q] > 0.0 ? pd[q] : 1e-300) / tau;
+            const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
             pd[q] = lp;
             mx = fmax(mx, lp);
           }
@@ -358,6 +360,7 @@ __global__ __launch_bounds__(FG_THREADS, 1) void fastgen_kernel(FastGen g) {
           for (int q = q0; q < q1; ++q) {
             c += pd[q];
             if (u < c) { pick = q; break; }
+            if (pd[q] > 0.0) pick = q;   // (u past the rounded walk: the last code of weight > 0)
           }
         }
         // exactly one lane holds the pick (u < total); fall back to Q-1
@@ -829,12 +832,12 @@ __device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lan
   int next = 0;
   if (local + 1 >= n_given) {
     // sampling weights w_q proportional to exp(log(p_q) / tau)
-    // (generate.py:229-233); at tau == 1 that is p_q itself
+    // (generate.py:229-233); at tau == 1 that is p_q itself; p_q == 0: w_q = 0
     const double tau = (double)temperature;
     if (temperature != 1.0f) {
       double mx = -1e300;
       for (int q = lane; q < Q; q += 64) {
-        const double lp = log(pd[q] > 0.0 ? pd[q] : 1e-300) / tau;
+        const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
         pd[q] = lp;
         mx = fmax(mx, lp);
       }
@@ -865,6 +868,7 @@ __device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lan
       for (int q = q0; q < q1; ++q) {
         c += pd[q];
         if (u < c) { pick = q; break; }
+        if (pd[q] > 0.0) pick = q;       // (u past the rounded walk: the last code of weight > 0)
       }
     }
     int best = pick;
@@ -1260,7 +1264,7 @@ __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& 
     double lp[2] = {-1e300, -1e300};
 #pragma unroll
     for (int j = 0; j < PER; ++j)
-      if (q0 + j < q1) lp[j] = log(pq[j] > 0.0 ? pq[j] : 1e-300) / tau;
+      if (q0 + j < q1) lp[j] = pq[j] > 0.0 ? log(pq[j]) / tau : -INFINITY;
     const double wm = wave_max_f64(PER == 2 ? fmax(lp[0], lp[1]) : lp[0]);
     if (lane == 0 && wave < 4) part[4 + wave] = wm;
     __syncthreads();
@@ -1286,7 +1290,7 @@ __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& 
   const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
   int next = -1;
   if (q1 > q0 && u >= excl && u < incl)
-    next = (PER == 2 && q1 - q0 == 2 && u >= excl + pq[0]) ? q0 + 1 : q0;
+    next = (PER == 2 && q1 - q0 == 2 && pq[1] > 0.0 && u >= excl + pq[0]) ? q0 + 1 : q0;
   // (u == total after rounding: the last code, as fg_draw_wave)
   if (q1 == Q && q1 > q0 && u >= incl) next = Q - 1;
   if (next >= 0) {
@@ -2167,7 +2171,7 @@ __global__ __launch_bounds__(F64 ? 512 : FGW_THREADS, 1) void fastgen_wide_kerne
         if (g.temperature != 1.0f) {
           double mx = -1e300;
           for (int q = lane; q < Q; q += 64) {
-            const double lp = log(pd[q] > 0.0 ? pd[q] : 1e-300) / tau;
+            const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
             pd[q] = lp;
             mx = fmax(mx, lp);
           }
@@ -2198,6 +2202,7 @@ __global__ __launch_bounds__(F64 ? 512 : FGW_THREADS, 1) void fastgen_wide_kerne
           for (int q = q0; q < q1; ++q) {
             c += pd[q];
             if (u < c) { pick = q; break; }
+            if (pd[q] > 0.0) pick = q;   // (u past the rounded walk: the last code of weight > 0)
           }
         }
         int best = pick;

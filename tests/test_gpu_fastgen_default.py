@@ -12,12 +12,17 @@ import numpy as np
 import pytest
 import torch
 
+import draw_ref as D
 from util import O, ROOT, cfg_with, build_pair
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5            # probabilities, float32 device path vs float64 oracle
 N_TRACE = 1200        # > 2 * 512 (two wraps of the longest ring) + graph replay
 N_SEED = 6000         # > receptive field 5117
+N_GEN = 16000         # BASELINE.json configs[4]: free-running draws
+SHARP = 5.0           # postprocess2 scale of the gc case: max probability ~0.2 - 0.8
+PATHS = (('one_wg', False, False), ('multi_cu_graph', True, False),
+         ('multi_cu_persistent', True, True))
 
 
 def default_cfg(**kw):
@@ -176,3 +181,118 @@ def test_persistent_launch_failure_restores_state_and_falls_back(hip_lib, monkey
     assert calls == [0]                     # not tried again on this generator
     assert np.array_equal(more_a, more_b)
     assert torch.equal(a._gen['state'], b._gen['state'])
+
+
+@pytest.fixture(scope='module', params=['plain', 'gc_sharp'])
+def free_run(request, hip_lib):
+    """configs[4] at its stated length: generate(16000, seed_samples=[128],
+    seed=2) on each device path, plain and with GC 32 x 377 (id 123); in the
+    gc case postprocess2 is scaled by SHARP so that the distributions are far
+    from uniform and the drawn sequence follows them.  Returns (net, gid,
+    {path: (codes [16001], probabilities [16000, 256], end-state peek
+    [256])}, float64 oracle probabilities of all 16001 positions of the
+    persistent run's codes, as float32)."""
+    gc = request.param == 'gc_sharp'
+    cfg = default_cfg(**(dict(global_condition_channels=32,
+                              global_condition_cardinality=377) if gc else {}))
+    net, var = build_pair(cfg)
+    if gc:
+        var['postprocessing']['postprocess2'] = var['postprocessing']['postprocess2'] * SHARP
+        net.load_nested(var)
+    gid = 123 if gc else None
+    net.fastgen_graph_steps = 200
+    runs = {}
+    for name, multi, persist in PATHS:
+        net.fastgen_multi_cu = multi
+        net.fastgen_persistent = persist
+        out, pr = net.generate(N_GEN, seed_samples=[128], seed=2, return_proba_every=1,
+                               global_condition=gid)
+        out = out.cpu().numpy()
+        # the queues now hold codes 0 .. 15999; the last code is not pushed
+        peek = net.predict_proba_incremental(int(out[-1]), global_condition=gid,
+                                             push=False).cpu().numpy()
+        runs[name] = (out, pr.cpu().numpy(), peek)
+    codes = runs['multi_cu_persistent'][0]
+    emb = O.embed_gc(cfg, var, None if gid is None else np.array([gid]), 1)
+    logits = O.network_forward(cfg, var, O.one_hot(codes[None], 256, np.float64), emb)
+    ref = O._softmax64(logits[0])
+    return net, gid, runs, ref
+
+
+def _agree(c, codes):
+    """Number of leading codes two runs share (N_GEN + 1: all): probability
+    rows 0 .. _agree - 1 were computed from the same history."""
+    d = np.nonzero(c != codes)[0]
+    return int(d[0]) if d.size else N_GEN + 1
+
+
+def test_16000_samples_same_on_every_path(free_run):
+    """The single workgroup, the step kernels (80 graph replays) and ONE
+    persistent launch draw the same 16001 codes, their probabilities 1e-6
+    apart.  Far from uniform (gc_sharp: logits 5x larger, so 5x the rounding)
+    two paths may part at a rounding tie: the step's u * total lies between
+    the two paths' CDF boundaries, no farther from either than the two
+    probability rows are apart, and the codes are the two beside it."""
+    _, gid, runs, ref = free_run
+    codes, pr = runs['multi_cu_persistent'][:2]
+    assert codes.shape == (N_GEN + 1,) and codes[0] == 128
+    assert pr.shape == (N_GEN, 256)
+    path_tol = 1e-6 if gid is None else 1e-6 * SHARP
+    for name, (c, p, _) in runs.items():
+        k = _agree(c, codes)
+        if gid is None:
+            assert k == N_GEN + 1, (name, 'first differing code', k)
+        err = np.abs(p[:k] - pr[:k]).max(axis=1)
+        assert err.max() <= path_tol, (name, int(err.argmax()), float(err.max()))
+        if k <= N_GEN:
+            r = k - 1                      # the step that drew code k
+            u = D.uniform(2, r)
+            wa, wb = D.weights(p[r], 1.0), D.weights(pr[r], 1.0)
+            l1 = float(np.abs(wa - wb).sum())
+            assert max(float(D.margin(wa, u)), float(D.margin(wb, u))) <= l1, (name, k)
+            assert {int(c[k]), int(codes[k])} == set(D.boundary_codes(wb, u)), (name, k)
+    if gid is not None:
+        # (SHARP) the drawn sequence is not noise: the max probability is
+        # large along it
+        assert 0.2 < np.median(ref.max(axis=1)) < 0.95
+
+
+def test_16000_samples_match_restatement(free_run):
+    """Every one of the 16000 drawn codes of every path is
+    pick(weights(p, 1), uniform(2, k)) for its step k and the probabilities
+    the device returned for that step (tests/draw_ref.py)."""
+    _, _, runs, _ = free_run
+    for name, (c, p, _) in runs.items():
+        D.check_draws(c[1:], p, 1.0, 2, np.arange(N_GEN), what=name)
+
+
+def test_16000_samples_vs_float64_oracle(free_run):
+    """The device's probabilities at ALL 16000 steps (~31 wraps of the d = 512
+    rings, the sample and probability buffers at full length, the persistent
+    launch held for the whole run) equal the float64 oracle teacher-forced on
+    the drawn codes; so does the end state (a push=False peek at position
+    16000).  A path that parted from the persistent run at a rounding tie
+    (gc_sharp) is compared up to that step."""
+    _, gid, runs, ref = free_run
+    codes = runs['multi_cu_persistent'][0]
+    for name, (c, p, peek) in runs.items():
+        k = _agree(c, codes)
+        assert k == N_GEN + 1 or (gid is not None and name != 'multi_cu_persistent')
+        n = min(k, N_GEN)                 # rows computed from the persistent run's history
+        err = np.abs(p[:n] - ref[:n]).max(axis=1)
+        assert err.max() < TOL, (name, int(err.argmax()), float(err.max()))
+        if k == N_GEN + 1:
+            assert np.abs(peek - ref[N_GEN]).max() < TOL, name
+
+
+def test_16000_samples_continued_in_two_halves(free_run):
+    """generate(8000) then continue_generation(8000) on the persistent path
+    draws the codes of the single 16000-sample call: the counter goes on
+    from step 8000."""
+    net, gid, runs, _ = free_run
+    net.fastgen_multi_cu = net.fastgen_persistent = True
+    a = net.generate(N_GEN // 2, seed_samples=[128], seed=2,
+                     global_condition=gid).cpu().numpy()
+    b = net.continue_generation(N_GEN // 2, int(a[-1]), 1.0, gid, 2).cpu().numpy()
+    k = _agree(np.concatenate([a, b]), runs['multi_cu_persistent'][0])
+    assert k == N_GEN + 1, ('first differing code', k)
