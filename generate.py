@@ -65,13 +65,36 @@ def get_arguments(argv=None):
     p.add_argument('--gc_cardinality', type=int, default=None)
     p.add_argument('--gc_id', type=int, default=None)
     p.add_argument('--seed', type=int, default=0, help='sampling RNG seed')
+    p.add_argument('--clips', type=int, default=1,
+                   help='independent clips generated together (fast path); '
+                   'clip i draws with --seed + i and is written to '
+                   '<stem>_<i><ext>')
+    p.add_argument('--gc_ids', type=str, default=None,
+                   help='comma-separated global condition ids, one clip each '
+                   '(sets --clips to their number)')
     a = p.parse_args(argv)
+    if a.gc_ids is not None:
+        a.gc_ids = [int(v) for v in a.gc_ids.split(',') if v.strip()]
+        if not a.gc_ids:
+            raise ValueError('--gc_ids needs at least one id')
+        if a.clips not in (1, len(a.gc_ids)):
+            raise ValueError('--clips {} does not match the {} ids of --gc_ids'
+                             .format(a.clips, len(a.gc_ids)))
+        if a.gc_id is not None:
+            raise ValueError('give either --gc_id or --gc_ids')
+        a.clips = len(a.gc_ids)
+        if len(a.gc_ids) == 1:
+            a.gc_id, a.gc_ids = a.gc_ids[0], None
+    if a.clips < 1:
+        raise ValueError('--clips must be >= 1')
+    if a.clips > 1 and not a.fast_generation:
+        raise ValueError('--clips > 1 needs --fast_generation true')
     if a.gc_channels is not None:
         if a.gc_cardinality is None:
             raise ValueError("Globally conditioning but gc_cardinality not "
                              "specified. Use --gc_cardinality=377 for full "
                              "VCTK corpus.")
-        if a.gc_id is None:
+        if a.gc_id is None and a.gc_ids is None:
             raise ValueError("Globally conditioning, but global condition was "
                              "not specified. Use --gc_id to specify global "
                              "condition.")
@@ -138,6 +161,8 @@ def main(argv=None):
             out = mu_law_decode(np.asarray(codes, np.int32), Q).cpu().numpy()
             write_wav(out, rate, args.wav_out_path)
 
+    if args.clips > 1:
+        return _main_clips(args, net, waveform, Q, rate, logdir)
     if args.fast_generation:
         if args.wav_seed:
             print('Priming generation with {} seed samples...'
@@ -194,6 +219,54 @@ def main(argv=None):
             np.asarray(waveform, np.int32))
     dump(waveform)
     print('Finished generating. Codes saved under {}.'.format(logdir))
+    return 0
+
+
+def _clip_path(path, i):
+    stem, ext = os.path.splitext(path)
+    return '{}_{}{}'.format(stem, i, ext)
+
+
+def _main_clips(args, net, waveform, Q, rate, logdir):
+    """--clips N > 1: N streams in lock step (WaveNetModel.generate_batch),
+    clip i drawing with --seed + i, all primed by the same seed."""
+    from wavenet import mu_law_decode
+    N = args.clips
+    seeds = [args.seed + i for i in range(N)]
+    gc = args.gc_ids if args.gc_ids is not None else args.gc_id
+
+    def dump(codes):
+        if args.wav_out_path:
+            for i in range(N):
+                out = mu_law_decode(np.asarray(codes[i], np.int32), Q
+                                    ).cpu().numpy()
+                write_wav(out, rate, _clip_path(args.wav_out_path, i))
+
+    if args.wav_seed:
+        print('Priming generation of {} clips with {} seed samples...'
+              .format(N, len(waveform)))
+    chunk = args.save_every or args.samples
+    done = min(chunk, args.samples)
+    codes = net.generate_batch(done, seeds, seed_samples=waveform,
+                               temperature=args.temperature,
+                               global_condition=gc).cpu().numpy()
+    parts = [codes]
+    while done < args.samples:
+        if args.save_every:
+            dump(np.concatenate(parts, axis=1))
+        n = min(chunk, args.samples - done)
+        more = net.continue_generation_batch(n, parts[-1][:, -1], seeds,
+                                             args.temperature, gc)
+        parts.append(more.cpu().numpy())
+        done += n
+        print('Sample {:3<d}/{:3<d}'.format(done, args.samples), end='\r')
+    codes = np.concatenate(parts, axis=1).astype(np.int32)
+    print()
+    os.makedirs(logdir, exist_ok=True)
+    np.save(os.path.join(logdir, 'generated_codes.npy'), codes)
+    dump(codes)
+    print('Finished generating {} clips. Codes saved under {}.'
+          .format(N, logdir))
     return 0
 
 

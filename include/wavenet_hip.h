@@ -552,6 +552,66 @@ int wn_fastgen_pre(const float* layer0, long layer_stride,
 int wn_fastgen_pack(const float* layer0, long layer_stride, float* img, int L,
                     void* stream);
 
+/* ---- batched fast generation (csrc/wn_fastgen_batch.hip): 1 <= B <= 256
+ * independent streams stepped in lock step, the streams on the MFMA rows of
+ * the chain (32 per workgroup).  Shapes of wn_fastgen_step: C = 32, S <= 512,
+ * Q <= 512, L <= 64.  Rows are padded to Bp = wn_fastgen_batch_rows(B) (a
+ * multiple of 32); a stream's results do not depend on B or on its position.
+ * Buffers: state float[wn_fastgen_batch_state_floats] (ring rows [sum d][Bp][32]),
+ * cursors int32[4] ({steps pushed, draw pending, 0, 0}), prev int32[Bp] (code
+ * consumed one step back), pre float[L][Bp][64], z_all float[Bp][L * 32],
+ * h1 / h2 float[Bp][S], logits float[Bp][Q], seeds uint64[B].
+ * gc_bias_fg: [L][B][64] with bias_stream_stride 64 (per-stream GC bias), or
+ * [L][1][64] with 0, or NULL.
+ * samples_io int32[B][ctl[4]]: stream b's step i consumes samples_io[b][i]
+ * (cursors[0] - ctl[0] = i); proba_out (optional) float[B][ctl[5]][Q].
+ * ctl: int32[8] = {base (cursors[0] when the call started), n_given,
+ * proba_every, temperature (float bits), samples row stride, proba rows per
+ * stream, 0, 0}.  The draw of stream b takes seeds[b] and the counter rule of
+ * the single-stream generator.  A step's draw runs at the start of the NEXT
+ * step; wn_fastgen_batch_finish draws for the last one (no-op when none is
+ * pending).  wn_fastgen_batch_pre fills pre for the step the queues are at
+ * (call once before a sequence of steps). */
+int wn_fastgen_batch_rows(int B);
+long wn_fastgen_batch_state_floats(const int32_t* dilations_host, int L, int B);
+int wn_fastgen_batch_init(float* state, long state_floats, int32_t* cursors,
+                          int32_t* prev, int B, void* stream);
+int wn_fastgen_batch_pre(const float* layer0, long layer_stride,
+                         const float* gc_bias_fg, int bias_stream_stride,
+                         const int32_t* dilations_dev, int L, int B,
+                         const float* state, const int32_t* cursors, float* pre,
+                         void* stream);
+int wn_fastgen_batch_step(const float* params_causal, const float* layer0,
+                          long layer_stride, const float* skip_w,
+                          const float* skip_bsum, const float* post1_w,
+                          const float* post1_b, const float* post2_w,
+                          const float* post2_b, const float* gc_bias_fg,
+                          int bias_stream_stride, const int32_t* dilations_dev,
+                          int L, int S, int Q, int B, float* state,
+                          int32_t* cursors, int32_t* prev, int32_t* samples_io,
+                          const int32_t* ctl, const uint64_t* seeds,
+                          float* proba_out, int use_biases, float* pre,
+                          float* z_all, float* h1, float* h2, float* logits,
+                          void* stream);
+/* The stages [first, last) of one step (0 draw, 1 chain, 2 skip sum + next
+ * pre-activations, 3 post1, 4 logits; wn_fastgen_batch_step = 0 .. 5), same
+ * arguments: for timing each launch between the caller's own events. */
+int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
+                            const float* layer0, long layer_stride,
+                            const float* skip_w, const float* skip_bsum,
+                            const float* post1_w, const float* post1_b,
+                            const float* post2_w, const float* post2_b,
+                            const float* gc_bias_fg, int bias_stream_stride,
+                            const int32_t* dilations_dev, int L, int S, int Q,
+                            int B, float* state, int32_t* cursors, int32_t* prev,
+                            int32_t* samples_io, const int32_t* ctl,
+                            const uint64_t* seeds, float* proba_out,
+                            int use_biases, float* pre, float* z_all, float* h1,
+                            float* h2, float* logits, void* stream);
+int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
+                            const int32_t* ctl, const uint64_t* seeds,
+                            float* proba_out, const float* logits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

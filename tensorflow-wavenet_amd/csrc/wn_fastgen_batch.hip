@@ -1,0 +1,600 @@
+// Batched fast generation: B independent streams stepped in lock step
+// (WaveNetModel.generate_batch).  The batched counterpart of the step kernels
+// of wn_fastgen.hip (wn_fastgen_step): the reference's generator is batch
+// shaped (every FIFO queue holds (batch_size, channels) rows, model.py:450-485),
+// and with B streams each layer of the serial chain becomes a [B, 32] x [32, 64]
+// product, so the streams sit on the rows of v_mfma_f32_16x16x4_f32.
+//
+// One step, five launches (no in-launch waits, no cooperative launch):
+//   fgb_draw_kernel     B waves     : the PREVIOUS step's float64 softmax,
+//                                     temperature and inverse-CDF draw, one
+//                                     wave per stream (when one is pending)
+//   fgb_chain_kernel    Bp/32 WGs   : the L layers for a group of 32 streams
+//                                     (4 waves, one 16 x 16 output tile each)
+//   fgb_skip_kernel     many WGs    : h1 = relu(z_all . Ws + bsum), and the
+//                                     NEXT step's past-tap pre-activations of
+//                                     every (layer, group)
+//   fgb_post1_kernel                : h2 = relu(h1 . W1 + b1)
+//   fgb_logits_kernel               : logits = h2 . W2 + b2 (a draw pending)
+// wn_fastgen_batch_finish draws for the last step of a sequence.
+//
+// Batch invariance: a row's arithmetic never depends on B or on the stream's
+// position.  The MFMA tiles have a fixed height (zero-filled rows past B), an
+// f32 MFMA is an fmaf chain per output element whatever its row, and every
+// K split is a function of the model shape only.  Stream b therefore gives
+// bitwise the same probabilities and codes alone or inside any batch.
+//
+// State: ring row [sum(d)][Bp][32] (all streams share one cursor), so a
+// layer's past tap is one contiguous read for a whole group.
+#include "wn_common.h"
+
+#define FGB_MAXB 256
+#define FGB_TILE 32      // streams per chain workgroup
+#define FGB_MAXL 64
+#define FGB_MAXS 512
+#define FGB_MAXQ 512
+#define FGB_XLD 33       // LDS row stride of the chain's x / z tiles
+
+// ctl: int32[8] per call (device memory, so that a captured graph serves
+// every call): base (cursors[0] when the call started), n_given, proba_every,
+// temperature (float bits), row stride of samples_io, rows per stream of
+// proba_out, 0, 0
+#define FGB_CTL_BASE 0
+#define FGB_CTL_NGIVEN 1
+#define FGB_CTL_PEVERY 2
+#define FGB_CTL_TEMP 3
+#define FGB_CTL_LDS 4
+#define FGB_CTL_LDP 5
+
+struct FgBatch {
+  const float* causal;     // [2][Q][32]
+  const float* layer0;     // layer blocks
+  long layer_stride;
+  const float* skip_w;     // [L * 32][S]
+  const float* skip_bsum;  // [S] or null
+  const float* post1_w;    // [S][S]
+  const float* post1_b;    // [S] or null
+  const float* post2_w;    // [S][Q]
+  const float* post2_b;    // [Q] or null
+  const float* bias_fg;    // [L][nb][64] or null; nb = B (stride 64) or 1 (stride 0)
+  int bias_stride;
+  const int32_t* dil;
+  int L, S, Q, B, Bp;
+  float* state;            // [sum(d)][Bp][32]
+  int32_t* cursors;        // [0] steps pushed, [1] draw pending
+  int32_t* prev;           // [Bp] code consumed one step back (-1: none)
+  int32_t* samples;        // [B][ctl[LDS]], indexed by cursors[0] - ctl[BASE]
+  const int32_t* ctl;
+  const uint64_t* seeds;   // [B]
+  float* proba_out;        // [B][ctl[LDP]][Q] or null
+  int use_dense_bias;
+  float* pre;              // [L][Bp][64]
+  float* z_all;            // [Bp][L * 32]
+  float* h1;               // [Bp][S]
+  float* h2;               // [Bp][S]
+  float* logits;           // [Bp][Q]
+};
+
+__device__ __forceinline__ uint64_t fgb_splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// 16 x 16 x 4 f32 MFMA.  Lane l: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15];
+// C/D: column l & 15, rows 4 (l >> 4) + r.
+__device__ __forceinline__ f32x4 fgb_mfma(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// ---------------------------------------------------------------- the draw
+// float64 softmax of stream b's logits, temperature, inverse-CDF draw:
+// fg_draw_wave of wn_fastgen.hip with the stream's own rows and seed (the
+// counter rule of tests/draw_ref.py: counter = the step that produced the
+// logits).  One wave; pd: FGB_MAXQ doubles of LDS owned by it.
+__device__ void fgb_draw_wave(const FgBatch& g, double* pd, int lane, int b, int step) {
+  const int Q = g.Q;
+  const float* lg = g.logits + (long)b * Q;
+  const int local = step - g.ctl[FGB_CTL_BASE];
+  const int n_given = g.ctl[FGB_CTL_NGIVEN];
+  const int proba_every = g.ctl[FGB_CTL_PEVERY] > 0 ? g.ctl[FGB_CTL_PEVERY] : 1;
+  const float temperature = __int_as_float(g.ctl[FGB_CTL_TEMP]);
+  int32_t* samples = g.samples + (long)b * g.ctl[FGB_CTL_LDS];
+  const uint64_t seed = g.seeds[b];
+  for (int q = lane; q < Q; q += 64) pd[q] = (double)lg[q];
+  __builtin_amdgcn_wave_barrier();
+  double m = -1e300;
+  for (int q = lane; q < Q; q += 64) m = fmax(m, pd[q]);
+  for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+  double se = 0.0;
+  for (int q = lane; q < Q; q += 64) {
+    const double e = exp(pd[q] - m);
+    pd[q] = e;
+    se += e;
+  }
+  for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
+  const bool want_p = g.proba_out && (local % proba_every == 0);
+  float* po = want_p ? g.proba_out + ((long)b * g.ctl[FGB_CTL_LDP] + local / proba_every) * Q
+                     : nullptr;
+  for (int q = lane; q < Q; q += 64) {
+    const float p32 = (float)(pd[q] / se);
+    if (po) po[q] = p32;
+    pd[q] = (double)p32;
+  }
+  if (local + 1 < n_given) return;       // still inside the given samples
+  const double tau = (double)temperature;
+  if (temperature != 1.0f) {
+    double mx = -1e300;
+    for (int q = lane; q < Q; q += 64) {
+      const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
+      pd[q] = lp;
+      mx = fmax(mx, lp);
+    }
+    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
+  }
+  __builtin_amdgcn_wave_barrier();
+  const int per = (Q + 63) / 64;
+  const int q0 = lane * per, q1 = min(Q, q0 + per);
+  double seg = 0.0;
+  for (int q = q0; q < q1; ++q) seg += pd[q];
+  double incl = seg;
+  for (int o = 1; o < 64; o <<= 1) {
+    const double v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
+  }
+  const double total = __shfl(incl, 63);
+  const uint64_t r = fgb_splitmix64(seed ^ fgb_splitmix64((uint64_t)step));
+  const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
+  const double up = __shfl_up(incl, 1);
+  const double excl = lane == 0 ? 0.0 : up;
+  int pick = -1;
+  if (u >= excl && u < incl) {
+    double c = excl;
+    pick = q1 - 1;
+    for (int q = q0; q < q1; ++q) {
+      c += pd[q];
+      if (u < c) { pick = q; break; }
+      if (pd[q] > 0.0) pick = q;
+    }
+  }
+  int best = pick;
+  for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
+  if (best < 0) best = Q - 1;
+  if (lane == 0) samples[local + 1] = best;
+}
+
+// one wave per stream; reads the cursors, writes none (the chain kernel that
+// follows clears the pending flag, wn_fastgen_batch_finish a memset)
+__global__ __launch_bounds__(256) void fgb_draw_kernel(FgBatch g) {
+  __shared__ double pd[4][FGB_MAXQ];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + w;
+  if (!g.cursors[1] || b >= g.B) return;
+  fgb_draw_wave(g, pd[w], lane, b, g.cursors[0] - 1);
+}
+
+// ---------------------------------------------------------------- the chain
+// Workgroup = 32 streams, 4 waves; wave w owns output tile (rows 16 (w & 1),
+// columns 16 (w >> 1)) of the filter, the gate (same rows / columns, so
+// tanh . sigmoid stays in the lane) and the dense output.  x and z pass
+// between the waves through LDS (two barriers a layer).  Each layer's
+// B operands, dense bias and past-tap pre-activations are loaded into
+// registers two layers ahead (they do not depend on the chain).
+struct FgbLW {
+  float f[8], gt[8], d[8];   // Wf[1], Wg[1], Wd: B[k = 4 s + kk][col]
+  float pf[4], pg[4];        // pre[l][row][col], pre[l][row][32 + col]
+  float bd;
+};
+
+__global__ __launch_bounds__(256) void fgb_chain_kernel(FgBatch g) {
+  __shared__ float xs[FGB_TILE * FGB_XLD];
+  __shared__ float zs[FGB_TILE * FGB_XLD];
+  __shared__ int roff_s[FGB_MAXL], pos_s[FGB_MAXL];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int rb = w & 1, cb = w >> 1;
+  const int ci = lane & 15, kk = lane >> 4;
+  const int col = cb * 16 + ci;            // this lane's output channel
+  const int arow = rb * 16 + ci;           // this lane's A-operand row
+  const int row0 = rb * 16 + kk * 4;       // first of its four output rows
+  const int b0 = blockIdx.x * FGB_TILE;
+  const int L = g.L, Q = g.Q, Bp = g.Bp, KZ = g.L * 32;
+  const int T = g.cursors[0];
+  const int local = T - g.ctl[FGB_CTL_BASE];
+  const long lds = g.ctl[FGB_CTL_LDS];
+
+  auto load = [&](FgbLW& W, int l) {
+    if (l < L) {
+      const float* blk = g.layer0 + (long)l * g.layer_stride;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int k = 4 * s + kk;
+        W.f[s] = blk[1 * 1024 + k * 32 + col];
+        W.gt[s] = blk[3 * 1024 + k * 32 + col];
+        W.d[s] = blk[4 * 1024 + k * 32 + col];
+      }
+      const float* pr = g.pre + ((long)l * Bp + b0 + row0) * 64 + col;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        W.pf[r] = pr[r * 64];
+        W.pg[r] = pr[r * 64 + 32];
+      }
+      W.bd = g.use_dense_bias ? blk[LAYER_OFF_BD + col] : 0.f;
+    }
+  };
+  FgbLW wa, wb;
+  load(wa, 0);
+  load(wb, 1);
+
+  if (w == 0) {   // ring offsets = exclusive prefix sum of the dilations
+    const int dl = lane < L ? g.dil[lane] : 0;
+    int incl = dl;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane < L) {
+      roff_s[lane] = incl - dl;
+      pos_s[lane] = T % dl;
+    }
+  }
+  // causal layer (filter width 2): x = W[0][prev] + W[1][code]
+  float x[4];
+  int code[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = b0 + row0 + r;
+    int c = -1, p = -1;
+    if (b < g.B) {
+      c = g.samples[b * lds + local];
+      p = g.prev[b];
+    }
+    float v = 0.f;
+    if (p >= 0 && p < Q) v = g.causal[(long)p * 32 + col];
+    if (c >= 0 && c < Q) v += g.causal[((long)Q + c) * 32 + col];
+    x[r] = v;
+    code[r] = c;
+    xs[(row0 + r) * FGB_XLD + col] = v;
+  }
+  __syncthreads();
+  // (every wave has read prev[] for its rows)
+  if (cb == 0 && ci == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (b0 + row0 + r < g.B) g.prev[b0 + row0 + r] = code[r];
+  }
+  if (blockIdx.x == 0 && tid == 0) g.cursors[1] = 0;   // the draw has run
+
+  auto body = [&](int l, const FgbLW& W) {
+    // enqueue x_l[T]
+    float* ring = g.state + ((long)(roff_s[l] + pos_s[l]) * Bp + b0 + row0) * 32 + col;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ring[r * 32] = x[r];
+    f32x4 af = {W.pf[0], W.pf[1], W.pf[2], W.pf[3]};
+    f32x4 ag = {W.pg[0], W.pg[1], W.pg[2], W.pg[3]};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const float a = xs[arow * FGB_XLD + 4 * s + kk];
+      af = fgb_mfma(a, W.f[s], af);
+      ag = fgb_mfma(a, W.gt[s], ag);
+    }
+    float* zo = g.z_all + (long)(b0 + row0) * KZ + l * 32 + col;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      // tanh(a) = 2 sigmoid(2 a) - 1, as the single-stream chain
+      const float th = fmaf(2.f, wn_sigmoid(2.f * af[r]), -1.f);
+      const float z = th * wn_sigmoid(ag[r]);
+      zo[(long)r * KZ] = z;
+      zs[(row0 + r) * FGB_XLD + col] = z;
+    }
+    __syncthreads();
+    if (l + 1 < L) {
+      f32x4 ad = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 8; ++s)
+        ad = fgb_mfma(zs[arow * FGB_XLD + 4 * s + kk], W.d[s], ad);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        x[r] += W.bd + ad[r];
+        xs[(row0 + r) * FGB_XLD + col] = x[r];
+      }
+    }
+    __syncthreads();
+  };
+  for (int l = 0; l < L; l += 2) {
+    body(l, wa);
+    load(wa, l + 2);
+    if (l + 1 < L) {
+      body(l + 1, wb);
+      load(wb, l + 3);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- the tail
+// out[m][n] = act(sum_k A[m][k] W[k][n] + bias[n]) for one 16 x 16 tile:
+// the four waves take fixed K quarters, each lane group kk one sixteenth of
+// K (a function of K only), and the quarters are summed in a fixed order.
+struct FgbGemm {
+  const float* A;
+  long lda;
+  int K;
+  const float* W;
+  long ldw;
+  int N;
+  const float* bias;
+  int relu;
+  float* out;
+  long ldo;
+};
+
+__device__ __forceinline__ void fgb_gemm_tile(const FgbGemm& p, int nt, int mt,
+                                              float (*red)[256]) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ci = lane & 15, kk = lane >> 4;
+  const int Kc = (p.K + 15) / 16;
+  const int k0 = (w * 4 + kk) * Kc;
+  const int jc = min(nt * 16 + ci, p.N - 1);   // (columns past N: not stored)
+  const float* ap = p.A + (long)(mt * 16 + ci) * p.lda;
+  const float* wp = p.W + jc;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int s = 0; s < Kc; ++s) {
+    const int k = k0 + s;
+    const int kc = min(k, p.K - 1);
+    float a = ap[kc];
+    const float bw = wp[(long)kc * p.ldw];
+    if (k >= p.K) a = 0.f;
+    acc = fgb_mfma(a, bw, acc);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[w][(kk * 4 + r) * 16 + ci] = acc[r];
+  __syncthreads();
+  const int row = tid >> 4, j = nt * 16 + (tid & 15);
+  if (j < p.N) {
+    float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    if (p.bias) v += p.bias[j];
+    if (p.relu) v = fmaxf(v, 0.f);
+    p.out[(long)(mt * 16 + row) * p.ldo + j] = v;
+  }
+}
+
+// pre[l][b][0:32 | 32:64] = x_l[t' - d_l] (Wf[0] | Wg[0]) + bias_fg[l][b] for
+// the step t' = cursors[0] + ahead, group gi (rows past B: 0).  Wave w:
+// rows 16 (w & 1), filter (w < 2) or gate half, two 16-column tiles.
+__device__ __forceinline__ void fgb_pre_tile(const FgBatch& g, int l, int gi, int ahead) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int rb = w & 1, half = w >> 1;
+  const int ci = lane & 15, kk = lane >> 4;
+  int roff = 0;
+  for (int i = 0; i < l; ++i) roff += g.dil[i];
+  const int d = g.dil[l];
+  const int tpos = g.cursors[0] + ahead;
+  const float* xr = g.state + ((long)(roff + tpos % d) * g.Bp + gi * FGB_TILE + rb * 16 + ci) * 32;
+  const float* wt = g.layer0 + (long)l * g.layer_stride + half * 2048;   // Wf[0] / Wg[0]
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int k = 4 * s + kk;
+    const float a = xr[k];
+    a0 = fgb_mfma(a, wt[k * 32 + ci], a0);
+    a1 = fgb_mfma(a, wt[k * 32 + 16 + ci], a1);
+  }
+  const long lstride = g.bias_stride ? (long)g.B * 64 : 64;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = gi * FGB_TILE + rb * 16 + kk * 4 + r;
+    float* out = g.pre + ((long)l * g.Bp + b) * 64 + half * 32;
+    float v0 = 0.f, v1 = 0.f;
+    if (b < g.B) {
+      float c0 = 0.f, c1 = 0.f;
+      if (g.bias_fg) {
+        const float* bb = g.bias_fg + l * lstride + (long)b * g.bias_stride + half * 32;
+        c0 = bb[ci];
+        c1 = bb[16 + ci];
+      }
+      v0 = c0 + a0[r];
+      v1 = c1 + a1[r];
+    }
+    out[ci] = v0;
+    out[16 + ci] = v1;
+  }
+}
+
+__global__ __launch_bounds__(256) void fgb_pre_kernel(FgBatch g, int ahead) {
+  fgb_pre_tile(g, blockIdx.x / (g.Bp / FGB_TILE), blockIdx.x % (g.Bp / FGB_TILE), ahead);
+}
+
+__host__ __device__ __forceinline__ int fgb_ntiles(int n) { return (n + 15) / 16; }
+
+// h1 = relu(z_all . Ws + bsum), then L x Bp/32 more workgroups: the next
+// step's pre-activations
+__global__ __launch_bounds__(256) void fgb_skip_kernel(FgBatch g) {
+  __shared__ float red[4][256];
+  const int nt = fgb_ntiles(g.S), nskip = nt * (g.Bp / 16);
+  const int bid = blockIdx.x;
+  if (bid >= nskip) {                       // workgroup-uniform
+    const int r = bid - nskip, ng = g.Bp / FGB_TILE;
+    fgb_pre_tile(g, r / ng, r % ng, 1);
+    return;
+  }
+  FgbGemm p = {g.z_all, (long)g.L * 32, g.L * 32, g.skip_w, g.S, g.S, g.skip_bsum, 1, g.h1, g.S};
+  fgb_gemm_tile(p, bid % nt, bid / nt, red);
+}
+
+__global__ __launch_bounds__(256) void fgb_post1_kernel(FgBatch g) {
+  __shared__ float red[4][256];
+  const int nt = fgb_ntiles(g.S);
+  FgbGemm p = {g.h1, g.S, g.S, g.post1_w, g.S, g.S, g.post1_b, 1, g.h2, g.S};
+  fgb_gemm_tile(p, blockIdx.x % nt, blockIdx.x / nt, red);
+}
+
+__global__ __launch_bounds__(256) void fgb_logits_kernel(FgBatch g) {
+  __shared__ float red[4][256];
+  const int nt = fgb_ntiles(g.Q);
+  FgbGemm p = {g.h2, g.S, g.S, g.post2_w, g.Q, g.Q, g.post2_b, 0, g.logits, g.Q};
+  fgb_gemm_tile(p, blockIdx.x % nt, blockIdx.x / nt, red);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {   // (no other workgroup reads them)
+    g.cursors[0] += 1;
+    g.cursors[1] = 1;                           // a draw is pending
+  }
+}
+
+// ------------------------------------------------------------------- C ABI
+static int fgb_rows(int B) { return (B + FGB_TILE - 1) / FGB_TILE * FGB_TILE; }
+
+static int fgb_check_batch(int B) {
+  if (B <= 0) return WN_ERR_BAD_SHAPE;
+  if (B > FGB_MAXB) return WN_ERR_UNSUPPORTED;
+  return WN_OK;
+}
+
+extern "C" {
+
+int wn_fastgen_batch_rows(int B) {
+  const int rc = fgb_check_batch(B);
+  return rc != WN_OK ? rc : fgb_rows(B);
+}
+
+long wn_fastgen_batch_state_floats(const int32_t* dilations_host, int L, int B) {
+  if (!dilations_host) return WN_ERR_NULL;
+  if (L <= 0) return WN_ERR_BAD_SHAPE;
+  if (L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  long n = 0;
+  for (int l = 0; l < L; ++l) {
+    if (dilations_host[l] <= 0) return WN_ERR_BAD_SHAPE;
+    n += dilations_host[l];
+  }
+  return n * fgb_rows(B) * 32;
+}
+
+int wn_fastgen_batch_init(float* state, long state_floats, int32_t* cursors, int32_t* prev,
+                          int B, void* stream) {
+  if (!state || !cursors || !prev) return WN_ERR_NULL;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  if (state_floats <= 0) return WN_ERR_BAD_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(state, 0, state_floats * sizeof(float), s) != hipSuccess ||
+      hipMemsetD32Async((hipDeviceptr_t)cursors, 0, 4, s) != hipSuccess ||
+      hipMemsetD32Async((hipDeviceptr_t)prev, -1, fgb_rows(B), s) != hipSuccess)
+    return WN_ERR_LAUNCH;
+  return WN_OK;
+}
+
+int wn_fastgen_batch_pre(const float* layer0, long layer_stride, const float* gc_bias_fg,
+                         int bias_stream_stride, const int32_t* dilations_dev, int L, int B,
+                         const float* state, const int32_t* cursors, float* pre,
+                         void* stream) {
+  if (!layer0 || !dilations_dev || !state || !cursors || !pre) return WN_ERR_NULL;
+  if (L <= 0 || (bias_stream_stride != 0 && bias_stream_stride != 64)) return WN_ERR_BAD_SHAPE;
+  if (L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  FgBatch g = {};
+  g.layer0 = layer0; g.layer_stride = layer_stride; g.bias_fg = gc_bias_fg;
+  g.bias_stride = bias_stream_stride; g.dil = dilations_dev; g.L = L; g.B = B;
+  g.Bp = fgb_rows(B); g.state = const_cast<float*>(state);
+  g.cursors = const_cast<int32_t*>(cursors); g.pre = pre;
+  hipLaunchKernelGGL(fgb_pre_kernel, dim3(L * (g.Bp / FGB_TILE)), dim3(256), 0,
+                     (hipStream_t)stream, g, 0);
+  return wn_check_launch();
+}
+
+// Enqueue the stages [first, last) of one step: 0 draw, 1 chain, 2 skip sum +
+// next pre-activations, 3 post1, 4 logits (wn_fastgen_batch_step: all five;
+// single stages let a caller time each launch between its own events).
+int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
+                            const float* layer0, long layer_stride, const float* skip_w,
+                            const float* skip_bsum, const float* post1_w,
+                            const float* post1_b, const float* post2_w, const float* post2_b,
+                            const float* gc_bias_fg, int bias_stream_stride,
+                            const int32_t* dilations_dev, int L, int S, int Q, int B,
+                            float* state, int32_t* cursors, int32_t* prev,
+                            int32_t* samples_io, const int32_t* ctl, const uint64_t* seeds,
+                            float* proba_out, int use_biases, float* pre, float* z_all,
+                            float* h1, float* h2, float* logits, void* stream) {
+  if (!params_causal || !layer0 || !skip_w || !post1_w || !post2_w || !dilations_dev ||
+      !state || !cursors || !prev || !samples_io || !ctl || !seeds || !pre || !z_all ||
+      !h1 || !h2 || !logits)
+    return WN_ERR_NULL;
+  if (L <= 0 || S <= 0 || Q <= 0 || (bias_stream_stride != 0 && bias_stream_stride != 64) ||
+      first < 0 || last > 5 || first >= last)
+    return WN_ERR_BAD_SHAPE;
+  if (S > FGB_MAXS || Q > FGB_MAXQ || L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  FgBatch g;
+  g.causal = params_causal; g.layer0 = layer0; g.layer_stride = layer_stride;
+  g.skip_w = skip_w; g.skip_bsum = skip_bsum; g.post1_w = post1_w; g.post1_b = post1_b;
+  g.post2_w = post2_w; g.post2_b = post2_b; g.bias_fg = gc_bias_fg;
+  g.bias_stride = bias_stream_stride; g.dil = dilations_dev;
+  g.L = L; g.S = S; g.Q = Q; g.B = B; g.Bp = fgb_rows(B);
+  g.state = state; g.cursors = cursors; g.prev = prev; g.samples = samples_io;
+  g.ctl = ctl; g.seeds = seeds; g.proba_out = proba_out; g.use_dense_bias = use_biases;
+  g.pre = pre; g.z_all = z_all; g.h1 = h1; g.h2 = h2; g.logits = logits;
+  hipStream_t s = (hipStream_t)stream;
+  const int mt = g.Bp / 16, ng = g.Bp / FGB_TILE;
+  for (int stage = first; stage < last; ++stage) {
+    switch (stage) {
+      case 0:
+        hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
+        break;
+      case 1:
+        hipLaunchKernelGGL(fgb_chain_kernel, dim3(ng), dim3(256), 0, s, g);
+        break;
+      case 2:
+        hipLaunchKernelGGL(fgb_skip_kernel, dim3(fgb_ntiles(S) * mt + L * ng), dim3(256), 0, s,
+                           g);
+        break;
+      case 3:
+        hipLaunchKernelGGL(fgb_post1_kernel, dim3(fgb_ntiles(S) * mt), dim3(256), 0, s, g);
+        break;
+      default:
+        hipLaunchKernelGGL(fgb_logits_kernel, dim3(fgb_ntiles(Q) * mt), dim3(256), 0, s, g);
+        break;
+    }
+  }
+  return wn_check_launch();
+}
+
+int wn_fastgen_batch_step(const float* params_causal, const float* layer0, long layer_stride,
+                          const float* skip_w, const float* skip_bsum, const float* post1_w,
+                          const float* post1_b, const float* post2_w, const float* post2_b,
+                          const float* gc_bias_fg, int bias_stream_stride,
+                          const int32_t* dilations_dev, int L, int S, int Q, int B,
+                          float* state, int32_t* cursors, int32_t* prev, int32_t* samples_io,
+                          const int32_t* ctl, const uint64_t* seeds, float* proba_out,
+                          int use_biases, float* pre, float* z_all, float* h1, float* h2,
+                          float* logits, void* stream) {
+  return wn_fastgen_batch_stages(0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+                                 post1_w, post1_b, post2_w, post2_b, gc_bias_fg,
+                                 bias_stream_stride, dilations_dev, L, S, Q, B, state, cursors,
+                                 prev, samples_io, ctl, seeds, proba_out, use_biases, pre, z_all,
+                                 h1, h2, logits, stream);
+}
+
+int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
+                            const int32_t* ctl, const uint64_t* seeds, float* proba_out,
+                            const float* logits, void* stream) {
+  if (!cursors || !samples_io || !ctl || !seeds || !logits) return WN_ERR_NULL;
+  if (Q <= 0) return WN_ERR_BAD_SHAPE;
+  if (Q > FGB_MAXQ) return WN_ERR_UNSUPPORTED;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  FgBatch g = {};
+  g.Q = Q; g.B = B; g.Bp = fgb_rows(B); g.cursors = cursors; g.samples = samples_io;
+  g.ctl = ctl; g.seeds = seeds; g.proba_out = proba_out; g.logits = const_cast<float*>(logits);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
+  if (wn_check_launch() != WN_OK) return WN_ERR_LAUNCH;
+  if (hipMemsetD32Async((hipDeviceptr_t)(cursors + 1), 0, 1, s) != hipSuccess)
+    return WN_ERR_LAUNCH;
+  return WN_OK;
+}
+
+}  // extern "C"

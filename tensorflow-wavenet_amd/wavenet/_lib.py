@@ -136,6 +136,20 @@ SIGNATURES = {
     'wn_fastgen_pre': (c_int, [P, c_long, P, P, c_int, P, P, P, P]),
     'wn_fastgen_finish': (c_int, [c_int, P, P, P, P, P, P]),
     'wn_fastgen_pack': (c_int, [P, c_long, P, c_int, P]),
+    'wn_fastgen_batch_rows': (c_int, [c_int]),
+    'wn_fastgen_batch_state_floats': (c_long, [P, c_int, c_int]),
+    'wn_fastgen_batch_init': (c_int, [P, c_long, P, P, c_int, P]),
+    'wn_fastgen_batch_pre': (c_int, [P, c_long, P, c_int, P, c_int, c_int, P,
+                                     P, P, P]),
+    'wn_fastgen_batch_step': (c_int, [P, P, c_long, P, P, P, P, P, P, P,
+                                      c_int, P, c_int, c_int, c_int, c_int, P,
+                                      P, P, P, P, P, P, c_int, P, P, P, P, P,
+                                      P]),
+    'wn_fastgen_batch_stages': (c_int, [c_int, c_int, P, P, c_long, P, P, P,
+                                        P, P, P, P, c_int, P, c_int, c_int,
+                                        c_int, c_int, P, P, P, P, P, P, P,
+                                        c_int, P, P, P, P, P, P]),
+    'wn_fastgen_batch_finish': (c_int, [c_int, c_int, P, P, P, P, P, P, P]),
 }
 
 

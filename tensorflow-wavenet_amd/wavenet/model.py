@@ -406,6 +406,7 @@ class WaveNetModel(object):
         self._dil_dev = torch.tensor(self.dilations, dtype=torch.int32,
                                      device=self.device)
         self._gen = None
+        self._bgen = None
         self.init_ops = []
         self.push_ops = []
         self.variables = self._create_variables(seed)
@@ -599,6 +600,7 @@ class WaveNetModel(object):
             for n, v in self.named_variables():
                 v.copy_(torch.as_tensor(sd[n]).to(self.device))
         self._gen = None
+        self._bgen = None
 
     def load_nested(self, tree):
         """Load a nested dict shaped like `variables` (numpy / tensors)."""
@@ -615,6 +617,7 @@ class WaveNetModel(object):
         with torch.no_grad():
             rec(self.variables, tree)
         self._gen = None
+        self._bgen = None
 
     # ------------------------------------------------------------------ helpers
     def _overlap_tn_on(self, ws):
@@ -1814,3 +1817,357 @@ class WaveNetModel(object):
         self._gen_run(io, 1, n, temperature, seed, None, 1, global_condition,
                       multi_cu=self.fastgen_multi_cu)
         return io[1:]
+
+    # ------------------------------------------------ batched fast generation
+    FASTGEN_BATCH_MAX = 256        # wn_fastgen_batch_* (FGB_MAXB)
+
+    def _batch_gen_check(self):
+        """The shapes wn_fastgen_batch_step covers (those of the single-stream
+        step kernels), checked before anything touches a device."""
+        if self.CB > 1:
+            raise NotImplementedError(
+                'generate_batch supports at most 32 residual / dilation '
+                'channels (this model has %d); use generate() per stream'
+                % max(self.R, self.D))
+        if self.filter_width > 2 or self.scalar_input:
+            raise NotImplementedError(
+                'generate_batch needs filter_width 2 and one-hot input '
+                '(model.py:597-603), as every fast generation path does; use '
+                'predict_proba (generate.py --fast_generation false)')
+        if self.S > 512 or self.Q > 512 or self.L > 64:
+            raise NotImplementedError(
+                'generate_batch supports at most 512 skip / quantization '
+                'channels and 64 layers; use generate() per stream')
+
+    def _batch_seeds(self, seeds):
+        """One 64-bit draw seed per stream -> int64 array (bit pattern)."""
+        s = [int(v) & (2**64 - 1) for v in seeds]
+        if not 1 <= len(s) <= self.FASTGEN_BATCH_MAX:
+            raise ValueError('generate_batch takes 1 to %d streams (one seed '
+                             'each), got %d' % (self.FASTGEN_BATCH_MAX, len(s)))
+        return np.asarray(s, dtype=np.uint64).view(np.int64)
+
+    def _batch_codes(self, seed_samples, B):
+        """seed_samples -> int32 [B, n]: None (Q // 2 for every stream), one
+        sequence shared by all streams, or one row per stream."""
+        if seed_samples is None:
+            return np.full((B, 1), self.Q // 2, np.int32)
+        if isinstance(seed_samples, torch.Tensor):
+            seed_samples = seed_samples.cpu().numpy()
+        try:
+            a = np.asarray(seed_samples)
+        except ValueError:             # ragged rows
+            a = None
+        if a is None or a.dtype == object or a.ndim not in (1, 2):
+            raise ValueError('seed_samples must be None, one sequence shared '
+                             'by all streams, or [B, n]: the same number of '
+                             'seed codes for every stream')
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (B, a.shape[0]))
+        if a.shape[0] != B:
+            raise ValueError('seed_samples has %d rows for %d streams'
+                             % (a.shape[0], B))
+        if a.shape[1] < 1:
+            raise ValueError('seed_samples needs at least one code per stream')
+        return np.array(a, dtype=np.int32, order='C')   # (a writable copy)
+
+    def _batch_gc(self, global_condition, B):
+        """None, one id shared by all streams, or B ids -> int32 [B] / None."""
+        if global_condition is None:
+            return None
+        g = global_condition
+        if isinstance(g, torch.Tensor):
+            g = g.cpu().numpy()
+        g = np.asarray(g).reshape(-1)
+        if g.size == 1:
+            g = np.repeat(g, B)
+        if g.size != B:
+            raise ValueError('global_condition has %d ids for %d streams'
+                             % (g.size, B))
+        return g.astype(np.int32)
+
+    @staticmethod
+    def _check_temperature(temperature):
+        if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
+            raise ValueError('temperature must be a finite number > 0, got %r'
+                             % (temperature,))
+
+    def _batch_generator(self, B):
+        """Device state of the batched generator for B streams, separate from
+        the single-stream generator's (`_gen`): ring rows [sum d][Bp][32]."""
+        g = self._bgen
+        if g is not None and g['B'] == B:
+            return g
+        self._bgen = None
+        lib = _lib.load()
+        Bp = lib.wn_fastgen_batch_rows(B)
+        _lib.check(min(Bp, 0), 'wn_fastgen_batch_rows')
+        dil = np.asarray(self.dilations, dtype=np.int32)
+        nfl = lib.wn_fastgen_batch_state_floats(dil.ctypes.data, self.L, B)
+        _lib.check(int(min(nfl, 0)), 'wn_fastgen_batch_state_floats')
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        g = dict(
+            B=B, Bp=Bp,
+            state=torch.zeros(nfl, **f32),
+            # [0] steps pushed, [1] draw pending
+            cursors=torch.zeros(4, **i32),
+            prev=torch.full((Bp,), -1, **i32),
+            dil=torch.from_numpy(dil).to(self.device),
+            bias=torch.zeros(self.L * B * 2 * CH, **f32),
+            bsum=torch.zeros(self.S, **f32),
+            seeds=torch.zeros(B, dtype=torch.int64, device=self.device),
+            ctl=torch.zeros(8, **i32),
+            pre=torch.zeros(self.L * Bp * 2 * CH, **f32),
+            z_all=torch.zeros(Bp * self.L * CH, **f32),
+            h1=torch.zeros(Bp * self.S, **f32),
+            h2=torch.zeros(Bp * self.S, **f32),
+            logits=torch.zeros(Bp * self.Q, **f32),
+            graphs={}, warm=False, steps=0)
+        self._bgen = g
+        return g
+
+    def _batch_reset(self, g):
+        _lib.call('wn_fastgen_batch_init', _lib.ptr(g['state']),
+                  g['state'].numel(), _lib.ptr(g['cursors']),
+                  _lib.ptr(g['prev']), g['B'], _lib.stream())
+        g['steps'] = 0
+
+    def _batch_buf(self, g, name, n, dtype):
+        """Persistent buffer of the batched generator (grown geometrically;
+        growing drops the captured graphs, which hold its address)."""
+        buf = g.get(name)
+        if buf is None or buf.numel() < n:
+            cap = max(int(n), 2 * (buf.numel() if buf is not None else 0), 4096)
+            g[name] = buf = torch.zeros(cap, dtype=dtype, device=self.device)
+            g['graphs'].clear()
+        return buf
+
+    def _batch_prepare(self, g, io, n_given, n_steps, temperature, seeds,
+                       proba, proba_every, gc):
+        """Everything a sequence of n_steps batched steps needs before the
+        first: GC / filter-gate bias, control block, io / probability
+        buffers, the first step's past-tap pre-activations.  Returns the
+        argument tuple of wn_fastgen_batch_step (without the stream) and the
+        buffers _batch_complete reads back."""
+        B, Q = g['B'], self.Q
+        P = self.params
+        st = _lib.stream()
+        ids = self._gc_ids(gc, B)
+        bias, bstride = self._bias_fg(g['bias'], ids, B)
+        bsum = None
+        if self.use_biases:
+            _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), self.L,
+                      self.S, _lib.ptr(g['bsum']), st)
+            bsum = g['bsum']
+        ub = self.use_biases
+        g['seeds'].copy_(torch.from_numpy(seeds))
+        ld = int(n_steps) + 1
+        pe = max(1, int(proba_every))
+        rows = (int(n_steps) + pe - 1) // pe if proba is not None else 0
+        iob = self._batch_buf(g, 'io_buf', B * ld, torch.int32)
+        iob[:B * ld].view(B, ld).copy_(io)
+        pb = None
+        if proba is not None:
+            pb = self._batch_buf(g, 'proba_buf', B * rows * Q, torch.float32)
+        ctl = np.zeros(8, np.uint32)
+        ctl[0], ctl[1], ctl[2] = g['steps'], int(n_given), pe
+        ctl[3] = np.float32(temperature).view(np.uint32)
+        ctl[4], ctl[5] = ld, rows
+        g['ctl'].copy_(torch.from_numpy(ctl.view(np.int32)))
+        layer0 = _lib.ptr(self._layer_block(P, 0))
+        bptr = None if bias is None else _lib.ptr(bias)
+        # past-tap pre-activations of the first step (every step then leaves
+        # the next step's behind)
+        _lib.call('wn_fastgen_batch_pre', layer0, self.layer_stride, bptr,
+                  bstride, _lib.ptr(g['dil']), self.L, B, _lib.ptr(g['state']),
+                  _lib.ptr(g['cursors']), _lib.ptr(g['pre']), st)
+        args = (_lib.ptr(self._seg(P, 'causal')), layer0, self.layer_stride,
+                _lib.ptr(self._seg(P, 'skip_w')), _lib.ptr(bsum),
+                _lib.ptr(self._seg(P, 'post1_w')),
+                _lib.ptr(self._seg(P, 'post1_b')) if ub else None,
+                _lib.ptr(self._seg(P, 'post2_w')),
+                _lib.ptr(self._seg(P, 'post2_b')) if ub else None,
+                bptr, bstride, _lib.ptr(g['dil']), self.L, self.S, Q, B,
+                _lib.ptr(g['state']), _lib.ptr(g['cursors']),
+                _lib.ptr(g['prev']), _lib.ptr(iob), _lib.ptr(g['ctl']),
+                _lib.ptr(g['seeds']), _lib.ptr(pb), 1 if ub else 0,
+                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
+                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
+        return dict(args=args, iob=iob, pb=pb, ld=ld, rows=rows)
+
+    def _batch_complete(self, g, prep, io, proba, n_steps):
+        """The last step's draw (every other one runs at the next step's
+        start), then the codes / probabilities back into io / proba."""
+        B, Q = g['B'], self.Q
+        iob, pb, ld, rows = prep['iob'], prep['pb'], prep['ld'], prep['rows']
+        _lib.call('wn_fastgen_batch_finish', Q, B, _lib.ptr(g['cursors']),
+                  _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(g['seeds']),
+                  _lib.ptr(pb), _lib.ptr(g['logits']), _lib.stream())
+        g['steps'] += int(n_steps)
+        io.copy_(iob[:B * ld].view(B, ld))
+        if proba is not None:
+            proba.copy_(pb[:B * rows * Q].view(B, rows, Q))
+
+    def _batch_run(self, g, io, n_given, n_steps, temperature, seeds, proba,
+                   proba_every, gc):
+        """n_steps lock-step steps of all B streams: io int32 [B, n_steps + 1]
+        (the first n_given codes of every row are given, the rest drawn);
+        proba float32 [B, rows, Q] or None.  Five kernels per step, captured
+        into a hipGraph once and replayed (per-call values live in `ctl`)."""
+        prep = self._batch_prepare(g, io, n_given, n_steps, temperature, seeds,
+                                   proba, proba_every, gc)
+        args = prep['args']
+
+        def one():
+            _lib.call('wn_fastgen_batch_step', *args, _lib.stream())
+
+        def graph_of(nsteps):
+            key = (args, nsteps)
+            gr = g['graphs'].get(key)
+            if gr is None:
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    for _ in range(nsteps):
+                        one()
+                if len(g['graphs']) > 8:
+                    g['graphs'].clear()
+                g['graphs'][key] = gr
+            return gr
+        done = 0
+        if not g['warm']:
+            one()                      # module load etc. outside any capture
+            done, g['warm'] = 1, True
+        for per in (int(self.fastgen_graph_steps),
+                    max(1, int(self.fastgen_graph_steps) // 10)):
+            if per > 1 and n_steps - done >= per:
+                gr = graph_of(per)
+                while n_steps - done >= per:
+                    gr.replay()
+                    done += per
+        for _ in range(n_steps - done):
+            one()
+        self._batch_complete(g, prep, io, proba, n_steps)
+
+    def _batch_prime(self, g, codes, gc):
+        """prime_generator for all B streams: the queues after codes [B, n0]
+        (host int32) were pushed one by one.  ONE batch-1 forward pass per
+        distinct (seed, GC id) -- a seed shared by all streams is one pass --
+        whose ring rows go to every stream that has it.  A stream's queues are
+        then bitwise those it gets alone, or from prime_generator, whatever B,
+        and the forward's workspace is one seed long whatever B."""
+        B, Bp = g['B'], g['Bp']
+        self._batch_reset(g)
+        n0 = int(codes.shape[1])
+        groups = {}
+        for b in range(B):
+            key = (codes[b].tobytes(), None if gc is None else int(gc[b]))
+            groups.setdefault(key, []).append(b)
+        ws = self._workspace(1, n0, False)
+        X = ws.X.reshape(-1, CH)[:self.L * n0]
+        # layer l's queue holds x_l[t] for the last d_l steps: activation
+        # plane l, row t -> ring entry roff_l + t % d_l (row b of the entry)
+        src, ent, roff = [], [], 0
+        for l, d in enumerate(self.dilations):
+            t = np.arange(max(0, n0 - d), n0, dtype=np.int64)
+            src.append(l * n0 + t)
+            ent.append(roff + t % d)
+            roff += d
+        src = torch.from_numpy(np.concatenate(src)).to(self.device)
+        ent = np.concatenate(ent)
+        state = g['state'].view(-1, CH)
+        for rows in groups.values():
+            b0 = rows[0]
+            ws.q.copy_(torch.from_numpy(np.ascontiguousarray(codes[b0])))
+            ids = self._gc_ids(None if gc is None else gc[b0:b0 + 1], 1)
+            self._forward(ws, ids, save_ts=0)
+            # (+ the forward launch's poison word: 0, or NaN after an
+            # expired wait)
+            vals = X.index_select(0, src) + ws.loss_parts[0]
+            dst = (ent[None, :] * Bp + np.asarray(rows, np.int64)[:, None])
+            state.index_copy_(0, torch.from_numpy(dst.reshape(-1)).to(
+                self.device), vals.repeat(len(rows), 1))
+        g['cursors'][0] = n0
+        g['prev'][:B].copy_(torch.from_numpy(np.ascontiguousarray(codes[:, -1])))
+        g['steps'] = n0
+
+    def generate_batch(self, num_samples, seeds, seed_samples=None,
+                       temperature=1.0, global_condition=None,
+                       return_proba_every=0):
+        """`generate` for B = len(seeds) independent streams stepped in lock
+        step (1 <= B <= 256).  Stream b draws with seeds[b] under generate()'s
+        counter rule, so it is the same random process as
+        generate(seed=seeds[b]), and its results do not depend on the other
+        streams.  seed_samples: None (Q // 2 for every stream), one sequence
+        shared by all streams, or [B, n]; global_condition: None, one id, or
+        B ids.  Returns int32 [B, n + num_samples] (and float32
+        [B, ceil(steps / k), Q] probabilities with return_proba_every = k)."""
+        self._batch_gen_check()
+        sd = self._batch_seeds(seeds)
+        B = len(sd)
+        codes = self._batch_codes(seed_samples, B)
+        gc = self._batch_gc(global_condition, B)
+        self._check_temperature(temperature)
+        n = int(num_samples)
+        if n < 0:
+            raise ValueError('num_samples must be >= 0, got %d' % n)
+        self._check_supported()
+        n_given = codes.shape[1]
+        n_steps = n_given - 1 + n
+        out = torch.zeros((B, n_given + n), dtype=torch.int32,
+                          device=self.device)
+        out[:, :n_given] = torch.from_numpy(codes).to(self.device)
+        pe = int(return_proba_every)
+        proba = None
+        if pe > 0:
+            proba = torch.empty((B, (n_steps + pe - 1) // pe, self.Q),
+                                dtype=torch.float32, device=self.device)
+        g = self._batch_generator(B)
+        self._batch_reset(g)
+        if pe == 0 and n_given - 1 >= self.fastgen_prime_forward_min and n > 0:
+            self._batch_prime(g, codes[:, :n_given - 1], gc)
+            tail = out[:, n_given - 1:].contiguous()   # [last seed | drawn ...]
+            self._batch_run(g, tail, 1, n, temperature, sd, None, 1, gc)
+            out[:, n_given - 1:] = tail
+        elif n_steps > 0:
+            self._batch_run(g, out, n_given, n_steps, temperature, sd, proba,
+                            pe, gc)
+        return (out, proba) if pe > 0 else out
+
+    def continue_generation_batch(self, num_samples, last_samples, seeds,
+                                  temperature=1.0, global_condition=None,
+                                  return_proba_every=0):
+        """Draw `num_samples` more samples for every stream of the last
+        generate_batch call (the queues stay on the device; last_samples[b]
+        is stream b's last code so far, not yet pushed).  Returns int32
+        [B, num_samples] (and the probabilities, as generate_batch)."""
+        self._batch_gen_check()
+        sd = self._batch_seeds(seeds)
+        B = len(sd)
+        last = last_samples
+        if isinstance(last, torch.Tensor):
+            last = last.cpu().numpy()
+        last = np.asarray(last, dtype=np.int32).reshape(-1)
+        if last.size != B:
+            raise ValueError('last_samples has %d codes for %d streams'
+                             % (last.size, B))
+        gc = self._batch_gc(global_condition, B)
+        self._check_temperature(temperature)
+        n = int(num_samples)
+        if n < 0:
+            raise ValueError('num_samples must be >= 0, got %d' % n)
+        self._check_supported()
+        g = self._bgen
+        if g is None or g['B'] != B:
+            raise RuntimeError('no batched generation of %d streams to '
+                               'continue: call generate_batch first' % B)
+        io = torch.zeros((B, n + 1), dtype=torch.int32, device=self.device)
+        io[:, 0] = torch.from_numpy(last).to(self.device)
+        pe = int(return_proba_every)
+        proba = None
+        if pe > 0:
+            proba = torch.empty((B, (n + pe - 1) // pe, self.Q),
+                                dtype=torch.float32, device=self.device)
+        if n > 0:
+            self._batch_run(g, io, 1, n, temperature, sd, proba, pe, gc)
+        return (io[:, 1:], proba) if pe > 0 else io[:, 1:]
