@@ -306,4 +306,108 @@ __device__ __forceinline__ void gate_grad(const f32x16& dz, const f32x16& zz,
   }
 }
 
+// ---------------------------------------------------------------------------
+// The sampling draw of fast generation (generate.py:229-240), one copy for
+// every draw site (tests/draw_ref.py restates it in float64 numpy):
+//   p    = float32(softmax_f64(logits))            the probabilities returned
+//   w_q  = exp(log(p_q) / tau - max)               w = p at tau == 1; 0 at p == 0
+//   u    = uniform(seed, counter) * sum(w)         counter-based, no state
+//   code = the inverse CDF of w at u
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// the draw's uniform in [0, 1): the top 53 bits of splitmix64(seed ^ splitmix64(counter))
+// (also in halves, for a caller that hashes before its logits are ready)
+__device__ __forceinline__ uint64_t draw_bits(uint64_t seed, uint64_t counter) {
+  return splitmix64(seed ^ splitmix64(counter));
+}
+__device__ __forceinline__ double draw_unit(uint64_t bits) {
+  return (double)(bits >> 11) * (1.0 / 9007199254740992.0);
+}
+__device__ __forceinline__ double draw_uniform(uint64_t seed, uint64_t counter) {
+  return draw_unit(draw_bits(seed, counter));
+}
+
+// the weight exponent log(p) / tau; p == 0 (float32 underflow) gets -inf, so
+// weight exactly 0 at any tau, as np.log(0) gives it in the reference
+__device__ __forceinline__ double draw_log_weight(double p, double tau) {
+  return p > 0.0 ? log(p) / tau : -INFINITY;
+}
+
+// float64 softmax (model.py:620-621) by one wave of the Q logits in pd.
+// Leaves the float32-rounded probabilities, the ones generate.py sees, in pd
+// as doubles and stores them to po unless it is null.  Each exp is evaluated
+// once and kept in pd.
+__device__ __forceinline__ void wave_softmax_f64(double* pd, int Q, int lane, float* po) {
+  double m = -1e300;
+  for (int q = lane; q < Q; q += 64) m = fmax(m, pd[q]);
+  for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+  double se = 0.0;
+  for (int q = lane; q < Q; q += 64) {
+    const double e = exp(pd[q] - m);
+    pd[q] = e;
+    se += e;
+  }
+  for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
+  for (int q = lane; q < Q; q += 64) {
+    const float p32 = (float)(pd[q] / se);
+    if (po) po[q] = p32;
+    pd[q] = (double)p32;
+  }
+}
+
+// The draw by one wave from the probabilities wave_softmax_f64 left in pd
+// (overwritten with the weights): temperature, then the inverse CDF over
+// per-lane contiguous segments (segment sums -> prefix sum -> pick) with the
+// uniform of (seed, counter).  Returns the code in every lane.
+__device__ __forceinline__ int wave_draw_f64(double* pd, int Q, int lane, float temperature,
+                                             uint64_t seed, uint64_t counter) {
+  if (temperature != 1.0f) {
+    const double tau = (double)temperature;
+    double mx = -1e300;
+    for (int q = lane; q < Q; q += 64) {
+      const double lp = draw_log_weight(pd[q], tau);
+      pd[q] = lp;
+      mx = fmax(mx, lp);
+    }
+    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
+  }
+  __builtin_amdgcn_wave_barrier();
+  const int per = (Q + 63) / 64;
+  const int q0 = lane * per, q1 = min(Q, q0 + per);
+  double seg = 0.0;
+  for (int q = q0; q < q1; ++q) seg += pd[q];
+  double incl = seg;
+  for (int o = 1; o < 64; o <<= 1) {
+    const double v = __shfl_up(incl, o);
+    if (lane >= o) incl += v;
+  }
+  const double total = __shfl(incl, 63);
+  const double u = draw_uniform(seed, counter) * total;
+  // (the neighbour's inclusive sum, not incl - seg: the lanes' intervals
+  // then tile [0, total) exactly -- no gap a draw could fall into)
+  const double up = __shfl_up(incl, 1);
+  const double excl = lane == 0 ? 0.0 : up;
+  int pick = -1;
+  if (u >= excl && u < incl) {
+    double c = excl;
+    pick = q1 - 1;
+    for (int q = q0; q < q1; ++q) {
+      c += pd[q];
+      if (u < c) { pick = q; break; }
+      if (pd[q] > 0.0) pick = q;   // (u past the rounded walk: the last code of weight > 0)
+    }
+  }
+  // exactly one lane holds the pick (u < total); fall back to Q - 1
+  int best = pick;
+  for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
+  return best < 0 ? Q - 1 : best;
+}
+
 #endif  // __HIPCC__

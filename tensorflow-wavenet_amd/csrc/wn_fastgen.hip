@@ -26,13 +26,6 @@
 #define FG_MAXS 512
 #define FG_MAXQ 512
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // v_readlane_b32 on a float (the builtin is typed int: bit-cast, never convert)
 __device__ __forceinline__ float readlane_f(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -294,79 +287,15 @@ __global__ __launch_bounds__(FG_THREADS, 1) void fastgen_kernel(FastGen g) {
       }
       __syncthreads();
     }
-    // softmax in float64 (model.py:620-621), optional temperature
-    // (generate.py:229-233), draw (generate.py:239-240)
+    // softmax in float64, optional temperature, draw (wn_common.h)
     if (wave == 0) {
-      double m = -1e300;
-      for (int q = lane; q < Q; q += 64) m = fmax(m, pd[q]);
-      for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-      double se = 0.0;
-      for (int q = lane; q < Q; q += 64) {
-        const double e = exp(pd[q] - m);    // evaluated once, kept in LDS
-        pd[q] = e;
-        se += e;
-      }
-      for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
       const bool want_p = g.proba_out && (step % g.proba_every == 0);
-      float* po = want_p ? g.proba_out + (long)(step / g.proba_every) * Q : nullptr;
-      for (int q = lane; q < Q; q += 64) {
-        const float p32 = (float)(pd[q] / se);
-        if (po) po[q] = p32;
-        pd[q] = (double)p32;  // the float32 probabilities generate.py sees
-      }
+      wave_softmax_f64(pd, Q, lane, want_p ? g.proba_out + (long)(step / g.proba_every) * Q : nullptr);
     }
     __syncthreads();
     if (step + 1 >= g.n_given) {
       if (wave == 0) {
-        // temperature: exp(log(p)/tau - logsumexp) in float64, then inverse
-        // CDF with a counter-based uniform (np.random.choice equivalent)
-        // (sampling weights proportional to exp(log(p)/tau); at tau == 1
-        // that is p itself, no transcendental needed; a probability of 0 --
-        // float32 underflow -- has weight exactly 0 at any tau, as
-        // np.log(0) = -inf gives it in the reference)
-        const double tau = (double)g.temperature;
-        if (g.temperature != 1.0f) {
-          double mx = -1e300;
-          for (int q = lane; q < Q; q += 64) {
-            const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
-            pd[q] = lp;
-            mx = fmax(mx, lp);
-          }
-          for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-          for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
-        }
-        __builtin_amdgcn_wave_barrier();
-        // per-lane contiguous segment [q0, q1): segment sums -> prefix -> pick
-        const int per = (Q + 63) / 64;
-        const int q0 = lane * per, q1 = min(Q, q0 + per);
-        double seg = 0.0;
-        for (int q = q0; q < q1; ++q) seg += pd[q];
-        double incl = seg;
-        for (int o = 1; o < 64; o <<= 1) {
-          const double v = __shfl_up(incl, o);
-          if (lane >= o) incl += v;
-        }
-        const double total = __shfl(incl, 63);
-        const uint64_t r = splitmix64(g.seed ^ splitmix64((uint64_t)tpos));
-        const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
-        // (the neighbour's inclusive sum, not incl - seg: the lanes' intervals
-        // then tile [0, total) exactly -- no gap a draw could fall into)
-        const double up = __shfl_up(incl, 1);
-        const double excl = lane == 0 ? 0.0 : up;
-        int pick = -1;
-        if (u >= excl && u < incl) {
-          double c = excl;
-          pick = q1 - 1;
-          for (int q = q0; q < q1; ++q) {
-            c += pd[q];
-            if (u < c) { pick = q; break; }
-            if (pd[q] > 0.0) pick = q;   // (u past the rounded walk: the last code of weight > 0)
-          }
-        }
-        // exactly one lane holds the pick (u < total); fall back to Q-1
-        int best = pick;
-        for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
-        if (best < 0) best = Q - 1;
+        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.seed, (uint64_t)tpos);
         if (lane == 0) {
           g.samples[step + 1] = best;
           s_code = best;
@@ -507,8 +436,7 @@ __global__ __launch_bounds__(256) void fg_pre_kernel(FgStep g, int ahead) {
   fg_pre_layer(g, blockIdx.x, ahead, lds);
 }
 
-__device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lane,
-                                            int steps_done, const float* lg = nullptr);
+__device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lane, int steps_done);
 
 #ifdef FG_STAMPS   // diagnostic build: per-layer phase stamps of the chain wave
 __device__ unsigned long long fg_dbg[8 + FG_MAXL * 8];
@@ -798,84 +726,35 @@ __global__ __launch_bounds__(256) void fg_logits_kernel(FgStep g) {
 // sample; the release / acquire fences cost what the saved boundary returns.
 // It runs at the START of the next step's chain kernel instead, next to that
 // kernel's weight / table prologue.)
-__device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lane,
-                                            int steps_done, const float* lg) {
+// What the draw reads from ctl[]: constant over a launch, read once.
+struct FgDrawCtl {
+  int base, n_given, proba_every;
+  float temperature;
+  uint64_t seed;
+};
+__device__ __forceinline__ FgDrawCtl fg_draw_ctl(const FgStep& g) {
+  FgDrawCtl c;
+  c.base = g.ctl[FGCTL_BASE];
+  c.n_given = g.ctl[FGCTL_NGIVEN];
+  c.proba_every = g.ctl[FGCTL_PEVERY] > 0 ? g.ctl[FGCTL_PEVERY] : 1;
+  c.temperature = __int_as_float(g.ctl[FGCTL_TEMP]);
+  c.seed = (uint64_t)(uint32_t)g.ctl[FGCTL_SEED] | ((uint64_t)(uint32_t)g.ctl[FGCTL_SEED + 1] << 32);
+  return c;
+}
+
+__device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lane, int steps_done) {
   const int Q = g.Q;
-  if (!lg) lg = g.logits;      // (the persistent kernel hands in its own coherent copy)
-  const int local = steps_done - g.ctl[FGCTL_BASE];
+  const FgDrawCtl dc = fg_draw_ctl(g);
+  const int local = steps_done - dc.base;
   const int code = g.samples[local];
-  const int n_given = g.ctl[FGCTL_NGIVEN];
-  const int proba_every = g.ctl[FGCTL_PEVERY] > 0 ? g.ctl[FGCTL_PEVERY] : 1;
-  const float temperature = __int_as_float(g.ctl[FGCTL_TEMP]);
-  const uint64_t seed = (uint64_t)(uint32_t)g.ctl[FGCTL_SEED] |
-                        ((uint64_t)(uint32_t)g.ctl[FGCTL_SEED + 1] << 32);
-  for (int q = lane; q < Q; q += 64) pd[q] = (double)lg[q];
+  for (int q = lane; q < Q; q += 64) pd[q] = (double)g.logits[q];
   __builtin_amdgcn_wave_barrier();
-  double m = -1e300;
-  for (int q = lane; q < Q; q += 64) m = fmax(m, pd[q]);
-  for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-  // each double-precision exp / log is evaluated once and kept in LDS
-  double se = 0.0;
-  for (int q = lane; q < Q; q += 64) {
-    const double e = exp(pd[q] - m);
-    pd[q] = e;
-    se += e;
-  }
-  for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
-  const bool want_p = g.proba_out && (local % proba_every == 0);
-  float* po = want_p ? g.proba_out + (long)(local / proba_every) * Q : nullptr;
-  for (int q = lane; q < Q; q += 64) {
-    const float p32 = (float)(pd[q] / se);
-    if (po) po[q] = p32;
-    pd[q] = (double)p32;
-  }
-  int next = 0;
-  if (local + 1 >= n_given) {
-    // sampling weights w_q proportional to exp(log(p_q) / tau)
-    // (generate.py:229-233); at tau == 1 that is p_q itself; p_q == 0: w_q = 0
-    const double tau = (double)temperature;
-    if (temperature != 1.0f) {
-      double mx = -1e300;
-      for (int q = lane; q < Q; q += 64) {
-        const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
-        pd[q] = lp;
-        mx = fmax(mx, lp);
-      }
-      for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-      for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int per = (Q + 63) / 64;
-    const int q0 = lane * per, q1 = min(Q, q0 + per);
-    double seg = 0.0;
-    for (int q = q0; q < q1; ++q) seg += pd[q];
-    double incl = seg;
-    for (int o = 1; o < 64; o <<= 1) {
-      const double v = __shfl_up(incl, o);
-      if (lane >= o) incl += v;
-    }
-    const double total = __shfl(incl, 63);
-    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)steps_done));
-    const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
-    // (the neighbour's inclusive sum, not incl - seg: the lanes' intervals
-    // then tile [0, total) exactly -- no gap a draw could fall into)
-    const double up = __shfl_up(incl, 1);
-    const double excl = lane == 0 ? 0.0 : up;
-    int pick = -1;
-    if (u >= excl && u < incl) {
-      double c = excl;
-      pick = q1 - 1;
-      for (int q = q0; q < q1; ++q) {
-        c += pd[q];
-        if (u < c) { pick = q; break; }
-        if (pd[q] > 0.0) pick = q;       // (u past the rounded walk: the last code of weight > 0)
-      }
-    }
-    int best = pick;
-    for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
-    if (best < 0) best = Q - 1;
-    if (lane == 0) g.samples[local + 1] = best;
-    next = best;
+  const bool want_p = g.proba_out && (local % dc.proba_every == 0);
+  wave_softmax_f64(pd, Q, lane, want_p ? g.proba_out + (long)(local / dc.proba_every) * Q : nullptr);
+  int next;
+  if (local + 1 >= dc.n_given) {
+    next = wave_draw_f64(pd, Q, lane, dc.temperature, dc.seed, (uint64_t)steps_done);
+    if (lane == 0) g.samples[local + 1] = next;
   } else {
     next = g.samples[local + 1];           // still inside the given samples
   }
@@ -1168,25 +1047,10 @@ __device__ __forceinline__ void fg_row_halves(float v, float& lo, float& hi) {
   hi = __uint_as_float(pr[1]);
 }
 
-// What the draw reads from ctl[]: constant over a launch, read once.
-struct FgDrawCtl {
-  int base, n_given, proba_every;
-  float temperature;
-  uint64_t seed;
-};
-__device__ __forceinline__ FgDrawCtl fg_draw_ctl(const FgStep& g) {
-  FgDrawCtl c;
-  c.base = g.ctl[FGCTL_BASE];
-  c.n_given = g.ctl[FGCTL_NGIVEN];
-  c.proba_every = g.ctl[FGCTL_PEVERY] > 0 ? g.ctl[FGCTL_PEVERY] : 1;
-  c.temperature = __int_as_float(g.ctl[FGCTL_TEMP]);
-  c.seed = (uint64_t)(uint32_t)g.ctl[FGCTL_SEED] | ((uint64_t)(uint32_t)g.ctl[FGCTL_SEED + 1] << 32);
-  return c;
-}
-
-// The draw of fg_draw_wave by the persistent kernel's draw workgroup (its first
-// 256 threads compute, Q <= 512): float64 softmax of the Q logits in LDS `lgs`,
-// temperature, inverse-CDF draw with the same random number.  One exp / log /
+// The draw of wave_softmax_f64 + wave_draw_f64 (wn_common.h) by the persistent
+// kernel's draw workgroup (its first 256 threads compute, Q <= 512): float64
+// softmax of the Q logits in LDS `lgs`, temperature, inverse-CDF draw with the
+// same random number.  One exp / log /
 // division per thread instead of Q / 64 per lane.  Every wave keeps its values
 // in registers: sums and the prefix sum are DPP scans inside the wave plus one
 // partial per wave in LDS (two workgroup barriers per step; round 4: five, and
@@ -1219,7 +1083,7 @@ __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& 
     fgp_put(x0ll + lane, v, step);
   };
   // (the step's random number does not wait for the logits)
-  const uint64_t r = splitmix64(dc.seed ^ splitmix64((uint64_t)steps_done));
+  const uint64_t r = draw_bits(dc.seed, (uint64_t)steps_done);
   // the maximum: every wave for itself over all Q logits
   float mf = -3.0e38f;
   if (Q == 256) {                                      // (the reference's 8-bit mu-law: one read)
@@ -1264,7 +1128,7 @@ __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& 
     double lp[2] = {-1e300, -1e300};
 #pragma unroll
     for (int j = 0; j < PER; ++j)
-      if (q0 + j < q1) lp[j] = pq[j] > 0.0 ? log(pq[j]) / tau : -INFINITY;
+      if (q0 + j < q1) lp[j] = draw_log_weight(pq[j], tau);
     const double wm = wave_max_f64(PER == 2 ? fmax(lp[0], lp[1]) : lp[0]);
     if (lane == 0 && wave < 4) part[4 + wave] = wm;
     __syncthreads();
@@ -1287,11 +1151,11 @@ __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& 
   const double total = ((part[8] + part[9]) + part[10]) + part[11];
   incl += offs;
   excl += offs;
-  const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
+  const double u = draw_unit(r) * total;
   int next = -1;
   if (q1 > q0 && u >= excl && u < incl)
     next = (PER == 2 && q1 - q0 == 2 && pq[1] > 0.0 && u >= excl + pq[0]) ? q0 + 1 : q0;
-  // (u == total after rounding: the last code, as fg_draw_wave)
+  // (u == total after rounding: the last code, as wave_draw_f64)
   if (q1 == Q && q1 > q0 && u >= incl) next = Q - 1;
   if (next >= 0) {
     g.samples[local + 1] = next;
@@ -1734,8 +1598,8 @@ __global__ __launch_bounds__(FGP_THREADS) void fg_persist_kernel(FgPersist a) {
 //   1. thread (which, c): a_which[c] = bias + st . W_which[0][:, c] + x . W_which[1][:, c]
 //   2. z = tanh(a_f) sigmoid(a_g); the queue entry is replaced by x (push)
 //   3. x += bd + z . Wd  (every layer, as model.py:377-380); total += z . Ws_l
-// then the post-processing mat-vecs, the float64 softmax and the same
-// counter-based draw as fastgen_kernel (same seed -> same uniform per step).
+// then the post-processing mat-vecs and the float64 softmax and counter-based
+// draw of wn_common.h (same seed -> same uniform per step).
 // Queues: layer l's ring holds d_l rows of C floats at state + roff[l] * C.
 // ===========================================================================
 #define FGW_THREADS 256
@@ -2144,70 +2008,15 @@ __global__ __launch_bounds__(F64 ? 512 : FGW_THREADS, 1) void fastgen_wide_kerne
       }
       __syncthreads();
     }
-    // ---- softmax in float64, temperature, draw: as fastgen_kernel
+    // ---- softmax in float64, temperature, draw (wn_common.h)
     if (wave == 0) {
-      double m = -1e300;
-      for (int q = lane; q < Q; q += 64) m = fmax(m, pd[q]);
-      for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-      double se = 0.0;
-      for (int q = lane; q < Q; q += 64) {
-        const double e = exp(pd[q] - m);
-        pd[q] = e;
-        se += e;
-      }
-      for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
       const bool want_p = g.proba_out && (step % g.proba_every == 0);
-      float* po = want_p ? g.proba_out + (long)(step / g.proba_every) * Q : nullptr;
-      for (int q = lane; q < Q; q += 64) {
-        const float p32 = (float)(pd[q] / se);
-        if (po) po[q] = p32;
-        pd[q] = (double)p32;
-      }
+      wave_softmax_f64(pd, Q, lane, want_p ? g.proba_out + (long)(step / g.proba_every) * Q : nullptr);
     }
     __syncthreads();
     if (step + 1 >= g.n_given) {
       if (wave == 0) {
-        const double tau = (double)g.temperature;
-        if (g.temperature != 1.0f) {
-          double mx = -1e300;
-          for (int q = lane; q < Q; q += 64) {
-            const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
-            pd[q] = lp;
-            mx = fmax(mx, lp);
-          }
-          for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-          for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int per = (Q + 63) / 64;
-        const int q0 = lane * per, q1 = min(Q, q0 + per);
-        double seg = 0.0;
-        for (int q = q0; q < q1; ++q) seg += pd[q];
-        double incl = seg;
-        for (int o = 1; o < 64; o <<= 1) {
-          const double v = __shfl_up(incl, o);
-          if (lane >= o) incl += v;
-        }
-        const double total = __shfl(incl, 63);
-        const uint64_t r = splitmix64(g.seed ^ splitmix64((uint64_t)tpos));
-        const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
-        // (the neighbour's inclusive sum, not incl - seg: the lanes' intervals
-        // then tile [0, total) exactly -- no gap a draw could fall into)
-        const double up = __shfl_up(incl, 1);
-        const double excl = lane == 0 ? 0.0 : up;
-        int pick = -1;
-        if (u >= excl && u < incl) {
-          double c = excl;
-          pick = q1 - 1;
-          for (int q = q0; q < q1; ++q) {
-            c += pd[q];
-            if (u < c) { pick = q; break; }
-            if (pd[q] > 0.0) pick = q;   // (u past the rounded walk: the last code of weight > 0)
-          }
-        }
-        int best = pick;
-        for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
-        if (best < 0) best = Q - 1;
+        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.seed, (uint64_t)tpos);
         if (lane == 0) {
           g.samples[step + 1] = best;
           s_code = best;

@@ -75,13 +75,6 @@ struct FgBatch {
   float* logits;           // [Bp][Q]
 };
 
-__device__ __forceinline__ uint64_t fgb_splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // 16 x 16 x 4 f32 MFMA.  Lane l: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15];
 // C/D: column l & 15, rows 4 (l >> 4) + r.
 __device__ __forceinline__ f32x4 fgb_mfma(float a, float b, f32x4 c) {
@@ -89,80 +82,24 @@ __device__ __forceinline__ f32x4 fgb_mfma(float a, float b, f32x4 c) {
 }
 
 // ---------------------------------------------------------------- the draw
-// float64 softmax of stream b's logits, temperature, inverse-CDF draw:
-// fg_draw_wave of wn_fastgen.hip with the stream's own rows and seed (the
-// counter rule of tests/draw_ref.py: counter = the step that produced the
-// logits).  One wave; pd: FGB_MAXQ doubles of LDS owned by it.
+// The draw of wn_common.h for stream b: its own rows and seed, counter = the
+// step that produced the logits (the counter rule of tests/draw_ref.py).  One
+// wave; pd: FGB_MAXQ doubles of LDS owned by it.
 __device__ void fgb_draw_wave(const FgBatch& g, double* pd, int lane, int b, int step) {
   const int Q = g.Q;
   const float* lg = g.logits + (long)b * Q;
   const int local = step - g.ctl[FGB_CTL_BASE];
-  const int n_given = g.ctl[FGB_CTL_NGIVEN];
   const int proba_every = g.ctl[FGB_CTL_PEVERY] > 0 ? g.ctl[FGB_CTL_PEVERY] : 1;
-  const float temperature = __int_as_float(g.ctl[FGB_CTL_TEMP]);
-  int32_t* samples = g.samples + (long)b * g.ctl[FGB_CTL_LDS];
-  const uint64_t seed = g.seeds[b];
   for (int q = lane; q < Q; q += 64) pd[q] = (double)lg[q];
   __builtin_amdgcn_wave_barrier();
-  double m = -1e300;
-  for (int q = lane; q < Q; q += 64) m = fmax(m, pd[q]);
-  for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-  double se = 0.0;
-  for (int q = lane; q < Q; q += 64) {
-    const double e = exp(pd[q] - m);
-    pd[q] = e;
-    se += e;
-  }
-  for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
   const bool want_p = g.proba_out && (local % proba_every == 0);
-  float* po = want_p ? g.proba_out + ((long)b * g.ctl[FGB_CTL_LDP] + local / proba_every) * Q
-                     : nullptr;
-  for (int q = lane; q < Q; q += 64) {
-    const float p32 = (float)(pd[q] / se);
-    if (po) po[q] = p32;
-    pd[q] = (double)p32;
-  }
-  if (local + 1 < n_given) return;       // still inside the given samples
-  const double tau = (double)temperature;
-  if (temperature != 1.0f) {
-    double mx = -1e300;
-    for (int q = lane; q < Q; q += 64) {
-      const double lp = pd[q] > 0.0 ? log(pd[q]) / tau : -INFINITY;
-      pd[q] = lp;
-      mx = fmax(mx, lp);
-    }
-    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-    for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
-  }
-  __builtin_amdgcn_wave_barrier();
-  const int per = (Q + 63) / 64;
-  const int q0 = lane * per, q1 = min(Q, q0 + per);
-  double seg = 0.0;
-  for (int q = q0; q < q1; ++q) seg += pd[q];
-  double incl = seg;
-  for (int o = 1; o < 64; o <<= 1) {
-    const double v = __shfl_up(incl, o);
-    if (lane >= o) incl += v;
-  }
-  const double total = __shfl(incl, 63);
-  const uint64_t r = fgb_splitmix64(seed ^ fgb_splitmix64((uint64_t)step));
-  const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * total;
-  const double up = __shfl_up(incl, 1);
-  const double excl = lane == 0 ? 0.0 : up;
-  int pick = -1;
-  if (u >= excl && u < incl) {
-    double c = excl;
-    pick = q1 - 1;
-    for (int q = q0; q < q1; ++q) {
-      c += pd[q];
-      if (u < c) { pick = q; break; }
-      if (pd[q] > 0.0) pick = q;
-    }
-  }
-  int best = pick;
-  for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
-  if (best < 0) best = Q - 1;
-  if (lane == 0) samples[local + 1] = best;
+  wave_softmax_f64(pd, Q, lane,
+                   want_p ? g.proba_out + ((long)b * g.ctl[FGB_CTL_LDP] + local / proba_every) * Q
+                          : nullptr);
+  if (local + 1 < g.ctl[FGB_CTL_NGIVEN]) return;   // still inside the given samples
+  const int code = wave_draw_f64(pd, Q, lane, __int_as_float(g.ctl[FGB_CTL_TEMP]), g.seeds[b],
+                                 (uint64_t)step);
+  if (lane == 0) g.samples[(long)b * g.ctl[FGB_CTL_LDS] + local + 1] = code;
 }
 
 // one wave per stream; reads the cursors, writes none (the chain kernel that

@@ -1646,12 +1646,25 @@ class WaveNetModel(object):
                 _lib.check(code, 'wn_fastgen_persist')
             del snap
 
-        def one():
-            _lib.call('wn_fastgen_step', *common, *tail, _lib.stream())
+        self._replay_steps(g, (common, tail), lambda: _lib.call(
+            'wn_fastgen_step', *common, *tail, _lib.stream()), n_steps)
+        # the last step's draw (every other one ran inside the next step)
+        _lib.call('wn_fastgen_finish', self.Q, _lib.ptr(g['cursors']),
+                  _lib.ptr(io), _lib.ptr(g['ctl']), _lib.ptr(pb),
+                  _lib.ptr(g['logits']), _lib.stream())
+        g['steps'] += int(n_steps)
+        samples_io[:n_io].copy_(io[:n_io])
+        if proba_out is not None:
+            proba_out.view(-1).copy_(pb[:proba_out.numel()])
 
+    def _replay_steps(self, g, key, one, n_steps):
+        """n_steps calls of one() (a step's launches) for generator dict g:
+        the first step g ever runs outside any capture, then hipGraphs of
+        fastgen_graph_steps and of a tenth of that many steps, captured once
+        per (key, length) and replayed, then single steps.  key must hold
+        every pointer and value the launches were given."""
         def graph_of(nsteps):
-            key = (common, tail, nsteps)
-            gr = g['graphs'].get(key)
+            gr = g['graphs'].get((key, nsteps))
             if gr is None:
                 gr = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gr):
@@ -1659,7 +1672,7 @@ class WaveNetModel(object):
                         one()
                 if len(g['graphs']) > 8:
                     g['graphs'].clear()
-                g['graphs'][key] = gr
+                g['graphs'][key, nsteps] = gr
             return gr
         done = 0
         if not g['warm']:
@@ -1674,14 +1687,6 @@ class WaveNetModel(object):
                     done += per
         for _ in range(n_steps - done):
             one()
-        # the last step's draw (every other one ran inside the next step)
-        _lib.call('wn_fastgen_finish', self.Q, _lib.ptr(g['cursors']),
-                  _lib.ptr(io), _lib.ptr(g['ctl']), _lib.ptr(pb),
-                  _lib.ptr(g['logits']), _lib.stream())
-        g['steps'] += int(n_steps)
-        samples_io[:n_io].copy_(io[:n_io])
-        if proba_out is not None:
-            proba_out.view(-1).copy_(pb[:proba_out.numel()])
 
     def _gen_buf(self, name, n, dtype):
         """Persistent per-generator buffer of at least n elements (grown
@@ -2019,34 +2024,8 @@ class WaveNetModel(object):
                                    proba, proba_every, gc)
         args = prep['args']
 
-        def one():
-            _lib.call('wn_fastgen_batch_step', *args, _lib.stream())
-
-        def graph_of(nsteps):
-            key = (args, nsteps)
-            gr = g['graphs'].get(key)
-            if gr is None:
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr):
-                    for _ in range(nsteps):
-                        one()
-                if len(g['graphs']) > 8:
-                    g['graphs'].clear()
-                g['graphs'][key] = gr
-            return gr
-        done = 0
-        if not g['warm']:
-            one()                      # module load etc. outside any capture
-            done, g['warm'] = 1, True
-        for per in (int(self.fastgen_graph_steps),
-                    max(1, int(self.fastgen_graph_steps) // 10)):
-            if per > 1 and n_steps - done >= per:
-                gr = graph_of(per)
-                while n_steps - done >= per:
-                    gr.replay()
-                    done += per
-        for _ in range(n_steps - done):
-            one()
+        self._replay_steps(g, args, lambda: _lib.call(
+            'wn_fastgen_batch_step', *args, _lib.stream()), n_steps)
         self._batch_complete(g, prep, io, proba, n_steps)
 
     def _batch_prime(self, g, codes, gc):

@@ -3,15 +3,19 @@ log(p) / T, normalise, np.random.choice) with the device's random numbers, in
 float64 numpy and never through the library.  The tests compare every code
 the device draws with pick(weights(p, T), uniform(seed, counter)).
 
-The random number.  Every draw site of csrc/wn_fastgen.hip (fastgen_kernel,
-fg_draw_wave, fg_draw_wg256<1|2>, fastgen_wide_kernel) takes
+The random number.  Every draw site (fastgen_kernel, fg_draw_wave,
+fg_draw_wg256<1|2> and fastgen_wide_kernel of csrc/wn_fastgen.hip,
+fgb_draw_wave of csrc/wn_fastgen_batch.hip) takes the uniform of
+csrc/wn_common.h (draw_uniform, or its halves draw_bits and draw_unit),
     r = splitmix64(seed ^ splitmix64(counter)),   u = (r >> 11) * 2**-53
-and walks the inverse CDF of the weights at u * total.
+and walks the inverse CDF of the weights at u * total.  All but fg_draw_wg256
+draw with wave_draw_f64 of the same header.
 
 The counter is the generator's absolute step count at the step that consumes
 the code before the drawn one: `tpos` = cursors[0] + step in fastgen_kernel
-and fastgen_wide_kernel, `steps_done` in fg_draw_wave and `base + i` (=
-steps_done) in fg_draw_wg256.  After reset_generator(), output code k + 1 of
+and fastgen_wide_kernel, `steps_done` in fg_draw_wave, `base + i` (=
+steps_done) in fg_draw_wg256 and `step` (the step that produced the logits,
+per stream) in fgb_draw_wave.  After reset_generator(), output code k + 1 of
 generate() (index k + 1 of the returned codes, seed samples included) is
 drawn with counter k; prime_generator() leaves cursors[0] = len(seed) - 1,
 which keeps that rule; continue_generation() goes on counting from where the

@@ -22,7 +22,8 @@ TAUS = (1.0, 0.7, 0.05, 3.0, 100.0)
 KINDS = ('random', 'cliff', 'near_ties')
 SEED_CODES = 2          # seed_samples=[Q // 2, 3]: code k + 1 drawn with counter k
 ENTRIES = ('wn_fastgen_run', 'wn_fastgen_step', 'wn_fastgen_persist',
-           'wn_fastgen_run_wide')
+           'wn_fastgen_run_wide', 'wn_fastgen_batch_step')
+BATCH = 4               # streams of the batched site, each with its own seed
 
 # (id, quantization channels, residual = dilation channels, device flags,
 #  the entry point that must run, cooperative wide launch)
@@ -34,7 +35,8 @@ SITES = [('one_wg', Q, 32, dict(fastgen_multi_cu=False), 'wn_fastgen_run', None)
           'wn_fastgen_persist', None) for Q in (100, 256, 320, 512)] + \
         [('wide', 1024, 32, dict(), 'wn_fastgen_run_wide', False),
          ('wide_coop', 256, 64, dict(fastgen_wide_coop=True), 'wn_fastgen_run_wide', True),
-         ('wide_single', 256, 64, dict(fastgen_wide_coop=False), 'wn_fastgen_run_wide', False)]
+         ('wide_single', 256, 64, dict(fastgen_wide_coop=False), 'wn_fastgen_run_wide', False),
+         ('batch', 256, 32, dict(), 'wn_fastgen_batch_step', None)]
 
 
 def _softmax32(logits):
@@ -77,7 +79,8 @@ def test_draw_matches_restatement(hip_lib, monkeypatch, site, Q, R, flags, entry
     twice per run, and then only a code beside the boundary); (c) no code of
     probability 0 is drawn -- for temperatures 1, 0.7, 0.05, 3 and 100 (the
     near-ties vector: 1, 0.05 and 100), with graph replays crossed and seeds
-    whose runs hold uniforms within 1e-3 of 0 and of 1."""
+    whose runs hold uniforms within 1e-3 of 0 and of 1.  The batched site
+    (generate_batch) checks all of this for each of BATCH streams."""
     from wavenet import _lib
     cfg = cfg_with(MID, batch_size=1, quantization_channels=Q,
                    residual_channels=R, dilation_channels=R)
@@ -109,14 +112,21 @@ def test_draw_matches_restatement(hip_lib, monkeypatch, site, Q, R, flags, entry
             if kind == 'near_ties' and T in (0.7, 3.0):
                 continue                   # (GPU time: ties need no more temperatures)
             what = '%s Q=%d R=%d %s T=%g' % (site, Q, R, kind, T)
-            seed = _seed_with_extremes(counters, 1000 * (ki * len(TAUS) + ti) + Q)
+            seeds = [_seed_with_extremes(counters, 1000 * (ki * len(TAUS) + ti) + Q)]
             for e in ENTRIES:
                 calls[e].clear()
             if net._gen is not None and net._gen.get('coop') is not None:
                 net._gen['coop'].zero_()
-            codes, proba = net.generate(N_DRAW, seed_samples=[Q // 2, 3],
-                                        temperature=T, seed=seed,
-                                        return_proba_every=1)
+            if site == 'batch':
+                while len(seeds) < BATCH:
+                    seeds.append(_seed_with_extremes(counters, seeds[-1] + 1))
+                codes, proba = net.generate_batch(N_DRAW, seeds, seed_samples=[Q // 2, 3],
+                                                  temperature=T, return_proba_every=1)
+            else:
+                codes, proba = net.generate(N_DRAW, seed_samples=[Q // 2, 3],
+                                            temperature=T, seed=seeds[0],
+                                            return_proba_every=1)
+                codes, proba = codes[None], proba[None]
             codes, proba = codes.cpu().numpy(), proba.cpu().numpy()
             # the intended draw site ran, and nothing else
             assert calls[entry], (what, 'not called', entry)
@@ -131,17 +141,19 @@ def test_draw_matches_restatement(hip_lib, monkeypatch, site, Q, R, flags, entry
                 assert int(net._gen['coop'].count_nonzero()) > 0, \
                     (what, 'the cooperative launch did not run')
             # (a) probabilities
-            assert proba.shape == (N_DRAW + 1, Q) and codes.shape == (N_DRAW + 2,)
+            B = len(seeds)
+            assert proba.shape == (B, N_DRAW + 1, Q) and codes.shape == (B, N_DRAW + 2)
             assert np.array_equal(proba == 0, np.broadcast_to(p_ref == 0, proba.shape)), what
             ulp = np.abs(proba - p_ref) / np.spacing(p_ref)
             assert ulp.max() <= 1.0, (what, float(ulp.max()), np.unravel_index(ulp.argmax(), ulp.shape))
             # (b), (c) drawn codes: code k + 1 drawn with counter k from row k
-            u = D.uniform(seed, counters)
-            assert u.min() < 1e-3 and u.max() > 1 - 1e-3
-            assert codes[0] == Q // 2 and codes[1] == 3
-            D.check_draws(codes[SEED_CODES:], proba[1:], float(np.float32(T)), seed,
-                          counters, what=what)
-            if kind == 'cliff' and T == 100.0:
-                # the three +110 codes carry weight exp(-0.1) each: the draw
-                # must not collapse onto the top code
-                assert len(np.unique(codes[SEED_CODES:])) == 4, what
+            for b, seed in enumerate(seeds):
+                u = D.uniform(seed, counters)
+                assert u.min() < 1e-3 and u.max() > 1 - 1e-3
+                assert codes[b, 0] == Q // 2 and codes[b, 1] == 3
+                D.check_draws(codes[b, SEED_CODES:], proba[b, 1:], float(np.float32(T)), seed,
+                              counters, what='%s stream %d' % (what, b))
+                if kind == 'cliff' and T == 100.0:
+                    # the three +110 codes carry weight exp(-0.1) each: the draw
+                    # must not collapse onto the top code
+                    assert len(np.unique(codes[b, SEED_CODES:])) == 4, what
