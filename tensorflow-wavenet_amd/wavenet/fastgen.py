@@ -1,0 +1,611 @@
+"""Fast generation, host side (_create_generator, predict_proba_incremental,
+wavenet/model.py:444-626; the loop of generate.py:195-241): the queues of one
+stream (`net._gen`) or of B streams in lock step (`net._bgen`) stay on the
+device.  Library entry points are looked up when they run."""
+import functools
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+
+CH = 32
+_EXPIRED = dict(
+    coop='wn_fastgen_run_wide: a hand-over wait inside the cooperative '
+         'generation launch expired (2 s: its workgroups were not all '
+         'resident); state restored, continuing with the single workgroup '
+         '(net.fastgen_wide_coop = False selects it up front)',
+    persist='wn_fastgen_persist: a hand-over wait inside the persistent '
+            'generation launch expired (2 s: its workgroups were not all '
+            'resident); state restored, continuing with the step kernels '
+            '(net.fastgen_persistent = False selects them up front)')
+
+
+# ------------------------------------------------ shared by both generators
+def _new_state(net, dil, nfl, rows, nbias, **extra):
+    # queues of nfl floats, bias of nbias streams, step scratch of `rows`
+    f32 = dict(dtype=torch.float32, device=net.device)
+    return dict(
+        state=torch.zeros(nfl, **f32),
+        # one stream: [0] steps done, [1] previous code, [2] draw pending;
+        # B streams: [0] steps pushed, [1] draw pending
+        cursors=torch.zeros(4, dtype=torch.int32, device=net.device),
+        dil=torch.from_numpy(dil).to(net.device),
+        bias=torch.zeros(net.L * nbias * 2 * net.CHn, **f32),
+        bsum=torch.zeros(net.S, **f32),
+        ctl=torch.zeros(8, dtype=torch.int32, device=net.device),
+        pre=torch.zeros(net.L * rows * 2 * CH, **f32),
+        z_all=torch.zeros(rows * net.L * CH, **f32),
+        h1=torch.zeros(rows * net.S, **f32),
+        h2=torch.zeros(rows * net.S, **f32),
+        logits=torch.zeros(rows * net.Q, **f32),
+        graphs={}, warm=False, steps=0, **extra)
+
+
+def _check_temperature(temperature):
+    if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
+        raise ValueError('temperature must be a finite number > 0, got %r'
+                         % (temperature,))
+
+
+def _buf(net, g, name, n, dtype):
+    """Persistent buffer of g of at least n elements (grown geometrically;
+    growing drops the captured graphs, which hold its address)."""
+    buf = g.get(name)
+    if buf is None or buf.numel() < n:
+        cap = max(int(n), 2 * (buf.numel() if buf is not None else 0), 4096)
+        g[name] = buf = torch.zeros(cap, dtype=dtype, device=net.device)
+        g['graphs'].clear()
+    return buf
+
+
+def _weights(net, g, gc, B):
+    """GC / filter-gate bias and skip-bias sum of B streams -> the nine
+    parameter pointers, the bias pointer and its stream stride."""
+    P, ub = net.params, net.use_biases
+    bias, bstride = net._bias_fg(g['bias'], net._gc_ids(gc, B), B)
+    bsum = None
+    if ub:
+        _lib.call('wn_sum_rows', _lib.ptr(net._seg(P, 'skip_b')), net.L,
+                  net.S, _lib.ptr(g['bsum']), _lib.stream())
+        bsum = g['bsum']
+    w = (_lib.ptr(net._seg(P, 'causal')), _lib.ptr(net._layer_block(P, 0)),
+         net.layer_stride, _lib.ptr(net._seg(P, 'skip_w')), _lib.ptr(bsum),
+         _lib.ptr(net._seg(P, 'post1_w')),
+         _lib.ptr(net._seg(P, 'post1_b')) if ub else None,
+         _lib.ptr(net._seg(P, 'post2_w')),
+         _lib.ptr(net._seg(P, 'post2_b')) if ub else None)
+    return w, _lib.ptr(bias), bstride
+
+
+def _stage(net, g, io, n_given, n_steps, temperature, proba, proba_every,
+           seed=None):
+    # per-call values go to ctl and two persistent buffers (codes io [B, >=
+    # n_steps + 1], probabilities), so captured graphs stay valid; ctl words
+    # 4-5: one stream's seed, or B streams' row stride and probability rows
+    B, ld = io.shape[0], int(n_steps) + 1
+    pe = max(1, int(proba_every))
+    rows = (int(n_steps) + pe - 1) // pe if proba is not None else 0
+    iob = _buf(net, g, 'io_buf', B * ld, torch.int32)
+    iob[:B * ld].view(B, ld).copy_(io[:, :ld])
+    pb = None
+    if proba is not None:
+        pb = _buf(net, g, 'proba_buf', B * rows * net.Q, torch.float32)
+    ctl = np.zeros(8, np.uint32)
+    ctl[0], ctl[1], ctl[2] = g['steps'], int(n_given), pe
+    ctl[3] = np.float32(temperature).view(np.uint32)
+    ctl[4], ctl[5] = (ld, rows) if seed is None else \
+        (seed & 0xffffffff, seed >> 32)
+    g['ctl'].copy_(torch.from_numpy(ctl.view(np.int32)))
+    return iob, pb
+
+
+def _replay_steps(net, g, key, one, n_steps):
+    """n_steps calls of one() (a step's launches) for generator dict g:
+    the first step g ever runs outside any capture, then hipGraphs of
+    fastgen_graph_steps and of a tenth of that many steps, captured once
+    per (key, length) and replayed, then single steps.  key must hold
+    every pointer and value the launches were given."""
+    def graph_of(nsteps):
+        gr = g['graphs'].get((key, nsteps))
+        if gr is None:
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                for _ in range(nsteps):
+                    one()
+            if len(g['graphs']) > 8:
+                g['graphs'].clear()
+            g['graphs'][key, nsteps] = gr
+        return gr
+    done = 0
+    if not g['warm']:
+        one()                      # module load etc. outside any capture
+        done, g['warm'] = 1, True
+    for per in (int(net.fastgen_graph_steps),
+                max(1, int(net.fastgen_graph_steps) // 10)):
+        if per > 1 and n_steps - done >= per:
+            gr = graph_of(per)
+            while n_steps - done >= per:
+                gr.replay()
+                done += per
+    for _ in range(n_steps - done):
+        one()
+
+
+def _expired(net, kind, scratch, restore):
+    # what the residency check cannot see (CUs held elsewhere, a CU mask)
+    # shows as an expired hand-over wait, word 12 of the scratch: `restore`
+    # is copied back and the caller repeats the run on a path that always
+    # completes.  (synchronises; a generation call ends on the host anyway)
+    if int(scratch[12]) == 0:
+        return False
+    warnings.warn(_EXPIRED[kind])
+    for t, saved in restore:
+        t.copy_(saved)
+    # (remembered on the MODEL: a new generator on the same busy device must
+    # not pay another expired wait)
+    net._gen_launch_failed[kind] = True
+    return True
+
+
+def _prime(net, g, n0, groups, Bp):
+    # ONE batch-1 forward pass per (codes [n0], GC id, streams): layer l's
+    # queue holds its last d_l inputs x_l[t] (model.py:473-484), rows of
+    # activation planes l * CB + cb; ring rows are [entries][Bp][32]
+    CB = net.CB
+    src, dst, roff = [], [], 0
+    for l, d in enumerate(net.dilations):
+        t = np.arange(max(0, n0 - d), n0, dtype=np.int64)
+        for cb in range(CB):
+            src.append((l * CB + cb) * n0 + t)
+            dst.append((roff + t % d) * CB + cb)
+        roff += d
+    src = torch.from_numpy(np.concatenate(src)).to(net.device)
+    dst = np.concatenate(dst)
+    ws = net._workspace(1, n0, False)
+    for codes, gc, streams in groups:
+        ws.q.copy_(codes)
+        net._forward(ws, net._gc_ids(gc, 1), save_ts=0)
+        # (+ the forward launch's poison word: 0, or NaN after an expired wait)
+        vals = ws.X.reshape(-1, CH).index_select(0, src) + ws.loss_parts[0]
+        rows = dst[None, :] * Bp + np.asarray(streams, np.int64)[:, None]
+        g['state'].view(-1, CH).index_copy_(
+            0, torch.from_numpy(rows.reshape(-1)).to(net.device),
+            vals.repeat(len(streams), 1))
+
+
+def _seeded(net, io, n_given, n, pe, prime, run):
+    # io [..., n_given + n] starts with the seed codes; returns the
+    # probabilities [..., rows, Q] of every pe-th step, or None
+    n_steps = n_given - 1 + n
+    proba = None
+    if pe > 0:
+        proba = torch.empty(io.shape[:-1] + ((n_steps + pe - 1) // pe, net.Q),
+                            dtype=torch.float32, device=net.device)
+    if prime and pe == 0 and n_given - 1 >= net.fastgen_prime_forward_min \
+            and n > 0:
+        # the reference's own TODO (generate.py:199-201): fill the queues
+        # from a forward pass over the seed instead of stepping through it
+        prime()
+        tail = io[..., n_given - 1:].clone()   # [last seed | generated ...]
+        run(tail, 1, n, None, 1)
+        io[..., n_given - 1:] = tail
+    elif n_steps > 0:
+        run(io, n_given, n_steps, proba, max(1, pe))
+    return proba
+
+
+# --------------------------------------------------------------- one stream
+def generator(net, global_condition):
+    """Device-resident incremental-generation state (_create_generator,
+    model.py:444-516): ring buffers standing in for the FIFO queues."""
+    if net.CHn > net.FASTGEN_MAX_CHANNELS:
+        raise NotImplementedError(
+            'fast (incremental) generation supports at most %d residual / '
+            'dilation channels on the HIP path; predict_proba (generate.py '
+            'without --fast_generation) has no such limit'
+            % net.FASTGEN_MAX_CHANNELS)
+    if net._gen is None:
+        dil = np.asarray(net.dilations, dtype=np.int32)
+        # (queue entries are rows of CHn = 32 * blocks floats)
+        nfl = _lib.load().wn_fastgen_state_floats(dil.ctypes.data,
+                                                  net.L) * net.CB
+        f32 = dict(dtype=torch.float32, device=net.device)
+        net._gen = _new_state(
+            net, dil, nfl, 1, 1, cw_img=torch.zeros(net.L * 3072, **f32),
+            proba=torch.empty(net.Q, **f32),
+            io=torch.zeros(2, dtype=torch.int32, device=net.device))
+        reset(net)
+    return net._gen
+
+
+def reset(net):
+    g = net._gen
+    _lib.call('wn_fastgen_init', _lib.ptr(g['state']), g['state'].numel(),
+              _lib.ptr(g['cursors']), net.L, _lib.stream())
+    g['steps'] = 0
+
+
+def run(net, temperature, seed, global_condition, samples_io, n_given,
+        n_steps, proba_out, proba_every, push=True, multi_cu=False):
+    """Run `n_steps` generation steps on samples_io int32 [n_steps + 1]
+    (the first n_given codes given, the rest drawn) on one device path."""
+    # (wn_fastgen_step reads both from the device control block and cannot
+    # reject them; the reference applies the temperature as log(p) / T,
+    # generate.py:229-233)
+    _check_temperature(temperature)
+    if int(n_given) < 1:
+        raise ValueError('n_given must be >= 1, got %r' % (n_given,))
+    g = generator(net, global_condition)
+    w, bias, _ = _weights(net, g, global_condition, 1)
+    head = w + (bias, _lib.ptr(g['dil']))
+    queues = (_lib.ptr(g['state']), _lib.ptr(g['cursors']))
+    sd = int(seed) & (2**64 - 1)
+    ub = 1 if net.use_biases else 0
+    run_args = queues + (_lib.ptr(samples_io), int(n_given), int(n_steps),
+                         float(temperature), sd, _lib.ptr(proba_out),
+                         int(proba_every), ub, 1 if push else 0)
+    if net.CB > 1 or net.S > 512 or net.Q > 512 or net.L > 64:
+        _run_wide(net, g, samples_io,
+                  head + (net.L, net.CHn, net.S, net.Q) + run_args)
+    elif not multi_cu or not push:
+        # ONE single-workgroup kernel; the peek always runs here, as the
+        # multi-CU launches advance the queues with every step they take
+        _lib.call('wn_fastgen_run', *head, net.L, net.S, net.Q, *run_args,
+                  _lib.stream())
+    else:
+        st = _lib.stream()
+        layer0 = _lib.ptr(net._layer_block(net.params, 0))
+        # weights are constant while generating: pack the chain blocks once,
+        # and compute the past-tap pre-activations of the first step (every
+        # step then leaves the next step's behind)
+        _lib.call('wn_fastgen_pack', layer0, net.layer_stride,
+                  _lib.ptr(g['cw_img']), net.L, st)
+        _lib.call('wn_fastgen_pre', layer0, net.layer_stride, bias,
+                  _lib.ptr(g['dil']), net.L, *queues, _lib.ptr(g['pre']), st)
+        io = samples_io.view(1, -1)
+        iob, pb = _stage(net, g, io, n_given, n_steps, temperature,
+                         proba_out, proba_every, seed=sd)
+        common = head + (net.L, net.S, net.Q) + queues + (_lib.ptr(iob),)
+        tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), ub, _lib.ptr(g['cw_img']),
+                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
+                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
+        if not (net.fastgen_persistent
+                and not net._gen_launch_failed.get('persist')
+                and _run_persistent(net, g, common, tail, io, iob, n_steps)):
+            _run_steps(net, g, common, tail, iob, pb, n_steps)
+        samples_io[:int(n_steps) + 1].copy_(iob[:int(n_steps) + 1])
+        if proba_out is not None:
+            proba_out.view(-1).copy_(pb[:proba_out.numel()])
+    if push:
+        g['steps'] += int(n_steps)
+
+
+def _run_wide(net, g, samples_io, args):
+    # more than 32 channels, or more S / Q / L than the tuned kernels hold
+    # in LDS: one workgroup, or the cooperative launch (skip sum and post-
+    # processing on other CUs) where the library has one for the shape
+    coop = None
+    if net.fastgen_wide_coop and not net._gen_launch_failed.get('coop'):
+        if 'coop' not in g:
+            nb = _lib.load().wn_fastgen_wide_coop_bytes(
+                net.L, net.CHn, net.S, net.Q)
+            g['coop'] = torch.zeros(nb // 4, dtype=torch.int32,
+                                    device=net.device) if nb else None
+        coop = g['coop']
+    if coop is not None:
+        # an expired wait: queues, cursors and samples are restored and the
+        # single workgroup, which always completes, repeats the run
+        snap = [(t, t.clone()) for t in (g['state'], g['cursors'], samples_io)]
+        _lib.call('wn_fastgen_run_wide', *args, _lib.ptr(coop), _lib.stream())
+        if not _expired(net, 'coop', coop, snap):
+            return
+    _lib.call('wn_fastgen_run_wide', *args, None, _lib.stream())
+
+
+def _run_persistent(net, g, common, tail, io, iob, n_steps):
+    # ONE launch for the run; its workgroups must all be resident, which
+    # the library checks (WN_ERR_UNSUPPORTED).  False: the step kernels, which
+    # always complete, run it (after an expired wait, from restored state)
+    lib = _lib.load()
+    sync = _buf(net, g, 'fgp_sync', 16, torch.int32)
+    ll = _buf(net, g, 'fgp_ll', int(lib.wn_fastgen_persist_ll_words(
+        net.L, net.S, net.Q)), torch.int64)
+    snap = [(t, t.clone()) for t in (g['state'], g['cursors'], g['pre'])]
+    code = lib.wn_fastgen_persist(*common, *tail, _lib.ptr(sync),
+                                  _lib.ptr(ll), int(n_steps), _lib.stream())
+    if code == 0:
+        n_io = int(n_steps) + 1
+        return not _expired(net, 'persist', sync,
+                            snap + [(iob[:n_io], io[0, :n_io])])
+    if code != -2:                 # WN_ERR_UNSUPPORTED: not resident / shape
+        _lib.check(code, 'wn_fastgen_persist')
+    return False
+
+
+def _run_steps(net, g, common, tail, iob, pb, n_steps):
+    _replay_steps(net, g, (common, tail), lambda: _lib.call(
+        'wn_fastgen_step', *common, *tail, _lib.stream()), n_steps)
+    # the last step's draw (every other one ran inside the next step)
+    _lib.call('wn_fastgen_finish', net.Q, _lib.ptr(g['cursors']),
+              _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(pb),
+              _lib.ptr(g['logits']), _lib.stream())
+
+
+def predict_proba_incremental(net, waveform, global_condition, push):
+    if net.filter_width > 2:
+        raise NotImplementedError("Incremental generation does not "
+                                  "support filter_width > 2.")
+    if net.scalar_input:
+        raise NotImplementedError("Scalar input is not supported by "
+                                  "fast generation.")
+    net._check_supported()
+    g = generator(net, global_condition)
+    w = waveform
+    if isinstance(w, torch.Tensor):
+        g['io'][0:1].copy_(w.reshape(-1)[-1:].to(torch.int32))
+    else:
+        g['io'][0] = int(np.asarray(w).reshape(-1)[-1])
+    run(net, 1.0, 0, global_condition, g['io'], 1, 1, g['proba'], 1,
+        push=push)
+    return g['proba'].clone()
+
+
+def generate(net, num_samples, seed_samples, temperature, global_condition,
+             seed, return_proba_every):
+    net._check_supported()
+    if net.filter_width > 2 or net.scalar_input:
+        raise NotImplementedError('fast generation needs filter_width 2 '
+                                  'and one-hot input (model.py:597-603)')
+    if seed_samples is None:
+        seed_samples = [net.Q // 2]
+    s = torch.as_tensor(np.asarray(seed_samples),
+                        dtype=torch.int32).reshape(-1)
+    n_given, n = int(s.numel()), int(num_samples)
+    io = torch.zeros(n_given + n, dtype=torch.int32, device=net.device)
+    io[:n_given] = s.to(net.device)
+    net.reset_generator()
+    pe = int(return_proba_every)
+    proba = _seeded(net, io, n_given, n, pe,
+                    lambda: prime(net, io[:n_given - 1], global_condition),
+                    functools.partial(run, net, temperature, seed,
+                                      global_condition,
+                                      multi_cu=net.fastgen_multi_cu))
+    return (io, proba) if pe > 0 else io
+
+
+def prime(net, codes, global_condition):
+    if net.filter_width > 2 or net.scalar_input:
+        raise NotImplementedError('fast generation needs filter_width 2 '
+                                  'and one-hot input (model.py:597-603)')
+    net._check_supported()
+    g = generator(net, global_condition)
+    reset(net)
+    w = torch.as_tensor(codes).to(device=net.device,
+                                  dtype=torch.int32).reshape(-1)
+    n0 = int(w.numel())
+    if n0 == 0:
+        return
+    _prime(net, g, n0, [(w, global_condition, [0])], 1)
+    g['cursors'][0] = n0
+    g['cursors'][1:2].copy_(w[-1:])
+    g['steps'] = n0
+
+
+def continue_generation(net, num_samples, last_sample, temperature,
+                        global_condition, seed):
+    net._check_supported()
+    n = int(num_samples)
+    io = torch.zeros(n + 1, dtype=torch.int32, device=net.device)
+    io[0] = int(last_sample)
+    run(net, temperature, seed, global_condition, io, 1, n, None, 1,
+        multi_cu=net.fastgen_multi_cu)
+    return io[1:]
+
+
+# ---------------------------------------------------------------- B streams
+def _batch_args(net, seeds, per_stream, global_condition, temperature,
+                num_samples):
+    """The batched entry points' checks, in order, before anything touches
+    a device -> seeds (int64 bit patterns), per_stream(B), GC ids, n."""
+    if net.CB > 1:
+        raise NotImplementedError(
+            'generate_batch supports at most 32 residual / dilation '
+            'channels (this model has %d); use generate() per stream'
+            % max(net.R, net.D))
+    if net.filter_width > 2 or net.scalar_input:
+        raise NotImplementedError(
+            'generate_batch needs filter_width 2 and one-hot input '
+            '(model.py:597-603), as every fast generation path does; use '
+            'predict_proba (generate.py --fast_generation false)')
+    if net.S > 512 or net.Q > 512 or net.L > 64:
+        raise NotImplementedError(
+            'generate_batch supports at most 512 skip / quantization '
+            'channels and 64 layers; use generate() per stream')
+    s = [int(v) & (2**64 - 1) for v in seeds]
+    if not 1 <= len(s) <= net.FASTGEN_BATCH_MAX:
+        raise ValueError('generate_batch takes 1 to %d streams (one seed '
+                         'each), got %d' % (net.FASTGEN_BATCH_MAX, len(s)))
+    B = len(s)
+    rows = per_stream(B)
+    gc = global_condition
+    if gc is not None:
+        if isinstance(gc, torch.Tensor):
+            gc = gc.cpu().numpy()
+        gc = np.asarray(gc).reshape(-1)
+        if gc.size == 1:
+            gc = np.repeat(gc, B)
+        if gc.size != B:
+            raise ValueError('global_condition has %d ids for %d streams'
+                             % (gc.size, B))
+        gc = gc.astype(np.int32)
+    _check_temperature(temperature)
+    n = int(num_samples)
+    if n < 0:
+        raise ValueError('num_samples must be >= 0, got %d' % n)
+    net._check_supported()
+    return np.asarray(s, dtype=np.uint64).view(np.int64), rows, gc, n
+
+
+def _batch_codes(net, seed_samples, B):
+    """seed_samples -> int32 [B, n]: None (Q // 2 for every stream), one
+    sequence shared by all streams, or one row per stream."""
+    if seed_samples is None:
+        return np.full((B, 1), net.Q // 2, np.int32)
+    if isinstance(seed_samples, torch.Tensor):
+        seed_samples = seed_samples.cpu().numpy()
+    try:
+        a = np.asarray(seed_samples)
+    except ValueError:             # ragged rows
+        a = None
+    if a is None or a.dtype == object or a.ndim not in (1, 2):
+        raise ValueError('seed_samples must be None, one sequence shared '
+                         'by all streams, or [B, n]: the same number of '
+                         'seed codes for every stream')
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (B, a.shape[0]))
+    if a.shape[0] != B:
+        raise ValueError('seed_samples has %d rows for %d streams'
+                         % (a.shape[0], B))
+    if a.shape[1] < 1:
+        raise ValueError('seed_samples needs at least one code per stream')
+    return np.array(a, dtype=np.int32, order='C')   # (a writable copy)
+
+
+def _batch_last(last, B):
+    if isinstance(last, torch.Tensor):
+        last = last.cpu().numpy()
+    last = np.asarray(last, dtype=np.int32).reshape(-1)
+    if last.size != B:
+        raise ValueError('last_samples has %d codes for %d streams'
+                         % (last.size, B))
+    return last
+
+
+def batch_generator(net, B):
+    """Device state of the batched generator for B streams, separate from
+    the single-stream generator's (`_gen`): ring rows [sum d][Bp][32]."""
+    g = net._bgen
+    if g is not None and g['B'] == B:
+        return g
+    net._bgen = None
+    lib = _lib.load()
+    Bp = lib.wn_fastgen_batch_rows(B)
+    _lib.check(min(Bp, 0), 'wn_fastgen_batch_rows')
+    dil = np.asarray(net.dilations, dtype=np.int32)
+    nfl = lib.wn_fastgen_batch_state_floats(dil.ctypes.data, net.L, B)
+    _lib.check(int(min(nfl, 0)), 'wn_fastgen_batch_state_floats')
+    net._bgen = _new_state(
+        net, dil, nfl, Bp, B, B=B, Bp=Bp,
+        seeds=torch.zeros(B, dtype=torch.int64, device=net.device),
+        prev=torch.full((Bp,), -1, dtype=torch.int32, device=net.device))
+    return net._bgen
+
+
+def batch_reset(net, g):
+    _lib.call('wn_fastgen_batch_init', _lib.ptr(g['state']),
+              g['state'].numel(), _lib.ptr(g['cursors']),
+              _lib.ptr(g['prev']), g['B'], _lib.stream())
+    g['steps'] = 0
+
+
+def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
+                  proba_every, gc):
+    """Everything n_steps batched steps need before the first: the args of
+    wn_fastgen_batch_step (no stream) and the buffers batch_complete reads."""
+    B = g['B']
+    w, bias, bstride = _weights(net, g, gc, B)
+    g['seeds'].copy_(torch.from_numpy(seeds))
+    iob, pb = _stage(net, g, io, n_given, n_steps, temperature, proba,
+                     proba_every)
+    # past-tap pre-activations of the first step (every step then leaves
+    # the next step's behind)
+    _lib.call('wn_fastgen_batch_pre',
+              _lib.ptr(net._layer_block(net.params, 0)), net.layer_stride,
+              bias, bstride, _lib.ptr(g['dil']), net.L, B,
+              _lib.ptr(g['state']), _lib.ptr(g['cursors']),
+              _lib.ptr(g['pre']), _lib.stream())
+    args = w + (bias, bstride, _lib.ptr(g['dil']), net.L, net.S, net.Q, B,
+                _lib.ptr(g['state']), _lib.ptr(g['cursors']),
+                _lib.ptr(g['prev']), _lib.ptr(iob), _lib.ptr(g['ctl']),
+                _lib.ptr(g['seeds']), _lib.ptr(pb), 1 if net.use_biases else 0,
+                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
+                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
+    return dict(args=args, iob=iob, pb=pb)
+
+
+def batch_complete(net, g, prep, io, proba, n_steps):
+    """The last step's draw (every other one runs at the next step's
+    start), then the codes / probabilities back into io / proba."""
+    _lib.call('wn_fastgen_batch_finish', net.Q, g['B'],
+              _lib.ptr(g['cursors']), _lib.ptr(prep['iob']),
+              _lib.ptr(g['ctl']), _lib.ptr(g['seeds']), _lib.ptr(prep['pb']),
+              _lib.ptr(g['logits']), _lib.stream())
+    g['steps'] += int(n_steps)
+    io.copy_(prep['iob'][:io.numel()].view(io.shape))
+    if proba is not None:
+        proba.view(-1).copy_(prep['pb'][:proba.numel()])
+
+
+def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
+               proba_every):
+    # n_steps lock-step steps of all B streams on io [B, n_steps + 1]: five
+    # kernels per step, captured into a hipGraph once and replayed
+    prep = batch_prepare(net, g, io, n_given, n_steps, temperature, seeds,
+                         proba, proba_every, gc)
+    args = prep['args']
+    _replay_steps(net, g, args, lambda: _lib.call(
+        'wn_fastgen_batch_step', *args, _lib.stream()), n_steps)
+    batch_complete(net, g, prep, io, proba, n_steps)
+
+
+def generate_batch(net, num_samples, seeds, seed_samples, temperature,
+                   global_condition, return_proba_every):
+    sd, codes, gc, n = _batch_args(
+        net, seeds, functools.partial(_batch_codes, net, seed_samples),
+        global_condition, temperature, num_samples)
+    B, n_given = codes.shape
+    out = torch.zeros((B, n_given + n), dtype=torch.int32, device=net.device)
+    out[:, :n_given] = torch.from_numpy(codes).to(net.device)
+    g = batch_generator(net, B)
+    batch_reset(net, g)
+
+    def prime():
+        # ONE forward pass per distinct (seed, GC id): a stream's queues are
+        # bitwise those it gets alone, whatever B
+        batch_reset(net, g)
+        n0, groups = n_given - 1, {}
+        for b in range(B):
+            key = (codes[b, :n0].tobytes(), None if gc is None else int(gc[b]))
+            groups.setdefault(key, []).append(b)
+        _prime(net, g, n0, [
+            (torch.from_numpy(np.ascontiguousarray(codes[s[0], :n0])),
+             None if gc is None else gc[s[0]:s[0] + 1], s)
+            for s in groups.values()], g['Bp'])
+        g['cursors'][0] = n0
+        g['prev'][:B].copy_(torch.from_numpy(codes[:, n0 - 1].copy()))
+        g['steps'] = n0
+    pe = int(return_proba_every)
+    proba = _seeded(net, out, n_given, n, pe, prime, functools.partial(
+        _batch_run, net, g, temperature, sd, gc))
+    return (out, proba) if pe > 0 else out
+
+
+def continue_generation_batch(net, num_samples, last_samples, seeds,
+                              temperature, global_condition,
+                              return_proba_every):
+    sd, last, gc, n = _batch_args(
+        net, seeds, functools.partial(_batch_last, last_samples),
+        global_condition, temperature, num_samples)
+    B = len(sd)
+    g = net._bgen
+    if g is None or g['B'] != B:
+        raise RuntimeError('no batched generation of %d streams to '
+                           'continue: call generate_batch first' % B)
+    io = torch.zeros((B, n + 1), dtype=torch.int32, device=net.device)
+    io[:, 0] = torch.from_numpy(last).to(net.device)
+    pe = int(return_proba_every)
+    proba = _seeded(net, io, 1, n, pe, None,
+                    functools.partial(_batch_run, net, g, temperature, sd, gc))
+    return (io[:, 1:], proba) if pe > 0 else io[:, 1:]

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import fastgen
 from .ops import mu_law_encode, mu_law_decode, mu_law_tables
 
 CH = 32                      # channels per activation plane (one block)
@@ -1424,281 +1425,9 @@ class WaveNetModel(object):
         # expired: wrong probabilities are never returned silently
         return out + ws.loss_parts[0]
 
-    # ---------------------------------------------------------- fast generation
+    # ------------------------------------------ fast generation (fastgen.py)
     FASTGEN_MAX_CHANNELS = 1024    # wn_fastgen_run_wide (FGW_MAXC)
-
-    def _generator(self, global_condition):
-        """Device-resident incremental-generation state (_create_generator,
-        model.py:444-516): ring buffers standing in for the FIFO queues."""
-        if self.CHn > self.FASTGEN_MAX_CHANNELS:
-            raise NotImplementedError(
-                'fast (incremental) generation supports at most %d residual / '
-                'dilation channels on the HIP path; predict_proba (generate.py '
-                'without --fast_generation) has no such limit'
-                % self.FASTGEN_MAX_CHANNELS)
-        if self._gen is None:
-            lib = _lib.load()
-            dil = np.asarray(self.dilations, dtype=np.int32)
-            # (queue entries are rows of CHn = 32 * blocks floats)
-            nfl = lib.wn_fastgen_state_floats(dil.ctypes.data, self.L) * self.CB
-            g = dict(
-                state=torch.zeros(nfl, dtype=torch.float32, device=self.device),
-                # [0] steps done, [1] previous code, [2] draw pending
-                cursors=torch.zeros(4, dtype=torch.int32, device=self.device),
-                dil=torch.from_numpy(dil).to(self.device),
-                bias=torch.zeros((self.L, 1, 2 * self.CHn),
-                                 dtype=torch.float32, device=self.device),
-                bsum=torch.zeros(self.S, dtype=torch.float32,
-                                 device=self.device),
-                proba=torch.empty(self.Q, dtype=torch.float32,
-                                  device=self.device),
-                z_all=torch.zeros(self.L * CH, dtype=torch.float32,
-                                  device=self.device),
-                cw_img=torch.zeros(self.L * 3072, dtype=torch.float32,
-                                   device=self.device),
-                pre=torch.zeros(self.L * 64, dtype=torch.float32,
-                                device=self.device),
-                ctl=torch.zeros(8, dtype=torch.int32, device=self.device),
-                graphs={}, warm=False,
-                h1=torch.zeros(self.S, dtype=torch.float32,
-                               device=self.device),
-                h2=torch.zeros(self.S, dtype=torch.float32,
-                               device=self.device),
-                logits=torch.zeros(self.Q, dtype=torch.float32,
-                                   device=self.device),
-                steps=0,
-                io=torch.zeros(2, dtype=torch.int32, device=self.device))
-            self._gen = g
-            self._gen_reset()
-        return self._gen
-
-    def _gen_reset(self):
-        g = self._gen
-        _lib.call('wn_fastgen_init', _lib.ptr(g['state']), g['state'].numel(),
-                  _lib.ptr(g['cursors']), self.L, _lib.stream())
-        g['steps'] = 0
-
-    def _gen_run(self, samples_io, n_given, n_steps, temperature, seed,
-                 proba_out, proba_every, global_condition, push=True,
-                 multi_cu=False):
-        """Run `n_steps` generation steps.  multi_cu=False: ONE persistent
-        single-workgroup kernel (also the push=False peek).  multi_cu=True:
-        four kernels per step spread over many CUs, captured into a hipGraph
-        and replayed (config 5 throughput path)."""
-        # (wn_fastgen_step reads both from the device control block and cannot
-        # reject them; the reference applies the temperature as log(p) / T,
-        # generate.py:229-233)
-        if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
-            raise ValueError('temperature must be a finite number > 0, got %r'
-                             % (temperature,))
-        if int(n_given) < 1:
-            raise ValueError('n_given must be >= 1, got %r' % (n_given,))
-        g = self._generator(global_condition)
-        ids = self._gc_ids(global_condition, 1) if self.card is not None \
-            else None
-        bias, _ = self._bias_fg(g['bias'], ids, 1)
-        P = self.params
-        bsum = None
-        if self.use_biases:
-            _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), self.L,
-                      self.S, _lib.ptr(g['bsum']), _lib.stream())
-            bsum = g['bsum']
-        ub = self.use_biases
-        common = (_lib.ptr(self._seg(P, 'causal')),
-                  _lib.ptr(self._layer_block(P, 0)), self.layer_stride,
-                  _lib.ptr(self._seg(P, 'skip_w')), _lib.ptr(bsum),
-                  _lib.ptr(self._seg(P, 'post1_w')),
-                  _lib.ptr(self._seg(P, 'post1_b')) if ub else None,
-                  _lib.ptr(self._seg(P, 'post2_w')),
-                  _lib.ptr(self._seg(P, 'post2_b')) if ub else None,
-                  None if bias is None else _lib.ptr(bias), _lib.ptr(g['dil']),
-                  self.L, self.S, self.Q, _lib.ptr(g['state']),
-                  _lib.ptr(g['cursors']), _lib.ptr(samples_io))
-        sd = int(seed) & (2**64 - 1)
-        if self.CB > 1 or self.S > 512 or self.Q > 512 or self.L > 64:
-            # more than 32 channels, or more skip / quantization channels or
-            # layers than the tuned kernels hold in LDS (FG_MAXS / FG_MAXQ /
-            # FG_MAXL): the wide single-workgroup generator
-            # 64 channels: the cooperative launch (skip sum and post-processing
-            # on other CUs) when the library has one for the shape; it falls
-            # back to the single workgroup by itself when the workgroups would
-            # not all be resident
-            coop = None
-            if self.fastgen_wide_coop and not self._gen_launch_failed.get('coop'):
-                if 'coop' not in g:
-                    nb = _lib.load().wn_fastgen_wide_coop_bytes(
-                        self.L, self.CHn, self.S, self.Q)
-                    g['coop'] = torch.zeros(nb // 4, dtype=torch.int32,
-                                            device=self.device) if nb else None
-                coop = g['coop']
-
-            def run(scratch):
-                _lib.call('wn_fastgen_run_wide', *common[:11], self.L, self.CHn,
-                          self.S, self.Q, *common[14:], int(n_given), int(n_steps),
-                          float(temperature), sd, _lib.ptr(proba_out),
-                          int(proba_every), 1 if ub else 0, 1 if push else 0,
-                          _lib.ptr(scratch), _lib.stream())
-            if coop is None:
-                run(None)
-            else:
-                # What the library's residency check cannot see -- another
-                # process or stream holding CUs, a CU mask -- shows as an
-                # expired hand-over wait (word 12 of the scratch): the queues,
-                # cursors and samples are then restored from a snapshot taken
-                # here and the run is repeated by the single workgroup, which
-                # always completes.
-                snap = (g['state'].clone(), g['cursors'].clone(), samples_io.clone())
-                run(coop)
-                if int(coop[12]) != 0:     # (synchronises; the call ends on the host anyway)
-                    import warnings
-                    warnings.warn(
-                        'wn_fastgen_run_wide: a hand-over wait inside the '
-                        'cooperative generation launch expired (2 s: its '
-                        'workgroups were not all resident); state restored, '
-                        'continuing with the single workgroup '
-                        '(net.fastgen_wide_coop = False selects it up front)')
-                    g['state'].copy_(snap[0])
-                    g['cursors'].copy_(snap[1])
-                    samples_io.copy_(snap[2])
-                    # (remembered on the MODEL: a new generator on the same busy
-                    # device must not pay another expired wait)
-                    self._gen_launch_failed['coop'] = True
-                    run(None)
-                del snap
-            if push:
-                g['steps'] += int(n_steps)
-            return
-        if not multi_cu or not push:
-            _lib.call('wn_fastgen_run', *common, int(n_given), int(n_steps),
-                      float(temperature), sd, _lib.ptr(proba_out),
-                      int(proba_every), 1 if ub else 0, 1 if push else 0,
-                      _lib.stream())
-            if push:
-                g['steps'] += int(n_steps)
-            return
-        base = g['steps']
-        st = _lib.stream()
-        # weights are constant while generating: pack the chain blocks once,
-        # and compute the past-tap pre-activations of the first step (every
-        # step then leaves the next step's behind)
-        _lib.call('wn_fastgen_pack', _lib.ptr(self._layer_block(P, 0)),
-                  self.layer_stride, _lib.ptr(g['cw_img']), self.L, st)
-        _lib.call('wn_fastgen_pre', _lib.ptr(self._layer_block(P, 0)),
-                  self.layer_stride, None if bias is None else _lib.ptr(bias),
-                  _lib.ptr(g['dil']), self.L, _lib.ptr(g['state']),
-                  _lib.ptr(g['cursors']), _lib.ptr(g['pre']), st)
-        # per-call values live in device memory (ctl) and in two persistent
-        # buffers (codes, probabilities), so a captured graph holds nothing
-        # that changes between calls and is reused
-        n_io = int(n_steps) + 1
-        pe = max(1, int(proba_every))
-        io = self._gen_buf('io_buf', n_io, torch.int32)
-        io[:n_io].copy_(samples_io[:n_io])
-        pb = None
-        if proba_out is not None:
-            rows = (int(n_steps) + pe - 1) // pe
-            pb = self._gen_buf('proba_buf', rows * self.Q, torch.float32)
-        ctl = np.zeros(8, np.uint32)
-        ctl[0], ctl[1], ctl[2] = base, int(n_given), pe
-        ctl[3] = np.float32(temperature).view(np.uint32)
-        ctl[4], ctl[5] = sd & 0xffffffff, sd >> 32
-        g['ctl'].copy_(torch.from_numpy(ctl.view(np.int32)))
-        common = common[:-1] + (_lib.ptr(io),)
-        tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), 1 if ub else 0,
-                _lib.ptr(g['cw_img']), _lib.ptr(g['pre']), _lib.ptr(g['z_all']),
-                _lib.ptr(g['h1']), _lib.ptr(g['h2']), _lib.ptr(g['logits']))
-
-        lib = _lib.load()
-        if self.fastgen_persistent and not self._gen_launch_failed.get('persist'):
-            # ONE persistent launch for the run.  Every workgroup has to be
-            # resident at once; the library checks that against the launch
-            # configuration's occupancy (WN_ERR_UNSUPPORTED: the step kernels
-            # below).  What it cannot see -- another process or stream holding
-            # CUs, a CU mask -- shows as an expired hand-over wait (sync[12]):
-            # the generator's state is then restored from a snapshot taken
-            # here and the run falls through to the step kernels, which always
-            # complete; `steps` advances only after a successful run.
-            sync = self._gen_buf('fgp_sync', 16, torch.int32)
-            ll = self._gen_buf('fgp_ll', int(lib.wn_fastgen_persist_ll_words(
-                self.L, self.S, self.Q)), torch.int64)
-            snap = (g['state'].clone(), g['cursors'].clone(), g['pre'].clone())
-            code = lib.wn_fastgen_persist(*common, *tail, _lib.ptr(sync),
-                                          _lib.ptr(ll), int(n_steps), _lib.stream())
-            if code == 0:
-                if int(sync[12]) == 0:   # (synchronises; a generation call ends on the host anyway)
-                    g['steps'] += int(n_steps)
-                    samples_io[:n_io].copy_(io[:n_io])
-                    if proba_out is not None:
-                        proba_out.view(-1).copy_(pb[:proba_out.numel()])
-                    return
-                import warnings
-                warnings.warn(
-                    'wn_fastgen_persist: a hand-over wait inside the persistent '
-                    'generation launch expired (2 s: its workgroups were not all '
-                    'resident); state restored, continuing with the step kernels '
-                    '(net.fastgen_persistent = False selects them up front)')
-                g['state'].copy_(snap[0])
-                g['cursors'].copy_(snap[1])
-                g['pre'].copy_(snap[2])
-                io[:n_io].copy_(samples_io[:n_io])
-                self._gen_launch_failed['persist'] = True
-            elif code != -2:             # WN_ERR_UNSUPPORTED: not resident / shape
-                _lib.check(code, 'wn_fastgen_persist')
-            del snap
-
-        self._replay_steps(g, (common, tail), lambda: _lib.call(
-            'wn_fastgen_step', *common, *tail, _lib.stream()), n_steps)
-        # the last step's draw (every other one ran inside the next step)
-        _lib.call('wn_fastgen_finish', self.Q, _lib.ptr(g['cursors']),
-                  _lib.ptr(io), _lib.ptr(g['ctl']), _lib.ptr(pb),
-                  _lib.ptr(g['logits']), _lib.stream())
-        g['steps'] += int(n_steps)
-        samples_io[:n_io].copy_(io[:n_io])
-        if proba_out is not None:
-            proba_out.view(-1).copy_(pb[:proba_out.numel()])
-
-    def _replay_steps(self, g, key, one, n_steps):
-        """n_steps calls of one() (a step's launches) for generator dict g:
-        the first step g ever runs outside any capture, then hipGraphs of
-        fastgen_graph_steps and of a tenth of that many steps, captured once
-        per (key, length) and replayed, then single steps.  key must hold
-        every pointer and value the launches were given."""
-        def graph_of(nsteps):
-            gr = g['graphs'].get((key, nsteps))
-            if gr is None:
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr):
-                    for _ in range(nsteps):
-                        one()
-                if len(g['graphs']) > 8:
-                    g['graphs'].clear()
-                g['graphs'][key, nsteps] = gr
-            return gr
-        done = 0
-        if not g['warm']:
-            one()                      # module load etc. outside any capture
-            done, g['warm'] = 1, True
-        for per in (int(self.fastgen_graph_steps),
-                    max(1, int(self.fastgen_graph_steps) // 10)):
-            if per > 1 and n_steps - done >= per:
-                gr = graph_of(per)
-                while n_steps - done >= per:
-                    gr.replay()
-                    done += per
-        for _ in range(n_steps - done):
-            one()
-
-    def _gen_buf(self, name, n, dtype):
-        """Persistent per-generator buffer of at least n elements (grown
-        geometrically; growing drops the captured graphs, which hold its
-        address)."""
-        g = self._gen
-        buf = g.get(name)
-        if buf is None or buf.numel() < n:
-            cap = max(int(n), 2 * (buf.numel() if buf is not None else 0), 4096)
-            g[name] = buf = torch.zeros(cap, dtype=dtype, device=self.device)
-            g['graphs'].clear()
-        return buf
+    FASTGEN_BATCH_MAX = 256        # wn_fastgen_batch_* (FGB_MAXB)
 
     def predict_proba_incremental(self, waveform, global_condition=None,
                                   name='wavenet', push=True):
@@ -1707,27 +1436,13 @@ class WaveNetModel(object):
         samples (model.py:592-626).  Eager counterpart of running the
         reference's proba op together with `net.push_ops` (push=True) or
         alone (push=False); `net.reset_generator()` is `net.init_ops`.'''
-        if self.filter_width > 2:
-            raise NotImplementedError("Incremental generation does not "
-                                      "support filter_width > 2.")
-        if self.scalar_input:
-            raise NotImplementedError("Scalar input is not supported by "
-                                      "fast generation.")
-        self._check_supported()
-        g = self._generator(global_condition)
-        w = waveform
-        if isinstance(w, torch.Tensor):
-            g['io'][0:1].copy_(w.reshape(-1)[-1:].to(torch.int32))
-        else:
-            g['io'][0] = int(np.asarray(w).reshape(-1)[-1])
-        self._gen_run(g['io'], 1, 1, 1.0, 0, g['proba'], 1, global_condition,
-                      push=push)
-        return g['proba'].clone()
+        return fastgen.predict_proba_incremental(self, waveform,
+                                                 global_condition, push)
 
     def reset_generator(self):
         """net.init_ops: refill every queue with zeros (model.py:457-479)."""
-        self._generator(None)
-        self._gen_reset()
+        fastgen.generator(self, None)
+        fastgen.reset(self)
 
     def generate(self, num_samples, seed_samples=None, temperature=1.0,
                  global_condition=None, seed=0, return_proba_every=0):
@@ -1736,38 +1451,8 @@ class WaveNetModel(object):
         test_model.py:63), then draw `num_samples` samples with temperature.
         Returns int32 codes [len(seed) + num_samples] (and the probabilities
         of every `return_proba_every`-th step when requested)."""
-        self._check_supported()
-        if self.filter_width > 2 or self.scalar_input:
-            raise NotImplementedError('fast generation needs filter_width 2 '
-                                      'and one-hot input (model.py:597-603)')
-        if seed_samples is None:
-            seed_samples = [self.Q // 2]
-        s = torch.as_tensor(np.asarray(seed_samples), dtype=torch.int32).reshape(-1)
-        n_given = int(s.numel())
-        n_steps = n_given - 1 + int(num_samples)
-        io = torch.zeros(n_steps + 1, dtype=torch.int32, device=self.device)
-        io[:n_given] = s.to(self.device)
-        self.reset_generator()
-        pe = int(return_proba_every)
-        proba = None
-        if pe > 0:
-            proba = torch.empty(((n_steps + pe - 1) // pe, self.Q),
-                                dtype=torch.float32, device=self.device)
-        if pe == 0 and n_given - 1 >= self.fastgen_prime_forward_min and \
-                int(num_samples) > 0:
-            # the reference's own TODO (generate.py:199-201): fill the queues
-            # from a forward pass over the seed instead of stepping through it
-            self.prime_generator(io[:n_given - 1], global_condition)
-            io2 = io[n_given - 1:].clone()     # [last seed | generated ...]
-            self._gen_run(io2, 1, int(num_samples), temperature, seed, None,
-                          1, global_condition, multi_cu=self.fastgen_multi_cu)
-            io[n_given - 1:] = io2
-        elif n_steps > 0:
-            self._gen_run(io, n_given, n_steps, temperature, seed, proba,
-                          pe if pe > 0 else 1, global_condition,
-                          multi_cu=self.fastgen_multi_cu)
-        out = io[:n_given + int(num_samples)]
-        return (out, proba) if pe > 0 else out
+        return fastgen.generate(self, num_samples, seed_samples, temperature,
+                                global_condition, seed, return_proba_every)
 
     def prime_generator(self, codes, global_condition=None):
         """Set the incremental-generation queues to the state they have after
@@ -1775,300 +1460,15 @@ class WaveNetModel(object):
         ONE batch forward pass: layer l's queue (capacity d_l) holds the last
         d_l inputs x_l[t] of that layer (model.py:473-484), which are rows of
         the forward pass's per-layer activation planes."""
-        if self.filter_width > 2 or self.scalar_input:
-            raise NotImplementedError('fast generation needs filter_width 2 '
-                                      'and one-hot input (model.py:597-603)')
-        self._check_supported()
-        g = self._generator(global_condition)
-        self._gen_reset()
-        w = torch.as_tensor(codes).to(device=self.device,
-                                      dtype=torch.int32).reshape(-1)
-        n0 = int(w.numel())
-        if n0 == 0:
-            return
-        ws = self._workspace(1, n0, False)
-        ws.q.copy_(w)
-        ids = self._gc_ids(global_condition, 1)
-        self._forward(ws, ids, save_ts=0)
-        # a queue entry is a row of CB 32-wide blocks; block cb of layer l's
-        # input is activation plane l * CB + cb
-        CB = self.CB
-        src, dst, roff = [], [], 0
-        for l, d in enumerate(self.dilations):
-            t = np.arange(max(0, n0 - d), n0, dtype=np.int64)
-            for cb in range(CB):
-                src.append((l * CB + cb) * n0 + t)
-                dst.append((roff + t % d) * CB + cb)
-            roff += d
-        src = torch.from_numpy(np.concatenate(src)).to(self.device)
-        dst = torch.from_numpy(np.concatenate(dst)).to(self.device)
-        X = ws.X.reshape(-1, CH)[:self.L * CB * n0]
-        # (+ the forward launch's poison word: 0, or NaN after an expired wait)
-        g['state'].view(-1, CH).index_copy_(
-            0, dst, X.index_select(0, src) + ws.loss_parts[0])
-        g['cursors'][0] = n0
-        g['cursors'][1:2].copy_(w[-1:])
-        g['steps'] = n0
+        fastgen.prime(self, codes, global_condition)
 
     def continue_generation(self, num_samples, last_sample, temperature=1.0,
                             global_condition=None, seed=0):
         """Draw `num_samples` more samples after `generate` (the queues stay
         on the device; `last_sample` is the last code drawn so far, which has
         not been pushed yet).  Returns the new int32 codes."""
-        self._check_supported()
-        n = int(num_samples)
-        io = torch.zeros(n + 1, dtype=torch.int32, device=self.device)
-        io[0] = int(last_sample)
-        self._gen_run(io, 1, n, temperature, seed, None, 1, global_condition,
-                      multi_cu=self.fastgen_multi_cu)
-        return io[1:]
-
-    # ------------------------------------------------ batched fast generation
-    FASTGEN_BATCH_MAX = 256        # wn_fastgen_batch_* (FGB_MAXB)
-
-    def _batch_gen_check(self):
-        """The shapes wn_fastgen_batch_step covers (those of the single-stream
-        step kernels), checked before anything touches a device."""
-        if self.CB > 1:
-            raise NotImplementedError(
-                'generate_batch supports at most 32 residual / dilation '
-                'channels (this model has %d); use generate() per stream'
-                % max(self.R, self.D))
-        if self.filter_width > 2 or self.scalar_input:
-            raise NotImplementedError(
-                'generate_batch needs filter_width 2 and one-hot input '
-                '(model.py:597-603), as every fast generation path does; use '
-                'predict_proba (generate.py --fast_generation false)')
-        if self.S > 512 or self.Q > 512 or self.L > 64:
-            raise NotImplementedError(
-                'generate_batch supports at most 512 skip / quantization '
-                'channels and 64 layers; use generate() per stream')
-
-    def _batch_seeds(self, seeds):
-        """One 64-bit draw seed per stream -> int64 array (bit pattern)."""
-        s = [int(v) & (2**64 - 1) for v in seeds]
-        if not 1 <= len(s) <= self.FASTGEN_BATCH_MAX:
-            raise ValueError('generate_batch takes 1 to %d streams (one seed '
-                             'each), got %d' % (self.FASTGEN_BATCH_MAX, len(s)))
-        return np.asarray(s, dtype=np.uint64).view(np.int64)
-
-    def _batch_codes(self, seed_samples, B):
-        """seed_samples -> int32 [B, n]: None (Q // 2 for every stream), one
-        sequence shared by all streams, or one row per stream."""
-        if seed_samples is None:
-            return np.full((B, 1), self.Q // 2, np.int32)
-        if isinstance(seed_samples, torch.Tensor):
-            seed_samples = seed_samples.cpu().numpy()
-        try:
-            a = np.asarray(seed_samples)
-        except ValueError:             # ragged rows
-            a = None
-        if a is None or a.dtype == object or a.ndim not in (1, 2):
-            raise ValueError('seed_samples must be None, one sequence shared '
-                             'by all streams, or [B, n]: the same number of '
-                             'seed codes for every stream')
-        if a.ndim == 1:
-            a = np.broadcast_to(a, (B, a.shape[0]))
-        if a.shape[0] != B:
-            raise ValueError('seed_samples has %d rows for %d streams'
-                             % (a.shape[0], B))
-        if a.shape[1] < 1:
-            raise ValueError('seed_samples needs at least one code per stream')
-        return np.array(a, dtype=np.int32, order='C')   # (a writable copy)
-
-    def _batch_gc(self, global_condition, B):
-        """None, one id shared by all streams, or B ids -> int32 [B] / None."""
-        if global_condition is None:
-            return None
-        g = global_condition
-        if isinstance(g, torch.Tensor):
-            g = g.cpu().numpy()
-        g = np.asarray(g).reshape(-1)
-        if g.size == 1:
-            g = np.repeat(g, B)
-        if g.size != B:
-            raise ValueError('global_condition has %d ids for %d streams'
-                             % (g.size, B))
-        return g.astype(np.int32)
-
-    @staticmethod
-    def _check_temperature(temperature):
-        if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
-            raise ValueError('temperature must be a finite number > 0, got %r'
-                             % (temperature,))
-
-    def _batch_generator(self, B):
-        """Device state of the batched generator for B streams, separate from
-        the single-stream generator's (`_gen`): ring rows [sum d][Bp][32]."""
-        g = self._bgen
-        if g is not None and g['B'] == B:
-            return g
-        self._bgen = None
-        lib = _lib.load()
-        Bp = lib.wn_fastgen_batch_rows(B)
-        _lib.check(min(Bp, 0), 'wn_fastgen_batch_rows')
-        dil = np.asarray(self.dilations, dtype=np.int32)
-        nfl = lib.wn_fastgen_batch_state_floats(dil.ctypes.data, self.L, B)
-        _lib.check(int(min(nfl, 0)), 'wn_fastgen_batch_state_floats')
-        f32 = dict(dtype=torch.float32, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
-        g = dict(
-            B=B, Bp=Bp,
-            state=torch.zeros(nfl, **f32),
-            # [0] steps pushed, [1] draw pending
-            cursors=torch.zeros(4, **i32),
-            prev=torch.full((Bp,), -1, **i32),
-            dil=torch.from_numpy(dil).to(self.device),
-            bias=torch.zeros(self.L * B * 2 * CH, **f32),
-            bsum=torch.zeros(self.S, **f32),
-            seeds=torch.zeros(B, dtype=torch.int64, device=self.device),
-            ctl=torch.zeros(8, **i32),
-            pre=torch.zeros(self.L * Bp * 2 * CH, **f32),
-            z_all=torch.zeros(Bp * self.L * CH, **f32),
-            h1=torch.zeros(Bp * self.S, **f32),
-            h2=torch.zeros(Bp * self.S, **f32),
-            logits=torch.zeros(Bp * self.Q, **f32),
-            graphs={}, warm=False, steps=0)
-        self._bgen = g
-        return g
-
-    def _batch_reset(self, g):
-        _lib.call('wn_fastgen_batch_init', _lib.ptr(g['state']),
-                  g['state'].numel(), _lib.ptr(g['cursors']),
-                  _lib.ptr(g['prev']), g['B'], _lib.stream())
-        g['steps'] = 0
-
-    def _batch_buf(self, g, name, n, dtype):
-        """Persistent buffer of the batched generator (grown geometrically;
-        growing drops the captured graphs, which hold its address)."""
-        buf = g.get(name)
-        if buf is None or buf.numel() < n:
-            cap = max(int(n), 2 * (buf.numel() if buf is not None else 0), 4096)
-            g[name] = buf = torch.zeros(cap, dtype=dtype, device=self.device)
-            g['graphs'].clear()
-        return buf
-
-    def _batch_prepare(self, g, io, n_given, n_steps, temperature, seeds,
-                       proba, proba_every, gc):
-        """Everything a sequence of n_steps batched steps needs before the
-        first: GC / filter-gate bias, control block, io / probability
-        buffers, the first step's past-tap pre-activations.  Returns the
-        argument tuple of wn_fastgen_batch_step (without the stream) and the
-        buffers _batch_complete reads back."""
-        B, Q = g['B'], self.Q
-        P = self.params
-        st = _lib.stream()
-        ids = self._gc_ids(gc, B)
-        bias, bstride = self._bias_fg(g['bias'], ids, B)
-        bsum = None
-        if self.use_biases:
-            _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), self.L,
-                      self.S, _lib.ptr(g['bsum']), st)
-            bsum = g['bsum']
-        ub = self.use_biases
-        g['seeds'].copy_(torch.from_numpy(seeds))
-        ld = int(n_steps) + 1
-        pe = max(1, int(proba_every))
-        rows = (int(n_steps) + pe - 1) // pe if proba is not None else 0
-        iob = self._batch_buf(g, 'io_buf', B * ld, torch.int32)
-        iob[:B * ld].view(B, ld).copy_(io)
-        pb = None
-        if proba is not None:
-            pb = self._batch_buf(g, 'proba_buf', B * rows * Q, torch.float32)
-        ctl = np.zeros(8, np.uint32)
-        ctl[0], ctl[1], ctl[2] = g['steps'], int(n_given), pe
-        ctl[3] = np.float32(temperature).view(np.uint32)
-        ctl[4], ctl[5] = ld, rows
-        g['ctl'].copy_(torch.from_numpy(ctl.view(np.int32)))
-        layer0 = _lib.ptr(self._layer_block(P, 0))
-        bptr = None if bias is None else _lib.ptr(bias)
-        # past-tap pre-activations of the first step (every step then leaves
-        # the next step's behind)
-        _lib.call('wn_fastgen_batch_pre', layer0, self.layer_stride, bptr,
-                  bstride, _lib.ptr(g['dil']), self.L, B, _lib.ptr(g['state']),
-                  _lib.ptr(g['cursors']), _lib.ptr(g['pre']), st)
-        args = (_lib.ptr(self._seg(P, 'causal')), layer0, self.layer_stride,
-                _lib.ptr(self._seg(P, 'skip_w')), _lib.ptr(bsum),
-                _lib.ptr(self._seg(P, 'post1_w')),
-                _lib.ptr(self._seg(P, 'post1_b')) if ub else None,
-                _lib.ptr(self._seg(P, 'post2_w')),
-                _lib.ptr(self._seg(P, 'post2_b')) if ub else None,
-                bptr, bstride, _lib.ptr(g['dil']), self.L, self.S, Q, B,
-                _lib.ptr(g['state']), _lib.ptr(g['cursors']),
-                _lib.ptr(g['prev']), _lib.ptr(iob), _lib.ptr(g['ctl']),
-                _lib.ptr(g['seeds']), _lib.ptr(pb), 1 if ub else 0,
-                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
-                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
-        return dict(args=args, iob=iob, pb=pb, ld=ld, rows=rows)
-
-    def _batch_complete(self, g, prep, io, proba, n_steps):
-        """The last step's draw (every other one runs at the next step's
-        start), then the codes / probabilities back into io / proba."""
-        B, Q = g['B'], self.Q
-        iob, pb, ld, rows = prep['iob'], prep['pb'], prep['ld'], prep['rows']
-        _lib.call('wn_fastgen_batch_finish', Q, B, _lib.ptr(g['cursors']),
-                  _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(g['seeds']),
-                  _lib.ptr(pb), _lib.ptr(g['logits']), _lib.stream())
-        g['steps'] += int(n_steps)
-        io.copy_(iob[:B * ld].view(B, ld))
-        if proba is not None:
-            proba.copy_(pb[:B * rows * Q].view(B, rows, Q))
-
-    def _batch_run(self, g, io, n_given, n_steps, temperature, seeds, proba,
-                   proba_every, gc):
-        """n_steps lock-step steps of all B streams: io int32 [B, n_steps + 1]
-        (the first n_given codes of every row are given, the rest drawn);
-        proba float32 [B, rows, Q] or None.  Five kernels per step, captured
-        into a hipGraph once and replayed (per-call values live in `ctl`)."""
-        prep = self._batch_prepare(g, io, n_given, n_steps, temperature, seeds,
-                                   proba, proba_every, gc)
-        args = prep['args']
-
-        self._replay_steps(g, args, lambda: _lib.call(
-            'wn_fastgen_batch_step', *args, _lib.stream()), n_steps)
-        self._batch_complete(g, prep, io, proba, n_steps)
-
-    def _batch_prime(self, g, codes, gc):
-        """prime_generator for all B streams: the queues after codes [B, n0]
-        (host int32) were pushed one by one.  ONE batch-1 forward pass per
-        distinct (seed, GC id) -- a seed shared by all streams is one pass --
-        whose ring rows go to every stream that has it.  A stream's queues are
-        then bitwise those it gets alone, or from prime_generator, whatever B,
-        and the forward's workspace is one seed long whatever B."""
-        B, Bp = g['B'], g['Bp']
-        self._batch_reset(g)
-        n0 = int(codes.shape[1])
-        groups = {}
-        for b in range(B):
-            key = (codes[b].tobytes(), None if gc is None else int(gc[b]))
-            groups.setdefault(key, []).append(b)
-        ws = self._workspace(1, n0, False)
-        X = ws.X.reshape(-1, CH)[:self.L * n0]
-        # layer l's queue holds x_l[t] for the last d_l steps: activation
-        # plane l, row t -> ring entry roff_l + t % d_l (row b of the entry)
-        src, ent, roff = [], [], 0
-        for l, d in enumerate(self.dilations):
-            t = np.arange(max(0, n0 - d), n0, dtype=np.int64)
-            src.append(l * n0 + t)
-            ent.append(roff + t % d)
-            roff += d
-        src = torch.from_numpy(np.concatenate(src)).to(self.device)
-        ent = np.concatenate(ent)
-        state = g['state'].view(-1, CH)
-        for rows in groups.values():
-            b0 = rows[0]
-            ws.q.copy_(torch.from_numpy(np.ascontiguousarray(codes[b0])))
-            ids = self._gc_ids(None if gc is None else gc[b0:b0 + 1], 1)
-            self._forward(ws, ids, save_ts=0)
-            # (+ the forward launch's poison word: 0, or NaN after an
-            # expired wait)
-            vals = X.index_select(0, src) + ws.loss_parts[0]
-            dst = (ent[None, :] * Bp + np.asarray(rows, np.int64)[:, None])
-            state.index_copy_(0, torch.from_numpy(dst.reshape(-1)).to(
-                self.device), vals.repeat(len(rows), 1))
-        g['cursors'][0] = n0
-        g['prev'][:B].copy_(torch.from_numpy(np.ascontiguousarray(codes[:, -1])))
-        g['steps'] = n0
+        return fastgen.continue_generation(self, num_samples, last_sample,
+                                           temperature, global_condition, seed)
 
     def generate_batch(self, num_samples, seeds, seed_samples=None,
                        temperature=1.0, global_condition=None,
@@ -2081,37 +1481,9 @@ class WaveNetModel(object):
         shared by all streams, or [B, n]; global_condition: None, one id, or
         B ids.  Returns int32 [B, n + num_samples] (and float32
         [B, ceil(steps / k), Q] probabilities with return_proba_every = k)."""
-        self._batch_gen_check()
-        sd = self._batch_seeds(seeds)
-        B = len(sd)
-        codes = self._batch_codes(seed_samples, B)
-        gc = self._batch_gc(global_condition, B)
-        self._check_temperature(temperature)
-        n = int(num_samples)
-        if n < 0:
-            raise ValueError('num_samples must be >= 0, got %d' % n)
-        self._check_supported()
-        n_given = codes.shape[1]
-        n_steps = n_given - 1 + n
-        out = torch.zeros((B, n_given + n), dtype=torch.int32,
-                          device=self.device)
-        out[:, :n_given] = torch.from_numpy(codes).to(self.device)
-        pe = int(return_proba_every)
-        proba = None
-        if pe > 0:
-            proba = torch.empty((B, (n_steps + pe - 1) // pe, self.Q),
-                                dtype=torch.float32, device=self.device)
-        g = self._batch_generator(B)
-        self._batch_reset(g)
-        if pe == 0 and n_given - 1 >= self.fastgen_prime_forward_min and n > 0:
-            self._batch_prime(g, codes[:, :n_given - 1], gc)
-            tail = out[:, n_given - 1:].contiguous()   # [last seed | drawn ...]
-            self._batch_run(g, tail, 1, n, temperature, sd, None, 1, gc)
-            out[:, n_given - 1:] = tail
-        elif n_steps > 0:
-            self._batch_run(g, out, n_given, n_steps, temperature, sd, proba,
-                            pe, gc)
-        return (out, proba) if pe > 0 else out
+        return fastgen.generate_batch(self, num_samples, seeds, seed_samples,
+                                      temperature, global_condition,
+                                      return_proba_every)
 
     def continue_generation_batch(self, num_samples, last_samples, seeds,
                                   temperature=1.0, global_condition=None,
@@ -2120,33 +1492,6 @@ class WaveNetModel(object):
         generate_batch call (the queues stay on the device; last_samples[b]
         is stream b's last code so far, not yet pushed).  Returns int32
         [B, num_samples] (and the probabilities, as generate_batch)."""
-        self._batch_gen_check()
-        sd = self._batch_seeds(seeds)
-        B = len(sd)
-        last = last_samples
-        if isinstance(last, torch.Tensor):
-            last = last.cpu().numpy()
-        last = np.asarray(last, dtype=np.int32).reshape(-1)
-        if last.size != B:
-            raise ValueError('last_samples has %d codes for %d streams'
-                             % (last.size, B))
-        gc = self._batch_gc(global_condition, B)
-        self._check_temperature(temperature)
-        n = int(num_samples)
-        if n < 0:
-            raise ValueError('num_samples must be >= 0, got %d' % n)
-        self._check_supported()
-        g = self._bgen
-        if g is None or g['B'] != B:
-            raise RuntimeError('no batched generation of %d streams to '
-                               'continue: call generate_batch first' % B)
-        io = torch.zeros((B, n + 1), dtype=torch.int32, device=self.device)
-        io[:, 0] = torch.from_numpy(last).to(self.device)
-        pe = int(return_proba_every)
-        proba = None
-        if pe > 0:
-            proba = torch.empty((B, (n + pe - 1) // pe, self.Q),
-                                dtype=torch.float32, device=self.device)
-        if n > 0:
-            self._batch_run(g, io, 1, n, temperature, sd, proba, pe, gc)
-        return (io[:, 1:], proba) if pe > 0 else io[:, 1:]
+        return fastgen.continue_generation_batch(
+            self, num_samples, last_samples, seeds, temperature,
+            global_condition, return_proba_every)

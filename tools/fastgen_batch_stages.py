@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import WaveNetModel, _lib  # noqa: E402
+from wavenet import WaveNetModel, _lib, fastgen  # noqa: E402
 from util import model_kwargs  # noqa: E402
 
 STAGES = ('draw', 'chain', 'skip_pre', 'post1', 'logits')
@@ -38,10 +38,10 @@ for B in Bs:
     e1.synchronize()
     graph_us = e0.elapsed_time(e1) * 1e3 / n
     # the same steps, one launch at a time between events
-    g = net._batch_generator(B)
-    net._batch_reset(g)
+    g = fastgen.batch_generator(net, B)
+    fastgen.batch_reset(net, g)
     io = torch.full((B, n + 1), net.Q // 2, dtype=torch.int32, device=net.device)
-    prep = net._batch_prepare(g, io, 1, n, 1.0, seeds, None, 1, None)
+    prep = fastgen.batch_prepare(net, g, io, 1, n, 1.0, seeds, None, 1, None)
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(6)] for _ in range(n)]
     st = _lib.stream()
     for i in range(n):
@@ -50,7 +50,7 @@ for B in Bs:
             _lib.call('wn_fastgen_batch_stages', k, k + 1, *prep['args'], st)
         ev[i][5].record()
     torch.cuda.synchronize()
-    net._batch_complete(g, prep, io, None, n)
+    fastgen.batch_complete(net, g, prep, io, None, n)
     same = bool(torch.equal(io, ref))
     t = np.array([[ev[i][k].elapsed_time(ev[i][k + 1]) * 1e3 for k in range(5)]
                   for i in range(50, n)])
