@@ -7,6 +7,13 @@ kernel (`WaveNetModel.generate`): priming with a --wav_seed (generate.py:195-210
 one step per seed sample) and temperature sampling happen on the device.
 --fast_generation false uses the windowed naive path (`predict_proba`, host-side
 np.random.choice) like the reference.  wav I/O is scipy (librosa is absent).
+
+Local conditioning (naive path only): --lc_path features.npy [frames, Lc] are
+upsampled by repetition (--lc_hop samples per frame) and ONE sample is
+generated per upsampled row after the seed (--samples is ignored).  Row k sits
+beside generated sample k, as in training (the row beside input sample t
+conditions the prediction of sample t + 1); the seed's rows are zeros.  Each
+window passes its own rows to predict_proba.
 """
 from __future__ import division
 from __future__ import print_function
@@ -69,6 +76,11 @@ def get_arguments(argv=None):
                    help='independent clips generated together (fast path); '
                    'clip i draws with --seed + i and is written to '
                    '<stem>_<i><ext>')
+    p.add_argument('--lc_path', type=str, default=None,
+                   help='local conditioning features (.npy, [frames, '
+                   'channels]); needs --fast_generation false')
+    p.add_argument('--lc_hop', type=int, default=1,
+                   help='audio samples per feature frame of --lc_path')
     p.add_argument('--gc_ids', type=str, default=None,
                    help='comma-separated global condition ids, one clip each '
                    '(sets --clips to their number)')
@@ -120,6 +132,22 @@ def create_seed(filename, sample_rate, quantization_channels,
 
 def main(argv=None):
     args = get_arguments(argv)
+    lc_rows = None
+    if args.lc_path is not None:
+        if args.fast_generation:
+            print('Local conditioning (--lc_path) needs the naive path: '
+                  'pass --fast_generation false (fast generation with local '
+                  'conditioning is not supported yet).')
+            return 1
+        from wavenet.audio_reader import upsample_lc
+        feats = np.load(args.lc_path)
+        if feats.ndim != 2 or feats.shape[0] == 0 or args.lc_hop <= 0:
+            print('--lc_path must hold [frames, channels] features and '
+                  '--lc_hop must be positive')
+            return 1
+        lc_rows = upsample_lc(feats, args.lc_hop,
+                              feats.shape[0] * args.lc_hop)
+        args.samples = lc_rows.shape[0]
     from wavenet import WaveNetModel, mu_law_decode
     started = "{0:%Y-%m-%dT%H-%M-%S}".format(datetime.now())
     logdir = os.path.join(args.logdir, 'generate', started)
@@ -138,7 +166,8 @@ def main(argv=None):
         initial_filter_width=wavenet_params['initial_filter_width'],
         global_condition_channels=args.gc_channels,
         global_condition_cardinality=args.gc_cardinality,
-        residual_postproc=wavenet_params.get("residual_postproc", False))
+        residual_postproc=wavenet_params.get("residual_postproc", False),
+        local_condition_channels=None if lc_rows is None else lc_rows.shape[1])
     print('Restoring model from {}'.format(args.checkpoint))
     if tf_checkpoint.checkpoint_format(args.checkpoint):
         # a checkpoint written by the reference itself (tf.train.Saver)
@@ -192,10 +221,23 @@ def main(argv=None):
         # one workspace for the whole window: the growing inputs of the first
         # `window` steps are views of it
         net.reserve(1, min(args.window, len(waveform) + args.samples))
+        lc_full = None
+        if lc_rows is not None:
+            # row of every input position: zeros beside the seed, feature row
+            # k beside generated sample k
+            n0 = len(waveform)
+            lc_full = np.zeros((n0 + args.samples, lc_rows.shape[1]),
+                               np.float32)
+            lc_full[n0:] = lc_rows
         for step in range(args.samples):
             window = waveform[-args.window:] if len(waveform) > args.window \
                 else waveform
-            prediction = net.predict_proba(np.asarray(window), gc
+            lc = None
+            if lc_full is not None:
+                e = len(waveform)
+                lc = lc_full[e - len(window):e][None]
+            prediction = net.predict_proba(np.asarray(window), gc,
+                                           local_condition=lc
                                            ).cpu().numpy().astype(np.float64)
             # temperature (generate.py:229-233)
             with np.errstate(divide='ignore'):

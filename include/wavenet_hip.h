@@ -286,6 +286,18 @@ int wn_stack_fwd_skip(float* X, float* Z, float* SG, const float* wimg,
                       unsigned* ctl, float* poison, int L, int B, int T, int save_sg,
                       int variant, const float* skip_img, const float* skip_bsum,
                       float* h1, void* stream);
+/* Local conditioning: wn_stack_fwd where row r of layer l ALSO adds its own
+ * filter | gate addend lc_add[r * lc_row_stride + l * 64 .. + 63] (lc_add =
+ * lc rows x the LC weights of all layers, one GEMM per pass) to the
+ * pre-activations; r = b * T + t.  lc_row_stride >= 64 L, a multiple of 4;
+ * lc_add 16-byte aligned.  32-row tiles only: a variant word that resolves to
+ * 16 rows (wn_stack_tile_rows) is WN_ERR_UNSUPPORTED. */
+int wn_stack_fwd_lc(float* X, float* Z, float* SG, const float* wimg,
+                    const float* bias, long bias_layer_stride,
+                    int bias_clip_stride, const int* dilations, unsigned* flags,
+                    unsigned* ctl, float* poison, int L, int B, int T, int save_sg,
+                    int variant, const float* lc_add, long lc_row_stride,
+                    void* stream);
 int wn_stack_bwd_slabs(int B, int T, int variant);
 int wn_stack_bwd(const float* X, const float* Z, const float* SG,
                  const float* dZ, float* DX, long dx_layer_stride, float* Q,
@@ -293,6 +305,17 @@ int wn_stack_bwd(const float* X, const float* Z, const float* SG,
                  long slab_layer_stride, float* tilesum, const int* dilations,
                  unsigned* flags, unsigned* ctl, float* poison, int L, int B,
                  int T, int variant, void* stream);
+/* Local conditioning: wn_stack_bwd that ALSO stores the pre-activation
+ * gradients da_f | da_g of row r and layer l at lc_da[r * lc_row_stride + l * 64
+ * .. + 63] (same layout and constraints as wn_stack_fwd_lc's lc_add); the LC
+ * weight gradients are lc^T da (wn_gemm_tn).  32-row tiles only. */
+int wn_stack_bwd_lc(const float* X, const float* Z, const float* SG,
+                    const float* dZ, float* DX, long dx_layer_stride, float* Q,
+                    const float* wimg, float* slabs,
+                    long slab_layer_stride, float* tilesum, const int* dilations,
+                    unsigned* flags, unsigned* ctl, float* poison, int L, int B,
+                    int T, int variant, float* lc_da, long lc_row_stride,
+                    void* stream);
 
 /* ---- fp32 MFMA GEMMs: the skip sum + post-processing of
  * wavenet/model.py:303-305, 430-440 (_create_network) and their gradients.

@@ -236,8 +236,26 @@ __global__ void stack_skip_pack_kernel(const float* __restrict__ skip_w, float* 
   }
 }
 
-template <int SAVE, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void stack_fwd_kernel(StackFwd a) {
+// Local conditioning (the kernels instantiated with a StackLc argument): the
+// filter | gate values of row r and layer l at lc.p[r * lc.row_stride + l * 64
+// ..] -- the forward's per-row addends, the backward's stored pre-activation
+// gradients.  A second kernel
+// argument instead of new StackFwd / StackBwd fields: the kernels without it
+// keep their argument block, and with it their machine code, as they were.
+struct StackLc {
+  float* p;
+  long row_stride;
+};
+// (the argument of a kernel instantiated with one StackLc; only named inside
+// `if constexpr` branches of the instantiations that have it)
+__device__ __forceinline__ StackLc stack_lc_arg(StackLc lc) { return lc; }
+
+// Lc = StackLc (the local-conditioning launch): every row also adds its own 64
+// addend values to the filter | gate pre-activations, on top of the per-clip
+// bias
+template <int SAVE, int WAVES, typename... Lc>
+__global__ __launch_bounds__(WAVES * 64) void stack_fwd_kernel(StackFwd a, Lc... lc_) {
+  constexpr bool LC = sizeof...(Lc) > 0;
   __shared__ __attribute__((aligned(1024))) float wl[2 * STACK_WBUF];
   __shared__ __attribute__((aligned(16))) float tiles[WAVES * 1024];
   __shared__ int s_group;
@@ -326,6 +344,25 @@ __global__ __launch_bounds__(WAVES * 64) void stack_fwd_kernel(StackFwd a) {
       } else {
         af = frag_zero();
         ag = frag_zero();
+      }
+      if constexpr (LC) {
+        // this lane's row t0 + j, channels 8 q + 4 h .. + 3 (frag_bcast's
+        // order); rows past the clip's end read nothing
+        const StackLc lc = stack_lc_arg(lc_...);
+        if (j < hi) {
+          const float* ap = lc.p + ((size_t)b * T + t0 + j) * lc.row_stride +
+                            (size_t)l * 64 + 4 * h;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 vf = *reinterpret_cast<const f32x4*>(ap + 8 * q);
+            const f32x4 vg = *reinterpret_cast<const f32x4*>(ap + 32 + 8 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              af[4 * q + e] += vf[e];
+              ag[4 * q + e] += vg[e];
+            }
+          }
+        }
       }
       // ---- the dilated tap: rows t0-d .. t0-d+31 of x_l, written by the
       // owners of (at most) two tiles of this clip.  Their flags are requested
@@ -713,8 +750,12 @@ __device__ __forceinline__ void tile_dma_rs(float* lds_tile, wn_rsrc_t rs, int s
 // instead of two, 160 instead of 176 MFMAs, 9 instead of 11 plane passes
 // through memory, and the hand-over is published in the middle of a tile
 // (before its weight-gradient products) instead of at its end.
-template <int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void stack_bwd_kernel(StackBwd a) {
+// Lc = StackLc (the local-conditioning launch): also store the pre-activation
+// gradients da_f | da_g of every row (the host's lc^T da GEMM turns them into
+// the local-conditioning weight gradients)
+template <int WAVES, typename... Lc>
+__global__ __launch_bounds__(WAVES * 64) void stack_bwd_kernel(StackBwd a, Lc... lc_) {
+  constexpr bool LC = sizeof...(Lc) > 0;
   constexpr int SLAB = WAVES > 1 ? LAYER_BLOCK_FLOATS : 16;   // ordered-accumulation slab
   __shared__ __attribute__((aligned(1024))) float wl[2 * SB_WIMG];
   __shared__ __attribute__((aligned(1024))) float tiles[WAVES * 3072];
@@ -919,6 +960,20 @@ __global__ __launch_bounds__(WAVES * 64) void stack_bwd_kernel(StackBwd a) {
 #else
           gate_grad(dz, zz, ss, df, dg);
 #endif
+          if constexpr (LC) {
+            const StackLc lc = stack_lc_arg(lc_...);
+            if (j < hi) {               // row tt0 + j, channels as in the forward
+              float* dp = lc.p + ((size_t)b * T + tt0 + j) * lc.row_stride +
+                          (size_t)l * 64 + 4 * h;
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                *reinterpret_cast<f32x4*>(dp + 8 * q) =
+                    f32x4{df[4 * q], df[4 * q + 1], df[4 * q + 2], df[4 * q + 3]};
+                *reinterpret_cast<f32x4*>(dp + 32 + 8 * q) =
+                    f32x4{dg[4 * q], dg[4 * q + 1], dg[4 * q + 2], dg[4 * q + 3]};
+              }
+            }
+          }
           // (Wg's first chunk requested during Wf's last MFMAs: 1637 -> 1622 us)
           f32x4 wpre = *reinterpret_cast<const f32x4*>(wm + 1 * 1024 + woff);
           mma32s_chain(dx, df, wm + 1 * 1024, woff, wpre, wm + 0 * 1024);  // da_f[t] * Wf[1]^T
@@ -2161,7 +2216,7 @@ static int stack_fwd_launch(float* X, float* Z, float* SG, const float* wimg,
                  int bias_clip_stride, const int* dilations, unsigned* flags,
                  unsigned* ctl, float* poison, int L, int B, int T, int save_sg,
                  int variant, void* stream, const float* skimg, const float* sk_bsum,
-                 float* sk_out) {
+                 float* sk_out, const float* lc_add = nullptr, long lc_row_stride = 0) {
   if (!X || !Z || !wimg || !dilations || !flags || !ctl) return WN_ERR_NULL;
   if (save_sg && !SG) return WN_ERR_NULL;
   if (L <= 0 || B <= 0 || T <= 0) return WN_ERR_BAD_SHAPE;
@@ -2175,11 +2230,14 @@ static int stack_fwd_launch(float* X, float* Z, float* SG, const float* wimg,
   a.ctl = ctl; a.poison = poison; a.L = L; a.B = B; a.T = T;
   a.plane = (long)B * T * WN_CH;
   a.skimg = skimg; a.sk_bsum = sk_bsum; a.sk_out = sk_out;
+  const StackLc lc{const_cast<float*>(lc_add), lc_row_stride};
 #ifdef STACK_STAMPS
   if (!g_stack_dbg) return WN_ERR_NULL;
   a.dbg = g_stack_dbg;
 #endif
   if (L > STACK_MAXL) return WN_ERR_UNSUPPORTED;
+  // (local conditioning: the 32-row launch only)
+  if (lc_add && (skimg || wn_stack_tile_rows(B, T, variant) != 32)) return WN_ERR_UNSUPPORTED;
   if (skimg) {
     // the 16-row launch with a partner wave per tile (stack_fwd16_kernel<.., true>)
     if (!sk_out || !wn_aligned16(skimg) || !wn_aligned16(sk_out) ||
@@ -2244,12 +2302,16 @@ static int stack_fwd_launch(float* X, float* Z, float* SG, const float* wimg,
   if (g > cus) g = cus;
   dim3 grid((unsigned)g), block(waves * 64);
   hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(W)                                                             \
-  do {                                                                        \
-    if (save_sg)                                                              \
-      hipLaunchKernelGGL((stack_fwd_kernel<2, W>), grid, block, 0, s, a);     \
-    else                                                                      \
-      hipLaunchKernelGGL((stack_fwd_kernel<0, W>), grid, block, 0, s, a);     \
+#define LAUNCH(W)                                                                  \
+  do {                                                                             \
+    if (lc_add && save_sg)                                                         \
+      hipLaunchKernelGGL((stack_fwd_kernel<2, W, StackLc>), grid, block, 0, s, a, lc);   \
+    else if (lc_add)                                                               \
+      hipLaunchKernelGGL((stack_fwd_kernel<0, W, StackLc>), grid, block, 0, s, a, lc);   \
+    else if (save_sg)                                                              \
+      hipLaunchKernelGGL((stack_fwd_kernel<2, W>), grid, block, 0, s, a);          \
+    else                                                                           \
+      hipLaunchKernelGGL((stack_fwd_kernel<0, W>), grid, block, 0, s, a);          \
   } while (0)
   switch (waves) {
     case 16: LAUNCH(16); break;
@@ -2270,6 +2332,25 @@ int wn_stack_fwd(float* X, float* Z, float* SG, const float* wimg,
   return stack_fwd_launch(X, Z, SG, wimg, bias, bias_layer_stride, bias_clip_stride, dilations,
                           flags, ctl, poison, L, B, T, save_sg, variant, stream, nullptr,
                           nullptr, nullptr);
+}
+
+// wn_stack_fwd with local conditioning: row r of layer l also adds
+// lc_add[r * lc_row_stride + l * 64 ..] (64 floats, filter | gate) to its
+// pre-activations.  32-row tiles only: the variant word must resolve to them.
+int wn_stack_fwd_lc(float* X, float* Z, float* SG, const float* wimg,
+                    const float* bias, long bias_layer_stride,
+                    int bias_clip_stride, const int* dilations, unsigned* flags,
+                    unsigned* ctl, float* poison, int L, int B, int T, int save_sg,
+                    int variant, const float* lc_add, long lc_row_stride,
+                    void* stream) {
+  if (!lc_add) return WN_ERR_NULL;
+  if (!wn_aligned16(lc_add)) return WN_ERR_MISALIGNED;
+  if (L <= 0 || B <= 0 || T <= 0 || lc_row_stride < 64L * L || (lc_row_stride & 3))
+    return WN_ERR_BAD_SHAPE;
+  if (wn_stack_tile_rows(B, T, variant) != 32) return WN_ERR_UNSUPPORTED;
+  return stack_fwd_launch(X, Z, SG, wimg, bias, bias_layer_stride, bias_clip_stride, dilations,
+                          flags, ctl, poison, L, B, T, save_sg, variant, stream, nullptr,
+                          nullptr, nullptr, lc_add, lc_row_stride);
 }
 
 // wn_stack_fwd + the skip sum in the same launch: h1[N][512] = relu(sum_l z_l Ws_l
@@ -2332,12 +2413,13 @@ int wn_stack_bwd_slabs(int B, int T, int variant) {
   return (int)((ntiles + (long)w * t - 1) / ((long)w * t));
 }
 
-int wn_stack_bwd(const float* X, const float* Z, const float* SG,
+static int stack_bwd_launch(const float* X, const float* Z, const float* SG,
                  const float* dZ, float* DX, long dx_layer_stride, float* Q,
                  const float* wimg, float* slabs,
                  long slab_layer_stride, float* tilesum, const int* dilations,
                  unsigned* flags, unsigned* ctl, float* poison, int L, int B,
-                 int T, int variant, void* stream) {
+                 int T, int variant, void* stream, float* lc_da = nullptr,
+                 long lc_row_stride = 0) {
   if (!X || !Z || !SG || !dZ || !DX || !Q || !wimg || !slabs || !dilations ||
       !flags || !ctl)
     return WN_ERR_NULL;
@@ -2362,6 +2444,7 @@ int wn_stack_bwd(const float* X, const float* Z, const float* SG,
   a.dil = dilations; a.flags = flags; a.ctl = ctl; a.poison = poison;
   a.L = L; a.B = B; a.T = T;
   a.tpw = tpw; a.plane = (long)B * T * WN_CH;
+  const StackLc lc{lc_da, lc_row_stride};
 #ifdef STACK_STAMPS
   if (!g_stack_dbg_b) return WN_ERR_NULL;
   a.dbg = g_stack_dbg_b;
@@ -2373,12 +2456,19 @@ int wn_stack_bwd(const float* X, const float* Z, const float* SG,
   // a single plane rewritten in place
   if (dx_layer_stride != (long)B * T * WN_CH && dx_layer_stride != 0)
     return WN_ERR_BAD_SHAPE;
+  if (lc_da && rows != 32) return WN_ERR_UNSUPPORTED;   // (local conditioning: 32 rows only)
   if (rows == 16) {
     if (waves == 8) hipLaunchKernelGGL((stack_bwd16_kernel<8>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((stack_bwd16_kernel<4>), grid, block, 0, s, a);
     return wn_check_launch();
   }
-#define LAUNCH(W) hipLaunchKernelGGL((stack_bwd_kernel<W>), grid, block, 0, s, a)
+#define LAUNCH(W)                                                          \
+  do {                                                                     \
+    if (lc_da)                                                             \
+      hipLaunchKernelGGL((stack_bwd_kernel<W, StackLc>), grid, block, 0, s, a, lc); \
+    else                                                                   \
+      hipLaunchKernelGGL((stack_bwd_kernel<W>), grid, block, 0, s, a);     \
+  } while (0)
   switch (waves) {
     case 8: LAUNCH(8); break;
     case 4: LAUNCH(4); break;
@@ -2387,6 +2477,37 @@ int wn_stack_bwd(const float* X, const float* Z, const float* SG,
   }
 #undef LAUNCH
   return wn_check_launch();
+}
+
+int wn_stack_bwd(const float* X, const float* Z, const float* SG,
+                 const float* dZ, float* DX, long dx_layer_stride, float* Q,
+                 const float* wimg, float* slabs,
+                 long slab_layer_stride, float* tilesum, const int* dilations,
+                 unsigned* flags, unsigned* ctl, float* poison, int L, int B,
+                 int T, int variant, void* stream) {
+  return stack_bwd_launch(X, Z, SG, dZ, DX, dx_layer_stride, Q, wimg, slabs,
+                          slab_layer_stride, tilesum, dilations, flags, ctl, poison, L,
+                          B, T, variant, stream);
+}
+
+// wn_stack_bwd with local conditioning: also stores the pre-activation
+// gradients da_f | da_g of row r and layer l at lc_da[r * lc_row_stride + l * 64 ..]
+// (64 floats).  32-row tiles only: the variant word must resolve to them.
+int wn_stack_bwd_lc(const float* X, const float* Z, const float* SG,
+                    const float* dZ, float* DX, long dx_layer_stride, float* Q,
+                    const float* wimg, float* slabs,
+                    long slab_layer_stride, float* tilesum, const int* dilations,
+                    unsigned* flags, unsigned* ctl, float* poison, int L, int B,
+                    int T, int variant, float* lc_da, long lc_row_stride,
+                    void* stream) {
+  if (!lc_da) return WN_ERR_NULL;
+  if (!wn_aligned16(lc_da)) return WN_ERR_MISALIGNED;
+  if (L <= 0 || B <= 0 || T <= 0 || lc_row_stride < 64L * L || (lc_row_stride & 3))
+    return WN_ERR_BAD_SHAPE;
+  if (wn_stack_tile_rows(B, T, variant) != 32) return WN_ERR_UNSUPPORTED;
+  return stack_bwd_launch(X, Z, SG, dZ, DX, dx_layer_stride, Q, wimg, slabs,
+                          slab_layer_stride, tilesum, dilations, flags, ctl, poison, L,
+                          B, T, variant, stream, lc_da, lc_row_stride);
 }
 
 }  // extern "C"

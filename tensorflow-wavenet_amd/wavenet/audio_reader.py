@@ -10,6 +10,14 @@ silence_threshold, queue_size)`, `dequeue`, `dequeue_gc`, `start_threads`,
 `gc_category_cardinality`); new keyword arguments `rank` / `world` shard the
 file list per data-parallel rank, `seed` makes the shuffle reproducible.
 
+Local conditioning (`lc_channels`, `lc_hop`): next to every `<clip>.wav` a
+`<clip>.npy` of frame-rate features [frames, lc_channels].  They are upsampled
+to audio rate by repetition (frame f covers samples f * lc_hop .. + lc_hop - 1),
+then silence trimming and piece cutting take the SAME sample indices of audio
+and features, so that feature row t of a piece sits beside its sample t.
+`dequeue` followed by `dequeue_lc` returns the features of the pieces just
+dequeued.
+
 librosa is not available in this image: wav I/O is scipy.io.wavfile,
 resampling is scipy.signal.resample_poly (librosa's default is a Kaiser-windowed
 sinc; the two differ at the 1e-3 level, which only matters if one wants
@@ -108,14 +116,62 @@ def rms_energy(audio, frame_length=2048, hop_length=512):
     return np.sqrt(np.mean(y[idx] ** 2, axis=1))
 
 
-def trim_silence(audio, threshold, frame_length=2048, hop_length=512):
-    '''Removes silence at the beginning and end of a sample.'''
+def trim_bounds(audio, threshold, frame_length=2048, hop_length=512):
+    '''[lo, hi) of `audio` that trim_silence keeps.'''
     energy = rms_energy(audio, frame_length, hop_length)
     frames = np.nonzero(energy > threshold)[0]
     if frames.size == 0:
-        return audio[0:0]
-    lo, hi = frames[0] * hop_length, frames[-1] * hop_length
+        return 0, 0
+    return frames[0] * hop_length, frames[-1] * hop_length
+
+
+def trim_silence(audio, threshold, frame_length=2048, hop_length=512):
+    '''Removes silence at the beginning and end of a sample.'''
+    lo, hi = trim_bounds(audio, threshold, frame_length, hop_length)
     return audio[lo:hi]
+
+
+def trim_silence_lc(audio, lc, threshold, frame_length=2048, hop_length=512):
+    '''trim_silence of the audio; the audio-rate features [T, Lc] lose the
+    same rows.'''
+    lo, hi = trim_bounds(audio, threshold, frame_length, hop_length)
+    return audio[lo:hi], lc[lo:hi]
+
+
+def lc_path_of(filename):
+    '''The features of `<clip>.wav` live in `<clip>.npy`.'''
+    return os.path.splitext(filename)[0] + '.npy'
+
+
+def upsample_lc(feats, hop, num_samples, lc_channels=None):
+    '''Frame-rate features [frames, Lc] -> audio rate [num_samples, Lc] by
+    repetition: frame f covers samples f * hop .. f * hop + hop - 1.  The
+    audio may run past the last frame by less than one hop (the last frame is
+    repeated); anything else is a ValueError.'''
+    feats = np.asarray(feats, dtype=np.float32)
+    if feats.ndim != 2:
+        raise ValueError('local conditioning features must be [frames, '
+                         'channels], got shape %s' % (feats.shape,))
+    if lc_channels is not None and feats.shape[1] != lc_channels:
+        raise ValueError('features have %d channels, expected %d'
+                         % (feats.shape[1], lc_channels))
+    hop = int(hop)
+    if hop <= 0:
+        raise ValueError('lc_hop must be positive')
+    frames_needed = (int(num_samples) + hop - 1) // hop
+    if feats.shape[0] < frames_needed - 1 or feats.shape[0] == 0:
+        raise ValueError('%d feature frames at hop %d do not cover %d samples'
+                         % (feats.shape[0], hop, num_samples))
+    up = np.repeat(feats, hop, axis=0)
+    if up.shape[0] < num_samples:
+        up = np.concatenate([up, np.repeat(up[-1:], num_samples - up.shape[0],
+                                           axis=0)])
+    return np.ascontiguousarray(up[:num_samples])
+
+
+def load_lc(path, hop, num_samples, lc_channels=None):
+    '''upsample_lc of the features stored in `path` (.npy).'''
+    return upsample_lc(np.load(path), hop, num_samples, lc_channels)
 
 
 def load_generic_audio(files, sample_rate, rng):
@@ -141,13 +197,23 @@ class AudioReader(object):
                  queue_size=32,
                  rank=0,
                  world=1,
-                 seed=None):
+                 seed=None,
+                 *,
+                 lc_channels=None,
+                 lc_hop=None):
         self.audio_dir = audio_dir
         self.sample_rate = sample_rate
         self.coord = coord if coord is not None else Coordinator()
         self.sample_size = sample_size
         self.silence_threshold = silence_threshold
         self.gc_enabled = gc_enabled
+        self.lc_channels = lc_channels
+        self.lc_hop = lc_hop
+        self.lc_enabled = lc_channels is not None
+        if self.lc_enabled and not lc_hop:
+            raise ValueError('local conditioning needs lc_hop (samples per '
+                             'feature frame)')
+        self._last_lc = None
         self.threads = []
         self.queue = queue.Queue(maxsize=queue_size)
         self.gc_queue = queue.Queue(maxsize=queue_size) if gc_enabled else None
@@ -172,6 +238,12 @@ class AudioReader(object):
         self.files = files[rank::world] if world > 1 else files
         if not self.files:
             raise ValueError('rank %d of %d has no audio files' % (rank, world))
+        if self.lc_enabled:
+            missing = [f for f in self.files if not os.path.exists(lc_path_of(f))]
+            if missing:
+                raise ValueError('local conditioning is enabled, but %d wav '
+                                 'file(s) have no features next to them, e.g. %s'
+                                 % (len(missing), lc_path_of(missing[0])))
 
     # ------------------------------------------------------------- consumer
     def _get(self, q):
@@ -189,11 +261,34 @@ class AudioReader(object):
         at the end (tf.PaddingFIFOQueue.dequeue_many semantics)."""
         import torch
         pieces = [self._get(self.queue) for _ in range(num_elements)]
+        if self.lc_enabled:
+            # (items are (audio piece, feature piece) pairs: dequeue_lc
+            # returns the features of exactly these pieces)
+            feats = [f for _, f in pieces]
+            pieces = [p for p, _ in pieces]
+            tmax = max(p.shape[0] for p in pieces)
+            lc = np.zeros((num_elements, tmax, self.lc_channels), np.float32)
+            for i, f in enumerate(feats):
+                lc[i, :f.shape[0]] = f
+            self._last_lc = torch.from_numpy(lc)
         tmax = max(p.shape[0] for p in pieces)
         out = np.zeros((num_elements, tmax, 1), np.float32)
         for i, p in enumerate(pieces):
             out[i, :p.shape[0], :] = p
         return torch.from_numpy(out)
+
+    def dequeue_lc(self, num_elements):
+        """float32 [num_elements, T_max, lc_channels]: the audio-rate features
+        of the pieces the last `dequeue(num_elements)` returned (zero-padded
+        like them); row t sits beside sample t."""
+        if not self.lc_enabled:
+            raise ValueError('AudioReader was built without lc_channels')
+        lc = self._last_lc
+        if lc is None or lc.shape[0] != num_elements:
+            raise ValueError('dequeue_lc(%d) must follow dequeue(%d)'
+                             % (num_elements, num_elements))
+        self._last_lc = None
+        return lc
 
     def dequeue_gc(self, num_elements):
         import torch
@@ -210,40 +305,58 @@ class AudioReader(object):
                 continue
         return False
 
-    def thread_main(self, sess=None):
+    def iter_pieces(self):
+        """One pass over the (shuffled) files: (piece [n, 1], category id,
+        feature piece [n, lc_channels] or None) in queue order."""
         buffer_ = np.zeros((0,), np.float32)
+        lc_buf = np.zeros((0, self.lc_channels or 0), np.float32)
+        for audio, filename, category_id in load_generic_audio(
+                self.files, self.sample_rate, self._rng):
+            lc = None
+            if self.lc_enabled:
+                lc = load_lc(lc_path_of(filename), self.lc_hop, audio.shape[0],
+                             self.lc_channels)
+            if self.silence_threshold is not None:
+                if lc is not None:
+                    a, lc = trim_silence_lc(audio[:, 0], lc,
+                                            self.silence_threshold)
+                else:
+                    a = trim_silence(audio[:, 0], self.silence_threshold)
+                audio = a.reshape(-1, 1)
+                if audio.size == 0:
+                    print("Warning: {} was ignored as it contains only "
+                          "silence. Consider decreasing trim_silence "
+                          "threshold, or adjust volume of the audio."
+                          .format(filename))
+            if self.sample_size:
+                # cut into fixed-size pieces (the last piece of a file is
+                # short; consecutive files are concatenated like the
+                # reference's running buffer); features at the same indices
+                buffer_ = np.append(buffer_, audio)
+                if lc is not None:
+                    lc_buf = np.concatenate([lc_buf, lc])
+                while len(buffer_) > 0:
+                    piece = buffer_[:self.sample_size].reshape(-1, 1)
+                    lp = lc_buf[:self.sample_size].copy() if lc is not None \
+                        else None
+                    yield piece.copy(), category_id, lp
+                    buffer_ = buffer_[self.sample_size:]
+                    if lc is not None:
+                        lc_buf = lc_buf[self.sample_size:]
+            elif audio.size:
+                yield audio, category_id, lc
+
+    def thread_main(self, sess=None):
         while not self.coord.should_stop():      # many passes over the data
-            for audio, filename, category_id in load_generic_audio(
-                    self.files, self.sample_rate, self._rng):
+            for piece, category_id, lc in self.iter_pieces():
                 if self.coord.should_stop():
                     return
-                if self.silence_threshold is not None:
-                    audio = trim_silence(audio[:, 0], self.silence_threshold)
-                    audio = audio.reshape(-1, 1)
-                    if audio.size == 0:
-                        print("Warning: {} was ignored as it contains only "
-                              "silence. Consider decreasing trim_silence "
-                              "threshold, or adjust volume of the audio."
-                              .format(filename))
-                if self.sample_size:
-                    # cut into fixed-size pieces (the last piece of a file is
-                    # short; consecutive files are concatenated like the
-                    # reference's running buffer)
-                    buffer_ = np.append(buffer_, audio)
-                    while len(buffer_) > 0:
-                        piece = buffer_[:self.sample_size].reshape(-1, 1)
-                        if not self._put(self.queue, piece.copy()):
-                            return
-                        buffer_ = buffer_[self.sample_size:]
-                        if self.gc_enabled and not self._put(self.gc_queue,
-                                                             category_id):
-                            return
-                elif audio.size:
-                    if not self._put(self.queue, audio):
-                        return
-                    if self.gc_enabled and not self._put(self.gc_queue,
-                                                         category_id):
-                        return
+                item = (piece, lc) if self.lc_enabled else piece
+                if not self._put(self.queue, item):
+                    return
+                if self.gc_enabled and not self._put(self.gc_queue,
+                                                     category_id):
+                    return
 
     def start_threads(self, sess=None, n_threads=1):
         for _ in range(n_threads):

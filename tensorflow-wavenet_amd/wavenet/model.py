@@ -65,7 +65,7 @@ class _Workspace(object):
         f32 = dict(dtype=torch.float32, device=dev)
         self.B, self.T, self.N, self.training = B, T, N, training
         # (the variant word of the stack launches is fixed per workspace)
-        self.stack_variant = int(net.stack_variant)
+        self.stack_variant = net._stack_variant_for_launch()
         self.capacity = N if parent is None else parent.capacity
         lib = _lib.load()
 
@@ -114,6 +114,12 @@ class _Workspace(object):
         alloc('loss_parts', (2 + self.nparts,), fill=0.0)
         alloc('loss', (1,), fill=0.0)
         alloc('proba', (Q,))
+        if net.Lc:
+            # local conditioning: the rows [N][Lc, padded to 4 with zero
+            # columns] and the per-row filter | gate addends of every layer
+            # [N][L][64] (lc x lc_w, the layout wn_stack_fwd_lc reads)
+            alloc('lc', (N, net.Lcp), fill=0.0)
+            alloc('lc_add', (N, L * 64))
         if net.blocked:
             # partial pre-activations of a layer wider than one chunk of
             # channel blocks (wavenet/blocked.py), planes af | ag
@@ -198,6 +204,13 @@ class _Workspace(object):
             self.splits[key] = sp
             need = max(need, sp * lib.wn_gemm_tn_slab_floats(mw, nw))
         need_tn = need
+        if net.Lc:
+            # lc^T da (local-conditioning weight gradients), on the main stream
+            # after the backward stack: the pre-activation gradients [N][L][64]
+            alloc('lc_da', (N, L * 64))
+            sp = lib.wn_gemm_tn_splits(N, net.Lcp, L * 64, 0)
+            self.splits['lc'] = sp
+            need = max(need, sp * lib.wn_gemm_tn_slab_floats(net.Lcp, L * 64))
         # scalar-input causal wgrad: [splits][initial_filter_width][32] slabs
         need = max(need, max(256, self.splits['causal'])
                    * max(32, net.initial_filter_width) * CH)
@@ -257,7 +270,9 @@ class WaveNetModel(object):
                  global_condition_cardinality=None,
                  residual_postproc=False,
                  device=None,
-                 seed=0):
+                 seed=0,
+                 *,
+                 local_condition_channels=None):
         self.batch_size = batch_size
         self.dilations = list(dilations)
         self.filter_width = filter_width
@@ -272,6 +287,15 @@ class WaveNetModel(object):
         self.global_condition_channels = global_condition_channels
         self.global_condition_cardinality = global_condition_cardinality
         self.residual_postproc = residual_postproc
+        # local conditioning (WaveNet paper 2.5): per-sample features lc[b, t]
+        # of this many channels, see `loss` / `predict_proba`
+        self.local_condition_channels = local_condition_channels
+        self.Lc = self._check_local_condition_family(
+            local_condition_channels, filter_width, residual_channels,
+            dilation_channels, scalar_input)
+        # (LC weights as [Lcp][L][64]: rows padded to a multiple of 4 for the
+        # GEMMs, zero)
+        self.Lcp = _align(self.Lc, 4) if self.Lc else 0
         # TF's fused softmax-xent back-propagates softmax/(B*T) through the
         # all-zero-label last row of every clip [inferred].
         self.tf_xent_zero_label_quirk = True
@@ -412,9 +436,40 @@ class WaveNetModel(object):
         self.push_ops = []
         self.variables = self._create_variables(seed)
 
+    LC_SUPPORTED = ('local conditioning is supported for residual / dilation '
+                    'channels <= 32, filter_width 2 and one-hot input (not '
+                    'scalar_input), on the persistent stack launches '
+                    '(stack_fwd / stack_bwd = True)')
+
+    @classmethod
+    def _check_local_condition_family(cls, lc, filter_width, R, D, scalar_input):
+        """Number of LC channels (0 without LC); raises before any device is
+        touched for a combination outside the supported family."""
+        if lc is None:
+            return 0
+        if isinstance(lc, bool) or int(lc) != lc or int(lc) <= 0:
+            raise ValueError('local_condition_channels must be a positive int, '
+                             'got %r' % (lc,))
+        why = None
+        if max(int(R), int(D)) > CH:
+            why = 'more than 32 residual / dilation channels'
+        elif int(filter_width) != 2:
+            why = 'filter_width %d' % int(filter_width)
+        elif scalar_input:
+            why = 'scalar_input'
+        if why:
+            raise NotImplementedError('%s: %s' % (why, cls.LC_SUPPORTED))
+        return int(lc)
+
     @property
     def stack_variant(self):
         return self._stack_variant
+
+    def _stack_variant_for_launch(self):
+        """The variant word the stack launches of a new workspace get: an LC
+        model always runs the 32-row launches (wn_stack_fwd_lc / _bwd_lc)."""
+        v = int(self._stack_variant)
+        return (v & ~0x3f) | 32 if self.Lc else v
 
     @stack_variant.setter
     def stack_variant(self, v):
@@ -444,6 +499,12 @@ class WaveNetModel(object):
         add('causal', (self.initial_filter_width if self.scalar_input
                        else self.KW * Q) * C)
         add('layers', L * self.layer_stride)
+        if self.Lc:
+            # local conditioning: [Lcp][L][64] (filter | gate columns of every
+            # layer next to each other, the addend GEMM's weight as it is).  In
+            # front of skip_w: the data-parallel tail all-reduce starts there
+            # (parallel.tail_start) before this gradient exists
+            add('lc_w', self.Lcp * L * 64)
         add('skip_w', L * C * S)
         add('skip_b', L * S)
         add('post1_w', S * S)
@@ -480,6 +541,7 @@ class WaveNetModel(object):
         layers = self._seg(flat, 'layers').view(L, self.layer_stride)
         skw = self._seg(flat, 'skip_w').view(L, 1, CH, S)
         skb = self._seg(flat, 'skip_b').view(L, S)
+        lcw = self._seg(flat, 'lc_w').view(self.Lcp, L, 64) if self.Lc else None
         var['dilated_stack'] = []
         for i in range(L):
             blk = layers[i]
@@ -498,6 +560,9 @@ class WaveNetModel(object):
                 gcg = blk[OFF_GC + G * CH:OFF_GC + 2 * G * CH].view(1, G, CH)
                 cur['gc_gateweights'] = gcg[:, :, :D]
                 cur['gc_filtweights'] = gcf[:, :, :D]
+            if lcw is not None:                 # [Lc, dilation_channels]
+                cur['lc_filtweights'] = lcw[:self.Lc, i, :D]
+                cur['lc_gateweights'] = lcw[:self.Lc, i, 32:32 + D]
             if self.use_biases:
                 cur['filter_bias'] = blk[OFF_BF:OFF_BF + D]
                 cur['gate_bias'] = blk[OFF_BG:OFF_BG + D]
@@ -535,6 +600,12 @@ class WaveNetModel(object):
                         _xavier_(cur[k], gen)
             _xavier_(v['postprocessing']['postprocess1'], gen)
             _xavier_(v['postprocessing']['postprocess2'], gen)
+            # (drawn last: every other variable gets the values it has in the
+            # same model without LC)
+            for cur in v['dilated_stack']:
+                for k in ['lc_filtweights', 'lc_gateweights']:
+                    if k in cur:
+                        _xavier_(cur[k], gen)
             # biases: zeros (model.py:27)
             self.params.copy_(host)
 
@@ -577,9 +648,10 @@ class WaveNetModel(object):
         out.append((prefix + '/causal_layer/filter',
                     tree['causal_layer']['filter']))
         order = ['filter', 'gate', 'dense', 'skip', 'gc_gateweights',
-                 'gc_filtweights', 'filter_bias', 'gate_bias', 'dense_bias',
-                 'skip_bias']
+                 'gc_filtweights', 'lc_gateweights', 'lc_filtweights',
+                 'filter_bias', 'gate_bias', 'dense_bias', 'skip_bias']
         tfname = {'gc_gateweights': 'gc_gate', 'gc_filtweights': 'gc_filter',
+                  'lc_gateweights': 'lc_gate', 'lc_filtweights': 'lc_filter',
                   'skip_bias': 'slip_bias'}       # sic, model.py:183-204
         for i, cur in enumerate(tree['dilated_stack']):
             for k in order:
@@ -766,6 +838,49 @@ class WaveNetModel(object):
                              % (ids.numel(), B))
         return ids.contiguous()
 
+    def _lc_rows(self, local_condition, B, T, what):
+        """Validate the local-conditioning rows of a call ([B, T, Lc], float)
+        before anything is launched; returns them as a float32 tensor on the
+        device, or None for a model without LC."""
+        if not self.Lc:
+            if local_condition is not None:
+                raise ValueError('%s: this model was built without local '
+                                 'conditioning (local_condition_channels=None)'
+                                 % what)
+            return None
+        if local_condition is None:
+            raise ValueError('%s: the model was built with local conditioning '
+                             '(%d channels); an lc batch [%d, %d, %d] is required'
+                             % (what, self.Lc, B, T, self.Lc))
+        lc = local_condition
+        if not isinstance(lc, torch.Tensor):
+            lc = torch.as_tensor(np.asarray(lc, dtype=np.float32))
+        if B == 1 and lc.dim() == 2:
+            lc = lc.unsqueeze(0)
+        if tuple(lc.shape) != (B, T, self.Lc):
+            raise ValueError('%s: local conditioning must have shape [B, T, Lc] '
+                             '= [%d, %d, %d] (row t beside input sample t), got %s'
+                             % (what, B, T, self.Lc, tuple(lc.shape)))
+        if lc.is_floating_point() is False:
+            raise ValueError('%s: local conditioning must be floating point'
+                             % what)
+        return lc.to(device=self.device, dtype=torch.float32)
+
+    def _check_lc_paths(self):
+        """An LC model runs the persistent 32-row stack launches only."""
+        if self.Lc and not (self.stack_fwd and self.stack_bwd):
+            raise NotImplementedError(
+                'stack_fwd / stack_bwd = False with local conditioning: '
+                + self.LC_SUPPORTED)
+
+    def _stage_lc(self, ws, lc):
+        if lc is not None:
+            if not (ws.N * CH * 4 < 2 ** 31 and self.L <= 256):
+                raise NotImplementedError(
+                    'local conditioning needs B * T < 2^24 and at most 256 '
+                    'layers (the persistent stack launches)')
+            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
+
     def _layer_block(self, flat, l):
         o, _ = self.segments['layers']
         return flat[o + l * self.layer_stride: o + (l + 1) * self.layer_stride]
@@ -935,10 +1050,26 @@ class WaveNetModel(object):
                 _lib.call_timed('wn_stack_fwd_skip', stack_args + (
                     _lib.ptr(ws.skimg), _lib.ptr(bsum_f), _lib.ptr(ws.h1), st),
                     0.0, getattr(self, '_gemm_events', None))
+            elif self.Lc:
+                # local conditioning: the per-row filter | gate addends of all
+                # layers, lc [N][Lcp] x lc_w [Lcp][L * 64], then the stack
+                # launch that adds them (32-row tiles: the workspace's variant)
+                W64 = L * 64
+                _lib.call_timed('wn_gemm_nn', (
+                    _lib.ptr(ws.lc), self.Lcp, 0, 0,
+                    _lib.ptr(self._seg(P, 'lc_w')), W64, None, None, 0, None,
+                    0, _lib.ptr(ws.lc_add), W64, 0, 0, None, N, W64, self.Lcp,
+                    0, st), 2.0 * N * W64 * self.Lcp,
+                    getattr(self, '_gemm_events', None))
+                _lib.call_timed('wn_stack_fwd_lc', stack_args + (
+                    _lib.ptr(ws.lc_add), W64, st), 0.0,
+                    getattr(self, '_gemm_events', None))
             else:
                 # (flops 0: timed in bench.py's instrumented pass for its HBM roofline)
                 _lib.call_timed('wn_stack_fwd', stack_args + (st,), 0.0,
                                 getattr(self, '_gemm_events', None))
+        if self.Lc and not stack:
+            raise NotImplementedError(self.LC_SUPPORTED)
         for l, d in enumerate(self.dilations if not self.blocked and not stack
                               else []):
             last = l == L - 1
@@ -1116,6 +1247,8 @@ class WaveNetModel(object):
         # residual stack, last layer first
         if not self._legacy_bwd():
             # one launch per layer; the launches are chained through dx only
+            if self.Lc and not (self._stack_bwd_ok() and getattr(ws, 'stack_bwd', False)):
+                raise NotImplementedError(self.LC_SUPPORTED)
             dxin, xp = None, 0
             tsum = None if ws.dsum is None else ws.tilesum
             if self._stack_bwd_ok() and getattr(ws, 'stack_bwd', False):
@@ -1125,7 +1258,7 @@ class WaveNetModel(object):
                 if not self._bwd_image_with_fwd(ws):
                     _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(P, 0)),
                               self.layer_stride, None, _lib.ptr(ws.wimg_b), L, st)
-                _lib.call_timed('wn_stack_bwd', (
+                bargs = (
                     _lib.ptr(ws.X), _lib.ptr(ws.Z),
                     _lib.ptr(ws.SG), _lib.ptr(ws.dZ), _lib.ptr(ws.DX),
                     ws.N * CH if ws.keep_dx else 0,
@@ -1134,8 +1267,15 @@ class WaveNetModel(object):
                     None if tsum is None else _lib.ptr(tsum),
                     _lib.ptr(self._dil_dev), _lib.ptr(ws.stack_flags_b),
                     _lib.ptr(ws.stack_ctl_b),
-                    _lib.ptr(ws.loss_parts[1:]), L, B, T, ws.stack_variant, st), 0.0,
-                    getattr(self, '_gemm_events', None))
+                    _lib.ptr(ws.loss_parts[1:]), L, B, T, ws.stack_variant)
+                if self.Lc:
+                    # ... that also stores da_f | da_g of every row and layer
+                    _lib.call_timed('wn_stack_bwd_lc', bargs + (
+                        _lib.ptr(ws.lc_da), L * 64, st), 0.0,
+                        getattr(self, '_gemm_events', None))
+                else:
+                    _lib.call_timed('wn_stack_bwd', bargs + (st,), 0.0,
+                                    getattr(self, '_gemm_events', None))
                 self._backward_tail(ws, ids, ws.DX[0], ws.nslab_s, True,
                                     tile_rows=ws.stack_rows)
                 return
@@ -1267,6 +1407,19 @@ class WaveNetModel(object):
                           CH, 0, st)
                 _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, sl, 1, 0,
                           0, Q * CH, _lib.ptr(gc_[tap * Q * CH:]), 0, 1, 0, st)
+        if self.Lc:
+            # local conditioning: d lc_w [Lcp][L * 64] = lc^T [da_f | da_g of
+            # every layer] (the rows the backward stack stored)
+            W64 = L * 64
+            sp = ws.splits['lc']
+            _lib.call_timed('wn_gemm_tn', (
+                _lib.ptr(ws.lc), self.Lcp, 0, 0, None, 0, T, _lib.ptr(ws.lc_da),
+                W64, _lib.ptr(ws.slabs), sp, N, self.Lcp, W64, 0, st),
+                2.0 * N * W64 * self.Lcp, getattr(self, '_gemm_events', None))
+            _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp,
+                      lib.wn_gemm_tn_slab_floats(self.Lcp, W64), 1, 0, 0,
+                      self.Lcp * W64, _lib.ptr(self._seg(Gr, 'lc_w')), 0, 1, 0,
+                      st)
         if ws.dsum is not None:
             _lib.call('wn_gc_grad', _lib.ptr(self._layer_block(P, 0)),
                       self.layer_stride, self.OFF_GC, self.G,
@@ -1291,31 +1444,43 @@ class WaveNetModel(object):
              global_condition_batch=None,
              l2_regularization_strength=None,
              name='wavenet',
-             backward=True):
+             backward=True,
+             *,
+             local_condition_batch=None):
         '''Creates a WaveNet network and returns the autoencoding loss
         (model.py:628-685).  input_batch: float audio in [-1, 1], anything
         reshapeable to [batch_size, -1].  With backward=True (default) the
         gradient of the returned loss w.r.t. every variable is left in
-        `self.grads` (the flat bucket `optimizer.minimize` consumes).'''
+        `self.grads` (the flat bucket `optimizer.minimize` consumes).
+
+        local_condition_batch (models built with local_condition_channels=Lc,
+        required there and refused elsewhere): float [batch_size, T, Lc] at
+        audio rate.  Row t sits beside input sample t; the output at t is the
+        distribution of sample t + 1, so row t conditions the prediction of
+        sample t + 1.  Frame-rate features are upsampled by repetition first.'''
         self._check_supported()
         B = self.batch_size
         a = input_batch
         if not isinstance(a, torch.Tensor):
             a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
+        lc = self._lc_rows(local_condition_batch, B, a.shape[1], 'loss')
+        self._check_lc_paths()
         q = mu_law_encode(a, self.Q)
         return self.loss_from_codes(q, global_condition_batch,
                                     l2_regularization_strength, backward,
-                                    audio=a)
+                                    audio=a, local_condition_batch=lc)
 
     def loss_from_codes(self, q, global_condition_batch=None,
                         l2_regularization_strength=None, backward=True,
-                        audio=None):
+                        audio=None, *, local_condition_batch=None):
         self._check_supported()
         B = self.batch_size
         q = q.reshape(B, -1)
         T = q.shape[1]
         N = B * T
+        lc = self._lc_rows(local_condition_batch, B, T, 'loss')
+        self._check_lc_paths()
         ws = self._workspace(B, T, backward)
         if backward and self._tail_work is not None:
             # the previous backward pass started its tail all-reduce and no
@@ -1335,6 +1500,7 @@ class WaveNetModel(object):
                 raise ValueError('scalar_input needs the float audio')
             ws.audio.copy_(audio.reshape(-1))
         ids = self._gc_ids(global_condition_batch, B)
+        self._stage_lc(ws, lc)
         st = _lib.stream()
         # 0: inference; 1: tanh + sigmoid planes (legacy backward kernels);
         # 2: sigmoid plane only (wn_layer_bwd2)
@@ -1400,10 +1566,16 @@ class WaveNetModel(object):
             self._l2m = m
         return self._l2m
 
-    def predict_proba(self, waveform, global_condition=None, name='wavenet'):
+    def predict_proba(self, waveform, global_condition=None, name='wavenet',
+                      *, local_condition=None):
         '''Computes the probability distribution of the next sample based on
         all samples in the input waveform (model.py:564-590).  waveform:
-        already-quantised int samples.'''
+        already-quantised int samples.
+
+        local_condition (LC models only, required there): float [B, T, Lc]
+        (or [T, Lc] with batch_size 1), row t beside waveform sample t.  The
+        returned distribution is that of the sample after the last one, so
+        the last row conditions it.'''
         self._check_supported()
         B = self.batch_size
         w = waveform
@@ -1411,12 +1583,15 @@ class WaveNetModel(object):
             w = torch.as_tensor(np.asarray(w))
         w = w.to(device=self.device, dtype=torch.int32).reshape(B, -1)
         T = w.shape[1]
+        lc = self._lc_rows(local_condition, B, T, 'predict_proba')
+        self._check_lc_paths()
         ws = self._workspace(B, T, False)
         ws.q.copy_(w.reshape(-1))
         if self.scalar_input:
             # decode the codes back to floats in [-1, 1] (model.py:570-576)
             ws.audio.copy_(mu_law_decode(w, self.Q).reshape(-1))
         ids = self._gc_ids(global_condition, B)
+        self._stage_lc(ws, lc)
         self._forward(ws, ids, save_ts=0)
         out = torch.empty(self.Q, dtype=torch.float32, device=self.device)
         _lib.call('wn_softmax64_row', _lib.ptr(ws.logits[B * T - 1]), self.Q,
@@ -1429,6 +1604,13 @@ class WaveNetModel(object):
     FASTGEN_MAX_CHANNELS = 1024    # wn_fastgen_run_wide (FGW_MAXC)
     FASTGEN_BATCH_MAX = 256        # wn_fastgen_batch_* (FGB_MAXB)
 
+    def _no_lc_fastgen(self, what):
+        if self.Lc:
+            raise NotImplementedError(
+                '%s: fast generation does not support local conditioning yet; '
+                'generate with predict_proba(..., local_condition=...) '
+                '(generate.py --fast_generation false)' % what)
+
     def predict_proba_incremental(self, waveform, global_condition=None,
                                   name='wavenet', push=True):
         '''Computes the probability distribution of the next sample
@@ -1436,11 +1618,13 @@ class WaveNetModel(object):
         samples (model.py:592-626).  Eager counterpart of running the
         reference's proba op together with `net.push_ops` (push=True) or
         alone (push=False); `net.reset_generator()` is `net.init_ops`.'''
+        self._no_lc_fastgen('predict_proba_incremental')
         return fastgen.predict_proba_incremental(self, waveform,
                                                  global_condition, push)
 
     def reset_generator(self):
         """net.init_ops: refill every queue with zeros (model.py:457-479)."""
+        self._no_lc_fastgen('reset_generator')
         fastgen.generator(self, None)
         fastgen.reset(self)
 
@@ -1451,6 +1635,7 @@ class WaveNetModel(object):
         test_model.py:63), then draw `num_samples` samples with temperature.
         Returns int32 codes [len(seed) + num_samples] (and the probabilities
         of every `return_proba_every`-th step when requested)."""
+        self._no_lc_fastgen('generate')
         return fastgen.generate(self, num_samples, seed_samples, temperature,
                                 global_condition, seed, return_proba_every)
 
@@ -1460,6 +1645,7 @@ class WaveNetModel(object):
         ONE batch forward pass: layer l's queue (capacity d_l) holds the last
         d_l inputs x_l[t] of that layer (model.py:473-484), which are rows of
         the forward pass's per-layer activation planes."""
+        self._no_lc_fastgen('prime_generator')
         fastgen.prime(self, codes, global_condition)
 
     def continue_generation(self, num_samples, last_sample, temperature=1.0,
@@ -1467,6 +1653,7 @@ class WaveNetModel(object):
         """Draw `num_samples` more samples after `generate` (the queues stay
         on the device; `last_sample` is the last code drawn so far, which has
         not been pushed yet).  Returns the new int32 codes."""
+        self._no_lc_fastgen('continue_generation')
         return fastgen.continue_generation(self, num_samples, last_sample,
                                            temperature, global_condition, seed)
 
@@ -1481,6 +1668,7 @@ class WaveNetModel(object):
         shared by all streams, or [B, n]; global_condition: None, one id, or
         B ids.  Returns int32 [B, n + num_samples] (and float32
         [B, ceil(steps / k), Q] probabilities with return_proba_every = k)."""
+        self._no_lc_fastgen('generate_batch')
         return fastgen.generate_batch(self, num_samples, seeds, seed_samples,
                                       temperature, global_condition,
                                       return_proba_every)
@@ -1492,6 +1680,7 @@ class WaveNetModel(object):
         generate_batch call (the queues stay on the device; last_samples[b]
         is stream b's last code so far, not yet pushed).  Returns int32
         [B, num_samples] (and the probabilities, as generate_batch)."""
+        self._no_lc_fastgen('continue_generation_batch')
         return fastgen.continue_generation_batch(
             self, num_samples, last_samples, seeds, temperature,
             global_condition, return_proba_every)

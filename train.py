@@ -96,6 +96,16 @@ def get_arguments(argv=None):
                    help='Train on synthetic sine clips (no --data_dir needed).')
     p.add_argument('--gc_cardinality', type=int, default=None,
                    help='Only with --synthetic: number of speaker ids.')
+    p.add_argument('--lc_channels', type=int, default=None,
+                   help='Local conditioning: channels of the per-sample '
+                        'features, read from <clip>.npy [frames, channels] '
+                        'next to every wav (random features with '
+                        '--synthetic).  Feature row t conditions the '
+                        'prediction of sample t + 1.')
+    p.add_argument('--lc_hop', type=int, default=None,
+                   help='Local conditioning: audio samples per feature frame '
+                        '(frames are upsampled by repetition).  Default 1 '
+                        'with --synthetic.')
     return p.parse_args(argv)
 
 
@@ -185,11 +195,13 @@ def validate_directories(args):
 class SyntheticReader(object):
     """Sine-plus-noise clips of `sample_size` samples (BASELINE.md data)."""
 
-    def __init__(self, sample_size, gc_cardinality=None, rank=0, seed=1234):
+    def __init__(self, sample_size, gc_cardinality=None, rank=0, seed=1234,
+                 lc_channels=None, lc_hop=1):
         self.T, self.card = sample_size, gc_cardinality
         self.rng = np.random.default_rng(seed + rank)
         self.gc_category_cardinality = gc_cardinality
         self.count = rank * 1000003
+        self.lc_channels, self.lc_hop = lc_channels, lc_hop
 
     def _clip(self):
         self.count += 1
@@ -207,6 +219,15 @@ class SyntheticReader(object):
     def dequeue_gc(self, n):
         return torch.tensor([(37 * i) % self.card for i in self._last_ids],
                             dtype=torch.int32)
+
+    def dequeue_lc(self, n):
+        """Random frame-rate features upsampled by repetition: [n, T, Lc]."""
+        from wavenet.audio_reader import upsample_lc
+        frames = (self.T + self.lc_hop - 1) // self.lc_hop
+        return torch.from_numpy(np.stack([
+            upsample_lc(self.rng.standard_normal(
+                (frames, self.lc_channels)).astype(np.float32),
+                self.lc_hop, self.T) for _ in range(n)]))
 
     def start_threads(self, *a, **k):
         return []
@@ -242,17 +263,25 @@ def main(argv=None):
     # trimming.
     silence_threshold = args.silence_threshold
     gc_enabled = args.gc_channels is not None
+    lc_enabled = args.lc_channels is not None
     if args.synthetic:
         reader = SyntheticReader(args.sample_size,
                                  args.gc_cardinality if gc_enabled else None,
-                                 rank=rank)
+                                 rank=rank, lc_channels=args.lc_channels,
+                                 lc_hop=args.lc_hop or 1)
     else:
+        if lc_enabled and not args.lc_hop:
+            print('--lc_channels needs --lc_hop (audio samples per feature '
+                  'frame)')
+            return 1
         reader = AudioReader(args.data_dir, coord,
                              sample_rate=wavenet_params['sample_rate'],
                              gc_enabled=gc_enabled,
                              sample_size=args.sample_size,
                              silence_threshold=silence_threshold,
-                             rank=rank, world=world, seed=rank)
+                             rank=rank, world=world, seed=rank,
+                             lc_channels=args.lc_channels,
+                             lc_hop=args.lc_hop)
 
     net = WaveNetModel(
         batch_size=args.batch_size,
@@ -268,7 +297,8 @@ def main(argv=None):
         histograms=args.histograms,
         global_condition_channels=args.gc_channels,
         global_condition_cardinality=reader.gc_category_cardinality,
-        residual_postproc=wavenet_params.get("residual_postproc", False))
+        residual_postproc=wavenet_params.get("residual_postproc", False),
+        local_condition_channels=args.lc_channels)
     l2 = args.l2_regularization_strength or None
     optimizer = optimizer_factory[args.optimizer](
         learning_rate=args.learning_rate, momentum=args.momentum)
@@ -378,8 +408,9 @@ def main(argv=None):
             try:
                 audio = reader.dequeue(args.batch_size)
                 gc = reader.dequeue_gc(args.batch_size) if gc_enabled else None
+                lc = reader.dequeue_lc(args.batch_size) if lc_enabled else None
             except Exception as e:        # e.g. a reader-thread failure
-                err, audio, gc = e, None, None
+                err, audio, gc, lc = e, None, None, None
             n_t, all_ok = parallel.agree_step(
                 audio.shape[1] if err is None else 0, err is None, net.device)
             if not all_ok:
@@ -389,6 +420,8 @@ def main(argv=None):
             if n_t < 2:
                 continue
             audio = audio[:, :n_t]
+            if lc is not None:
+                lc = lc[:, :n_t]
             if audio.device.type == 'cpu' and net.device.type == 'cuda':
                 # pinned staging + asynchronous copy: a pageable host tensor
                 # handed to net.loss is copied synchronously BEHIND the previous
@@ -404,7 +437,8 @@ def main(argv=None):
                                 torch.profiler.ProfilerActivity.CUDA])
                 prof.__enter__()
             loss = net.loss(input_batch=audio, global_condition_batch=gc,
-                            l2_regularization_strength=l2)
+                            l2_regularization_strength=l2,
+                            local_condition_batch=lc)
             optimizer.minimize(loss)
             # The reference fetches the loss inside sess.run and so waits for
             # every step (train.py:300-311).  Here the step is queued on the
