@@ -166,7 +166,8 @@ def _prime(net, g, n0, groups, Bp):
     ws = net._workspace(1, n0, False)
     for codes, gc, streams in groups:
         ws.q.copy_(codes)
-        net._forward(ws, net._gc_ids(gc, 1), save_ts=0)
+        net._run_pass('fwd', ws, net._gc_ids(gc, 1),
+                      net._step_path(ws, False))
         # (+ the forward launch's poison word: 0, or NaN after an expired wait)
         vals = ws.X.reshape(-1, CH).index_select(0, src) + ws.loss_parts[0]
         rows = dst[None, :] * Bp + np.asarray(streams, np.int64)[:, None]

@@ -16,6 +16,7 @@ MI355X-first design:
 There is no CPU / PyTorch compute fallback: without the HIP library or a GPU
 every entry point raises.
 """
+import collections
 import math
 import os
 
@@ -29,6 +30,26 @@ from .ops import mu_law_encode, mu_law_decode, mu_law_tables
 CH = 32                      # channels per activation plane (one block)
 # layer block (floats) for filter width K and C = 32 * blocks padded channels:
 #   Wf[K][C][C] Wg[K][C][C] Wd[C][C] bf[C] bg[C] bd[C] (+ gc weights [G][C] x 2)
+
+
+# Beside the backward stack of a very small batch (256 - 512 32-row tiles) the
+# side stream's TN GEMMs run this fraction of their splits: fewer, longer
+# workgroups disturb the stack's dependent chain less (B = 1, T = 16000, 500
+# tiles: 1.89 -> 1.80 ms per step at 0.6; 0.75 and 0.4 lose; at B = 2 nothing
+# changes; at most one tile per CU is too short for it to matter)
+TN_SIDE_SPLIT_FRAC = 0.6
+
+# What one loss() / predict_proba() call launches, decided once per call by
+# WaveNetModel._step_path and the key of its launch plans: the residual stack's
+# forward `fwd` ('stack' | 'stack_skip' | 'stack_lc' persistent launches, or
+# 'layer' | 'layer_k' | 'blocked' per layer) and backward `bwd` (None, 'stack' |
+# 'stack_lc' | 'layer2' | 'layer_k' | 'blocked'), the saved planes `save_ts`
+# (0 | 1: tanh + sigmoid | 2: sigmoid), and `pack_both` (the forward's
+# wn_stack_pack writes the backward image too), `overlap_tn` (TN GEMMs on the
+# side stream), `early_allreduce`, `causal_wgrad`, `gemm_mode`, `variant`.
+StepPath = collections.namedtuple('StepPath', [
+    'fwd', 'save_ts', 'bwd', 'pack_both', 'overlap_tn', 'early_allreduce',
+    'causal_wgrad', 'gemm_mode', 'variant'])
 
 
 def layer_w(K, C=CH):
@@ -64,10 +85,13 @@ class _Workspace(object):
         N = B * T
         f32 = dict(dtype=torch.float32, device=dev)
         self.B, self.T, self.N, self.training = B, T, N, training
-        # (the variant word of the stack launches is fixed per workspace)
+        # (the variant word of the stack launches is fixed per workspace, and so
+        # is the library's answer whether wn_stack_fwd_skip covers the shape)
         self.stack_variant = net._stack_variant_for_launch()
         self.capacity = N if parent is None else parent.capacity
         lib = _lib.load()
+        self.fwd_skip_ok = bool(lib.wn_stack_fwd_skip_ok(B, T, S,
+                                                         self.stack_variant))
 
         def alloc(name, shape, dtype=torch.float32, fill=None):
             n = int(np.prod(shape))
@@ -129,7 +153,7 @@ class _Workspace(object):
         # the generic-tap / channel-block backward kernels also need the tanh
         # plane and two ping-pong pairs of pre-activation-gradient planes; the
         # default wn_stack_bwd / wn_layer_bwd2 do not
-        self.legacy = net._legacy_bwd()
+        self.legacy = net._layer_path() != 'layer'
         self.TH = alloc('TH', (LP, N, CH)) if self.legacy else None
         alloc('SG', (LP, N, CH))
         alloc('dZ', (LP, N, CH))
@@ -146,8 +170,7 @@ class _Workspace(object):
         # tests/test_gpu_stack.py (`net.stack_bwd_keep_dx`) keep dL/dx_l of
         # EVERY layer.  Plus the q planes, flags and control block (allocated
         # whenever the option could apply)
-        self.stack_bwd = (net.stack_bwd and not net.blocked and not net.generic_layers
-                          and L <= 256 and N * CH * 4 < 2 ** 31)
+        self.stack_bwd = bool(net.stack_bwd and net._stack_ok(N))
         if self.stack_bwd:
             self.keep_dx = bool(net.stack_bwd_keep_dx)
             if parent is not None and getattr(parent, 'DX', None) is not None:
@@ -313,13 +336,9 @@ class WaveNetModel(object):
         # 2.94 -> 2.89; neutral at B = 4, 1 % SLOWER at B = 8).  True / False
         # force it.
         self.overlap_tn = None
-        self.overlap_tn_split_frac = 0.6
         # channel-block models (33 - 128 channels): dz and the gate gradients
         # in one launch (False: two launches, A/B and tests; bitwise equal)
         self.wide_fuse_gate = True
-        # column sums (bias gradients) of the weight-gradient GEMMs spread over
-        # all tile rows of a split (False: one owner tile row, A/B)
-        self.tn_spread_colsum = True
         # forward of the residual stack as ONE persistent launch
         # (wn_stack_fwd: tiles stay in registers from layer to layer, the
         # dilated taps are handed over through per-tile flags) instead of one
@@ -343,13 +362,13 @@ class WaveNetModel(object):
         # data-parallel runs (wavenet/parallel.py): start the all-reduce of the
         # skip / post-processing gradients -- 82 % of the bucket, complete
         # before the backward stack launch -- from inside the backward pass,
-        # on a communication stream beside that launch.  The training loop
-        # switches it on: it promises that optimizer.minimize (which joins)
+        # on a communication stream beside that launch.  Opt-in (train.py
+        # --dp_overlap_allreduce; bench.py times it as a trial): whoever
+        # switches it on promises that optimizer.minimize (which joins)
         # follows every loss().  Ignored outside torch.distributed and when L2
         # regularisation is on.
         self.dp_overlap_allreduce = False
         self._tail_work = None
-        self._early_ok = False
         # generate(): four kernels per sample over many CUs, replayed from a
         # hipGraph, instead of the single-workgroup persistent kernel
         self.fastgen_multi_cu = True
@@ -374,9 +393,9 @@ class WaveNetModel(object):
         # replay recorded (function, args) launch sequences instead of
         # re-deriving ~235 argument lists per step in Python
         self.use_launch_plans = True
-        # causal-layer weight gradient as a segmented sum (K = 2, Q <= 256)
-        # instead of two one-hot MFMA contractions
-        self.causal_wgrad_segsum = True
+        # bench.py's live roofline: a list collects (start, end, flops, name)
+        # HIP events of the timed launches (_lib.call_timed); None: untimed
+        self._gemm_events = None
         # seeds longer than this are primed from ONE batch forward pass
         # instead of one incremental step per seed sample
         self.fastgen_prime_forward_min = 64
@@ -698,11 +717,54 @@ class WaveNetModel(object):
             return bool(self.overlap_tn)
         return ws.B * ((ws.T + 31) // 32) <= 1024 and not self.blocked
 
-    def _early_on(self):
-        """The tail all-reduce starts inside this step's backward pass."""
+    def _layer_path(self):
+        """The per-layer kernels: 'blocked' (channel blocks), 'layer_k'
+        (generic taps, or `generic_layers` forced) or 'layer' (two taps, which
+        alone can run the persistent stack launches instead)."""
+        return 'blocked' if self.blocked else \
+            'layer_k' if self.generic_layers else 'layer'
+
+    def _stack_ok(self, N=None):
+        """The persistent stack launches cover the model's layers and, given
+        N = B * T, its rows (the backward's 32-bit plane offsets)."""
+        return (self._layer_path() == 'layer' and self.L <= 256 and
+                (N is None or N * CH * 4 < 2 ** 31))
+
+    def _stack_bwd_ok(self):
+        """wn_stack_bwd covers what wn_layer_bwd2 covers."""
+        return bool(self.stack_bwd and self._stack_ok())
+
+    def _step_path(self, ws, backward, l2=False):
+        """The StepPath of one call on workspace `ws`, from the model's
+        switches as they are now and the ones `ws` froze (stack_bwd, the
+        variant word).  l2: L2 regularisation is on (it adds to the whole
+        bucket after the backward pass: the tail all-reduce must wait)."""
+        layers, lc = self._layer_path(), '_lc' if self.Lc else ''
+        fwd = layers
+        if self.stack_fwd and self._stack_ok():
+            # (small batches: the skip sum inside the stack launch)
+            skip = (self.stack_fwd_skip and self.gemm_mode == 'fp32' and
+                    not self.residual_postproc and ws.fwd_skip_ok)
+            fwd = 'stack_skip' if skip else 'stack' + lc
+        if not backward:
+            return StepPath(fwd, 0, None, False, False, False, None,
+                            self.gemm_mode, ws.stack_variant)
+        bwd = layers
+        if layers == 'layer':
+            bwd = 'stack' + lc if self._stack_bwd_ok() and ws.stack_bwd \
+                else 'layer2'
+        if self.Lc and bwd != 'stack_lc':
+            # (a training workspace reserved while stack_bwd was off)
+            raise NotImplementedError(self.LC_SUPPORTED)
         from . import parallel
-        return bool(self.dp_overlap_allreduce and self._early_ok
-                    and parallel.is_distributed())
+        early = bool(self.dp_overlap_allreduce and not l2 and
+                     parallel.is_distributed())
+        causal = (None if layers == 'blocked' else 'scalar' if self.scalar_input
+                  else 'segsum' if self.KW == 2 and self.Q <= 256 else 'onehot')
+        return StepPath(fwd, 2 if layers == 'layer' else 1, bwd,
+                        fwd.startswith('stack') and bwd.startswith('stack'),
+                        self._overlap_tn_on(ws), early, causal,
+                        self.gemm_mode, ws.stack_variant)
 
     def _early_allreduce(self):
         from . import parallel
@@ -714,13 +776,6 @@ class WaveNetModel(object):
             # kernels on the main stream are the critical path
             self._side = torch.cuda.Stream(device=self.device, priority=0)
         return self._side
-
-    def _legacy_bwd(self):
-        """The generic-tap (filter_width > 2) and channel-block (> 32 channels)
-        models: their backward keeps the tanh plane and ping-pong
-        pre-activation-gradient planes; the default-width two-tap model runs
-        wn_stack_bwd / wn_layer_bwd2, which do not."""
-        return self.generic_layers or self.blocked
 
     def check_device_errors(self):
         """Raise if a persistent stack launch recorded an expired dependency
@@ -752,19 +807,6 @@ class WaveNetModel(object):
                     ctl[3] = 0
             ws.loss_parts[:2] = 0.0
 
-    def _bwd_image_with_fwd(self, ws):
-        """True when the training forward runs the persistent stack launch and
-        the backward will too: wn_stack_pack then writes both weight images in
-        the forward's launch (the parameters do not change in between)."""
-        return bool(self.stack_fwd and not self.blocked and not self.generic_layers
-                    and self.L <= 256 and not self._legacy_bwd()
-                    and self._stack_bwd_ok() and getattr(ws, 'stack_bwd', False)
-                    and getattr(ws, 'wimg_b', None) is not None)
-
-    def _stack_bwd_ok(self):
-        """wn_stack_bwd covers what wn_layer_bwd2 covers."""
-        return self.stack_bwd and not self._legacy_bwd() and self.L <= 256
-
     def _check_supported(self):
         if self._unsupported:
             raise NotImplementedError(self._unsupported)
@@ -776,8 +818,8 @@ class WaveNetModel(object):
     def _workspace(self, B, T, training):
         key = (B, T, bool(training))
         ws = self._ws.get(key)
-        if ws is not None and training and self._legacy_bwd() and \
-                not ws.legacy:
+        if ws is not None and training and self._layer_path() != 'layer' \
+                and not ws.legacy:
             self._ws = {}          # switched to a legacy backward: re-allocate
             ws = None
         if ws is not None:
@@ -799,7 +841,7 @@ class WaveNetModel(object):
             if prev and not training:
                 t_alloc = max(T, min(2 * max(w.T for w in prev), 1 << 20))
             self._ws = {k: w for k, w in self._ws.items()
-                        if self._owner_kind(w) != bool(training)}
+                        if w.training != bool(training)}
             owner = _Workspace(self, B, t_alloc, training)
             self._ws[(B, t_alloc, bool(training))] = owner
             ws = owner if t_alloc == T else \
@@ -811,10 +853,6 @@ class WaveNetModel(object):
             self._ws = owners
             self._ws[key] = ws
         return ws
-
-    @staticmethod
-    def _owner_kind(ws):
-        return bool(ws.training)
 
     def reserve(self, batch_size, max_samples, training=False):
         """Allocate the workspace for up to `max_samples` samples per clip now
@@ -839,9 +877,10 @@ class WaveNetModel(object):
         return ids.contiguous()
 
     def _lc_rows(self, local_condition, B, T, what):
-        """Validate the local-conditioning rows of a call ([B, T, Lc], float)
-        before anything is launched; returns them as a float32 tensor on the
-        device, or None for a model without LC."""
+        """Validate a call's local-conditioning rows ([B, T, Lc], float) and
+        that the persistent 32-row stack launches, the only ones an LC model
+        runs, cover the call -- before anything is allocated or launched.
+        Returns the rows as float32 on the device (None without LC)."""
         if not self.Lc:
             if local_condition is not None:
                 raise ValueError('%s: this model was built without local '
@@ -864,22 +903,17 @@ class WaveNetModel(object):
         if lc.is_floating_point() is False:
             raise ValueError('%s: local conditioning must be floating point'
                              % what)
-        return lc.to(device=self.device, dtype=torch.float32)
-
-    def _check_lc_paths(self):
-        """An LC model runs the persistent 32-row stack launches only."""
-        if self.Lc and not (self.stack_fwd and self.stack_bwd):
+        if not (self.stack_fwd and self.stack_bwd):
             raise NotImplementedError(
                 'stack_fwd / stack_bwd = False with local conditioning: '
                 + self.LC_SUPPORTED)
-
-    def _stage_lc(self, ws, lc):
-        if lc is not None:
-            if not (ws.N * CH * 4 < 2 ** 31 and self.L <= 256):
-                raise NotImplementedError(
-                    'local conditioning needs B * T < 2^24 and at most 256 '
-                    'layers (the persistent stack launches)')
-            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
+        if self._layer_path() != 'layer':       # (generic_layers forced)
+            raise NotImplementedError(self.LC_SUPPORTED)
+        if not self._stack_ok(B * T):
+            raise NotImplementedError(
+                'local conditioning needs B * T < 2^24 and at most 256 '
+                'layers (the persistent stack launches)')
+        return lc.to(device=self.device, dtype=torch.float32)
 
     def _layer_block(self, flat, l):
         o, _ = self.segments['layers']
@@ -932,15 +966,9 @@ class WaveNetModel(object):
                 args = args[:-1] + (_lib.ptr(buf), nprod, args[-1])
         k = -7 if name == 'wn_gemm_nn_split' else -5
         _lib.call_timed(name, args, 2.0 * args[k] * args[k + 1] * args[k + 2],
-                        getattr(self, '_gemm_events', None))
+                        self._gemm_events)
 
     # ------------------------------------------------------------ launch plans
-    def _plan_key(self, tag, ws, ids, extra):
-        return (tag, extra, ids is not None, self.generic_layers,
-                self.overlap_tn,
-                self.overlap_tn_split_frac, self.wide_fuse_gate, self.tn_spread_colsum, self.stack_fwd, self.stack_fwd_skip, self.stack_bwd, ws.stack_variant, self._early_on(), self.gemm_mode, self.causal_wgrad_segsum, self.tf_xent_zero_label_quirk,
-                _lib.stream(), self.params.data_ptr(), self.grads.data_ptr())
-
     def _stage_ids(self, ws, ids):
         """GC ids into a workspace-owned buffer, so that recorded launch
         arguments never point at a caller's temporary."""
@@ -950,143 +978,69 @@ class WaveNetModel(object):
             ws.gc_ids.copy_(ids)
         return ws.gc_ids
 
-    def _forward(self, ws, ids, save_ts):
-        """Forward pass through a recorded launch plan (see _lib.record)."""
+    def _run_pass(self, tag, ws, ids, path):
+        """The forward ('fwd') or backward ('bwd') pass through a recorded
+        launch plan (see _lib.record), keyed by the call's StepPath."""
+        eager = self._forward_eager if tag == 'fwd' else self._backward_eager
         ids = self._stage_ids(ws, ids)
-        if not self.use_launch_plans:
-            return self._forward_eager(ws, ids, save_ts)
-        key = self._plan_key('fwd', ws, ids, save_ts)
+        if not self.use_launch_plans or (tag == 'bwd' and path.bwd == 'blocked'):
+            # (the channel-block backward's gradient-block copies are torch
+            # ops a launch plan cannot replay)
+            return eager(ws, ids, path)
+        key = (tag, path, ids is not None, _lib.stream(),
+               self.params.data_ptr(), self.grads.data_ptr())
         plan = ws.plans.get(key, 0)
         if plan == 0:                 # first use of this workspace: eager
             ws.plans[key] = None
-            self._forward_eager(ws, ids, save_ts)
+            eager(ws, ids, path)
         elif plan is None:            # second use: record while executing
             with _lib.record() as rec:
-                self._forward_eager(ws, ids, save_ts)
+                eager(ws, ids, path)
             ws.plans[key] = rec.plan
         else:
-            _lib.replay(plan, getattr(self, '_gemm_events', None))
-
-    def _backward(self, ws, ids):
-        ids = self._stage_ids(ws, ids)
-        if not self.use_launch_plans or self.blocked:
-            # (the channel-block path, whose gradient-block copies are torch ops
-            # a launch plan cannot replay)
-            return self._backward_eager(ws, ids)
-        key = self._plan_key('bwd', ws, ids, None)
-        plan = ws.plans.get(key, 0)
-        if plan == 0:
-            ws.plans[key] = None
-            self._backward_eager(ws, ids)
-        elif plan is None:
-            with _lib.record() as rec:
-                self._backward_eager(ws, ids)
-            ws.plans[key] = rec.plan
-        else:
-            _lib.replay(plan, getattr(self, '_gemm_events', None))
+            _lib.replay(plan, self._gemm_events)
 
     # ------------------------------------------------------------------ forward
-    def _forward_eager(self, ws, ids, save_ts):
+    def _forward_eager(self, ws, ids, path):
         """_create_network (model.py:389-442) on codes ws.q -> ws.logits."""
         st = _lib.stream()
         B, T, N, L, S, Q = ws.B, ws.T, ws.N, self.L, self.S, self.Q
         P = self.params
-        if self.scalar_input:
-            wc = self._seg(P, 'causal')
-            for cb in range(self.CB):          # one plane per channel block
+        wc = self._seg(P, 'causal')
+        for cb in range(self.CB):              # one plane per channel block
+            if self.scalar_input:
                 _lib.call('wn_scalar_causal_fwd', _lib.ptr(ws.audio),
                           _lib.ptr(wc[cb * CH:]), self.CHn, _lib.ptr(ws.X[cb]),
                           B, T, self.initial_filter_width, st)
-        else:
-            wc = self._seg(P, 'causal')
-            for cb in range(self.CB):          # one plane per channel block
+            else:
                 _lib.call('wn_causal_gather', _lib.ptr(ws.q),
                           _lib.ptr(wc[cb * CH:]), _lib.ptr(ws.X[cb]), B, T, Q,
                           self.KW, self.CHn, st)
         bias, bstride = self._bias_fg(ws.bias_fg, ids, B)
-        if self.blocked:
+        save_ts = path.save_ts
+        if path.fwd == 'blocked':
             from . import blocked
             blocked.forward_layers(self, ws, bias, bstride, bool(save_ts), st)
-        stack = (self.stack_fwd and not self.blocked and not self.generic_layers
-                 and save_ts in (0, 2) and L <= 256)
-        fuse_skip = False
-        if stack:
-            # all L layers in one persistent launch (csrc/wn_stack.hip)
-            # (its transposed weight images, one small launch per call)
-            # (a training forward packs the backward stack's image in the
-            # same launch: one launch per step instead of two)
-            both = save_ts == 2 and self._bwd_image_with_fwd(ws)
-            _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(P, 0)),
-                      self.layer_stride, _lib.ptr(ws.wimg_f),
-                      _lib.ptr(ws.wimg_b) if both else None, L, st)
-            stack_args = (_lib.ptr(ws.X), _lib.ptr(ws.Z),
-                          _lib.ptr(ws.SG) if save_ts else None,
-                          _lib.ptr(ws.wimg_f),
-                          None if bias is None else _lib.ptr(bias),
-                          0 if bias is None else bias.shape[1] * bias.shape[2],
-                          bstride, _lib.ptr(self._dil_dev),
-                          _lib.ptr(ws.stack_flags), _lib.ptr(ws.stack_ctl),
-                          _lib.ptr(ws.loss_parts),
-                          L, B, T, 1 if save_ts else 0, ws.stack_variant)
-            # small batches: the skip sum h1 = relu(sum_l z_l Ws_l + sum_l bs_l)
-            # inside the stack launch (wn_stack_fwd_skip: a partner wave per
-            # tile; the launch's matrix pipe is three quarters idle otherwise)
-            fuse_skip = bool(
-                self.stack_fwd_skip and self.gemm_mode == 'fp32' and
-                not self.residual_postproc and
-                _lib.load().wn_stack_fwd_skip_ok(B, T, S, ws.stack_variant))
-            if fuse_skip:
-                if getattr(ws, 'skimg', None) is None:
-                    ws.skimg = torch.empty(
-                        int(_lib.load().wn_stack_skip_img_floats(L)),
-                        dtype=torch.float32, device=self.device)
-                bsum_f = None
-                if self.use_biases:
-                    _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), L,
-                              S, _lib.ptr(ws.bsum), st)
-                    bsum_f = ws.bsum
-                _lib.call('wn_stack_skip_pack', _lib.ptr(self._seg(P, 'skip_w')),
-                          L, _lib.ptr(ws.skimg), st)
-                _lib.call_timed('wn_stack_fwd_skip', stack_args + (
-                    _lib.ptr(ws.skimg), _lib.ptr(bsum_f), _lib.ptr(ws.h1), st),
-                    0.0, getattr(self, '_gemm_events', None))
-            elif self.Lc:
-                # local conditioning: the per-row filter | gate addends of all
-                # layers, lc [N][Lcp] x lc_w [Lcp][L * 64], then the stack
-                # launch that adds them (32-row tiles: the workspace's variant)
-                W64 = L * 64
-                _lib.call_timed('wn_gemm_nn', (
-                    _lib.ptr(ws.lc), self.Lcp, 0, 0,
-                    _lib.ptr(self._seg(P, 'lc_w')), W64, None, None, 0, None,
-                    0, _lib.ptr(ws.lc_add), W64, 0, 0, None, N, W64, self.Lcp,
-                    0, st), 2.0 * N * W64 * self.Lcp,
-                    getattr(self, '_gemm_events', None))
-                _lib.call_timed('wn_stack_fwd_lc', stack_args + (
-                    _lib.ptr(ws.lc_add), W64, st), 0.0,
-                    getattr(self, '_gemm_events', None))
-            else:
-                # (flops 0: timed in bench.py's instrumented pass for its HBM roofline)
-                _lib.call_timed('wn_stack_fwd', stack_args + (st,), 0.0,
-                                getattr(self, '_gemm_events', None))
-        if self.Lc and not stack:
-            raise NotImplementedError(self.LC_SUPPORTED)
-        for l, d in enumerate(self.dilations if not self.blocked and not stack
-                              else []):
-            last = l == L - 1
-            fargs = (_lib.ptr(ws.X[l]),
-                     None if last else _lib.ptr(ws.X[l + 1]),
-                     _lib.ptr(ws.Z[l]),
-                     _lib.ptr(ws.TH[l]) if save_ts == 1 else None,
-                     _lib.ptr(ws.SG[l]) if save_ts else None,
-                     _lib.ptr(self._layer_block(P, l)),
-                     None if bias is None else _lib.ptr(bias[l]), bstride,
-                     B, T, int(d))
-            if self.generic_layers:
-                _lib.call('wn_layer_fwd_k', *fargs, self.KW,
-                          0 if last else 1, 1 if save_ts else 0, st)
-            else:
-                _lib.call('wn_layer_fwd', *fargs, 0 if last else 1,
-                          int(save_ts), st)
+        elif path.fwd.startswith('stack'):
+            self._fwd_stack(ws, path, bias, bstride, st)
+        else:                      # 'layer' / 'layer_k': one launch per layer
+            for l, d in enumerate(self.dilations):
+                last = l == L - 1
+                fargs = (_lib.ptr(ws.X[l]),
+                         None if last else _lib.ptr(ws.X[l + 1]),
+                         _lib.ptr(ws.Z[l]),
+                         _lib.ptr(ws.TH[l]) if save_ts == 1 else None,
+                         _lib.ptr(ws.SG[l]) if save_ts else None,
+                         _lib.ptr(self._layer_block(P, l)),
+                         None if bias is None else _lib.ptr(bias[l]), bstride,
+                         B, T, int(d))
+                if path.fwd == 'layer_k':
+                    _lib.call('wn_layer_fwd_k', *fargs, self.KW,
+                              0 if last else 1, 1 if save_ts else 0, st)
+                else:
+                    _lib.call('wn_layer_fwd', *fargs, 0 if last else 1,
+                              int(save_ts), st)
+        fuse_skip = path.fwd == 'stack_skip'
         bsum = None
         if self.use_biases and not fuse_skip:
             _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), L, S,
@@ -1113,80 +1067,91 @@ class WaveNetModel(object):
              _lib.ptr(self._seg(P, 'post2_w')), Q, _lib.ptr(b2), None, 0,
              None, 0, _lib.ptr(ws.logits), Q, 0, 0, None, N, Q, S, 0)])
 
+    def _fwd_stack(self, ws, path, bias, bstride, st):
+        """All L layers in one persistent launch (csrc/wn_stack.hip) behind
+        their transposed weight images (wn_stack_pack, one small launch)."""
+        B, T, N, L, S = ws.B, ws.T, ws.N, self.L, self.S
+        P = self.params
+        _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(P, 0)),
+                  self.layer_stride, _lib.ptr(ws.wimg_f),
+                  _lib.ptr(ws.wimg_b) if path.pack_both else None, L, st)
+        save = path.save_ts != 0
+        stack_args = (_lib.ptr(ws.X), _lib.ptr(ws.Z),
+                      _lib.ptr(ws.SG) if save else None,
+                      _lib.ptr(ws.wimg_f),
+                      None if bias is None else _lib.ptr(bias),
+                      0 if bias is None else bias.shape[1] * bias.shape[2],
+                      bstride, _lib.ptr(self._dil_dev),
+                      _lib.ptr(ws.stack_flags), _lib.ptr(ws.stack_ctl),
+                      _lib.ptr(ws.loss_parts),
+                      L, B, T, 1 if save else 0, ws.stack_variant)
+        # (flops 0: timed in bench.py's instrumented pass for its HBM roofline)
+        if path.fwd == 'stack_skip':
+            # small batches: the skip sum h1 = relu(sum_l z_l Ws_l + sum_l bs_l)
+            # inside the stack launch (wn_stack_fwd_skip: a partner wave per
+            # tile; the launch's matrix pipe is three quarters idle otherwise)
+            if getattr(ws, 'skimg', None) is None:
+                ws.skimg = torch.empty(
+                    int(_lib.load().wn_stack_skip_img_floats(L)),
+                    dtype=torch.float32, device=self.device)
+            bsum_f = None
+            if self.use_biases:
+                _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), L,
+                          S, _lib.ptr(ws.bsum), st)
+                bsum_f = ws.bsum
+            _lib.call('wn_stack_skip_pack', _lib.ptr(self._seg(P, 'skip_w')),
+                      L, _lib.ptr(ws.skimg), st)
+            _lib.call_timed('wn_stack_fwd_skip', stack_args + (
+                _lib.ptr(ws.skimg), _lib.ptr(bsum_f), _lib.ptr(ws.h1), st),
+                0.0, self._gemm_events)
+        elif path.fwd == 'stack_lc':
+            # local conditioning: the per-row filter | gate addends of all
+            # layers, lc [N][Lcp] x lc_w [Lcp][L * 64], then the stack
+            # launch that adds them (32-row tiles: the workspace's variant)
+            W64 = L * 64
+            _lib.call_timed('wn_gemm_nn', (
+                _lib.ptr(ws.lc), self.Lcp, 0, 0,
+                _lib.ptr(self._seg(P, 'lc_w')), W64, None, None, 0, None,
+                0, _lib.ptr(ws.lc_add), W64, 0, 0, None, N, W64, self.Lcp,
+                0, st), 2.0 * N * W64 * self.Lcp, self._gemm_events)
+            _lib.call_timed('wn_stack_fwd_lc', stack_args + (
+                _lib.ptr(ws.lc_add), W64, st), 0.0, self._gemm_events)
+        else:
+            _lib.call_timed('wn_stack_fwd', stack_args + (st,), 0.0,
+                            self._gemm_events)
+
     # ------------------------------------------------------------------ backward
-    def _backward_eager(self, ws, ids):
+    def _backward_eager(self, ws, ids, path):
         """Hand-written gradient of loss() (the reference uses TF autodiff of
         model.py:628-685).  Consumes ws.logits == dlogits (in place)."""
         st = _lib.stream()
-        B, T, N, L, S, Q = ws.B, ws.T, ws.N, self.L, self.S, self.Q
+        self._bwd_post(ws, path, st)
+        if path.bwd == 'blocked':
+            # channel-block path: residual stack, causal layer and global
+            # conditioning gradients (wavenet/blocked.py)
+            from . import blocked
+            if path.overlap_tn:
+                main_s = torch.cuda.current_stream()
+                _lib.call_py(lambda: main_s.wait_event(ws.ev_join))
+            blocked.backward_layers(self, ws, ids, st)
+            return
+        # residual stack, last layer first, down to dL/dx_0
+        run = {'layer2': self._bwd_layer2,
+               'layer_k': self._bwd_layer_k}.get(path.bwd, self._bwd_stack)
+        self._backward_tail(ws, ids, path, run(ws, path, st))
+
+    def _bwd_post(self, ws, path, st):
+        """The data gradients first -- dc1 = (dlogits W2^T) * [c1 > 0],
+        dtotal = (dc1 W1^T) * [total > 0] (+ dh2 when residual_postproc),
+        dZ planes = dtotal Ws_all^T -- as ONE chained launch (a 128-row block
+        of a GEMM starts when that row block of the previous one is stored),
+        then the three weight-gradient (TN) GEMMs, whose operands all exist
+        by then: dW2 = h2^T dlogits, dW1 = h1^T dc1, dWs_all = Z^T dtotal
+        (+ column sums = the bias gradients)."""
+        N, L, S, Q = ws.N, self.L, self.S, self.Q
         P, Gr = self.params, self.grads
-        ub = 1 if self.use_biases else 0
         rp = self.residual_postproc
         dlog = ws.logits
-        lib = _lib.load()
-
-        deferred = []          # TN GEMMs postponed to the side stream
-        ovl = self._overlap_tn_on(ws)
-
-        def tn(*a, **kw):
-            if ovl:
-                deferred.append((a, kw))
-            else:
-                tn_now(st, ws.slabs, *a, **kw)
-
-        def tn_now(st, slabs, A, lda, a_planes, a_pstride, codes, shift, Gm,
-                   ldg, key, mw, nw, dst, dst_bias, replicate=1, rep_stride=0):
-            sp = ws.splits[key]
-            if ovl and 256 < ws.B * ((ws.T + 31) // 32) <= 512:
-                # beside the backward stack of a very small batch: fewer, longer
-                # workgroups disturb the stack's dependent chain less
-                # (B = 1, T = 16000 -- 500 tiles: 1.89 -> 1.80 ms per step at
-                # 0.6; 0.75 and 0.4 lose, and at B = 2 nothing changes; shapes
-                # of at most one tile per CU are too short for it to matter)
-                sp = max(1, int(sp * self.overlap_tn_split_frac))
-            sl = lib.wn_gemm_tn_slab_floats(mw, nw)
-            # the slabs' matrix and column sums go through ONE reduction launch
-            # when the shapes allow; then the column sums are "spread" too:
-            # every tile row of a split sums its share (wn_gemm_tn,
-            # want_colsum = 2)
-            mt = bool(ub and dst_bias is not None and (mw * nw) % 4 == 0 and
-                      nw % 4 == 0 and sl % 4 == 0 and rep_stride % 4 == 0)
-            tr = 1
-            if mt and self.gemm_mode == 'fp32' and codes is None and \
-                    self.tn_spread_colsum:
-                tr = int(lib.wn_gemm_tn_tail_rows(mw, nw))
-            if self.gemm_mode != 'fp32' and codes is None and N % 16 == 0:
-                # opt-in split-bf16 products (fewer, larger splits)
-                sp = min(sp, lib.wn_gemm_tn_splits(N, mw, nw, 2))
-                _lib.call('wn_gemm_tn_split', A, lda, a_planes, a_pstride, Gm,
-                          ldg, _lib.ptr(slabs), sp, N, mw, nw, ub,
-                          int(self.gemm_mode[-1]), st)
-            else:
-                _lib.call_timed('wn_gemm_tn',
-                                (A, lda, a_planes, a_pstride, codes, shift, T,
-                                 Gm, ldg, _lib.ptr(slabs), sp, N, mw, nw,
-                                 2 if tr > 1 else ub,
-                                 st), 2.0 * N * mw * nw,
-                                getattr(self, '_gemm_events', None))
-            if mt:
-                # matrix and column sums (bias gradient) in one launch
-                _lib.call('wn_reduce_slabs_mt', _lib.ptr(slabs), sp, sl,
-                          mw * nw, dst, nw, dst_bias, replicate, rep_stride,
-                          tr, st)
-                return
-            _lib.call('wn_reduce_slabs', _lib.ptr(slabs), sp, sl, 1, 0, 0,
-                      mw * nw, dst, 0, 1, 0, st)
-            if ub and dst_bias is not None:
-                _lib.call('wn_reduce_slabs', _lib.ptr(slabs), sp, sl, 1, 0,
-                          mw * nw, nw, dst_bias, 0, replicate, rep_stride, st)
-
-        # The data gradients first -- dc1 = (dlogits W2^T) * [c1 > 0],
-        # dtotal = (dc1 W1^T) * [total > 0] (+ dh2 when residual_postproc),
-        # dZ planes = dtotal Ws_all^T -- as ONE chained launch (a 128-row block
-        # of a GEMM starts when that row block of the previous one is stored),
-        # then the three weight-gradient (TN) GEMMs, whose operands all exist
-        # by then: dW2 = h2^T dlogits, dW1 = h1^T dc1, dWs_all = Z^T dtotal
-        # (+ column sums = the bias gradients).
         LP, C = L * self.CB, self.CHn      # planes, padded channels
         _lib.call('wn_transpose', _lib.ptr(self._seg(P, 'post2_w')), S, Q, Q,
                   _lib.ptr(ws.w2t), S, st)
@@ -1204,102 +1169,138 @@ class WaveNetModel(object):
         nn_dz = (_lib.ptr(ws.dtotal), S, 0, 0, _lib.ptr(ws.wst),
                  L * C, None, None, 0, None, 0, _lib.ptr(ws.dZ), 0, LP,
                  N * CH, None, N, L * C, S, 0)
-        # (small batches: the TN GEMMs run on a side stream beside the dZ GEMM
+        tns = [(_lib.ptr(ws.h2), S, 0, 0, _lib.ptr(dlog), Q, 'post2', S, Q,
+                _lib.ptr(self._seg(Gr, 'post2_w')),
+                _lib.ptr(self._seg(Gr, 'post2_b'))),
+               (_lib.ptr(ws.h1), S, 0, 0, _lib.ptr(ws.dc1), S, 'post1', S, S,
+                _lib.ptr(self._seg(Gr, 'post1_w')),
+                _lib.ptr(self._seg(Gr, 'post1_b'))),
+               # skip convs: dbs_l = colsum(dtotal) for every l
+               (_lib.ptr(ws.Z), 0, LP, N * CH, _lib.ptr(ws.dtotal), S, 'skip',
+                L * C, S, _lib.ptr(self._seg(Gr, 'skip_w')),
+                _lib.ptr(self._seg(Gr, 'skip_b')), L, S)]
+        if not path.overlap_tn:
+            self._nn_seq([nn_dc1, nn_dtotal, nn_dz])
+            for a in tns:
+                self._tn(ws, path, st, ws.slabs, *a)
+            if path.early_allreduce:
+                # skip / post-processing gradients are complete on this stream:
+                # their all-reduce runs beside the backward stack
+                self._early_allreduce()
+            return
+        # small batches: the TN GEMMs run on a side stream beside the dZ GEMM
         # and the backward stack, so the dZ GEMM stays a launch of its own
-        # behind the fork)
-        self._nn_seq([nn_dc1, nn_dtotal] if ovl else [nn_dc1, nn_dtotal, nn_dz])
-        tn(_lib.ptr(ws.h2), S, 0, 0, None, 0, _lib.ptr(dlog), Q, 'post2', S, Q,
-           _lib.ptr(self._seg(Gr, 'post2_w')),
-           _lib.ptr(self._seg(Gr, 'post2_b')))
-        tn(_lib.ptr(ws.h1), S, 0, 0, None, 0, _lib.ptr(ws.dc1), S, 'post1', S,
-           S, _lib.ptr(self._seg(Gr, 'post1_w')),
-           _lib.ptr(self._seg(Gr, 'post1_b')))
-        # skip convs: dbs_l = colsum(dtotal) for every l
-        tn(_lib.ptr(ws.Z), 0, LP, N * CH, None, 0, _lib.ptr(ws.dtotal), S,
-           'skip', L * C, S, _lib.ptr(self._seg(Gr, 'skip_w')),
-           _lib.ptr(self._seg(Gr, 'skip_b')), replicate=L, rep_stride=S)
-        if ovl:
-            # fork: everything the three TN GEMMs read exists now
-            # (forking behind the dZ GEMM instead, or another order of the
-            # three, changes nothing at B = 1: 1.80 ms either way)
-            main_s = torch.cuda.current_stream()
-            side_s = self._side_stream()
-            _lib.call_py(lambda: (ws.ev_fork.record(main_s),
-                                  side_s.wait_event(ws.ev_fork)))
-            for a, kw in deferred:
-                tn_now(side_s.cuda_stream, ws.slabs_tn, *a, **kw)
-            _lib.call_py(lambda: ws.ev_join.record(side_s))
-            self._nn(*(nn_dz + (st,)))
-        elif self._early_on():
-            # skip / post-processing gradients are complete on this stream:
-            # their all-reduce runs beside the backward stack
-            self._early_allreduce()
-        if self.blocked:
-            # channel-block path: residual stack, causal layer and global
-            # conditioning gradients (wavenet/blocked.py)
-            from . import blocked
-            if ovl:
-                main_s = torch.cuda.current_stream()
-                _lib.call_py(lambda: main_s.wait_event(ws.ev_join))
-            blocked.backward_layers(self, ws, ids, st)
-            return
+        # behind the fork.  The fork: everything the three TN GEMMs read
+        # exists now (forking behind the dZ GEMM instead, or another order of
+        # the three, changes nothing at B = 1: 1.80 ms either way)
+        self._nn_seq([nn_dc1, nn_dtotal])
+        main_s = torch.cuda.current_stream()
+        side_s = self._side_stream()
+        _lib.call_py(lambda: (ws.ev_fork.record(main_s),
+                              side_s.wait_event(ws.ev_fork)))
+        for a in tns:
+            self._tn(ws, path, side_s.cuda_stream, ws.slabs_tn, *a)
+        _lib.call_py(lambda: ws.ev_join.record(side_s))
+        self._nn(*(nn_dz + (st,)))
 
-        # residual stack, last layer first
-        if not self._legacy_bwd():
-            # one launch per layer; the launches are chained through dx only
-            if self.Lc and not (self._stack_bwd_ok() and getattr(ws, 'stack_bwd', False)):
-                raise NotImplementedError(self.LC_SUPPORTED)
-            dxin, xp = None, 0
-            tsum = None if ws.dsum is None else ws.tilesum
-            if self._stack_bwd_ok() and getattr(ws, 'stack_bwd', False):
-                if ws.stack_rows == 16 and tsum is not None:
-                    tsum = ws.tilesum16
-                # all L layers in one persistent launch (csrc/wn_stack.hip)
-                if not self._bwd_image_with_fwd(ws):
-                    _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(P, 0)),
-                              self.layer_stride, None, _lib.ptr(ws.wimg_b), L, st)
-                bargs = (
-                    _lib.ptr(ws.X), _lib.ptr(ws.Z),
-                    _lib.ptr(ws.SG), _lib.ptr(ws.dZ), _lib.ptr(ws.DX),
-                    ws.N * CH if ws.keep_dx else 0,
-                    _lib.ptr(ws.DQ), _lib.ptr(ws.wimg_b), _lib.ptr(ws.lslabs),
-                    ws.lslabs.shape[1] * self.LAYER_BLOCK,
-                    None if tsum is None else _lib.ptr(tsum),
-                    _lib.ptr(self._dil_dev), _lib.ptr(ws.stack_flags_b),
-                    _lib.ptr(ws.stack_ctl_b),
-                    _lib.ptr(ws.loss_parts[1:]), L, B, T, ws.stack_variant)
-                if self.Lc:
-                    # ... that also stores da_f | da_g of every row and layer
-                    _lib.call_timed('wn_stack_bwd_lc', bargs + (
-                        _lib.ptr(ws.lc_da), L * 64, st), 0.0,
-                        getattr(self, '_gemm_events', None))
-                else:
-                    _lib.call_timed('wn_stack_bwd', bargs + (st,), 0.0,
-                                    getattr(self, '_gemm_events', None))
-                self._backward_tail(ws, ids, ws.DX[0], ws.nslab_s, True,
-                                    tile_rows=ws.stack_rows)
-                return
-            # transposed weight images of all layers (the kernels DMA them
-            # into LDS): one small launch per step
-            _lib.call('wn_layer_bwd2_pack', _lib.ptr(self._layer_block(P, 0)),
-                      self.layer_stride, _lib.ptr(ws.wimg), L, st)
-            for l in range(L - 1, -1, -1):
-                dxo = ws.dx[xp]
-                _lib.call('wn_layer_bwd2', _lib.ptr(ws.X[l]), _lib.ptr(ws.Z[l]),
-                          _lib.ptr(ws.SG[l]), _lib.ptr(ws.dZ[l]),
-                          _lib.ptr(dxin), _lib.ptr(dxo),
-                          _lib.ptr(self._layer_block(P, l)),
-                          _lib.ptr(ws.wimg[l]), _lib.ptr(ws.lslabs[l]),
-                          None if tsum is None else _lib.ptr(tsum[l]),
-                          B, T, int(self.dilations[l]), st)
-                dxin, xp = dxo, 1 - xp
-            self._backward_tail(ws, ids, dxin, ws.nslab_2, True)
+    def _tn(self, ws, path, st, slabs, A, lda, a_planes, a_pstride, Gm, ldg,
+            key, mw, nw, dst, dst_bias, replicate=1, rep_stride=0):
+        """dst = A^T Gm (+ its column sums into dst_bias): one wn_gemm_tn into
+        the per-split `slabs` on stream `st`, then their fixed-order sum."""
+        lib = _lib.load()
+        N = ws.N
+        ub = 1 if self.use_biases else 0
+        sp = ws.splits[key]
+        if path.overlap_tn and 256 < ws.B * ((ws.T + 31) // 32) <= 512:
+            sp = max(1, int(sp * TN_SIDE_SPLIT_FRAC))
+        sl = lib.wn_gemm_tn_slab_floats(mw, nw)
+        # the slabs' matrix and column sums go through ONE reduction launch
+        # when the shapes allow; then the column sums are "spread" too:
+        # every tile row of a split sums its share (wn_gemm_tn,
+        # want_colsum = 2)
+        mt = bool(ub and dst_bias is not None and (mw * nw) % 4 == 0 and
+                  nw % 4 == 0 and sl % 4 == 0 and rep_stride % 4 == 0)
+        tr = int(lib.wn_gemm_tn_tail_rows(mw, nw)) \
+            if mt and path.gemm_mode == 'fp32' else 1
+        if path.gemm_mode != 'fp32' and N % 16 == 0:
+            # opt-in split-bf16 products (fewer, larger splits)
+            sp = min(sp, lib.wn_gemm_tn_splits(N, mw, nw, 2))
+            _lib.call('wn_gemm_tn_split', A, lda, a_planes, a_pstride, Gm,
+                      ldg, _lib.ptr(slabs), sp, N, mw, nw, ub,
+                      int(path.gemm_mode[-1]), st)
+        else:
+            _lib.call_timed('wn_gemm_tn',
+                            (A, lda, a_planes, a_pstride, None, 0, ws.T,
+                             Gm, ldg, _lib.ptr(slabs), sp, N, mw, nw,
+                             2 if tr > 1 else ub,
+                             st), 2.0 * N * mw * nw, self._gemm_events)
+        if mt:
+            # matrix and column sums (bias gradient) in one launch
+            _lib.call('wn_reduce_slabs_mt', _lib.ptr(slabs), sp, sl,
+                      mw * nw, dst, nw, dst_bias, replicate, rep_stride,
+                      tr, st)
             return
+        _lib.call('wn_reduce_slabs', _lib.ptr(slabs), sp, sl, 1, 0, 0,
+                  mw * nw, dst, 0, 1, 0, st)
+        if ub and dst_bias is not None:
+            _lib.call('wn_reduce_slabs', _lib.ptr(slabs), sp, sl, 1, 0,
+                      mw * nw, nw, dst_bias, 0, replicate, rep_stride, st)
 
-        # generic filter width (wn_layer_*_k; also a K = 2 model with
-        # `generic_layers` forced, tests): phase A of layer l - 1 and phase B
-        # of layer l per launch, pre-activation gradients through two ping-pong
-        # plane pairs, weight gradients per layer into slabs
+    def _bwd_stack(self, ws, path, st):
+        """All L layers in one persistent launch (csrc/wn_stack.hip)."""
+        B, T, L = ws.B, ws.T, self.L
+        tsum = None if ws.dsum is None else \
+            ws.tilesum16 if ws.stack_rows == 16 else ws.tilesum
+        if not path.pack_both:
+            _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(self.params, 0)),
+                      self.layer_stride, None, _lib.ptr(ws.wimg_b), L, st)
+        bargs = (
+            _lib.ptr(ws.X), _lib.ptr(ws.Z),
+            _lib.ptr(ws.SG), _lib.ptr(ws.dZ), _lib.ptr(ws.DX),
+            ws.N * CH if ws.keep_dx else 0,
+            _lib.ptr(ws.DQ), _lib.ptr(ws.wimg_b), _lib.ptr(ws.lslabs),
+            ws.lslabs.shape[1] * self.LAYER_BLOCK,
+            None if tsum is None else _lib.ptr(tsum),
+            _lib.ptr(self._dil_dev), _lib.ptr(ws.stack_flags_b),
+            _lib.ptr(ws.stack_ctl_b),
+            _lib.ptr(ws.loss_parts[1:]), L, B, T, ws.stack_variant)
+        if path.bwd == 'stack_lc':
+            # ... that also stores da_f | da_g of every row and layer
+            _lib.call_timed('wn_stack_bwd_lc', bargs + (
+                _lib.ptr(ws.lc_da), L * 64, st), 0.0, self._gemm_events)
+        else:
+            _lib.call_timed('wn_stack_bwd', bargs + (st,), 0.0,
+                            self._gemm_events)
+        return ws.DX[0]
+
+    def _bwd_layer2(self, ws, path, st):
+        """One wn_layer_bwd2 launch per layer, chained through dx only."""
+        B, T, L, P = ws.B, ws.T, self.L, self.params
+        tsum = None if ws.dsum is None else ws.tilesum
+        # transposed weight images of all layers (the kernels DMA them
+        # into LDS): one small launch per step
+        _lib.call('wn_layer_bwd2_pack', _lib.ptr(self._layer_block(P, 0)),
+                  self.layer_stride, _lib.ptr(ws.wimg), L, st)
+        dxin, xp = None, 0
+        for l in range(L - 1, -1, -1):
+            dxo = ws.dx[xp]
+            _lib.call('wn_layer_bwd2', _lib.ptr(ws.X[l]), _lib.ptr(ws.Z[l]),
+                      _lib.ptr(ws.SG[l]), _lib.ptr(ws.dZ[l]),
+                      _lib.ptr(dxin), _lib.ptr(dxo),
+                      _lib.ptr(self._layer_block(P, l)),
+                      _lib.ptr(ws.wimg[l]), _lib.ptr(ws.lslabs[l]),
+                      None if tsum is None else _lib.ptr(tsum[l]),
+                      B, T, int(self.dilations[l]), st)
+            dxin, xp = dxo, 1 - xp
+        return dxin
+
+    def _bwd_layer_k(self, ws, path, st):
+        """Generic filter width (wn_layer_*_k; also a K = 2 model with
+        `generic_layers` forced, tests): phase A of layer l - 1 and phase B
+        of layer l per launch, pre-activation gradients through two ping-pong
+        plane pairs, weight gradients per layer into slabs."""
+        B, T, L, P = ws.B, ws.T, self.L, self.params
+
         def da(p):
             return ws.da[p][0], ws.da[p][1]
 
@@ -1316,9 +1317,7 @@ class WaveNetModel(object):
                   _lib.ptr(ws.SG[L - 1]),
                   _lib.ptr(self._layer_block(P, L - 1)), _lib.ptr(f),
                   _lib.ptr(g), B, T, 1, 0, 1, st)
-        dxin = None           # dL/dx' of layer l (None for the last layer)
-        xp = 0
-        nslab = ws.nslab
+        dxin, xp = None, 0    # dL/dx' of layer l (None for the last layer)
         for l in range(L - 1, -1, -1):
             d = int(self.dilations[l])
             f, g = da(cur)
@@ -1346,17 +1345,16 @@ class WaveNetModel(object):
                           _lib.ptr(dxo), _lib.ptr(self._layer_block(P, l)),
                           None, None, None, None, None, None, B, T, d, 1, 0,
                           st)
-            dxin = dxo
-            xp = 1 - xp
-        self._backward_tail(ws, ids, dxin, nslab, False)
+            dxin, xp = dxo, 1 - xp
+        return dxin
 
-    def _backward_tail(self, ws, ids, dxin, nslab, fused, tile_rows=32):
+    def _backward_tail(self, ws, ids, path, dxin):
         """After the residual stack: slab reductions of the layer-block
         gradients, causal-layer and global-conditioning gradients."""
-        if self._overlap_tn_on(ws):
+        if path.overlap_tn:
             main_s = torch.cuda.current_stream()
             _lib.call_py(lambda: main_s.wait_event(ws.ev_join))     # join
-            if self._early_on():
+            if path.early_allreduce:
                 # (small batches: the side stream's weight-gradient GEMMs have
                 # just joined; the tail's all-reduce runs beside the slab
                 # reductions and the causal / conditioning gradients)
@@ -1366,13 +1364,17 @@ class WaveNetModel(object):
         P, Gr = self.params, self.grads
         ub = 1 if self.use_biases else 0
         lib = _lib.load()
-        if fused and ws.dsum is not None:
+        stack = path.bwd.startswith('stack')
+        if path.bwd != 'layer_k' and ws.dsum is not None:
             # per-clip sums of da_l for every layer from the per-tile sums the
             # fused kernel wrote (fixed order over a clip's tiles)
+            tile_rows = ws.stack_rows if stack else 32
             tpc = (T + tile_rows - 1) // tile_rows
             _lib.call('wn_reduce_slabs', _lib.ptr(ws.tilesum), tpc, 64, L * B,
                       tpc * 64, 0, 64, _lib.ptr(ws.dsum), 64, 1, 0, st)
         # layer-block gradients: fixed-order sum of the per-workgroup slabs
+        nslab = ws.nslab_s if stack else \
+            ws.nslab_2 if path.bwd == 'layer2' else ws.nslab
         lo, _ = self.segments['layers']
         _lib.call('wn_reduce_slabs', _lib.ptr(ws.lslabs), nslab,
                   self.LAYER_BLOCK, L, ws.lslabs.shape[1] * self.LAYER_BLOCK,
@@ -1380,23 +1382,23 @@ class WaveNetModel(object):
                   _lib.ptr(Gr[lo:]),
                   self.layer_stride, 1, 0, st)
         # causal layer: dWc[1][v] = sum_t [q[t]==v] dx0[t]; dWc[0][v] likewise
-        # with q[t-1]  (one-hot operand generated on the fly)
+        # with q[t-1]
         gc_ = self._seg(Gr, 'causal')
-        if self.scalar_input:
+        if path.causal_wgrad == 'scalar':
             K0 = self.initial_filter_width
             sp = ws.splits['causal']
             _lib.call('wn_scalar_causal_wgrad', _lib.ptr(ws.audio),
                       _lib.ptr(dxin), _lib.ptr(ws.slabs), sp, B, T, K0, st)
             _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, K0 * CH, 1,
                       0, 0, K0 * CH, _lib.ptr(gc_), 0, 1, 0, st)
-        elif self.KW == 2 and Q <= 256 and self.causal_wgrad_segsum:
-            # segmented sum over the codes (no one-hot contraction)
+        elif path.causal_wgrad == 'segsum':
             ns = ws.nslab_c
             _lib.call('wn_causal_wgrad', _lib.ptr(ws.q), _lib.ptr(dxin),
                       _lib.ptr(ws.slabs), ns, B, T, Q, st)
             _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), ns, 2 * Q * CH,
                       1, 0, 0, 2 * Q * CH, _lib.ptr(gc_), 0, 1, 0, st)
         else:
+            # (one-hot operand generated on the fly)
             K = self.KW
             for tap in range(K):
                 shift = (K - 1 - tap) + (K - 1) // 2
@@ -1415,7 +1417,7 @@ class WaveNetModel(object):
             _lib.call_timed('wn_gemm_tn', (
                 _lib.ptr(ws.lc), self.Lcp, 0, 0, None, 0, T, _lib.ptr(ws.lc_da),
                 W64, _lib.ptr(ws.slabs), sp, N, self.Lcp, W64, 0, st),
-                2.0 * N * W64 * self.Lcp, getattr(self, '_gemm_events', None))
+                2.0 * N * W64 * self.Lcp, self._gemm_events)
             _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp,
                       lib.wn_gemm_tn_slab_floats(self.Lcp, W64), 1, 0, 0,
                       self.Lcp * W64, _lib.ptr(self._seg(Gr, 'lc_w')), 0, 1, 0,
@@ -1465,7 +1467,6 @@ class WaveNetModel(object):
             a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
         lc = self._lc_rows(local_condition_batch, B, a.shape[1], 'loss')
-        self._check_lc_paths()
         q = mu_law_encode(a, self.Q)
         return self.loss_from_codes(q, global_condition_batch,
                                     l2_regularization_strength, backward,
@@ -1480,7 +1481,6 @@ class WaveNetModel(object):
         T = q.shape[1]
         N = B * T
         lc = self._lc_rows(local_condition_batch, B, T, 'loss')
-        self._check_lc_paths()
         ws = self._workspace(B, T, backward)
         if backward and self._tail_work is not None:
             # the previous backward pass started its tail all-reduce and no
@@ -1500,12 +1500,14 @@ class WaveNetModel(object):
                 raise ValueError('scalar_input needs the float audio')
             ws.audio.copy_(audio.reshape(-1))
         ids = self._gc_ids(global_condition_batch, B)
-        self._stage_lc(ws, lc)
+        if lc is not None:
+            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
         st = _lib.stream()
-        # 0: inference; 1: tanh + sigmoid planes (legacy backward kernels);
-        # 2: sigmoid plane only (wn_layer_bwd2)
-        self._forward(ws, ids, save_ts=0 if not backward else
-                      (1 if self._legacy_bwd() else 2))
+        # (L2 adds lambda * params to the WHOLE bucket after the backward
+        # pass: the tail must not have been summed over ranks before that)
+        path = self._step_path(ws, backward,
+                               l2=l2_regularization_strength is not None)
+        self._run_pass('fwd', ws, ids, path)
         _lib.call('wn_xent', _lib.ptr(ws.logits), self.Q, _lib.ptr(ws.q),
                   _lib.ptr(ws.logits) if backward else None,
                   _lib.ptr(ws.loss_parts[2:]), B, T, self.Q,
@@ -1514,11 +1516,8 @@ class WaveNetModel(object):
                   0, 0, 1, _lib.ptr(ws.loss), 0, 1, 0, st)
         loss = ws.loss[0] / float(N)                    # reduce_mean, :666
         if backward:
-            # (L2 adds lambda * params to the WHOLE bucket after the backward
-            # pass: the tail must not have been summed over ranks before that)
-            self._early_ok = l2_regularization_strength is None
             try:
-                self._backward(ws, ids)
+                self._run_pass('bwd', ws, ids, path)
             except BaseException:
                 # (a launch error after the tail's all-reduce was issued: join
                 # it, so that the next step does not find it dangling)
@@ -1584,15 +1583,15 @@ class WaveNetModel(object):
         w = w.to(device=self.device, dtype=torch.int32).reshape(B, -1)
         T = w.shape[1]
         lc = self._lc_rows(local_condition, B, T, 'predict_proba')
-        self._check_lc_paths()
         ws = self._workspace(B, T, False)
         ws.q.copy_(w.reshape(-1))
         if self.scalar_input:
             # decode the codes back to floats in [-1, 1] (model.py:570-576)
             ws.audio.copy_(mu_law_decode(w, self.Q).reshape(-1))
         ids = self._gc_ids(global_condition, B)
-        self._stage_lc(ws, lc)
-        self._forward(ws, ids, save_ts=0)
+        if lc is not None:
+            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
+        self._run_pass('fwd', ws, ids, self._step_path(ws, False))
         out = torch.empty(self.Q, dtype=torch.float32, device=self.device)
         _lib.call('wn_softmax64_row', _lib.ptr(ws.logits[B * T - 1]), self.Q,
                   _lib.ptr(out), _lib.stream())

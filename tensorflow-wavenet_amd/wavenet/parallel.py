@@ -13,11 +13,11 @@ the ring moves 2(N-1)/N * 6 MB per GPU (~70 us of wire time at N=8 over
 per-link-bound xGMI, plus the collective's launch and the wait for the slowest
 rank) against a >= 7 ms step.
 
-Two calls per step (round 5, `model.dp_overlap_allreduce`, what bench.py /
-train.py switch on under torch.distributed): the bucket's TAIL -- skip convs
-and post-processing, 82 % of the bytes (76 % with global conditioning), laid
-out last -- is complete when the
-three weight-gradient GEMMs are, i.e. BEFORE the 1.5 ms backward stack launch
+Two calls per step (round 5, `model.dp_overlap_allreduce`; opt-in through
+`train.py --dp_overlap_allreduce`, bench.py times it as a trial): the bucket's
+TAIL -- skip convs and post-processing, 82 % of the bytes (76 % with global
+conditioning), laid out last -- is complete when the three weight-gradient
+GEMMs are, i.e. BEFORE the 1.5 ms backward stack launch
 starts.  `begin_tail_allreduce` (called from inside the backward pass at that
 point) issues its all-reduce on a communication stream behind an event, so it
 runs beside the backward stack; `allreduce_gradients` (optimizer.minimize)

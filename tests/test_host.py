@@ -176,3 +176,46 @@ def test_bench_dump_outputs_float32_and_capped(tmp_path):
     assert a.size == 1000 and np.array_equal(a, b)
     assert np.isin(a, arrays['variables'].astype(np.float32)).all()
     assert sum(os.path.getsize(str(p)) for p in (tmp_path / 'a').iterdir()) <= cap
+
+
+def test_step_path_of_a_call():
+    """WaveNetModel._step_path: the launches one call takes, from the model's
+    switches now and the ones its workspace froze (a stand-in here)."""
+    from types import SimpleNamespace
+    from wavenet import WaveNetModel
+
+    def path(backward=True, skip_ok=False, ws_stack_bwd=True, B=8, **over):
+        kw = dict(model_kwargs(cfg_with(DEFAULT, batch_size=B)))
+        kw.update({k: over.pop(k) for k in list(over) if k in kw})
+        net = WaveNetModel(device='cpu', **kw)
+        for k, v in over.items():
+            setattr(net, k, v)
+        ws = SimpleNamespace(B=B, T=16000, fwd_skip_ok=skip_ok,
+                             stack_bwd=ws_stack_bwd, stack_variant=0)
+        return net._step_path(ws, backward)
+
+    p = path()
+    assert (p.fwd, p.save_ts, p.bwd, p.pack_both, p.overlap_tn,
+            p.early_allreduce, p.causal_wgrad) == \
+        ('stack', 2, 'stack', True, False, False, 'segsum')
+    p = path(B=1, skip_ok=True)
+    assert (p.fwd, p.bwd, p.pack_both, p.overlap_tn) == \
+        ('stack_skip', 'stack', True, True)
+    assert path(B=1, skip_ok=True, residual_postproc=True).fwd == 'stack'
+    assert path(backward=False) == path(backward=False, stack_bwd=False)
+    assert path(backward=False).bwd is None
+    p = path(ws_stack_bwd=False)
+    assert (p.fwd, p.bwd, p.pack_both) == ('stack', 'layer2', False)
+    p = path(stack_fwd=False)
+    assert (p.fwd, p.bwd, p.pack_both) == ('layer', 'stack', False)
+    p = path(generic_layers=True)
+    assert (p.fwd, p.save_ts, p.bwd) == ('layer_k', 1, 'layer_k')
+    p = path(filter_width=3)
+    assert (p.fwd, p.bwd, p.causal_wgrad) == ('layer_k', 'layer_k', 'onehot')
+    p = path(residual_channels=64, dilation_channels=64, overlap_tn=True)
+    assert (p.fwd, p.bwd, p.causal_wgrad, p.overlap_tn) == \
+        ('blocked', 'blocked', None, True)
+    assert path(quantization_channels=512).causal_wgrad == 'onehot'
+    assert path(scalar_input=True).causal_wgrad == 'scalar'
+    # (the launch-plan key: equal paths, equal plans)
+    assert path() == path() and path() != path(gemm_mode='bf16x6')
