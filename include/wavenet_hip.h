@@ -299,6 +299,14 @@ int wn_stack_fwd_lc(float* X, float* Z, float* SG, const float* wimg,
                     int variant, const float* lc_add, long lc_row_stride,
                     void* stream);
 int wn_stack_bwd_slabs(int B, int T, int variant);
+/* Launch-shape queries (no device needed: 256 CUs are assumed without one).
+ * wn_stack_fwd_waves: waves (= tiles) per workgroup wn_stack_fwd / _fwd_lc
+ * launch for the shape and variant word.  wn_stack_bwd_waves: waves per
+ * workgroup of wn_stack_bwd / _bwd_lc, and its tiles per wave and layer in
+ * *tiles_per_wave.  Both answer for the tile height wn_stack_tile_rows picks;
+ * B or T <= 0 is WN_ERR_BAD_SHAPE, a NULL tiles_per_wave WN_ERR_NULL. */
+int wn_stack_fwd_waves(int B, int T, int variant);
+int wn_stack_bwd_waves(int B, int T, int variant, int* tiles_per_wave);
 int wn_stack_bwd(const float* X, const float* Z, const float* SG,
                  const float* dZ, float* DX, long dx_layer_stride, float* Q,
                  const float* wimg, float* slabs,

@@ -2194,13 +2194,43 @@ int wn_stack_pack(const float* layer0, long layer_stride, float* wimg_fwd,
 // floats of the skip image wn_stack_skip_pack writes for wn_stack_fwd_skip
 long wn_stack_skip_img_floats(int L) { return L > 0 ? (long)4 * L * SK_WAVE : 0; }
 
+// waves (= tiles) per workgroup of wn_stack_fwd / _fwd_lc for a shape (B, T > 0).
+// 16-row tiles: one wave per SIMD while that covers the batch in one pass,
+// else two (the variant word may force 4 / 8).  32-row tiles: 16 when that
+// fills every CU, fewer for small batches so that the tiles still spread over
+// the whole chip.
+static int stack_fwd_waves(int B, int T, int variant) {
+  const int cus = wn_device_cus();
+  if (wn_stack_tile_rows(B, T, variant) == 16) {
+    const long nt16 = (long)B * ((T + 15) / 16);
+    return variant_waves(variant, (nt16 + 3) / 4 <= cus ? 4 : 8, false);
+  }
+  const long ntiles = (long)B * ((T + 31) / 32);
+  // (a layer costs a workgroup about max(7 us of dependent latency, 2.2 us of
+  // matrix-pipe time per wave of a SIMD); groups beyond one per CU run in passes)
+  int waves = 16;
+  long best = -1;
+  for (int w = 16; w >= 1; w >>= 1) {
+    const long groups = (ntiles + w - 1) / w;
+    const long passes = (groups + cus - 1) / cus;
+    const long per_layer = w * 22 / 4 > 70 ? w * 22 / 4 : 70;   // 0.1 us
+    const long cost = passes * per_layer;
+    if (best < 0 || cost <= best) { best = cost; waves = w; }   // ties: fewer waves per CU
+  }
+  return waves;
+}
+
+int wn_stack_fwd_waves(int B, int T, int variant) {
+  if (B <= 0 || T <= 0) return WN_ERR_BAD_SHAPE;
+  return stack_fwd_waves(B, T, variant);
+}
+
 // 1 when wn_stack_fwd_skip covers the shape: the 16-row launch with one wave per
 // SIMD (small batches), 512 skip channels
 int wn_stack_fwd_skip_ok(int B, int T, int S, int variant) {
   if (B <= 0 || T <= 0 || S != SK_S) return 0;
   if (wn_stack_tile_rows(B, T, variant) != 16) return 0;
-  const long nt16 = (long)B * ((T + 15) / 16);
-  return variant_waves(variant, (nt16 + 3) / 4 <= wn_device_cus() ? 4 : 8, false) == 4;
+  return stack_fwd_waves(B, T, variant) == 4;
 }
 
 int wn_stack_skip_pack(const float* skip_w, int L, float* img, void* stream) {
@@ -2266,8 +2296,7 @@ static int stack_fwd_launch(float* X, float* Z, float* SG, const float* wimg,
     if ((long)B * T * WN_CH * 4 >= (1L << 31)) return WN_ERR_UNSUPPORTED;
     const long nt16 = (long)B * ((T + 15) / 16);
     const int cus16 = wn_device_cus();
-    // one wave per SIMD while that covers the batch in one pass, else two
-    const int w16 = variant_waves(variant, (nt16 + 3) / 4 <= cus16 ? 4 : 8, false);
+    const int w16 = stack_fwd_waves(B, T, variant);
     long g16 = (nt16 + w16 - 1) / w16;
     if (g16 > cus16) g16 = cus16;
     dim3 grid16((unsigned)g16), block16(w16 * 64);
@@ -2283,21 +2312,9 @@ static int stack_fwd_launch(float* X, float* Z, float* SG, const float* wimg,
 #undef LAUNCH16
     return wn_check_launch();
   }
-  // waves (= tiles) per workgroup: 16 when that fills every CU, fewer for
-  // small batches so that the tiles still spread over the whole chip
   const long ntiles = (long)B * ((T + 31) / 32);
   const int cus = wn_device_cus();
-  // (a layer costs a workgroup about max(7 us of dependent latency, 2.2 us of
-  // matrix-pipe time per wave of a SIMD); groups beyond one per CU run in passes)
-  int waves = 16;
-  long best = -1;
-  for (int w = 16; w >= 1; w >>= 1) {
-    const long groups = (ntiles + w - 1) / w;
-    const long passes = (groups + cus - 1) / cus;
-    const long per_layer = w * 22 / 4 > 70 ? w * 22 / 4 : 70;   // 0.1 us
-    const long cost = passes * per_layer;
-    if (best < 0 || cost <= best) { best = cost; waves = w; }   // ties: fewer waves per CU
-  }
+  const int waves = stack_fwd_waves(B, T, variant);
   long g = (ntiles + waves - 1) / waves;
   if (g > cus) g = cus;
   dim3 grid((unsigned)g), block(waves * 64);
@@ -2401,6 +2418,14 @@ static void stack_bwd_shape(int B, int T, int variant, int* waves_out, int* tpw_
   }
   *waves_out = bw;
   *tpw_out = bt;
+}
+
+int wn_stack_bwd_waves(int B, int T, int variant, int* tiles_per_wave) {
+  if (!tiles_per_wave) return WN_ERR_NULL;
+  if (B <= 0 || T <= 0) return WN_ERR_BAD_SHAPE;
+  int w;
+  stack_bwd_shape(B, T, variant, &w, tiles_per_wave);
+  return w;
 }
 
 // weight-gradient slabs per layer wn_stack_bwd writes (= tile groups)

@@ -46,6 +46,8 @@ SIGNATURES = {
                                 c_int, c_int, c_int, c_int, c_int, P, c_long,
                                 P]),
     'wn_stack_bwd_slabs': (c_int, [c_int, c_int, c_int]),
+    'wn_stack_fwd_waves': (c_int, [c_int, c_int, c_int]),
+    'wn_stack_bwd_waves': (c_int, [c_int, c_int, c_int, P]),
     'wn_stack_bwd': (c_int, [P, P, P, P, P, c_long, P, P, P, c_long, P, P, P,
                              P, P, c_int, c_int, c_int, c_int, P]),
     'wn_stack_bwd_lc': (c_int, [P, P, P, P, P, c_long, P, P, P, c_long, P, P,

@@ -7,6 +7,8 @@ tests/test_gpu_parallel.py, never collected by pytest).
                bucket all-reduce, 1/N folded into the update kernel; with
                spec['overlap'] as two calls, the tail from inside the backward
                pass) for `steps` steps and rank 0 saves the parameters.
+               spec['lc'] = Lc: a local-conditioning model, every rank on its
+               shard of one [steps, B, T, Lc] feature batch.
   mode nccl1 : world_size-1 process group over backend "nccl" (= RCCL):
                broadcast of net.params and all-reduce of net.grads go through
                the RCCL code path on the device bucket.
@@ -30,11 +32,22 @@ def main():
     torch.cuda.set_device(local % torch.cuda.device_count())
     B, T, steps = spec['B'], spec['T'], spec['steps']
     cfg = cfg_with(MID, batch_size=B // world, **spec.get('cfg', {}))
-    net, var = build_pair(cfg)
+    Lc = spec.get('lc')
+    if Lc:
+        # local conditioning: the model's own initialisation, the same seed
+        # on every rank
+        from util import model_kwargs
+        from wavenet import WaveNetModel
+        net = WaveNetModel(seed=5, local_condition_channels=Lc,
+                           **model_kwargs(cfg))
+    else:
+        net, var = build_pair(cfg)
     rng = np.random.default_rng(17)
     audio = rng.uniform(-1, 1, (steps, B, T)).astype(np.float32)
     ids = rng.integers(0, cfg.get('global_condition_cardinality') or 1,
                        (steps, B))
+    lcb = rng.standard_normal((steps, B, T, Lc)).astype(np.float32) \
+        if Lc else None
     gc = cfg.get('global_condition_cardinality') is not None
     if spec['mode'] == 'nccl1':
         import torch.distributed as dist
@@ -83,6 +96,7 @@ def main():
         with torch.no_grad():
             net.params.add_(1.0)
     parallel.broadcast_parameters(net)
+    lc_w0 = net._seg(net.params, 'lc_w').cpu().numpy() if Lc else None
     opt = optimizer_factory[spec['opt']](learning_rate=spec['lr'],
                                          momentum=0.9)
     lo, hi = parallel.shard_range(B, rank, world)
@@ -91,13 +105,18 @@ def main():
     net.dp_overlap_allreduce = bool(spec.get('overlap', False))
     losses = []
     for s in range(steps):
-        loss = net.loss(audio[s, lo:hi], ids[s, lo:hi] if gc else None)
+        loss = net.loss(audio[s, lo:hi], ids[s, lo:hi] if gc else None,
+                        local_condition_batch=lcb[s, lo:hi] if Lc else None)
         opt.minimize(loss)
         losses.append(float(parallel.allreduce_mean_scalar(loss)))
     torch.cuda.synchronize()
     if rank == 0:
+        extra = {}
+        if Lc:
+            extra = dict(lc_w0=lc_w0,
+                         lc_w=net._seg(net.params, 'lc_w').cpu().numpy())
         np.savez(spec['out'], params=net.params.cpu().numpy(),
-                 losses=np.asarray(losses))
+                 losses=np.asarray(losses), **extra)
     if parallel.is_distributed():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -48,21 +48,10 @@ def flatten(tree, prefix=''):
     return [(prefix, np.asarray(tree))]
 
 
-def loss_and_grads(var, dilations, codes, lc=None, gc_ids=None, use_biases=False,
-                   quantization_channels=256, relu_masks=None,
-                   tf_xent_zero_label_quirk=True):
-    """var: the model's `variables` tree as numpy (model_tree); dilations:
-    one per layer; codes int [B, T]; lc float
-    [B, T, Lc] or None.  relu_masks: optional dict(total=, c1=) of bool
-    [B, T, S] -- the device's ReLU decisions, used in place of the float64
-    ones (they can differ only where a pre-activation rounds across zero).
-    Returns (loss, gradient tree shaped like `var`)."""
-    v = _to_torch(var)
-    Q = quantization_channels
-    q = torch.as_tensor(np.asarray(codes), dtype=torch.int64)
-    B, T = q.shape
+def _forward(v, dilations, q, lct, gc_ids, use_biases, Q, relu_masks,
+             residual_postproc):
+    """Logits [B, T, Q] of the torch tree `v` (float64)."""
     enc = F.one_hot(q, Q).to(torch.float64)
-    lct = None if lc is None else torch.as_tensor(np.asarray(lc, np.float64))
     gce = None
     if gc_ids is not None:
         gce = v['embeddings']['gc_embedding'][
@@ -102,9 +91,44 @@ def loss_and_grads(var, dilations, codes, lc=None, gc_ids=None, use_biases=False
     c1 = relu(total, 'total') @ p['postprocess1'][0]
     if use_biases:
         c1 = c1 + p['postprocess1_bias']
-    raw = relu(c1, 'c1') @ p['postprocess2'][0]
+    h2 = relu(c1, 'c1')
+    if residual_postproc:
+        h2 = h2 + total            # (the pre-ReLU skip sum)
+    raw = h2 @ p['postprocess2'][0]
     if use_biases:
         raw = raw + p['postprocess2_bias']
+    return raw, enc
+
+
+def _leaves(tree, name=''):
+    """[(last key, tensor)] of a torch tree."""
+    if isinstance(tree, dict):
+        return [x for k in sorted(tree) for x in _leaves(tree[k], k)]
+    if isinstance(tree, list):
+        return [x for t in tree for x in _leaves(t, name)]
+    return [(name, tree)]
+
+
+def loss_and_grads(var, dilations, codes, lc=None, gc_ids=None, use_biases=False,
+                   quantization_channels=256, relu_masks=None,
+                   tf_xent_zero_label_quirk=True, residual_postproc=False,
+                   l2=None, tf_bias_name_quirk=True, return_logits=False):
+    """var: the model's `variables` tree as numpy (model_tree); dilations:
+    one per layer; codes int [B, T]; lc float
+    [B, T, Lc] or None.  relu_masks: optional dict(total=, c1=) of bool
+    [B, T, S] -- the device's ReLU decisions, used in place of the float64
+    ones (they can differ only where a pre-activation rounds across zero).
+    residual_postproc: the pre-ReLU skip sum is added to the post-ReLU c1.
+    l2: lam of the L2 term lam * sum(w^2) / 2 over every variable, or (with
+    tf_bias_name_quirk False) over those whose name does not say 'bias'.
+    Returns (loss, gradient tree shaped like `var`), and with return_logits
+    the float64 logits [B, T, Q] as a third item."""
+    v = _to_torch(var)
+    Q = quantization_channels
+    q = torch.as_tensor(np.asarray(codes), dtype=torch.int64)
+    lct = None if lc is None else torch.as_tensor(np.asarray(lc, np.float64))
+    raw, enc = _forward(v, dilations, q, lct, gc_ids, use_biases, Q,
+                        relu_masks, residual_postproc)
     lab = F.pad(enc[:, 1:, :], (0, 0, 0, 1)).reshape(-1, Q)
     pred = raw.reshape(-1, Q)
     lse = torch.logsumexp(pred, -1)
@@ -114,8 +138,27 @@ def loss_and_grads(var, dilations, codes, lc=None, gc_ids=None, use_biases=False
         # clip adds 0 to the loss but its softmax to the gradient
         row = torch.where(lab.sum(-1) > 0, row, lse - lse.detach())
     loss = row.mean()
+    if l2 is not None:
+        loss = loss + float(l2) * sum(
+            (w * w).sum() / 2 for n, w in _leaves(v)
+            if tf_bias_name_quirk or 'bias' not in n)
     loss.backward()
-    return float(loss.detach()), _grads(v)
+    out = (float(loss.detach()), _grads(v))
+    if return_logits:
+        out += (raw.detach().numpy(),)
+    return out
+
+
+def logits(var, dilations, codes, lc=None, gc_ids=None, use_biases=False,
+           quantization_channels=256, residual_postproc=False):
+    """The float64 logits [B, T, Q] alone (no gradients)."""
+    with torch.no_grad():
+        raw, _ = _forward(
+            _to_torch(var), dilations,
+            torch.as_tensor(np.asarray(codes), dtype=torch.int64),
+            None if lc is None else torch.as_tensor(np.asarray(lc, np.float64)),
+            gc_ids, use_biases, quantization_channels, None, residual_postproc)
+    return raw.numpy()
 
 
 def model_tree(net, grads=False):
@@ -129,5 +172,7 @@ def device_relu_masks(net, B, T):
     """The ReLU decisions of the model's last training forward pass."""
     ws = [w for w in net._ws.values() if w.T == T and w.training][0]
     S = net.S
+    # (with residual_postproc h2 = relu(c1) + total: c1 is kept on its own)
+    c1 = ws.c1 if net.residual_postproc else ws.h2
     return dict(total=(ws.h1 > 0).cpu().numpy().reshape(B, T, S),
-                c1=(ws.h2 > 0).cpu().numpy().reshape(B, T, S))
+                c1=(c1 > 0).cpu().numpy().reshape(B, T, S))

@@ -117,6 +117,71 @@ def test_stack_entries_validate_without_gpu(hip_lib):
                                 None, 2, 1, 64, 0, None) == -1       # neither 0 nor a plane
 
 
+def test_stack_launch_shape_queries(hip_lib):
+    """wn_stack_fwd_waves / wn_stack_bwd_waves: the waves per workgroup (and
+    the backward's tiles per wave) the stack launches pick, by the number of
+    32-row tiles B * ceil(T / 32) (256 CUs assumed without a device)."""
+    from wavenet import _lib
+
+    def bwd(B, T, v):
+        tpw = ctypes.c_int(-7)
+        w = hip_lib.wn_stack_bwd_waves(B, T, v, ctypes.byref(tpw))
+        return w, tpw.value
+
+    # (32-row tiles, forward waves, backward waves, tiles per wave)
+    table = [(1, 1, 4, 1), (256, 1, 4, 1), (257, 2, 4, 1), (512, 2, 4, 1),
+             (513, 4, 4, 1), (1024, 4, 4, 1), (1025, 8, 8, 1), (2048, 8, 8, 1),
+             (2049, 16, 8, 2), (4000, 16, 8, 2), (4096, 16, 8, 2),
+             (4097, 16, 8, 3)]
+    v32 = _lib.stack_variant(rows=32)
+    for nt, fw, bw, tpw in table:
+        for B, T in ((1, 32 * nt), (nt, 32), (1, 32 * nt - 31)):
+            assert hip_lib.wn_stack_tile_rows(B, T, v32) == 32
+            assert hip_lib.wn_stack_fwd_waves(B, T, v32) == fw, (B, T)
+            assert bwd(B, T, v32) == (bw, tpw), (B, T)
+    # the shapes of tests/test_gpu_local_condition.py and the training step
+    assert hip_lib.wn_stack_fwd_waves(2, 4200, v32) == 2                 # 264 tiles
+    assert hip_lib.wn_stack_fwd_waves(8, 8300, v32) == 16
+    assert bwd(8, 8300, v32) == (8, 2)
+    assert hip_lib.wn_stack_fwd_waves(8, 16000, 0) == 16                 # 4000 tiles
+    assert bwd(8, 16000, 0) == (8, 2)
+    # forced backward waves: tiles per wave so that one pass covers the batch
+    for nt, w, tpw in ((264, 1, 2), (528, 2, 2), (100, 1, 1), (256, 1, 1),
+                       (257, 1, 2), (1025, 4, 2), (2049, 8, 2), (528, 8, 1),
+                       (4097, 4, 5)):
+        v = _lib.stack_variant(rows=32, waves=w)
+        assert bwd(1, 32 * nt, v) == (w, tpw), (nt, w)
+        # (the 32-row forward takes no forced waves)
+        assert hip_lib.wn_stack_fwd_waves(1, 32 * nt, v) == \
+            hip_lib.wn_stack_fwd_waves(1, 32 * nt, v32)
+    assert bwd(1, 32 * 100, _lib.stack_variant(rows=32, waves=3)) == (4, 1)  # not a count
+    # slabs per layer = ceil(tiles / (waves x tiles per wave))
+    for B, T, v in ((8, 16000, 0), (2, 4200, _lib.stack_variant(32, 1)),
+                    (4, 4200, _lib.stack_variant(32, 2)), (1, 16000, 0)):
+        w, tpw = bwd(B, T, v)
+        rows = hip_lib.wn_stack_tile_rows(B, T, v)
+        nt = B * -(-T // rows)
+        assert hip_lib.wn_stack_bwd_slabs(B, T, v) == -(-nt // (w * tpw))
+    # 16-row tiles: the forward has one wave per SIMD while that covers the
+    # batch in one pass, else two (or what the variant word forces); the
+    # backward 8 waves (or 4) of one tile each
+    assert hip_lib.wn_stack_tile_rows(1, 16000, 0) == 16
+    assert hip_lib.wn_stack_fwd_waves(1, 16000, 0) == 4                 # 1000 tiles
+    assert hip_lib.wn_stack_fwd_waves(2, 16000, 16) == 8                # 2000 tiles
+    assert hip_lib.wn_stack_fwd_waves(2, 16000, 16 | (4 << 8)) == 4
+    assert bwd(1, 16000, 0) == (8, 1)
+    assert bwd(1, 16000, 16 | (4 << 8)) == (4, 1)
+    assert hip_lib.wn_stack_fwd_skip_ok(1, 16000, 512, 0) == 1
+    assert hip_lib.wn_stack_fwd_skip_ok(2, 16000, 512, 16) == 0
+    # argument errors
+    t = ctypes.c_int(-7)
+    for B, T in ((0, 100), (1, 0), (-1, 100), (1, -5)):
+        assert hip_lib.wn_stack_fwd_waves(B, T, 0) == -1
+        assert hip_lib.wn_stack_bwd_waves(B, T, 0, ctypes.byref(t)) == -1
+    assert t.value == -7
+    assert hip_lib.wn_stack_bwd_waves(1, 100, 0, None) == -5
+
+
 @pytest.mark.parametrize('q', [2, 16, 123, 128, 256])
 def test_host_tables_equal_oracle(hip_lib, q):
     thr = np.empty(q - 1, np.float32)

@@ -123,6 +123,34 @@ def test_tail_allreduce_inside_backward_equals_one_call(hip_lib, tmp_path, B, T)
     assert np.abs(res[True]['losses'] - one['losses']).max() < 1e-6
 
 
+def test_two_ranks_lc_model_equal_single_process(hip_lib, tmp_path):
+    """Local conditioning over two ranks (gloo, sharing this GPU), with the
+    tail all-reduce from inside the backward pass and without, against one
+    process with the whole batch: three Adam steps, B = 4, T = 300.  The LC
+    weights sit in front of the tail (parallel.tail_start), so the early
+    all-reduce cannot start before their gradient exists; every rank reads
+    its own shard of the LC batch."""
+    spec = dict(mode='dp', B=4, T=300, steps=3, opt='adam', lr=1e-3, lc=20,
+                cfg=dict(global_condition_channels=4,
+                         global_condition_cardinality=5))
+    env = dict(WN_SHARE_GPU='1', WN_DIST_BACKEND='gloo')
+    res = {}
+    for ov in (False, True):
+        out = str(tmp_path / ('lc_ov%d.npz' % ov))
+        _run_ranks(dict(spec, overlap=ov, out=out), 2, env)
+        res[ov] = np.load(out)
+    one = str(tmp_path / 'lc_one.npz')
+    _run_ranks(dict(spec, out=one), 1)
+    one = np.load(one)
+    assert np.abs(res[True]['losses'] - res[False]['losses']).max() <= 1e-7
+    assert np.abs(res[True]['params'] - res[False]['params']).max() <= 1e-7
+    for ov in (False, True):
+        assert np.abs(res[ov]['params'] - one['params']).max() <= 1e-6
+        assert np.abs(res[ov]['losses'] - one['losses']).max() < 1e-6
+        assert np.array_equal(res[ov]['lc_w0'], one['lc_w0'])
+        assert np.abs(res[ov]['lc_w'] - res[ov]['lc_w0']).max() > 1e-4
+
+
 def _bench_json(args, env, timeout=900):
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args
                        + ['--no-secondary', '--no-cpu-baseline'],

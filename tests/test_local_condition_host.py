@@ -151,7 +151,9 @@ def test_fast_generation_refuses_lc_models_before_the_device():
 
 
 def test_restatement_matches_oracle_without_lc():
-    """tests/lc_ref.py with lc=None is the project's float64 oracle."""
+    """tests/lc_ref.py with lc=None is the project's float64 oracle: plainly,
+    with residual_postproc, and with L2 under either bias-name setting (loss,
+    every gradient and the logits)."""
     cfg = cfg_with(TINY, batch_size=2)
     var = O.create_variables(cfg, seed=3, dtype=np.float64, bias_scale=0.1)
     # (the model holds float32: the oracle gets the same rounded weights)
@@ -160,18 +162,45 @@ def test_restatement_matches_oracle_without_lc():
                      else np.asarray(t, np.float32).astype(np.float64))
     var = r32(var)
     audio = np.random.default_rng(5).uniform(-1, 1, (2, 50)).astype(np.float32)
-    ref_loss, ref_g = O.loss_and_grads(cfg, var, audio, dtype=np.float64)
     net = _net(batch_size=2, dilations=cfg['dilations'], residual_channels=8,
                dilation_channels=8, skip_channels=16, quantization_channels=16)
     net.load_nested(var)
     codes = O.mu_law_encode(audio, 16)
-    loss, g = lc_ref.loss_and_grads(lc_ref.model_tree(net), cfg['dilations'],
-                                    np.asarray(codes), None, use_biases=True,
-                                    quantization_channels=16)
-    assert abs(loss - ref_loss) < 1e-9
-    got = dict(flat_named(g))
-    for n, r in flat_named(ref_g):
-        assert np.abs(got[n] - r).max() <= 1e-9 * max(1.0, np.abs(r).max()), n
+    # (residual_postproc, l2, tf_bias_name_quirk)
+    for rp, l2, quirk in ((False, None, True), (True, None, True),
+                          (False, 0.05, True), (False, 0.05, False),
+                          (True, 0.05, False)):
+        c = cfg_with(cfg, residual_postproc=rp)
+        ref_loss, ref_g = O.loss_and_grads(c, var, audio, l2=l2,
+                                           dtype=np.float64,
+                                           tf_bias_name_quirk=quirk)
+        ref_logits = O.loss(c, var, audio, dtype=np.float64,
+                            keep=True)[1]['logits']
+        loss, g, lg = lc_ref.loss_and_grads(
+            lc_ref.model_tree(net), cfg['dilations'], np.asarray(codes), None,
+            use_biases=True, quantization_channels=16, residual_postproc=rp,
+            l2=l2, tf_bias_name_quirk=quirk, return_logits=True)
+        assert abs(loss - ref_loss) < 1e-9, (rp, l2, quirk)
+        got = dict(flat_named(g))
+        for n, r in flat_named(ref_g):
+            assert np.abs(got[n] - r).max() <= 1e-9 * max(1.0, np.abs(r).max()), \
+                (rp, l2, quirk, n)
+        assert np.abs(lg - ref_logits).max() < 1e-9
+        fwd = lc_ref.logits(lc_ref.model_tree(net), cfg['dilations'],
+                            np.asarray(codes), None, use_biases=True,
+                            quantization_channels=16, residual_postproc=rp)
+        assert np.array_equal(fwd, lg)
+    # the L2 term itself: with the quirk off the biases leave it
+    la = lc_ref.loss_and_grads(lc_ref.model_tree(net), cfg['dilations'],
+                               np.asarray(codes), None, use_biases=True,
+                               quantization_channels=16, l2=0.05)[0]
+    lb = lc_ref.loss_and_grads(lc_ref.model_tree(net), cfg['dilations'],
+                               np.asarray(codes), None, use_biases=True,
+                               quantization_channels=16, l2=0.05,
+                               tf_bias_name_quirk=False)[0]
+    nb = sum((a ** 2).sum() / 2 for n, a in flat_named(var)
+             if 'bias' in n.split('/')[-1])
+    assert nb > 0 and abs((la - lb) - 0.05 * nb) < 1e-12
 
 
 # ---- entry points: argument validation without launching -------------------
