@@ -8,12 +8,16 @@ one step per seed sample) and temperature sampling happen on the device.
 --fast_generation false uses the windowed naive path (`predict_proba`, host-side
 np.random.choice) like the reference.  wav I/O is scipy (librosa is absent).
 
-Local conditioning (naive path only): --lc_path features.npy [frames, Lc] are
-upsampled by repetition (--lc_hop samples per frame) and ONE sample is
-generated per upsampled row after the seed (--samples is ignored).  Row k sits
-beside generated sample k, as in training (the row beside input sample t
-conditions the prediction of sample t + 1); the seed's rows are zeros.  Each
-window passes its own rows to predict_proba.
+Local conditioning: --lc_path features.npy [frames, Lc] are upsampled by
+repetition (--lc_hop samples per frame) and ONE sample is generated per
+upsampled row after the seed (--samples is ignored).  Row k sits beside
+generated sample k, as in training (the row beside input sample t conditions
+the prediction of sample t + 1); the seed's rows are zeros.  On the naive path
+(--fast_generation false) each window passes its own rows to predict_proba.
+--lc_fast_generation true opts in to fast generation instead: `generate` /
+`continue_generation` (in --save_every chunks) take the rows of the positions
+they step through, and with --clips N `generate_batch` runs the N clips on
+rows shared by all of them.  Without either flag --lc_path is refused.
 """
 from __future__ import division
 from __future__ import print_function
@@ -78,7 +82,11 @@ def get_arguments(argv=None):
                    '<stem>_<i><ext>')
     p.add_argument('--lc_path', type=str, default=None,
                    help='local conditioning features (.npy, [frames, '
-                   'channels]); needs --fast_generation false')
+                   'channels]); needs --fast_generation false or '
+                   '--lc_fast_generation true')
+    p.add_argument('--lc_fast_generation', type=_str_to_bool, default=False,
+                   help='with --lc_path: generate on the fast path '
+                   '(default false: --lc_path needs --fast_generation false)')
     p.add_argument('--lc_hop', type=int, default=1,
                    help='audio samples per feature frame of --lc_path')
     p.add_argument('--gc_ids', type=str, default=None,
@@ -134,10 +142,11 @@ def main(argv=None):
     args = get_arguments(argv)
     lc_rows = None
     if args.lc_path is not None:
-        if args.fast_generation:
+        if args.fast_generation and not args.lc_fast_generation:
             print('Local conditioning (--lc_path) needs the naive path: '
-                  'pass --fast_generation false (fast generation with local '
-                  'conditioning is not supported yet).')
+                  'pass --fast_generation false, or opt in to fast '
+                  'generation with local conditioning with '
+                  '--lc_fast_generation true.')
             return 1
         from wavenet.audio_reader import upsample_lc
         feats = np.load(args.lc_path)
@@ -190,8 +199,20 @@ def main(argv=None):
             out = mu_law_decode(np.asarray(codes, np.int32), Q).cpu().numpy()
             write_wav(out, rate, args.wav_out_path)
 
+    lc_full = None
+    if lc_rows is not None:
+        # row of every input position: zeros beside the seed, feature row
+        # k beside generated sample k
+        n0 = len(waveform)
+        lc_full = np.zeros((n0 + args.samples, lc_rows.shape[1]),
+                           np.float32)
+        lc_full[n0:] = lc_rows
+
+    def rows(pos, n):              # the rows of the n positions from pos
+        return None if lc_full is None else lc_full[pos:pos + n]
+
     if args.clips > 1:
-        return _main_clips(args, net, waveform, Q, rate, logdir)
+        return _main_clips(args, net, waveform, Q, rate, logdir, rows)
     if args.fast_generation:
         if args.wav_seed:
             print('Priming generation with {} seed samples...'
@@ -200,17 +221,20 @@ def main(argv=None):
         done = 0
         # first call primes (teacher-forced steps) and starts drawing; later
         # chunks continue from the device-resident queues
-        codes = net.generate(min(chunk, args.samples), seed_samples=waveform,
+        n1 = min(chunk, args.samples)
+        codes = net.generate(n1, seed_samples=waveform,
                              temperature=args.temperature,
-                             global_condition=gc, seed=args.seed)
+                             global_condition=gc, seed=args.seed,
+                             local_condition=rows(0, len(waveform) + n1 - 1))
         waveform = codes.cpu().numpy().tolist()
         done += min(chunk, args.samples)
         if args.save_every and done < args.samples:
             dump(waveform)
         while done < args.samples:
             n = min(chunk, args.samples - done)
-            more = net.continue_generation(n, waveform[-1], args.temperature,
-                                           gc, args.seed)
+            more = net.continue_generation(
+                n, waveform[-1], args.temperature, gc, args.seed,
+                local_condition=rows(len(waveform) - 1, n))
             waveform.extend(more.cpu().numpy().tolist())
             done += n
             print('Sample {:3<d}/{:3<d}'.format(done, args.samples), end='\r')
@@ -221,14 +245,6 @@ def main(argv=None):
         # one workspace for the whole window: the growing inputs of the first
         # `window` steps are views of it
         net.reserve(1, min(args.window, len(waveform) + args.samples))
-        lc_full = None
-        if lc_rows is not None:
-            # row of every input position: zeros beside the seed, feature row
-            # k beside generated sample k
-            n0 = len(waveform)
-            lc_full = np.zeros((n0 + args.samples, lc_rows.shape[1]),
-                               np.float32)
-            lc_full[n0:] = lc_rows
         for step in range(args.samples):
             window = waveform[-args.window:] if len(waveform) > args.window \
                 else waveform
@@ -269,9 +285,10 @@ def _clip_path(path, i):
     return '{}_{}{}'.format(stem, i, ext)
 
 
-def _main_clips(args, net, waveform, Q, rate, logdir):
+def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None):
     """--clips N > 1: N streams in lock step (WaveNetModel.generate_batch),
-    clip i drawing with --seed + i, all primed by the same seed."""
+    clip i drawing with --seed + i, all primed by the same seed (and, with
+    --lc_path, conditioned on the same rows(position, n))."""
     from wavenet import mu_law_decode
     N = args.clips
     seeds = [args.seed + i for i in range(N)]
@@ -291,14 +308,17 @@ def _main_clips(args, net, waveform, Q, rate, logdir):
     done = min(chunk, args.samples)
     codes = net.generate_batch(done, seeds, seed_samples=waveform,
                                temperature=args.temperature,
-                               global_condition=gc).cpu().numpy()
+                               global_condition=gc,
+                               local_condition=rows(0, len(waveform) + done - 1)
+                               ).cpu().numpy()
     parts = [codes]
     while done < args.samples:
         if args.save_every:
             dump(np.concatenate(parts, axis=1))
         n = min(chunk, args.samples - done)
-        more = net.continue_generation_batch(n, parts[-1][:, -1], seeds,
-                                             args.temperature, gc)
+        more = net.continue_generation_batch(
+            n, parts[-1][:, -1], seeds, args.temperature, gc,
+            local_condition=rows(len(waveform) + done - 1, n))
         parts.append(more.cpu().numpy())
         done += n
         print('Sample {:3<d}/{:3<d}'.format(done, args.samples), end='\r')

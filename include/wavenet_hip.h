@@ -643,6 +643,88 @@ int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
                             const int32_t* ctl, const uint64_t* seeds,
                             float* proba_out, const float* logits, void* stream);
 
+/* ---- local conditioning in fast generation (csrc/wn_fastgen_lc.hip).
+ * The conditioned-bias ring: for positions p = p0 .. p0 + n_rows - 1 and every
+ * stream b,
+ *   ring[p % R][l][b][0:64] = gc_bias_fg[l][b] + sum_k lc[b][p - p0][k] lc_w[k][l][0:64]
+ * (lc row i of stream b at lc + b * lc_stream_stride + i * Lc; lc_w the
+ * model's [Lcp][L][64] segment; gc_bias_fg as wn_fastgen_batch_pre's, or NULL).
+ * The sum is one fmaf chain in k order: a row's bits depend on Lc only.
+ * ring_stream_stride 64: ring [R][L][B][64]; 0: [R][L][1][64], one row for
+ * all streams (then lc_stream_stride and bias_stream_stride must be 0).
+ * n_rows <= R, 1 <= B <= 256. */
+int wn_fastgen_lc_bias(const float* lc, long lc_stream_stride, int Lc,
+                       const float* lc_w, int L, const float* gc_bias_fg,
+                       int bias_stream_stride, int B, long p0, int n_rows,
+                       float* ring, int R, int ring_stream_stride, void* stream);
+/* The _lc variants take the arguments of their entry point plus the ring
+ * (lc_ring, its rows lc_R, its stream stride lc_stride: 0 or 64) and read the
+ * filter|gate bias of step p from ring row p % lc_R in place of gc_bias_fg
+ * (which they still accept and do not read).  Step p is the step that
+ * consumes the input at position p (cursors[0] = p when it starts): its row
+ * holds the LC row beside that input.  Everything else is the plain entry
+ * point's: the draw, the chain, the skip sum and the post-processing. */
+int wn_fastgen_run_lc(const float* params_causal, const float* layer0,
+                      long layer_stride, const float* skip_w,
+                      const float* skip_bsum, const float* post1_w,
+                      const float* post1_b, const float* post2_w,
+                      const float* post2_b, const float* gc_bias_fg,
+                      const int32_t* dilations_dev, int L, int S, int Q,
+                      float* state, int32_t* cursors, int32_t* samples_io,
+                      int n_given, int n_steps, float temperature,
+                      uint64_t seed, float* proba_out, int proba_every,
+                      int use_biases, int push, const float* lc_ring, int lc_R,
+                      int lc_stride, void* stream);
+int wn_fastgen_pre_lc(const float* layer0, long layer_stride,
+                      const float* gc_bias_fg, const int32_t* dilations_dev,
+                      int L, const float* state, const int32_t* cursors,
+                      float* pre, const float* lc_ring, int lc_R, int lc_stride,
+                      void* stream);
+int wn_fastgen_step_lc(const float* params_causal, const float* layer0,
+                       long layer_stride, const float* skip_w,
+                       const float* skip_bsum, const float* post1_w,
+                       const float* post1_b, const float* post2_w,
+                       const float* post2_b, const float* gc_bias_fg,
+                       const int32_t* dilations_dev, int L, int S, int Q,
+                       float* state, int32_t* cursors, int32_t* samples_io,
+                       const int32_t* ctl, float* proba_out, int use_biases,
+                       const float* cw_img, float* pre, float* z_all, float* h1,
+                       float* h2, float* logits, const float* lc_ring, int lc_R,
+                       int lc_stride, void* stream);
+int wn_fastgen_persist_lc(const float* params_causal, const float* layer0,
+                          long layer_stride, const float* skip_w,
+                          const float* skip_bsum, const float* post1_w,
+                          const float* post1_b, const float* post2_w,
+                          const float* post2_b, const float* gc_bias_fg,
+                          const int32_t* dilations_dev, int L, int S, int Q,
+                          float* state, int32_t* cursors, int32_t* samples_io,
+                          const int32_t* ctl, float* proba_out, int use_biases,
+                          const float* cw_img, float* pre, float* z_all,
+                          float* h1, float* h2, float* logits, unsigned* sync,
+                          unsigned long long* ll, int n_steps,
+                          const float* lc_ring, int lc_R, int lc_stride,
+                          void* stream);
+int wn_fastgen_batch_pre_lc(const float* layer0, long layer_stride,
+                            const float* gc_bias_fg, int bias_stream_stride,
+                            const int32_t* dilations_dev, int L, int B,
+                            const float* state, const int32_t* cursors,
+                            float* pre, const float* lc_ring, int lc_R,
+                            int lc_stride, void* stream);
+int wn_fastgen_batch_step_lc(const float* params_causal, const float* layer0,
+                             long layer_stride, const float* skip_w,
+                             const float* skip_bsum, const float* post1_w,
+                             const float* post1_b, const float* post2_w,
+                             const float* post2_b, const float* gc_bias_fg,
+                             int bias_stream_stride,
+                             const int32_t* dilations_dev, int L, int S, int Q,
+                             int B, float* state, int32_t* cursors,
+                             int32_t* prev, int32_t* samples_io,
+                             const int32_t* ctl, const uint64_t* seeds,
+                             float* proba_out, int use_biases, float* pre,
+                             float* z_all, float* h1, float* h2, float* logits,
+                             const float* lc_ring, int lc_R, int lc_stride,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

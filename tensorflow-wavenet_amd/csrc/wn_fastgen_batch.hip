@@ -301,7 +301,16 @@ __device__ __forceinline__ void fgb_gemm_tile(const FgbGemm& p, int nt, int mt,
 // pre[l][b][0:32 | 32:64] = x_l[t' - d_l] (Wf[0] | Wg[0]) + bias_fg[l][b] for
 // the step t' = cursors[0] + ahead, group gi (rows past B: 0).  Wave w:
 // rows 16 (w & 1), filter (w < 2) or gate half, two 16-column tiles.
-__device__ __forceinline__ void fgb_pre_tile(const FgBatch& g, int l, int gi, int ahead) {
+// LC: the bias of stream b is row tpos of the conditioned-bias ring
+// [R][L][nb][64] (wn_fastgen_lc_bias; nb = B with stream stride 64, 1 with 0).
+struct FgbLc {
+  const float* ring;
+  int R, stride;
+};
+
+template <bool LC>
+__device__ __forceinline__ void fgb_pre_tile(const FgBatch& g, const FgbLc& lc, int l, int gi,
+                                             int ahead) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int rb = w & 1, half = w >> 1;
   const int ci = lane & 15, kk = lane >> 4;
@@ -327,7 +336,13 @@ __device__ __forceinline__ void fgb_pre_tile(const FgBatch& g, int l, int gi, in
     float v0 = 0.f, v1 = 0.f;
     if (b < g.B) {
       float c0 = 0.f, c1 = 0.f;
-      if (g.bias_fg) {
+      if (LC) {
+        const long rl = lc.stride ? (long)g.B * 64 : 64;
+        const float* bb = lc.ring + ((long)(tpos % lc.R) * g.L + l) * rl + (long)b * lc.stride +
+                          half * 32;
+        c0 = bb[ci];
+        c1 = bb[16 + ci];
+      } else if (g.bias_fg) {
         const float* bb = g.bias_fg + l * lstride + (long)b * g.bias_stride + half * 32;
         c0 = bb[ci];
         c1 = bb[16 + ci];
@@ -341,24 +356,41 @@ __device__ __forceinline__ void fgb_pre_tile(const FgBatch& g, int l, int gi, in
 }
 
 __global__ __launch_bounds__(256) void fgb_pre_kernel(FgBatch g, int ahead) {
-  fgb_pre_tile(g, blockIdx.x / (g.Bp / FGB_TILE), blockIdx.x % (g.Bp / FGB_TILE), ahead);
+  const FgbLc none = {nullptr, 0, 0};
+  fgb_pre_tile<false>(g, none, blockIdx.x / (g.Bp / FGB_TILE), blockIdx.x % (g.Bp / FGB_TILE),
+                      ahead);
+}
+
+__global__ __launch_bounds__(256) void fgb_pre_lc_kernel(FgBatch g, FgbLc lc, int ahead) {
+  fgb_pre_tile<true>(g, lc, blockIdx.x / (g.Bp / FGB_TILE), blockIdx.x % (g.Bp / FGB_TILE),
+                     ahead);
 }
 
 __host__ __device__ __forceinline__ int fgb_ntiles(int n) { return (n + 15) / 16; }
 
 // h1 = relu(z_all . Ws + bsum), then L x Bp/32 more workgroups: the next
 // step's pre-activations
-__global__ __launch_bounds__(256) void fgb_skip_kernel(FgBatch g) {
+template <bool LC>
+__device__ __forceinline__ void fgb_skip_body(const FgBatch& g, const FgbLc& lc) {
   __shared__ float red[4][256];
   const int nt = fgb_ntiles(g.S), nskip = nt * (g.Bp / 16);
   const int bid = blockIdx.x;
   if (bid >= nskip) {                       // workgroup-uniform
     const int r = bid - nskip, ng = g.Bp / FGB_TILE;
-    fgb_pre_tile(g, r / ng, r % ng, 1);
+    fgb_pre_tile<LC>(g, lc, r / ng, r % ng, 1);
     return;
   }
   FgbGemm p = {g.z_all, (long)g.L * 32, g.L * 32, g.skip_w, g.S, g.S, g.skip_bsum, 1, g.h1, g.S};
   fgb_gemm_tile(p, bid % nt, bid / nt, red);
+}
+
+__global__ __launch_bounds__(256) void fgb_skip_kernel(FgBatch g) {
+  const FgbLc none = {nullptr, 0, 0};
+  fgb_skip_body<false>(g, none);
+}
+
+__global__ __launch_bounds__(256) void fgb_skip_lc_kernel(FgBatch g, FgbLc lc) {
+  fgb_skip_body<true>(g, lc);
 }
 
 __global__ __launch_bounds__(256) void fgb_post1_kernel(FgBatch g) {
@@ -385,6 +417,14 @@ static int fgb_rows(int B) { return (B + FGB_TILE - 1) / FGB_TILE * FGB_TILE; }
 static int fgb_check_batch(int B) {
   if (B <= 0) return WN_ERR_BAD_SHAPE;
   if (B > FGB_MAXB) return WN_ERR_UNSUPPORTED;
+  return WN_OK;
+}
+
+// null: no local conditioning; else the ring must be set and its shape sane
+static int fgb_check_lc(const FgbLc* lc) {
+  if (!lc) return WN_OK;
+  if (!lc->ring) return WN_ERR_NULL;
+  if (lc->R < 1 || (lc->stride != 0 && lc->stride != 64)) return WN_ERR_BAD_SHAPE;
   return WN_OK;
 }
 
@@ -423,11 +463,13 @@ int wn_fastgen_batch_init(float* state, long state_floats, int32_t* cursors, int
   return WN_OK;
 }
 
-int wn_fastgen_batch_pre(const float* layer0, long layer_stride, const float* gc_bias_fg,
-                         int bias_stream_stride, const int32_t* dilations_dev, int L, int B,
-                         const float* state, const int32_t* cursors, float* pre,
-                         void* stream) {
+static int fgb_pre(const FgbLc* lc, const float* layer0, long layer_stride,
+                   const float* gc_bias_fg, int bias_stream_stride,
+                   const int32_t* dilations_dev, int L, int B, const float* state,
+                   const int32_t* cursors, float* pre, void* stream) {
   if (!layer0 || !dilations_dev || !state || !cursors || !pre) return WN_ERR_NULL;
+  const int lrc = fgb_check_lc(lc);
+  if (lrc != WN_OK) return lrc;
   if (L <= 0 || (bias_stream_stride != 0 && bias_stream_stride != 64)) return WN_ERR_BAD_SHAPE;
   if (L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
   const int rc = fgb_check_batch(B);
@@ -437,15 +479,36 @@ int wn_fastgen_batch_pre(const float* layer0, long layer_stride, const float* gc
   g.bias_stride = bias_stream_stride; g.dil = dilations_dev; g.L = L; g.B = B;
   g.Bp = fgb_rows(B); g.state = const_cast<float*>(state);
   g.cursors = const_cast<int32_t*>(cursors); g.pre = pre;
-  hipLaunchKernelGGL(fgb_pre_kernel, dim3(L * (g.Bp / FGB_TILE)), dim3(256), 0,
-                     (hipStream_t)stream, g, 0);
+  if (lc)
+    hipLaunchKernelGGL(fgb_pre_lc_kernel, dim3(L * (g.Bp / FGB_TILE)), dim3(256), 0,
+                       (hipStream_t)stream, g, *lc, 0);
+  else
+    hipLaunchKernelGGL(fgb_pre_kernel, dim3(L * (g.Bp / FGB_TILE)), dim3(256), 0,
+                       (hipStream_t)stream, g, 0);
   return wn_check_launch();
+}
+
+int wn_fastgen_batch_pre(const float* layer0, long layer_stride, const float* gc_bias_fg,
+                         int bias_stream_stride, const int32_t* dilations_dev, int L, int B,
+                         const float* state, const int32_t* cursors, float* pre,
+                         void* stream) {
+  return fgb_pre(nullptr, layer0, layer_stride, gc_bias_fg, bias_stream_stride, dilations_dev,
+                 L, B, state, cursors, pre, stream);
+}
+
+int wn_fastgen_batch_pre_lc(const float* layer0, long layer_stride, const float* gc_bias_fg,
+                            int bias_stream_stride, const int32_t* dilations_dev, int L, int B,
+                            const float* state, const int32_t* cursors, float* pre,
+                            const float* lc_ring, int lc_R, int lc_stride, void* stream) {
+  const FgbLc lc = {lc_ring, lc_R, lc_stride};
+  return fgb_pre(&lc, layer0, layer_stride, gc_bias_fg, bias_stream_stride, dilations_dev, L, B,
+                 state, cursors, pre, stream);
 }
 
 // Enqueue the stages [first, last) of one step: 0 draw, 1 chain, 2 skip sum +
 // next pre-activations, 3 post1, 4 logits (wn_fastgen_batch_step: all five;
 // single stages let a caller time each launch between its own events).
-int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
+static int fgb_stages(const FgbLc* lc, int first, int last, const float* params_causal,
                             const float* layer0, long layer_stride, const float* skip_w,
                             const float* skip_bsum, const float* post1_w,
                             const float* post1_b, const float* post2_w, const float* post2_b,
@@ -462,6 +525,8 @@ int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
   if (L <= 0 || S <= 0 || Q <= 0 || (bias_stream_stride != 0 && bias_stream_stride != 64) ||
       first < 0 || last > 5 || first >= last)
     return WN_ERR_BAD_SHAPE;
+  const int lrc = fgb_check_lc(lc);
+  if (lrc != WN_OK) return lrc;
   if (S > FGB_MAXS || Q > FGB_MAXQ || L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
   const int rc = fgb_check_batch(B);
   if (rc != WN_OK) return rc;
@@ -485,8 +550,12 @@ int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
         hipLaunchKernelGGL(fgb_chain_kernel, dim3(ng), dim3(256), 0, s, g);
         break;
       case 2:
-        hipLaunchKernelGGL(fgb_skip_kernel, dim3(fgb_ntiles(S) * mt + L * ng), dim3(256), 0, s,
-                           g);
+        if (lc)
+          hipLaunchKernelGGL(fgb_skip_lc_kernel, dim3(fgb_ntiles(S) * mt + L * ng), dim3(256), 0,
+                             s, g, *lc);
+        else
+          hipLaunchKernelGGL(fgb_skip_kernel, dim3(fgb_ntiles(S) * mt + L * ng), dim3(256), 0, s,
+                             g);
         break;
       case 3:
         hipLaunchKernelGGL(fgb_post1_kernel, dim3(fgb_ntiles(S) * mt), dim3(256), 0, s, g);
@@ -499,6 +568,39 @@ int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
   return wn_check_launch();
 }
 
+int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
+                            const float* layer0, long layer_stride, const float* skip_w,
+                            const float* skip_bsum, const float* post1_w,
+                            const float* post1_b, const float* post2_w, const float* post2_b,
+                            const float* gc_bias_fg, int bias_stream_stride,
+                            const int32_t* dilations_dev, int L, int S, int Q, int B,
+                            float* state, int32_t* cursors, int32_t* prev,
+                            int32_t* samples_io, const int32_t* ctl, const uint64_t* seeds,
+                            float* proba_out, int use_biases, float* pre, float* z_all,
+                            float* h1, float* h2, float* logits, void* stream) {
+  return fgb_stages(nullptr, first, last, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+                    post1_w, post1_b, post2_w, post2_b, gc_bias_fg, bias_stream_stride,
+                    dilations_dev, L, S, Q, B, state, cursors, prev, samples_io, ctl, seeds,
+                    proba_out, use_biases, pre, z_all, h1, h2, logits, stream);
+}
+
+int wn_fastgen_batch_step_lc(const float* params_causal, const float* layer0, long layer_stride,
+                             const float* skip_w, const float* skip_bsum, const float* post1_w,
+                             const float* post1_b, const float* post2_w, const float* post2_b,
+                             const float* gc_bias_fg, int bias_stream_stride,
+                             const int32_t* dilations_dev, int L, int S, int Q, int B,
+                             float* state, int32_t* cursors, int32_t* prev, int32_t* samples_io,
+                             const int32_t* ctl, const uint64_t* seeds, float* proba_out,
+                             int use_biases, float* pre, float* z_all, float* h1, float* h2,
+                             float* logits, const float* lc_ring, int lc_R, int lc_stride,
+                             void* stream) {
+  const FgbLc lc = {lc_ring, lc_R, lc_stride};
+  return fgb_stages(&lc, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum, post1_w,
+                    post1_b, post2_w, post2_b, gc_bias_fg, bias_stream_stride, dilations_dev, L,
+                    S, Q, B, state, cursors, prev, samples_io, ctl, seeds, proba_out, use_biases,
+                    pre, z_all, h1, h2, logits, stream);
+}
+
 int wn_fastgen_batch_step(const float* params_causal, const float* layer0, long layer_stride,
                           const float* skip_w, const float* skip_bsum, const float* post1_w,
                           const float* post1_b, const float* post2_w, const float* post2_b,
@@ -508,7 +610,7 @@ int wn_fastgen_batch_step(const float* params_causal, const float* layer0, long 
                           const int32_t* ctl, const uint64_t* seeds, float* proba_out,
                           int use_biases, float* pre, float* z_all, float* h1, float* h2,
                           float* logits, void* stream) {
-  return wn_fastgen_batch_stages(0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+  return fgb_stages(nullptr, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum,
                                  post1_w, post1_b, post2_w, post2_b, gc_bias_fg,
                                  bias_stream_stride, dilations_dev, L, S, Q, B, state, cursors,
                                  prev, samples_io, ctl, seeds, proba_out, use_biases, pre, z_all,

@@ -158,7 +158,17 @@ SIGNATURES = {
                                         c_int, c_int, P, P, P, P, P, P, P,
                                         c_int, P, P, P, P, P, P]),
     'wn_fastgen_batch_finish': (c_int, [c_int, c_int, P, P, P, P, P, P, P]),
+    # local conditioning: the conditioned-bias ring and the _lc variants
+    # (the entry point's arguments + ring, its rows R, its stream stride)
+    'wn_fastgen_lc_bias': (c_int, [P, c_long, c_int, P, c_int, P, c_int,
+                                   c_int, c_long, c_int, P, c_int, c_int, P]),
 }
+for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
+              'wn_fastgen_persist', 'wn_fastgen_batch_pre',
+              'wn_fastgen_batch_step'):
+    # ..., const float* lc_ring, int lc_R, int lc_stride, void* stream
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + '_lc'] = (_res, _args[:-1] + [P, c_int, c_int, P])
 
 
 

@@ -43,6 +43,91 @@ def _new_state(net, dil, nfl, rows, nbias, **extra):
         graphs={}, warm=False, steps=0, **extra)
 
 
+# ----------------------------------------------- local conditioning (LC)
+# A call of n_steps steps on an LC model runs in chunks of C steps.  Before
+# the chunk at call step a, the conditioned-bias ring (wn_fastgen_lc_bias)
+# gets the rows of steps a .. a + C: step t also forms step t + 1's past-tap
+# pre-activations, so a chunk needs one row past its end and the ring
+# R = C + 1 rows (slot = position % R).  The row past the call's last input is
+# written from a zero LC row; its value is never used, since every call
+# recomputes its first step's pre-activations.
+LC_RING_BYTES = 256 << 20
+# one stream: a smaller ring (it stays allocated with the generator); 2600
+# steps per chunk for the default stack, one persistent launch each
+LC_RING_BYTES_ONE = 32 << 20
+
+
+def lc_chunk(n_steps, row_bytes, forced=None, graph_steps=200, proba_every=1,
+             budget=LC_RING_BYTES):
+    """Steps per chunk: `forced` (net.fastgen_lc_chunk), else as many as a
+    ring of `budget` bytes holds (rows of `row_bytes`) rounded down to a
+    multiple of the graph length, but at least one graph length; then a
+    multiple of proba_every (so that every chunk starts on a probability
+    row) and at most n_steps."""
+    if forced is not None:
+        c = int(forced)
+        if c < 1:
+            raise ValueError('fastgen_lc_chunk must be >= 1 or None, got %r'
+                             % (forced,))
+    else:
+        c = max(1, int(budget) // int(row_bytes) - 1)
+        c = max(int(graph_steps), c - c % int(graph_steps))
+    pe = max(1, int(proba_every))
+    c = -(-c // pe) * pe
+    return max(1, min(c, int(n_steps)))
+
+
+def lc_plan(n_steps, chunk):
+    """[(a, n)]: chunks of n steps starting at call step a; each fills ring
+    rows a .. a + n (n + 1 rows; row n_steps is the zero lookahead row)."""
+    return [(a, min(chunk, n_steps - a)) for a in range(0, n_steps, chunk)]
+
+
+def _lc_device(net, lc):
+    # a call's LC rows, checked by the model, as float32 on the device (once)
+    return None if lc is None else lc.to(device=net.device,
+                                         dtype=torch.float32).contiguous()
+
+
+def _lc_rows_padded(net, lc, n_steps):
+    # [..., n_steps, Lc] -> float32 [..., n_steps + 1, Lc] (the zero row)
+    z = torch.zeros(lc.shape[:-2] + (1, net.Lc), dtype=torch.float32,
+                    device=net.device)
+    return torch.cat([lc.to(device=net.device, dtype=torch.float32), z],
+                     dim=-2).contiguous()
+
+
+class _LcRing(object):
+    """The ring of one call: rows of `lcz` [nl, n_steps + 1, Lc] (nl = 1:
+    shared by all B streams) for the positions p0 + call step."""
+
+    def __init__(self, net, g, lcz, B, bias, bstride, n_steps, pe):
+        self.net, self.lcz, self.B = net, lcz, B
+        self.bias, self.bstride = bias, bstride
+        self.lc_stride = lcz.shape[-2] * net.Lc if lcz.shape[0] > 1 else 0
+        self.rstride = 64 if (self.lc_stride or bstride) else 0
+        nr = B if self.rstride else 1
+        row = net.L * nr * 64
+        self.C = lc_chunk(n_steps, row * 4, net.fastgen_lc_chunk,
+                          int(net.fastgen_graph_steps), pe,
+                          LC_RING_BYTES if B > 1 else LC_RING_BYTES_ONE)
+        self.R = self.C + 1
+        self.ring = _buf(net, g, 'lc_ring', self.R * row, torch.float32)
+        self.p0 = int(g['steps'])
+        self.plan = lc_plan(n_steps, self.C)
+
+    def args(self):
+        return (_lib.ptr(self.ring), self.R, self.rstride)
+
+    def fill(self, a, n):
+        net = self.net
+        _lib.call('wn_fastgen_lc_bias', _lib.ptr(self.lcz[0, a]),
+                  self.lc_stride, net.Lc, _lib.ptr(net._seg(net.params, 'lc_w')),
+                  net.L, self.bias, self.bstride, self.B,
+                  self.p0 + a, n + 1, _lib.ptr(self.ring), self.R,
+                  self.rstride, _lib.stream())
+
+
 def _check_temperature(temperature):
     if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
         raise ValueError('temperature must be a finite number > 0, got %r'
@@ -164,8 +249,10 @@ def _prime(net, g, n0, groups, Bp):
     src = torch.from_numpy(np.concatenate(src)).to(net.device)
     dst = np.concatenate(dst)
     ws = net._workspace(1, n0, False)
-    for codes, gc, streams in groups:
+    for codes, gc, streams, lc in groups:
         ws.q.copy_(codes)
+        if lc is not None:         # the seed's LC rows, as predict_proba
+            ws.lc[:, :net.Lc].copy_(lc.reshape(n0, net.Lc))
         net._run_pass('fwd', ws, net._gc_ids(gc, 1),
                       net._step_path(ws, False))
         # (+ the forward launch's poison word: 0, or NaN after an expired wait)
@@ -176,16 +263,22 @@ def _prime(net, g, n0, groups, Bp):
             vals.repeat(len(streams), 1))
 
 
-def _seeded(net, io, n_given, n, pe, prime, run):
+def _seeded(net, io, n_given, n, pe, prime, run, lc=None):
     # io [..., n_given + n] starts with the seed codes; returns the
-    # probabilities [..., rows, Q] of every pe-th step, or None
+    # probabilities [..., rows, Q] of every pe-th step, or None.  lc: the
+    # call's LC rows [..., n_steps, Lc] (run gets those of its steps)
     n_steps = n_given - 1 + n
+    primed = prime and pe == 0 and \
+        n_given - 1 >= net.fastgen_prime_forward_min and n > 0 and \
+        (lc is None or net._lc_forward_ok(n_given - 1))
+    if lc is not None:
+        run = functools.partial(run, lc=lc[..., n_given - 1:, :] if primed
+                                else lc)
     proba = None
     if pe > 0:
         proba = torch.empty(io.shape[:-1] + ((n_steps + pe - 1) // pe, net.Q),
                             dtype=torch.float32, device=net.device)
-    if prime and pe == 0 and n_given - 1 >= net.fastgen_prime_forward_min \
-            and n > 0:
+    if primed:
         # the reference's own TODO (generate.py:199-201): fill the queues
         # from a forward pass over the seed instead of stepping through it
         prime()
@@ -229,9 +322,10 @@ def reset(net):
 
 
 def run(net, temperature, seed, global_condition, samples_io, n_given,
-        n_steps, proba_out, proba_every, push=True, multi_cu=False):
+        n_steps, proba_out, proba_every, push=True, multi_cu=False, lc=None):
     """Run `n_steps` generation steps on samples_io int32 [n_steps + 1]
-    (the first n_given codes given, the rest drawn) on one device path."""
+    (the first n_given codes given, the rest drawn) on one device path.
+    lc: an LC model's rows [n_steps, Lc], row i beside samples_io[i]."""
     # (wn_fastgen_step reads both from the device control block and cannot
     # reject them; the reference applies the temperature as log(p) / T,
     # generate.py:229-233)
@@ -247,7 +341,11 @@ def run(net, temperature, seed, global_condition, samples_io, n_given,
     run_args = queues + (_lib.ptr(samples_io), int(n_given), int(n_steps),
                          float(temperature), sd, _lib.ptr(proba_out),
                          int(proba_every), ub, 1 if push else 0)
-    if net.CB > 1 or net.S > 512 or net.Q > 512 or net.L > 64:
+    if lc is not None:
+        _run_lc(net, g, head, bias, queues, samples_io, int(n_given),
+                int(n_steps), float(temperature), sd, proba_out,
+                max(1, int(proba_every)), ub, push, multi_cu, lc)
+    elif net.CB > 1 or net.S > 512 or net.Q > 512 or net.L > 64:
         _run_wide(net, g, samples_io,
                   head + (net.L, net.CHn, net.S, net.Q) + run_args)
     elif not multi_cu or not push:
@@ -283,6 +381,86 @@ def run(net, temperature, seed, global_condition, samples_io, n_given,
         g['steps'] += int(n_steps)
 
 
+def _run_lc(net, g, head, bias, queues, samples_io, n_given, n_steps,
+            temperature, sd, proba_out, pe, ub, push, multi_cu, lc):
+    # one LC call, chunk by chunk (see _LcRing); the paths of run()
+    ring = _LcRing(net, g, _lc_rows_padded(net, lc.reshape(1, n_steps, net.Lc),
+                                           n_steps), 1, bias, 0, n_steps, pe)
+    Q = net.Q
+
+    def prows(a):                  # the probability rows from call step a
+        return None if proba_out is None else proba_out.view(-1)[a // pe * Q:]
+    if not multi_cu or not push:
+        for a, n in ring.plan:
+            ring.fill(a, n)
+            _lib.call('wn_fastgen_run_lc', *head, net.L, net.S, net.Q,
+                      *queues, _lib.ptr(samples_io[a:]), max(1, n_given - a),
+                      n, temperature, sd, _lib.ptr(prows(a)), pe, ub,
+                      1 if push else 0, *ring.args(), _lib.stream())
+        return
+    st = _lib.stream()
+    layer0 = _lib.ptr(net._layer_block(net.params, 0))
+    _lib.call('wn_fastgen_pack', layer0, net.layer_stride,
+              _lib.ptr(g['cw_img']), net.L, st)
+    io = samples_io.view(1, -1)
+    steps0 = g['steps']
+
+    def sub(a, n_run):
+        # calls steps a .. a + n_run as a call of their own (ctl, io, proba)
+        g['steps'] = steps0 + a
+        pr = prows(a)
+        iob, pb = _stage(net, g, io[:, a:], max(1, n_given - a), n_run,
+                         temperature, pr, pe, seed=sd)
+        common = head + (net.L, net.S, net.Q) + queues + (_lib.ptr(iob),)
+        tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), ub, _lib.ptr(g['cw_img']),
+                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
+                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
+
+        def done():
+            samples_io[a:a + n_run + 1].copy_(iob[:n_run + 1])
+            if pr is not None:
+                k = (n_run + pe - 1) // pe * Q
+                pr[:k].copy_(pb[:k])
+        return iob, pb, common, tail, done
+
+    def pre():
+        _lib.call('wn_fastgen_pre_lc', layer0, net.layer_stride, bias,
+                  _lib.ptr(g['dil']), net.L, *queues, _lib.ptr(g['pre']),
+                  *ring.args(), st)
+    a_step = n_steps               # where the step kernels take over
+    if net.fastgen_persistent and not net._gen_launch_failed.get('persist'):
+        for a, n in ring.plan:
+            ring.fill(a, n)
+            pre()
+            iob, pb, common, tail, done = sub(a, n)
+            if not _run_persistent(net, g, common, tail, io[:, a:], iob, n,
+                                   lc=ring.args()):
+                a_step = a
+                break
+            done()
+    else:
+        a_step = 0
+    if a_step < n_steps:
+        # the step kernels from call step a_step (state as the launches left it)
+        plan = [(a, n) for a, n in ring.plan if a >= a_step]
+        ring.fill(*plan[0])
+        pre()
+        iob, pb, common, tail, done = sub(a_step, n_steps - a_step)
+        lcargs = ring.args()
+        for i, (a, n) in enumerate(plan):
+            if i:
+                ring.fill(a, n)
+            # (the stream is looked up inside: a capture runs on its own)
+            _replay_steps(net, g, (common, tail, lcargs), lambda: _lib.call(
+                'wn_fastgen_step_lc', *common, *tail, *lcargs, _lib.stream()),
+                n)
+        _lib.call('wn_fastgen_finish', net.Q, _lib.ptr(g['cursors']),
+                  _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(pb),
+                  _lib.ptr(g['logits']), st)
+        done()
+    g['steps'] = steps0
+
+
 def _run_wide(net, g, samples_io, args):
     # more than 32 channels, or more S / Q / L than the tuned kernels hold
     # in LDS: one workgroup, or the cooperative launch (skip sum and post-
@@ -305,7 +483,7 @@ def _run_wide(net, g, samples_io, args):
     _lib.call('wn_fastgen_run_wide', *args, None, _lib.stream())
 
 
-def _run_persistent(net, g, common, tail, io, iob, n_steps):
+def _run_persistent(net, g, common, tail, io, iob, n_steps, lc=None):
     # ONE launch for the run; its workgroups must all be resident, which
     # the library checks (WN_ERR_UNSUPPORTED).  False: the step kernels, which
     # always complete, run it (after an expired wait, from restored state)
@@ -314,14 +492,19 @@ def _run_persistent(net, g, common, tail, io, iob, n_steps):
     ll = _buf(net, g, 'fgp_ll', int(lib.wn_fastgen_persist_ll_words(
         net.L, net.S, net.Q)), torch.int64)
     snap = [(t, t.clone()) for t in (g['state'], g['cursors'], g['pre'])]
-    code = lib.wn_fastgen_persist(*common, *tail, _lib.ptr(sync),
-                                  _lib.ptr(ll), int(n_steps), _lib.stream())
+    if lc is None:
+        code = lib.wn_fastgen_persist(*common, *tail, _lib.ptr(sync),
+                                      _lib.ptr(ll), int(n_steps), _lib.stream())
+    else:
+        code = lib.wn_fastgen_persist_lc(*common, *tail, _lib.ptr(sync),
+                                         _lib.ptr(ll), int(n_steps), *lc,
+                                         _lib.stream())
     if code == 0:
         n_io = int(n_steps) + 1
         return not _expired(net, 'persist', sync,
                             snap + [(iob[:n_io], io[0, :n_io])])
     if code != -2:                 # WN_ERR_UNSUPPORTED: not resident / shape
-        _lib.check(code, 'wn_fastgen_persist')
+        _lib.check(code, 'wn_fastgen_persist' + ('' if lc is None else '_lc'))
     return False
 
 
@@ -334,7 +517,7 @@ def _run_steps(net, g, common, tail, iob, pb, n_steps):
               _lib.ptr(g['logits']), _lib.stream())
 
 
-def predict_proba_incremental(net, waveform, global_condition, push):
+def predict_proba_incremental(net, waveform, global_condition, push, lc=None):
     if net.filter_width > 2:
         raise NotImplementedError("Incremental generation does not "
                                   "support filter_width > 2.")
@@ -349,16 +532,17 @@ def predict_proba_incremental(net, waveform, global_condition, push):
     else:
         g['io'][0] = int(np.asarray(w).reshape(-1)[-1])
     run(net, 1.0, 0, global_condition, g['io'], 1, 1, g['proba'], 1,
-        push=push)
+        push=push, lc=lc)
     return g['proba'].clone()
 
 
 def generate(net, num_samples, seed_samples, temperature, global_condition,
-             seed, return_proba_every):
+             seed, return_proba_every, lc=None):
     net._check_supported()
     if net.filter_width > 2 or net.scalar_input:
         raise NotImplementedError('fast generation needs filter_width 2 '
                                   'and one-hot input (model.py:597-603)')
+    lc = _lc_device(net, lc)
     if seed_samples is None:
         seed_samples = [net.Q // 2]
     s = torch.as_tensor(np.asarray(seed_samples),
@@ -366,42 +550,46 @@ def generate(net, num_samples, seed_samples, temperature, global_condition,
     n_given, n = int(s.numel()), int(num_samples)
     io = torch.zeros(n_given + n, dtype=torch.int32, device=net.device)
     io[:n_given] = s.to(net.device)
-    net.reset_generator()
+    # (net.reset_generator(), which an LC model refuses)
+    generator(net, None)
+    reset(net)
     pe = int(return_proba_every)
     proba = _seeded(net, io, n_given, n, pe,
-                    lambda: prime(net, io[:n_given - 1], global_condition),
+                    lambda: prime(net, io[:n_given - 1], global_condition,
+                                  None if lc is None else lc[:n_given - 1]),
                     functools.partial(run, net, temperature, seed,
                                       global_condition,
-                                      multi_cu=net.fastgen_multi_cu))
+                                      multi_cu=net.fastgen_multi_cu), lc)
     return (io, proba) if pe > 0 else io
 
 
-def prime(net, codes, global_condition):
+def prime(net, codes, global_condition, lc=None):
     if net.filter_width > 2 or net.scalar_input:
         raise NotImplementedError('fast generation needs filter_width 2 '
                                   'and one-hot input (model.py:597-603)')
     net._check_supported()
     g = generator(net, global_condition)
     reset(net)
+    lc = _lc_device(net, lc)
     w = torch.as_tensor(codes).to(device=net.device,
                                   dtype=torch.int32).reshape(-1)
     n0 = int(w.numel())
     if n0 == 0:
         return
-    _prime(net, g, n0, [(w, global_condition, [0])], 1)
+    _prime(net, g, n0, [(w, global_condition, [0], lc)], 1)
     g['cursors'][0] = n0
     g['cursors'][1:2].copy_(w[-1:])
     g['steps'] = n0
 
 
 def continue_generation(net, num_samples, last_sample, temperature,
-                        global_condition, seed):
+                        global_condition, seed, lc=None):
     net._check_supported()
     n = int(num_samples)
     io = torch.zeros(n + 1, dtype=torch.int32, device=net.device)
     io[0] = int(last_sample)
     run(net, temperature, seed, global_condition, io, 1, n, None, 1,
-        multi_cu=net.fastgen_multi_cu)
+        multi_cu=net.fastgen_multi_cu, lc=lc)
     return io[1:]
 
 
@@ -512,28 +700,40 @@ def batch_reset(net, g):
 
 
 def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
-                  proba_every, gc):
+                  proba_every, gc, lc=None):
     """Everything n_steps batched steps need before the first: the args of
-    wn_fastgen_batch_step (no stream) and the buffers batch_complete reads."""
+    wn_fastgen_batch_step (no stream) and the buffers batch_complete reads.
+    lc (LC models): rows [B or 1, n_steps, Lc]; the result then holds the
+    call's ring (`ring`), its first chunk filled, and the pre-activations
+    are those of wn_fastgen_batch_pre_lc."""
     B = g['B']
     w, bias, bstride = _weights(net, g, gc, B)
+    ring = None
+    if lc is not None:
+        ring = _LcRing(net, g, _lc_rows_padded(net, lc, n_steps), B, bias,
+                       bstride, n_steps, proba_every)
+        ring.fill(*ring.plan[0])
     g['seeds'].copy_(torch.from_numpy(seeds))
     iob, pb = _stage(net, g, io, n_given, n_steps, temperature, proba,
                      proba_every)
     # past-tap pre-activations of the first step (every step then leaves
     # the next step's behind)
-    _lib.call('wn_fastgen_batch_pre',
-              _lib.ptr(net._layer_block(net.params, 0)), net.layer_stride,
-              bias, bstride, _lib.ptr(g['dil']), net.L, B,
-              _lib.ptr(g['state']), _lib.ptr(g['cursors']),
-              _lib.ptr(g['pre']), _lib.stream())
+    pre_args = (_lib.ptr(net._layer_block(net.params, 0)), net.layer_stride,
+                bias, bstride, _lib.ptr(g['dil']), net.L, B,
+                _lib.ptr(g['state']), _lib.ptr(g['cursors']),
+                _lib.ptr(g['pre']))
+    if ring is None:
+        _lib.call('wn_fastgen_batch_pre', *pre_args, _lib.stream())
+    else:
+        _lib.call('wn_fastgen_batch_pre_lc', *pre_args, *ring.args(),
+                  _lib.stream())
     args = w + (bias, bstride, _lib.ptr(g['dil']), net.L, net.S, net.Q, B,
                 _lib.ptr(g['state']), _lib.ptr(g['cursors']),
                 _lib.ptr(g['prev']), _lib.ptr(iob), _lib.ptr(g['ctl']),
                 _lib.ptr(g['seeds']), _lib.ptr(pb), 1 if net.use_biases else 0,
                 _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
                 _lib.ptr(g['h2']), _lib.ptr(g['logits']))
-    return dict(args=args, iob=iob, pb=pb)
+    return dict(args=args, iob=iob, pb=pb, ring=ring)
 
 
 def batch_complete(net, g, prep, io, proba, n_steps):
@@ -550,23 +750,39 @@ def batch_complete(net, g, prep, io, proba, n_steps):
 
 
 def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
-               proba_every):
+               proba_every, lc=None):
     # n_steps lock-step steps of all B streams on io [B, n_steps + 1]: five
-    # kernels per step, captured into a hipGraph once and replayed
+    # kernels per step, captured into a hipGraph once and replayed (LC: in
+    # chunks, the ring filled before each)
     prep = batch_prepare(net, g, io, n_given, n_steps, temperature, seeds,
-                         proba, proba_every, gc)
-    args = prep['args']
-    _replay_steps(net, g, args, lambda: _lib.call(
-        'wn_fastgen_batch_step', *args, _lib.stream()), n_steps)
+                         proba, proba_every, gc, lc)
+    args, ring = prep['args'], prep['ring']
+    if ring is None:
+        _replay_steps(net, g, args, lambda: _lib.call(
+            'wn_fastgen_batch_step', *args, _lib.stream()), n_steps)
+    else:
+        lcargs = ring.args()
+        for i, (a, n) in enumerate(ring.plan):
+            if i:
+                ring.fill(a, n)
+            _replay_steps(net, g, (args, lcargs), lambda: _lib.call(
+                'wn_fastgen_batch_step_lc', *args, *lcargs, _lib.stream()), n)
     batch_complete(net, g, prep, io, proba, n_steps)
 
 
 def generate_batch(net, num_samples, seeds, seed_samples, temperature,
-                   global_condition, return_proba_every):
-    sd, codes, gc, n = _batch_args(
-        net, seeds, functools.partial(_batch_codes, net, seed_samples),
-        global_condition, temperature, num_samples)
+                   global_condition, return_proba_every, lc=None):
+    def per_stream(B):
+        codes = _batch_codes(net, seed_samples, B)
+        if not net.Lc and lc is None:
+            return codes, None
+        return codes, net._fastgen_lc(lc, 'generate_batch', codes.shape[1] +
+                                      int(num_samples) - 1, B)
+    sd, (codes, lc), gc, n = _batch_args(net, seeds, per_stream,
+                                         global_condition, temperature,
+                                         num_samples)
     B, n_given = codes.shape
+    lc = _lc_device(net, lc)
     out = torch.zeros((B, n_given + n), dtype=torch.int32, device=net.device)
     out[:, :n_given] = torch.from_numpy(codes).to(net.device)
     g = batch_generator(net, B)
@@ -577,36 +793,48 @@ def generate_batch(net, num_samples, seeds, seed_samples, temperature,
         # bitwise those it gets alone, whatever B
         batch_reset(net, g)
         n0, groups = n_given - 1, {}
+        # (LC: the seed's rows are part of the key)
+        lch = None if lc is None else lc[:, :n0].cpu().numpy()
         for b in range(B):
-            key = (codes[b, :n0].tobytes(), None if gc is None else int(gc[b]))
+            key = (codes[b, :n0].tobytes(), None if gc is None else int(gc[b]),
+                   None if lch is None else lch[b % len(lch)].tobytes())
             groups.setdefault(key, []).append(b)
         _prime(net, g, n0, [
             (torch.from_numpy(np.ascontiguousarray(codes[s[0], :n0])),
-             None if gc is None else gc[s[0]:s[0] + 1], s)
+             None if gc is None else gc[s[0]:s[0] + 1], s,
+             None if lc is None else lc[s[0] % lc.shape[0], :n0])
             for s in groups.values()], g['Bp'])
         g['cursors'][0] = n0
         g['prev'][:B].copy_(torch.from_numpy(codes[:, n0 - 1].copy()))
         g['steps'] = n0
     pe = int(return_proba_every)
     proba = _seeded(net, out, n_given, n, pe, prime, functools.partial(
-        _batch_run, net, g, temperature, sd, gc))
+        _batch_run, net, g, temperature, sd, gc), lc)
     return (out, proba) if pe > 0 else out
 
 
 def continue_generation_batch(net, num_samples, last_samples, seeds,
                               temperature, global_condition,
-                              return_proba_every):
-    sd, last, gc, n = _batch_args(
-        net, seeds, functools.partial(_batch_last, last_samples),
-        global_condition, temperature, num_samples)
+                              return_proba_every, lc=None):
+    def per_stream(B):
+        last = _batch_last(last_samples, B)
+        if not net.Lc and lc is None:
+            return last, None
+        return last, net._fastgen_lc(lc, 'continue_generation_batch',
+                                     int(num_samples), B)
+    sd, (last, lc), gc, n = _batch_args(net, seeds, per_stream,
+                                        global_condition, temperature,
+                                        num_samples)
     B = len(sd)
     g = net._bgen
     if g is None or g['B'] != B:
         raise RuntimeError('no batched generation of %d streams to '
                            'continue: call generate_batch first' % B)
+    lc = _lc_device(net, lc)
     io = torch.zeros((B, n + 1), dtype=torch.int32, device=net.device)
     io[:, 0] = torch.from_numpy(last).to(net.device)
     pe = int(return_proba_every)
     proba = _seeded(net, io, 1, n, pe, None,
-                    functools.partial(_batch_run, net, g, temperature, sd, gc))
+                    functools.partial(_batch_run, net, g, temperature, sd, gc),
+                    lc)
     return (io[:, 1:], proba) if pe > 0 else io[:, 1:]

@@ -263,6 +263,15 @@ class _Workspace(object):
         alloc('l2', (1,), fill=0.0)
 
 
+def _n_codes(codes):
+    """Number of codes of a seed (None: the one default code)."""
+    if codes is None:
+        return 1
+    if isinstance(codes, torch.Tensor):
+        return int(codes.numel())
+    return int(np.asarray(codes).size)
+
+
 class WaveNetModel(object):
     '''Implements the WaveNet network for generative audio (MI355X / HIP).
 
@@ -399,6 +408,10 @@ class WaveNetModel(object):
         # seeds longer than this are primed from ONE batch forward pass
         # instead of one incremental step per seed sample
         self.fastgen_prime_forward_min = 64
+        # LC models: steps per chunk of a fast-generation call (the
+        # conditioned-bias ring holds chunk + 1 rows); None: as many as
+        # fastgen.LC_RING_BYTES holds, a multiple of fastgen_graph_steps
+        self.fastgen_lc_chunk = None
 
         _lib.load()
         if device is None:
@@ -1606,59 +1619,157 @@ class WaveNetModel(object):
     def _no_lc_fastgen(self, what):
         if self.Lc:
             raise NotImplementedError(
-                '%s: fast generation does not support local conditioning yet; '
-                'generate with predict_proba(..., local_condition=...) '
-                '(generate.py --fast_generation false)' % what)
+                '%s: an LC model generates fast with local_condition=... '
+                '(one row per input position the call steps through), or '
+                'naively with predict_proba(..., local_condition=...) '
+                '(generate.py --fast_generation false)%s'
+                % (what, '' if what != 'reset_generator' else
+                   "; reset an LC model's generator with prime_generator([], "
+                   'local_condition=np.zeros((0, Lc)))'))
+
+    def _lc_forward_ok(self, n0):
+        """The forward pass over n0 seed codes (forward priming) carries the
+        LC rows: it is the persistent stack launch wn_stack_fwd_lc, as in
+        predict_proba.  Otherwise the seed is stepped through."""
+        return bool(self.stack_fwd and self.stack_bwd and
+                    self._stack_ok(n0))
+
+    def _fastgen_lc(self, local_condition, what, T, B=None):
+        """The fast entry points' LC rows, checked before any device work:
+        None without LC; else a float tensor where the caller had them,
+        [T, Lc] (B None) or [B or 1, T, Lc] (B streams: one set per stream,
+        or one shared).  fastgen moves them to the device once per call."""
+        if not self.Lc:
+            if local_condition is not None:
+                raise ValueError('%s: this model was built without local '
+                                 'conditioning (local_condition_channels=None)'
+                                 % what)
+            return None
+        if local_condition is None:
+            self._no_lc_fastgen(what)
+        if self.S > 512 or self.Q > 512 or self.L > 64:
+            raise NotImplementedError(
+                '%s: fast generation with local conditioning supports at most '
+                '512 skip / quantization channels and 64 layers (this model: '
+                'S = %d, Q = %d, L = %d); use predict_proba'
+                % (what, self.S, self.Q, self.L))
+        lc = local_condition
+        if not isinstance(lc, torch.Tensor):
+            lc = np.asarray(lc)
+            if lc.dtype == object:
+                raise ValueError('%s: local_condition must be a float array'
+                                 % what)
+            lc = torch.from_numpy(lc)
+        if not lc.is_floating_point():
+            raise ValueError('%s: local_condition must be floating point'
+                             % what)
+        shape, Lc = tuple(lc.shape), self.Lc
+        if B is None:
+            if shape != (T, Lc):
+                raise ValueError('%s: local_condition must have shape [%d, %d] '
+                                 '(one row per input position), got %s'
+                                 % (what, T, Lc, shape))
+        else:
+            if shape == (T, Lc):
+                lc = lc.unsqueeze(0)
+            elif shape != (B, T, Lc):
+                raise ValueError('%s: local_condition must have shape '
+                                 '[%d, %d, %d] or [%d, %d] (shared by all '
+                                 'streams), got %s'
+                                 % (what, B, T, Lc, T, Lc, shape))
+        return lc
 
     def predict_proba_incremental(self, waveform, global_condition=None,
-                                  name='wavenet', push=True):
+                                  name='wavenet', push=True, *,
+                                  local_condition=None):
         '''Computes the probability distribution of the next sample
         incrementally, based on a single sample and all previously passed
         samples (model.py:592-626).  Eager counterpart of running the
         reference's proba op together with `net.push_ops` (push=True) or
-        alone (push=False); `net.reset_generator()` is `net.init_ops`.'''
-        self._no_lc_fastgen('predict_proba_incremental')
+        alone (push=False); `net.reset_generator()` is `net.init_ops`.
+
+        local_condition (LC models only, required there): float [Lc] or
+        [1, Lc], the row beside the sample pushed or peeked.  An LC model's
+        generator is reset with prime_generator([], local_condition=
+        np.zeros((0, Lc))).'''
+        lc = local_condition
+        if self.Lc and lc is not None and np.ndim(lc) == 1:
+            lc = lc.reshape(1, -1) if isinstance(lc, torch.Tensor) \
+                else np.asarray(lc).reshape(1, -1)
+        lc = self._fastgen_lc(lc, 'predict_proba_incremental', 1)
         return fastgen.predict_proba_incremental(self, waveform,
-                                                 global_condition, push)
+                                                 global_condition, push, lc)
 
     def reset_generator(self):
-        """net.init_ops: refill every queue with zeros (model.py:457-479)."""
+        """net.init_ops: refill every queue with zeros (model.py:457-479).
+        An LC model refuses it: its generator is reset with
+        prime_generator([], local_condition=np.zeros((0, Lc)))."""
         self._no_lc_fastgen('reset_generator')
         fastgen.generator(self, None)
         fastgen.reset(self)
 
     def generate(self, num_samples, seed_samples=None, temperature=1.0,
-                 global_condition=None, seed=0, return_proba_every=0):
+                 global_condition=None, seed=0, return_proba_every=0, *,
+                 local_condition=None):
         """The whole generate.py:195-241 loop on the device: prime with
         `seed_samples` (int codes; default one random-free seed 128 as in
         test_model.py:63), then draw `num_samples` samples with temperature.
         Returns int32 codes [len(seed) + num_samples] (and the probabilities
-        of every `return_proba_every`-th step when requested)."""
-        self._no_lc_fastgen('generate')
-        return fastgen.generate(self, num_samples, seed_samples, temperature,
-                                global_condition, seed, return_proba_every)
+        of every `return_proba_every`-th step when requested).
 
-    def prime_generator(self, codes, global_condition=None):
+        local_condition (LC models only, required there): float
+        [len(seed) + num_samples - 1, Lc], row i beside code i of the result
+        (it conditions the prediction of code i + 1).  The generator is
+        reset internally (reset_generator itself refuses LC models)."""
+        lc = None
+        if self.Lc or local_condition is not None:
+            lc = self._fastgen_lc(local_condition, 'generate',
+                                  _n_codes(seed_samples) + int(num_samples) - 1)
+        return fastgen.generate(self, num_samples, seed_samples, temperature,
+                                global_condition, seed, return_proba_every,
+                                lc)
+
+    def prime_generator(self, codes, global_condition=None, *,
+                        local_condition=None):
         """Set the incremental-generation queues to the state they have after
         `codes` were pushed one by one from a fresh `reset_generator()`, using
         ONE batch forward pass: layer l's queue (capacity d_l) holds the last
         d_l inputs x_l[t] of that layer (model.py:473-484), which are rows of
-        the forward pass's per-layer activation planes."""
-        self._no_lc_fastgen('prime_generator')
-        fastgen.prime(self, codes, global_condition)
+        the forward pass's per-layer activation planes.
+
+        local_condition (LC models only, required there): float
+        [len(codes), Lc], row i beside codes[i]; with no codes and
+        np.zeros((0, Lc)) this resets an LC model's generator."""
+        lc = self._fastgen_lc(local_condition, 'prime_generator',
+                              _n_codes(codes))
+        if lc is not None and lc.shape[0] > 0 and \
+                not self._lc_forward_ok(lc.shape[0]):
+            raise NotImplementedError(
+                'prime_generator: the forward pass that primes an LC model '
+                'is the persistent stack launch (wn_stack_fwd_lc): '
+                + self.LC_SUPPORTED + ', fewer than 2^24 codes')
+        fastgen.prime(self, codes, global_condition, lc)
 
     def continue_generation(self, num_samples, last_sample, temperature=1.0,
-                            global_condition=None, seed=0):
+                            global_condition=None, seed=0, *,
+                            local_condition=None):
         """Draw `num_samples` more samples after `generate` (the queues stay
         on the device; `last_sample` is the last code drawn so far, which has
-        not been pushed yet).  Returns the new int32 codes."""
-        self._no_lc_fastgen('continue_generation')
+        not been pushed yet).  Returns the new int32 codes.
+
+        local_condition (LC models only, required there): float
+        [num_samples, Lc]; row 0 sits beside `last_sample`, row k beside new
+        code k - 1.  generate(a) then continue_generation(b) on consecutive
+        rows is the process of one generate(a + b)."""
+        lc = self._fastgen_lc(local_condition, 'continue_generation',
+                              int(num_samples))
         return fastgen.continue_generation(self, num_samples, last_sample,
-                                           temperature, global_condition, seed)
+                                           temperature, global_condition, seed,
+                                           lc)
 
     def generate_batch(self, num_samples, seeds, seed_samples=None,
                        temperature=1.0, global_condition=None,
-                       return_proba_every=0):
+                       return_proba_every=0, *, local_condition=None):
         """`generate` for B = len(seeds) independent streams stepped in lock
         step (1 <= B <= 256).  Stream b draws with seeds[b] under generate()'s
         counter rule, so it is the same random process as
@@ -1666,20 +1777,32 @@ class WaveNetModel(object):
         streams.  seed_samples: None (Q // 2 for every stream), one sequence
         shared by all streams, or [B, n]; global_condition: None, one id, or
         B ids.  Returns int32 [B, n + num_samples] (and float32
-        [B, ceil(steps / k), Q] probabilities with return_proba_every = k)."""
-        self._no_lc_fastgen('generate_batch')
+        [B, ceil(steps / k), Q] probabilities with return_proba_every = k).
+
+        local_condition (LC models only, required there): float
+        [B, n + num_samples - 1, Lc] (n seed codes per stream), or
+        [n + num_samples - 1, Lc] shared by all streams; rows as generate's."""
+        # (the rows are checked in _batch_args's order, beside the seed codes)
+        if self.Lc and local_condition is None:
+            self._no_lc_fastgen('generate_batch')
         return fastgen.generate_batch(self, num_samples, seeds, seed_samples,
                                       temperature, global_condition,
-                                      return_proba_every)
+                                      return_proba_every, local_condition)
 
     def continue_generation_batch(self, num_samples, last_samples, seeds,
                                   temperature=1.0, global_condition=None,
-                                  return_proba_every=0):
+                                  return_proba_every=0, *,
+                                  local_condition=None):
         """Draw `num_samples` more samples for every stream of the last
         generate_batch call (the queues stay on the device; last_samples[b]
         is stream b's last code so far, not yet pushed).  Returns int32
-        [B, num_samples] (and the probabilities, as generate_batch)."""
-        self._no_lc_fastgen('continue_generation_batch')
+        [B, num_samples] (and the probabilities, as generate_batch).
+
+        local_condition (LC models only, required there): float
+        [B, num_samples, Lc] or [num_samples, Lc], rows as
+        continue_generation's."""
+        if self.Lc and local_condition is None:
+            self._no_lc_fastgen('continue_generation_batch')
         return fastgen.continue_generation_batch(
             self, num_samples, last_samples, seeds, temperature,
-            global_condition, return_proba_every)
+            global_condition, return_proba_every, local_condition)

@@ -11,6 +11,17 @@ kernels (an extra StackLc argument); the fingerprints of every other kernel
 must not change when they do.
 
     python tools/stack_disasm.py [build/wn_stack.o] [--dump DIR]
+
+--match REGEX fingerprints the kernels whose names match REGEX instead (any
+object; --exclude REGEX drops names), e.g. the fast-generation kernels
+without their local-conditioning variants (profiles/fastgen_disasm_lc.txt):
+
+    python tools/stack_disasm.py build/wn_fastgen.o --match 'kernel' \
+        --exclude '_lc_' --strip-padding
+
+--strip-padding drops the run of s_nop after a kernel's last instruction:
+the padding up to the next function in the code object, which depends on
+what follows the kernel, not on its code.
 """
 import argparse
 import hashlib
@@ -40,15 +51,22 @@ def disassemble(obj):
              '-C', co], text=True)
 
 
-def kernels(text):
-    """{name: [normalised instruction lines]} for every stack kernel."""
+def kernels(text, match=None, exclude=None):
+    """{name: [normalised instruction lines]} for every stack kernel (or
+    every kernel whose name matches `match` and not `exclude`)."""
     out, cur = {}, None
     for line in text.splitlines():
         m = re.match(r'^[0-9a-f]+ <(.*)>:$', line)
         if m:
             name = m.group(1)
             cur = None
-            if 'stack_' in name and '_kernel' in name:
+            if match is None:
+                want = 'stack_' in name and '_kernel' in name
+            else:
+                want = re.search(match, name) is not None
+            if exclude is not None and re.search(exclude, name):
+                want = False
+            if want:
                 cur = out.setdefault(name, [])
             continue
         if cur is None:
@@ -64,8 +82,19 @@ def main(argv=None):
     ap.add_argument('obj', nargs='?', default=DEFAULT_OBJ)
     ap.add_argument('--dump', default=None,
                     help='also write each kernel\'s normalised text here')
+    ap.add_argument('--match', default=None,
+                    help='regex of the kernel names to fingerprint '
+                         '(default: the stack kernels)')
+    ap.add_argument('--exclude', default=None,
+                    help='regex of kernel names to leave out')
+    ap.add_argument('--strip-padding', action='store_true',
+                    help='drop the s_nop padding after each kernel')
     args = ap.parse_args(argv)
-    ks = kernels(disassemble(args.obj))
+    ks = kernels(disassemble(args.obj), args.match, args.exclude)
+    if args.strip_padding:
+        for body in ks.values():
+            while body and body[-1] in ('s_nop 0', '...'):
+                body.pop()
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
     for name in sorted(ks):
