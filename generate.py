@@ -18,6 +18,10 @@ the prediction of sample t + 1); the seed's rows are zeros.  On the naive path
 `continue_generation` (in --save_every chunks) take the rows of the positions
 they step through, and with --clips N `generate_batch` runs the N clips on
 rows shared by all of them.  Without either flag --lc_path is refused.
+With --lc_upsample_scales (a model trained with train.py
+--lc_upsample_scales) the frames are upsampled once by the checkpoint's
+learned network (`upsample_local_condition`) instead of by repetition; the
+flows above then run on those rows.
 """
 from __future__ import division
 from __future__ import print_function
@@ -89,6 +93,9 @@ def get_arguments(argv=None):
                    '(default false: --lc_path needs --fast_generation false)')
     p.add_argument('--lc_hop', type=int, default=1,
                    help='audio samples per feature frame of --lc_path')
+    p.add_argument('--lc_upsample_scales', type=str, default=None,
+                   help='with --lc_path: the scales of the model\'s learned '
+                   'upsampler (train.py --lc_upsample_scales), e.g. 4,5,10')
     p.add_argument('--gc_ids', type=str, default=None,
                    help='comma-separated global condition ids, one clip each '
                    '(sets --clips to their number)')
@@ -138,9 +145,26 @@ def create_seed(filename, sample_rate, quantization_channels,
     return quantized[:min(int(quantized.numel()), window_size)]
 
 
+def upsampler_mismatch(net, sd):
+    """A message when the checkpoint's upsampler variables (state dict `sd`)
+    and the model's (--lc_upsample_scales) differ, else None."""
+    mine = {n: tuple(v.shape) for n, v in net.named_variables()
+            if '/lc_upsample/' in n}
+    theirs = {n: tuple(np.shape(v)) for n, v in sd.items()
+              if '/lc_upsample/' in n}
+    if mine == theirs:
+        return None
+    def desc(d):
+        filt = [d[n][0] for n in sorted(d) if n.endswith('/filter')]
+        return ','.join(str(s) for s in filt) if filt else 'none'
+    return ('the checkpoint\'s learned upsampler (wavenet/lc_upsample/..., '
+            'scales %s) does not match --lc_upsample_scales (scales %s)'
+            % (desc(theirs), desc(mine)))
+
+
 def main(argv=None):
     args = get_arguments(argv)
-    lc_rows = None
+    lc_rows, lc_scales = None, None
     if args.lc_path is not None:
         if args.fast_generation and not args.lc_fast_generation:
             print('Local conditioning (--lc_path) needs the naive path: '
@@ -154,8 +178,24 @@ def main(argv=None):
             print('--lc_path must hold [frames, channels] features and '
                   '--lc_hop must be positive')
             return 1
-        lc_rows = upsample_lc(feats, args.lc_hop,
-                              feats.shape[0] * args.lc_hop)
+        if args.lc_upsample_scales is not None:
+            try:
+                lc_scales = tuple(int(x) for x in
+                                  args.lc_upsample_scales.split(','))
+            except ValueError:
+                print('--lc_upsample_scales must be comma-separated ints')
+                return 1
+            hop = int(np.prod(lc_scales))
+            if args.lc_hop not in (1, hop):
+                print('--lc_hop %d disagrees with --lc_upsample_scales %s '
+                      '(hop %d)' % (args.lc_hop, args.lc_upsample_scales, hop))
+                return 1
+            # (the rows come from the model's upsampler once it is loaded)
+            lc_rows = np.zeros((feats.shape[0] * hop, feats.shape[1]),
+                               np.float32)
+        else:
+            lc_rows = upsample_lc(feats, args.lc_hop,
+                                  feats.shape[0] * args.lc_hop)
         args.samples = lc_rows.shape[0]
     from wavenet import WaveNetModel, mu_law_decode
     started = "{0:%Y-%m-%dT%H-%M-%S}".format(datetime.now())
@@ -176,14 +216,24 @@ def main(argv=None):
         global_condition_channels=args.gc_channels,
         global_condition_cardinality=args.gc_cardinality,
         residual_postproc=wavenet_params.get("residual_postproc", False),
-        local_condition_channels=None if lc_rows is None else lc_rows.shape[1])
+        local_condition_channels=None if lc_rows is None else lc_rows.shape[1],
+        local_condition_upsample_scales=lc_scales)
     print('Restoring model from {}'.format(args.checkpoint))
     if tf_checkpoint.checkpoint_format(args.checkpoint):
         # a checkpoint written by the reference itself (tf.train.Saver)
         tf_checkpoint.load_into(net, args.checkpoint)
     else:
-        net.load_state_dict(torch.load(args.checkpoint,
-                                       map_location='cpu')['variables'])
+        sd = torch.load(args.checkpoint, map_location='cpu')['variables']
+        if lc_rows is not None:
+            why = upsampler_mismatch(net, sd)
+            if why:
+                print(why)
+                return 1
+        net.load_state_dict(sd)
+    if lc_scales is not None:
+        # the checkpoint's learned upsampler, once for the whole run
+        lc_rows = net.upsample_local_condition(
+            feats.astype(np.float32), lc_rows.shape[0]).cpu().numpy()
     Q = wavenet_params['quantization_channels']
     rate = wavenet_params['sample_rate']
     gc = None if args.gc_id is None else [args.gc_id]

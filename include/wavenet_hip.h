@@ -725,6 +725,34 @@ int wn_fastgen_batch_step_lc(const float* params_causal, const float* layer0,
                              const float* lc_ring, int lc_R, int lc_stride,
                              void* stream);
 
+/* ---- learned upsampling of frame-rate local-conditioning features
+ * (csrc/wn_misc.hip).  scales: host array of m (1..8) ints >= 2, hop = their
+ * product <= 4096.  `up`: the model's lc_up segment, the filters W_i[s_i][3] of
+ * all layers back to back, then (use_bias) the m biases;
+ * wn_lc_upsample_floats(scales, m, use_bias) floats (0 for bad scales).
+ * Layer i maps an input row u to output slot j of s_i:
+ *   out[c] = b_i + W_i[j][0] u[c-1] + W_i[j][1] u[c] + W_i[j][2] u[c+1]
+ * (u[-1] = u[Lc] = 0).  Row r = b * T + t gets frame p / hop of clip b,
+ * p = off[b] + t, through the slot digits of p % hop (most significant
+ * first).  frames [B][F][Lc]; off int32 [B] on the device; 1 <= Lc <= 512.
+ * fwd writes rows[r * ld_rows + 0 .. ld_rows - 1], zeros from column Lc on.
+ * bwd: every workgroup owns a fixed range of rows and writes the
+ * (layer, slot, tap) and bias partials of d rows [N][ld_drows] into its slab
+ * (slab_stride >= wn_lc_upsample_floats floats, same layout as `up`); sum
+ * them with wn_reduce_slabs.  num_slabs = wn_lc_upsample_bwd_slabs(B * T,
+ * floats).  No atomics: the result depends on B * T and the inputs only. */
+int wn_lc_upsample_floats(const int* scales, int m, int use_bias);
+int wn_lc_upsample_fwd(const float* frames, int F, const int32_t* off,
+                       const float* up, const int* scales, int m, int Lc,
+                       int use_bias, float* rows, int ld_rows, int B, int T,
+                       void* stream);
+int wn_lc_upsample_bwd_slabs(long rows, int nacc);
+int wn_lc_upsample_bwd(const float* frames, int F, const int32_t* off,
+                       const float* up, const int* scales, int m, int Lc,
+                       int use_bias, const float* drows, int ld_drows, int B,
+                       int T, float* slabs, int num_slabs, long slab_stride,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1071,3 +1071,291 @@ int wn_sum_rows(const float* in, int rows, int n, float* out, void* stream) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Learned upsampling of frame-rate local-conditioning features (WaveNet paper
+// 2.5).  Layer i (scale s_i) is a transposed convolution over time with
+// kernel = stride = s_i and, over the feature axis, a 3-tap kernel with zero
+// padding and one scalar bias:
+//   out[c] = b_i + W_i[j][0] u[c-1] + W_i[j][1] u[c] + W_i[j][2] u[c+1]
+// for output slot j of an input row u.  Timeline position p = off[b] + t takes
+// frame p / hop and the slot digits of p % hop, most significant first.  A
+// row is computed from its frame, its slot and the weights alone, in one
+// fixed order (explicit FMAs): its bits do not depend on the batch, the clip
+// length, the offset or the call.
+//
+// Segment layout (`up`): filters W_i[s_i][3] of all layers back to back, then
+// (use_bias) the m biases.  Per launch: frames [B][F][Lc], off[b] int32.
+// ---------------------------------------------------------------------------
+#define LCUP_MAX_LAYERS 8
+#define LCUP_MAX_LC 512
+#define LCUP_CPL (LCUP_MAX_LC / 64)          // channels per lane
+
+struct LcUpGeom {
+  int m, hop, Lc, use_bias;
+  int s[LCUP_MAX_LAYERS];    // scales
+  int suf[LCUP_MAX_LAYERS];  // s_{i+1} * ... * s_m (slot digit divisor)
+  int fo[LCUP_MAX_LAYERS];   // filter offset of layer i in the segment
+  int bo;                    // offset of the biases
+};
+
+__device__ __forceinline__ int lcup_slot(const LcUpGeom& g, int i, int j) {
+  return (j / g.suf[i]) % g.s[i];
+}
+
+// one layer of one row: buf_in / buf_out hold Lc + 2 floats with a zero at
+// either end (index c + 1 is channel c)
+__device__ __forceinline__ void lcup_layer(const LcUpGeom& g,
+                                           const float* __restrict__ up, int i,
+                                           int j, const float* bin, float* bout,
+                                           int lane) {
+  const int slot = lcup_slot(g, i, j);
+  const float* w = up + g.fo[i] + 3 * slot;
+  const float w0 = w[0], w1 = w[1], w2 = w[2];
+  const float b = g.use_bias ? up[g.bo + i] : 0.f;
+#pragma unroll
+  for (int k = 0; k < LCUP_CPL; ++k) {
+    const int c = lane + 64 * k;
+    if (c < g.Lc) {
+      float a = b;
+      a = fmaf(w0, bin[c], a);
+      a = fmaf(w1, bin[c + 1], a);
+      a = fmaf(w2, bin[c + 2], a);
+      bout[c + 1] = a;
+    }
+  }
+}
+
+// the frame row of row r into buf (zero ends); returns the slot index p % hop
+__device__ __forceinline__ int lcup_load(const LcUpGeom& g,
+                                         const float* __restrict__ frames,
+                                         int F, const int32_t* __restrict__ off,
+                                         int T, long r, float* buf, int lane) {
+  const int b = (int)(r / T), t = (int)(r - (long)b * T);
+  const long p = (long)off[b] + t;
+  long f = p / g.hop;
+  if (f > F - 1) f = F - 1;          // (the host checks coverage; never read past)
+  const float* src = frames + ((long)b * F + f) * g.Lc;
+#pragma unroll
+  for (int k = 0; k < LCUP_CPL; ++k) {
+    const int c = lane + 64 * k;
+    if (c < g.Lc) buf[c + 1] = src[c];
+  }
+  if (lane == 0) {
+    buf[0] = 0.f;
+    buf[g.Lc + 1] = 0.f;
+  }
+  return (int)(p % g.hop);
+}
+
+// forward: one wave per row, four rows per workgroup, ping-pong rows in LDS
+__global__ __launch_bounds__(256) void lc_upsample_fwd_kernel(
+    LcUpGeom g, const float* __restrict__ frames, int F,
+    const int32_t* __restrict__ off, const float* __restrict__ up,
+    float* __restrict__ out, int ldo, int T, long N) {
+  __shared__ float lds[4][2][LCUP_MAX_LC + 2];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + wv;
+  const bool live = r < N;
+  float* b0 = lds[wv][0];
+  float* b1 = lds[wv][1];
+  if (lane == 0) b1[0] = b1[g.Lc + 1] = 0.f;
+  const int j = live ? lcup_load(g, frames, F, off, T, r, b0, lane) : 0;
+  __syncthreads();
+  for (int i = 0; i < g.m; ++i) {
+    if (live) lcup_layer(g, up, i, j, (i & 1) ? b1 : b0, (i & 1) ? b0 : b1, lane);
+    __syncthreads();
+  }
+  if (!live) return;
+  const float* res = (g.m & 1) ? b1 : b0;
+  float* dst = out + r * ldo;
+  for (int c = lane; c < ldo; c += 64) dst[c] = c < g.Lc ? res[c + 1] : 0.f;
+}
+
+__device__ __forceinline__ float lcup_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// backward: one wave per workgroup owning rows [w * rpw, (w + 1) * rpw).  Per
+// row: the layer chain again (every layer's input kept in LDS), then d row
+// back through the layers; the (layer, slot, tap) and bias partials add up in
+// LDS in row order and go to the workgroup's slab at the end.
+__global__ __launch_bounds__(64) void lc_upsample_bwd_kernel(
+    LcUpGeom g, const float* __restrict__ frames, int F,
+    const int32_t* __restrict__ off, const float* __restrict__ up,
+    const float* __restrict__ drows, int ldd, int T, long N, long rpw,
+    float* __restrict__ slabs, long slab_stride, int nacc) {
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x;
+  const int W = g.Lc + 2;
+  float* U = lds;                              // [m + 1][W]
+  float* G0 = U + (g.m + 1) * W;               // [2][W]
+  float* acc = G0 + 2 * W;                     // [nacc]
+  for (int e = lane; e < nacc; e += 64) acc[e] = 0.f;
+  for (int e = lane; e < 2 * W; e += 64) G0[e] = 0.f;
+  for (int i = 1; i <= g.m; ++i)
+    if (lane == 0) U[i * W] = U[i * W + g.Lc + 1] = 0.f;
+  __syncthreads();
+  const long r0 = (long)blockIdx.x * rpw;
+  const long r1 = r0 + rpw < N ? r0 + rpw : N;
+  for (long r = r0; r < r1; ++r) {
+    const int j = lcup_load(g, frames, F, off, T, r, U, lane);
+    __syncthreads();
+    for (int i = 0; i < g.m; ++i) {
+      lcup_layer(g, up, i, j, U + i * W, U + (i + 1) * W, lane);
+      __syncthreads();
+    }
+    float* gc = G0;
+    float* gn = G0 + W;
+    const float* dr = drows + r * ldd;
+#pragma unroll
+    for (int k = 0; k < LCUP_CPL; ++k) {
+      const int c = lane + 64 * k;
+      if (c < g.Lc) gc[c + 1] = dr[c];
+    }
+    __syncthreads();
+    for (int i = g.m - 1; i >= 0; --i) {
+      const float* u = U + i * W;
+      float p0 = 0.f, p1 = 0.f, p2 = 0.f, pb = 0.f;
+#pragma unroll
+      for (int k = 0; k < LCUP_CPL; ++k) {
+        const int c = lane + 64 * k;
+        if (c < g.Lc) {
+          const float d = gc[c + 1];
+          p0 = fmaf(d, u[c], p0);
+          p1 = fmaf(d, u[c + 1], p1);
+          p2 = fmaf(d, u[c + 2], p2);
+          pb += d;
+        }
+      }
+      p0 = lcup_wave_sum(p0);
+      p1 = lcup_wave_sum(p1);
+      p2 = lcup_wave_sum(p2);
+      pb = lcup_wave_sum(pb);
+      const int slot = lcup_slot(g, i, j);
+      const int fw = g.fo[i] + 3 * slot;
+      if (lane == 0) {
+        acc[fw] += p0;
+        acc[fw + 1] += p1;
+        acc[fw + 2] += p2;
+        if (g.use_bias) acc[g.bo + i] += pb;
+      }
+      if (i > 0) {
+        // d u[c] = W0 d out[c + 1] + W1 d out[c] + W2 d out[c - 1]
+        const float* w = up + fw;
+        const float w0 = w[0], w1 = w[1], w2 = w[2];
+#pragma unroll
+        for (int k = 0; k < LCUP_CPL; ++k) {
+          const int c = lane + 64 * k;
+          if (c < g.Lc) {
+            float a = w0 * gc[c + 2];
+            a = fmaf(w1, gc[c + 1], a);
+            a = fmaf(w2, gc[c], a);
+            gn[c + 1] = a;
+          }
+        }
+        float* t = gc;
+        gc = gn;
+        gn = t;
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  float* dst = slabs + (long)blockIdx.x * slab_stride;
+  for (int e = lane; e < nacc; e += 64) dst[e] = acc[e];
+}
+
+static int lcup_geom(const int* scales, int m, int Lc, int use_bias,
+                     LcUpGeom* g, int* nacc) {
+  if (!scales) return WN_ERR_NULL;
+  if (m < 1 || m > LCUP_MAX_LAYERS || Lc < 1 || Lc > LCUP_MAX_LC)
+    return WN_ERR_BAD_SHAPE;
+  long hop = 1;
+  for (int i = 0; i < m; ++i) {
+    if (scales[i] < 2) return WN_ERR_BAD_SHAPE;
+    hop *= scales[i];
+    if (hop > 4096) return WN_ERR_BAD_SHAPE;
+  }
+  g->m = m;
+  g->hop = (int)hop;
+  g->Lc = Lc;
+  g->use_bias = use_bias ? 1 : 0;
+  int fo = 0, suf = 1;
+  for (int i = m - 1; i >= 0; --i) {
+    g->suf[i] = suf;
+    suf *= scales[i];
+  }
+  for (int i = 0; i < LCUP_MAX_LAYERS; ++i) {
+    g->s[i] = i < m ? scales[i] : 1;
+    if (i >= m) g->suf[i] = 1;
+    g->fo[i] = fo;
+    if (i < m) fo += 3 * scales[i];
+  }
+  g->bo = fo;
+  *nacc = fo + (use_bias ? m : 0);
+  return WN_OK;
+}
+
+extern "C" {
+
+int wn_lc_upsample_floats(const int* scales, int m, int use_bias) {
+  LcUpGeom g;
+  int n = 0;
+  if (lcup_geom(scales, m, 1, use_bias, &g, &n) != WN_OK) return 0;
+  return n;
+}
+
+int wn_lc_upsample_fwd(const float* frames, int F, const int32_t* off,
+                       const float* up, const int* scales, int m, int Lc,
+                       int use_bias, float* rows, int ld_rows, int B, int T,
+                       void* stream) {
+  if (!frames || !off || !up || !rows) return WN_ERR_NULL;
+  LcUpGeom g;
+  int nacc = 0;
+  const int rc = lcup_geom(scales, m, Lc, use_bias, &g, &nacc);
+  if (rc != WN_OK) return rc;
+  if (F < 1 || B < 1 || T < 1 || ld_rows < Lc) return WN_ERR_BAD_SHAPE;
+  const long N = (long)B * T;
+  hipLaunchKernelGGL(lc_upsample_fwd_kernel, dim3((unsigned)((N + 3) / 4)),
+                     dim3(256), 0, (hipStream_t)stream, g, frames, F, off, up,
+                     rows, ld_rows, T, N);
+  return wn_check_launch();
+}
+
+int wn_lc_upsample_bwd_slabs(long rows, int nacc) {
+  if (rows <= 0 || nacc <= 0) return 0;
+  long n = (rows + 31) / 32;                   // >= 32 rows per workgroup
+  long cap = (16L << 20) / nacc;               // <= 64 MB of slabs
+  if (cap < 64) cap = 64;
+  if (n > 4096) n = 4096;
+  if (n > cap) n = cap;
+  return (int)(n < 1 ? 1 : n);
+}
+
+int wn_lc_upsample_bwd(const float* frames, int F, const int32_t* off,
+                       const float* up, const int* scales, int m, int Lc,
+                       int use_bias, const float* drows, int ld_drows, int B,
+                       int T, float* slabs, int num_slabs, long slab_stride,
+                       void* stream) {
+  if (!frames || !off || !up || !drows || !slabs) return WN_ERR_NULL;
+  LcUpGeom g;
+  int nacc = 0;
+  const int rc = lcup_geom(scales, m, Lc, use_bias, &g, &nacc);
+  if (rc != WN_OK) return rc;
+  if (F < 1 || B < 1 || T < 1 || ld_drows < Lc || num_slabs < 1 ||
+      slab_stride < nacc)
+    return WN_ERR_BAD_SHAPE;
+  const long N = (long)B * T;
+  const long rpw = (N + num_slabs - 1) / num_slabs;
+  const size_t lds = sizeof(float) * ((size_t)(m + 3) * (Lc + 2) + nacc);
+  if (lds > 64 * 1024) return WN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(lc_upsample_bwd_kernel, dim3((unsigned)num_slabs),
+                     dim3(64), lds, (hipStream_t)stream, g, frames, F, off, up,
+                     drows, ld_drows, T, N, rpw, slabs, slab_stride, nacc);
+  return wn_check_launch();
+}
+
+}  // extern "C"

@@ -162,6 +162,13 @@ SIGNATURES = {
     # (the entry point's arguments + ring, its rows R, its stream stride)
     'wn_fastgen_lc_bias': (c_int, [P, c_long, c_int, P, c_int, P, c_int,
                                    c_int, c_long, c_int, P, c_int, c_int, P]),
+    # learned upsampling of frame-rate LC features (the scales: a host array)
+    'wn_lc_upsample_floats': (c_int, [P, c_int, c_int]),
+    'wn_lc_upsample_fwd': (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P,
+                                   c_int, c_int, c_int, P]),
+    'wn_lc_upsample_bwd_slabs': (c_int, [c_long, c_int]),
+    'wn_lc_upsample_bwd': (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P,
+                                   c_int, c_int, c_int, P, c_int, c_long, P]),
 }
 for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
               'wn_fastgen_persist', 'wn_fastgen_batch_pre',

@@ -18,6 +18,13 @@ and features, so that feature row t of a piece sits beside its sample t.
 `dequeue` followed by `dequeue_lc` returns the features of the pieces just
 dequeued.
 
+Frames mode (`lc_frames=True`, for a model that upsamples on the device with
+its learned network): a piece comes with the frames of its whole clip (the
+last frame repeated up to the clip's length, as upsample_lc does) and its
+offset, the clip-relative index of its first sample (silence trimming's
+start plus k * sample_size; pieces never span files).
+`dequeue_lc_frames` returns them for the pieces just dequeued.
+
 librosa is not available in this image: wav I/O is scipy.io.wavfile,
 resampling is scipy.signal.resample_poly (librosa's default is a Kaiser-windowed
 sinc; the two differ at the 1e-3 level, which only matters if one wants
@@ -169,6 +176,24 @@ def upsample_lc(feats, hop, num_samples, lc_channels=None):
     return np.ascontiguousarray(up[:num_samples])
 
 
+def pad_lc_frames(feats, hop, num_samples, lc_channels=None):
+    '''The frames [frames, Lc] that upsample_lc repeats over `num_samples`
+    (the last one repeated while the audio runs past it): upsample_lc of the
+    result at any length up to num_samples is upsample_lc of `feats`.'''
+    feats = np.asarray(feats, dtype=np.float32)
+    # (upsample_lc's checks, on a few samples of the same frames)
+    upsample_lc(feats, hop, 1, lc_channels)
+    hop = int(hop)
+    need = (int(num_samples) + hop - 1) // hop
+    if feats.shape[0] < need - 1:
+        raise ValueError('%d feature frames at hop %d do not cover %d samples'
+                         % (feats.shape[0], hop, num_samples))
+    if feats.shape[0] < need:
+        feats = np.concatenate([feats, np.repeat(
+            feats[-1:], need - feats.shape[0], axis=0)])
+    return np.ascontiguousarray(feats)
+
+
 def load_lc(path, hop, num_samples, lc_channels=None):
     '''upsample_lc of the features stored in `path` (.npy).'''
     return upsample_lc(np.load(path), hop, num_samples, lc_channels)
@@ -200,7 +225,8 @@ class AudioReader(object):
                  seed=None,
                  *,
                  lc_channels=None,
-                 lc_hop=None):
+                 lc_hop=None,
+                 lc_frames=False):
         self.audio_dir = audio_dir
         self.sample_rate = sample_rate
         self.coord = coord if coord is not None else Coordinator()
@@ -210,6 +236,8 @@ class AudioReader(object):
         self.lc_channels = lc_channels
         self.lc_hop = lc_hop
         self.lc_enabled = lc_channels is not None
+        # frames mode: pieces carry (clip frames, offset), not audio-rate rows
+        self.lc_frames = bool(lc_frames) and self.lc_enabled
         if self.lc_enabled and not lc_hop:
             raise ValueError('local conditioning needs lc_hop (samples per '
                              'feature frame)')
@@ -266,11 +294,22 @@ class AudioReader(object):
             # returns the features of exactly these pieces)
             feats = [f for _, f in pieces]
             pieces = [p for p, _ in pieces]
-            tmax = max(p.shape[0] for p in pieces)
-            lc = np.zeros((num_elements, tmax, self.lc_channels), np.float32)
-            for i, f in enumerate(feats):
-                lc[i, :f.shape[0]] = f
-            self._last_lc = torch.from_numpy(lc)
+            if self.lc_frames:
+                # [n, F_max, Lc] zero-padded frames + int64 offsets [n]
+                fmax = max(f.shape[0] for f, _ in feats)
+                fr = np.zeros((num_elements, fmax, self.lc_channels),
+                              np.float32)
+                for i, (f, _) in enumerate(feats):
+                    fr[i, :f.shape[0]] = f
+                self._last_lc = (torch.from_numpy(fr), torch.tensor(
+                    [o for _, o in feats], dtype=torch.int64))
+            else:
+                tmax = max(p.shape[0] for p in pieces)
+                lc = np.zeros((num_elements, tmax, self.lc_channels),
+                              np.float32)
+                for i, f in enumerate(feats):
+                    lc[i, :f.shape[0]] = f
+                self._last_lc = torch.from_numpy(lc)
         tmax = max(p.shape[0] for p in pieces)
         out = np.zeros((num_elements, tmax, 1), np.float32)
         for i, p in enumerate(pieces):
@@ -281,10 +320,27 @@ class AudioReader(object):
         """float32 [num_elements, T_max, lc_channels]: the audio-rate features
         of the pieces the last `dequeue(num_elements)` returned (zero-padded
         like them); row t sits beside sample t."""
-        if not self.lc_enabled:
-            raise ValueError('AudioReader was built without lc_channels')
+        if not self.lc_enabled or self.lc_frames:
+            raise ValueError('AudioReader was built without lc_channels'
+                             if not self.lc_enabled else
+                             'frames mode: use dequeue_lc_frames')
+        return self._take_lc(num_elements)
+
+    def dequeue_lc_frames(self, num_elements):
+        """Frames mode: (frames float32 [num_elements, F_max, lc_channels],
+        offsets int64 [num_elements]) of the pieces the last
+        `dequeue(num_elements)` returned: sample t of piece i sits at position
+        offsets[i] + t of its clip, whose frame is (offsets[i] + t) // lc_hop
+        (frames zero-padded behind each clip's own)."""
+        if not self.lc_frames:
+            raise ValueError('AudioReader was built without lc_frames')
+        return self._take_lc(num_elements)
+
+    def _take_lc(self, num_elements):
         lc = self._last_lc
-        if lc is None or lc.shape[0] != num_elements:
+        n = None if lc is None else \
+            (lc[1].shape[0] if isinstance(lc, tuple) else lc.shape[0])
+        if n != num_elements:
             raise ValueError('dequeue_lc(%d) must follow dequeue(%d)'
                              % (num_elements, num_elements))
         self._last_lc = None
@@ -313,6 +369,10 @@ class AudioReader(object):
         for audio, filename, category_id in load_generic_audio(
                 self.files, self.sample_rate, self._rng):
             lc = None
+            if self.lc_frames:
+                yield from self._frame_pieces(audio[:, 0], filename,
+                                              category_id)
+                continue
             if self.lc_enabled:
                 lc = load_lc(lc_path_of(filename), self.lc_hop, audio.shape[0],
                              self.lc_channels)
@@ -345,6 +405,25 @@ class AudioReader(object):
                         lc_buf = lc_buf[self.sample_size:]
             elif audio.size:
                 yield audio, category_id, lc
+
+    def _frame_pieces(self, audio, filename, category_id):
+        """iter_pieces of one file in frames mode: (piece [n, 1], category
+        id, (clip frames, offset of the piece's first sample))."""
+        frames = pad_lc_frames(np.load(lc_path_of(filename)), self.lc_hop,
+                               audio.shape[0], self.lc_channels)
+        lo = 0
+        if self.silence_threshold is not None:
+            lo, hi = trim_bounds(audio, self.silence_threshold)
+            audio = audio[lo:hi]
+            if audio.size == 0:
+                print("Warning: {} was ignored as it contains only "
+                      "silence. Consider decreasing trim_silence "
+                      "threshold, or adjust volume of the audio."
+                      .format(filename))
+        step = self.sample_size or max(audio.size, 1)
+        for k in range(0, audio.size, step):
+            yield (audio[k:k + step].reshape(-1, 1).copy(), category_id,
+                   (frames, int(lo + k)))
 
     def thread_main(self, sess=None):
         while not self.coord.should_stop():      # many passes over the data

@@ -17,6 +17,7 @@ There is no CPU / PyTorch compute fallback: without the HIP library or a GPU
 every entry point raises.
 """
 import collections
+import ctypes
 import math
 import os
 
@@ -144,6 +145,12 @@ class _Workspace(object):
             # [N][L][64] (lc x lc_w, the layout wn_stack_fwd_lc reads)
             alloc('lc', (N, net.Lcp), fill=0.0)
             alloc('lc_add', (N, L * 64))
+        if net.lc_up:
+            # learned upsampling: the frames each clip needs [B][Fw][Lc]
+            # (frame offset // hop on) and the offsets in the first frame
+            self.lc_fw = net._lc_frame_window(T)
+            alloc('lc_frames', (B, self.lc_fw, net.Lc), fill=0.0)
+            alloc('lc_off', (B,), torch.int32, fill=0)
         if net.blocked:
             # partial pre-activations of a layer wider than one chunk of
             # channel blocks (wavenet/blocked.py), planes af | ag
@@ -234,6 +241,15 @@ class _Workspace(object):
             sp = lib.wn_gemm_tn_splits(N, net.Lcp, L * 64, 0)
             self.splits['lc'] = sp
             need = max(need, sp * lib.wn_gemm_tn_slab_floats(net.Lcp, L * 64))
+        if net.lc_up:
+            # the gradient of the rows d rows = lc_da lc_w^T, and the
+            # upsampler's per-workgroup slabs
+            alloc('lc_wT', (L * 64, net.Lcp))
+            alloc('lc_drows', (N, net.Lcp))
+            self.lc_up_n = net._lc_up_floats()
+            self.lc_up_stride = _align(self.lc_up_n, 4)
+            self.lc_up_nslab = lib.wn_lc_upsample_bwd_slabs(N, self.lc_up_n)
+            alloc('lc_up_slabs', (self.lc_up_nslab, self.lc_up_stride))
         # scalar-input causal wgrad: [splits][initial_filter_width][32] slabs
         need = max(need, max(256, self.splits['causal'])
                    * max(32, net.initial_filter_width) * CH)
@@ -304,7 +320,8 @@ class WaveNetModel(object):
                  device=None,
                  seed=0,
                  *,
-                 local_condition_channels=None):
+                 local_condition_channels=None,
+                 local_condition_upsample_scales=None):
         self.batch_size = batch_size
         self.dilations = list(dilations)
         self.filter_width = filter_width
@@ -328,6 +345,17 @@ class WaveNetModel(object):
         # (LC weights as [Lcp][L][64]: rows padded to a multiple of 4 for the
         # GEMMs, zero)
         self.Lcp = _align(self.Lc, 4) if self.Lc else 0
+        # learned upsampling of frame-rate LC features (transposed
+        # convolutions over time, kernel = stride = s_i, see
+        # upsample_local_condition): the scales, or None (rows at audio rate)
+        self.local_condition_upsample_scales = self._check_lc_upsample(
+            local_condition_upsample_scales, local_condition_channels)
+        self.lc_up = self.local_condition_upsample_scales
+        self.lc_hop = int(np.prod(self.lc_up)) if self.lc_up else 0
+        # (the scales as the host int array the upsampler launches read;
+        # kept alive with the model, recorded launch plans hold its address)
+        self._lc_up_c = (ctypes.c_int * len(self.lc_up))(*self.lc_up) \
+            if self.lc_up else None
         # TF's fused softmax-xent back-propagates softmax/(B*T) through the
         # all-zero-label last row of every clip [inferred].
         self.tf_xent_zero_label_quirk = True
@@ -493,6 +521,43 @@ class WaveNetModel(object):
             raise NotImplementedError('%s: %s' % (why, cls.LC_SUPPORTED))
         return int(lc)
 
+    LC_UPSAMPLE_MAX_LAYERS = 8
+    LC_UPSAMPLE_MAX_HOP = 4096
+    LC_UPSAMPLE_MAX_CHANNELS = 512     # wn_lc_upsample_* (LCUP_MAX_LC)
+
+    @classmethod
+    def _check_lc_upsample(cls, scales, lc):
+        """The upsampler's scales as a tuple of ints (None without one);
+        raises before any library or device is touched."""
+        if scales is None:
+            return None
+        if lc is None:
+            raise ValueError('local_condition_upsample_scales needs '
+                             'local_condition_channels')
+        try:
+            sc = tuple(scales)
+        except TypeError:
+            raise ValueError('local_condition_upsample_scales must be a tuple '
+                             'of ints, got %r' % (scales,))
+        if not 1 <= len(sc) <= cls.LC_UPSAMPLE_MAX_LAYERS or any(
+                isinstance(s, (bool, np.bool_)) or
+                not isinstance(s, (int, np.integer)) or int(s) < 2
+                for s in sc):
+            raise ValueError('local_condition_upsample_scales must be 1 to %d '
+                             'ints >= 2, got %r'
+                             % (cls.LC_UPSAMPLE_MAX_LAYERS, scales))
+        sc = tuple(int(s) for s in sc)
+        if int(np.prod(sc)) > cls.LC_UPSAMPLE_MAX_HOP:
+            raise ValueError('local_condition_upsample_scales: the hop (their '
+                             'product, %d) must be at most %d'
+                             % (int(np.prod(sc)), cls.LC_UPSAMPLE_MAX_HOP))
+        if int(lc) > cls.LC_UPSAMPLE_MAX_CHANNELS:
+            raise NotImplementedError(
+                'the local-conditioning upsampler supports at most %d channels '
+                '(local_condition_channels = %d)'
+                % (cls.LC_UPSAMPLE_MAX_CHANNELS, int(lc)))
+        return sc
+
     @property
     def stack_variant(self):
         return self._stack_variant
@@ -537,6 +602,10 @@ class WaveNetModel(object):
             # front of skip_w: the data-parallel tail all-reduce starts there
             # (parallel.tail_start) before this gradient exists
             add('lc_w', self.Lcp * L * 64)
+        if self.lc_up:
+            # the upsampler: filters [s_i][3] of every layer, then (biases)
+            # one scalar per layer.  Also in front of skip_w
+            add('lc_up', self._lc_up_floats())
         add('skip_w', L * C * S)
         add('skip_b', L * S)
         add('post1_w', S * S)
@@ -550,6 +619,10 @@ class WaveNetModel(object):
         self.gradients = self._views(self.grads)
         self._init_variables(seed)
         return self.variables
+
+    def _lc_up_floats(self):
+        return 3 * sum(self.lc_up) + (len(self.lc_up) if self.use_biases
+                                      else 0)
 
     def _seg(self, flat, name):
         o, n = self.segments[name]
@@ -601,6 +674,16 @@ class WaveNetModel(object):
                 cur['dense_bias'] = blk[OFF_BD:OFF_BD + R]
                 cur['skip_bias'] = skb[i]
             var['dilated_stack'].append(cur)
+        if self.lc_up:
+            # the upsampler, layer i: filter [s_i][3] (slot, tap), bias [1]
+            up, fo, nf = self._seg(flat, 'lc_up'), 0, 3 * sum(self.lc_up)
+            var['lc_upsample'] = []
+            for i, s in enumerate(self.lc_up):
+                cur = {'filter': up[fo:fo + 3 * s].view(s, 3)}
+                if self.use_biases:
+                    cur['bias'] = up[nf + i:nf + i + 1]
+                var['lc_upsample'].append(cur)
+                fo += 3 * s
         post = dict()
         post['postprocess1'] = self._seg(flat, 'post1_w').view(1, S, S)
         post['postprocess2'] = self._seg(flat, 'post2_w').view(1, S, Q)
@@ -638,6 +721,10 @@ class WaveNetModel(object):
                 for k in ['lc_filtweights', 'lc_gateweights']:
                     if k in cur:
                         _xavier_(cur[k], gen)
+            # the upsampler starts as repetition: W_i[j] = (0, 1, 0), b_i = 0
+            # (no draws: every other variable keeps its values)
+            for cur in v.get('lc_upsample', []):
+                cur['filter'][:, 1] = 1.0
             # biases: zeros (model.py:27)
             self.params.copy_(host)
 
@@ -690,6 +777,11 @@ class WaveNetModel(object):
                 if k in cur:
                     out.append(('%s/dilated_stack/layer%d/%s'
                                 % (prefix, i, tfname.get(k, k)), cur[k]))
+        for i, cur in enumerate(tree.get('lc_upsample', [])):
+            for k in ['filter', 'bias']:
+                if k in cur:
+                    out.append(('%s/lc_upsample/layer%d/%s' % (prefix, i, k),
+                                cur[k]))
         for k in ['postprocess1', 'postprocess2', 'postprocess1_bias',
                   'postprocess2_bias']:
             if k in tree['postprocessing']:
@@ -927,6 +1019,161 @@ class WaveNetModel(object):
                 'local conditioning needs B * T < 2^24 and at most 256 '
                 'layers (the persistent stack launches)')
         return lc.to(device=self.device, dtype=torch.float32)
+
+    def _lc_input(self, local_condition, offset, B, T, what):
+        """A loss call's LC input: rows (_lc_rows), or for a model with the
+        upsampler (frames on the host or device [B, F, Lc], offsets int64
+        [B] on the host), checked before anything is launched."""
+        if not self.lc_up:
+            if not (isinstance(offset, (int, np.integer)) and
+                    not isinstance(offset, bool) and int(offset) == 0):
+                raise ValueError('%s: local_condition_offset is for models '
+                                 'built with local_condition_upsample_scales'
+                                 % what)
+            return self._lc_rows(local_condition, B, T, what)
+        fr, off = self._lc_frames(local_condition, offset, B, T, what)
+        self._lc_launch_checks(B, T)
+        return fr, off
+
+    def _lc_launch_checks(self, B, T):
+        if not (self.stack_fwd and self.stack_bwd):
+            raise NotImplementedError(
+                'stack_fwd / stack_bwd = False with local conditioning: '
+                + self.LC_SUPPORTED)
+        if self._layer_path() != 'layer':       # (generic_layers forced)
+            raise NotImplementedError(self.LC_SUPPORTED)
+        if not self._stack_ok(B * T):
+            raise NotImplementedError(
+                'local conditioning needs B * T < 2^24 and at most 256 '
+                'layers (the persistent stack launches)')
+
+    def _lc_frame_window(self, T):
+        """Frames a clip of T samples touches at most (any offset)."""
+        return (T + self.lc_hop - 2) // self.lc_hop + 1
+
+    def _lc_frames(self, frames, offset, B, T, what):
+        """Validate frame-rate LC features [B, F, Lc] (or [F, Lc] with B = 1)
+        and the offsets (an int or B non-negative ints).  Returns the frames
+        as a float tensor where the caller had them and the offsets as int64
+        numpy [B]."""
+        Lc, hop = self.Lc, self.lc_hop
+        shape = '[B, F, Lc] = [%d, F, %d] with F >= (offset + %d - 1) // %d + 1' \
+            % (B, Lc, T, hop)
+        if frames is None:
+            raise ValueError('%s: the model upsamples local conditioning '
+                             '(hop %d); frames %s are required'
+                             % (what, hop, shape))
+        fr = frames
+        if not isinstance(fr, torch.Tensor):
+            fr = np.asarray(fr)
+            if fr.dtype == object or not np.issubdtype(fr.dtype, np.floating):
+                raise ValueError('%s: local conditioning frames must be a '
+                                 'float array %s' % (what, shape))
+            fr = torch.from_numpy(fr)
+        if not fr.is_floating_point():
+            raise ValueError('%s: local conditioning frames must be floating '
+                             'point' % what)
+        if B == 1 and fr.dim() == 2:
+            fr = fr.unsqueeze(0)
+        if fr.dim() != 3 or fr.shape[0] != B or fr.shape[2] != Lc or \
+                fr.shape[1] < 1:
+            raise ValueError('%s: local conditioning frames must have shape %s,'
+                             ' got %s' % (what, shape, tuple(fr.shape)))
+        if isinstance(offset, torch.Tensor):
+            offset = offset.detach().cpu().numpy()
+        off = np.asarray(offset)
+        if off.dtype == object or off.dtype == np.bool_ or \
+                not np.issubdtype(off.dtype, np.integer):
+            raise ValueError('%s: local_condition_offset must be an int or %d '
+                             'ints, got %r' % (what, B, offset))
+        if off.ndim == 0:
+            off = np.full(B, int(off), np.int64)
+        if off.shape != (B,):
+            raise ValueError('%s: local_condition_offset must be an int or %d '
+                             'ints, got shape %s' % (what, B, off.shape))
+        off = off.astype(np.int64)
+        if (off < 0).any():
+            raise ValueError('%s: local_condition_offset must be non-negative, '
+                             'got %s' % (what, off.tolist()))
+        need = int(((off + T - 1) // hop).max()) + 1
+        if fr.shape[1] < need:
+            raise ValueError('%s: %d frames do not cover position offset + T - '
+                             '1 = %d: local conditioning frames must have shape '
+                             '%s (here F >= %d), got %s'
+                             % (what, fr.shape[1], int((off + T - 1).max()),
+                                shape, need, tuple(fr.shape)))
+        return fr, off
+
+    def _stage_frames(self, fr, off, T, dst_frames, dst_off):
+        """The frames clip b touches, frame offset[b] // hop on, into
+        dst_frames [B][Fw][Lc] (device) and offset[b] % hop into dst_off."""
+        B, F = fr.shape[0], fr.shape[1]
+        hop, Fw = self.lc_hop, dst_frames.shape[1]
+        idx = np.minimum((off // hop)[:, None] + np.arange(Fw)[None, :], F - 1)
+        rows = torch.arange(B, device=fr.device)[:, None]
+        sel = fr[rows, torch.as_tensor(idx, device=fr.device)]
+        dst_frames.copy_(sel)
+        dst_off.copy_(torch.as_tensor((off % hop).astype(np.int32)))
+
+    def _lc_upsample(self, frames, off, B, T, rows, st):
+        """rows[B * T][Lcp] = the upsampler on staged frames / offsets."""
+        _lib.call('wn_lc_upsample_fwd', _lib.ptr(frames), frames.shape[1],
+                  _lib.ptr(off), _lib.ptr(self._seg(self.params, 'lc_up')),
+                  ctypes.addressof(self._lc_up_c), len(self.lc_up), self.Lc,
+                  1 if self.use_biases else 0, _lib.ptr(rows), self.Lcp, B, T,
+                  st)
+
+    def _lc_upsample_bwd(self, ws, st):
+        """The upsampler's gradients: d rows [N][Lcp] = lc_da lc_w^T (the
+        transposed LC weights, one NN GEMM), then every workgroup's
+        (layer, slot, tap) partials of its rows, summed in a fixed order."""
+        L, N, W64 = self.L, ws.N, self.L * 64
+        _lib.call('wn_transpose', _lib.ptr(self._seg(self.params, 'lc_w')),
+                  self.Lcp, W64, W64, _lib.ptr(ws.lc_wT), self.Lcp, st)
+        _lib.call_timed('wn_gemm_nn', (
+            _lib.ptr(ws.lc_da), W64, 0, 0, _lib.ptr(ws.lc_wT), self.Lcp, None,
+            None, 0, None, 0, _lib.ptr(ws.lc_drows), self.Lcp, 0, 0, None, N,
+            self.Lcp, W64, 0, st), 2.0 * N * W64 * self.Lcp, self._gemm_events)
+        _lib.call('wn_lc_upsample_bwd', _lib.ptr(ws.lc_frames), ws.lc_fw,
+                  _lib.ptr(ws.lc_off), _lib.ptr(self._seg(self.params, 'lc_up')),
+                  ctypes.addressof(self._lc_up_c), len(self.lc_up), self.Lc,
+                  1 if self.use_biases else 0, _lib.ptr(ws.lc_drows), self.Lcp,
+                  ws.B, ws.T, _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
+                  ws.lc_up_stride, st)
+        _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
+                  ws.lc_up_stride, 1, 0, 0, ws.lc_up_n,
+                  _lib.ptr(self._seg(self.grads, 'lc_up')), 0, 1, 0, st)
+
+    def upsample_local_condition(self, frames, num_samples, offset=0):
+        """The learned upsampler on frame-rate features: frames float
+        [B, F, Lc] (or [F, Lc]) -> device float32 rows [B, num_samples, Lc]
+        (or [num_samples, Lc]); row t is timeline position offset[b] + t
+        (offset: an int or B non-negative ints).  The same kernel as the
+        training forward: a row's bits depend on its frame, its slot and the
+        weights only.  The rows feed predict_proba and fast generation."""
+        self._check_supported()
+        if not self.lc_up:
+            raise ValueError('upsample_local_condition: the model was built '
+                             'without local_condition_upsample_scales')
+        n = int(num_samples)
+        if n < 1:
+            raise ValueError('upsample_local_condition: num_samples must be '
+                             'positive, got %r' % (num_samples,))
+        if not isinstance(frames, torch.Tensor):
+            frames = np.asarray(frames)
+        two_d = frames.ndim == 2
+        B = 1 if two_d or frames.ndim < 2 else frames.shape[0]
+        fr, off = self._lc_frames(frames, offset, B, n,
+                                  'upsample_local_condition')
+        dev = self.device
+        staged = torch.empty((B, self._lc_frame_window(n), self.Lc),
+                             dtype=torch.float32, device=dev)
+        offs = torch.empty((B,), dtype=torch.int32, device=dev)
+        self._stage_frames(fr, off, n, staged, offs)
+        rows = torch.empty((B * n, self.Lcp), dtype=torch.float32, device=dev)
+        self._lc_upsample(staged, offs, B, n, rows, _lib.stream())
+        out = rows[:, :self.Lc].reshape(B, n, self.Lc).contiguous()
+        return out[0] if two_d else out
 
     def _layer_block(self, flat, l):
         o, _ = self.segments['layers']
@@ -1435,6 +1682,8 @@ class WaveNetModel(object):
                       lib.wn_gemm_tn_slab_floats(self.Lcp, W64), 1, 0, 0,
                       self.Lcp * W64, _lib.ptr(self._seg(Gr, 'lc_w')), 0, 1, 0,
                       st)
+        if self.lc_up:
+            self._lc_upsample_bwd(ws, st)
         if ws.dsum is not None:
             _lib.call('wn_gc_grad', _lib.ptr(self._layer_block(P, 0)),
                       self.layer_stride, self.OFF_GC, self.G,
@@ -1461,7 +1710,8 @@ class WaveNetModel(object):
              name='wavenet',
              backward=True,
              *,
-             local_condition_batch=None):
+             local_condition_batch=None,
+             local_condition_offset=0):
         '''Creates a WaveNet network and returns the autoencoding loss
         (model.py:628-685).  input_batch: float audio in [-1, 1], anything
         reshapeable to [batch_size, -1].  With backward=True (default) the
@@ -1472,28 +1722,41 @@ class WaveNetModel(object):
         required there and refused elsewhere): float [batch_size, T, Lc] at
         audio rate.  Row t sits beside input sample t; the output at t is the
         distribution of sample t + 1, so row t conditions the prediction of
-        sample t + 1.  Frame-rate features are upsampled by repetition first.'''
+        sample t + 1.  Frame-rate features are upsampled by repetition first.
+
+        Models built with local_condition_upsample_scales take FRAMES
+        instead: float [batch_size, F, Lc], upsampled on the device by the
+        learned network (gradients flow into it).  local_condition_offset
+        (an int or batch_size non-negative ints, default 0): input sample t
+        of clip b sits at timeline position offset[b] + t, which takes frame
+        (offset[b] + t) // hop; F must cover offset[b] + T - 1.'''
         self._check_supported()
         B = self.batch_size
         a = input_batch
         if not isinstance(a, torch.Tensor):
             a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
-        lc = self._lc_rows(local_condition_batch, B, a.shape[1], 'loss')
+        lc = self._lc_input(local_condition_batch, local_condition_offset, B,
+                            a.shape[1], 'loss')
         q = mu_law_encode(a, self.Q)
         return self.loss_from_codes(q, global_condition_batch,
                                     l2_regularization_strength, backward,
-                                    audio=a, local_condition_batch=lc)
+                                    audio=a, local_condition_batch=(
+                                        local_condition_batch if self.lc_up
+                                        else lc),
+                                    local_condition_offset=local_condition_offset)
 
     def loss_from_codes(self, q, global_condition_batch=None,
                         l2_regularization_strength=None, backward=True,
-                        audio=None, *, local_condition_batch=None):
+                        audio=None, *, local_condition_batch=None,
+                        local_condition_offset=0):
         self._check_supported()
         B = self.batch_size
         q = q.reshape(B, -1)
         T = q.shape[1]
         N = B * T
-        lc = self._lc_rows(local_condition_batch, B, T, 'loss')
+        lc = self._lc_input(local_condition_batch, local_condition_offset, B,
+                            T, 'loss')
         ws = self._workspace(B, T, backward)
         if backward and self._tail_work is not None:
             # the previous backward pass started its tail all-reduce and no
@@ -1513,9 +1776,13 @@ class WaveNetModel(object):
                 raise ValueError('scalar_input needs the float audio')
             ws.audio.copy_(audio.reshape(-1))
         ids = self._gc_ids(global_condition_batch, B)
-        if lc is not None:
-            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
         st = _lib.stream()
+        if self.lc_up:
+            # frames: the rows are the upsampler's, into ws.lc
+            self._stage_frames(lc[0], lc[1], T, ws.lc_frames, ws.lc_off)
+            self._lc_upsample(ws.lc_frames, ws.lc_off, B, T, ws.lc, st)
+        elif lc is not None:
+            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
         # (L2 adds lambda * params to the WHOLE bucket after the backward
         # pass: the tail must not have been summed over ranks before that)
         path = self._step_path(ws, backward,

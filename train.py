@@ -106,7 +106,32 @@ def get_arguments(argv=None):
                    help='Local conditioning: audio samples per feature frame '
                         '(frames are upsampled by repetition).  Default 1 '
                         'with --synthetic.')
+    p.add_argument('--lc_upsample_scales', type=str, default=None,
+                   help='Local conditioning: upsample the frames on the device '
+                        'with a learned network of transposed convolutions, '
+                        'one layer per scale, e.g. 4,5,10 (hop = their '
+                        'product; --lc_hop must be absent or equal to it).')
     return p.parse_args(argv)
+
+
+def lc_upsample_scales(args):
+    """(scales tuple, hop) of --lc_upsample_scales, or (None, args.lc_hop);
+    ValueError for a malformed list or an --lc_hop that disagrees."""
+    if args.lc_upsample_scales is None:
+        return None, args.lc_hop
+    try:
+        scales = tuple(int(x) for x in args.lc_upsample_scales.split(','))
+    except ValueError:
+        raise ValueError('--lc_upsample_scales must be comma-separated ints, '
+                         'got %r' % args.lc_upsample_scales)
+    if args.lc_channels is None:
+        raise ValueError('--lc_upsample_scales needs --lc_channels')
+    hop = int(np.prod(scales))
+    if args.lc_hop is not None and args.lc_hop != hop:
+        raise ValueError('--lc_hop %d disagrees with --lc_upsample_scales %s '
+                         '(hop = their product, %d)'
+                         % (args.lc_hop, args.lc_upsample_scales, hop))
+    return scales, hop
 
 
 def checkpoint_path(logdir, step):
@@ -220,6 +245,16 @@ class SyntheticReader(object):
         return torch.tensor([(37 * i) % self.card for i in self._last_ids],
                             dtype=torch.int32)
 
+    def dequeue_lc_frames(self, n):
+        """Random frame-rate features [n, F, Lc] and offsets [n] in
+        [0, 4 * lc_hop): sample t of clip i sits at position offsets[i] + t."""
+        hop = self.lc_hop
+        offs = self.rng.integers(0, 4 * hop, n)
+        frames = (int(offs.max()) + self.T - 1) // hop + 1
+        return (torch.from_numpy(self.rng.standard_normal(
+            (n, frames, self.lc_channels)).astype(np.float32)),
+            torch.from_numpy(offs.astype(np.int64)))
+
     def dequeue_lc(self, n):
         """Random frame-rate features upsampled by repetition: [n, T, Lc]."""
         from wavenet.audio_reader import upsample_lc
@@ -235,6 +270,11 @@ class SyntheticReader(object):
 
 def main(argv=None):
     args = get_arguments(argv)
+    try:
+        lc_scales, lc_hop = lc_upsample_scales(args)
+    except ValueError as e:
+        print(str(e))
+        return 1
     try:
         directories = validate_directories(args)
     except ValueError as e:
@@ -268,9 +308,9 @@ def main(argv=None):
         reader = SyntheticReader(args.sample_size,
                                  args.gc_cardinality if gc_enabled else None,
                                  rank=rank, lc_channels=args.lc_channels,
-                                 lc_hop=args.lc_hop or 1)
+                                 lc_hop=lc_hop or 1)
     else:
-        if lc_enabled and not args.lc_hop:
+        if lc_enabled and not lc_hop:
             print('--lc_channels needs --lc_hop (audio samples per feature '
                   'frame)')
             return 1
@@ -281,7 +321,7 @@ def main(argv=None):
                              silence_threshold=silence_threshold,
                              rank=rank, world=world, seed=rank,
                              lc_channels=args.lc_channels,
-                             lc_hop=args.lc_hop)
+                             lc_hop=lc_hop, lc_frames=lc_scales is not None)
 
     net = WaveNetModel(
         batch_size=args.batch_size,
@@ -298,7 +338,8 @@ def main(argv=None):
         global_condition_channels=args.gc_channels,
         global_condition_cardinality=reader.gc_category_cardinality,
         residual_postproc=wavenet_params.get("residual_postproc", False),
-        local_condition_channels=args.lc_channels)
+        local_condition_channels=args.lc_channels,
+        local_condition_upsample_scales=lc_scales)
     l2 = args.l2_regularization_strength or None
     optimizer = optimizer_factory[args.optimizer](
         learning_rate=args.learning_rate, momentum=args.momentum)
@@ -408,7 +449,12 @@ def main(argv=None):
             try:
                 audio = reader.dequeue(args.batch_size)
                 gc = reader.dequeue_gc(args.batch_size) if gc_enabled else None
-                lc = reader.dequeue_lc(args.batch_size) if lc_enabled else None
+                lc, lc_off = None, 0
+                if lc_scales is not None:
+                    # frames + offsets: the model upsamples on the device
+                    lc, lc_off = reader.dequeue_lc_frames(args.batch_size)
+                elif lc_enabled:
+                    lc = reader.dequeue_lc(args.batch_size)
             except Exception as e:        # e.g. a reader-thread failure
                 err, audio, gc, lc = e, None, None, None
             n_t, all_ok = parallel.agree_step(
@@ -420,7 +466,7 @@ def main(argv=None):
             if n_t < 2:
                 continue
             audio = audio[:, :n_t]
-            if lc is not None:
+            if lc is not None and lc_scales is None:
                 lc = lc[:, :n_t]
             if audio.device.type == 'cpu' and net.device.type == 'cuda':
                 # pinned staging + asynchronous copy: a pageable host tensor
@@ -438,7 +484,8 @@ def main(argv=None):
                 prof.__enter__()
             loss = net.loss(input_batch=audio, global_condition_batch=gc,
                             l2_regularization_strength=l2,
-                            local_condition_batch=lc)
+                            local_condition_batch=lc,
+                            local_condition_offset=lc_off)
             optimizer.minimize(loss)
             # The reference fetches the loss inside sess.run and so waits for
             # every step (train.py:300-311).  Here the step is queued on the
