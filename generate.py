@@ -21,7 +21,9 @@ rows shared by all of them.  Without either flag --lc_path is refused.
 With --lc_upsample_scales (a model trained with train.py
 --lc_upsample_scales) the frames are upsampled once by the checkpoint's
 learned network (`upsample_local_condition`) instead of by repetition; the
-flows above then run on those rows.
+flows above then run on those rows.  --lc_context P (a model trained with
+train.py --lc_context P) applies the checkpoint's frame-context convolution in
+front of that upsampler.
 """
 from __future__ import division
 from __future__ import print_function
@@ -96,6 +98,9 @@ def get_arguments(argv=None):
     p.add_argument('--lc_upsample_scales', type=str, default=None,
                    help='with --lc_path: the scales of the model\'s learned '
                    'upsampler (train.py --lc_upsample_scales), e.g. 4,5,10')
+    p.add_argument('--lc_context', type=int, default=None,
+                   help='with --lc_upsample_scales: P of the model\'s '
+                   'frame-context convolution (train.py --lc_context)')
     p.add_argument('--gc_ids', type=str, default=None,
                    help='comma-separated global condition ids, one clip each '
                    '(sets --clips to their number)')
@@ -162,6 +167,22 @@ def upsampler_mismatch(net, sd):
             % (desc(theirs), desc(mine)))
 
 
+def context_mismatch(net, sd):
+    """A message when the checkpoint's frame-context filter (state dict
+    `sd`) and the model's (--lc_context) differ, else None."""
+    name = 'wavenet/lc_context/filter'
+    mine = dict(net.named_variables()).get(name)
+    mine = None if mine is None else tuple(mine.shape)
+    theirs = tuple(np.shape(sd[name])) if name in sd else None
+    if mine == theirs:
+        return None
+    def desc(shape):
+        return 'none' if shape is None else 'P = %d, shape %s' % (
+            (shape[0] - 1) // 2, 'x'.join(str(n) for n in shape))
+    return ('the checkpoint\'s frame-context filter (%s, %s) does not match '
+            '--lc_context (%s)' % (name, desc(theirs), desc(mine)))
+
+
 def main(argv=None):
     args = get_arguments(argv)
     lc_rows, lc_scales = None, None
@@ -190,9 +211,15 @@ def main(argv=None):
                 print('--lc_hop %d disagrees with --lc_upsample_scales %s '
                       '(hop %d)' % (args.lc_hop, args.lc_upsample_scales, hop))
                 return 1
+            if args.lc_context is not None and not 0 <= args.lc_context <= 8:
+                print('--lc_context must be from 0 to 8')
+                return 1
             # (the rows come from the model's upsampler once it is loaded)
             lc_rows = np.zeros((feats.shape[0] * hop, feats.shape[1]),
                                np.float32)
+        elif args.lc_context is not None:
+            print('--lc_context needs --lc_upsample_scales')
+            return 1
         else:
             lc_rows = upsample_lc(feats, args.lc_hop,
                                   feats.shape[0] * args.lc_hop)
@@ -217,7 +244,8 @@ def main(argv=None):
         global_condition_cardinality=args.gc_cardinality,
         residual_postproc=wavenet_params.get("residual_postproc", False),
         local_condition_channels=None if lc_rows is None else lc_rows.shape[1],
-        local_condition_upsample_scales=lc_scales)
+        local_condition_upsample_scales=lc_scales,
+        local_condition_context=args.lc_context if lc_scales else None)
     print('Restoring model from {}'.format(args.checkpoint))
     if tf_checkpoint.checkpoint_format(args.checkpoint):
         # a checkpoint written by the reference itself (tf.train.Saver)
@@ -225,7 +253,7 @@ def main(argv=None):
     else:
         sd = torch.load(args.checkpoint, map_location='cpu')['variables']
         if lc_rows is not None:
-            why = upsampler_mismatch(net, sd)
+            why = upsampler_mismatch(net, sd) or context_mismatch(net, sd)
             if why:
                 print(why)
                 return 1

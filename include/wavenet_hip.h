@@ -752,6 +752,35 @@ int wn_lc_upsample_bwd(const float* frames, int F, const int32_t* off,
                        int use_bias, const float* drows, int ld_drows, int B,
                        int T, float* slabs, int num_slabs, long slab_stride,
                        void* stream);
+/* bwd_ctx: wn_lc_upsample_bwd (the same slabs, bitwise) that also writes the
+ * gradient at the upsampler's input, dframes [B][F][Lc]: per frame the sum
+ * over its rows of the layer-0 input's gradient (its three taps).  Needs
+ * every row's frame inside F ((T + hop - 2) / hop + 1 <= F, off[b] < hop).
+ * dpart: num_slabs * 2 * Lc floats of per-workgroup parts (frames shared
+ * between workgroups), added in workgroup order by a second launch; a frame
+ * without rows gets zero.  No atomics. */
+int wn_lc_upsample_bwd_ctx(const float* frames, int F, const int32_t* off,
+                           const float* up, const int* scales, int m, int Lc,
+                           int use_bias, const float* drows, int ld_drows,
+                           int B, int T, float* slabs, int num_slabs,
+                           long slab_stride, float* dframes, float* dpart,
+                           void* stream);
+
+/* ---- frame-context convolution in front of the upsampler (csrc/wn_misc.hip).
+ * 0 <= p <= 8, 1 <= Lc <= 512; w [2p + 1][Lc][Lc] ([K][Cin][Cout]), no bias.
+ * x [B][Fx][Lc]: frames staged with p frames of context either side, Fx >=
+ * Fw + 2p.  fwd: ctx[b][f][j] = sum_{k, c} w[k][c][j] x[b][f + k][c] for
+ * f < Fw, ctx [B][Fw][Lc]; an output's bits depend on x[b][f .. f + 2p] and w
+ * only.  wgrad: dw[k][c][j] = sum_{b, f < Fw} x[b][f + k][c] dctx[b][f][j]:
+ * slab s sums a fixed range of the B * Fw frames, [(2p + 1) Lc][Lc] floats
+ * per slab (slab_stride >= that); sum them with wn_reduce_slabs.
+ * num_slabs = wn_lc_context_wgrad_slabs(B * Fw, (2p + 1) * Lc * Lc). */
+int wn_lc_context_fwd(const float* x, int Fx, const float* w, int p, int Lc,
+                      float* ctx, int Fw, int B, void* stream);
+int wn_lc_context_wgrad_slabs(long rows, int nacc);
+int wn_lc_context_wgrad(const float* x, int Fx, const float* dctx, int Fw,
+                        int p, int Lc, int B, float* slabs, int num_slabs,
+                        long slab_stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,15 @@ SIGNATURES = {
     'wn_lc_upsample_bwd_slabs': (c_int, [c_long, c_int]),
     'wn_lc_upsample_bwd': (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P,
                                    c_int, c_int, c_int, P, c_int, c_long, P]),
+    'wn_lc_upsample_bwd_ctx': (c_int, [P, c_int, P, P, P, c_int, c_int, c_int,
+                                       P, c_int, c_int, c_int, P, c_int,
+                                       c_long, P, P, P]),
+    # frame-context convolution in front of the upsampler
+    'wn_lc_context_fwd': (c_int, [P, c_int, P, c_int, c_int, P, c_int, c_int,
+                                  P]),
+    'wn_lc_context_wgrad_slabs': (c_int, [c_long, c_int]),
+    'wn_lc_context_wgrad': (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P,
+                                    c_int, c_long, P]),
 }
 for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
               'wn_fastgen_persist', 'wn_fastgen_batch_pre',

@@ -151,6 +151,11 @@ class _Workspace(object):
             self.lc_fw = net._lc_frame_window(T)
             alloc('lc_frames', (B, self.lc_fw, net.Lc), fill=0.0)
             alloc('lc_off', (B,), torch.int32, fill=0)
+        if net.lc_ctx is not None:
+            # frame context: the frames staged with p frames either side
+            # [B][Fw + 2p][Lc]; lc_frames holds the convolution's output
+            alloc('lc_xframes', (B, self.lc_fw + 2 * net.lc_ctx, net.Lc),
+                  fill=0.0)
         if net.blocked:
             # partial pre-activations of a layer wider than one chunk of
             # channel blocks (wavenet/blocked.py), planes af | ag
@@ -250,6 +255,16 @@ class _Workspace(object):
             self.lc_up_stride = _align(self.lc_up_n, 4)
             self.lc_up_nslab = lib.wn_lc_upsample_bwd_slabs(N, self.lc_up_n)
             alloc('lc_up_slabs', (self.lc_up_nslab, self.lc_up_stride))
+        if net.lc_ctx is not None:
+            # d frames at the upsampler's input [B][Fw][Lc], the upsampler
+            # workgroups' parts of shared frames, the context filter's slabs
+            alloc('lc_dctx', (B, self.lc_fw, net.Lc))
+            alloc('lc_dpart', (self.lc_up_nslab, 2, net.Lc))
+            self.lc_ctx_n = (2 * net.lc_ctx + 1) * net.Lc * net.Lc
+            self.lc_ctx_stride = _align(self.lc_ctx_n, 4)
+            self.lc_ctx_nslab = lib.wn_lc_context_wgrad_slabs(
+                B * self.lc_fw, self.lc_ctx_n)
+            alloc('lc_ctx_slabs', (self.lc_ctx_nslab, self.lc_ctx_stride))
         # scalar-input causal wgrad: [splits][initial_filter_width][32] slabs
         need = max(need, max(256, self.splits['causal'])
                    * max(32, net.initial_filter_width) * CH)
@@ -321,7 +336,8 @@ class WaveNetModel(object):
                  seed=0,
                  *,
                  local_condition_channels=None,
-                 local_condition_upsample_scales=None):
+                 local_condition_upsample_scales=None,
+                 local_condition_context=None):
         self.batch_size = batch_size
         self.dilations = list(dilations)
         self.filter_width = filter_width
@@ -356,6 +372,11 @@ class WaveNetModel(object):
         # kept alive with the model, recorded launch plans hold its address)
         self._lc_up_c = (ctypes.c_int * len(self.lc_up))(*self.lc_up) \
             if self.lc_up else None
+        # frame-context convolution in front of the upsampler (kernel 2p + 1
+        # over frames, Lc -> Lc, no bias): p, or None without one
+        self.local_condition_context = self._check_lc_context(
+            local_condition_context, self.lc_up)
+        self.lc_ctx = self.local_condition_context
         # TF's fused softmax-xent back-propagates softmax/(B*T) through the
         # all-zero-label last row of every clip [inferred].
         self.tf_xent_zero_label_quirk = True
@@ -558,6 +579,25 @@ class WaveNetModel(object):
                 % (cls.LC_UPSAMPLE_MAX_CHANNELS, int(lc)))
         return sc
 
+    LC_CONTEXT_MAX = 8                 # wn_lc_context_* (LCCTX_MAX_P)
+
+    @classmethod
+    def _check_lc_context(cls, p, scales):
+        """The context half-width p as an int (None without one); raises
+        before any library or device is touched."""
+        if p is None:
+            return None
+        if isinstance(p, (bool, np.bool_)) or \
+                not isinstance(p, (int, np.integer)) or \
+                not 0 <= int(p) <= cls.LC_CONTEXT_MAX:
+            raise ValueError('local_condition_context must be an int from 0 to '
+                             '%d, got %r' % (cls.LC_CONTEXT_MAX, p))
+        if not scales:
+            raise ValueError('local_condition_context needs '
+                             'local_condition_upsample_scales (it convolves '
+                             'frames; repetition-row models take rows)')
+        return int(p)
+
     @property
     def stack_variant(self):
         return self._stack_variant
@@ -606,6 +646,10 @@ class WaveNetModel(object):
             # the upsampler: filters [s_i][3] of every layer, then (biases)
             # one scalar per layer.  Also in front of skip_w
             add('lc_up', self._lc_up_floats())
+        if self.lc_ctx is not None:
+            # the frame-context filter [2p + 1][Lc][Lc].  Also in front of
+            # skip_w
+            add('lc_ctx', (2 * self.lc_ctx + 1) * self.Lc * self.Lc)
         add('skip_w', L * C * S)
         add('skip_b', L * S)
         add('post1_w', S * S)
@@ -684,6 +728,9 @@ class WaveNetModel(object):
                     cur['bias'] = up[nf + i:nf + i + 1]
                 var['lc_upsample'].append(cur)
                 fo += 3 * s
+        if self.lc_ctx is not None:
+            var['lc_context'] = {'filter': self._seg(flat, 'lc_ctx').view(
+                2 * self.lc_ctx + 1, self.Lc, self.Lc)}
         post = dict()
         post['postprocess1'] = self._seg(flat, 'post1_w').view(1, S, S)
         post['postprocess2'] = self._seg(flat, 'post2_w').view(1, S, Q)
@@ -725,6 +772,10 @@ class WaveNetModel(object):
             # (no draws: every other variable keeps its values)
             for cur in v.get('lc_upsample', []):
                 cur['filter'][:, 1] = 1.0
+            # the context filter starts as the identity: centre tap I, the
+            # others zero (no draws either)
+            if 'lc_context' in v:
+                v['lc_context']['filter'][self.lc_ctx] = torch.eye(self.Lc)
             # biases: zeros (model.py:27)
             self.params.copy_(host)
 
@@ -782,6 +833,9 @@ class WaveNetModel(object):
                 if k in cur:
                     out.append(('%s/lc_upsample/layer%d/%s' % (prefix, i, k),
                                 cur[k]))
+        if 'lc_context' in tree:
+            out.append((prefix + '/lc_context/filter',
+                        tree['lc_context']['filter']))
         for k in ['postprocess1', 'postprocess2', 'postprocess1_bias',
                   'postprocess2_bias']:
             if k in tree['postprocessing']:
@@ -1109,11 +1163,41 @@ class WaveNetModel(object):
         dst_frames [B][Fw][Lc] (device) and offset[b] % hop into dst_off."""
         B, F = fr.shape[0], fr.shape[1]
         hop, Fw = self.lc_hop, dst_frames.shape[1]
-        idx = np.minimum((off // hop)[:, None] + np.arange(Fw)[None, :], F - 1)
-        rows = torch.arange(B, device=fr.device)[:, None]
-        sel = fr[rows, torch.as_tensor(idx, device=fr.device)]
-        dst_frames.copy_(sel)
+        if self.lc_ctx is not None:
+            self._stage_context_frames(fr, off, dst_frames)
+        else:
+            idx = np.minimum((off // hop)[:, None] + np.arange(Fw)[None, :],
+                             F - 1)
+            rows = torch.arange(B, device=fr.device)[:, None]
+            sel = fr[rows, torch.as_tensor(idx, device=fr.device)]
+            dst_frames.copy_(sel)
         dst_off.copy_(torch.as_tensor((off % hop).astype(np.int32)))
+
+    def _context_window(self, off, F, Fx):
+        """Frame indices [B][Fx] of the context staging window (frame
+        offset // hop - p on) and whether each lies inside the clip."""
+        idx = (off // self.lc_hop - self.lc_ctx)[:, None] + \
+            np.arange(Fx)[None, :]
+        return idx, (idx >= 0) & (idx < F)
+
+    def _stage_context_frames(self, fr, off, dst):
+        """A context model's staging: dst [B][Fw + 2p][Lc] = frames offset //
+        hop - p on, zero rows outside [0, F)."""
+        B, F = fr.shape[0], fr.shape[1]
+        idx, inside = self._context_window(off, F, dst.shape[1])
+        rows = torch.arange(B, device=fr.device)[:, None]
+        sel = fr[rows, torch.as_tensor(np.clip(idx, 0, F - 1),
+                                       device=fr.device)]
+        keep = torch.as_tensor(inside, device=fr.device)[:, :, None]
+        dst.copy_(torch.where(keep, sel, torch.zeros((), dtype=sel.dtype,
+                                                     device=sel.device)))
+
+    def _lc_context(self, x, ctx, B, st):
+        """ctx [B][Fw][Lc] = the frame-context convolution of the staged
+        frames x [B][Fw + 2p][Lc]."""
+        _lib.call('wn_lc_context_fwd', _lib.ptr(x), x.shape[1],
+                  _lib.ptr(self._seg(self.params, 'lc_ctx')), self.lc_ctx,
+                  self.Lc, _lib.ptr(ctx), ctx.shape[1], B, st)
 
     def _lc_upsample(self, frames, off, B, T, rows, st):
         """rows[B * T][Lcp] = the upsampler on staged frames / offsets."""
@@ -1134,15 +1218,30 @@ class WaveNetModel(object):
             _lib.ptr(ws.lc_da), W64, 0, 0, _lib.ptr(ws.lc_wT), self.Lcp, None,
             None, 0, None, 0, _lib.ptr(ws.lc_drows), self.Lcp, 0, 0, None, N,
             self.Lcp, W64, 0, st), 2.0 * N * W64 * self.Lcp, self._gemm_events)
-        _lib.call('wn_lc_upsample_bwd', _lib.ptr(ws.lc_frames), ws.lc_fw,
-                  _lib.ptr(ws.lc_off), _lib.ptr(self._seg(self.params, 'lc_up')),
-                  ctypes.addressof(self._lc_up_c), len(self.lc_up), self.Lc,
-                  1 if self.use_biases else 0, _lib.ptr(ws.lc_drows), self.Lcp,
-                  ws.B, ws.T, _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
-                  ws.lc_up_stride, st)
+        args = (_lib.ptr(ws.lc_frames), ws.lc_fw, _lib.ptr(ws.lc_off),
+                _lib.ptr(self._seg(self.params, 'lc_up')),
+                ctypes.addressof(self._lc_up_c), len(self.lc_up), self.Lc,
+                1 if self.use_biases else 0, _lib.ptr(ws.lc_drows), self.Lcp,
+                ws.B, ws.T, _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
+                ws.lc_up_stride)
+        if self.lc_ctx is None:
+            _lib.call('wn_lc_upsample_bwd', *args, st)
+        else:
+            # (the same slabs) + d ctx, the gradient at the upsampler's input
+            _lib.call('wn_lc_upsample_bwd_ctx', *args, _lib.ptr(ws.lc_dctx),
+                      _lib.ptr(ws.lc_dpart), st)
         _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
                   ws.lc_up_stride, 1, 0, 0, ws.lc_up_n,
                   _lib.ptr(self._seg(self.grads, 'lc_up')), 0, 1, 0, st)
+        if self.lc_ctx is not None:
+            # d W[k] = sum over frames of x[f + k]^T d ctx[f]
+            _lib.call('wn_lc_context_wgrad', _lib.ptr(ws.lc_xframes),
+                      ws.lc_xframes.shape[1], _lib.ptr(ws.lc_dctx), ws.lc_fw,
+                      self.lc_ctx, self.Lc, ws.B, _lib.ptr(ws.lc_ctx_slabs),
+                      ws.lc_ctx_nslab, ws.lc_ctx_stride, st)
+            _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_ctx_slabs),
+                      ws.lc_ctx_nslab, ws.lc_ctx_stride, 1, 0, 0, ws.lc_ctx_n,
+                      _lib.ptr(self._seg(self.grads, 'lc_ctx')), 0, 1, 0, st)
 
     def upsample_local_condition(self, frames, num_samples, offset=0):
         """The learned upsampler on frame-rate features: frames float
@@ -1166,12 +1265,20 @@ class WaveNetModel(object):
         fr, off = self._lc_frames(frames, offset, B, n,
                                   'upsample_local_condition')
         dev = self.device
-        staged = torch.empty((B, self._lc_frame_window(n), self.Lc),
-                             dtype=torch.float32, device=dev)
+        Fw = self._lc_frame_window(n)
+        staged = torch.empty((B, Fw, self.Lc), dtype=torch.float32, device=dev)
         offs = torch.empty((B,), dtype=torch.int32, device=dev)
-        self._stage_frames(fr, off, n, staged, offs)
+        st = _lib.stream()
+        if self.lc_ctx is not None:
+            # the context convolution of the staged window into `staged`
+            x = torch.empty((B, Fw + 2 * self.lc_ctx, self.Lc),
+                            dtype=torch.float32, device=dev)
+            self._stage_frames(fr, off, n, x, offs)
+            self._lc_context(x, staged, B, st)
+        else:
+            self._stage_frames(fr, off, n, staged, offs)
         rows = torch.empty((B * n, self.Lcp), dtype=torch.float32, device=dev)
-        self._lc_upsample(staged, offs, B, n, rows, _lib.stream())
+        self._lc_upsample(staged, offs, B, n, rows, st)
         out = rows[:, :self.Lc].reshape(B, n, self.Lc).contiguous()
         return out[0] if two_d else out
 
@@ -1777,7 +1884,13 @@ class WaveNetModel(object):
             ws.audio.copy_(audio.reshape(-1))
         ids = self._gc_ids(global_condition_batch, B)
         st = _lib.stream()
-        if self.lc_up:
+        if self.lc_ctx is not None:
+            # frames: the context convolution into ws.lc_frames, then the
+            # upsampler's rows into ws.lc
+            self._stage_frames(lc[0], lc[1], T, ws.lc_xframes, ws.lc_off)
+            self._lc_context(ws.lc_xframes, ws.lc_frames, B, st)
+            self._lc_upsample(ws.lc_frames, ws.lc_off, B, T, ws.lc, st)
+        elif self.lc_up:
             # frames: the rows are the upsampler's, into ws.lc
             self._stage_frames(lc[0], lc[1], T, ws.lc_frames, ws.lc_off)
             self._lc_upsample(ws.lc_frames, ws.lc_off, B, T, ws.lc, st)

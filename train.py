@@ -111,6 +111,11 @@ def get_arguments(argv=None):
                         'with a learned network of transposed convolutions, '
                         'one layer per scale, e.g. 4,5,10 (hop = their '
                         'product; --lc_hop must be absent or equal to it).')
+    p.add_argument('--lc_context', type=int, default=None,
+                   help='Local conditioning: a learned convolution over 2P + 1 '
+                        'frames (P frames either side, channels to channels) '
+                        'in front of the upsampler, 0 <= P <= 8.  Needs '
+                        '--lc_upsample_scales.')
     return p.parse_args(argv)
 
 
@@ -132,6 +137,21 @@ def lc_upsample_scales(args):
                          '(hop = their product, %d)'
                          % (args.lc_hop, args.lc_upsample_scales, hop))
     return scales, hop
+
+
+def lc_context(args):
+    """P of --lc_context (None without it); ValueError without
+    --lc_upsample_scales or out of range."""
+    if args.lc_context is None:
+        return None
+    if args.lc_upsample_scales is None:
+        raise ValueError('--lc_context needs --lc_upsample_scales (it '
+                         'convolves frames)')
+    from wavenet import WaveNetModel
+    if not 0 <= args.lc_context <= WaveNetModel.LC_CONTEXT_MAX:
+        raise ValueError('--lc_context must be from 0 to %d, got %d'
+                         % (WaveNetModel.LC_CONTEXT_MAX, args.lc_context))
+    return args.lc_context
 
 
 def checkpoint_path(logdir, step):
@@ -272,6 +292,7 @@ def main(argv=None):
     args = get_arguments(argv)
     try:
         lc_scales, lc_hop = lc_upsample_scales(args)
+        lc_ctx = lc_context(args)
     except ValueError as e:
         print(str(e))
         return 1
@@ -339,7 +360,8 @@ def main(argv=None):
         global_condition_cardinality=reader.gc_category_cardinality,
         residual_postproc=wavenet_params.get("residual_postproc", False),
         local_condition_channels=args.lc_channels,
-        local_condition_upsample_scales=lc_scales)
+        local_condition_upsample_scales=lc_scales,
+        local_condition_context=lc_ctx)
     l2 = args.l2_regularization_strength or None
     optimizer = optimizer_factory[args.optimizer](
         learning_rate=args.learning_rate, momentum=args.momentum)
