@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import local_condition as lcond
 
 CH = 32
 _EXPIRED = dict(
@@ -251,8 +252,7 @@ def _prime(net, g, n0, groups, Bp):
     ws = net._workspace(1, n0, False)
     for codes, gc, streams, lc in groups:
         ws.q.copy_(codes)
-        if lc is not None:         # the seed's LC rows, as predict_proba
-            ws.lc[:, :net.Lc].copy_(lc.reshape(n0, net.Lc))
+        lcond.fill(net, lc, ws)    # the seed's LC rows, as predict_proba
         net._run_pass('fwd', ws, net._gc_ids(gc, 1),
                       net._step_path(ws, False))
         # (+ the forward launch's poison word: 0, or NaN after an expired wait)
@@ -270,7 +270,7 @@ def _seeded(net, io, n_given, n, pe, prime, run, lc=None):
     n_steps = n_given - 1 + n
     primed = prime and pe == 0 and \
         n_given - 1 >= net.fastgen_prime_forward_min and n > 0 and \
-        (lc is None or net._lc_forward_ok(n_given - 1))
+        (lc is None or lcond.forward_ok(net, n_given - 1))
     if lc is not None:
         run = functools.partial(run, lc=lc[..., n_given - 1:, :] if primed
                                 else lc)
@@ -776,8 +776,9 @@ def generate_batch(net, num_samples, seeds, seed_samples, temperature,
         codes = _batch_codes(net, seed_samples, B)
         if not net.Lc and lc is None:
             return codes, None
-        return codes, net._fastgen_lc(lc, 'generate_batch', codes.shape[1] +
-                                      int(num_samples) - 1, B)
+        return codes, lcond.fastgen_rows(net, lc, 'generate_batch',
+                                         codes.shape[1] + int(num_samples) - 1,
+                                         B)
     sd, (codes, lc), gc, n = _batch_args(net, seeds, per_stream,
                                          global_condition, temperature,
                                          num_samples)
@@ -820,8 +821,8 @@ def continue_generation_batch(net, num_samples, last_samples, seeds,
         last = _batch_last(last_samples, B)
         if not net.Lc and lc is None:
             return last, None
-        return last, net._fastgen_lc(lc, 'continue_generation_batch',
-                                     int(num_samples), B)
+        return last, lcond.fastgen_rows(net, lc, 'continue_generation_batch',
+                                        int(num_samples), B)
     sd, (last, lc), gc, n = _batch_args(net, seeds, per_stream,
                                         global_condition, temperature,
                                         num_samples)

@@ -17,7 +17,6 @@ There is no CPU / PyTorch compute fallback: without the HIP library or a GPU
 every entry point raises.
 """
 import collections
-import ctypes
 import math
 import os
 
@@ -26,6 +25,7 @@ import torch
 
 from . import _lib
 from . import fastgen
+from . import local_condition as lcond
 from .ops import mu_law_encode, mu_law_decode, mu_law_tables
 
 CH = 32                      # channels per activation plane (one block)
@@ -139,23 +139,7 @@ class _Workspace(object):
         alloc('loss_parts', (2 + self.nparts,), fill=0.0)
         alloc('loss', (1,), fill=0.0)
         alloc('proba', (Q,))
-        if net.Lc:
-            # local conditioning: the rows [N][Lc, padded to 4 with zero
-            # columns] and the per-row filter | gate addends of every layer
-            # [N][L][64] (lc x lc_w, the layout wn_stack_fwd_lc reads)
-            alloc('lc', (N, net.Lcp), fill=0.0)
-            alloc('lc_add', (N, L * 64))
-        if net.lc_up:
-            # learned upsampling: the frames each clip needs [B][Fw][Lc]
-            # (frame offset // hop on) and the offsets in the first frame
-            self.lc_fw = net._lc_frame_window(T)
-            alloc('lc_frames', (B, self.lc_fw, net.Lc), fill=0.0)
-            alloc('lc_off', (B,), torch.int32, fill=0)
-        if net.lc_ctx is not None:
-            # frame context: the frames staged with p frames either side
-            # [B][Fw + 2p][Lc]; lc_frames holds the convolution's output
-            alloc('lc_xframes', (B, self.lc_fw + 2 * net.lc_ctx, net.Lc),
-                  fill=0.0)
+        lcond.alloc_workspace(net, self, alloc, False)
         if net.blocked:
             # partial pre-activations of a layer wider than one chunk of
             # channel blocks (wavenet/blocked.py), planes af | ag
@@ -239,32 +223,7 @@ class _Workspace(object):
             self.splits[key] = sp
             need = max(need, sp * lib.wn_gemm_tn_slab_floats(mw, nw))
         need_tn = need
-        if net.Lc:
-            # lc^T da (local-conditioning weight gradients), on the main stream
-            # after the backward stack: the pre-activation gradients [N][L][64]
-            alloc('lc_da', (N, L * 64))
-            sp = lib.wn_gemm_tn_splits(N, net.Lcp, L * 64, 0)
-            self.splits['lc'] = sp
-            need = max(need, sp * lib.wn_gemm_tn_slab_floats(net.Lcp, L * 64))
-        if net.lc_up:
-            # the gradient of the rows d rows = lc_da lc_w^T, and the
-            # upsampler's per-workgroup slabs
-            alloc('lc_wT', (L * 64, net.Lcp))
-            alloc('lc_drows', (N, net.Lcp))
-            self.lc_up_n = net._lc_up_floats()
-            self.lc_up_stride = _align(self.lc_up_n, 4)
-            self.lc_up_nslab = lib.wn_lc_upsample_bwd_slabs(N, self.lc_up_n)
-            alloc('lc_up_slabs', (self.lc_up_nslab, self.lc_up_stride))
-        if net.lc_ctx is not None:
-            # d frames at the upsampler's input [B][Fw][Lc], the upsampler
-            # workgroups' parts of shared frames, the context filter's slabs
-            alloc('lc_dctx', (B, self.lc_fw, net.Lc))
-            alloc('lc_dpart', (self.lc_up_nslab, 2, net.Lc))
-            self.lc_ctx_n = (2 * net.lc_ctx + 1) * net.Lc * net.Lc
-            self.lc_ctx_stride = _align(self.lc_ctx_n, 4)
-            self.lc_ctx_nslab = lib.wn_lc_context_wgrad_slabs(
-                B * self.lc_fw, self.lc_ctx_n)
-            alloc('lc_ctx_slabs', (self.lc_ctx_nslab, self.lc_ctx_stride))
+        need = max(need, lcond.alloc_workspace(net, self, alloc, True))
         # scalar-input causal wgrad: [splits][initial_filter_width][32] slabs
         need = max(need, max(256, self.splits['causal'])
                    * max(32, net.initial_filter_width) * CH)
@@ -354,29 +313,9 @@ class WaveNetModel(object):
         self.residual_postproc = residual_postproc
         # local conditioning (WaveNet paper 2.5): per-sample features lc[b, t]
         # of this many channels, see `loss` / `predict_proba`
-        self.local_condition_channels = local_condition_channels
-        self.Lc = self._check_local_condition_family(
-            local_condition_channels, filter_width, residual_channels,
-            dilation_channels, scalar_input)
-        # (LC weights as [Lcp][L][64]: rows padded to a multiple of 4 for the
-        # GEMMs, zero)
-        self.Lcp = _align(self.Lc, 4) if self.Lc else 0
-        # learned upsampling of frame-rate LC features (transposed
-        # convolutions over time, kernel = stride = s_i, see
-        # upsample_local_condition): the scales, or None (rows at audio rate)
-        self.local_condition_upsample_scales = self._check_lc_upsample(
-            local_condition_upsample_scales, local_condition_channels)
-        self.lc_up = self.local_condition_upsample_scales
-        self.lc_hop = int(np.prod(self.lc_up)) if self.lc_up else 0
-        # (the scales as the host int array the upsampler launches read;
-        # kept alive with the model, recorded launch plans hold its address)
-        self._lc_up_c = (ctypes.c_int * len(self.lc_up))(*self.lc_up) \
-            if self.lc_up else None
-        # frame-context convolution in front of the upsampler (kernel 2p + 1
-        # over frames, Lc -> Lc, no bias): p, or None without one
-        self.local_condition_context = self._check_lc_context(
-            local_condition_context, self.lc_up)
-        self.lc_ctx = self.local_condition_context
+        lcond.configure(self, local_condition_channels,
+                        local_condition_upsample_scales,
+                        local_condition_context)
         # TF's fused softmax-xent back-propagates softmax/(B*T) through the
         # all-zero-label last row of every clip [inferred].
         self.tf_xent_zero_label_quirk = True
@@ -517,86 +456,20 @@ class WaveNetModel(object):
         self.push_ops = []
         self.variables = self._create_variables(seed)
 
+    # local conditioning's limits (checked in wavenet/local_condition.py)
     LC_SUPPORTED = ('local conditioning is supported for residual / dilation '
                     'channels <= 32, filter_width 2 and one-hot input (not '
                     'scalar_input), on the persistent stack launches '
                     '(stack_fwd / stack_bwd = True)')
-
-    @classmethod
-    def _check_local_condition_family(cls, lc, filter_width, R, D, scalar_input):
-        """Number of LC channels (0 without LC); raises before any device is
-        touched for a combination outside the supported family."""
-        if lc is None:
-            return 0
-        if isinstance(lc, bool) or int(lc) != lc or int(lc) <= 0:
-            raise ValueError('local_condition_channels must be a positive int, '
-                             'got %r' % (lc,))
-        why = None
-        if max(int(R), int(D)) > CH:
-            why = 'more than 32 residual / dilation channels'
-        elif int(filter_width) != 2:
-            why = 'filter_width %d' % int(filter_width)
-        elif scalar_input:
-            why = 'scalar_input'
-        if why:
-            raise NotImplementedError('%s: %s' % (why, cls.LC_SUPPORTED))
-        return int(lc)
-
     LC_UPSAMPLE_MAX_LAYERS = 8
     LC_UPSAMPLE_MAX_HOP = 4096
     LC_UPSAMPLE_MAX_CHANNELS = 512     # wn_lc_upsample_* (LCUP_MAX_LC)
-
-    @classmethod
-    def _check_lc_upsample(cls, scales, lc):
-        """The upsampler's scales as a tuple of ints (None without one);
-        raises before any library or device is touched."""
-        if scales is None:
-            return None
-        if lc is None:
-            raise ValueError('local_condition_upsample_scales needs '
-                             'local_condition_channels')
-        try:
-            sc = tuple(scales)
-        except TypeError:
-            raise ValueError('local_condition_upsample_scales must be a tuple '
-                             'of ints, got %r' % (scales,))
-        if not 1 <= len(sc) <= cls.LC_UPSAMPLE_MAX_LAYERS or any(
-                isinstance(s, (bool, np.bool_)) or
-                not isinstance(s, (int, np.integer)) or int(s) < 2
-                for s in sc):
-            raise ValueError('local_condition_upsample_scales must be 1 to %d '
-                             'ints >= 2, got %r'
-                             % (cls.LC_UPSAMPLE_MAX_LAYERS, scales))
-        sc = tuple(int(s) for s in sc)
-        if int(np.prod(sc)) > cls.LC_UPSAMPLE_MAX_HOP:
-            raise ValueError('local_condition_upsample_scales: the hop (their '
-                             'product, %d) must be at most %d'
-                             % (int(np.prod(sc)), cls.LC_UPSAMPLE_MAX_HOP))
-        if int(lc) > cls.LC_UPSAMPLE_MAX_CHANNELS:
-            raise NotImplementedError(
-                'the local-conditioning upsampler supports at most %d channels '
-                '(local_condition_channels = %d)'
-                % (cls.LC_UPSAMPLE_MAX_CHANNELS, int(lc)))
-        return sc
-
     LC_CONTEXT_MAX = 8                 # wn_lc_context_* (LCCTX_MAX_P)
-
-    @classmethod
-    def _check_lc_context(cls, p, scales):
-        """The context half-width p as an int (None without one); raises
-        before any library or device is touched."""
-        if p is None:
-            return None
-        if isinstance(p, (bool, np.bool_)) or \
-                not isinstance(p, (int, np.integer)) or \
-                not 0 <= int(p) <= cls.LC_CONTEXT_MAX:
-            raise ValueError('local_condition_context must be an int from 0 to '
-                             '%d, got %r' % (cls.LC_CONTEXT_MAX, p))
-        if not scales:
-            raise ValueError('local_condition_context needs '
-                             'local_condition_upsample_scales (it convolves '
-                             'frames; repetition-row models take rows)')
-        return int(p)
+    # (LC checks under the names the host tests call them by)
+    _lc_rows = lcond.rows
+    _lc_input = lcond.check
+    _lc_frames = lcond.frames
+    _lc_forward_ok = lcond.forward_ok
 
     @property
     def stack_variant(self):
@@ -645,7 +518,7 @@ class WaveNetModel(object):
         if self.lc_up:
             # the upsampler: filters [s_i][3] of every layer, then (biases)
             # one scalar per layer.  Also in front of skip_w
-            add('lc_up', self._lc_up_floats())
+            add('lc_up', lcond.up_floats(self))
         if self.lc_ctx is not None:
             # the frame-context filter [2p + 1][Lc][Lc].  Also in front of
             # skip_w
@@ -663,10 +536,6 @@ class WaveNetModel(object):
         self.gradients = self._views(self.grads)
         self._init_variables(seed)
         return self.variables
-
-    def _lc_up_floats(self):
-        return 3 * sum(self.lc_up) + (len(self.lc_up) if self.use_biases
-                                      else 0)
 
     def _seg(self, flat, name):
         o, n = self.segments[name]
@@ -1035,214 +904,6 @@ class WaveNetModel(object):
                              % (ids.numel(), B))
         return ids.contiguous()
 
-    def _lc_rows(self, local_condition, B, T, what):
-        """Validate a call's local-conditioning rows ([B, T, Lc], float) and
-        that the persistent 32-row stack launches, the only ones an LC model
-        runs, cover the call -- before anything is allocated or launched.
-        Returns the rows as float32 on the device (None without LC)."""
-        if not self.Lc:
-            if local_condition is not None:
-                raise ValueError('%s: this model was built without local '
-                                 'conditioning (local_condition_channels=None)'
-                                 % what)
-            return None
-        if local_condition is None:
-            raise ValueError('%s: the model was built with local conditioning '
-                             '(%d channels); an lc batch [%d, %d, %d] is required'
-                             % (what, self.Lc, B, T, self.Lc))
-        lc = local_condition
-        if not isinstance(lc, torch.Tensor):
-            lc = torch.as_tensor(np.asarray(lc, dtype=np.float32))
-        if B == 1 and lc.dim() == 2:
-            lc = lc.unsqueeze(0)
-        if tuple(lc.shape) != (B, T, self.Lc):
-            raise ValueError('%s: local conditioning must have shape [B, T, Lc] '
-                             '= [%d, %d, %d] (row t beside input sample t), got %s'
-                             % (what, B, T, self.Lc, tuple(lc.shape)))
-        if lc.is_floating_point() is False:
-            raise ValueError('%s: local conditioning must be floating point'
-                             % what)
-        if not (self.stack_fwd and self.stack_bwd):
-            raise NotImplementedError(
-                'stack_fwd / stack_bwd = False with local conditioning: '
-                + self.LC_SUPPORTED)
-        if self._layer_path() != 'layer':       # (generic_layers forced)
-            raise NotImplementedError(self.LC_SUPPORTED)
-        if not self._stack_ok(B * T):
-            raise NotImplementedError(
-                'local conditioning needs B * T < 2^24 and at most 256 '
-                'layers (the persistent stack launches)')
-        return lc.to(device=self.device, dtype=torch.float32)
-
-    def _lc_input(self, local_condition, offset, B, T, what):
-        """A loss call's LC input: rows (_lc_rows), or for a model with the
-        upsampler (frames on the host or device [B, F, Lc], offsets int64
-        [B] on the host), checked before anything is launched."""
-        if not self.lc_up:
-            if not (isinstance(offset, (int, np.integer)) and
-                    not isinstance(offset, bool) and int(offset) == 0):
-                raise ValueError('%s: local_condition_offset is for models '
-                                 'built with local_condition_upsample_scales'
-                                 % what)
-            return self._lc_rows(local_condition, B, T, what)
-        fr, off = self._lc_frames(local_condition, offset, B, T, what)
-        self._lc_launch_checks(B, T)
-        return fr, off
-
-    def _lc_launch_checks(self, B, T):
-        if not (self.stack_fwd and self.stack_bwd):
-            raise NotImplementedError(
-                'stack_fwd / stack_bwd = False with local conditioning: '
-                + self.LC_SUPPORTED)
-        if self._layer_path() != 'layer':       # (generic_layers forced)
-            raise NotImplementedError(self.LC_SUPPORTED)
-        if not self._stack_ok(B * T):
-            raise NotImplementedError(
-                'local conditioning needs B * T < 2^24 and at most 256 '
-                'layers (the persistent stack launches)')
-
-    def _lc_frame_window(self, T):
-        """Frames a clip of T samples touches at most (any offset)."""
-        return (T + self.lc_hop - 2) // self.lc_hop + 1
-
-    def _lc_frames(self, frames, offset, B, T, what):
-        """Validate frame-rate LC features [B, F, Lc] (or [F, Lc] with B = 1)
-        and the offsets (an int or B non-negative ints).  Returns the frames
-        as a float tensor where the caller had them and the offsets as int64
-        numpy [B]."""
-        Lc, hop = self.Lc, self.lc_hop
-        shape = '[B, F, Lc] = [%d, F, %d] with F >= (offset + %d - 1) // %d + 1' \
-            % (B, Lc, T, hop)
-        if frames is None:
-            raise ValueError('%s: the model upsamples local conditioning '
-                             '(hop %d); frames %s are required'
-                             % (what, hop, shape))
-        fr = frames
-        if not isinstance(fr, torch.Tensor):
-            fr = np.asarray(fr)
-            if fr.dtype == object or not np.issubdtype(fr.dtype, np.floating):
-                raise ValueError('%s: local conditioning frames must be a '
-                                 'float array %s' % (what, shape))
-            fr = torch.from_numpy(fr)
-        if not fr.is_floating_point():
-            raise ValueError('%s: local conditioning frames must be floating '
-                             'point' % what)
-        if B == 1 and fr.dim() == 2:
-            fr = fr.unsqueeze(0)
-        if fr.dim() != 3 or fr.shape[0] != B or fr.shape[2] != Lc or \
-                fr.shape[1] < 1:
-            raise ValueError('%s: local conditioning frames must have shape %s,'
-                             ' got %s' % (what, shape, tuple(fr.shape)))
-        if isinstance(offset, torch.Tensor):
-            offset = offset.detach().cpu().numpy()
-        off = np.asarray(offset)
-        if off.dtype == object or off.dtype == np.bool_ or \
-                not np.issubdtype(off.dtype, np.integer):
-            raise ValueError('%s: local_condition_offset must be an int or %d '
-                             'ints, got %r' % (what, B, offset))
-        if off.ndim == 0:
-            off = np.full(B, int(off), np.int64)
-        if off.shape != (B,):
-            raise ValueError('%s: local_condition_offset must be an int or %d '
-                             'ints, got shape %s' % (what, B, off.shape))
-        off = off.astype(np.int64)
-        if (off < 0).any():
-            raise ValueError('%s: local_condition_offset must be non-negative, '
-                             'got %s' % (what, off.tolist()))
-        need = int(((off + T - 1) // hop).max()) + 1
-        if fr.shape[1] < need:
-            raise ValueError('%s: %d frames do not cover position offset + T - '
-                             '1 = %d: local conditioning frames must have shape '
-                             '%s (here F >= %d), got %s'
-                             % (what, fr.shape[1], int((off + T - 1).max()),
-                                shape, need, tuple(fr.shape)))
-        return fr, off
-
-    def _stage_frames(self, fr, off, T, dst_frames, dst_off):
-        """The frames clip b touches, frame offset[b] // hop on, into
-        dst_frames [B][Fw][Lc] (device) and offset[b] % hop into dst_off."""
-        B, F = fr.shape[0], fr.shape[1]
-        hop, Fw = self.lc_hop, dst_frames.shape[1]
-        if self.lc_ctx is not None:
-            self._stage_context_frames(fr, off, dst_frames)
-        else:
-            idx = np.minimum((off // hop)[:, None] + np.arange(Fw)[None, :],
-                             F - 1)
-            rows = torch.arange(B, device=fr.device)[:, None]
-            sel = fr[rows, torch.as_tensor(idx, device=fr.device)]
-            dst_frames.copy_(sel)
-        dst_off.copy_(torch.as_tensor((off % hop).astype(np.int32)))
-
-    def _context_window(self, off, F, Fx):
-        """Frame indices [B][Fx] of the context staging window (frame
-        offset // hop - p on) and whether each lies inside the clip."""
-        idx = (off // self.lc_hop - self.lc_ctx)[:, None] + \
-            np.arange(Fx)[None, :]
-        return idx, (idx >= 0) & (idx < F)
-
-    def _stage_context_frames(self, fr, off, dst):
-        """A context model's staging: dst [B][Fw + 2p][Lc] = frames offset //
-        hop - p on, zero rows outside [0, F)."""
-        B, F = fr.shape[0], fr.shape[1]
-        idx, inside = self._context_window(off, F, dst.shape[1])
-        rows = torch.arange(B, device=fr.device)[:, None]
-        sel = fr[rows, torch.as_tensor(np.clip(idx, 0, F - 1),
-                                       device=fr.device)]
-        keep = torch.as_tensor(inside, device=fr.device)[:, :, None]
-        dst.copy_(torch.where(keep, sel, torch.zeros((), dtype=sel.dtype,
-                                                     device=sel.device)))
-
-    def _lc_context(self, x, ctx, B, st):
-        """ctx [B][Fw][Lc] = the frame-context convolution of the staged
-        frames x [B][Fw + 2p][Lc]."""
-        _lib.call('wn_lc_context_fwd', _lib.ptr(x), x.shape[1],
-                  _lib.ptr(self._seg(self.params, 'lc_ctx')), self.lc_ctx,
-                  self.Lc, _lib.ptr(ctx), ctx.shape[1], B, st)
-
-    def _lc_upsample(self, frames, off, B, T, rows, st):
-        """rows[B * T][Lcp] = the upsampler on staged frames / offsets."""
-        _lib.call('wn_lc_upsample_fwd', _lib.ptr(frames), frames.shape[1],
-                  _lib.ptr(off), _lib.ptr(self._seg(self.params, 'lc_up')),
-                  ctypes.addressof(self._lc_up_c), len(self.lc_up), self.Lc,
-                  1 if self.use_biases else 0, _lib.ptr(rows), self.Lcp, B, T,
-                  st)
-
-    def _lc_upsample_bwd(self, ws, st):
-        """The upsampler's gradients: d rows [N][Lcp] = lc_da lc_w^T (the
-        transposed LC weights, one NN GEMM), then every workgroup's
-        (layer, slot, tap) partials of its rows, summed in a fixed order."""
-        L, N, W64 = self.L, ws.N, self.L * 64
-        _lib.call('wn_transpose', _lib.ptr(self._seg(self.params, 'lc_w')),
-                  self.Lcp, W64, W64, _lib.ptr(ws.lc_wT), self.Lcp, st)
-        _lib.call_timed('wn_gemm_nn', (
-            _lib.ptr(ws.lc_da), W64, 0, 0, _lib.ptr(ws.lc_wT), self.Lcp, None,
-            None, 0, None, 0, _lib.ptr(ws.lc_drows), self.Lcp, 0, 0, None, N,
-            self.Lcp, W64, 0, st), 2.0 * N * W64 * self.Lcp, self._gemm_events)
-        args = (_lib.ptr(ws.lc_frames), ws.lc_fw, _lib.ptr(ws.lc_off),
-                _lib.ptr(self._seg(self.params, 'lc_up')),
-                ctypes.addressof(self._lc_up_c), len(self.lc_up), self.Lc,
-                1 if self.use_biases else 0, _lib.ptr(ws.lc_drows), self.Lcp,
-                ws.B, ws.T, _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
-                ws.lc_up_stride)
-        if self.lc_ctx is None:
-            _lib.call('wn_lc_upsample_bwd', *args, st)
-        else:
-            # (the same slabs) + d ctx, the gradient at the upsampler's input
-            _lib.call('wn_lc_upsample_bwd_ctx', *args, _lib.ptr(ws.lc_dctx),
-                      _lib.ptr(ws.lc_dpart), st)
-        _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
-                  ws.lc_up_stride, 1, 0, 0, ws.lc_up_n,
-                  _lib.ptr(self._seg(self.grads, 'lc_up')), 0, 1, 0, st)
-        if self.lc_ctx is not None:
-            # d W[k] = sum over frames of x[f + k]^T d ctx[f]
-            _lib.call('wn_lc_context_wgrad', _lib.ptr(ws.lc_xframes),
-                      ws.lc_xframes.shape[1], _lib.ptr(ws.lc_dctx), ws.lc_fw,
-                      self.lc_ctx, self.Lc, ws.B, _lib.ptr(ws.lc_ctx_slabs),
-                      ws.lc_ctx_nslab, ws.lc_ctx_stride, st)
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_ctx_slabs),
-                      ws.lc_ctx_nslab, ws.lc_ctx_stride, 1, 0, 0, ws.lc_ctx_n,
-                      _lib.ptr(self._seg(self.grads, 'lc_ctx')), 0, 1, 0, st)
-
     def upsample_local_condition(self, frames, num_samples, offset=0):
         """The learned upsampler on frame-rate features: frames float
         [B, F, Lc] (or [F, Lc]) -> device float32 rows [B, num_samples, Lc]
@@ -1250,37 +911,7 @@ class WaveNetModel(object):
         (offset: an int or B non-negative ints).  The same kernel as the
         training forward: a row's bits depend on its frame, its slot and the
         weights only.  The rows feed predict_proba and fast generation."""
-        self._check_supported()
-        if not self.lc_up:
-            raise ValueError('upsample_local_condition: the model was built '
-                             'without local_condition_upsample_scales')
-        n = int(num_samples)
-        if n < 1:
-            raise ValueError('upsample_local_condition: num_samples must be '
-                             'positive, got %r' % (num_samples,))
-        if not isinstance(frames, torch.Tensor):
-            frames = np.asarray(frames)
-        two_d = frames.ndim == 2
-        B = 1 if two_d or frames.ndim < 2 else frames.shape[0]
-        fr, off = self._lc_frames(frames, offset, B, n,
-                                  'upsample_local_condition')
-        dev = self.device
-        Fw = self._lc_frame_window(n)
-        staged = torch.empty((B, Fw, self.Lc), dtype=torch.float32, device=dev)
-        offs = torch.empty((B,), dtype=torch.int32, device=dev)
-        st = _lib.stream()
-        if self.lc_ctx is not None:
-            # the context convolution of the staged window into `staged`
-            x = torch.empty((B, Fw + 2 * self.lc_ctx, self.Lc),
-                            dtype=torch.float32, device=dev)
-            self._stage_frames(fr, off, n, x, offs)
-            self._lc_context(x, staged, B, st)
-        else:
-            self._stage_frames(fr, off, n, staged, offs)
-        rows = torch.empty((B * n, self.Lcp), dtype=torch.float32, device=dev)
-        self._lc_upsample(staged, offs, B, n, rows, st)
-        out = rows[:, :self.Lc].reshape(B, n, self.Lc).contiguous()
-        return out[0] if two_d else out
+        return lcond.upsample(self, frames, num_samples, offset)
 
     def _layer_block(self, flat, l):
         o, _ = self.segments['layers']
@@ -1777,20 +1408,7 @@ class WaveNetModel(object):
                 _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, sl, 1, 0,
                           0, Q * CH, _lib.ptr(gc_[tap * Q * CH:]), 0, 1, 0, st)
         if self.Lc:
-            # local conditioning: d lc_w [Lcp][L * 64] = lc^T [da_f | da_g of
-            # every layer] (the rows the backward stack stored)
-            W64 = L * 64
-            sp = ws.splits['lc']
-            _lib.call_timed('wn_gemm_tn', (
-                _lib.ptr(ws.lc), self.Lcp, 0, 0, None, 0, T, _lib.ptr(ws.lc_da),
-                W64, _lib.ptr(ws.slabs), sp, N, self.Lcp, W64, 0, st),
-                2.0 * N * W64 * self.Lcp, self._gemm_events)
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp,
-                      lib.wn_gemm_tn_slab_floats(self.Lcp, W64), 1, 0, 0,
-                      self.Lcp * W64, _lib.ptr(self._seg(Gr, 'lc_w')), 0, 1, 0,
-                      st)
-        if self.lc_up:
-            self._lc_upsample_bwd(ws, st)
+            lcond.backward(self, ws, st)
         if ws.dsum is not None:
             _lib.call('wn_gc_grad', _lib.ptr(self._layer_block(P, 0)),
                       self.layer_stride, self.OFF_GC, self.G,
@@ -1843,27 +1461,28 @@ class WaveNetModel(object):
         if not isinstance(a, torch.Tensor):
             a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
-        lc = self._lc_input(local_condition_batch, local_condition_offset, B,
-                            a.shape[1], 'loss')
-        q = mu_law_encode(a, self.Q)
-        return self.loss_from_codes(q, global_condition_batch,
-                                    l2_regularization_strength, backward,
-                                    audio=a, local_condition_batch=(
-                                        local_condition_batch if self.lc_up
-                                        else lc),
-                                    local_condition_offset=local_condition_offset)
+        lc = lcond.check(self, local_condition_batch, local_condition_offset,
+                         B, a.shape[1], 'loss')
+        return self._loss(mu_law_encode(a, self.Q), global_condition_batch,
+                          l2_regularization_strength, backward, a, lc)
 
     def loss_from_codes(self, q, global_condition_batch=None,
                         l2_regularization_strength=None, backward=True,
                         audio=None, *, local_condition_batch=None,
                         local_condition_offset=0):
         self._check_supported()
-        B = self.batch_size
-        q = q.reshape(B, -1)
-        T = q.shape[1]
+        q = q.reshape(self.batch_size, -1)
+        lc = lcond.check(self, local_condition_batch, local_condition_offset,
+                         self.batch_size, q.shape[1], 'loss')
+        return self._loss(q, global_condition_batch,
+                          l2_regularization_strength, backward, audio, lc)
+
+    def _loss(self, q, global_condition_batch, l2_regularization_strength,
+              backward, audio, lc):
+        """loss_from_codes on codes q [B, T] with the LC input checked
+        (local_condition.check)."""
+        B, T = q.shape
         N = B * T
-        lc = self._lc_input(local_condition_batch, local_condition_offset, B,
-                            T, 'loss')
         ws = self._workspace(B, T, backward)
         if backward and self._tail_work is not None:
             # the previous backward pass started its tail all-reduce and no
@@ -1884,18 +1503,7 @@ class WaveNetModel(object):
             ws.audio.copy_(audio.reshape(-1))
         ids = self._gc_ids(global_condition_batch, B)
         st = _lib.stream()
-        if self.lc_ctx is not None:
-            # frames: the context convolution into ws.lc_frames, then the
-            # upsampler's rows into ws.lc
-            self._stage_frames(lc[0], lc[1], T, ws.lc_xframes, ws.lc_off)
-            self._lc_context(ws.lc_xframes, ws.lc_frames, B, st)
-            self._lc_upsample(ws.lc_frames, ws.lc_off, B, T, ws.lc, st)
-        elif self.lc_up:
-            # frames: the rows are the upsampler's, into ws.lc
-            self._stage_frames(lc[0], lc[1], T, ws.lc_frames, ws.lc_off)
-            self._lc_upsample(ws.lc_frames, ws.lc_off, B, T, ws.lc, st)
-        elif lc is not None:
-            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
+        lcond.fill(self, lc, ws)
         # (L2 adds lambda * params to the WHOLE bucket after the backward
         # pass: the tail must not have been summed over ranks before that)
         path = self._step_path(ws, backward,
@@ -1975,15 +1583,14 @@ class WaveNetModel(object):
             w = torch.as_tensor(np.asarray(w))
         w = w.to(device=self.device, dtype=torch.int32).reshape(B, -1)
         T = w.shape[1]
-        lc = self._lc_rows(local_condition, B, T, 'predict_proba')
+        lc = lcond.rows(self, local_condition, B, T, 'predict_proba')
         ws = self._workspace(B, T, False)
         ws.q.copy_(w.reshape(-1))
         if self.scalar_input:
             # decode the codes back to floats in [-1, 1] (model.py:570-576)
             ws.audio.copy_(mu_law_decode(w, self.Q).reshape(-1))
         ids = self._gc_ids(global_condition, B)
-        if lc is not None:
-            ws.lc[:, :self.Lc].copy_(lc.reshape(ws.N, self.Lc))
+        lcond.fill(self, lc, ws)
         self._run_pass('fwd', ws, ids, self._step_path(ws, False))
         out = torch.empty(self.Q, dtype=torch.float32, device=self.device)
         _lib.call('wn_softmax64_row', _lib.ptr(ws.logits[B * T - 1]), self.Q,
@@ -1995,69 +1602,6 @@ class WaveNetModel(object):
     # ------------------------------------------ fast generation (fastgen.py)
     FASTGEN_MAX_CHANNELS = 1024    # wn_fastgen_run_wide (FGW_MAXC)
     FASTGEN_BATCH_MAX = 256        # wn_fastgen_batch_* (FGB_MAXB)
-
-    def _no_lc_fastgen(self, what):
-        if self.Lc:
-            raise NotImplementedError(
-                '%s: an LC model generates fast with local_condition=... '
-                '(one row per input position the call steps through), or '
-                'naively with predict_proba(..., local_condition=...) '
-                '(generate.py --fast_generation false)%s'
-                % (what, '' if what != 'reset_generator' else
-                   "; reset an LC model's generator with prime_generator([], "
-                   'local_condition=np.zeros((0, Lc)))'))
-
-    def _lc_forward_ok(self, n0):
-        """The forward pass over n0 seed codes (forward priming) carries the
-        LC rows: it is the persistent stack launch wn_stack_fwd_lc, as in
-        predict_proba.  Otherwise the seed is stepped through."""
-        return bool(self.stack_fwd and self.stack_bwd and
-                    self._stack_ok(n0))
-
-    def _fastgen_lc(self, local_condition, what, T, B=None):
-        """The fast entry points' LC rows, checked before any device work:
-        None without LC; else a float tensor where the caller had them,
-        [T, Lc] (B None) or [B or 1, T, Lc] (B streams: one set per stream,
-        or one shared).  fastgen moves them to the device once per call."""
-        if not self.Lc:
-            if local_condition is not None:
-                raise ValueError('%s: this model was built without local '
-                                 'conditioning (local_condition_channels=None)'
-                                 % what)
-            return None
-        if local_condition is None:
-            self._no_lc_fastgen(what)
-        if self.S > 512 or self.Q > 512 or self.L > 64:
-            raise NotImplementedError(
-                '%s: fast generation with local conditioning supports at most '
-                '512 skip / quantization channels and 64 layers (this model: '
-                'S = %d, Q = %d, L = %d); use predict_proba'
-                % (what, self.S, self.Q, self.L))
-        lc = local_condition
-        if not isinstance(lc, torch.Tensor):
-            lc = np.asarray(lc)
-            if lc.dtype == object:
-                raise ValueError('%s: local_condition must be a float array'
-                                 % what)
-            lc = torch.from_numpy(lc)
-        if not lc.is_floating_point():
-            raise ValueError('%s: local_condition must be floating point'
-                             % what)
-        shape, Lc = tuple(lc.shape), self.Lc
-        if B is None:
-            if shape != (T, Lc):
-                raise ValueError('%s: local_condition must have shape [%d, %d] '
-                                 '(one row per input position), got %s'
-                                 % (what, T, Lc, shape))
-        else:
-            if shape == (T, Lc):
-                lc = lc.unsqueeze(0)
-            elif shape != (B, T, Lc):
-                raise ValueError('%s: local_condition must have shape '
-                                 '[%d, %d, %d] or [%d, %d] (shared by all '
-                                 'streams), got %s'
-                                 % (what, B, T, Lc, T, Lc, shape))
-        return lc
 
     def predict_proba_incremental(self, waveform, global_condition=None,
                                   name='wavenet', push=True, *,
@@ -2076,7 +1620,7 @@ class WaveNetModel(object):
         if self.Lc and lc is not None and np.ndim(lc) == 1:
             lc = lc.reshape(1, -1) if isinstance(lc, torch.Tensor) \
                 else np.asarray(lc).reshape(1, -1)
-        lc = self._fastgen_lc(lc, 'predict_proba_incremental', 1)
+        lc = lcond.fastgen_rows(self, lc, 'predict_proba_incremental', 1)
         return fastgen.predict_proba_incremental(self, waveform,
                                                  global_condition, push, lc)
 
@@ -2084,7 +1628,7 @@ class WaveNetModel(object):
         """net.init_ops: refill every queue with zeros (model.py:457-479).
         An LC model refuses it: its generator is reset with
         prime_generator([], local_condition=np.zeros((0, Lc)))."""
-        self._no_lc_fastgen('reset_generator')
+        lcond.refuse_fastgen(self, 'reset_generator')
         fastgen.generator(self, None)
         fastgen.reset(self)
 
@@ -2103,8 +1647,9 @@ class WaveNetModel(object):
         reset internally (reset_generator itself refuses LC models)."""
         lc = None
         if self.Lc or local_condition is not None:
-            lc = self._fastgen_lc(local_condition, 'generate',
-                                  _n_codes(seed_samples) + int(num_samples) - 1)
+            lc = lcond.fastgen_rows(self, local_condition, 'generate',
+                                    _n_codes(seed_samples) + int(num_samples)
+                                    - 1)
         return fastgen.generate(self, num_samples, seed_samples, temperature,
                                 global_condition, seed, return_proba_every,
                                 lc)
@@ -2120,10 +1665,10 @@ class WaveNetModel(object):
         local_condition (LC models only, required there): float
         [len(codes), Lc], row i beside codes[i]; with no codes and
         np.zeros((0, Lc)) this resets an LC model's generator."""
-        lc = self._fastgen_lc(local_condition, 'prime_generator',
-                              _n_codes(codes))
+        lc = lcond.fastgen_rows(self, local_condition, 'prime_generator',
+                                _n_codes(codes))
         if lc is not None and lc.shape[0] > 0 and \
-                not self._lc_forward_ok(lc.shape[0]):
+                not lcond.forward_ok(self, lc.shape[0]):
             raise NotImplementedError(
                 'prime_generator: the forward pass that primes an LC model '
                 'is the persistent stack launch (wn_stack_fwd_lc): '
@@ -2141,8 +1686,8 @@ class WaveNetModel(object):
         [num_samples, Lc]; row 0 sits beside `last_sample`, row k beside new
         code k - 1.  generate(a) then continue_generation(b) on consecutive
         rows is the process of one generate(a + b)."""
-        lc = self._fastgen_lc(local_condition, 'continue_generation',
-                              int(num_samples))
+        lc = lcond.fastgen_rows(self, local_condition, 'continue_generation',
+                                int(num_samples))
         return fastgen.continue_generation(self, num_samples, last_sample,
                                            temperature, global_condition, seed,
                                            lc)
@@ -2164,7 +1709,7 @@ class WaveNetModel(object):
         [n + num_samples - 1, Lc] shared by all streams; rows as generate's."""
         # (the rows are checked in _batch_args's order, beside the seed codes)
         if self.Lc and local_condition is None:
-            self._no_lc_fastgen('generate_batch')
+            lcond.refuse_fastgen(self, 'generate_batch')
         return fastgen.generate_batch(self, num_samples, seeds, seed_samples,
                                       temperature, global_condition,
                                       return_proba_every, local_condition)
@@ -2182,7 +1727,7 @@ class WaveNetModel(object):
         [B, num_samples, Lc] or [num_samples, Lc], rows as
         continue_generation's."""
         if self.Lc and local_condition is None:
-            self._no_lc_fastgen('continue_generation_batch')
+            lcond.refuse_fastgen(self, 'continue_generation_batch')
         return fastgen.continue_generation_batch(
             self, num_samples, last_samples, seeds, temperature,
             global_condition, return_proba_every, local_condition)

@@ -9,6 +9,11 @@ tests/test_gpu_parallel.py, never collected by pytest).
                pass) for `steps` steps and rank 0 saves the parameters.
                spec['lc'] = Lc: a local-conditioning model, every rank on its
                shard of one [steps, B, T, Lc] feature batch.
+  mode frames: `world` ranks as in dp, on the learned LC upsampler
+               (spec['scales']) and, given spec['p'], the frame-context
+               convolution: every rank trains on its shard of one batch of
+               frames and offsets and saves its own parameters
+               (tests/test_gpu_lc_upsample.py, test_gpu_lc_context.py).
   mode nccl1 : world_size-1 process group over backend "nccl" (= RCCL):
                broadcast of net.params and all-reduce of net.grads go through
                the RCCL code path on the device bucket.
@@ -25,11 +30,47 @@ sys.path.insert(0, HERE)
 from util import O, MID, cfg_with, build_pair  # noqa: E402
 
 
+def frames(spec, rank, world):
+    from util import model_kwargs
+    from wavenet import WaveNetModel, parallel, optimizer_factory
+    B, T, steps, Lc = spec['B'], spec['T'], spec['steps'], spec['lc']
+    scales = tuple(spec['scales'])
+    hop = int(np.prod(scales))
+    cfg = cfg_with(MID, batch_size=B // world, use_biases=True)
+    net = WaveNetModel(seed=5, local_condition_channels=Lc,
+                       local_condition_upsample_scales=scales,
+                       local_condition_context=spec.get('p'),
+                       **model_kwargs(cfg))
+    rng = np.random.default_rng(17)
+    audio = rng.uniform(-1, 1, (steps, B, T)).astype(np.float32)
+    F = (T + 3 * hop) // hop + 1
+    fr = rng.standard_normal((steps, B, F, Lc)).astype(np.float32)
+    offs = rng.integers(0, 2 * hop, (steps, B))
+    parallel.broadcast_parameters(net)
+    opt = optimizer_factory['adam'](learning_rate=spec['lr'], momentum=0.9)
+    lo, hi = parallel.shard_range(B, rank, world)
+    net.dp_overlap_allreduce = bool(spec.get('overlap', False))
+    for s in range(steps):
+        loss = net.loss(audio[s, lo:hi], local_condition_batch=fr[s, lo:hi],
+                        local_condition_offset=offs[s, lo:hi])
+        opt.minimize(loss)
+    torch.cuda.synchronize()
+    np.savez(spec['out'] % rank, params=net.params.cpu().numpy(),
+             **{k: net._seg(net.params, k).cpu().numpy()
+                for k in ('lc_up', 'lc_ctx') if k in net.segments})
+
+
 def main():
     spec = json.loads(sys.argv[1])
     from wavenet import parallel, optimizer_factory
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(local % torch.cuda.device_count())
+    if spec['mode'] == 'frames':
+        frames(spec, rank, world)
+        if parallel.is_distributed():
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
     B, T, steps = spec['B'], spec['T'], spec['steps']
     cfg = cfg_with(MID, batch_size=B // world, **spec.get('cfg', {}))
     Lc = spec.get('lc')

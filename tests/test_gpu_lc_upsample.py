@@ -334,8 +334,8 @@ def test_two_ranks_keep_identical_upsampler_weights(hip_lib, tmp_path):
     port = s.getsockname()[1]
     s.close()
     out = str(tmp_path / 'rank%d.npz')
-    spec = dict(B=4, T=300, steps=3, lc=12, scales=[4, 5], lr=1e-2,
-                overlap=True, out=out)
+    spec = dict(mode='frames', B=4, T=300, steps=3, lc=12, scales=[4, 5],
+                lr=1e-2, overlap=True, out=out)
     procs = []
     for r in range(2):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE='2',
@@ -343,7 +343,7 @@ def test_two_ranks_keep_identical_upsampler_weights(hip_lib, tmp_path):
                    HSA_ENABLE_IPC_MODE_LEGACY='0', WN_SHARE_GPU='1',
                    WN_DIST_BACKEND='gloo')
         procs.append(subprocess.Popen(
-            [sys.executable, os.path.join(HERE, 'dp_lc_up_worker.py'),
+            [sys.executable, os.path.join(HERE, 'dp_worker.py'),
              json.dumps(spec)], env=env, stdout=subprocess.PIPE,
             stderr=subprocess.STDOUT))
     outs = []

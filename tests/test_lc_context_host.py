@@ -157,19 +157,31 @@ def test_ref_identity_is_the_frames():
     assert torch.equal(lc_ctx_ref.context(frames, W), frames)
 
 
-def test_stage_frames_window():
+def _staged(net, fr, off, T, Fx):
+    """local_condition.stage over the window of offsets `off` (no frame
+    cover check: the window runs past the clip on purpose)."""
+    from wavenet import local_condition
+    win = local_condition.window(net, off, fr.shape[1], T)
+    dst = torch.full((fr.shape[0], Fx, fr.shape[2]), -1.0)
+    dst_off = torch.zeros(fr.shape[0], dtype=torch.int32)
+    local_condition.stage(net, local_condition.Frames(fr, off, T, *win), dst,
+                          dst_off)
+    return dst, dst_off, win
+
+
+def test_stage_frames_fill_rules():
+    """Both fill rules of the staging window: zero rows outside the clip
+    with context (p = 0 included), the clamp to frame F - 1 without."""
+    from wavenet import local_condition
     net = _net(lc=3, scales=(2, 5), p=2)          # hop 10
     fr = torch.arange(2 * 12 * 3, dtype=torch.float32).view(2, 12, 3) + 1
     T = 35
-    Fw = net._lc_frame_window(T)
-    assert Fw == 5
-    dst = torch.full((2, Fw + 4, 3), -1.0)
-    off = torch.zeros(2, dtype=torch.int32)
+    Fw = local_condition.frame_window(net, T)
+    assert Fw == 5                                 # (35 + 8) // 10 + 1
     # clip 0 near offset 0: window frames -2 .. 6; clip 1 near its last
     # frame: offset 87 -> frames 6 .. 14 of 12
-    net._stage_frames(fr, np.array([0, 87]), T, dst, off)
+    dst, off, (idx, inside) = _staged(net, fr, np.array([0, 87]), T, Fw + 4)
     assert off.tolist() == [0, 7]
-    idx, inside = net._context_window(np.array([0, 87]), 12, Fw + 4)
     assert idx.tolist() == [list(range(-2, 7)), list(range(6, 15))]
     assert inside[0].tolist() == [False] * 2 + [True] * 7
     assert inside[1].tolist() == [True] * 6 + [False] * 3
@@ -179,15 +191,17 @@ def test_stage_frames_window():
     assert torch.equal(dst[1, 6:], torch.zeros(3, 3))
     # p = 0: the window without context, zero rows past the clip (no clamp)
     net0 = _net(lc=3, scales=(2, 5), p=0)
-    dst0 = torch.full((2, Fw, 3), -1.0)
-    net0._stage_frames(fr, np.array([0, 87]), T, dst0, off)
+    dst0, _, _ = _staged(net0, fr, np.array([0, 87]), T, Fw)
     assert torch.equal(dst0[0], fr[0, :5])
     assert torch.equal(dst0[1, :4], fr[1, 8:12])
     assert torch.equal(dst0[1, 4], torch.zeros(3))
-    # a model without context keeps its clamp
+    # a model without context keeps its clamp: clip 1 takes frames 8 .. 11
+    # (12 frames: the window's last entry is clamped)
     plain = _net(lc=3, scales=(2, 5), p=None)
-    dstp = torch.full((2, Fw, 3), -1.0)
-    plain._stage_frames(fr, np.array([0, 87]), T, dstp, off)
+    dstp, offp, _ = _staged(plain, fr, np.array([0, 87]), T, Fw)
+    assert offp.tolist() == [0, 7]
+    assert torch.equal(dstp[0], fr[0, :5])
+    assert torch.equal(dstp[1, :4], fr[1, 8:12])
     assert torch.equal(dstp[1, 4], fr[1, 11])
 
 

@@ -208,22 +208,6 @@ def test_frames_and_offset_validation():
         plain._lc_input(np.zeros((B, T, 8), np.float32), 3, B, T, 'loss')
 
 
-def test_stage_frames_window():
-    net = _net(lc=3, scales=(2, 5))           # hop 10
-    fr = torch.arange(2 * 12 * 3, dtype=torch.float32).view(2, 12, 3)
-    T = 35
-    Fw = net._lc_frame_window(T)
-    assert Fw == 5                             # (35 + 8) // 10 + 1
-    dst = torch.zeros(2, Fw, 3)
-    off = torch.zeros(2, dtype=torch.int32)
-    net._stage_frames(fr, np.array([0, 87]), T, dst, off)
-    assert off.tolist() == [0, 7]
-    assert torch.equal(dst[0], fr[0, :5])
-    # clip 1: frames 8 .. 11 (12 frames: the window's last entry is clamped)
-    assert torch.equal(dst[1, :4], fr[1, 8:12])
-    assert torch.equal(dst[1, 4], fr[1, 11])
-
-
 def _corpus(tmp_path, Lc, hop):
     rng = np.random.default_rng(1)
     sr = 16000

@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import tf_checkpoint  # noqa: E402
+from wavenet import local_condition, tf_checkpoint  # noqa: E402
 
 BATCH_SIZE = 1
 DATA_DIRECTORY = './VCTK-Corpus'
@@ -122,21 +122,10 @@ def get_arguments(argv=None):
 def lc_upsample_scales(args):
     """(scales tuple, hop) of --lc_upsample_scales, or (None, args.lc_hop);
     ValueError for a malformed list or an --lc_hop that disagrees."""
-    if args.lc_upsample_scales is None:
-        return None, args.lc_hop
-    try:
-        scales = tuple(int(x) for x in args.lc_upsample_scales.split(','))
-    except ValueError:
-        raise ValueError('--lc_upsample_scales must be comma-separated ints, '
-                         'got %r' % args.lc_upsample_scales)
-    if args.lc_channels is None:
+    if args.lc_upsample_scales is not None and args.lc_channels is None:
         raise ValueError('--lc_upsample_scales needs --lc_channels')
-    hop = int(np.prod(scales))
-    if args.lc_hop is not None and args.lc_hop != hop:
-        raise ValueError('--lc_hop %d disagrees with --lc_upsample_scales %s '
-                         '(hop = their product, %d)'
-                         % (args.lc_hop, args.lc_upsample_scales, hop))
-    return scales, hop
+    return local_condition.parse_cli(args.lc_upsample_scales, args.lc_hop,
+                                     None)[:2]
 
 
 def lc_context(args):
@@ -144,14 +133,8 @@ def lc_context(args):
     --lc_upsample_scales or out of range."""
     if args.lc_context is None:
         return None
-    if args.lc_upsample_scales is None:
-        raise ValueError('--lc_context needs --lc_upsample_scales (it '
-                         'convolves frames)')
-    from wavenet import WaveNetModel
-    if not 0 <= args.lc_context <= WaveNetModel.LC_CONTEXT_MAX:
-        raise ValueError('--lc_context must be from 0 to %d, got %d'
-                         % (WaveNetModel.LC_CONTEXT_MAX, args.lc_context))
-    return args.lc_context
+    return local_condition.parse_cli(args.lc_upsample_scales, None,
+                                     args.lc_context)[2]
 
 
 def checkpoint_path(logdir, step):
