@@ -405,6 +405,20 @@ int wn_xent_partials(long rows);
 int wn_xent(const float* logits, long ld, const int32_t* q, float* dlogits,
             float* loss_partials, int B, int T, int Q, int tf_quirk,
             void* stream);
+/* wn_xent for a batch of right-padded clips: lengths [B] (device int32, the
+ * real samples of every clip, clamped to [0, T] by the kernel; the host
+ * checks 1 <= lengths[b] <= T) and inv_den (device float, 1 / denominator:
+ * 1 / sum(lengths) for the masked mean).  Clip b is treated as a clip of
+ * T = lengths[b] fed alone; rows t >= lengths[b] add nothing to the loss and
+ * get dlogits rows of exact zeros.  Both are READ FROM DEVICE MEMORY when the
+ * kernel runs, so a recorded launch replays with the values staged for this
+ * call.  Same partials as wn_xent; lengths[b] = T for every clip and
+ * *inv_den = 1.0f / (float)(B*T) give wn_xent's results bit for bit.
+ * lengths and inv_den 4-byte aligned, else WN_ERR_MISALIGNED. */
+int wn_xent_masked(const float* logits, long ld, const int32_t* q,
+                   const int32_t* lengths, const float* inv_den,
+                   float* dlogits, float* loss_partials, int B, int T, int Q,
+                   int tf_quirk, void* stream);
 int wn_softmax64_row(const float* logits_row, int Q, float* proba,
                      void* stream);
 

@@ -190,11 +190,28 @@ __global__ __launch_bounds__(1024) void scalar_causal_wgrad_kernel(
 // loss term is 0 but it stays in the mean's denominator, and with
 // tf_quirk != 0 it back-propagates softmax/(B*T) like TF's fused kernel
 // (backprop = softmax - labels).
+//
+// MASKED (wn_xent_masked): clip b has lengths[b] real samples and right
+// padding after them, and is treated as a clip of T = lengths[b] fed alone:
+// row lengths[b] - 1 is its label-less last row, rows t >= lengths[b] add
+// nothing to the loss and get an all-zero dlogits row without an exponential
+// being evaluated.  1 / denominator arrives in inv_n like 1 / (B*T) does.
+// One body for both kernels: lengths[b] = T takes exactly the unmasked
+// arithmetic, so the two agree bit for bit there.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void xent_kernel(
+// row -> its clip's length (T when nothing is masked)
+template <bool MASKED>
+__device__ __forceinline__ int xent_len(long row, int T,
+                                        const int32_t* lengths) {
+  return MASKED ? min(max(lengths[row / T], 0), T) : T;
+}
+
+template <bool MASKED>
+__device__ __forceinline__ void xent_body(
     const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
-    int T, int Q, float inv_n, int tf_quirk) {
+    const int32_t* __restrict__ lengths, float* __restrict__ dlogits,
+    float* __restrict__ loss_partials, long rows, int T, int Q, float inv_n,
+    int tf_quirk) {
   __shared__ float wsum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float lsum = 0.f;
@@ -211,7 +228,15 @@ __global__ __launch_bounds__(256) void xent_kernel(
       if (nrow < rows)
         vn = *reinterpret_cast<const f32x4*>(logits + nrow * ld + lane * 4);
       const int t = (int)(row % T);
-      const int label = (t + 1 < T) ? q[row + 1] : -1;
+      const int len = xent_len<MASKED>(row, T, lengths);
+      if (MASKED && t >= len) {              // padding
+        if (dlogits)
+          *reinterpret_cast<f32x4*>(dlogits + row * ld + lane * 4) =
+              f32x4{0.f, 0.f, 0.f, 0.f};
+        v = vn;
+        continue;
+      }
+      const int label = (t + 1 < len) ? q[row + 1] : -1;
       const bool has_label = label >= 0 && label < Q;
       float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
 #pragma unroll
@@ -249,7 +274,15 @@ __global__ __launch_bounds__(256) void xent_kernel(
   for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += nwaves) {
     const float* lp = logits + row * ld;
     const int t = (int)(row % T);
-    const int label = (t + 1 < T) ? q[row + 1] : -1;
+    const int len = xent_len<MASKED>(row, T, lengths);
+    if (MASKED && t >= len) {                // padding
+      if (dlogits)
+        for (int c = lane * 4; c < Q; c += 256)
+          *reinterpret_cast<f32x4*>(dlogits + row * ld + c) =
+              f32x4{0.f, 0.f, 0.f, 0.f};
+      continue;
+    }
+    const int label = (t + 1 < len) ? q[row + 1] : -1;
     const bool has_label = label >= 0 && label < Q;
     float m = -INFINITY;
     for (int c = lane * 4; c < Q; c += 256) {
@@ -288,6 +321,25 @@ __global__ __launch_bounds__(256) void xent_kernel(
   __syncthreads();
   if (threadIdx.x == 0)
     loss_partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+__global__ __launch_bounds__(256) void xent_kernel(
+    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
+    float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
+    int T, int Q, float inv_n, int tf_quirk) {
+  xent_body<false>(logits, ld, q, nullptr, dlogits, loss_partials, rows, T, Q,
+                   inv_n, tf_quirk);
+}
+
+// lengths [B] and 1 / denominator are read from device memory: a recorded
+// launch replays with this call's values
+__global__ __launch_bounds__(256) void xent_masked_kernel(
+    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
+    const int32_t* __restrict__ lengths, const float* __restrict__ inv_den,
+    float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
+    int T, int Q, int tf_quirk) {
+  xent_body<true>(logits, ld, q, lengths, dlogits, loss_partials, rows, T, Q,
+                  *inv_den, tf_quirk);
 }
 
 // softmax of ONE row in float64, cast to float32 (model.py:584-585, 620-621)
@@ -899,6 +951,24 @@ int wn_xent(const float* logits, long ld, const int32_t* q, float* dlogits,
   hipLaunchKernelGGL(xent_kernel, dim3(wn_xent_partials(rows)), dim3(256), 0,
                      (hipStream_t)stream, logits, ld, q, dlogits,
                      loss_partials, rows, T, Q, inv_n, tf_quirk);
+  return wn_check_launch();
+}
+
+int wn_xent_masked(const float* logits, long ld, const int32_t* q,
+                   const int32_t* lengths, const float* inv_den,
+                   float* dlogits, float* loss_partials, int B, int T, int Q,
+                   int tf_quirk, void* stream) {
+  if (!logits || !q || !lengths || !inv_den || !loss_partials)
+    return WN_ERR_NULL;
+  if (B <= 0 || T <= 0 || Q <= 0) return WN_ERR_BAD_SHAPE;
+  if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
+  if (!wn_aligned16(logits) || (dlogits && !wn_aligned16(dlogits)) ||
+      ((uintptr_t)lengths & 3) || ((uintptr_t)inv_den & 3))
+    return WN_ERR_MISALIGNED;
+  const long rows = (long)B * T;
+  hipLaunchKernelGGL(xent_masked_kernel, dim3(wn_xent_partials(rows)),
+                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, lengths,
+                     inv_den, dlogits, loss_partials, rows, T, Q, tf_quirk);
   return wn_check_launch();
 }
 

@@ -99,6 +99,8 @@ SIGNATURES = {
     'wn_transpose': (c_int, [P, c_int, c_int, c_long, P, c_long, P]),
     'wn_xent_partials': (c_int, [c_long]),
     'wn_xent': (c_int, [P, c_long, P, P, P, c_int, c_int, c_int, c_int, P]),
+    'wn_xent_masked': (c_int, [P, c_long, P, P, P, P, P, c_int, c_int, c_int,
+                               c_int, P]),
     'wn_softmax64_row': (c_int, [P, c_int, P, P]),
     'wn_adam': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float,
                         c_float, c_float, c_float, P, P]),

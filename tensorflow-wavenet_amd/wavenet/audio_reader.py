@@ -242,6 +242,7 @@ class AudioReader(object):
             raise ValueError('local conditioning needs lc_hop (samples per '
                              'feature frame)')
         self._last_lc = None
+        self._last_lengths = None
         self.threads = []
         self.queue = queue.Queue(maxsize=queue_size)
         self.gc_queue = queue.Queue(maxsize=queue_size) if gc_enabled else None
@@ -289,6 +290,8 @@ class AudioReader(object):
         at the end (tf.PaddingFIFOQueue.dequeue_many semantics)."""
         import torch
         pieces = [self._get(self.queue) for _ in range(num_elements)]
+        self._last_lengths = [(p[0] if self.lc_enabled else p).shape[0]
+                              for p in pieces]
         if self.lc_enabled:
             # (items are (audio piece, feature piece) pairs: dequeue_lc
             # returns the features of exactly these pieces)
@@ -315,6 +318,19 @@ class AudioReader(object):
         for i, p in enumerate(pieces):
             out[i, :p.shape[0], :] = p
         return torch.from_numpy(out)
+
+    def dequeue_lengths(self, num_elements):
+        """int64 [num_elements]: the unpadded sample counts of the pieces the
+        last `dequeue(num_elements)` returned (WaveNetModel.loss's `lengths`;
+        everything behind them in dequeue's rows, and in the features' or
+        frames', is zero padding)."""
+        import torch
+        n = self._last_lengths
+        if n is None or len(n) != num_elements:
+            raise ValueError('dequeue_lengths(%d) must follow dequeue(%d)'
+                             % (num_elements, num_elements))
+        self._last_lengths = None
+        return torch.tensor(n, dtype=torch.int64)
 
     def dequeue_lc(self, num_elements):
         """float32 [num_elements, T_max, lc_channels]: the audio-rate features

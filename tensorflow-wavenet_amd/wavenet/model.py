@@ -138,6 +138,10 @@ class _Workspace(object):
         # shares them)
         alloc('loss_parts', (2 + self.nparts,), fill=0.0)
         alloc('loss', (1,), fill=0.0)
+        # masked loss (loss(lengths=...)): the clips' lengths and, in the last
+        # word, the bits of float32 1 / denominator, staged per call; the
+        # kernel reads them from here, so a replayed launch sees this call's
+        alloc('xent_mask', (B + 1,), torch.int32, fill=0)
         alloc('proba', (Q,))
         lcond.alloc_workspace(net, self, alloc, False)
         if net.blocked:
@@ -251,6 +255,39 @@ class _Workspace(object):
             if net.G else None
         alloc('l2_parts', (lib.wn_l2_partials_count(),))
         alloc('l2', (1,), fill=0.0)
+
+
+def check_lengths(lengths, loss_denominator, B, T, what):
+    """The `lengths` / `loss_denominator` of a loss call, checked on the host:
+    None without lengths, else (lengths as int32 numpy [B], the denominator
+    as a float: sum(lengths) unless the caller gave one)."""
+    if lengths is None:
+        if loss_denominator is not None:
+            raise ValueError('%s: loss_denominator needs lengths' % what)
+        return None
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().cpu().numpy()
+    n = np.asarray(lengths)
+    if n.dtype == object or n.dtype == np.bool_ or \
+            not np.issubdtype(n.dtype, np.integer):
+        raise ValueError('%s: lengths must be %d integers (dtype %s)'
+                         % (what, B, n.dtype))
+    if n.shape != (B,):
+        raise ValueError('%s: lengths must have shape [%d], got %s'
+                         % (what, B, list(n.shape)))
+    if (n < 1).any() or (n > T).any():
+        raise ValueError('%s: lengths must lie in [1, T] = [1, %d], got %s'
+                         % (what, T, n.tolist()))
+    den = float(n.astype(np.int64).sum())
+    if loss_denominator is not None:
+        d = loss_denominator
+        if isinstance(d, (bool, np.bool_)) or \
+                not isinstance(d, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(d) or not d > 0:
+            raise ValueError('%s: loss_denominator must be a positive finite '
+                             'number, got %r' % (what, d))
+        den = float(d)
+    return n.astype(np.int32), den
 
 
 def _n_codes(codes):
@@ -1436,7 +1473,9 @@ class WaveNetModel(object):
              backward=True,
              *,
              local_condition_batch=None,
-             local_condition_offset=0):
+             local_condition_offset=0,
+             lengths=None,
+             loss_denominator=None):
         '''Creates a WaveNet network and returns the autoencoding loss
         (model.py:628-685).  input_batch: float audio in [-1, 1], anything
         reshapeable to [batch_size, -1].  With backward=True (default) the
@@ -1454,33 +1493,50 @@ class WaveNetModel(object):
         learned network (gradients flow into it).  local_condition_offset
         (an int or batch_size non-negative ints, default 0): input sample t
         of clip b sits at timeline position offset[b] + t, which takes frame
-        (offset[b] + t) // hop; F must cover offset[b] + T - 1.'''
+        (offset[b] + t) // hop; F must cover offset[b] + T - 1.
+
+        lengths (batch_size ints, 1 <= lengths[b] <= T): the batch is right
+        padded and clip b has lengths[b] real samples.  Clip b is treated as
+        a clip of T = lengths[b] fed alone: rows t + 1 < lengths[b] have the
+        target q[b][t + 1], row lengths[b] - 1 is the label-less last row,
+        rows t >= lengths[b] add nothing to the loss or to any gradient, and
+        the mean is taken over sum(lengths) rows instead of batch_size * T.
+        What the padding holds (audio, conditioning rows or frames) does not
+        matter.  loss_denominator (a positive number, only with lengths)
+        replaces sum(lengths): data-parallel ranks pass
+        parallel.masked_denominator, so that their averaged gradient is the
+        masked mean over the global batch.'''
         self._check_supported()
         B = self.batch_size
         a = input_batch
         if not isinstance(a, torch.Tensor):
             a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
+        mask = check_lengths(lengths, loss_denominator, B, a.shape[1], 'loss')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'loss')
         return self._loss(mu_law_encode(a, self.Q), global_condition_batch,
-                          l2_regularization_strength, backward, a, lc)
+                          l2_regularization_strength, backward, a, lc, mask)
 
     def loss_from_codes(self, q, global_condition_batch=None,
                         l2_regularization_strength=None, backward=True,
                         audio=None, *, local_condition_batch=None,
-                        local_condition_offset=0):
+                        local_condition_offset=0, lengths=None,
+                        loss_denominator=None):
         self._check_supported()
         q = q.reshape(self.batch_size, -1)
+        mask = check_lengths(lengths, loss_denominator, self.batch_size,
+                             q.shape[1], 'loss')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          self.batch_size, q.shape[1], 'loss')
         return self._loss(q, global_condition_batch,
-                          l2_regularization_strength, backward, audio, lc)
+                          l2_regularization_strength, backward, audio, lc,
+                          mask)
 
     def _loss(self, q, global_condition_batch, l2_regularization_strength,
-              backward, audio, lc):
+              backward, audio, lc, mask=None):
         """loss_from_codes on codes q [B, T] with the LC input checked
-        (local_condition.check)."""
+        (local_condition.check) and the lengths (check_lengths)."""
         B, T = q.shape
         N = B * T
         ws = self._workspace(B, T, backward)
@@ -1509,13 +1565,26 @@ class WaveNetModel(object):
         path = self._step_path(ws, backward,
                                l2=l2_regularization_strength is not None)
         self._run_pass('fwd', ws, ids, path)
-        _lib.call('wn_xent', _lib.ptr(ws.logits), self.Q, _lib.ptr(ws.q),
-                  _lib.ptr(ws.logits) if backward else None,
-                  _lib.ptr(ws.loss_parts[2:]), B, T, self.Q,
-                  1 if self.tf_xent_zero_label_quirk else 0, st)
+        quirk = 1 if self.tf_xent_zero_label_quirk else 0
+        if mask is None:
+            den = float(N)
+            _lib.call('wn_xent', _lib.ptr(ws.logits), self.Q, _lib.ptr(ws.q),
+                      _lib.ptr(ws.logits) if backward else None,
+                      _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk, st)
+        else:
+            # the kernel scales by float32 1 / den as wn_xent does by 1 / N
+            lengths, den = mask
+            inv = np.float32(1.0) / np.float32(den)
+            ws.xent_mask.copy_(torch.from_numpy(np.concatenate(
+                [lengths, np.array([inv], np.float32).view(np.int32)])))
+            _lib.call('wn_xent_masked', _lib.ptr(ws.logits), self.Q,
+                      _lib.ptr(ws.q), _lib.ptr(ws.xent_mask),
+                      _lib.ptr(ws.xent_mask[B:]),
+                      _lib.ptr(ws.logits) if backward else None,
+                      _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk, st)
         _lib.call('wn_reduce_slabs', _lib.ptr(ws.loss_parts), ws.nparts + 2, 1, 1,
                   0, 0, 1, _lib.ptr(ws.loss), 0, 1, 0, st)
-        loss = ws.loss[0] / float(N)                    # reduce_mean, :666
+        loss = ws.loss[0] / den                         # reduce_mean, :666
         if backward:
             try:
                 self._run_pass('bwd', ws, ids, path)

@@ -257,6 +257,24 @@ def agree_step(n_samples, ok=True, device='cpu'):
     return int(t[0]), bool(int(t[1]))
 
 
+def masked_denominator(lengths, device='cpu'):
+    """The `loss_denominator` of a masked loss step (WaveNetModel.loss with
+    `lengths`): (sum of lengths over ALL ranks' clips) / world.  Every rank
+    divides its loss and gradients by it, and the optimizer averages the
+    ranks' gradients (1 / world), so the applied gradient is the masked mean
+    over the global batch; the ranks' logged losses average to the global
+    masked mean as well.  The lengths are host data known before the step:
+    one host collective of one integer that never waits for the device.
+    Call it after agree_step, with the lengths already cut to the common T."""
+    total = int(torch.as_tensor(lengths).to(torch.int64).sum())
+    if not is_distributed():
+        return float(total)
+    group, device = _ctl(device)
+    t = torch.tensor([total], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return int(t.cpu()[0]) / float(dist.get_world_size())
+
+
 def any_rank(flag, device='cpu'):
     """True on EVERY rank when `flag` is true on at least one (all-reduce MAX):
     for decisions that must be taken by all ranks in the same step (aborting

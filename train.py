@@ -116,6 +116,13 @@ def get_arguments(argv=None):
                         'frames (P frames either side, channels to channels) '
                         'in front of the upsampler, 0 <= P <= 8.  Needs '
                         '--lc_upsample_scales.')
+    p.add_argument('--mask_padding', type=_str_to_bool, default=False,
+                   help='Batches of clips of different lengths: pass the '
+                        'clips\' real lengths to the loss, so that the zero '
+                        'padding behind the shorter ones is neither learned '
+                        'nor counted in the mean (WaveNetModel.loss, '
+                        '`lengths`).  Prints the real samples per step beside '
+                        'the loss.')
     return p.parse_args(argv)
 
 
@@ -267,6 +274,9 @@ class SyntheticReader(object):
                 (frames, self.lc_channels)).astype(np.float32),
                 self.lc_hop, self.T) for _ in range(n)]))
 
+    def dequeue_lengths(self, n):
+        return torch.full((n,), self.T, dtype=torch.int64)
+
     def start_threads(self, *a, **k):
         return []
 
@@ -376,7 +386,7 @@ def main(argv=None):
     pending = None            # (step, mean loss tensor, start time) not yet printed
     last_report = [None]
 
-    def report(k, mean_loss, started):
+    def report(k, mean_loss, started, real=None):
         """Fetch step k's loss (waits for that step), check it, print / log the
         reference's line (train.py:310-311).  sec/step: from the previous line
         (the pipeline's cadence), or from the step's start for the first."""
@@ -404,10 +414,14 @@ def main(argv=None):
                           last_report[0] > started else started)
         last_report[0] = now
         if rank == 0:
+            # (--mask_padding: `real` = the step's real samples, all ranks')
             print('step {:d} - loss = {:.3f}, ({:.3f} sec/step)'
-                  .format(k, loss_value, duration))
-            events.write(json.dumps({'step': k, 'loss': loss_value,
-                                     'sec_per_step': duration}) + '\n')
+                  .format(k, loss_value, duration) +
+                  ('' if real is None else ', {:d} real samples'.format(real)))
+            line = {'step': k, 'loss': loss_value, 'sec_per_step': duration}
+            if real is not None:
+                line['real_samples'] = real
+            events.write(json.dumps(line) + '\n')
             events.flush()
 
     fetch_slots = {}
@@ -453,6 +467,8 @@ def main(argv=None):
             err = None
             try:
                 audio = reader.dequeue(args.batch_size)
+                lengths = reader.dequeue_lengths(args.batch_size).numpy() \
+                    if args.mask_padding else None
                 gc = reader.dequeue_gc(args.batch_size) if gc_enabled else None
                 lc, lc_off = None, 0
                 if lc_scales is not None:
@@ -461,14 +477,22 @@ def main(argv=None):
                 elif lc_enabled:
                     lc = reader.dequeue_lc(args.batch_size)
             except Exception as e:        # e.g. a reader-thread failure
-                err, audio, gc, lc = e, None, None, None
+                err, audio, gc, lc, lengths = e, None, None, None, None
             n_t, all_ok = parallel.agree_step(
                 audio.shape[1] if err is None else 0, err is None, net.device)
             if not all_ok:
                 raise RuntimeError('rank %d: a rank failed to produce a batch '
                                    'at step %d%s' % (rank, step, '' if err is
                                                      None else ': %r' % err))
-            if n_t < 2:
+            den = real = None
+            if lengths is not None:
+                # (cut to the common T like the rows; every rank's longest
+                # real clip is then n_t samples, so the guard below looks at
+                # the longest real length and decides the same on every rank)
+                lengths = np.minimum(lengths, n_t)
+                den = parallel.masked_denominator(lengths, net.device)
+                real = int(round(den * world))
+            if (n_t if lengths is None else int(lengths.max())) < 2:
                 continue
             audio = audio[:, :n_t]
             if lc is not None and lc_scales is None:
@@ -490,7 +514,8 @@ def main(argv=None):
             loss = net.loss(input_batch=audio, global_condition_batch=gc,
                             l2_regularization_strength=l2,
                             local_condition_batch=lc,
-                            local_condition_offset=lc_off)
+                            local_condition_offset=lc_off,
+                            lengths=lengths, loss_denominator=den)
             optimizer.minimize(loss)
             # The reference fetches the loss inside sess.run and so waits for
             # every step (train.py:300-311).  Here the step is queued on the
@@ -501,7 +526,7 @@ def main(argv=None):
             mean_loss = fetch_later(parallel.allreduce_mean_scalar(loss), step)
             if pending is not None:
                 report(*pending)
-            pending = (step, mean_loss, start_time)
+            pending = (step, mean_loss, start_time, real)
             if trace_step:
                 report(*pending)
                 pending = None
