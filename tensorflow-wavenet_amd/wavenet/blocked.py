@@ -27,6 +27,7 @@ wavenet_params.json has 32 / 32 channels and runs the fused kernels).
 import torch
 
 from . import _lib
+from .train_pass import reduce_slabs
 
 CH = 32
 
@@ -118,9 +119,7 @@ def backward_layers(net, ws, ids, st):
     P, Gr = net.params, net.grads
     ub = net.use_biases
     pstride = N * CH
-    lib = _lib.load()
-    WF = (2 * K + 1) * 1024
-    nslab = ws.nslab
+    nslab = ws.region['pairs'].count
     if CB in (2, 4) and K == 2:
         # the all-input-blocks weight-gradient kernel of 64- / 128-channel
         # layers holds one workgroup per CU: one round of them per pass (the
@@ -207,30 +206,28 @@ def backward_layers(net, ws, ids, st):
                       _lib.ptr(w['wg'][wo:]), C, M, B, T, d, nk, k0, K, CB,
                       pstride, st)
         dxin, xp = dxo, 1 - xp
-    sp = ws.splits['causal']
     if net.scalar_input:
         # ---- causal layer on scalar input (model.py:143-153): per block
-        K0 = net.initial_filter_width
+        K0, reg = net.initial_filter_width, ws.region['causal_scalar']
         gs = net._seg(Gr, 'causal').view(K0, C)
         for cb in range(CB):
             _lib.call('wn_scalar_causal_wgrad', _lib.ptr(ws.audio),
-                      _lib.ptr(dxin[cb]), _lib.ptr(ws.slabs), sp, B, T, K0, st)
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, K0 * CH, 1,
-                      0, 0, K0 * CH, _lib.ptr(ws.blk_tmp), 0, 1, 0, st)
+                      _lib.ptr(dxin[cb]), _lib.ptr(reg.buf), reg.count, B, T,
+                      K0, st)
+            reduce_slabs(reg, _lib.ptr(ws.blk_tmp), st)
             gs[:, cb * CH:(cb + 1) * CH].copy_(
                 ws.blk_tmp[:K0 * CH].view(K0, CH))
         K = 0                                  # no one-hot taps below
     # ---- causal layer (model.py:227-234): one-hot contraction per tap / block
     gc_ = None if net.scalar_input else net._seg(Gr, 'causal').view(K, Q, C)
-    sl = lib.wn_gemm_tn_slab_floats(Q, CH)
+    reg = ws.region['causal_onehot']
     for tap in range(K):
         shift = (K - 1 - tap) + (K - 1) // 2
         for cb in range(CB):
             _lib.call('wn_gemm_tn', None, 0, 0, 0, _lib.ptr(ws.q), shift, T,
-                      _lib.ptr(dxin[cb]), CH, _lib.ptr(ws.slabs), sp, N, Q, CH,
-                      0, st)
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, sl, 1, 0, 0,
-                      Q * CH, _lib.ptr(ws.blk_tmp), 0, 1, 0, st)
+                      _lib.ptr(dxin[cb]), CH, _lib.ptr(reg.buf), reg.count, N,
+                      Q, CH, 0, st)
+            reduce_slabs(reg, _lib.ptr(ws.blk_tmp), st)
             gc_[tap, :, cb * CH:(cb + 1) * CH].copy_(
                 ws.blk_tmp[:Q * CH].view(Q, CH))
     if ws.dsum is not None:

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import local_condition as lcond
+from . import train_pass
 
 CH = 32
 _EXPIRED = dict(
@@ -150,7 +151,8 @@ def _weights(net, g, gc, B):
     """GC / filter-gate bias and skip-bias sum of B streams -> the nine
     parameter pointers, the bias pointer and its stream stride."""
     P, ub = net.params, net.use_biases
-    bias, bstride = net._bias_fg(g['bias'], net._gc_ids(gc, B), B)
+    bias, bstride = train_pass.bias_fg(net, g['bias'],
+                                       net._gc_ids(gc, B), B)
     bsum = None
     if ub:
         _lib.call('wn_sum_rows', _lib.ptr(net._seg(P, 'skip_b')), net.L,
@@ -253,8 +255,8 @@ def _prime(net, g, n0, groups, Bp):
     for codes, gc, streams, lc in groups:
         ws.q.copy_(codes)
         lcond.fill(net, lc, ws)    # the seed's LC rows, as predict_proba
-        net._run_pass('fwd', ws, net._gc_ids(gc, 1),
-                      net._step_path(ws, False))
+        train_pass.run_pass(net, 'fwd', ws, net._gc_ids(gc, 1),
+                            train_pass.step_path(net, ws, False))
         # (+ the forward launch's poison word: 0, or NaN after an expired wait)
         vals = ws.X.reshape(-1, CH).index_select(0, src) + ws.loss_parts[0]
         rows = dst[None, :] * Bp + np.asarray(streams, np.int64)[:, None]

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import train_pass
 
 # a checked frames input: frames [B, F, Lc] (a float tensor where the caller
 # had them), offsets int64 [B], clip length T, the staging window (window)
@@ -359,14 +360,12 @@ def backward(net, ws, st):
     stored); d rows = lc_da lc_w^T, the upsampler's (layer, slot, tap)
     partials per workgroup summed in a fixed order; the context's from d ctx."""
     N, W64, Lcp = ws.N, net.L * 64, net.Lcp
-    sp = ws.splits['lc']
+    reg = ws.region['lc_w']
     _lib.call_timed('wn_gemm_tn', (
         _lib.ptr(ws.lc), Lcp, 0, 0, None, 0, ws.T, _lib.ptr(ws.lc_da), W64,
-        _lib.ptr(ws.slabs), sp, N, Lcp, W64, 0, st),
+        _lib.ptr(reg.buf), reg.count, N, Lcp, W64, 0, st),
         2.0 * N * W64 * Lcp, net._gemm_events)
-    _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp,
-              _lib.load().wn_gemm_tn_slab_floats(Lcp, W64), 1, 0, 0,
-              Lcp * W64, _lib.ptr(net._seg(net.grads, 'lc_w')), 0, 1, 0, st)
+    train_pass.reduce_slabs(reg, _lib.ptr(net._seg(net.grads, 'lc_w')), st)
     if not net.lc_up:
         return
     _lib.call('wn_transpose', _lib.ptr(net._seg(net.params, 'lc_w')), Lcp,
@@ -375,39 +374,38 @@ def backward(net, ws, st):
         _lib.ptr(ws.lc_da), W64, 0, 0, _lib.ptr(ws.lc_wT), Lcp, None, None,
         0, None, 0, _lib.ptr(ws.lc_drows), Lcp, 0, 0, None, N, Lcp, W64, 0,
         st), 2.0 * N * W64 * Lcp, net._gemm_events)
+    reg = ws.region['lc_up']
     args = (_lib.ptr(ws.lc_frames), ws.lc_fw, _lib.ptr(ws.lc_off),
             _lib.ptr(net._seg(net.params, 'lc_up')),
             ctypes.addressof(net._lc_up_c), len(net.lc_up), net.Lc,
             1 if net.use_biases else 0, _lib.ptr(ws.lc_drows), Lcp, ws.B,
-            ws.T, _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab, ws.lc_up_stride)
+            ws.T, _lib.ptr(reg.buf), reg.count, reg.stride)
     if net.lc_ctx is None:
         _lib.call('wn_lc_upsample_bwd', *args, st)
     else:
         # (the same slabs) + d ctx
         _lib.call('wn_lc_upsample_bwd_ctx', *args, _lib.ptr(ws.lc_dctx),
                   _lib.ptr(ws.lc_dpart), st)
-    _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_up_slabs), ws.lc_up_nslab,
-              ws.lc_up_stride, 1, 0, 0, ws.lc_up_n,
-              _lib.ptr(net._seg(net.grads, 'lc_up')), 0, 1, 0, st)
+    train_pass.reduce_slabs(reg, _lib.ptr(net._seg(net.grads, 'lc_up')), st)
     if net.lc_ctx is not None:
         # d W[k] = sum over frames of x[f + k]^T d ctx[f]
+        reg = ws.region['lc_ctx']
         _lib.call('wn_lc_context_wgrad', _lib.ptr(ws.lc_xframes),
                   ws.lc_xframes.shape[1], _lib.ptr(ws.lc_dctx), ws.lc_fw,
-                  net.lc_ctx, net.Lc, ws.B, _lib.ptr(ws.lc_ctx_slabs),
-                  ws.lc_ctx_nslab, ws.lc_ctx_stride, st)
-        _lib.call('wn_reduce_slabs', _lib.ptr(ws.lc_ctx_slabs),
-                  ws.lc_ctx_nslab, ws.lc_ctx_stride, 1, 0, 0, ws.lc_ctx_n,
-                  _lib.ptr(net._seg(net.grads, 'lc_ctx')), 0, 1, 0, st)
+                  net.lc_ctx, net.Lc, ws.B, _lib.ptr(reg.buf), reg.count,
+                  reg.stride, st)
+        train_pass.reduce_slabs(reg, _lib.ptr(net._seg(net.grads, 'lc_ctx')), st)
 
 
-def alloc_workspace(net, ws, alloc, training):
-    """Workspace ws's LC buffers, forward or (training) backward ones;
-    returns the floats of ws.slabs the lc_w TN GEMM needs."""
+def alloc_workspace(net, ws, alloc, region):
+    """Workspace ws's LC buffers: the forward ones (region None), or the
+    backward ones and their slab regions (`region`: the workspace's call
+    that declares one, workspace.py)."""
     if not net.Lc:
-        return 0
+        return
     L, Lc, B, N = net.L, net.Lc, ws.B, ws.N
     lib = _lib.load()
-    if not training:
+    if region is None:
         # the rows and lc x lc_w [N][L][64] (filter | gate, wn_stack_fwd_lc)
         alloc('lc', (N, net.Lcp), fill=0.0)
         alloc('lc_add', (N, L * 64))
@@ -419,28 +417,26 @@ def alloc_workspace(net, ws, alloc, training):
         if net.lc_ctx is not None:
             # context: staged [B][Fw + 2p][Lc]; lc_frames is its output
             alloc('lc_xframes', (B, ws.lc_fw + 2 * net.lc_ctx, Lc), fill=0.0)
-        return 0
-    # the pre-activation gradients [N][L][64] for lc^T da
+        return
+    # the pre-activation gradients [N][L][64] for lc^T da, whose TN GEMM's
+    # slabs share ws.slabs
     alloc('lc_da', (N, L * 64))
-    sp = ws.splits['lc'] = lib.wn_gemm_tn_splits(N, net.Lcp, L * 64, 0)
+    region('lc_w', lib.wn_gemm_tn_splits(N, net.Lcp, L * 64, 0),
+           lib.wn_gemm_tn_slab_floats(net.Lcp, L * 64), net.Lcp * L * 64)
     if net.lc_up:
         # d rows = lc_da lc_w^T, the upsampler's per-workgroup slabs
         alloc('lc_wT', (L * 64, net.Lcp))
         alloc('lc_drows', (N, net.Lcp))
-        ws.lc_up_n = up_floats(net)
-        ws.lc_up_stride = _align4(ws.lc_up_n)
-        ws.lc_up_nslab = lib.wn_lc_upsample_bwd_slabs(N, ws.lc_up_n)
-        alloc('lc_up_slabs', (ws.lc_up_nslab, ws.lc_up_stride))
+        n = up_floats(net)
+        nslab = lib.wn_lc_upsample_bwd_slabs(N, n)
+        region('lc_up', nslab, _align4(n), n, own='lc_up_slabs')
     if net.lc_ctx is not None:
         # d ctx [B][Fw][Lc], workgroups' parts of shared frames, slabs
         alloc('lc_dctx', (B, ws.lc_fw, Lc))
-        alloc('lc_dpart', (ws.lc_up_nslab, 2, Lc))
-        ws.lc_ctx_n = (2 * net.lc_ctx + 1) * Lc * Lc
-        ws.lc_ctx_stride = _align4(ws.lc_ctx_n)
-        ws.lc_ctx_nslab = lib.wn_lc_context_wgrad_slabs(B * ws.lc_fw,
-                                                        ws.lc_ctx_n)
-        alloc('lc_ctx_slabs', (ws.lc_ctx_nslab, ws.lc_ctx_stride))
-    return sp * lib.wn_gemm_tn_slab_floats(net.Lcp, L * 64)
+        alloc('lc_dpart', (nslab, 2, Lc))
+        n = (2 * net.lc_ctx + 1) * Lc * Lc
+        region('lc_ctx', lib.wn_lc_context_wgrad_slabs(B * ws.lc_fw, n),
+               _align4(n), n, own='lc_ctx_slabs')
 
 
 def parse_cli(scales, hop, context):

@@ -16,9 +16,7 @@ MI355X-first design:
 There is no CPU / PyTorch compute fallback: without the HIP library or a GPU
 every entry point raises.
 """
-import collections
 import math
-import os
 
 import numpy as np
 import torch
@@ -26,31 +24,13 @@ import torch
 from . import _lib
 from . import fastgen
 from . import local_condition as lcond
+from . import train_pass
+from . import workspace
 from .ops import mu_law_encode, mu_law_decode, mu_law_tables
+from .workspace import CH
 
-CH = 32                      # channels per activation plane (one block)
 # layer block (floats) for filter width K and C = 32 * blocks padded channels:
 #   Wf[K][C][C] Wg[K][C][C] Wd[C][C] bf[C] bg[C] bd[C] (+ gc weights [G][C] x 2)
-
-
-# Beside the backward stack of a very small batch (256 - 512 32-row tiles) the
-# side stream's TN GEMMs run this fraction of their splits: fewer, longer
-# workgroups disturb the stack's dependent chain less (B = 1, T = 16000, 500
-# tiles: 1.89 -> 1.80 ms per step at 0.6; 0.75 and 0.4 lose; at B = 2 nothing
-# changes; at most one tile per CU is too short for it to matter)
-TN_SIDE_SPLIT_FRAC = 0.6
-
-# What one loss() / predict_proba() call launches, decided once per call by
-# WaveNetModel._step_path and the key of its launch plans: the residual stack's
-# forward `fwd` ('stack' | 'stack_skip' | 'stack_lc' persistent launches, or
-# 'layer' | 'layer_k' | 'blocked' per layer) and backward `bwd` (None, 'stack' |
-# 'stack_lc' | 'layer2' | 'layer_k' | 'blocked'), the saved planes `save_ts`
-# (0 | 1: tanh + sigmoid | 2: sigmoid), and `pack_both` (the forward's
-# wn_stack_pack writes the backward image too), `overlap_tn` (TN GEMMs on the
-# side stream), `early_allreduce`, `causal_wgrad`, `gemm_mode`, `variant`.
-StepPath = collections.namedtuple('StepPath', [
-    'fwd', 'save_ts', 'bwd', 'pack_both', 'overlap_tn', 'early_allreduce',
-    'causal_wgrad', 'gemm_mode', 'variant'])
 
 
 def layer_w(K, C=CH):
@@ -69,192 +49,6 @@ def _xavier_(t, gen):
     lim = math.sqrt(6.0 / (rf * shape[-2] + rf * shape[-1]))
     vals = (torch.rand(shape, generator=gen, dtype=torch.float32) * 2 - 1) * lim
     t.copy_(vals.to(t.device))
-
-
-class _Workspace(object):
-    """Caller-owned device buffers for one (B, T) shape (the library never
-    allocates).  Sized for 288 GB HBM: everything stays resident.  A workspace
-    for a smaller T (same B) is carved out of an existing larger one
-    (`parent`) without allocating -- the windowed naive generation path calls
-    predict_proba with a growing T."""
-
-    def __init__(self, net, B, T, training, parent=None):
-        dev = net.device
-        L, S, Q = net.L, net.S, net.Q
-        CB, CHn = net.CB, net.CHn       # channel blocks, padded channels
-        LP = L * CB                     # activation planes per tensor
-        N = B * T
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.B, self.T, self.N, self.training = B, T, N, training
-        # (the variant word of the stack launches is fixed per workspace, and so
-        # is the library's answer whether wn_stack_fwd_skip covers the shape)
-        self.stack_variant = net._stack_variant_for_launch()
-        self.capacity = N if parent is None else parent.capacity
-        lib = _lib.load()
-        self.fwd_skip_ok = bool(lib.wn_stack_fwd_skip_ok(B, T, S,
-                                                         self.stack_variant))
-
-        def alloc(name, shape, dtype=torch.float32, fill=None):
-            n = int(np.prod(shape))
-            if parent is not None and getattr(parent, name, None) is not None:
-                t = getattr(parent, name).reshape(-1)[:n].view(shape)
-            else:
-                fresh.add(name)
-                if fill is None:
-                    t = torch.empty(shape, dtype=dtype, device=dev)
-                else:
-                    t = torch.full(shape, fill, dtype=dtype, device=dev)
-            setattr(self, name, t)
-            return t
-
-        fresh = set()   # buffers this workspace owns (not views of the parent's)
-
-        self.plans = {}
-        alloc('q', (N,), torch.int32)
-        self.gc_ids = alloc('gc_ids', (B,), torch.int32) \
-            if net.card is not None else None
-        self.audio = alloc('audio', (N,)) if net.scalar_input else None
-        alloc('X', (LP, N, CH))
-        alloc('Z', (LP, N, CH))
-        alloc('h1', (N, S))
-        alloc('h2', (N, S))
-        alloc('logits', (N, Q))
-        alloc('bias_fg', (L, B, 2 * CHn))
-        # persistent residual-stack kernels (wn_stack_fwd): one "rows are in
-        # memory" flag per (layer, 32-row tile) and a 4-word control block
-        # {group ticket, workgroups done, epoch, error}; epochs start at 1
-        alloc('stack_flags', (lib.wn_stack_flag_count(B, T, L),), torch.int32,
-              fill=0)
-        alloc('wimg_f', (L, lib.wn_stack_wimg_floats()))
-        alloc('stack_ctl', (4,), torch.int32, fill=0)
-        if 'stack_ctl' in fresh:         # (a view shares the owner's epoch)
-            self.stack_ctl[2] = 1
-        alloc('bsum', (S,))
-        self.total = alloc('total', (N, S)) if net.residual_postproc else None
-        self.nparts = lib.wn_xent_partials(N)
-        # (the first 2 words: the NaN "poison" of wn_stack_fwd / wn_stack_bwd,
-        # summed into the loss with the partials that follow them: an expired
-        # wait turns the loss NaN; in front so that a carved-out workspace
-        # shares them)
-        alloc('loss_parts', (2 + self.nparts,), fill=0.0)
-        alloc('loss', (1,), fill=0.0)
-        # masked loss (loss(lengths=...)): the clips' lengths and, in the last
-        # word, the bits of float32 1 / denominator, staged per call; the
-        # kernel reads them from here, so a replayed launch sees this call's
-        alloc('xent_mask', (B + 1,), torch.int32, fill=0)
-        alloc('proba', (Q,))
-        lcond.alloc_workspace(net, self, alloc, False)
-        if net.blocked:
-            # partial pre-activations of a layer wider than one chunk of
-            # channel blocks (wavenet/blocked.py), planes af | ag
-            alloc('pre', (2 * CB, N, CH))
-        if not training:
-            return
-        # the generic-tap / channel-block backward kernels also need the tanh
-        # plane and two ping-pong pairs of pre-activation-gradient planes; the
-        # default wn_stack_bwd / wn_layer_bwd2 do not
-        self.legacy = net._layer_path() != 'layer'
-        self.TH = alloc('TH', (LP, N, CH)) if self.legacy else None
-        alloc('SG', (LP, N, CH))
-        alloc('dZ', (LP, N, CH))
-        alloc('dc1', (N, S))
-        alloc('dtotal', (N, S))
-        self.dh2 = alloc('dh2', (N, S)) if net.residual_postproc else None
-        self.c1 = alloc('c1', (N, S)) if net.residual_postproc else None
-        self.da = alloc('da', (2, 2 * CB, N, CH)) if self.legacy else None
-        alloc('dx', (2, CB, N, CH))
-        # persistent backward (wn_stack_bwd), "push" formulation: a tile's
-        # own dx rows have no reader but the wave that wrote them, so ONE
-        # plane is rewritten in place from layer to layer (it stays in the L2
-        # / Infinity Cache; DX[0] ends up as dL/dx_0).  The per-layer checks of
-        # tests/test_gpu_stack.py (`net.stack_bwd_keep_dx`) keep dL/dx_l of
-        # EVERY layer.  Plus the q planes, flags and control block (allocated
-        # whenever the option could apply)
-        self.stack_bwd = bool(net.stack_bwd and net._stack_ok(N))
-        if self.stack_bwd:
-            self.keep_dx = bool(net.stack_bwd_keep_dx)
-            if parent is not None and getattr(parent, 'DX', None) is not None:
-                self.keep_dx = parent.keep_dx
-            alloc('DX', (L if self.keep_dx else 1, N, CH))
-            # q_l planes of the "push" formulation: what a tile's rows send to
-            # the rows d earlier (csrc/wn_stack.hip)
-            alloc('DQ', (L, N, CH))
-            alloc('wimg_b', (L, lib.wn_stack_wimg_floats()))
-            alloc('stack_flags_b', (lib.wn_stack_flag_count(B, T, L),),
-                  torch.int32, fill=0)
-            alloc('stack_ctl_b', (4,), torch.int32, fill=0)
-            # a child whose parent was built without the backward stack
-            # buffers owns fresh flags (all 0): its epoch must start at 1 too
-            if 'stack_ctl_b' in fresh:
-                self.stack_ctl_b[2] = 1
-        if net.blocked:                  # channel-block path scratch
-            alloc('dzb', (CB, N, CH))
-            alloc('wdT', (CHn, CHn))
-            alloc('blk_tmp', (max((2 * net.KW + 1) * 1024 + 96, Q * CH,
-                                  net.initial_filter_width * CH),))
-            alloc('cs_tmp', (B, 64))
-        alloc('w2t', (Q, S))
-        alloc('w1t', (S, S))
-        alloc('wst', (S, L * CHn))
-        ntiles = B * ((T + 31) // 32)
-        self.nslab = max(1, min(512, ntiles // 4))
-        if net.blocked:
-            # the pair-slab scratch of the channel-block path grows with the
-            # SQUARE of the block count (CB^2 x nslab x up to 17.5 K floats:
-            # 36 GB at 1024 channels and 8 taps with 512 slabs): fewer, longer
-            # row splits beyond 8 GB instead of an opaque allocation failure
-            per = CB * CB * ((2 * min(net.KW, 8) + 1) * 1024 + 96) * 4
-            self.nslab = max(1, min(self.nslab, (8 << 30) // per))
-        self.nslab_2 = lib.wn_layer_bwd2_slabs(B, T)
-        self.nslab_s = lib.wn_stack_bwd_slabs(B, T, self.stack_variant) \
-            if self.stack_bwd else 0
-        alloc('wimg', (L, lib.wn_layer_bwd2_wimg_floats()))
-        if net.blocked:
-            # channel-block path: one slab region per (input, output) block
-            # pair of ONE layer (wavenet/blocked.py); the per-layer slabs of the
-            # 32-channel kernels are not used
-            alloc('pslabs', (CB * CB, self.nslab,
-                             (2 * min(net.KW, 8) + 1) * 1024 + 96))
-            alloc('lslabs', (1, 1, 4))
-        else:
-            alloc('lslabs', (L, max(self.nslab, self.nslab_2,
-                                    self.nslab_s), net.LAYER_BLOCK))
-        need = 0
-        self.splits = {}
-        for key, (mw, nw) in dict(post2=(S, Q), post1=(S, S), skip=(L * CHn, S),
-                                  causal=(Q, CH)).items():
-            sp = lib.wn_gemm_tn_splits(N, mw, nw, 1 if key == 'causal' else 0)
-            self.splits[key] = sp
-            need = max(need, sp * lib.wn_gemm_tn_slab_floats(mw, nw))
-        need_tn = need
-        need = max(need, lcond.alloc_workspace(net, self, alloc, True))
-        # scalar-input causal wgrad: [splits][initial_filter_width][32] slabs
-        need = max(need, max(256, self.splits['causal'])
-                   * max(32, net.initial_filter_width) * CH)
-        self.nslab_c = lib.wn_causal_wgrad_slabs(N)
-        need = max(need, self.nslab_c * 2 * Q * CH)
-        alloc('slabs', (need,))
-        alloc('slabs_tn', (need_tn,))     # TN GEMMs on the side stream
-        self.ev_fork = torch.cuda.Event() if dev.type == 'cuda' else None
-        self.ev_join = torch.cuda.Event() if dev.type == 'cuda' else None
-        self.dsum = alloc('dsum', (L, B, 2 * CHn)) if net.G else None
-        self.gc_part = alloc('gc_part', (L, B, net.G)) if net.G else None
-        # per-tile column sums of da: [L][tiles][64] for 32-row tiles (the
-        # per-layer kernels, wn_stack_bwd on big batches) or 16-row tiles
-        # (wn_stack_bwd on small ones, wn_stack_tile_rows): two views of one buffer
-        self.stack_rows = lib.wn_stack_tile_rows(B, T, self.stack_variant)
-        nt16 = B * ((T + 15) // 16)
-        if net.G:
-            buf = alloc('tilesum_buf', (L * nt16 * 64,))
-            self.tilesum = buf[:L * ntiles * 64].view(L, ntiles, 64)
-            self.tilesum16 = buf.view(L, nt16, 64)
-        else:
-            self.tilesum = self.tilesum16 = None
-        self.dsum_part = alloc(
-            'dsum_part', (B * lib.wn_colsum_clip_chunks(T) * 64,)) \
-            if net.G else None
-        alloc('l2_parts', (lib.wn_l2_partials_count(),))
-        alloc('l2', (1,), fill=0.0)
 
 
 def check_lengths(lengths, loss_denominator, B, T, what):
@@ -799,53 +593,10 @@ class WaveNetModel(object):
         """wn_stack_bwd covers what wn_layer_bwd2 covers."""
         return bool(self.stack_bwd and self._stack_ok())
 
-    def _step_path(self, ws, backward, l2=False):
-        """The StepPath of one call on workspace `ws`, from the model's
-        switches as they are now and the ones `ws` froze (stack_bwd, the
-        variant word).  l2: L2 regularisation is on (it adds to the whole
-        bucket after the backward pass: the tail all-reduce must wait)."""
-        layers, lc = self._layer_path(), '_lc' if self.Lc else ''
-        fwd = layers
-        if self.stack_fwd and self._stack_ok():
-            # (small batches: the skip sum inside the stack launch)
-            skip = (self.stack_fwd_skip and self.gemm_mode == 'fp32' and
-                    not self.residual_postproc and ws.fwd_skip_ok)
-            fwd = 'stack_skip' if skip else 'stack' + lc
-        if not backward:
-            return StepPath(fwd, 0, None, False, False, False, None,
-                            self.gemm_mode, ws.stack_variant)
-        bwd = layers
-        if layers == 'layer':
-            bwd = 'stack' + lc if self._stack_bwd_ok() and ws.stack_bwd \
-                else 'layer2'
-        if self.Lc and bwd != 'stack_lc':
-            # (a training workspace reserved while stack_bwd was off)
-            raise NotImplementedError(self.LC_SUPPORTED)
-        from . import parallel
-        early = bool(self.dp_overlap_allreduce and not l2 and
-                     parallel.is_distributed())
-        causal = (None if layers == 'blocked' else 'scalar' if self.scalar_input
-                  else 'segsum' if self.KW == 2 and self.Q <= 256 else 'onehot')
-        return StepPath(fwd, 2 if layers == 'layer' else 1, bwd,
-                        fwd.startswith('stack') and bwd.startswith('stack'),
-                        self._overlap_tn_on(ws), early, causal,
-                        self.gemm_mode, ws.stack_variant)
-
-    def _early_allreduce(self):
-        from . import parallel
-        _lib.call_py(lambda: parallel.begin_tail_allreduce(self))
-
-    def _side_stream(self):
-        if getattr(self, '_side', None) is None:
-            # lower priority than the default stream: the residual-stack
-            # kernels on the main stream are the critical path
-            self._side = torch.cuda.Stream(device=self.device, priority=0)
-        return self._side
-
     def check_device_errors(self):
         """Raise if a persistent stack launch recorded an expired dependency
         wait (its control word 3; the loss of that step is NaN by
-        construction, see _Workspace.loss_parts).  Synchronises the device:
+        construction, see workspace.py, loss_parts).  Synchronises the device:
         meant for the moment a caller sees a non-finite loss."""
         for ws in self._ws.values():
             for name in ('stack_ctl', 'stack_ctl_b'):
@@ -881,43 +632,10 @@ class WaveNetModel(object):
                 'no CPU fallback' % self.device)
 
     def _workspace(self, B, T, training):
-        key = (B, T, bool(training))
-        ws = self._ws.get(key)
-        if ws is not None and training and self._layer_path() != 'layer' \
-                and not ws.legacy:
-            self._ws = {}          # switched to a legacy backward: re-allocate
-            ws = None
-        if ws is not None:
-            return ws
-        # carve out of a resident larger workspace of the same batch size
-        for (b, t, tr), cand in list(self._ws.items()):
-            if cand.capacity == cand.N and b == B and B * T <= cand.capacity \
-                    and (tr or not training):
-                ws = _Workspace(self, B, T, training, parent=cand)
-                break
-        if ws is None:
-            # grow geometrically (the naive generation path asks for T, T+1,
-            # ... up to its window) and keep ONE owner per kind resident: a
-            # training step and forward-only calls of another length do not
-            # evict each other's buffers and launch plans
-            prev = [w for (b, t, tr), w in self._ws.items()
-                    if w.capacity == w.N and tr == bool(training) and b == B]
-            t_alloc = T
-            if prev and not training:
-                t_alloc = max(T, min(2 * max(w.T for w in prev), 1 << 20))
-            self._ws = {k: w for k, w in self._ws.items()
-                        if w.training != bool(training)}
-            owner = _Workspace(self, B, t_alloc, training)
-            self._ws[(B, t_alloc, bool(training))] = owner
-            ws = owner if t_alloc == T else \
-                _Workspace(self, B, T, training, parent=owner)
-        self._ws[key] = ws
-        if len(self._ws) > 64:        # views are cheap but unbounded otherwise
-            owners = {k: v for k, v in self._ws.items()
-                      if v.capacity == v.N}
-            self._ws = owners
-            self._ws[key] = ws
-        return ws
+        return workspace.get(self, B, T, training)
+
+    def _step_path(self, ws, backward, l2=False):
+        return train_pass.step_path(self, ws, backward, l2)
 
     def reserve(self, batch_size, max_samples, training=False):
         """Allocate the workspace for up to `max_samples` samples per clip now
@@ -953,507 +671,6 @@ class WaveNetModel(object):
     def _layer_block(self, flat, l):
         o, _ = self.segments['layers']
         return flat[o + l * self.layer_stride: o + (l + 1) * self.layer_stride]
-
-    def _bias_fg(self, ws_bias, ids, B):
-        """Per-(layer, clip) filter|gate bias (+ GC 1x1 conv of the broadcast
-        embedding, model.py:272-290).  Returns (tensor or None, clip stride)."""
-        if not self.use_biases and ids is None:
-            return None, 0
-        nb = B if ids is not None else 1
-        W2 = 2 * self.CHn                  # filter | gate, padded channels
-        out = ws_bias.view(-1)[:self.L * nb * W2].view(self.L, nb, W2)
-        emb = self._seg(self.params, 'emb') if ids is not None else None
-        _lib.call('wn_gc_bias', _lib.ptr(self._layer_block(self.params, 0)),
-                  self.layer_stride, self.OFF_BF, self.OFF_GC, self.G or 0,
-                  _lib.ptr(emb), self.card or 0, _lib.ptr(ids), _lib.ptr(out),
-                  self.L, nb, self.CHn, _lib.stream())
-        return out, (W2 if ids is not None else 0)
-
-    def _nn_seq(self, calls):
-        """A sequence of row-wise dependent wn_gemm_nn calls (argument tuples
-        without the stream), one launch each.  (Round 4 also ran them as ONE
-        persistent launch with row-block dependencies inside: bitwise equal,
-        worth at most 0.4 % of a B = 8 step and a loss at small batches;
-        removed in round 5, DESIGN.md.)"""
-        st = _lib.stream()
-        for c in calls:
-            self._nn(*(c + (st,)))
-
-    def _nn(self, *args):
-        """wn_gemm_nn (or, when `gemm_mode` asks for it, wn_gemm_nn_split),
-        optionally bracketed by HIP events on the launch stream (bench.py's
-        live roofline measurement)."""
-        name = 'wn_gemm_nn'
-        if self.gemm_mode != 'fp32':
-            nprod = {'bf16x3': 3, 'bf16x6': 6, 'bf16x9': 9}[self.gemm_mode]
-            M, N, K = args[-5], args[-4], args[-3]
-            if K % 16 == 0:
-                # one scratch buffer per WEIGHT (its address), not per shape:
-                # equal-shaped GEMMs never share pieces
-                key = (args[4], K, N)
-                buf = self._wsplit.get(key)
-                if buf is None:
-                    nb = _lib.load().wn_gemm_split_w_bytes(K, N)
-                    buf = torch.empty(nb // 4, dtype=torch.int32,
-                                      device=self.device)
-                    self._wsplit[key] = buf
-                name = 'wn_gemm_nn_split'
-                args = args[:-1] + (_lib.ptr(buf), nprod, args[-1])
-        k = -7 if name == 'wn_gemm_nn_split' else -5
-        _lib.call_timed(name, args, 2.0 * args[k] * args[k + 1] * args[k + 2],
-                        self._gemm_events)
-
-    # ------------------------------------------------------------ launch plans
-    def _stage_ids(self, ws, ids):
-        """GC ids into a workspace-owned buffer, so that recorded launch
-        arguments never point at a caller's temporary."""
-        if ids is None:
-            return None
-        if ids.data_ptr() != ws.gc_ids.data_ptr():
-            ws.gc_ids.copy_(ids)
-        return ws.gc_ids
-
-    def _run_pass(self, tag, ws, ids, path):
-        """The forward ('fwd') or backward ('bwd') pass through a recorded
-        launch plan (see _lib.record), keyed by the call's StepPath."""
-        eager = self._forward_eager if tag == 'fwd' else self._backward_eager
-        ids = self._stage_ids(ws, ids)
-        if not self.use_launch_plans or (tag == 'bwd' and path.bwd == 'blocked'):
-            # (the channel-block backward's gradient-block copies are torch
-            # ops a launch plan cannot replay)
-            return eager(ws, ids, path)
-        key = (tag, path, ids is not None, _lib.stream(),
-               self.params.data_ptr(), self.grads.data_ptr())
-        plan = ws.plans.get(key, 0)
-        if plan == 0:                 # first use of this workspace: eager
-            ws.plans[key] = None
-            eager(ws, ids, path)
-        elif plan is None:            # second use: record while executing
-            with _lib.record() as rec:
-                eager(ws, ids, path)
-            ws.plans[key] = rec.plan
-        else:
-            _lib.replay(plan, self._gemm_events)
-
-    # ------------------------------------------------------------------ forward
-    def _forward_eager(self, ws, ids, path):
-        """_create_network (model.py:389-442) on codes ws.q -> ws.logits."""
-        st = _lib.stream()
-        B, T, N, L, S, Q = ws.B, ws.T, ws.N, self.L, self.S, self.Q
-        P = self.params
-        wc = self._seg(P, 'causal')
-        for cb in range(self.CB):              # one plane per channel block
-            if self.scalar_input:
-                _lib.call('wn_scalar_causal_fwd', _lib.ptr(ws.audio),
-                          _lib.ptr(wc[cb * CH:]), self.CHn, _lib.ptr(ws.X[cb]),
-                          B, T, self.initial_filter_width, st)
-            else:
-                _lib.call('wn_causal_gather', _lib.ptr(ws.q),
-                          _lib.ptr(wc[cb * CH:]), _lib.ptr(ws.X[cb]), B, T, Q,
-                          self.KW, self.CHn, st)
-        bias, bstride = self._bias_fg(ws.bias_fg, ids, B)
-        save_ts = path.save_ts
-        if path.fwd == 'blocked':
-            from . import blocked
-            blocked.forward_layers(self, ws, bias, bstride, bool(save_ts), st)
-        elif path.fwd.startswith('stack'):
-            self._fwd_stack(ws, path, bias, bstride, st)
-        else:                      # 'layer' / 'layer_k': one launch per layer
-            for l, d in enumerate(self.dilations):
-                last = l == L - 1
-                fargs = (_lib.ptr(ws.X[l]),
-                         None if last else _lib.ptr(ws.X[l + 1]),
-                         _lib.ptr(ws.Z[l]),
-                         _lib.ptr(ws.TH[l]) if save_ts == 1 else None,
-                         _lib.ptr(ws.SG[l]) if save_ts else None,
-                         _lib.ptr(self._layer_block(P, l)),
-                         None if bias is None else _lib.ptr(bias[l]), bstride,
-                         B, T, int(d))
-                if path.fwd == 'layer_k':
-                    _lib.call('wn_layer_fwd_k', *fargs, self.KW,
-                              0 if last else 1, 1 if save_ts else 0, st)
-                else:
-                    _lib.call('wn_layer_fwd', *fargs, 0 if last else 1,
-                              int(save_ts), st)
-        fuse_skip = path.fwd == 'stack_skip'
-        bsum = None
-        if self.use_biases and not fuse_skip:
-            _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), L, S,
-                      _lib.ptr(ws.bsum), st)
-            bsum = ws.bsum
-        # total = sum_l z_l * Ws_l (+ sum_l bs_l); h1 = relu(total)
-        LP, C = L * self.CB, self.CHn      # planes, padded channels
-        b1 = self._seg(P, 'post1_b') if self.use_biases else None
-        b2 = self._seg(P, 'post2_b') if self.use_biases else None
-        rp = self.residual_postproc
-        skip_gemm = [] if fuse_skip else [
-            (_lib.ptr(ws.Z), 0, LP, N * CH,
-             _lib.ptr(self._seg(P, 'skip_w')), S, _lib.ptr(bsum), None, 0,
-             None, 0, _lib.ptr(ws.h1), S, 0, 0,
-             _lib.ptr(ws.total) if self.residual_postproc else None,
-             N, S, L * C, 1)]
-        self._nn_seq(skip_gemm + [
-            (_lib.ptr(ws.h1), S, 0, 0,
-             _lib.ptr(self._seg(P, 'post1_w')), S, _lib.ptr(b1), None, 0,
-             _lib.ptr(ws.total) if rp else None, S, _lib.ptr(ws.h2), S, 0,
-             0, _lib.ptr(ws.c1) if (rp and ws.training) else None,
-             N, S, S, 1),
-            (_lib.ptr(ws.h2), S, 0, 0,
-             _lib.ptr(self._seg(P, 'post2_w')), Q, _lib.ptr(b2), None, 0,
-             None, 0, _lib.ptr(ws.logits), Q, 0, 0, None, N, Q, S, 0)])
-
-    def _fwd_stack(self, ws, path, bias, bstride, st):
-        """All L layers in one persistent launch (csrc/wn_stack.hip) behind
-        their transposed weight images (wn_stack_pack, one small launch)."""
-        B, T, N, L, S = ws.B, ws.T, ws.N, self.L, self.S
-        P = self.params
-        _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(P, 0)),
-                  self.layer_stride, _lib.ptr(ws.wimg_f),
-                  _lib.ptr(ws.wimg_b) if path.pack_both else None, L, st)
-        save = path.save_ts != 0
-        stack_args = (_lib.ptr(ws.X), _lib.ptr(ws.Z),
-                      _lib.ptr(ws.SG) if save else None,
-                      _lib.ptr(ws.wimg_f),
-                      None if bias is None else _lib.ptr(bias),
-                      0 if bias is None else bias.shape[1] * bias.shape[2],
-                      bstride, _lib.ptr(self._dil_dev),
-                      _lib.ptr(ws.stack_flags), _lib.ptr(ws.stack_ctl),
-                      _lib.ptr(ws.loss_parts),
-                      L, B, T, 1 if save else 0, ws.stack_variant)
-        # (flops 0: timed in bench.py's instrumented pass for its HBM roofline)
-        if path.fwd == 'stack_skip':
-            # small batches: the skip sum h1 = relu(sum_l z_l Ws_l + sum_l bs_l)
-            # inside the stack launch (wn_stack_fwd_skip: a partner wave per
-            # tile; the launch's matrix pipe is three quarters idle otherwise)
-            if getattr(ws, 'skimg', None) is None:
-                ws.skimg = torch.empty(
-                    int(_lib.load().wn_stack_skip_img_floats(L)),
-                    dtype=torch.float32, device=self.device)
-            bsum_f = None
-            if self.use_biases:
-                _lib.call('wn_sum_rows', _lib.ptr(self._seg(P, 'skip_b')), L,
-                          S, _lib.ptr(ws.bsum), st)
-                bsum_f = ws.bsum
-            _lib.call('wn_stack_skip_pack', _lib.ptr(self._seg(P, 'skip_w')),
-                      L, _lib.ptr(ws.skimg), st)
-            _lib.call_timed('wn_stack_fwd_skip', stack_args + (
-                _lib.ptr(ws.skimg), _lib.ptr(bsum_f), _lib.ptr(ws.h1), st),
-                0.0, self._gemm_events)
-        elif path.fwd == 'stack_lc':
-            # local conditioning: the per-row filter | gate addends of all
-            # layers, lc [N][Lcp] x lc_w [Lcp][L * 64], then the stack
-            # launch that adds them (32-row tiles: the workspace's variant)
-            W64 = L * 64
-            _lib.call_timed('wn_gemm_nn', (
-                _lib.ptr(ws.lc), self.Lcp, 0, 0,
-                _lib.ptr(self._seg(P, 'lc_w')), W64, None, None, 0, None,
-                0, _lib.ptr(ws.lc_add), W64, 0, 0, None, N, W64, self.Lcp,
-                0, st), 2.0 * N * W64 * self.Lcp, self._gemm_events)
-            _lib.call_timed('wn_stack_fwd_lc', stack_args + (
-                _lib.ptr(ws.lc_add), W64, st), 0.0, self._gemm_events)
-        else:
-            _lib.call_timed('wn_stack_fwd', stack_args + (st,), 0.0,
-                            self._gemm_events)
-
-    # ------------------------------------------------------------------ backward
-    def _backward_eager(self, ws, ids, path):
-        """Hand-written gradient of loss() (the reference uses TF autodiff of
-        model.py:628-685).  Consumes ws.logits == dlogits (in place)."""
-        st = _lib.stream()
-        self._bwd_post(ws, path, st)
-        if path.bwd == 'blocked':
-            # channel-block path: residual stack, causal layer and global
-            # conditioning gradients (wavenet/blocked.py)
-            from . import blocked
-            if path.overlap_tn:
-                main_s = torch.cuda.current_stream()
-                _lib.call_py(lambda: main_s.wait_event(ws.ev_join))
-            blocked.backward_layers(self, ws, ids, st)
-            return
-        # residual stack, last layer first, down to dL/dx_0
-        run = {'layer2': self._bwd_layer2,
-               'layer_k': self._bwd_layer_k}.get(path.bwd, self._bwd_stack)
-        self._backward_tail(ws, ids, path, run(ws, path, st))
-
-    def _bwd_post(self, ws, path, st):
-        """The data gradients first -- dc1 = (dlogits W2^T) * [c1 > 0],
-        dtotal = (dc1 W1^T) * [total > 0] (+ dh2 when residual_postproc),
-        dZ planes = dtotal Ws_all^T -- as ONE chained launch (a 128-row block
-        of a GEMM starts when that row block of the previous one is stored),
-        then the three weight-gradient (TN) GEMMs, whose operands all exist
-        by then: dW2 = h2^T dlogits, dW1 = h1^T dc1, dWs_all = Z^T dtotal
-        (+ column sums = the bias gradients)."""
-        N, L, S, Q = ws.N, self.L, self.S, self.Q
-        P, Gr = self.params, self.grads
-        rp = self.residual_postproc
-        dlog = ws.logits
-        LP, C = L * self.CB, self.CHn      # planes, padded channels
-        _lib.call('wn_transpose', _lib.ptr(self._seg(P, 'post2_w')), S, Q, Q,
-                  _lib.ptr(ws.w2t), S, st)
-        _lib.call('wn_transpose', _lib.ptr(self._seg(P, 'post1_w')), S, S, S,
-                  _lib.ptr(ws.w1t), S, st)
-        _lib.call('wn_transpose', _lib.ptr(self._seg(P, 'skip_w')), L * C, S,
-                  S, _lib.ptr(ws.wst), L * C, st)
-        nn_dc1 = (_lib.ptr(dlog), Q, 0, 0, _lib.ptr(ws.w2t), S,
-                  None, _lib.ptr(ws.c1 if rp else ws.h2), S, None, 0,
-                  _lib.ptr(ws.dc1), S, 0, 0, _lib.ptr(ws.dh2) if rp else None,
-                  N, S, Q, 0)
-        nn_dtotal = (_lib.ptr(ws.dc1), S, 0, 0, _lib.ptr(ws.w1t), S,
-                     None, _lib.ptr(ws.h1), S, _lib.ptr(ws.dh2) if rp else None,
-                     S, _lib.ptr(ws.dtotal), S, 0, 0, None, N, S, S, 0)
-        nn_dz = (_lib.ptr(ws.dtotal), S, 0, 0, _lib.ptr(ws.wst),
-                 L * C, None, None, 0, None, 0, _lib.ptr(ws.dZ), 0, LP,
-                 N * CH, None, N, L * C, S, 0)
-        tns = [(_lib.ptr(ws.h2), S, 0, 0, _lib.ptr(dlog), Q, 'post2', S, Q,
-                _lib.ptr(self._seg(Gr, 'post2_w')),
-                _lib.ptr(self._seg(Gr, 'post2_b'))),
-               (_lib.ptr(ws.h1), S, 0, 0, _lib.ptr(ws.dc1), S, 'post1', S, S,
-                _lib.ptr(self._seg(Gr, 'post1_w')),
-                _lib.ptr(self._seg(Gr, 'post1_b'))),
-               # skip convs: dbs_l = colsum(dtotal) for every l
-               (_lib.ptr(ws.Z), 0, LP, N * CH, _lib.ptr(ws.dtotal), S, 'skip',
-                L * C, S, _lib.ptr(self._seg(Gr, 'skip_w')),
-                _lib.ptr(self._seg(Gr, 'skip_b')), L, S)]
-        if not path.overlap_tn:
-            self._nn_seq([nn_dc1, nn_dtotal, nn_dz])
-            for a in tns:
-                self._tn(ws, path, st, ws.slabs, *a)
-            if path.early_allreduce:
-                # skip / post-processing gradients are complete on this stream:
-                # their all-reduce runs beside the backward stack
-                self._early_allreduce()
-            return
-        # small batches: the TN GEMMs run on a side stream beside the dZ GEMM
-        # and the backward stack, so the dZ GEMM stays a launch of its own
-        # behind the fork.  The fork: everything the three TN GEMMs read
-        # exists now (forking behind the dZ GEMM instead, or another order of
-        # the three, changes nothing at B = 1: 1.80 ms either way)
-        self._nn_seq([nn_dc1, nn_dtotal])
-        main_s = torch.cuda.current_stream()
-        side_s = self._side_stream()
-        _lib.call_py(lambda: (ws.ev_fork.record(main_s),
-                              side_s.wait_event(ws.ev_fork)))
-        for a in tns:
-            self._tn(ws, path, side_s.cuda_stream, ws.slabs_tn, *a)
-        _lib.call_py(lambda: ws.ev_join.record(side_s))
-        self._nn(*(nn_dz + (st,)))
-
-    def _tn(self, ws, path, st, slabs, A, lda, a_planes, a_pstride, Gm, ldg,
-            key, mw, nw, dst, dst_bias, replicate=1, rep_stride=0):
-        """dst = A^T Gm (+ its column sums into dst_bias): one wn_gemm_tn into
-        the per-split `slabs` on stream `st`, then their fixed-order sum."""
-        lib = _lib.load()
-        N = ws.N
-        ub = 1 if self.use_biases else 0
-        sp = ws.splits[key]
-        if path.overlap_tn and 256 < ws.B * ((ws.T + 31) // 32) <= 512:
-            sp = max(1, int(sp * TN_SIDE_SPLIT_FRAC))
-        sl = lib.wn_gemm_tn_slab_floats(mw, nw)
-        # the slabs' matrix and column sums go through ONE reduction launch
-        # when the shapes allow; then the column sums are "spread" too:
-        # every tile row of a split sums its share (wn_gemm_tn,
-        # want_colsum = 2)
-        mt = bool(ub and dst_bias is not None and (mw * nw) % 4 == 0 and
-                  nw % 4 == 0 and sl % 4 == 0 and rep_stride % 4 == 0)
-        tr = int(lib.wn_gemm_tn_tail_rows(mw, nw)) \
-            if mt and path.gemm_mode == 'fp32' else 1
-        if path.gemm_mode != 'fp32' and N % 16 == 0:
-            # opt-in split-bf16 products (fewer, larger splits)
-            sp = min(sp, lib.wn_gemm_tn_splits(N, mw, nw, 2))
-            _lib.call('wn_gemm_tn_split', A, lda, a_planes, a_pstride, Gm,
-                      ldg, _lib.ptr(slabs), sp, N, mw, nw, ub,
-                      int(path.gemm_mode[-1]), st)
-        else:
-            _lib.call_timed('wn_gemm_tn',
-                            (A, lda, a_planes, a_pstride, None, 0, ws.T,
-                             Gm, ldg, _lib.ptr(slabs), sp, N, mw, nw,
-                             2 if tr > 1 else ub,
-                             st), 2.0 * N * mw * nw, self._gemm_events)
-        if mt:
-            # matrix and column sums (bias gradient) in one launch
-            _lib.call('wn_reduce_slabs_mt', _lib.ptr(slabs), sp, sl,
-                      mw * nw, dst, nw, dst_bias, replicate, rep_stride,
-                      tr, st)
-            return
-        _lib.call('wn_reduce_slabs', _lib.ptr(slabs), sp, sl, 1, 0, 0,
-                  mw * nw, dst, 0, 1, 0, st)
-        if ub and dst_bias is not None:
-            _lib.call('wn_reduce_slabs', _lib.ptr(slabs), sp, sl, 1, 0,
-                      mw * nw, nw, dst_bias, 0, replicate, rep_stride, st)
-
-    def _bwd_stack(self, ws, path, st):
-        """All L layers in one persistent launch (csrc/wn_stack.hip)."""
-        B, T, L = ws.B, ws.T, self.L
-        tsum = None if ws.dsum is None else \
-            ws.tilesum16 if ws.stack_rows == 16 else ws.tilesum
-        if not path.pack_both:
-            _lib.call('wn_stack_pack', _lib.ptr(self._layer_block(self.params, 0)),
-                      self.layer_stride, None, _lib.ptr(ws.wimg_b), L, st)
-        bargs = (
-            _lib.ptr(ws.X), _lib.ptr(ws.Z),
-            _lib.ptr(ws.SG), _lib.ptr(ws.dZ), _lib.ptr(ws.DX),
-            ws.N * CH if ws.keep_dx else 0,
-            _lib.ptr(ws.DQ), _lib.ptr(ws.wimg_b), _lib.ptr(ws.lslabs),
-            ws.lslabs.shape[1] * self.LAYER_BLOCK,
-            None if tsum is None else _lib.ptr(tsum),
-            _lib.ptr(self._dil_dev), _lib.ptr(ws.stack_flags_b),
-            _lib.ptr(ws.stack_ctl_b),
-            _lib.ptr(ws.loss_parts[1:]), L, B, T, ws.stack_variant)
-        if path.bwd == 'stack_lc':
-            # ... that also stores da_f | da_g of every row and layer
-            _lib.call_timed('wn_stack_bwd_lc', bargs + (
-                _lib.ptr(ws.lc_da), L * 64, st), 0.0, self._gemm_events)
-        else:
-            _lib.call_timed('wn_stack_bwd', bargs + (st,), 0.0,
-                            self._gemm_events)
-        return ws.DX[0]
-
-    def _bwd_layer2(self, ws, path, st):
-        """One wn_layer_bwd2 launch per layer, chained through dx only."""
-        B, T, L, P = ws.B, ws.T, self.L, self.params
-        tsum = None if ws.dsum is None else ws.tilesum
-        # transposed weight images of all layers (the kernels DMA them
-        # into LDS): one small launch per step
-        _lib.call('wn_layer_bwd2_pack', _lib.ptr(self._layer_block(P, 0)),
-                  self.layer_stride, _lib.ptr(ws.wimg), L, st)
-        dxin, xp = None, 0
-        for l in range(L - 1, -1, -1):
-            dxo = ws.dx[xp]
-            _lib.call('wn_layer_bwd2', _lib.ptr(ws.X[l]), _lib.ptr(ws.Z[l]),
-                      _lib.ptr(ws.SG[l]), _lib.ptr(ws.dZ[l]),
-                      _lib.ptr(dxin), _lib.ptr(dxo),
-                      _lib.ptr(self._layer_block(P, l)),
-                      _lib.ptr(ws.wimg[l]), _lib.ptr(ws.lslabs[l]),
-                      None if tsum is None else _lib.ptr(tsum[l]),
-                      B, T, int(self.dilations[l]), st)
-            dxin, xp = dxo, 1 - xp
-        return dxin
-
-    def _bwd_layer_k(self, ws, path, st):
-        """Generic filter width (wn_layer_*_k; also a K = 2 model with
-        `generic_layers` forced, tests): phase A of layer l - 1 and phase B
-        of layer l per launch, pre-activation gradients through two ping-pong
-        plane pairs, weight gradients per layer into slabs."""
-        B, T, L, P = ws.B, ws.T, self.L, self.params
-
-        def da(p):
-            return ws.da[p][0], ws.da[p][1]
-
-        def layer_bwd(*a):           # (..., B, T, d, do_b, do_a, stream)
-            _lib.call('wn_layer_bwd_k', *a[:14], self.KW, *a[14:16], 1, 0, a[16])
-
-        def layer_wgrad(*a):         # (..., nslab, B, T, d, stream)
-            _lib.call('wn_layer_wgrad_k', *a[:10], self.KW, 0, self.KW, 1, 0, a[10])
-        cur = 0
-        f, g = da(cur)
-        # phase A of the last layer (no gradient flows into its x' output)
-        layer_bwd(None, None, None, None, None,
-                  _lib.ptr(ws.dZ[L - 1]), _lib.ptr(ws.TH[L - 1]),
-                  _lib.ptr(ws.SG[L - 1]),
-                  _lib.ptr(self._layer_block(P, L - 1)), _lib.ptr(f),
-                  _lib.ptr(g), B, T, 1, 0, 1, st)
-        dxin, xp = None, 0    # dL/dx' of layer l (None for the last layer)
-        for l in range(L - 1, -1, -1):
-            d = int(self.dilations[l])
-            f, g = da(cur)
-            dxo = ws.dx[xp]
-            layer_wgrad(_lib.ptr(ws.X[l]), _lib.ptr(f), _lib.ptr(g),
-                        None if dxin is None else _lib.ptr(ws.Z[l]),
-                        None if dxin is None else _lib.ptr(dxin),
-                        _lib.ptr(ws.lslabs[l]), ws.nslab, B, T, d, st)
-            if ws.dsum is not None:
-                _lib.call('wn_colsum_clip', _lib.ptr(f), _lib.ptr(g), B, T,
-                          _lib.ptr(ws.dsum_part), _lib.ptr(ws.dsum[l]), st)
-            if l > 0:
-                fn, gn = da(1 - cur)
-                layer_bwd(_lib.ptr(f), _lib.ptr(g),
-                          None if dxin is None else _lib.ptr(dxin),
-                          _lib.ptr(dxo), _lib.ptr(self._layer_block(P, l)),
-                          _lib.ptr(ws.dZ[l - 1]), _lib.ptr(ws.TH[l - 1]),
-                          _lib.ptr(ws.SG[l - 1]),
-                          _lib.ptr(self._layer_block(P, l - 1)), _lib.ptr(fn),
-                          _lib.ptr(gn), B, T, d, 1, 1, st)
-                cur = 1 - cur
-            else:
-                layer_bwd(_lib.ptr(f), _lib.ptr(g),
-                          None if dxin is None else _lib.ptr(dxin),
-                          _lib.ptr(dxo), _lib.ptr(self._layer_block(P, l)),
-                          None, None, None, None, None, None, B, T, d, 1, 0,
-                          st)
-            dxin, xp = dxo, 1 - xp
-        return dxin
-
-    def _backward_tail(self, ws, ids, path, dxin):
-        """After the residual stack: slab reductions of the layer-block
-        gradients, causal-layer and global-conditioning gradients."""
-        if path.overlap_tn:
-            main_s = torch.cuda.current_stream()
-            _lib.call_py(lambda: main_s.wait_event(ws.ev_join))     # join
-            if path.early_allreduce:
-                # (small batches: the side stream's weight-gradient GEMMs have
-                # just joined; the tail's all-reduce runs beside the slab
-                # reductions and the causal / conditioning gradients)
-                self._early_allreduce()
-        st = _lib.stream()
-        B, T, N, L, S, Q = ws.B, ws.T, ws.N, self.L, self.S, self.Q
-        P, Gr = self.params, self.grads
-        ub = 1 if self.use_biases else 0
-        lib = _lib.load()
-        stack = path.bwd.startswith('stack')
-        if path.bwd != 'layer_k' and ws.dsum is not None:
-            # per-clip sums of da_l for every layer from the per-tile sums the
-            # fused kernel wrote (fixed order over a clip's tiles)
-            tile_rows = ws.stack_rows if stack else 32
-            tpc = (T + tile_rows - 1) // tile_rows
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.tilesum), tpc, 64, L * B,
-                      tpc * 64, 0, 64, _lib.ptr(ws.dsum), 64, 1, 0, st)
-        # layer-block gradients: fixed-order sum of the per-workgroup slabs
-        nslab = ws.nslab_s if stack else \
-            ws.nslab_2 if path.bwd == 'layer2' else ws.nslab
-        lo, _ = self.segments['layers']
-        _lib.call('wn_reduce_slabs', _lib.ptr(ws.lslabs), nslab,
-                  self.LAYER_BLOCK, L, ws.lslabs.shape[1] * self.LAYER_BLOCK,
-                  0, self.LAYER_BLOCK if ub else self.LAYER_W,
-                  _lib.ptr(Gr[lo:]),
-                  self.layer_stride, 1, 0, st)
-        # causal layer: dWc[1][v] = sum_t [q[t]==v] dx0[t]; dWc[0][v] likewise
-        # with q[t-1]
-        gc_ = self._seg(Gr, 'causal')
-        if path.causal_wgrad == 'scalar':
-            K0 = self.initial_filter_width
-            sp = ws.splits['causal']
-            _lib.call('wn_scalar_causal_wgrad', _lib.ptr(ws.audio),
-                      _lib.ptr(dxin), _lib.ptr(ws.slabs), sp, B, T, K0, st)
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, K0 * CH, 1,
-                      0, 0, K0 * CH, _lib.ptr(gc_), 0, 1, 0, st)
-        elif path.causal_wgrad == 'segsum':
-            ns = ws.nslab_c
-            _lib.call('wn_causal_wgrad', _lib.ptr(ws.q), _lib.ptr(dxin),
-                      _lib.ptr(ws.slabs), ns, B, T, Q, st)
-            _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), ns, 2 * Q * CH,
-                      1, 0, 0, 2 * Q * CH, _lib.ptr(gc_), 0, 1, 0, st)
-        else:
-            # (one-hot operand generated on the fly)
-            K = self.KW
-            for tap in range(K):
-                shift = (K - 1 - tap) + (K - 1) // 2
-                sp = ws.splits['causal']
-                sl = lib.wn_gemm_tn_slab_floats(Q, CH)
-                _lib.call('wn_gemm_tn', None, 0, 0, 0, _lib.ptr(ws.q), shift,
-                          T, _lib.ptr(dxin), CH, _lib.ptr(ws.slabs), sp, N, Q,
-                          CH, 0, st)
-                _lib.call('wn_reduce_slabs', _lib.ptr(ws.slabs), sp, sl, 1, 0,
-                          0, Q * CH, _lib.ptr(gc_[tap * Q * CH:]), 0, 1, 0, st)
-        if self.Lc:
-            lcond.backward(self, ws, st)
-        if ws.dsum is not None:
-            _lib.call('wn_gc_grad', _lib.ptr(self._layer_block(P, 0)),
-                      self.layer_stride, self.OFF_GC, self.G,
-                      _lib.ptr(self._seg(P, 'emb')), self.card, _lib.ptr(ids),
-                      _lib.ptr(ws.dsum), L, B,
-                      _lib.ptr(self._layer_block(Gr, 0)),
-                      _lib.ptr(self._seg(Gr, 'emb')), _lib.ptr(ws.gc_part),
-                      self.CHn, st)
 
     # ------------------------------------------------------------------ API
     def encode(self, input_batch, B=None):
@@ -1562,9 +779,9 @@ class WaveNetModel(object):
         lcond.fill(self, lc, ws)
         # (L2 adds lambda * params to the WHOLE bucket after the backward
         # pass: the tail must not have been summed over ranks before that)
-        path = self._step_path(ws, backward,
-                               l2=l2_regularization_strength is not None)
-        self._run_pass('fwd', ws, ids, path)
+        path = train_pass.step_path(
+            self, ws, backward, l2=l2_regularization_strength is not None)
+        train_pass.run_pass(self, 'fwd', ws, ids, path)
         quirk = 1 if self.tf_xent_zero_label_quirk else 0
         if mask is None:
             den = float(N)
@@ -1587,7 +804,7 @@ class WaveNetModel(object):
         loss = ws.loss[0] / den                         # reduce_mean, :666
         if backward:
             try:
-                self._run_pass('bwd', ws, ids, path)
+                train_pass.run_pass(self, 'bwd', ws, ids, path)
             except BaseException:
                 # (a launch error after the tail's all-reduce was issued: join
                 # it, so that the next step does not find it dangling)
@@ -1660,7 +877,8 @@ class WaveNetModel(object):
             ws.audio.copy_(mu_law_decode(w, self.Q).reshape(-1))
         ids = self._gc_ids(global_condition, B)
         lcond.fill(self, lc, ws)
-        self._run_pass('fwd', ws, ids, self._step_path(ws, False))
+        train_pass.run_pass(self, 'fwd', ws, ids,
+                            train_pass.step_path(self, ws, False))
         out = torch.empty(self.Q, dtype=torch.float32, device=self.device)
         _lib.call('wn_softmax64_row', _lib.ptr(ws.logits[B * T - 1]), self.Q,
                   _lib.ptr(out), _lib.stream())
