@@ -104,6 +104,9 @@ def get_arguments(argv=None):
     p.add_argument('--gc_ids', type=str, default=None,
                    help='comma-separated global condition ids, one clip each '
                    '(sets --clips to their number)')
+    p.add_argument('--use_ema', type=_str_to_bool, default=False,
+                   help='generate from the checkpoint\'s exponential moving '
+                   'average of the weights (train.py --ema_decay)')
     a = p.parse_args(argv)
     if a.gc_ids is not None:
         a.gc_ids = [int(v) for v in a.gc_ids.split(',') if v.strip()]
@@ -185,6 +188,20 @@ def context_mismatch(net, sd):
 
 def main(argv=None):
     args = get_arguments(argv)
+    ckpt = None
+    if args.use_ema:
+        # (before any model is built: a checkpoint without EMA weights is
+        # refused whatever else the command line asks for)
+        if tf_checkpoint.checkpoint_format(args.checkpoint):
+            print('--use_ema true: a TensorFlow checkpoint holds no EMA '
+                  'weights.')
+            return 1
+        ckpt = torch.load(args.checkpoint, map_location='cpu')
+        if 'ema_variables' not in ckpt:
+            print('--use_ema true: the checkpoint {} holds no EMA weights '
+                  '(`ema_variables`); train with train.py --ema_decay.'
+                  .format(args.checkpoint))
+            return 1
     lc_rows, lc_scales, lc_ctx = None, None, None
     if args.lc_path is not None:
         if args.fast_generation and not args.lc_fast_generation:
@@ -242,7 +259,9 @@ def main(argv=None):
         # a checkpoint written by the reference itself (tf.train.Saver)
         tf_checkpoint.load_into(net, args.checkpoint)
     else:
-        sd = torch.load(args.checkpoint, map_location='cpu')['variables']
+        if ckpt is None:
+            ckpt = torch.load(args.checkpoint, map_location='cpu')
+        sd = ckpt['ema_variables' if args.use_ema else 'variables']
         if lc_rows is not None:
             why = upsampler_mismatch(net, sd) or context_mismatch(net, sd)
             if why:

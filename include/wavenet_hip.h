@@ -433,6 +433,51 @@ int wn_rmsprop(float* p, const float* g, float* ms, float* mom, long n,
                float lr, float decay, float momentum, float eps,
                float grad_scale, float l2, const float* l2_mask,
                void* stream);
+/* ---- global-norm gradient clipping (tf.clip_by_global_norm) and an
+ * exponential moving average of the weights (tf.train.
+ * ExponentialMovingAverage, no num_updates warm-up) inside the update.
+ *
+ * wn_grad_norm_partials writes wn_grad_norm_partials_count() (a constant)
+ * float64 sums of g[i]^2: partial k covers a contiguous range that depends on
+ * (n, count) only and is summed in a fixed order, no atomics -- the partials
+ * are a function of the bucket's bits and n, not of the device.  g 16-byte,
+ * partials 8-byte aligned, else WN_ERR_MISALIGNED.
+ *
+ * wn_*_clip: the update of wn_adam / wn_momentum / wn_rmsprop with
+ *   partials, nparts : the partials above (nparts == the count, else
+ *                      WN_ERR_BAD_SHAPE); NULL: no clipping
+ *   clip_norm        : positive and finite (else WN_ERR_BAD_SHAPE).  Every
+ *                      workgroup sums the partials in the same order in
+ *                      float64; norm = grad_scale * sqrt(sum), factor =
+ *                      clip_norm / max(norm, clip_norm), both float64; the
+ *                      gradient is scaled by grad_scale * (float)factor.
+ *                      norm <= clip_norm: factor is exactly 1 and the update
+ *                      is the plain entry point's bit for bit.  A non-finite
+ *                      norm gives a NaN factor, hence NaN parameters.
+ *   ema, ema_decay   : shadow weights [n], s -= (1 - decay) * (s - p_new) in
+ *                      float32 in the same pass; decay in [0, 1) (else
+ *                      WN_ERR_BAD_SHAPE); NULL: no EMA
+ *   norm_out         : one float, the norm before clipping (written only with
+ *                      partials); may be NULL. */
+int wn_grad_norm_partials_count(void);
+int wn_grad_norm_partials(const float* g, long n, double* partials,
+                          void* stream);
+int wn_adam_clip(float* p, const float* g, float* m, float* v, long n,
+                 float lr_t, float beta1, float beta2, float eps,
+                 float grad_scale, float l2, const float* l2_mask,
+                 const double* partials, int nparts, float clip_norm,
+                 float* ema, float ema_decay, float* norm_out, void* stream);
+int wn_momentum_clip(float* p, const float* g, float* acc, long n, float lr,
+                     float momentum, float grad_scale, float l2,
+                     const float* l2_mask, const double* partials, int nparts,
+                     float clip_norm, float* ema, float ema_decay,
+                     float* norm_out, void* stream);
+int wn_rmsprop_clip(float* p, const float* g, float* ms, float* mom, long n,
+                    float lr, float decay, float momentum, float eps,
+                    float grad_scale, float l2, const float* l2_mask,
+                    const double* partials, int nparts, float clip_norm,
+                    float* ema, float ema_decay, float* norm_out,
+                    void* stream);
 int wn_l2_partials_count(void);
 int wn_l2_partials(const float* p, long n, const float* mask, float* partials,
                    void* stream);

@@ -448,6 +448,155 @@ __global__ void l2_partials_kernel(const float* __restrict__ p, long n,
 }
 
 // ---------------------------------------------------------------------------
+// global-norm clipping (tf.clip_by_global_norm) and EMA weights
+// (tf.train.ExponentialMovingAverage) inside the optimizer launches.
+//
+// grad_norm_partials_kernel: GNORM_PARTS float64 sums of g[i]^2.  Partial k
+// covers elements [k * per, min(n, (k + 1) * per)), per = the multiple of 4
+// next above n / GNORM_PARTS; inside it thread t takes the 16-byte groups
+// t, t + 1024, ... in order, a wave is summed by a shuffle tree and the 16
+// wave sums in order.  Grid, block and ranges depend on (n, GNORM_PARTS) only:
+// the bits are a function of the bucket and n, not of the device.
+//
+// The *_clip kernels are the kernels above, element for element, behind a
+// prologue in which EVERY workgroup sums the same partials in the same order
+// (float64), forms  norm = grad_scale * sqrt(sum)  and
+// factor = clip_norm / max(norm, clip_norm)  (NaN for a non-finite norm, as
+// TensorFlow) and scales by  grad_scale * (float)factor  -- grad_scale itself
+// when norm <= clip_norm, so the update is then the plain kernel's bit for bit
+// -- and an epilogue  s -= (1 - decay) * (s - p_new)  on the shadow weights.
+// ---------------------------------------------------------------------------
+#define GNORM_PARTS 256
+#define GNORM_THREADS 1024
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;  // lane 0: the wave's sum
+}
+
+__global__ __launch_bounds__(GNORM_THREADS) void grad_norm_partials_kernel(
+    const float* __restrict__ g, long n, long per,
+    double* __restrict__ partials) {
+  __shared__ double red[GNORM_THREADS / 64];
+  const long lo = (long)blockIdx.x * per;
+  const long hi = lo + per < n ? lo + per : n;
+  double s = 0.0;
+  for (long i = lo + 4L * threadIdx.x; i < hi; i += 4L * GNORM_THREADS) {
+    if (i + 4 <= hi) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s += (double)v[e] * (double)v[e];
+    } else {
+      for (long j = i; j < hi; ++j) s += (double)g[j] * (double)g[j];
+    }
+  }
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < GNORM_THREADS / 64; ++w) t += red[w];
+    partials[blockIdx.x] = t;
+  }
+}
+
+// the effective gradient scale of a *_clip kernel (256 threads, all of them
+// call it); partials == nullptr: grad_scale
+__device__ __forceinline__ float clip_scale(const double* __restrict__ partials,
+                                            float clip_norm, float grad_scale,
+                                            float* __restrict__ norm_out) {
+  if (!partials) return grad_scale;
+  __shared__ double red[4];
+  const double s = wave_sum_f64(partials[threadIdx.x]);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const double sum = ((red[0] + red[1]) + red[2]) + red[3];
+  const double norm = (double)grad_scale * sqrt(sum);
+  const double cn = (double)clip_norm;
+  const double factor = isfinite(norm) ? cn / (norm > cn ? norm : cn)
+                                       : (double)NAN;
+  if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
+  return grad_scale * (float)factor;
+}
+
+__global__ __launch_bounds__(256) void adam_clip_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, long n, float lr_t, float b1, float b2, float eps,
+    float grad_scale, float l2, const float* __restrict__ l2_mask,
+    const double* __restrict__ partials, float clip_norm,
+    float* __restrict__ ema, float ema_decay, float* __restrict__ norm_out) {
+  const float scale = clip_scale(partials, clip_norm, grad_scale, norm_out);
+  const float keep = 1.f - ema_decay;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x) {
+    const float w = p[i];
+    float gg = g[i] * scale;
+    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
+    const float mm = b1 * m[i] + (1.f - b1) * gg;
+    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
+    m[i] = mm;
+    v[i] = vv;
+    const float pn = w - lr_t * mm / (sqrtf(vv) + eps);
+    p[i] = pn;
+    if (ema) {
+      const float s = ema[i];
+      ema[i] = s - keep * (s - pn);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void momentum_clip_kernel(
+    float* __restrict__ p, const float* __restrict__ g,
+    float* __restrict__ acc, long n, float lr, float mom, float grad_scale,
+    float l2, const float* __restrict__ l2_mask,
+    const double* __restrict__ partials, float clip_norm,
+    float* __restrict__ ema, float ema_decay, float* __restrict__ norm_out) {
+  const float scale = clip_scale(partials, clip_norm, grad_scale, norm_out);
+  const float keep = 1.f - ema_decay;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x) {
+    const float w = p[i];
+    float gg = g[i] * scale;
+    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
+    const float a = mom * acc[i] + gg;
+    acc[i] = a;
+    const float pn = w - lr * a;
+    p[i] = pn;
+    if (ema) {
+      const float s = ema[i];
+      ema[i] = s - keep * (s - pn);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void rmsprop_clip_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ ms,
+    float* __restrict__ mo, long n, float lr, float decay, float mom,
+    float eps, float grad_scale, float l2, const float* __restrict__ l2_mask,
+    const double* __restrict__ partials, float clip_norm,
+    float* __restrict__ ema, float ema_decay, float* __restrict__ norm_out) {
+  const float scale = clip_scale(partials, clip_norm, grad_scale, norm_out);
+  const float keep = 1.f - ema_decay;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x) {
+    const float w = p[i];
+    float gg = g[i] * scale;
+    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
+    const float s = decay * ms[i] + (1.f - decay) * gg * gg;
+    const float mm = mom * mo[i] + lr * gg / sqrtf(s + eps);
+    ms[i] = s;
+    mo[i] = mm;
+    const float pn = w - mm;
+    p[i] = pn;
+    if (ema) {
+      const float e = ema[i];
+      ema[i] = e - keep * (e - pn);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // global conditioning   (model.py:272-284, 533-562)
 // The GC 1x1 conv of a [B,1,G] embedding broadcast over T is a per-(clip,
 // layer) bias:  bias_fg[l][b][0:32] = bf_l + emb[id_b] * Wgcf_l, [32:64] gate.
@@ -1012,6 +1161,92 @@ int wn_rmsprop(float* p, const float* g, float* ms, float* mom, long n,
   hipLaunchKernelGGL(rmsprop_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
                      (hipStream_t)stream, p, g, ms, mom, n, lr, decay,
                      momentum, eps, grad_scale, l2, l2_mask);
+  return wn_check_launch();
+}
+
+int wn_grad_norm_partials_count(void) { return GNORM_PARTS; }
+
+int wn_grad_norm_partials(const float* g, long n, double* partials,
+                          void* stream) {
+  if (!g || !partials) return WN_ERR_NULL;
+  if (n <= 0) return WN_ERR_BAD_SHAPE;
+  if (!wn_aligned16(g) || ((uintptr_t)partials & 7)) return WN_ERR_MISALIGNED;
+  // elements per partial: a multiple of 4, so that every range starts on a
+  // 16-byte boundary
+  const long per = ((n + 4L * GNORM_PARTS - 1) / (4L * GNORM_PARTS)) * 4;
+  hipLaunchKernelGGL(grad_norm_partials_kernel, dim3(GNORM_PARTS),
+                     dim3(GNORM_THREADS), 0, (hipStream_t)stream, g, n, per,
+                     partials);
+  return wn_check_launch();
+}
+
+// the added arguments of the *_clip entry points
+static int clip_args_check(const double* partials, int nparts, float clip_norm,
+                           const float* ema, float ema_decay,
+                           const float* norm_out) {
+  if (partials) {
+    if (nparts != GNORM_PARTS) return WN_ERR_BAD_SHAPE;
+    if (!(clip_norm > 0.f) || !std::isfinite(clip_norm))
+      return WN_ERR_BAD_SHAPE;
+    if ((uintptr_t)partials & 7) return WN_ERR_MISALIGNED;
+  }
+  if (ema) {
+    if (!(ema_decay >= 0.f && ema_decay < 1.f)) return WN_ERR_BAD_SHAPE;
+    if ((uintptr_t)ema & 3) return WN_ERR_MISALIGNED;
+  }
+  if ((uintptr_t)norm_out & 3) return WN_ERR_MISALIGNED;
+  return WN_OK;
+}
+
+int wn_adam_clip(float* p, const float* g, float* m, float* v, long n,
+                 float lr_t, float beta1, float beta2, float eps,
+                 float grad_scale, float l2, const float* l2_mask,
+                 const double* partials, int nparts, float clip_norm,
+                 float* ema, float ema_decay, float* norm_out, void* stream) {
+  if (!p || !g || !m || !v) return WN_ERR_NULL;
+  if (n <= 0) return WN_ERR_BAD_SHAPE;
+  const int rc = clip_args_check(partials, nparts, clip_norm, ema, ema_decay,
+                                 norm_out);
+  if (rc != WN_OK) return rc;
+  hipLaunchKernelGGL(adam_clip_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
+                     (hipStream_t)stream, p, g, m, v, n, lr_t, beta1, beta2,
+                     eps, grad_scale, l2, l2_mask, partials, clip_norm, ema,
+                     ema_decay, norm_out);
+  return wn_check_launch();
+}
+
+int wn_momentum_clip(float* p, const float* g, float* acc, long n, float lr,
+                     float momentum, float grad_scale, float l2,
+                     const float* l2_mask, const double* partials, int nparts,
+                     float clip_norm, float* ema, float ema_decay,
+                     float* norm_out, void* stream) {
+  if (!p || !g || !acc) return WN_ERR_NULL;
+  if (n <= 0) return WN_ERR_BAD_SHAPE;
+  const int rc = clip_args_check(partials, nparts, clip_norm, ema, ema_decay,
+                                 norm_out);
+  if (rc != WN_OK) return rc;
+  hipLaunchKernelGGL(momentum_clip_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
+                     (hipStream_t)stream, p, g, acc, n, lr, momentum,
+                     grad_scale, l2, l2_mask, partials, clip_norm, ema,
+                     ema_decay, norm_out);
+  return wn_check_launch();
+}
+
+int wn_rmsprop_clip(float* p, const float* g, float* ms, float* mom, long n,
+                    float lr, float decay, float momentum, float eps,
+                    float grad_scale, float l2, const float* l2_mask,
+                    const double* partials, int nparts, float clip_norm,
+                    float* ema, float ema_decay, float* norm_out,
+                    void* stream) {
+  if (!p || !g || !ms || !mom) return WN_ERR_NULL;
+  if (n <= 0) return WN_ERR_BAD_SHAPE;
+  const int rc = clip_args_check(partials, nparts, clip_norm, ema, ema_decay,
+                                 norm_out);
+  if (rc != WN_OK) return rc;
+  hipLaunchKernelGGL(rmsprop_clip_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
+                     (hipStream_t)stream, p, g, ms, mom, n, lr, decay,
+                     momentum, eps, grad_scale, l2, l2_mask, partials,
+                     clip_norm, ema, ema_decay, norm_out);
   return wn_check_launch();
 }
 

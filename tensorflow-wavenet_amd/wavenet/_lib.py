@@ -108,6 +108,19 @@ SIGNATURES = {
                             c_float, P, P]),
     'wn_rmsprop': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float,
                            c_float, c_float, c_float, P, P]),
+    # the updates behind a global-norm clip, with EMA shadow weights:
+    # ..., partials, nparts, clip_norm, ema, ema_decay, norm_out, stream
+    'wn_grad_norm_partials_count': (c_int, []),
+    'wn_grad_norm_partials': (c_int, [P, c_long, P, P]),
+    'wn_adam_clip': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float,
+                             c_float, c_float, c_float, P, P, c_int, c_float,
+                             P, c_float, P, P]),
+    'wn_momentum_clip': (c_int, [P, P, P, c_long, c_float, c_float, c_float,
+                                 c_float, P, P, c_int, c_float, P, c_float, P,
+                                 P]),
+    'wn_rmsprop_clip': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float,
+                                c_float, c_float, c_float, P, P, c_int,
+                                c_float, P, c_float, P, P]),
     'wn_l2_partials_count': (c_int, []),
     'wn_l2_partials': (c_int, [P, c_long, P, P, P]),
     'wn_gc_bias': (c_int, [P, c_long, c_long, c_long, c_int, P, c_int, P, P,

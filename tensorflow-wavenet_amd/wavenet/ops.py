@@ -120,14 +120,58 @@ def causal_conv(value, filter_, dilation, name='causal_conv'):
 # ---------------------------------------------------------------------------
 
 
+def _check_clip_ema(clip_norm, ema_decay):
+    """Validate the keyword-only arguments of the optimizers (no library or
+    device is touched): clip_norm None or a positive finite number, ema_decay
+    None or a number in [0, 1).  Returns them as floats (or None)."""
+    if clip_norm is not None:
+        if isinstance(clip_norm, bool) or not isinstance(
+                clip_norm, (int, float, np.integer, np.floating)):
+            raise ValueError('clip_norm must be a positive finite number, '
+                             'got %r' % (clip_norm,))
+        clip_norm = float(clip_norm)
+        if not (clip_norm > 0.0 and math.isfinite(clip_norm)):
+            raise ValueError('clip_norm must be a positive finite number, '
+                             'got %r' % (clip_norm,))
+        if clip_norm > float(np.finfo(np.float32).max):
+            raise ValueError('clip_norm %r does not fit a float32'
+                             % (clip_norm,))
+    if ema_decay is not None:
+        if isinstance(ema_decay, bool) or not isinstance(
+                ema_decay, (int, float, np.integer, np.floating)):
+            raise ValueError('ema_decay must lie in [0, 1), got %r'
+                             % (ema_decay,))
+        ema_decay = float(ema_decay)
+        if not (0.0 <= ema_decay < 1.0) or float(np.float32(ema_decay)) >= 1.0:
+            raise ValueError('ema_decay must lie in [0, 1), got %r'
+                             % (ema_decay,))
+    return clip_norm, ema_decay
+
+
 class _Optimizer(object):
     """Fused flat-buffer optimizer.  `minimize(loss)` mirrors
     tf.train.Optimizer.minimize: `loss` is what WaveNetModel.loss returned
     (its gradients already sit in the model's flat gradient bucket); under
-    torch.distributed the bucket is all-reduced (RCCL) and averaged first."""
+    torch.distributed the bucket is all-reduced (RCCL) and averaged first.
 
-    def __init__(self):
+    clip_norm (keyword only): tf.clip_by_global_norm of the averaged global
+    gradient (L2 term included: `loss` has added it to the bucket) --
+    `wn_grad_norm_partials` after the all-reduce, then the `_clip` update, in
+    which every workgroup derives the same factor from the same partials; no
+    host wait.  `last_grad_norm` is then a device scalar holding the norm
+    before clipping (None without clip_norm).
+    ema_decay (keyword only): shadow weights s -= (1 - decay) * (s - p) in the
+    same pass, initialised to the parameters before the first update
+    (tf.train.ExponentialMovingAverage without num_updates).
+    With both None, minimize makes exactly the calls it made before they
+    existed."""
+
+    def __init__(self, clip_norm=None, ema_decay=None):
+        self.clip_norm, self.ema_decay = _check_clip_ema(clip_norm, ema_decay)
         self._slots = None
+        self._shadow = None
+        self._gn_parts = None
+        self.last_grad_norm = None
         self._step = 0
 
     def _make_slots(self, model):
@@ -135,6 +179,19 @@ class _Optimizer(object):
 
     def _apply(self, model, grad_scale):
         raise NotImplementedError
+
+    def _apply_clip(self, model, grad_scale, tail):
+        """The `_clip` entry point; `tail` = (partials, nparts, clip_norm,
+        ema, ema_decay, norm_out, stream)."""
+        raise NotImplementedError
+
+    def init_state(self, model):
+        """Create the slots (and, with ema_decay, the shadow as a copy of the
+        parameters) for `model` unless they exist."""
+        if self._slots is None:
+            self._make_slots(model)
+        if self.ema_decay is not None and self._shadow is None:
+            self._shadow = model.params.detach().clone()
 
     def minimize(self, loss, var_list=None):
         model = getattr(loss, '_wn_model', None)
@@ -145,17 +202,82 @@ class _Optimizer(object):
             raise ValueError('loss was computed with backward=False')
         from . import parallel
         scale = parallel.allreduce_gradients(model)
-        if self._slots is None:
-            self._make_slots(model)
+        self.init_state(model)
         self._step += 1
-        self._apply(model, scale)
+        if self.clip_norm is None and self.ema_decay is None:
+            self._apply(model, scale)
+            return loss
+        parts, nparts = None, 0
+        if self.clip_norm is not None:
+            if self._gn_parts is None:
+                nparts = _lib.load().wn_grad_norm_partials_count()
+                self._gn_parts = torch.zeros(nparts, dtype=torch.float64,
+                                             device=model.params.device)
+                self.last_grad_norm = torch.zeros(
+                    (), dtype=torch.float32, device=model.params.device)
+            parts, nparts = self._gn_parts, self._gn_parts.numel()
+            _lib.call('wn_grad_norm_partials', _lib.ptr(model.grads),
+                      model.grads.numel(), _lib.ptr(parts), _lib.stream())
+        self._apply_clip(model, scale, (
+            _lib.ptr(parts), nparts, self.clip_norm or 0.0,
+            _lib.ptr(self._shadow), self.ema_decay or 0.0,
+            _lib.ptr(self.last_grad_norm), _lib.stream()))
         return loss
+
+    # ---- checkpointing ---------------------------------------------------
+    def state_dict(self):
+        """{'kind', 'step', 'slots', 'shadow'}: the update count (Adam's bias
+        correction), the slot buffers and the EMA shadow (None without
+        ema_decay) as flat host tensors laid out like model.params."""
+        return {'kind': type(self).__name__, 'step': int(self._step),
+                'slots': None if self._slots is None else
+                [s.detach().cpu().clone() for s in self._slots],
+                'shadow': None if self._shadow is None else
+                self._shadow.detach().cpu().clone()}
+
+    def load_state_dict(self, sd, model):
+        """Restore `state_dict()` for `model` (whose flat parameter layout the
+        buffers share).  A state without shadow loaded into an optimizer with
+        ema_decay starts the shadow from the model's current parameters."""
+        if sd.get('kind') != type(self).__name__:
+            raise ValueError('optimizer state of a %s cannot be loaded into a '
+                             '%s' % (sd.get('kind'), type(self).__name__))
+        n, dev = model.params.numel(), model.params.device
+        def flat(t, what):
+            t = torch.as_tensor(t, dtype=torch.float32).reshape(-1)
+            if t.numel() != n:
+                raise ValueError('optimizer %s holds %d floats, the model %d'
+                                 % (what, t.numel(), n))
+            return t.to(dev).clone()
+        self._slots = None
+        if sd.get('slots') is not None:
+            self._make_slots(model)
+            if len(sd['slots']) != len(self._slots):
+                raise ValueError('optimizer state holds %d slots, a %s has %d'
+                                 % (len(sd['slots']), type(self).__name__,
+                                    len(self._slots)))
+            self._slots = [flat(s, 'slot') for s in sd['slots']]
+        self._shadow = None
+        if self.ema_decay is not None and sd.get('shadow') is not None:
+            self._shadow = flat(sd['shadow'], 'shadow')
+        self._step = int(sd['step'])
+
+    def ema_state_dict(self, model):
+        """The shadow weights under the keys of model.state_dict() (loadable
+        with model.load_state_dict)."""
+        if self.ema_decay is None:
+            raise ValueError('ema_state_dict() needs an optimizer built with '
+                             'ema_decay')
+        self.init_state(model)
+        return {n: v.detach().cpu().clone() for n, v in
+                model.named_variables(model._views(self._shadow))}
 
 
 class AdamOptimizer(_Optimizer):
     # tf.train.AdamOptimizer(learning_rate, epsilon=1e-4); `momentum` ignored
-    def __init__(self, learning_rate, epsilon=1e-4, beta1=0.9, beta2=0.999):
-        super(AdamOptimizer, self).__init__()
+    def __init__(self, learning_rate, epsilon=1e-4, beta1=0.9, beta2=0.999,
+                 *, clip_norm=None, ema_decay=None):
+        super(AdamOptimizer, self).__init__(clip_norm, ema_decay)
         self.lr, self.eps, self.b1, self.b2 = learning_rate, epsilon, beta1, beta2
 
     def _make_slots(self, model):
@@ -171,10 +293,20 @@ class AdamOptimizer(_Optimizer):
                   self.b1, self.b2, self.eps, grad_scale, 0.0, None,
                   _lib.stream())
 
+    def _apply_clip(self, model, grad_scale, tail):
+        t = self._step
+        lr_t = self.lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
+        m, v = self._slots
+        _lib.call('wn_adam_clip', _lib.ptr(model.params),
+                  _lib.ptr(model.grads), _lib.ptr(m), _lib.ptr(v),
+                  model.params.numel(), lr_t, self.b1, self.b2, self.eps,
+                  grad_scale, 0.0, None, *tail)
+
 
 class MomentumOptimizer(_Optimizer):
-    def __init__(self, learning_rate, momentum):
-        super(MomentumOptimizer, self).__init__()
+    def __init__(self, learning_rate, momentum, *, clip_norm=None,
+                 ema_decay=None):
+        super(MomentumOptimizer, self).__init__(clip_norm, ema_decay)
         self.lr, self.mom = learning_rate, momentum
 
     def _make_slots(self, model):
@@ -185,12 +317,19 @@ class MomentumOptimizer(_Optimizer):
                   _lib.ptr(self._slots[0]), model.params.numel(), self.lr,
                   self.mom, grad_scale, 0.0, None, _lib.stream())
 
+    def _apply_clip(self, model, grad_scale, tail):
+        _lib.call('wn_momentum_clip', _lib.ptr(model.params),
+                  _lib.ptr(model.grads), _lib.ptr(self._slots[0]),
+                  model.params.numel(), self.lr, self.mom, grad_scale, 0.0,
+                  None, *tail)
+
 
 class RMSPropOptimizer(_Optimizer):
     # tf.train.RMSPropOptimizer(lr, decay=0.9, momentum, epsilon=1e-5);
     # the `rms` slot starts at ONE (TensorFlow), `momentum` slot at zero.
-    def __init__(self, learning_rate, momentum, epsilon=1e-5, decay=0.9):
-        super(RMSPropOptimizer, self).__init__()
+    def __init__(self, learning_rate, momentum, epsilon=1e-5, decay=0.9, *,
+                 clip_norm=None, ema_decay=None):
+        super(RMSPropOptimizer, self).__init__(clip_norm, ema_decay)
         self.lr, self.mom, self.eps, self.decay = (learning_rate, momentum,
                                                    epsilon, decay)
 
@@ -204,18 +343,31 @@ class RMSPropOptimizer(_Optimizer):
                   model.params.numel(), self.lr, self.decay, self.mom,
                   self.eps, grad_scale, 0.0, None, _lib.stream())
 
+    def _apply_clip(self, model, grad_scale, tail):
+        _lib.call('wn_rmsprop_clip', _lib.ptr(model.params),
+                  _lib.ptr(model.grads), _lib.ptr(self._slots[0]),
+                  _lib.ptr(self._slots[1]), model.params.numel(), self.lr,
+                  self.decay, self.mom, self.eps, grad_scale, 0.0, None,
+                  *tail)
 
-def create_adam_optimizer(learning_rate, momentum):
-    return AdamOptimizer(learning_rate=learning_rate, epsilon=1e-4)
+
+def create_adam_optimizer(learning_rate, momentum, *, clip_norm=None,
+                          ema_decay=None):
+    return AdamOptimizer(learning_rate=learning_rate, epsilon=1e-4,
+                         clip_norm=clip_norm, ema_decay=ema_decay)
 
 
-def create_sgd_optimizer(learning_rate, momentum):
-    return MomentumOptimizer(learning_rate=learning_rate, momentum=momentum)
+def create_sgd_optimizer(learning_rate, momentum, *, clip_norm=None,
+                         ema_decay=None):
+    return MomentumOptimizer(learning_rate=learning_rate, momentum=momentum,
+                             clip_norm=clip_norm, ema_decay=ema_decay)
 
 
-def create_rmsprop_optimizer(learning_rate, momentum):
+def create_rmsprop_optimizer(learning_rate, momentum, *, clip_norm=None,
+                             ema_decay=None):
     return RMSPropOptimizer(learning_rate=learning_rate, momentum=momentum,
-                            epsilon=1e-5)
+                            epsilon=1e-5, clip_norm=clip_norm,
+                            ema_decay=ema_decay)
 
 
 optimizer_factory = {'adam': create_adam_optimizer,

@@ -123,6 +123,18 @@ def get_arguments(argv=None):
                         'nor counted in the mean (WaveNetModel.loss, '
                         '`lengths`).  Prints the real samples per step beside '
                         'the loss.')
+    p.add_argument('--clip_norm', type=float, default=None,
+                   help='Clip the gradient by its global norm '
+                        '(tf.clip_by_global_norm) inside the update: the norm '
+                        'of the whole averaged gradient, L2 term included, '
+                        'scaled down to this value when it is larger.  The '
+                        'norm before clipping is logged beside the loss.  '
+                        'Default: no clipping.')
+    p.add_argument('--ema_decay', type=float, default=None,
+                   help='Keep an exponential moving average of the weights '
+                        'with this decay, in [0, 1) (e.g. 0.9999); saved as '
+                        '`ema_variables` for generate.py --use_ema true.  '
+                        'Default: none.')
     return p.parse_args(argv)
 
 
@@ -148,12 +160,20 @@ def checkpoint_path(logdir, step):
     return os.path.join(logdir, 'model.ckpt-{}'.format(step))
 
 
-def save(net, logdir, step):
+def save(net, logdir, step, optimizer=None):
+    """`optimizer`: its step count, slots and shadow go in as 'optimizer'
+    and, with EMA weights, the shadow as 'ema_variables' (the keys of
+    'variables')."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
     path = checkpoint_path(logdir, step)
-    torch.save({'variables': net.state_dict(), 'step': step}, path)
+    ckpt = {'variables': net.state_dict(), 'step': step}
+    if optimizer is not None:
+        ckpt['optimizer'] = optimizer.state_dict()
+        if optimizer.ema_decay is not None:
+            ckpt['ema_variables'] = optimizer.ema_state_dict(net)
+    torch.save(ckpt, path)
     with open(os.path.join(logdir, 'checkpoint'), 'w') as f:
         f.write('model_checkpoint_path: "{}"\n'.format(os.path.basename(path)))
     print(' Done.')
@@ -180,7 +200,10 @@ def latest_checkpoint(logdir):
     return max(found, key=found.get) if found else None
 
 
-def load(net, logdir):
+def load(net, logdir, optimizer=None):
+    """`optimizer`: restored from the checkpoint's 'optimizer' entry when it
+    has one (checkpoints written before it existed, and the reference's own,
+    have none: the optimizer then starts afresh, as it always did)."""
     print("Trying to restore saved checkpoints from {} ...".format(logdir),
           end="")
     path = latest_checkpoint(logdir) if os.path.isdir(logdir) else None
@@ -195,7 +218,10 @@ def load(net, logdir):
         # written by the reference's tf.train.Saver (train.py:104-114 there)
         tf_checkpoint.load_into(net, path)
     else:
-        net.load_state_dict(torch.load(path, map_location='cpu')['variables'])
+        ckpt = torch.load(path, map_location='cpu')
+        net.load_state_dict(ckpt['variables'])
+        if optimizer is not None and 'optimizer' in ckpt:
+            optimizer.load_state_dict(ckpt['optimizer'], net)
     print(" Done.")
     return global_step
 
@@ -356,11 +382,16 @@ def main(argv=None):
         local_condition_upsample_scales=lc_scales,
         local_condition_context=lc_ctx)
     l2 = args.l2_regularization_strength or None
-    optimizer = optimizer_factory[args.optimizer](
-        learning_rate=args.learning_rate, momentum=args.momentum)
+    try:
+        optimizer = optimizer_factory[args.optimizer](
+            learning_rate=args.learning_rate, momentum=args.momentum,
+            clip_norm=args.clip_norm, ema_decay=args.ema_decay)
+    except ValueError as e:
+        print(str(e))
+        return 1
 
     try:
-        saved_global_step = load(net, restore_from)
+        saved_global_step = load(net, restore_from, optimizer)
         if is_overwritten_training or saved_global_step is None:
             # the first training step will be saved_global_step + 1
             saved_global_step = -1
@@ -386,7 +417,7 @@ def main(argv=None):
     pending = None            # (step, mean loss tensor, start time) not yet printed
     last_report = [None]
 
-    def report(k, mean_loss, started, real=None):
+    def report(k, mean_loss, started, real=None, norm=None):
         """Fetch step k's loss (waits for that step), check it, print / log the
         reference's line (train.py:310-311).  sec/step: from the previous line
         (the pipeline's cadence), or from the step's start for the first."""
@@ -395,6 +426,9 @@ def main(argv=None):
         host_scalar, done = mean_loss
         done.synchronize()
         loss_value = float(host_scalar)
+        # (--clip_norm: the norm before clipping, copied behind the loss on
+        # the same stream: complete once the loss's event is)
+        norm_value = None if norm is None else float(norm[0])
         if not np.isfinite(loss_value):
             # every rank sees the same NaN mean: decide TOGETHER whether a
             # kernel reported an error, so that no rank is left waiting in
@@ -417,8 +451,12 @@ def main(argv=None):
             # (--mask_padding: `real` = the step's real samples, all ranks')
             print('step {:d} - loss = {:.3f}, ({:.3f} sec/step)'
                   .format(k, loss_value, duration) +
-                  ('' if real is None else ', {:d} real samples'.format(real)))
+                  ('' if real is None else ', {:d} real samples'.format(real))
+                  + ('' if norm_value is None else
+                     ', grad norm = {:.3f}'.format(norm_value)))
             line = {'step': k, 'loss': loss_value, 'sec_per_step': duration}
+            if norm_value is not None:
+                line['grad_norm'] = norm_value
             if real is not None:
                 line['real_samples'] = real
             events.write(json.dumps(line) + '\n')
@@ -426,19 +464,20 @@ def main(argv=None):
 
     fetch_slots = {}
 
-    def fetch_later(t, k):
+    def fetch_later(t, k, tag=0):
         """(pinned host scalar, event): the scalar holds t once the event has
-        completed; two slots used alternately (a slot is read before the step
-        after next overwrites it)."""
+        completed; two slots per `tag` used alternately (a slot is read before
+        the step after next overwrites it)."""
+        k = 2 * tag + (k & 1)
         if not t.is_cuda:
             class _Done(object):
                 def synchronize(self):
                     pass
             return t.detach().reshape(()).clone(), _Done()
-        if (k & 1) not in fetch_slots:
-            fetch_slots[k & 1] = (torch.empty((), dtype=torch.float32).pin_memory(),
-                                  torch.cuda.Event())
-        host_scalar, ev = fetch_slots[k & 1]
+        if k not in fetch_slots:
+            fetch_slots[k] = (torch.empty((), dtype=torch.float32).pin_memory(),
+                              torch.cuda.Event())
+        host_scalar, ev = fetch_slots[k]
         host_scalar.copy_(t.detach().reshape(()).float(), non_blocking=True)
         ev.record()
         return host_scalar, ev
@@ -523,10 +562,14 @@ def main(argv=None):
             # runs (the same lines, one step late; 12.0 -> 9.5 ms per step at
             # 8 x 16000: bench.py's step time) -- except where the step's own state is needed at
             # once: a checkpoint step, a traced step, the last step.
+            # (the norm first: the loss's event, recorded behind both copies,
+            # then covers it.  Every rank holds the same norm: no collective)
+            norm = None if optimizer.last_grad_norm is None else \
+                fetch_later(optimizer.last_grad_norm, step, tag=1)
             mean_loss = fetch_later(parallel.allreduce_mean_scalar(loss), step)
             if pending is not None:
                 report(*pending)
-            pending = (step, mean_loss, start_time, real)
+            pending = (step, mean_loss, start_time, real, norm)
             if trace_step:
                 report(*pending)
                 pending = None
@@ -541,7 +584,7 @@ def main(argv=None):
                     report(*pending)
                     pending = None
             if rank == 0 and step % args.checkpoint_every == 0:
-                save(net, logdir, step)
+                save(net, logdir, step, optimizer)
                 last_saved_step = step
                 if args.histograms:
                     # the reference's histogram summaries (model.py:314-325)
@@ -559,7 +602,7 @@ def main(argv=None):
         print()
     finally:
         if rank == 0 and step is not None and step > last_saved_step:
-            save(net, logdir, step)
+            save(net, logdir, step, optimizer)
         coord.request_stop()
         coord.join(threads)
         if events:
