@@ -186,21 +186,51 @@ def context_mismatch(net, sd):
             '--lc_context (%s)' % (name, desc(theirs), desc(mine)))
 
 
+def open_ema_checkpoint(path):
+    """--use_ema true: (the checkpoint, None), or (None, why it holds no EMA
+    weights)."""
+    if tf_checkpoint.checkpoint_format(path):
+        return None, ('--use_ema true: a TensorFlow checkpoint holds no EMA '
+                      'weights.')
+    ckpt = torch.load(path, map_location='cpu')
+    if 'ema_variables' not in ckpt:
+        return None, ('--use_ema true: the checkpoint {} holds no EMA weights '
+                      '(`ema_variables`); train with train.py --ema_decay.'
+                      .format(path))
+    return ckpt, None
+
+
+def restore(net, path, use_ema=False, ckpt=None, check_lc=False):
+    """Load the checkpoint at `path` into `net` (evaluate.py shares this):
+    the reference's own TensorFlow format, or train.py's torch file `ckpt`
+    (read here unless the caller holds it), its `ema_variables` with use_ema.
+    check_lc: compare the learned upsampler's and the context filter's shapes
+    first.  Returns a message when they do not match, else None."""
+    print('Restoring model from {}'.format(path))
+    if tf_checkpoint.checkpoint_format(path):
+        # a checkpoint written by the reference itself (tf.train.Saver)
+        tf_checkpoint.load_into(net, path)
+        return None
+    if ckpt is None:
+        ckpt = torch.load(path, map_location='cpu')
+    sd = ckpt['ema_variables' if use_ema else 'variables']
+    if check_lc:
+        why = upsampler_mismatch(net, sd) or context_mismatch(net, sd)
+        if why:
+            return why
+    net.load_state_dict(sd)
+    return None
+
+
 def main(argv=None):
     args = get_arguments(argv)
     ckpt = None
     if args.use_ema:
         # (before any model is built: a checkpoint without EMA weights is
         # refused whatever else the command line asks for)
-        if tf_checkpoint.checkpoint_format(args.checkpoint):
-            print('--use_ema true: a TensorFlow checkpoint holds no EMA '
-                  'weights.')
-            return 1
-        ckpt = torch.load(args.checkpoint, map_location='cpu')
-        if 'ema_variables' not in ckpt:
-            print('--use_ema true: the checkpoint {} holds no EMA weights '
-                  '(`ema_variables`); train with train.py --ema_decay.'
-                  .format(args.checkpoint))
+        ckpt, why = open_ema_checkpoint(args.checkpoint)
+        if why:
+            print(why)
             return 1
     lc_rows, lc_scales, lc_ctx = None, None, None
     if args.lc_path is not None:
@@ -254,20 +284,11 @@ def main(argv=None):
         local_condition_channels=None if lc_rows is None else lc_rows.shape[1],
         local_condition_upsample_scales=lc_scales,
         local_condition_context=lc_ctx)
-    print('Restoring model from {}'.format(args.checkpoint))
-    if tf_checkpoint.checkpoint_format(args.checkpoint):
-        # a checkpoint written by the reference itself (tf.train.Saver)
-        tf_checkpoint.load_into(net, args.checkpoint)
-    else:
-        if ckpt is None:
-            ckpt = torch.load(args.checkpoint, map_location='cpu')
-        sd = ckpt['ema_variables' if args.use_ema else 'variables']
-        if lc_rows is not None:
-            why = upsampler_mismatch(net, sd) or context_mismatch(net, sd)
-            if why:
-                print(why)
-                return 1
-        net.load_state_dict(sd)
+    why = restore(net, args.checkpoint, args.use_ema, ckpt,
+                  check_lc=lc_rows is not None)
+    if why:
+        print(why)
+        return 1
     if lc_scales is not None:
         # the checkpoint's learned upsampler, once for the whole run
         lc_rows = net.upsample_local_condition(

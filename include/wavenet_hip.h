@@ -419,6 +419,30 @@ int wn_xent_masked(const float* logits, long ld, const int32_t* q,
                    const int32_t* lengths, const float* inv_den,
                    float* dlogits, float* loss_partials, int B, int T, int Q,
                    int tf_quirk, void* stream);
+/* Scoring of held-out data (WaveNetModel.score): the inputs of wn_xent_masked
+ * (lengths may be NULL: every clip has T rows), forward only.
+ *   row_nll      float [B*T], may be NULL: logsumexp(logits[b,t,:Q]) -
+ *                logits[b,t,q[b,t+1]] where row (b, t) has a target -- t + 1 <
+ *                len_b (lengths[b] clamped to [0, T]) and 0 <= q[b,t+1] < Q,
+ *                the loss kernels' rule -- and 0.0 elsewhere (the label-less
+ *                last row, padding: no exponential is evaluated there);
+ *   clip_nll     double [B]: the sum of clip b's row_nll values in float64;
+ *   clip_count   int32 [B]: its rows with a target;
+ *   clip_correct int32 [B]: those whose arg-max over [0, Q) is the target
+ *                (the lowest index wins a tie; a row containing NaN is never
+ *                correct, and its NaN reaches clip_nll).
+ * The row arithmetic is wn_xent's (float32); columns >= Q are not read.  The
+ * per-clip sums have a fixed order (no atomics): a function of the rows and
+ * len_b alone, the same bits with and without row_nll.  lengths is read from
+ * device memory when the kernels run.  scratch: wn_xent_score_scratch_floats(
+ * B*T) floats, caller-owned.  Errors as wn_xent (NULL -5, shape -1, Q % 4 or
+ * ld % 4 -2, alignment -3: logits 16 bytes, clip_nll 8, the others 4), all
+ * before any launch. */
+long wn_xent_score_scratch_floats(long rows);
+int wn_xent_score(const float* logits, long ld, const int32_t* q,
+                  const int32_t* lengths, float* row_nll, double* clip_nll,
+                  int32_t* clip_count, int32_t* clip_correct, float* scratch,
+                  int B, int T, int Q, void* stream);
 int wn_softmax64_row(const float* logits_row, int Q, float* proba,
                      void* stream);
 

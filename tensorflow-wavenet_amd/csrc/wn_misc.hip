@@ -342,6 +342,163 @@ __global__ __launch_bounds__(256) void xent_masked_kernel(
                   *inv_den, tf_quirk);
 }
 
+// ---------------------------------------------------------------------------
+// scoring (wn_xent_score): per-row negative log-likelihood, per-clip sums,
+// target counts and arg-max hits of held-out data.  Forward only.
+//
+// xent_score_rows_kernel: one wave per row, xent_body's float32 formulas
+// (max, expf, sum, m + logf(se), the same shuffle trees) on the rows that
+// have a target -- t + 1 < len_b and 0 <= q[b][t + 1] < Q -- and nothing but
+// a stored 0 for the others (the label-less last row, a code out of range,
+// padding): no exponential is evaluated there.  It writes nll[row] and
+// flag[row] = 0 (no target) | 1 (target) | 3 (target, and the lowest index of
+// the row's maximum over [0, Q) is the target; never for a row whose
+// logsumexp is NaN).  Columns >= Q are not read.
+// xent_score_clips_kernel: one workgroup per clip.  Thread i sums rows i,
+// i + 1024, ... below len_b - 1 in float64 (integers for the flags), a fixed
+// LDS tree finishes: a function of the rows' values and len_b alone, whatever
+// order the workgroups of either kernel ran in.  No atomics.
+// ---------------------------------------------------------------------------
+#define SCORE_CLIP_THREADS 1024
+
+__device__ __forceinline__ int wave_min_i32(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+
+__global__ __launch_bounds__(256) void xent_score_rows_kernel(
+    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
+    const int32_t* __restrict__ lengths, float* __restrict__ nll,
+    int32_t* __restrict__ flag, long rows, int T, int Q) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long nwaves = (long)gridDim.x * 4;
+  const int none = 0x7fffffff;
+  if (Q == 256) {
+    // xent_body's single pass: one 16-byte load per lane holds the row, the
+    // next row's load in flight under the reductions
+    long row = (long)blockIdx.x * 4 + wave;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row < rows) v = *reinterpret_cast<const f32x4*>(logits + row * ld + lane * 4);
+    for (; row < rows; row += nwaves) {
+      const long nrow = row + nwaves;
+      f32x4 vn = {0.f, 0.f, 0.f, 0.f};
+      if (nrow < rows)
+        vn = *reinterpret_cast<const f32x4*>(logits + nrow * ld + lane * 4);
+      const int t = (int)(row % T);
+      const int len = lengths ? min(max(lengths[row / T], 0), T) : T;
+      const int label = (t + 1 < len) ? q[row + 1] : -1;
+      if (!(label >= 0 && label < Q)) {      // no target: nothing to evaluate
+        if (lane == 0) {
+          nll[row] = 0.f;
+          flag[row] = 0;
+        }
+        v = vn;
+        continue;
+      }
+      float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      float e[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = expf(v[k] - m);
+      float se = (e[0] + e[1]) + (e[2] + e[3]);
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
+      const float lse = m + logf(se);
+      const float mine = (label >> 2) == lane ? v[label & 3] : 0.f;
+      float ll = mine;
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) ll += __shfl_xor(ll, o);
+      int best = none;                       // lowest index holding the maximum
+#pragma unroll
+      for (int k = 3; k >= 0; --k) best = v[k] == m ? lane * 4 + k : best;
+      best = wave_min_i32(best);
+      if (lane == 0) {
+        nll[row] = lse - ll;
+        flag[row] = (best == label && lse == lse) ? 3 : 1;
+      }
+      v = vn;
+    }
+    return;
+  }
+  for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += nwaves) {
+    const float* lp = logits + row * ld;
+    const int t = (int)(row % T);
+    const int len = lengths ? min(max(lengths[row / T], 0), T) : T;
+    const int label = (t + 1 < len) ? q[row + 1] : -1;
+    if (!(label >= 0 && label < Q)) {
+      if (lane == 0) {
+        nll[row] = 0.f;
+        flag[row] = 0;
+      }
+      continue;
+    }
+    float m = -INFINITY;
+    for (int c = lane * 4; c < Q; c += 256) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
+      m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float se = 0.f;
+    int best = none;
+    for (int c = lane * 4; c < Q; c += 256) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
+      se += expf(v[0] - m) + expf(v[1] - m) + expf(v[2] - m) + expf(v[3] - m);
+#pragma unroll
+      for (int k = 3; k >= 0; --k) best = v[k] == m ? min(best, c + k) : best;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
+    best = wave_min_i32(best);
+    const float lse = m + logf(se);
+    if (lane == 0) {
+      nll[row] = lse - lp[label];
+      flag[row] = (best == label && lse == lse) ? 3 : 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(SCORE_CLIP_THREADS) void xent_score_clips_kernel(
+    const float* __restrict__ nll, const int32_t* __restrict__ flag,
+    const int32_t* __restrict__ lengths, double* __restrict__ clip_nll,
+    int32_t* __restrict__ clip_count, int32_t* __restrict__ clip_correct,
+    int T) {
+  __shared__ double rs[SCORE_CLIP_THREADS];
+  __shared__ int rc[SCORE_CLIP_THREADS], rh[SCORE_CLIP_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int len = lengths ? min(max(lengths[b], 0), T) : T;
+  const float* pn = nll + (long)b * T;
+  const int32_t* pf = flag + (long)b * T;
+  double s = 0.0;
+  int c = 0, h = 0;
+  // (rows t >= len - 1 have no target: zeros by construction, not read)
+  for (int t = tid; t < len - 1; t += SCORE_CLIP_THREADS) {
+    const int f = pf[t];
+    s += (double)pn[t];
+    c += f & 1;
+    h += f >> 1;
+  }
+  rs[tid] = s;
+  rc[tid] = c;
+  rh[tid] = h;
+  __syncthreads();
+  for (int k = SCORE_CLIP_THREADS / 2; k > 0; k >>= 1) {
+    if (tid < k) {
+      rs[tid] += rs[tid + k];
+      rc[tid] += rc[tid + k];
+      rh[tid] += rh[tid + k];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    clip_nll[b] = rs[0];
+    clip_count[b] = rc[0];
+    clip_correct[b] = rh[0];
+  }
+}
+
 // softmax of ONE row in float64, cast to float32 (model.py:584-585, 620-621)
 __global__ void softmax64_row_kernel(const float* __restrict__ logits, int Q,
                                      float* __restrict__ proba) {
@@ -1118,6 +1275,37 @@ int wn_xent_masked(const float* logits, long ld, const int32_t* q,
   hipLaunchKernelGGL(xent_masked_kernel, dim3(wn_xent_partials(rows)),
                      dim3(256), 0, (hipStream_t)stream, logits, ld, q, lengths,
                      inv_den, dlogits, loss_partials, rows, T, Q, tf_quirk);
+  return wn_check_launch();
+}
+
+long wn_xent_score_scratch_floats(long rows) {
+  return rows > 0 ? 2 * rows : 0;          // flags [rows], row values [rows]
+}
+
+int wn_xent_score(const float* logits, long ld, const int32_t* q,
+                  const int32_t* lengths, float* row_nll, double* clip_nll,
+                  int32_t* clip_count, int32_t* clip_correct, float* scratch,
+                  int B, int T, int Q, void* stream) {
+  if (!logits || !q || !clip_nll || !clip_count || !clip_correct || !scratch)
+    return WN_ERR_NULL;
+  if (B <= 0 || T <= 0 || Q <= 0 || ld < Q) return WN_ERR_BAD_SHAPE;
+  if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
+  if (!wn_aligned16(logits) || ((uintptr_t)lengths & 3) ||
+      ((uintptr_t)row_nll & 3) || ((uintptr_t)clip_nll & 7) ||
+      ((uintptr_t)clip_count & 3) || ((uintptr_t)clip_correct & 3) ||
+      ((uintptr_t)scratch & 3))
+    return WN_ERR_MISALIGNED;
+  const long rows = (long)B * T;
+  int32_t* flag = reinterpret_cast<int32_t*>(scratch);
+  // (without row_nll the row values go to the scratch: the per-clip sums
+  // read the same bits either way)
+  float* nll = row_nll ? row_nll : scratch + rows;
+  hipLaunchKernelGGL(xent_score_rows_kernel, dim3(wn_xent_partials(rows)),
+                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, lengths,
+                     nll, flag, rows, T, Q);
+  hipLaunchKernelGGL(xent_score_clips_kernel, dim3(B),
+                     dim3(SCORE_CLIP_THREADS), 0, (hipStream_t)stream, nll,
+                     flag, lengths, clip_nll, clip_count, clip_correct, T);
   return wn_check_launch();
 }
 

@@ -101,6 +101,11 @@ SIGNATURES = {
     'wn_xent': (c_int, [P, c_long, P, P, P, c_int, c_int, c_int, c_int, P]),
     'wn_xent_masked': (c_int, [P, c_long, P, P, P, P, P, c_int, c_int, c_int,
                                c_int, P]),
+    # logits, ld, q, lengths, row_nll, clip_nll, clip_count, clip_correct,
+    # scratch, B, T, Q, stream
+    'wn_xent_score_scratch_floats': (c_long, [c_long]),
+    'wn_xent_score': (c_int, [P, c_long, P, P, P, P, P, P, P, c_int, c_int,
+                              c_int, P]),
     'wn_softmax64_row': (c_int, [P, c_int, P, P]),
     'wn_adam': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float,
                         c_float, c_float, c_float, P, P]),

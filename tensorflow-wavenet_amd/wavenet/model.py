@@ -833,6 +833,67 @@ class WaveNetModel(object):
         loss._wn_has_grads = bool(backward)
         return loss
 
+    def score(self, input_batch, global_condition_batch=None, *,
+              local_condition_batch=None, local_condition_offset=0,
+              lengths=None, per_sample=False):
+        '''Scores held-out audio: per-clip negative log-likelihood, target
+        count and top-1 hits.  Forward only -- the pass predict_proba makes,
+        on the forward-only workspace: no gradient is touched, no all-reduce
+        starts -- and without any host synchronisation.
+
+        Inputs, their checks and their errors are those of `loss`
+        (global_condition_batch, local_condition_batch / _offset, lengths),
+        except that a 2-D input_batch [B, T] may have ANY number of rows
+        B >= 1 (a validation set ends in a ragged batch); anything else is
+        reshaped to [batch_size, -1].
+
+        Returns scoring.Score(nll, count, correct, per_sample), device
+        tensors: nll float64 [B], the sum over clip b's rows with a target
+        of logsumexp(logits[b, t]) - logits[b, t, q[b, t + 1]] (nats);
+        count int32 [B], the rows with a target (lengths[b] - 1, T - 1
+        without lengths); correct int32 [B], those whose arg-max is the
+        target; per_sample float32 [B, T], each row's term (0 where there is
+        no target: the last real row and the padding), or None unless
+        per_sample=True.
+
+        Relation to the loss: loss(backward=False, lengths=n) ==
+        nll.sum() / sum(n) and loss(backward=False) == nll.sum() / (B * T)
+        (the reference's mean keeps the label-less rows in its denominator),
+        while nll.sum() / count.sum() is the true mean negative
+        log-likelihood per predicted sample, in nats; / ln 2 gives bits.'''
+        self._check_supported()
+        a = input_batch
+        if not isinstance(a, torch.Tensor):
+            a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
+        B = a.shape[0] if a.dim() == 2 and a.shape[0] >= 1 \
+            else self.batch_size
+        a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
+        mask = check_lengths(lengths, None, B, a.shape[1], 'score')
+        lc = lcond.check(self, local_condition_batch, local_condition_offset,
+                         B, a.shape[1], 'score')
+        from . import scoring
+        return scoring.score(self, mu_law_encode(a, self.Q),
+                             global_condition_batch, a, lc, mask, per_sample)
+
+    def score_from_codes(self, q, global_condition_batch=None, audio=None, *,
+                         local_condition_batch=None, local_condition_offset=0,
+                         lengths=None, per_sample=False):
+        """`score` on mu-law codes q (int, [B, T] with any B >= 1, else
+        reshaped to [batch_size, -1]); audio: the float audio a scalar_input
+        model needs."""
+        self._check_supported()
+        if not isinstance(q, torch.Tensor):
+            q = torch.as_tensor(np.asarray(q))
+        B = q.shape[0] if q.dim() == 2 and q.shape[0] >= 1 \
+            else self.batch_size
+        q = q.reshape(B, -1)
+        mask = check_lengths(lengths, None, B, q.shape[1], 'score')
+        lc = lcond.check(self, local_condition_batch, local_condition_offset,
+                         B, q.shape[1], 'score')
+        from . import scoring
+        return scoring.score(self, q, global_condition_batch, audio, lc, mask,
+                             per_sample)
+
     def _l2_tmp(self):
         if not hasattr(self, '_l2_parts'):
             self._l2_parts = torch.empty(_lib.load().wn_l2_partials_count(),

@@ -262,6 +262,15 @@ class _Optimizer(object):
             self._shadow = flat(sd['shadow'], 'shadow')
         self._step = int(sd['step'])
 
+    def ema_flat(self, model):
+        """The shadow weights as the flat device tensor, laid out like
+        model.params (evaluate.parameters_swapped takes it)."""
+        if self.ema_decay is None:
+            raise ValueError('ema_flat() needs an optimizer built with '
+                             'ema_decay')
+        self.init_state(model)
+        return self._shadow
+
     def ema_state_dict(self, model):
         """The shadow weights under the keys of model.state_dict() (loadable
         with model.load_state_dict)."""

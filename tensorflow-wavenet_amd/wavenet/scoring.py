@@ -1,0 +1,54 @@
+"""Scoring of held-out data, host side: the forward pass predict_proba makes,
+then wn_xent_score on its logits (csrc/wn_misc.hip).  Functions take the model
+first; WaveNetModel.score / score_from_codes call in here."""
+import collections
+
+import torch
+
+from . import _lib
+from . import local_condition as lcond
+from . import train_pass
+
+# nll float64 [B], count int32 [B], correct int32 [B] (device tensors, one
+# entry per clip), per_sample float32 [B, T] or None
+Score = collections.namedtuple('Score', 'nll count correct per_sample')
+
+
+def score(net, q, global_condition_batch, audio, lc, mask, per_sample):
+    """Score codes q [B, T] (any B >= 1) with the LC input checked
+    (local_condition.check) and the lengths (model.check_lengths).  Nothing
+    here waits for the device."""
+    B, T = q.shape
+    ws = net._workspace(B, T, False)
+    ws.q.copy_(q.reshape(-1))
+    if net.scalar_input:
+        if audio is None:
+            raise ValueError('scalar_input needs the float audio')
+        ws.audio.copy_(audio.reshape(-1))
+    ids = net._gc_ids(global_condition_batch, B)
+    lcond.fill(net, lc, ws)
+    train_pass.run_pass(net, 'fwd', ws, ids,
+                        train_pass.step_path(net, ws, False))
+    dev = net.device
+    nll = torch.empty(B, dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    correct = torch.empty(B, dtype=torch.int32, device=dev)
+    rows = torch.empty((B, T), dtype=torch.float32, device=dev) \
+        if per_sample else None
+    if getattr(ws, 'score_scratch', None) is None:
+        ws.score_scratch = torch.empty(
+            int(_lib.load().wn_xent_score_scratch_floats(B * T)),
+            dtype=torch.float32, device=dev)
+    lengths = None
+    if mask is not None:
+        # staged in the workspace like the masked loss's: the kernels read
+        # them from device memory
+        lengths = ws.xent_mask[:B]
+        lengths.copy_(torch.from_numpy(mask[0]))
+    _lib.call('wn_xent_score', _lib.ptr(ws.logits), net.Q, _lib.ptr(ws.q),
+              _lib.ptr(lengths), _lib.ptr(rows), _lib.ptr(nll),
+              _lib.ptr(count), _lib.ptr(correct), _lib.ptr(ws.score_scratch),
+              B, T, net.Q, _lib.stream())
+    # 0, or NaN when a dependency wait of the forward stack launch expired
+    # (as predict_proba): a wrong score is never returned silently
+    return Score(nll + ws.loss_parts[0], count, correct, rows)

@@ -135,7 +135,38 @@ def get_arguments(argv=None):
                         'with this decay, in [0, 1) (e.g. 0.9999); saved as '
                         '`ema_variables` for generate.py --use_ema true.  '
                         'Default: none.')
+    p.add_argument('--validation_dir', type=str, default=None,
+                   help='Directory of held-out wav files (and <clip>.npy '
+                        'features with --lc_channels): scored with '
+                        'WaveNetModel.score every --validate_every steps and '
+                        'after the last step; every rank scores its shard of '
+                        'the files.  Default: no validation.')
+    p.add_argument('--validate_every', type=int, default=None,
+                   help='Validate after every step divisible by this '
+                        '(default: --checkpoint_every).')
+    p.add_argument('--validation_batches', type=int, default=None,
+                   help='Score at most this many batches per rank and '
+                        'validation (default: the whole directory).')
+    p.add_argument('--validate_ema', type=_str_to_bool, default=False,
+                   help='Validate the exponential moving average of the '
+                        'weights instead of the weights (needs --ema_decay).')
     return p.parse_args(argv)
+
+
+def validation_flags(args):
+    """ValueError where the validation flags do not fit together."""
+    if args.validate_ema and args.ema_decay is None:
+        raise ValueError('--validate_ema true needs --ema_decay')
+    if args.validation_dir is None:
+        for flag in ('validate_every', 'validation_batches'):
+            if getattr(args, flag) is not None:
+                raise ValueError('--%s needs --validation_dir' % flag)
+        if args.validate_ema:
+            raise ValueError('--validate_ema needs --validation_dir')
+    for flag in ('validate_every', 'validation_batches'):
+        v = getattr(args, flag)
+        if v is not None and v < 1:
+            raise ValueError('--%s must be positive, got %d' % (flag, v))
 
 
 def lc_upsample_scales(args):
@@ -312,6 +343,7 @@ def main(argv=None):
     try:
         lc_scales, lc_hop = lc_upsample_scales(args)
         lc_ctx = lc_context(args)
+        validation_flags(args)
     except ValueError as e:
         print(str(e))
         return 1
@@ -406,6 +438,20 @@ def main(argv=None):
     # (opt-in: the schedule has not been measured on an N-GPU RCCL node yet)
     net.dp_overlap_allreduce = bool(args.dp_overlap_allreduce) and world > 1
 
+    vset = None
+    if args.validation_dir is not None:
+        from wavenet import evaluate as ev
+        # one deterministic pass per validation, this rank's shard of the
+        # sorted files, prepared like the training pieces
+        vset = ev.ValidationSet(
+            args.validation_dir, wavenet_params['sample_rate'],
+            sample_size=args.sample_size,
+            silence_threshold=silence_threshold, gc_enabled=gc_enabled,
+            gc_cardinality=reader.gc_category_cardinality,
+            lc_channels=args.lc_channels, lc_hop=lc_hop,
+            lc_frames=lc_scales is not None, rank=rank, world=world)
+    validate_every = args.validate_every or args.checkpoint_every
+
     threads = reader.start_threads()
     events = None
     if rank == 0:
@@ -416,6 +462,7 @@ def main(argv=None):
     last_saved_step = saved_global_step
     pending = None            # (step, mean loss tensor, start time) not yet printed
     last_report = [None]
+    last_run = validated = None   # --validation_dir: last step run / validated
 
     def report(k, mean_loss, started, real=None, norm=None):
         """Fetch step k's loss (waits for that step), check it, print / log the
@@ -460,6 +507,29 @@ def main(argv=None):
             if real is not None:
                 line['real_samples'] = real
             events.write(json.dumps(line) + '\n')
+            events.flush()
+
+    def validate(k):
+        """Score the validation set with the weights after step k's update
+        (the EMA shadow with --validate_ema): every rank its shard, ONE sum
+        over the ranks whatever a shard holds, rank 0 prints and logs."""
+        import contextlib
+        swap = ev.parameters_swapped(net, optimizer.ema_flat(net)) \
+            if args.validate_ema else contextlib.nullcontext()
+        with swap:
+            tot = ev.totals(net, vset.batches(args.batch_size),
+                            args.validation_batches)
+        res = ev.summary(ev.sum_over_ranks(tot, net.device))
+        if rank == 0:
+            print('step {:d} - validation loss = {:.3f}, bits/sample = {:.3f}'
+                  ', accuracy = {:.3f}'.format(
+                      k, res['nll_per_sample'], res['bits_per_sample'],
+                      res['accuracy']))
+            events.write(json.dumps({
+                'step': k, 'validation_loss': res['nll_per_sample'],
+                'validation_bits': res['bits_per_sample'],
+                'validation_accuracy': res['accuracy'],
+                'validation_samples': res['samples']}) + '\n')
             events.flush()
 
     fetch_slots = {}
@@ -595,9 +665,22 @@ def main(argv=None):
                         **{k + '/counts': v[0] for k, v in hs.items()},
                         **{k + '/range': np.asarray(v[1:])
                            for k, v in hs.items()})
+            if vset is not None:
+                last_run = step
+                if step % validate_every == 0:
+                    # (the one-step-late training line first: the lines stay
+                    # in order)
+                    if pending is not None:
+                        report(*pending)
+                        pending = None
+                    validate(step)
+                    validated = step
         if pending is not None:
             report(*pending)
             pending = None
+        if vset is not None and last_run is not None and \
+                validated != last_run:
+            validate(last_run)              # after the last step
     except KeyboardInterrupt:
         print()
     finally:
