@@ -809,7 +809,7 @@ int wn_fastgen_batch_step_lc(const float* params_causal, const float* layer0,
                              void* stream);
 
 /* ---- learned upsampling of frame-rate local-conditioning features
- * (csrc/wn_misc.hip).  scales: host array of m (1..8) ints >= 2, hop = their
+ * (csrc/wn_lc.hip).  scales: host array of m (1..8) ints >= 2, hop = their
  * product <= 4096.  `up`: the model's lc_up segment, the filters W_i[s_i][3] of
  * all layers back to back, then (use_bias) the m biases;
  * wn_lc_upsample_floats(scales, m, use_bias) floats (0 for bad scales).
@@ -849,7 +849,7 @@ int wn_lc_upsample_bwd_ctx(const float* frames, int F, const int32_t* off,
                            long slab_stride, float* dframes, float* dpart,
                            void* stream);
 
-/* ---- frame-context convolution in front of the upsampler (csrc/wn_misc.hip).
+/* ---- frame-context convolution in front of the upsampler (csrc/wn_lc.hip).
  * 0 <= p <= 8, 1 <= Lc <= 512; w [2p + 1][Lc][Lc] ([K][Cin][Cout]), no bias.
  * x [B][Fx][Lc]: frames staged with p frames of context either side, Fx >=
  * Fw + 2p.  fwd: ctx[b][f][j] = sum_{k, c} w[k][c][j] x[b][f + k][c] for

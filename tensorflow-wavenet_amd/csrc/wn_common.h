@@ -67,6 +67,14 @@ static inline bool wn_aligned16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
 }
 
+// workgroups of a grid-stride launch over n elements
+static inline int grid1d(long n, int block, int cap = 2048) {
+  long g = (n + block - 1) / block;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 #ifdef __HIPCC__
 
 __device__ __forceinline__ f32x16 frag_zero() {

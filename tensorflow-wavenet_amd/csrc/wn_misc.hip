@@ -1,7 +1,8 @@
 // Streaming (HBM-bound) kernels around the MFMA core: mu-law companding, the
-// one-hot "conv" of the causal layer as a 2-row gather, fused softmax
-// cross-entropy, optimizers with TensorFlow update rules, global-conditioning
-// helpers, and the thin exported ops (causal_conv, time_to_batch, ...).
+// one-hot "conv" of the causal layer as a 2-row gather and its weight
+// gradient, global-conditioning helpers, and the thin exported ops
+// (causal_conv, time_to_batch, ...).  The loss and scoring are in wn_loss.hip,
+// the optimizers in wn_optim.hip, the learned LC upsampler in wn_lc.hip.
 #include "wn_common.h"
 #include <stdlib.h>
 #include <cmath>
@@ -180,576 +181,6 @@ __global__ __launch_bounds__(1024) void scalar_causal_wgrad_kernel(
       if (++t == T) t = 0;
     }
     slabs[(long)blockIdx.x * K0 * 32 + k * 32 + c] = acc;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// fused softmax cross-entropy, forward + backward   (model.py:654-666)
-// One wave per row.  target of row (b,t) = q[b][t+1]; the last row of every
-// clip has the all-zero label row the reference pads in (model.py:659): its
-// loss term is 0 but it stays in the mean's denominator, and with
-// tf_quirk != 0 it back-propagates softmax/(B*T) like TF's fused kernel
-// (backprop = softmax - labels).
-//
-// MASKED (wn_xent_masked): clip b has lengths[b] real samples and right
-// padding after them, and is treated as a clip of T = lengths[b] fed alone:
-// row lengths[b] - 1 is its label-less last row, rows t >= lengths[b] add
-// nothing to the loss and get an all-zero dlogits row without an exponential
-// being evaluated.  1 / denominator arrives in inv_n like 1 / (B*T) does.
-// One body for both kernels: lengths[b] = T takes exactly the unmasked
-// arithmetic, so the two agree bit for bit there.
-// ---------------------------------------------------------------------------
-// row -> its clip's length (T when nothing is masked)
-template <bool MASKED>
-__device__ __forceinline__ int xent_len(long row, int T,
-                                        const int32_t* lengths) {
-  return MASKED ? min(max(lengths[row / T], 0), T) : T;
-}
-
-template <bool MASKED>
-__device__ __forceinline__ void xent_body(
-    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    const int32_t* __restrict__ lengths, float* __restrict__ dlogits,
-    float* __restrict__ loss_partials, long rows, int T, int Q, float inv_n,
-    int tf_quirk) {
-  __shared__ float wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float lsum = 0.f;
-  const long nwaves = (long)gridDim.x * 4;
-  if (Q == 256) {
-    // one 16-byte load per lane holds the whole row: a single pass, each exp
-    // evaluated once, the next row's load in flight under the reductions
-    long row = (long)blockIdx.x * 4 + wave;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < rows) v = *reinterpret_cast<const f32x4*>(logits + row * ld + lane * 4);
-    for (; row < rows; row += nwaves) {
-      const long nrow = row + nwaves;
-      f32x4 vn = {0.f, 0.f, 0.f, 0.f};
-      if (nrow < rows)
-        vn = *reinterpret_cast<const f32x4*>(logits + nrow * ld + lane * 4);
-      const int t = (int)(row % T);
-      const int len = xent_len<MASKED>(row, T, lengths);
-      if (MASKED && t >= len) {              // padding
-        if (dlogits)
-          *reinterpret_cast<f32x4*>(dlogits + row * ld + lane * 4) =
-              f32x4{0.f, 0.f, 0.f, 0.f};
-        v = vn;
-        continue;
-      }
-      const int label = (t + 1 < len) ? q[row + 1] : -1;
-      const bool has_label = label >= 0 && label < Q;
-      float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-      float e[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = expf(v[k] - m);
-      float se = (e[0] + e[1]) + (e[2] + e[3]);
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
-      const float lse = m + logf(se);
-      if (has_label) {
-        // the label's logit lives in lane label >> 2
-        const float mine = (label >> 2) == lane ? v[label & 3] : 0.f;
-        float ll = mine;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) ll += __shfl_xor(ll, o);
-        if (lane == 0) lsum += lse - ll;
-      }
-      if (dlogits) {
-        const float inv_se = 1.f / se;
-        const bool back = has_label || tf_quirk;
-        f32x4 g;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float p = back ? e[k] * inv_se : 0.f;
-          if (has_label && lane * 4 + k == label) p -= 1.f;
-          g[k] = p * inv_n;
-        }
-        *reinterpret_cast<f32x4*>(dlogits + row * ld + lane * 4) = g;
-      }
-      v = vn;
-    }
-  } else
-  for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += nwaves) {
-    const float* lp = logits + row * ld;
-    const int t = (int)(row % T);
-    const int len = xent_len<MASKED>(row, T, lengths);
-    if (MASKED && t >= len) {                // padding
-      if (dlogits)
-        for (int c = lane * 4; c < Q; c += 256)
-          *reinterpret_cast<f32x4*>(dlogits + row * ld + c) =
-              f32x4{0.f, 0.f, 0.f, 0.f};
-      continue;
-    }
-    const int label = (t + 1 < len) ? q[row + 1] : -1;
-    const bool has_label = label >= 0 && label < Q;
-    float m = -INFINITY;
-    for (int c = lane * 4; c < Q; c += 256) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
-      m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float se = 0.f;
-    for (int c = lane * 4; c < Q; c += 256) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
-      se += expf(v[0] - m) + expf(v[1] - m) + expf(v[2] - m) + expf(v[3] - m);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
-    const float lse = m + logf(se);
-    if (has_label && lane == 0) lsum += lse - lp[label];
-    const float inv_se = 1.f / se;
-    const bool back = has_label || tf_quirk;
-    if (dlogits) {
-      float* dp = dlogits + row * ld;
-      for (int c = lane * 4; c < Q; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
-        f32x4 g;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float p = back ? expf(v[e] - m) * inv_se : 0.f;
-          if (has_label && c + e == label) p -= 1.f;
-          g[e] = p * inv_n;
-        }
-        *reinterpret_cast<f32x4*>(dp + c) = g;
-      }
-    }
-  }
-  if (lane == 0) wsum[wave] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    loss_partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-__global__ __launch_bounds__(256) void xent_kernel(
-    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
-    int T, int Q, float inv_n, int tf_quirk) {
-  xent_body<false>(logits, ld, q, nullptr, dlogits, loss_partials, rows, T, Q,
-                   inv_n, tf_quirk);
-}
-
-// lengths [B] and 1 / denominator are read from device memory: a recorded
-// launch replays with this call's values
-__global__ __launch_bounds__(256) void xent_masked_kernel(
-    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    const int32_t* __restrict__ lengths, const float* __restrict__ inv_den,
-    float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
-    int T, int Q, int tf_quirk) {
-  xent_body<true>(logits, ld, q, lengths, dlogits, loss_partials, rows, T, Q,
-                  *inv_den, tf_quirk);
-}
-
-// ---------------------------------------------------------------------------
-// scoring (wn_xent_score): per-row negative log-likelihood, per-clip sums,
-// target counts and arg-max hits of held-out data.  Forward only.
-//
-// xent_score_rows_kernel: one wave per row, xent_body's float32 formulas
-// (max, expf, sum, m + logf(se), the same shuffle trees) on the rows that
-// have a target -- t + 1 < len_b and 0 <= q[b][t + 1] < Q -- and nothing but
-// a stored 0 for the others (the label-less last row, a code out of range,
-// padding): no exponential is evaluated there.  It writes nll[row] and
-// flag[row] = 0 (no target) | 1 (target) | 3 (target, and the lowest index of
-// the row's maximum over [0, Q) is the target; never for a row whose
-// logsumexp is NaN).  Columns >= Q are not read.
-// xent_score_clips_kernel: one workgroup per clip.  Thread i sums rows i,
-// i + 1024, ... below len_b - 1 in float64 (integers for the flags), a fixed
-// LDS tree finishes: a function of the rows' values and len_b alone, whatever
-// order the workgroups of either kernel ran in.  No atomics.
-// ---------------------------------------------------------------------------
-#define SCORE_CLIP_THREADS 1024
-
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-
-__global__ __launch_bounds__(256) void xent_score_rows_kernel(
-    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    const int32_t* __restrict__ lengths, float* __restrict__ nll,
-    int32_t* __restrict__ flag, long rows, int T, int Q) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long nwaves = (long)gridDim.x * 4;
-  const int none = 0x7fffffff;
-  if (Q == 256) {
-    // xent_body's single pass: one 16-byte load per lane holds the row, the
-    // next row's load in flight under the reductions
-    long row = (long)blockIdx.x * 4 + wave;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < rows) v = *reinterpret_cast<const f32x4*>(logits + row * ld + lane * 4);
-    for (; row < rows; row += nwaves) {
-      const long nrow = row + nwaves;
-      f32x4 vn = {0.f, 0.f, 0.f, 0.f};
-      if (nrow < rows)
-        vn = *reinterpret_cast<const f32x4*>(logits + nrow * ld + lane * 4);
-      const int t = (int)(row % T);
-      const int len = lengths ? min(max(lengths[row / T], 0), T) : T;
-      const int label = (t + 1 < len) ? q[row + 1] : -1;
-      if (!(label >= 0 && label < Q)) {      // no target: nothing to evaluate
-        if (lane == 0) {
-          nll[row] = 0.f;
-          flag[row] = 0;
-        }
-        v = vn;
-        continue;
-      }
-      float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-      float e[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = expf(v[k] - m);
-      float se = (e[0] + e[1]) + (e[2] + e[3]);
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
-      const float lse = m + logf(se);
-      const float mine = (label >> 2) == lane ? v[label & 3] : 0.f;
-      float ll = mine;
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) ll += __shfl_xor(ll, o);
-      int best = none;                       // lowest index holding the maximum
-#pragma unroll
-      for (int k = 3; k >= 0; --k) best = v[k] == m ? lane * 4 + k : best;
-      best = wave_min_i32(best);
-      if (lane == 0) {
-        nll[row] = lse - ll;
-        flag[row] = (best == label && lse == lse) ? 3 : 1;
-      }
-      v = vn;
-    }
-    return;
-  }
-  for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += nwaves) {
-    const float* lp = logits + row * ld;
-    const int t = (int)(row % T);
-    const int len = lengths ? min(max(lengths[row / T], 0), T) : T;
-    const int label = (t + 1 < len) ? q[row + 1] : -1;
-    if (!(label >= 0 && label < Q)) {
-      if (lane == 0) {
-        nll[row] = 0.f;
-        flag[row] = 0;
-      }
-      continue;
-    }
-    float m = -INFINITY;
-    for (int c = lane * 4; c < Q; c += 256) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
-      m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float se = 0.f;
-    int best = none;
-    for (int c = lane * 4; c < Q; c += 256) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(lp + c);
-      se += expf(v[0] - m) + expf(v[1] - m) + expf(v[2] - m) + expf(v[3] - m);
-#pragma unroll
-      for (int k = 3; k >= 0; --k) best = v[k] == m ? min(best, c + k) : best;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o);
-    best = wave_min_i32(best);
-    const float lse = m + logf(se);
-    if (lane == 0) {
-      nll[row] = lse - lp[label];
-      flag[row] = (best == label && lse == lse) ? 3 : 1;
-    }
-  }
-}
-
-__global__ __launch_bounds__(SCORE_CLIP_THREADS) void xent_score_clips_kernel(
-    const float* __restrict__ nll, const int32_t* __restrict__ flag,
-    const int32_t* __restrict__ lengths, double* __restrict__ clip_nll,
-    int32_t* __restrict__ clip_count, int32_t* __restrict__ clip_correct,
-    int T) {
-  __shared__ double rs[SCORE_CLIP_THREADS];
-  __shared__ int rc[SCORE_CLIP_THREADS], rh[SCORE_CLIP_THREADS];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int len = lengths ? min(max(lengths[b], 0), T) : T;
-  const float* pn = nll + (long)b * T;
-  const int32_t* pf = flag + (long)b * T;
-  double s = 0.0;
-  int c = 0, h = 0;
-  // (rows t >= len - 1 have no target: zeros by construction, not read)
-  for (int t = tid; t < len - 1; t += SCORE_CLIP_THREADS) {
-    const int f = pf[t];
-    s += (double)pn[t];
-    c += f & 1;
-    h += f >> 1;
-  }
-  rs[tid] = s;
-  rc[tid] = c;
-  rh[tid] = h;
-  __syncthreads();
-  for (int k = SCORE_CLIP_THREADS / 2; k > 0; k >>= 1) {
-    if (tid < k) {
-      rs[tid] += rs[tid + k];
-      rc[tid] += rc[tid + k];
-      rh[tid] += rh[tid + k];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    clip_nll[b] = rs[0];
-    clip_count[b] = rc[0];
-    clip_correct[b] = rh[0];
-  }
-}
-
-// softmax of ONE row in float64, cast to float32 (model.py:584-585, 620-621)
-__global__ void softmax64_row_kernel(const float* __restrict__ logits, int Q,
-                                     float* __restrict__ proba) {
-  __shared__ double red[256];
-  const int tid = threadIdx.x;
-  double m = -INFINITY;
-  for (int c = tid; c < Q; c += 256) m = fmax(m, (double)logits[c]);
-  red[tid] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  m = red[0];
-  __syncthreads();
-  double se = 0.0;
-  for (int c = tid; c < Q; c += 256) se += exp((double)logits[c] - m);
-  red[tid] = se;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  se = red[0];
-  for (int c = tid; c < Q; c += 256)
-    proba[c] = (float)(exp((double)logits[c] - m) / se);
-}
-
-// ---------------------------------------------------------------------------
-// optimizers, TensorFlow-0.10 update rules (wavenet/ops.py:6-24)
-//   g' = g * grad_scale + l2 * p * (l2_mask ? l2_mask[i] : 1)
-// ---------------------------------------------------------------------------
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                            float* __restrict__ m, float* __restrict__ v,
-                            long n, float lr_t, float b1, float b2, float eps,
-                            float grad_scale, float l2,
-                            const float* __restrict__ l2_mask) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float gg = g[i] * grad_scale;
-    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
-    const float mm = b1 * m[i] + (1.f - b1) * gg;
-    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    m[i] = mm;
-    v[i] = vv;
-    p[i] = w - lr_t * mm / (sqrtf(vv) + eps);
-  }
-}
-
-__global__ void momentum_kernel(float* __restrict__ p,
-                                const float* __restrict__ g,
-                                float* __restrict__ acc, long n, float lr,
-                                float mom, float grad_scale, float l2,
-                                const float* __restrict__ l2_mask) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float gg = g[i] * grad_scale;
-    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
-    const float a = mom * acc[i] + gg;
-    acc[i] = a;
-    p[i] = w - lr * a;
-  }
-}
-
-__global__ void rmsprop_kernel(float* __restrict__ p,
-                               const float* __restrict__ g,
-                               float* __restrict__ ms, float* __restrict__ mo,
-                               long n, float lr, float decay, float mom,
-                               float eps, float grad_scale, float l2,
-                               const float* __restrict__ l2_mask) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float gg = g[i] * grad_scale;
-    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
-    const float s = decay * ms[i] + (1.f - decay) * gg * gg;
-    const float mm = mom * mo[i] + lr * gg / sqrtf(s + eps);
-    ms[i] = s;
-    mo[i] = mm;
-    p[i] = w - mm;
-  }
-}
-
-// sum of squares / 2 (tf.nn.l2_loss) partials, with optional mask
-__global__ void l2_partials_kernel(const float* __restrict__ p, long n,
-                                   const float* __restrict__ mask,
-                                   float* __restrict__ partials) {
-  __shared__ float red[256];
-  float s = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    s += w * w * (mask ? mask[i] : 1.f);
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (unsigned k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[blockIdx.x] = 0.5f * red[0];
-}
-
-// ---------------------------------------------------------------------------
-// global-norm clipping (tf.clip_by_global_norm) and EMA weights
-// (tf.train.ExponentialMovingAverage) inside the optimizer launches.
-//
-// grad_norm_partials_kernel: GNORM_PARTS float64 sums of g[i]^2.  Partial k
-// covers elements [k * per, min(n, (k + 1) * per)), per = the multiple of 4
-// next above n / GNORM_PARTS; inside it thread t takes the 16-byte groups
-// t, t + 1024, ... in order, a wave is summed by a shuffle tree and the 16
-// wave sums in order.  Grid, block and ranges depend on (n, GNORM_PARTS) only:
-// the bits are a function of the bucket and n, not of the device.
-//
-// The *_clip kernels are the kernels above, element for element, behind a
-// prologue in which EVERY workgroup sums the same partials in the same order
-// (float64), forms  norm = grad_scale * sqrt(sum)  and
-// factor = clip_norm / max(norm, clip_norm)  (NaN for a non-finite norm, as
-// TensorFlow) and scales by  grad_scale * (float)factor  -- grad_scale itself
-// when norm <= clip_norm, so the update is then the plain kernel's bit for bit
-// -- and an epilogue  s -= (1 - decay) * (s - p_new)  on the shadow weights.
-// ---------------------------------------------------------------------------
-#define GNORM_PARTS 256
-#define GNORM_THREADS 1024
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;  // lane 0: the wave's sum
-}
-
-__global__ __launch_bounds__(GNORM_THREADS) void grad_norm_partials_kernel(
-    const float* __restrict__ g, long n, long per,
-    double* __restrict__ partials) {
-  __shared__ double red[GNORM_THREADS / 64];
-  const long lo = (long)blockIdx.x * per;
-  const long hi = lo + per < n ? lo + per : n;
-  double s = 0.0;
-  for (long i = lo + 4L * threadIdx.x; i < hi; i += 4L * GNORM_THREADS) {
-    if (i + 4 <= hi) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s += (double)v[e] * (double)v[e];
-    } else {
-      for (long j = i; j < hi; ++j) s += (double)g[j] * (double)g[j];
-    }
-  }
-  s = wave_sum_f64(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < GNORM_THREADS / 64; ++w) t += red[w];
-    partials[blockIdx.x] = t;
-  }
-}
-
-// the effective gradient scale of a *_clip kernel (256 threads, all of them
-// call it); partials == nullptr: grad_scale
-__device__ __forceinline__ float clip_scale(const double* __restrict__ partials,
-                                            float clip_norm, float grad_scale,
-                                            float* __restrict__ norm_out) {
-  if (!partials) return grad_scale;
-  __shared__ double red[4];
-  const double s = wave_sum_f64(partials[threadIdx.x]);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const double sum = ((red[0] + red[1]) + red[2]) + red[3];
-  const double norm = (double)grad_scale * sqrt(sum);
-  const double cn = (double)clip_norm;
-  const double factor = isfinite(norm) ? cn / (norm > cn ? norm : cn)
-                                       : (double)NAN;
-  if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
-  return grad_scale * (float)factor;
-}
-
-__global__ __launch_bounds__(256) void adam_clip_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    float* __restrict__ v, long n, float lr_t, float b1, float b2, float eps,
-    float grad_scale, float l2, const float* __restrict__ l2_mask,
-    const double* __restrict__ partials, float clip_norm,
-    float* __restrict__ ema, float ema_decay, float* __restrict__ norm_out) {
-  const float scale = clip_scale(partials, clip_norm, grad_scale, norm_out);
-  const float keep = 1.f - ema_decay;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float gg = g[i] * scale;
-    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
-    const float mm = b1 * m[i] + (1.f - b1) * gg;
-    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    m[i] = mm;
-    v[i] = vv;
-    const float pn = w - lr_t * mm / (sqrtf(vv) + eps);
-    p[i] = pn;
-    if (ema) {
-      const float s = ema[i];
-      ema[i] = s - keep * (s - pn);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void momentum_clip_kernel(
-    float* __restrict__ p, const float* __restrict__ g,
-    float* __restrict__ acc, long n, float lr, float mom, float grad_scale,
-    float l2, const float* __restrict__ l2_mask,
-    const double* __restrict__ partials, float clip_norm,
-    float* __restrict__ ema, float ema_decay, float* __restrict__ norm_out) {
-  const float scale = clip_scale(partials, clip_norm, grad_scale, norm_out);
-  const float keep = 1.f - ema_decay;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float gg = g[i] * scale;
-    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
-    const float a = mom * acc[i] + gg;
-    acc[i] = a;
-    const float pn = w - lr * a;
-    p[i] = pn;
-    if (ema) {
-      const float s = ema[i];
-      ema[i] = s - keep * (s - pn);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void rmsprop_clip_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ ms,
-    float* __restrict__ mo, long n, float lr, float decay, float mom,
-    float eps, float grad_scale, float l2, const float* __restrict__ l2_mask,
-    const double* __restrict__ partials, float clip_norm,
-    float* __restrict__ ema, float ema_decay, float* __restrict__ norm_out) {
-  const float scale = clip_scale(partials, clip_norm, grad_scale, norm_out);
-  const float keep = 1.f - ema_decay;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float gg = g[i] * scale;
-    if (l2 != 0.f) gg += l2 * w * (l2_mask ? l2_mask[i] : 1.f);
-    const float s = decay * ms[i] + (1.f - decay) * gg * gg;
-    const float mm = mom * mo[i] + lr * gg / sqrtf(s + eps);
-    ms[i] = s;
-    mo[i] = mm;
-    const float pn = w - mm;
-    p[i] = pn;
-    if (ema) {
-      const float e = ema[i];
-      ema[i] = e - keep * (e - pn);
-    }
   }
 }
 
@@ -955,13 +386,6 @@ __global__ void sum_rows_kernel(const float* __restrict__ in, int rows, int n,
   }
   for (; r < rows; ++r) s += in[(long)r * n + c];
   out[c] = s;
-}
-
-static inline int grid1d(long n, int block, int cap = 2048) {
-  long g = (n + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 extern "C" {
@@ -1238,217 +662,6 @@ int wn_causal_wgrad(const int32_t* q, const float* dx0, float* slabs,
   return wn_check_launch();
 }
 
-int wn_xent_partials(long rows) {
-  long g = (rows + 3) / 4;
-  if (g > 1024) g = 1024;
-  return (int)g;
-}
-
-int wn_xent(const float* logits, long ld, const int32_t* q, float* dlogits,
-            float* loss_partials, int B, int T, int Q, int tf_quirk,
-            void* stream) {
-  if (!logits || !q || !loss_partials) return WN_ERR_NULL;
-  if (B <= 0 || T <= 0 || Q <= 0) return WN_ERR_BAD_SHAPE;
-  if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
-  if (!wn_aligned16(logits) || (dlogits && !wn_aligned16(dlogits)))
-    return WN_ERR_MISALIGNED;
-  const long rows = (long)B * T;
-  const float inv_n = 1.0f / (float)rows;
-  hipLaunchKernelGGL(xent_kernel, dim3(wn_xent_partials(rows)), dim3(256), 0,
-                     (hipStream_t)stream, logits, ld, q, dlogits,
-                     loss_partials, rows, T, Q, inv_n, tf_quirk);
-  return wn_check_launch();
-}
-
-int wn_xent_masked(const float* logits, long ld, const int32_t* q,
-                   const int32_t* lengths, const float* inv_den,
-                   float* dlogits, float* loss_partials, int B, int T, int Q,
-                   int tf_quirk, void* stream) {
-  if (!logits || !q || !lengths || !inv_den || !loss_partials)
-    return WN_ERR_NULL;
-  if (B <= 0 || T <= 0 || Q <= 0) return WN_ERR_BAD_SHAPE;
-  if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
-  if (!wn_aligned16(logits) || (dlogits && !wn_aligned16(dlogits)) ||
-      ((uintptr_t)lengths & 3) || ((uintptr_t)inv_den & 3))
-    return WN_ERR_MISALIGNED;
-  const long rows = (long)B * T;
-  hipLaunchKernelGGL(xent_masked_kernel, dim3(wn_xent_partials(rows)),
-                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, lengths,
-                     inv_den, dlogits, loss_partials, rows, T, Q, tf_quirk);
-  return wn_check_launch();
-}
-
-long wn_xent_score_scratch_floats(long rows) {
-  return rows > 0 ? 2 * rows : 0;          // flags [rows], row values [rows]
-}
-
-int wn_xent_score(const float* logits, long ld, const int32_t* q,
-                  const int32_t* lengths, float* row_nll, double* clip_nll,
-                  int32_t* clip_count, int32_t* clip_correct, float* scratch,
-                  int B, int T, int Q, void* stream) {
-  if (!logits || !q || !clip_nll || !clip_count || !clip_correct || !scratch)
-    return WN_ERR_NULL;
-  if (B <= 0 || T <= 0 || Q <= 0 || ld < Q) return WN_ERR_BAD_SHAPE;
-  if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
-  if (!wn_aligned16(logits) || ((uintptr_t)lengths & 3) ||
-      ((uintptr_t)row_nll & 3) || ((uintptr_t)clip_nll & 7) ||
-      ((uintptr_t)clip_count & 3) || ((uintptr_t)clip_correct & 3) ||
-      ((uintptr_t)scratch & 3))
-    return WN_ERR_MISALIGNED;
-  const long rows = (long)B * T;
-  int32_t* flag = reinterpret_cast<int32_t*>(scratch);
-  // (without row_nll the row values go to the scratch: the per-clip sums
-  // read the same bits either way)
-  float* nll = row_nll ? row_nll : scratch + rows;
-  hipLaunchKernelGGL(xent_score_rows_kernel, dim3(wn_xent_partials(rows)),
-                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, lengths,
-                     nll, flag, rows, T, Q);
-  hipLaunchKernelGGL(xent_score_clips_kernel, dim3(B),
-                     dim3(SCORE_CLIP_THREADS), 0, (hipStream_t)stream, nll,
-                     flag, lengths, clip_nll, clip_count, clip_correct, T);
-  return wn_check_launch();
-}
-
-int wn_softmax64_row(const float* logits_row, int Q, float* proba,
-                     void* stream) {
-  if (!logits_row || !proba) return WN_ERR_NULL;
-  if (Q <= 0) return WN_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(softmax64_row_kernel, dim3(1), dim3(256), 0,
-                     (hipStream_t)stream, logits_row, Q, proba);
-  return wn_check_launch();
-}
-
-int wn_adam(float* p, const float* g, float* m, float* v, long n, float lr_t,
-            float beta1, float beta2, float eps, float grad_scale, float l2,
-            const float* l2_mask, void* stream) {
-  if (!p || !g || !m || !v) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, p, g, m, v, n, lr_t, beta1, beta2,
-                     eps, grad_scale, l2, l2_mask);
-  return wn_check_launch();
-}
-
-int wn_momentum(float* p, const float* g, float* acc, long n, float lr,
-                float momentum, float grad_scale, float l2,
-                const float* l2_mask, void* stream) {
-  if (!p || !g || !acc) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(momentum_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, p, g, acc, n, lr, momentum,
-                     grad_scale, l2, l2_mask);
-  return wn_check_launch();
-}
-
-int wn_rmsprop(float* p, const float* g, float* ms, float* mom, long n,
-               float lr, float decay, float momentum, float eps,
-               float grad_scale, float l2, const float* l2_mask,
-               void* stream) {
-  if (!p || !g || !ms || !mom) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(rmsprop_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, p, g, ms, mom, n, lr, decay,
-                     momentum, eps, grad_scale, l2, l2_mask);
-  return wn_check_launch();
-}
-
-int wn_grad_norm_partials_count(void) { return GNORM_PARTS; }
-
-int wn_grad_norm_partials(const float* g, long n, double* partials,
-                          void* stream) {
-  if (!g || !partials) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  if (!wn_aligned16(g) || ((uintptr_t)partials & 7)) return WN_ERR_MISALIGNED;
-  // elements per partial: a multiple of 4, so that every range starts on a
-  // 16-byte boundary
-  const long per = ((n + 4L * GNORM_PARTS - 1) / (4L * GNORM_PARTS)) * 4;
-  hipLaunchKernelGGL(grad_norm_partials_kernel, dim3(GNORM_PARTS),
-                     dim3(GNORM_THREADS), 0, (hipStream_t)stream, g, n, per,
-                     partials);
-  return wn_check_launch();
-}
-
-// the added arguments of the *_clip entry points
-static int clip_args_check(const double* partials, int nparts, float clip_norm,
-                           const float* ema, float ema_decay,
-                           const float* norm_out) {
-  if (partials) {
-    if (nparts != GNORM_PARTS) return WN_ERR_BAD_SHAPE;
-    if (!(clip_norm > 0.f) || !std::isfinite(clip_norm))
-      return WN_ERR_BAD_SHAPE;
-    if ((uintptr_t)partials & 7) return WN_ERR_MISALIGNED;
-  }
-  if (ema) {
-    if (!(ema_decay >= 0.f && ema_decay < 1.f)) return WN_ERR_BAD_SHAPE;
-    if ((uintptr_t)ema & 3) return WN_ERR_MISALIGNED;
-  }
-  if ((uintptr_t)norm_out & 3) return WN_ERR_MISALIGNED;
-  return WN_OK;
-}
-
-int wn_adam_clip(float* p, const float* g, float* m, float* v, long n,
-                 float lr_t, float beta1, float beta2, float eps,
-                 float grad_scale, float l2, const float* l2_mask,
-                 const double* partials, int nparts, float clip_norm,
-                 float* ema, float ema_decay, float* norm_out, void* stream) {
-  if (!p || !g || !m || !v) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  const int rc = clip_args_check(partials, nparts, clip_norm, ema, ema_decay,
-                                 norm_out);
-  if (rc != WN_OK) return rc;
-  hipLaunchKernelGGL(adam_clip_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, p, g, m, v, n, lr_t, beta1, beta2,
-                     eps, grad_scale, l2, l2_mask, partials, clip_norm, ema,
-                     ema_decay, norm_out);
-  return wn_check_launch();
-}
-
-int wn_momentum_clip(float* p, const float* g, float* acc, long n, float lr,
-                     float momentum, float grad_scale, float l2,
-                     const float* l2_mask, const double* partials, int nparts,
-                     float clip_norm, float* ema, float ema_decay,
-                     float* norm_out, void* stream) {
-  if (!p || !g || !acc) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  const int rc = clip_args_check(partials, nparts, clip_norm, ema, ema_decay,
-                                 norm_out);
-  if (rc != WN_OK) return rc;
-  hipLaunchKernelGGL(momentum_clip_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, p, g, acc, n, lr, momentum,
-                     grad_scale, l2, l2_mask, partials, clip_norm, ema,
-                     ema_decay, norm_out);
-  return wn_check_launch();
-}
-
-int wn_rmsprop_clip(float* p, const float* g, float* ms, float* mom, long n,
-                    float lr, float decay, float momentum, float eps,
-                    float grad_scale, float l2, const float* l2_mask,
-                    const double* partials, int nparts, float clip_norm,
-                    float* ema, float ema_decay, float* norm_out,
-                    void* stream) {
-  if (!p || !g || !ms || !mom) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  const int rc = clip_args_check(partials, nparts, clip_norm, ema, ema_decay,
-                                 norm_out);
-  if (rc != WN_OK) return rc;
-  hipLaunchKernelGGL(rmsprop_clip_kernel, dim3(grid1d(n, 256)), dim3(256), 0,
-                     (hipStream_t)stream, p, g, ms, mom, n, lr, decay,
-                     momentum, eps, grad_scale, l2, l2_mask, partials,
-                     clip_norm, ema, ema_decay, norm_out);
-  return wn_check_launch();
-}
-
-int wn_l2_partials_count(void) { return 256; }
-
-int wn_l2_partials(const float* p, long n, const float* mask, float* partials,
-                   void* stream) {
-  if (!p || !partials) return WN_ERR_NULL;
-  if (n <= 0) return WN_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(l2_partials_kernel, dim3(256), dim3(256), 0,
-                     (hipStream_t)stream, p, n, mask, partials);
-  return wn_check_launch();
-}
-
 int wn_gc_bias(const float* layer0, long layer_stride, long off_bias,
                long off_gc, int G, const float* emb, int card,
                const int32_t* ids, float* out, int L, int B, int ch,
@@ -1560,538 +773,6 @@ int wn_sum_rows(const float* in, int rows, int n, float* out, void* stream) {
   if (rows <= 0 || n <= 0) return WN_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(sum_rows_kernel, dim3((n + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, in, rows, n, out);
-  return wn_check_launch();
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// Learned upsampling of frame-rate local-conditioning features (WaveNet paper
-// 2.5).  Layer i (scale s_i) is a transposed convolution over time with
-// kernel = stride = s_i and, over the feature axis, a 3-tap kernel with zero
-// padding and one scalar bias:
-//   out[c] = b_i + W_i[j][0] u[c-1] + W_i[j][1] u[c] + W_i[j][2] u[c+1]
-// for output slot j of an input row u.  Timeline position p = off[b] + t takes
-// frame p / hop and the slot digits of p % hop, most significant first.  A
-// row is computed from its frame, its slot and the weights alone, in one
-// fixed order (explicit FMAs): its bits do not depend on the batch, the clip
-// length, the offset or the call.
-//
-// Segment layout (`up`): filters W_i[s_i][3] of all layers back to back, then
-// (use_bias) the m biases.  Per launch: frames [B][F][Lc], off[b] int32.
-// ---------------------------------------------------------------------------
-#define LCUP_MAX_LAYERS 8
-#define LCUP_MAX_LC 512
-#define LCUP_CPL (LCUP_MAX_LC / 64)          // channels per lane
-
-struct LcUpGeom {
-  int m, hop, Lc, use_bias;
-  int s[LCUP_MAX_LAYERS];    // scales
-  int suf[LCUP_MAX_LAYERS];  // s_{i+1} * ... * s_m (slot digit divisor)
-  int fo[LCUP_MAX_LAYERS];   // filter offset of layer i in the segment
-  int bo;                    // offset of the biases
-};
-
-__device__ __forceinline__ int lcup_slot(const LcUpGeom& g, int i, int j) {
-  return (j / g.suf[i]) % g.s[i];
-}
-
-// one layer of one row: buf_in / buf_out hold Lc + 2 floats with a zero at
-// either end (index c + 1 is channel c)
-__device__ __forceinline__ void lcup_layer(const LcUpGeom& g,
-                                           const float* __restrict__ up, int i,
-                                           int j, const float* bin, float* bout,
-                                           int lane) {
-  const int slot = lcup_slot(g, i, j);
-  const float* w = up + g.fo[i] + 3 * slot;
-  const float w0 = w[0], w1 = w[1], w2 = w[2];
-  const float b = g.use_bias ? up[g.bo + i] : 0.f;
-#pragma unroll
-  for (int k = 0; k < LCUP_CPL; ++k) {
-    const int c = lane + 64 * k;
-    if (c < g.Lc) {
-      float a = b;
-      a = fmaf(w0, bin[c], a);
-      a = fmaf(w1, bin[c + 1], a);
-      a = fmaf(w2, bin[c + 2], a);
-      bout[c + 1] = a;
-    }
-  }
-}
-
-// the frame row of row r into buf (zero ends); returns the slot index p % hop
-__device__ __forceinline__ int lcup_load(const LcUpGeom& g,
-                                         const float* __restrict__ frames,
-                                         int F, const int32_t* __restrict__ off,
-                                         int T, long r, float* buf, int lane) {
-  const int b = (int)(r / T), t = (int)(r - (long)b * T);
-  const long p = (long)off[b] + t;
-  long f = p / g.hop;
-  if (f > F - 1) f = F - 1;          // (the host checks coverage; never read past)
-  const float* src = frames + ((long)b * F + f) * g.Lc;
-#pragma unroll
-  for (int k = 0; k < LCUP_CPL; ++k) {
-    const int c = lane + 64 * k;
-    if (c < g.Lc) buf[c + 1] = src[c];
-  }
-  if (lane == 0) {
-    buf[0] = 0.f;
-    buf[g.Lc + 1] = 0.f;
-  }
-  return (int)(p % g.hop);
-}
-
-// forward: one wave per row, four rows per workgroup, ping-pong rows in LDS
-__global__ __launch_bounds__(256) void lc_upsample_fwd_kernel(
-    LcUpGeom g, const float* __restrict__ frames, int F,
-    const int32_t* __restrict__ off, const float* __restrict__ up,
-    float* __restrict__ out, int ldo, int T, long N) {
-  __shared__ float lds[4][2][LCUP_MAX_LC + 2];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + wv;
-  const bool live = r < N;
-  float* b0 = lds[wv][0];
-  float* b1 = lds[wv][1];
-  if (lane == 0) b1[0] = b1[g.Lc + 1] = 0.f;
-  const int j = live ? lcup_load(g, frames, F, off, T, r, b0, lane) : 0;
-  __syncthreads();
-  for (int i = 0; i < g.m; ++i) {
-    if (live) lcup_layer(g, up, i, j, (i & 1) ? b1 : b0, (i & 1) ? b0 : b1, lane);
-    __syncthreads();
-  }
-  if (!live) return;
-  const float* res = (g.m & 1) ? b1 : b0;
-  float* dst = out + r * ldo;
-  for (int c = lane; c < ldo; c += 64) dst[c] = c < g.Lc ? res[c + 1] : 0.f;
-}
-
-__device__ __forceinline__ float lcup_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// backward: one wave per workgroup owning rows [w * rpw, (w + 1) * rpw).  Per
-// row: the layer chain again (every layer's input kept in LDS), then d row
-// back through the layers; the (layer, slot, tap) and bias partials add up in
-// LDS in row order and go to the workgroup's slab at the end.
-// CTX (the frame-context variant): the gradient at the layer-0 input, summed
-// in registers in row order over the run of rows that share a frame (a
-// segment).  A segment that starts at the workgroup's first row goes to
-// dpart[w][0], one that ends at its last row (and does not start at its
-// first) to dpart[w][1], every other one straight to dfr[b][f]: no two
-// workgroups write the same float.  lc_context_dfix_kernel adds the parts.
-template <bool CTX>
-__global__ __launch_bounds__(64) void lc_upsample_bwd_kernel(
-    LcUpGeom g, const float* __restrict__ frames, int F,
-    const int32_t* __restrict__ off, const float* __restrict__ up,
-    const float* __restrict__ drows, int ldd, int T, long N, long rpw,
-    float* __restrict__ slabs, long slab_stride, int nacc,
-    float* __restrict__ dfr, float* __restrict__ dpart) {
-  extern __shared__ float lds[];
-  const int lane = threadIdx.x;
-  const int W = g.Lc + 2;
-  float* U = lds;                              // [m + 1][W]
-  float* G0 = U + (g.m + 1) * W;               // [2][W]
-  float* acc = G0 + 2 * W;                     // [nacc]
-  for (int e = lane; e < nacc; e += 64) acc[e] = 0.f;
-  for (int e = lane; e < 2 * W; e += 64) G0[e] = 0.f;
-  for (int i = 1; i <= g.m; ++i)
-    if (lane == 0) U[i * W] = U[i * W + g.Lc + 1] = 0.f;
-  __syncthreads();
-  const long r0 = (long)blockIdx.x * rpw;
-  const long r1 = r0 + rpw < N ? r0 + rpw : N;
-  float dacc[LCUP_CPL];
-  long seg_key = -1, seg_r = r0;      // (b * F + frame) and first row
-  if constexpr (CTX) {
-#pragma unroll
-    for (int k = 0; k < LCUP_CPL; ++k) dacc[k] = 0.f;
-  }
-  for (long r = r0; r < r1; ++r) {
-    if constexpr (CTX) {
-      const int b = (int)(r / T);
-      const long key = (long)b * F + ((long)off[b] + (r - (long)b * T)) / g.hop;
-      if (key != seg_key) {
-        if (seg_key >= 0) {
-          // a segment that ended before r1: dpart[w][0] or interior
-          float* dst = seg_r == r0
-                           ? dpart + (long)blockIdx.x * 2 * g.Lc
-                           : dfr + seg_key * g.Lc;
-#pragma unroll
-          for (int k = 0; k < LCUP_CPL; ++k) {
-            const int c = lane + 64 * k;
-            if (c < g.Lc) dst[c] = dacc[k];
-            dacc[k] = 0.f;
-          }
-        }
-        seg_key = key;
-        seg_r = r;
-      }
-    }
-    const int j = lcup_load(g, frames, F, off, T, r, U, lane);
-    __syncthreads();
-    for (int i = 0; i < g.m; ++i) {
-      lcup_layer(g, up, i, j, U + i * W, U + (i + 1) * W, lane);
-      __syncthreads();
-    }
-    float* gc = G0;
-    float* gn = G0 + W;
-    const float* dr = drows + r * ldd;
-#pragma unroll
-    for (int k = 0; k < LCUP_CPL; ++k) {
-      const int c = lane + 64 * k;
-      if (c < g.Lc) gc[c + 1] = dr[c];
-    }
-    __syncthreads();
-    for (int i = g.m - 1; i >= 0; --i) {
-      const float* u = U + i * W;
-      float p0 = 0.f, p1 = 0.f, p2 = 0.f, pb = 0.f;
-#pragma unroll
-      for (int k = 0; k < LCUP_CPL; ++k) {
-        const int c = lane + 64 * k;
-        if (c < g.Lc) {
-          const float d = gc[c + 1];
-          p0 = fmaf(d, u[c], p0);
-          p1 = fmaf(d, u[c + 1], p1);
-          p2 = fmaf(d, u[c + 2], p2);
-          pb += d;
-        }
-      }
-      p0 = lcup_wave_sum(p0);
-      p1 = lcup_wave_sum(p1);
-      p2 = lcup_wave_sum(p2);
-      pb = lcup_wave_sum(pb);
-      const int slot = lcup_slot(g, i, j);
-      const int fw = g.fo[i] + 3 * slot;
-      if (lane == 0) {
-        acc[fw] += p0;
-        acc[fw + 1] += p1;
-        acc[fw + 2] += p2;
-        if (g.use_bias) acc[g.bo + i] += pb;
-      }
-      if (i > 0) {
-        // d u[c] = W0 d out[c + 1] + W1 d out[c] + W2 d out[c - 1]
-        const float* w = up + fw;
-        const float w0 = w[0], w1 = w[1], w2 = w[2];
-#pragma unroll
-        for (int k = 0; k < LCUP_CPL; ++k) {
-          const int c = lane + 64 * k;
-          if (c < g.Lc) {
-            float a = w0 * gc[c + 2];
-            a = fmaf(w1, gc[c + 1], a);
-            a = fmaf(w2, gc[c], a);
-            gn[c + 1] = a;
-          }
-        }
-        float* t = gc;
-        gc = gn;
-        gn = t;
-      } else if constexpr (CTX) {
-        // the layer-0 input's gradient, the same three taps
-        const float* w = up + fw;
-        const float w0 = w[0], w1 = w[1], w2 = w[2];
-#pragma unroll
-        for (int k = 0; k < LCUP_CPL; ++k) {
-          const int c = lane + 64 * k;
-          if (c < g.Lc) {
-            float a = w0 * gc[c + 2];
-            a = fmaf(w1, gc[c + 1], a);
-            a = fmaf(w2, gc[c], a);
-            dacc[k] += a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if constexpr (CTX) {
-    // the last segment: dpart[w][0] if it is also the first, else [w][1]
-    float* dst = dpart + ((long)blockIdx.x * 2 + (seg_r == r0 ? 0 : 1)) * g.Lc;
-#pragma unroll
-    for (int k = 0; k < LCUP_CPL; ++k) {
-      const int c = lane + 64 * k;
-      if (seg_key >= 0 && c < g.Lc) dst[c] = dacc[k];
-    }
-  }
-  __syncthreads();
-  float* dst = slabs + (long)blockIdx.x * slab_stride;
-  for (int e = lane; e < nacc; e += 64) dst[e] = acc[e];
-}
-
-// d frames [B][F][Lc] of the frame-context variant: frame f of clip b
-// gathers rows [max(0, f hop - o), min(T, (f + 1) hop - o)) of the clip
-// (o = off[b] < hop).  A frame inside one workgroup's rows that is neither its
-// first nor its last segment was written by that workgroup; the others add
-// the workgroups' parts in workgroup order; a frame without rows is zero.
-__global__ __launch_bounds__(256) void lc_context_dfix_kernel(
-    const int32_t* __restrict__ off, int hop, int Lc, int F, int T, long N,
-    long rpw, const float* __restrict__ dpart, float* __restrict__ dfr,
-    long total) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  const int c = (int)(e % Lc);
-  const long bf = e / Lc;
-  const int b = (int)(bf / F), f = (int)(bf - (long)b * F);
-  const long o = off[b];
-  long t0 = (long)f * hop - o, t1 = t0 + hop;
-  if (t0 < 0) t0 = 0;
-  if (t1 > T) t1 = T;
-  if (t0 >= t1) {
-    dfr[e] = 0.f;
-    return;
-  }
-  const long ra = (long)b * T + t0, rb = (long)b * T + t1;
-  const long wlo = ra / rpw, whi = (rb - 1) / rpw;
-  if (wlo == whi) {
-    const long s = wlo * rpw, x = s + rpw < N ? s + rpw : N;
-    if (ra == s)
-      dfr[e] = dpart[(wlo * 2) * Lc + c];
-    else if (rb == x)
-      dfr[e] = dpart[(wlo * 2 + 1) * Lc + c];
-    return;                           // (else: written by the workgroup)
-  }
-  float a = 0.f;
-  for (long w = wlo; w <= whi; ++w)
-    a += dpart[(w * 2 + (ra <= w * rpw ? 0 : 1)) * Lc + c];
-  dfr[e] = a;
-}
-
-// ---------------------------------------------------------------------------
-// Frame-context convolution in front of the upsampler: a convolution over
-// frames with kernel 2p + 1, Lc -> Lc channels, no bias,
-//   ctx[b][f][j] = sum_{k, c} W[k][c][j] x[b][f + k][c]
-// on x [B][Fx][Lc], the frames staged with p frames of context either side
-// (window frame f + k is clip frame f + k - p; zeros outside the clip) and W
-// [2p + 1][Lc][Lc].  The window of output frame f is the contiguous run
-// x[b][f] .. x[b][f + 2p], K = (2p + 1) Lc floats, summed in kc order: an
-// output's bits depend on its window and W only.
-// ---------------------------------------------------------------------------
-#define LCCTX_MAX_P 8
-
-// forward: one wave per output frame, lane = channel j (+ 64 k); the window
-// value is the same for the whole wave
-__global__ __launch_bounds__(256) void lc_context_fwd_kernel(
-    const float* __restrict__ x, int Fx, const float* __restrict__ w, int K,
-    int Lc, float* __restrict__ ctx, int Fw, long rows) {
-  const int lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int b = (int)(r / Fw), f = (int)(r - (long)b * Fw);
-  const float* xr = x + ((long)b * Fx + f) * Lc;
-  float a[LCUP_CPL];
-#pragma unroll
-  for (int k = 0; k < LCUP_CPL; ++k) a[k] = 0.f;
-  for (int kc = 0; kc < K; ++kc) {
-    const float v = xr[kc];
-    const float* wr = w + (long)kc * Lc;
-#pragma unroll
-    for (int k = 0; k < LCUP_CPL; ++k) {
-      const int c = lane + 64 * k;
-      if (c < Lc) a[k] = fmaf(wr[c], v, a[k]);
-    }
-  }
-  float* dst = ctx + r * Lc;
-#pragma unroll
-  for (int k = 0; k < LCUP_CPL; ++k) {
-    const int c = lane + 64 * k;
-    if (c < Lc) dst[c] = a[k];
-  }
-}
-
-// weight gradient dW[kc][j] = sum_r x[r's window][kc] dctx[r][j]: one wave per
-// (kc, slab); slab s sums rows [s rps, (s + 1) rps) of the B * Fw output
-// frames in order into slabs[s][kc][j] (wn_reduce_slabs adds the slabs)
-__global__ __launch_bounds__(256) void lc_context_wgrad_kernel(
-    const float* __restrict__ x, int Fx, const float* __restrict__ d, int Fw,
-    int K, int Lc, long rows, long rps, float* __restrict__ slabs,
-    long slab_stride) {
-  const int lane = threadIdx.x & 63;
-  const long kc = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (kc >= K) return;
-  const long r0 = (long)blockIdx.y * rps;
-  const long r1 = r0 + rps < rows ? r0 + rps : rows;
-  float a[LCUP_CPL];
-#pragma unroll
-  for (int k = 0; k < LCUP_CPL; ++k) a[k] = 0.f;
-  for (long r = r0; r < r1; ++r) {
-    const int b = (int)(r / Fw), f = (int)(r - (long)b * Fw);
-    const float v = x[((long)b * Fx + f) * Lc + kc];
-    const float* dr = d + r * Lc;
-#pragma unroll
-    for (int k = 0; k < LCUP_CPL; ++k) {
-      const int c = lane + 64 * k;
-      if (c < Lc) a[k] = fmaf(v, dr[c], a[k]);
-    }
-  }
-  float* dst = slabs + (long)blockIdx.y * slab_stride + kc * Lc;
-#pragma unroll
-  for (int k = 0; k < LCUP_CPL; ++k) {
-    const int c = lane + 64 * k;
-    if (c < Lc) dst[c] = a[k];
-  }
-}
-
-static int lcup_geom(const int* scales, int m, int Lc, int use_bias,
-                     LcUpGeom* g, int* nacc) {
-  if (!scales) return WN_ERR_NULL;
-  if (m < 1 || m > LCUP_MAX_LAYERS || Lc < 1 || Lc > LCUP_MAX_LC)
-    return WN_ERR_BAD_SHAPE;
-  long hop = 1;
-  for (int i = 0; i < m; ++i) {
-    if (scales[i] < 2) return WN_ERR_BAD_SHAPE;
-    hop *= scales[i];
-    if (hop > 4096) return WN_ERR_BAD_SHAPE;
-  }
-  g->m = m;
-  g->hop = (int)hop;
-  g->Lc = Lc;
-  g->use_bias = use_bias ? 1 : 0;
-  int fo = 0, suf = 1;
-  for (int i = m - 1; i >= 0; --i) {
-    g->suf[i] = suf;
-    suf *= scales[i];
-  }
-  for (int i = 0; i < LCUP_MAX_LAYERS; ++i) {
-    g->s[i] = i < m ? scales[i] : 1;
-    if (i >= m) g->suf[i] = 1;
-    g->fo[i] = fo;
-    if (i < m) fo += 3 * scales[i];
-  }
-  g->bo = fo;
-  *nacc = fo + (use_bias ? m : 0);
-  return WN_OK;
-}
-
-extern "C" {
-
-int wn_lc_upsample_floats(const int* scales, int m, int use_bias) {
-  LcUpGeom g;
-  int n = 0;
-  if (lcup_geom(scales, m, 1, use_bias, &g, &n) != WN_OK) return 0;
-  return n;
-}
-
-int wn_lc_upsample_fwd(const float* frames, int F, const int32_t* off,
-                       const float* up, const int* scales, int m, int Lc,
-                       int use_bias, float* rows, int ld_rows, int B, int T,
-                       void* stream) {
-  if (!frames || !off || !up || !rows) return WN_ERR_NULL;
-  LcUpGeom g;
-  int nacc = 0;
-  const int rc = lcup_geom(scales, m, Lc, use_bias, &g, &nacc);
-  if (rc != WN_OK) return rc;
-  if (F < 1 || B < 1 || T < 1 || ld_rows < Lc) return WN_ERR_BAD_SHAPE;
-  const long N = (long)B * T;
-  hipLaunchKernelGGL(lc_upsample_fwd_kernel, dim3((unsigned)((N + 3) / 4)),
-                     dim3(256), 0, (hipStream_t)stream, g, frames, F, off, up,
-                     rows, ld_rows, T, N);
-  return wn_check_launch();
-}
-
-int wn_lc_upsample_bwd_slabs(long rows, int nacc) {
-  if (rows <= 0 || nacc <= 0) return 0;
-  long n = (rows + 31) / 32;                   // >= 32 rows per workgroup
-  long cap = (16L << 20) / nacc;               // <= 64 MB of slabs
-  if (cap < 64) cap = 64;
-  if (n > 4096) n = 4096;
-  if (n > cap) n = cap;
-  return (int)(n < 1 ? 1 : n);
-}
-
-int wn_lc_upsample_bwd(const float* frames, int F, const int32_t* off,
-                       const float* up, const int* scales, int m, int Lc,
-                       int use_bias, const float* drows, int ld_drows, int B,
-                       int T, float* slabs, int num_slabs, long slab_stride,
-                       void* stream) {
-  if (!frames || !off || !up || !drows || !slabs) return WN_ERR_NULL;
-  LcUpGeom g;
-  int nacc = 0;
-  const int rc = lcup_geom(scales, m, Lc, use_bias, &g, &nacc);
-  if (rc != WN_OK) return rc;
-  if (F < 1 || B < 1 || T < 1 || ld_drows < Lc || num_slabs < 1 ||
-      slab_stride < nacc)
-    return WN_ERR_BAD_SHAPE;
-  const long N = (long)B * T;
-  const long rpw = (N + num_slabs - 1) / num_slabs;
-  const size_t lds = sizeof(float) * ((size_t)(m + 3) * (Lc + 2) + nacc);
-  if (lds > 64 * 1024) return WN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(lc_upsample_bwd_kernel<false>, dim3((unsigned)num_slabs),
-                     dim3(64), lds, (hipStream_t)stream, g, frames, F, off, up,
-                     drows, ld_drows, T, N, rpw, slabs, slab_stride, nacc,
-                     nullptr, nullptr);
-  return wn_check_launch();
-}
-
-int wn_lc_upsample_bwd_ctx(const float* frames, int F, const int32_t* off,
-                           const float* up, const int* scales, int m, int Lc,
-                           int use_bias, const float* drows, int ld_drows,
-                           int B, int T, float* slabs, int num_slabs,
-                           long slab_stride, float* dframes, float* dpart,
-                           void* stream) {
-  if (!frames || !off || !up || !drows || !slabs || !dframes || !dpart)
-    return WN_ERR_NULL;
-  LcUpGeom g;
-  int nacc = 0;
-  const int rc = lcup_geom(scales, m, Lc, use_bias, &g, &nacc);
-  if (rc != WN_OK) return rc;
-  if (F < 1 || B < 1 || T < 1 || ld_drows < Lc || num_slabs < 1 ||
-      slab_stride < nacc)
-    return WN_ERR_BAD_SHAPE;
-  // every row's frame inside the F frames (offsets < hop on the device)
-  if ((long)(T + g.hop - 2) / g.hop + 1 > F) return WN_ERR_BAD_SHAPE;
-  const long N = (long)B * T;
-  const long rpw = (N + num_slabs - 1) / num_slabs;
-  const size_t lds = sizeof(float) * ((size_t)(m + 3) * (Lc + 2) + nacc);
-  if (lds > 64 * 1024) return WN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(lc_upsample_bwd_kernel<true>, dim3((unsigned)num_slabs),
-                     dim3(64), lds, (hipStream_t)stream, g, frames, F, off, up,
-                     drows, ld_drows, T, N, rpw, slabs, slab_stride, nacc,
-                     dframes, dpart);
-  const long total = (long)B * F * Lc;
-  hipLaunchKernelGGL(lc_context_dfix_kernel, dim3((unsigned)((total + 255) / 256)),
-                     dim3(256), 0, (hipStream_t)stream, off, g.hop, Lc, F, T, N,
-                     rpw, dpart, dframes, total);
-  return wn_check_launch();
-}
-
-int wn_lc_context_fwd(const float* x, int Fx, const float* w, int p, int Lc,
-                      float* ctx, int Fw, int B, void* stream) {
-  if (!x || !w || !ctx) return WN_ERR_NULL;
-  if (p < 0 || p > LCCTX_MAX_P || Lc < 1 || Lc > LCUP_MAX_LC || Fw < 1 ||
-      B < 1 || Fx < Fw + 2 * p)
-    return WN_ERR_BAD_SHAPE;
-  const long rows = (long)B * Fw;
-  hipLaunchKernelGGL(lc_context_fwd_kernel, dim3((unsigned)((rows + 3) / 4)),
-                     dim3(256), 0, (hipStream_t)stream, x, Fx, w,
-                     (2 * p + 1) * Lc, Lc, ctx, Fw, rows);
-  return wn_check_launch();
-}
-
-int wn_lc_context_wgrad_slabs(long rows, int nacc) {
-  if (rows <= 0 || nacc <= 0) return 0;
-  long n = (rows + 31) / 32;                   // >= 32 frames per slab
-  long cap = (16L << 20) / nacc;               // <= 64 MB of slabs
-  if (cap < 1) cap = 1;
-  if (n > 256) n = 256;
-  if (n > cap) n = cap;
-  return (int)(n < 1 ? 1 : n);
-}
-
-int wn_lc_context_wgrad(const float* x, int Fx, const float* dctx, int Fw,
-                        int p, int Lc, int B, float* slabs, int num_slabs,
-                        long slab_stride, void* stream) {
-  if (!x || !dctx || !slabs) return WN_ERR_NULL;
-  if (p < 0 || p > LCCTX_MAX_P || Lc < 1 || Lc > LCUP_MAX_LC || Fw < 1 ||
-      B < 1 || Fx < Fw + 2 * p || num_slabs < 1 || num_slabs > 65535)
-    return WN_ERR_BAD_SHAPE;
-  const int K = (2 * p + 1) * Lc;
-  if (slab_stride < (long)K * Lc) return WN_ERR_BAD_SHAPE;
-  const long rows = (long)B * Fw;
-  const long rps = (rows + num_slabs - 1) / num_slabs;
-  hipLaunchKernelGGL(lc_context_wgrad_kernel,
-                     dim3((unsigned)((K + 3) / 4), (unsigned)num_slabs),
-                     dim3(256), 0, (hipStream_t)stream, x, Fx, dctx, Fw, K, Lc,
-                     rows, rps, slabs, slab_stride);
   return wn_check_launch();
 }
 

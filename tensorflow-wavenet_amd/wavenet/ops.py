@@ -177,13 +177,24 @@ class _Optimizer(object):
     def _make_slots(self, model):
         raise NotImplementedError
 
-    def _apply(self, model, grad_scale):
+    _entry = None    # stem of the entry points: wn_<stem>, wn_<stem>_clip
+
+    def _rule_args(self):
+        """The entry point's arguments between n and grad_scale."""
         raise NotImplementedError
 
-    def _apply_clip(self, model, grad_scale, tail):
-        """The `_clip` entry point; `tail` = (partials, nparts, clip_norm,
-        ema, ema_decay, norm_out, stream)."""
-        raise NotImplementedError
+    def _apply(self, model, grad_scale, clip_tail=None):
+        """One update: wn_<stem>, or wn_<stem>_clip with `clip_tail` =
+        (partials, nparts, clip_norm, ema, ema_decay, norm_out) in front of
+        the stream."""
+        name = 'wn_' + self._entry
+        tail = (_lib.stream(),)
+        if clip_tail is not None:
+            name, tail = name + '_clip', tuple(clip_tail) + tail
+        _lib.call(name, _lib.ptr(model.params), _lib.ptr(model.grads),
+                  *[_lib.ptr(s) for s in self._slots],
+                  model.params.numel(), *self._rule_args(),
+                  grad_scale, 0.0, None, *tail)
 
     def init_state(self, model):
         """Create the slots (and, with ema_decay, the shadow as a copy of the
@@ -218,10 +229,10 @@ class _Optimizer(object):
             parts, nparts = self._gn_parts, self._gn_parts.numel()
             _lib.call('wn_grad_norm_partials', _lib.ptr(model.grads),
                       model.grads.numel(), _lib.ptr(parts), _lib.stream())
-        self._apply_clip(model, scale, (
+        self._apply(model, scale, (
             _lib.ptr(parts), nparts, self.clip_norm or 0.0,
             _lib.ptr(self._shadow), self.ema_decay or 0.0,
-            _lib.ptr(self.last_grad_norm), _lib.stream()))
+            _lib.ptr(self.last_grad_norm)))
         return loss
 
     # ---- checkpointing ---------------------------------------------------
@@ -284,6 +295,8 @@ class _Optimizer(object):
 
 class AdamOptimizer(_Optimizer):
     # tf.train.AdamOptimizer(learning_rate, epsilon=1e-4); `momentum` ignored
+    _entry = 'adam'
+
     def __init__(self, learning_rate, epsilon=1e-4, beta1=0.9, beta2=0.999,
                  *, clip_norm=None, ema_decay=None):
         super(AdamOptimizer, self).__init__(clip_norm, ema_decay)
@@ -293,26 +306,15 @@ class AdamOptimizer(_Optimizer):
         self._slots = [torch.zeros_like(model.params),
                        torch.zeros_like(model.params)]
 
-    def _apply(self, model, grad_scale):
+    def _rule_args(self):
         t = self._step
         lr_t = self.lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
-        m, v = self._slots
-        _lib.call('wn_adam', _lib.ptr(model.params), _lib.ptr(model.grads),
-                  _lib.ptr(m), _lib.ptr(v), model.params.numel(), lr_t,
-                  self.b1, self.b2, self.eps, grad_scale, 0.0, None,
-                  _lib.stream())
-
-    def _apply_clip(self, model, grad_scale, tail):
-        t = self._step
-        lr_t = self.lr * math.sqrt(1.0 - self.b2 ** t) / (1.0 - self.b1 ** t)
-        m, v = self._slots
-        _lib.call('wn_adam_clip', _lib.ptr(model.params),
-                  _lib.ptr(model.grads), _lib.ptr(m), _lib.ptr(v),
-                  model.params.numel(), lr_t, self.b1, self.b2, self.eps,
-                  grad_scale, 0.0, None, *tail)
+        return lr_t, self.b1, self.b2, self.eps
 
 
 class MomentumOptimizer(_Optimizer):
+    _entry = 'momentum'
+
     def __init__(self, learning_rate, momentum, *, clip_norm=None,
                  ema_decay=None):
         super(MomentumOptimizer, self).__init__(clip_norm, ema_decay)
@@ -321,21 +323,15 @@ class MomentumOptimizer(_Optimizer):
     def _make_slots(self, model):
         self._slots = [torch.zeros_like(model.params)]
 
-    def _apply(self, model, grad_scale):
-        _lib.call('wn_momentum', _lib.ptr(model.params), _lib.ptr(model.grads),
-                  _lib.ptr(self._slots[0]), model.params.numel(), self.lr,
-                  self.mom, grad_scale, 0.0, None, _lib.stream())
-
-    def _apply_clip(self, model, grad_scale, tail):
-        _lib.call('wn_momentum_clip', _lib.ptr(model.params),
-                  _lib.ptr(model.grads), _lib.ptr(self._slots[0]),
-                  model.params.numel(), self.lr, self.mom, grad_scale, 0.0,
-                  None, *tail)
+    def _rule_args(self):
+        return self.lr, self.mom
 
 
 class RMSPropOptimizer(_Optimizer):
     # tf.train.RMSPropOptimizer(lr, decay=0.9, momentum, epsilon=1e-5);
     # the `rms` slot starts at ONE (TensorFlow), `momentum` slot at zero.
+    _entry = 'rmsprop'
+
     def __init__(self, learning_rate, momentum, epsilon=1e-5, decay=0.9, *,
                  clip_norm=None, ema_decay=None):
         super(RMSPropOptimizer, self).__init__(clip_norm, ema_decay)
@@ -346,18 +342,8 @@ class RMSPropOptimizer(_Optimizer):
         self._slots = [torch.ones_like(model.params),
                        torch.zeros_like(model.params)]
 
-    def _apply(self, model, grad_scale):
-        _lib.call('wn_rmsprop', _lib.ptr(model.params), _lib.ptr(model.grads),
-                  _lib.ptr(self._slots[0]), _lib.ptr(self._slots[1]),
-                  model.params.numel(), self.lr, self.decay, self.mom,
-                  self.eps, grad_scale, 0.0, None, _lib.stream())
-
-    def _apply_clip(self, model, grad_scale, tail):
-        _lib.call('wn_rmsprop_clip', _lib.ptr(model.params),
-                  _lib.ptr(model.grads), _lib.ptr(self._slots[0]),
-                  _lib.ptr(self._slots[1]), model.params.numel(), self.lr,
-                  self.decay, self.mom, self.eps, grad_scale, 0.0, None,
-                  *tail)
+    def _rule_args(self):
+        return self.lr, self.decay, self.mom, self.eps
 
 
 def create_adam_optimizer(learning_rate, momentum, *, clip_norm=None,

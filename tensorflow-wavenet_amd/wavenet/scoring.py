@@ -1,5 +1,5 @@
 """Scoring of held-out data, host side: the forward pass predict_proba makes,
-then wn_xent_score on its logits (csrc/wn_misc.hip).  Functions take the model
+then wn_xent_score on its logits (csrc/wn_loss.hip).  Functions take the model
 first; WaveNetModel.score / score_from_codes call in here."""
 import collections
 

@@ -4,7 +4,7 @@ on top of oracle.TFOptimizer:
 
     norm   = grad_scale * sqrt(sum g_i^2)          the norm before clipping
     factor = clip_norm / max(norm, clip_norm)      (NaN when norm is not finite)
-    w'     = TFOptimizer.apply(w, g * grad_scale * factor)
+    w'     = TFOptimizer.apply(w, g * grad_scale * factor + l2 * w * l2_mask)
     s'     = s - (1 - decay) * (s - w')            s_0 = w_0 (the weights before
                                                    the first update)
 
@@ -40,14 +40,18 @@ class ClipEMAOptimizer(object):
         self.shadow = None
         self.last_norm = None
 
-    def apply(self, w, g, grad_scale=1.0):
+    def apply(self, w, g, grad_scale=1.0, l2=0.0, l2_mask=None):
         w = np.asarray(w, np.float64)
         g = np.asarray(g, np.float64)
         if self.ema_decay is not None and self.shadow is None:
             self.shadow = w.copy()
         self.last_norm = global_norm(g, grad_scale)
         f = clip_factor(self.last_norm, self.clip_norm)
-        w2 = self.opt.apply(w, g * (grad_scale * f))
+        g = g * (grad_scale * f)
+        if l2 != 0.0:
+            g = g + float(l2) * w * (1.0 if l2_mask is None else
+                                     np.asarray(l2_mask, np.float64))
+        w2 = self.opt.apply(w, g)
         if self.ema_decay is not None:
             self.shadow = self.shadow - (1.0 - self.ema_decay) * (
                 self.shadow - w2)

@@ -418,3 +418,102 @@ def test_resumed_step_is_bitwise_the_uninterrupted_one(hip_lib, tmp_path,
         assert train.load(net_d, str(tmp_path)) == 2
         steps(net_d, opt_d, 3, 4)
         assert not torch.equal(net_d.params, net_a.params)
+
+
+# ---- the entry points themselves: the L2 arm and the EMA epilogue ----------
+def _abi_step(kind, lr, mom, step, clip, p, g, slots, l2=0.0, mask=None,
+              ema=None, decay=0.0):
+    """One update through wn_X (clip False) or wn_X_clip with partials = None
+    (the clip inactive), on device tensors, in place."""
+    import math
+    from wavenet import _lib
+    stem, rule = {
+        'adam': ('adam', (lr * math.sqrt(1.0 - 0.999 ** step) /
+                          (1.0 - 0.9 ** step), 0.9, 0.999, 1e-4)),
+        'sgd': ('momentum', (lr, mom)),
+        'rmsprop': ('rmsprop', (lr, 0.9, mom, 1e-5))}[kind]
+    tail = (None, 0, 0.0, _lib.ptr(ema), decay, None) if clip else ()
+    _lib.call('wn_' + stem + ('_clip' if clip else ''), _lib.ptr(p),
+              _lib.ptr(g), *[_lib.ptr(s) for s in slots], p.numel(), *rule,
+              1.0, l2, _lib.ptr(mask), *(tail + (_lib.stream(),)))
+
+
+def _abi_inputs(kind, n, seed):
+    rng = np.random.default_rng(seed)
+    w = rng.uniform(-1, 1, n).astype(np.float32)
+    gs = [(0.1 * rng.uniform(-1, 1, n)).astype(np.float32) for _ in range(2)]
+    mask = (rng.random(n) < 0.5).astype(np.float32)
+    slots = [np.ones(n, np.float32), np.zeros(n, np.float32)] \
+        if kind == 'rmsprop' else \
+        [np.zeros(n, np.float32) for _ in range(2 if kind == 'adam' else 1)]
+    return w, gs, mask, slots
+
+
+def _dev(a):
+    return torch.as_tensor(a).to('cuda').clone()
+
+
+# 1031: no multiple of 4 or 256 (the loop's ragged end); the other is past
+# the 2048-workgroup cap of the launch (a second trip of the grid-stride loop)
+L2_NS = [1031, 2048 * 256 + 1031]
+
+
+@pytest.mark.parametrize('n', L2_NS)
+@pytest.mark.parametrize('kind,lr,mom', KINDS)
+def test_l2_arm_of_both_entry_points(hip_lib, kind, lr, mom, n):
+    """l2 = 0.01 with a mask of zeros and ones, two steps: wn_X and wn_X_clip
+    (partials = None, ema = None) leave the same bits in parameters and slots,
+    and both are within PARAM_TOL of the float64 rule (tests/clip_ref.py with
+    its l2 * w * mask term)."""
+    w, gs, mask, slots = _abi_inputs(kind, n, n + len(kind))
+    runs = []
+    for clip in (False, True):
+        p, sl, mk = _dev(w), [_dev(s) for s in slots], _dev(mask)
+        for step, g in enumerate(gs, 1):
+            _abi_step(kind, lr, mom, step, clip, p, _dev(g), sl, 0.01, mk)
+        torch.cuda.synchronize()
+        runs.append([p] + sl)
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+    ref = clip_ref.ClipEMAOptimizer(kind, lr, mom)
+    w64 = w.astype(np.float64)
+    for g in gs:
+        w64 = ref.apply(w64, g, l2=0.01, l2_mask=mask)
+    assert mask.min() == 0.0 and mask.max() == 1.0
+    errs = [float(np.abs(a.cpu().numpy() - b).max())
+            for a, b in zip(runs[0], [w64] + ref.opt.slots)]
+    print('l2 arm %s n %d: parameter and slot errors %s (bar %.0e)'
+          % (kind, n, ['%.3e' % e for e in errs], PARAM_TOL))
+    assert max(errs) < PARAM_TOL
+    # the term acts, and only where the mask is one
+    q, sq = _dev(w), [_dev(s) for s in slots]
+    _abi_step(kind, lr, mom, 1, False, q, _dev(gs[0]), sq)
+    _abi_step(kind, lr, mom, 2, False, q, _dev(gs[1]), sq)
+    same = (q == runs[0][0]).cpu().numpy()
+    assert same[mask == 0].all() and not same[mask == 1].all()
+
+
+@pytest.mark.parametrize('kind,lr,mom', KINDS)
+def test_ema_epilogue_with_the_clip_inactive(hip_lib, kind, lr, mom):
+    """wn_X_clip with partials = None and a shadow, n = 1031: the parameters
+    are the plain entry point's, the shadow is  s - (1 - decay) (s - p_new)
+    evaluated in float32 from the returned p_new, bit for bit."""
+    n, decay = 1031, 0.9
+    w, gs, _, slots = _abi_inputs(kind, n, 77)
+    s0 = np.random.default_rng(78).uniform(-1, 1, n).astype(np.float32)
+    p0, sl0 = _dev(w), [_dev(s) for s in slots]
+    _abi_step(kind, lr, mom, 1, False, p0, _dev(gs[0]), sl0)
+    p1, sl1, ema = _dev(w), [_dev(s) for s in slots], _dev(s0)
+    _abi_step(kind, lr, mom, 1, True, p1, _dev(gs[0]), sl1, ema=ema,
+              decay=decay)
+    torch.cuda.synchronize()
+    assert torch.equal(p0, p1)
+    for a, b in zip(sl0, sl1):
+        assert torch.equal(a, b)
+    pn = p1.cpu().numpy()
+    keep = np.float32(1.0) - np.float32(decay)
+    want = s0 - keep * (s0 - pn)
+    assert want.dtype == np.float32
+    assert np.array_equal(ema.cpu().numpy().view(np.int32),
+                          want.view(np.int32))
+    assert not np.array_equal(want, s0)

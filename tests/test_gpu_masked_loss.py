@@ -1,5 +1,5 @@
 """The masked loss on the GPU (`lengths` on WaveNetModel.loss /
-loss_from_codes, csrc/wn_misc.hip's xent_masked_kernel): parity with the
+loss_from_codes, csrc/wn_loss.hip's xent_masked_kernel): parity with the
 float64 masked reference (tests/masked_ref.py) on every kind of model, full
 lengths bitwise the unmasked loss, the padding's content irrelevant, the last
 real row's target not the padding, launch-plan replay with new lengths,

@@ -1,4 +1,4 @@
-"""Held-out scoring on the GPU (WaveNetModel.score, csrc/wn_misc.hip's
+"""Held-out scoring on the GPU (WaveNetModel.score, csrc/wn_loss.hip's
 wn_xent_score, wavenet/evaluate.py): the kernel alone against float64 on the
 same float32 logits, model parity with the float64 network on every kind of
 model, consistency with the loss, the padding's content irrelevant, ragged
@@ -120,6 +120,43 @@ def test_kernel_against_float64_on_the_same_logits(hip_lib, B, T, Q, ld):
         # the same bits again, and without row_nll
         assert _same(got, _kernel(x, codes, lengths, Q))
         assert _same(got[1:], _kernel(x, codes, lengths, Q, False)[1:])
+
+
+ROW_SHAPES = [(64, 64), (256, 256), (256, 260), (512, 516)]
+
+
+@pytest.mark.parametrize('Q, ld', ROW_SHAPES,
+                         ids=['q%d_ld%d' % s for s in ROW_SHAPES])
+def test_scored_row_is_the_loss_kernels_row_bit_for_bit(hip_lib, Q, ld):
+    """One clip of two samples: row 0 has a target, row 1 has none, so the
+    loss kernel's partial 0 is (lse - ll) + 0 + 0 + 0, row 0's value exactly.
+    Its bits equal row_nll[0] of wn_xent_score on the same buffers, through
+    wn_xent and through wn_xent_masked (lengths = [2], 1 / denominator 0.5),
+    in the Q == 256 arm and the generic one, with a padded leading dimension."""
+    from wavenet import _lib
+    rng = np.random.default_rng(Q + ld)
+    x = rng.uniform(-15.9, 15.9, (1, 2, ld)).astype(np.float32)
+    codes = np.array([[5, int(rng.integers(0, Q))]], np.int32)
+    dev = torch.device('cuda')
+    xd = torch.as_tensor(x).to(dev)
+    qd = torch.as_tensor(codes).to(dev)
+    assert _lib.load().wn_xent_partials(2) == 1
+    part = torch.full((1,), -7.0, dtype=torch.float32, device=dev)
+    _lib.call('wn_xent', _lib.ptr(xd), ld, _lib.ptr(qd), None, _lib.ptr(part),
+              1, 2, Q, 0, _lib.stream())
+    ln = torch.tensor([2], dtype=torch.int32, device=dev)
+    inv_den = torch.tensor([0.5], dtype=torch.float32, device=dev)
+    mpart = torch.full((1,), -7.0, dtype=torch.float32, device=dev)
+    _lib.call('wn_xent_masked', _lib.ptr(xd), ld, _lib.ptr(qd), _lib.ptr(ln),
+              _lib.ptr(inv_den), None, _lib.ptr(mpart), 1, 2, Q, 0,
+              _lib.stream())
+    torch.cuda.synchronize()
+    for lengths, loss in ((None, part), ([2], mpart)):
+        rows = _kernel(x, codes, lengths, Q)[0]
+        print('Q %d ld %d lengths %s: loss partial %r scored row %r'
+              % (Q, ld, lengths, float(loss[0]), float(rows[0, 0])))
+        assert float(rows[0, 0]) > 0 and float(rows[0, 1]) == 0.0
+        assert torch.equal(_bits(loss), _bits(rows[0, :1]))
 
 
 # ---- 2. model parity with float64 ----------------------------------------------------

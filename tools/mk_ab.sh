@@ -1,20 +1,38 @@
 #!/bin/bash
 # build two variants of the library for tools/ab_lib.sh:
-#   tools/mk_ab.sh <file.hip>   -> build/ab/lib_base.so (the file as of git HEAD)
-#                                  build/ab/lib_new.so  (the working tree)
+#   tools/mk_ab.sh [-r REV] <file.hip>...
+#     -> build/ab/lib_base.so (the named files as of REV, default HEAD)
+#        build/ab/lib_new.so  (the named files of the working tree)
+# A file that one side lacks is left out of that side, so a split or a merge
+# of sources is compared by naming every file involved:
+#   tools/mk_ab.sh -r HEAD~1 wn_misc.hip wn_loss.hip wn_optim.hip wn_lc.hip
+# Every other object comes from build/ (run the build first).
 set -e
 PK=tensorflow-wavenet_amd
-F=${1:-wn_stack.hip}
-N=${F%.hip}
-mkdir -p $PK/build/ab /tmp/ab_src
+REV=HEAD
+if [ "$1" = "-r" ]; then REV=$2; shift 2; fi
+[ $# -gt 0 ] || set -- wn_stack.hip
+S=$(mktemp -d)
+trap 'rm -rf $S' EXIT
+mkdir -p $PK/build/ab $S/base
 rm -f $PK/build/ab/lib_*.so
-mkdir -p /tmp/ab_src/base
-git show HEAD:$PK/csrc/$F > /tmp/ab_src/base/$F
-git show HEAD:$PK/csrc/wn_common.h > /tmp/ab_src/base/wn_common.h
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC"
-/opt/rocm/bin/hipcc $FL -c /tmp/ab_src/base/$F -o /tmp/ab_src/base.o
-/opt/rocm/bin/hipcc $FL -c $PK/csrc/$F -o /tmp/ab_src/new.o
-OTHERS=$(ls $PK/build/*.o | grep -v "/$N.o")
-/opt/rocm/bin/hipcc $FL -shared -o $PK/build/ab/lib_base.so /tmp/ab_src/base.o $OTHERS
-/opt/rocm/bin/hipcc $FL -shared -o $PK/build/ab/lib_new.so /tmp/ab_src/new.o $OTHERS
+git show $REV:$PK/csrc/wn_common.h > $S/base/wn_common.h
+OTHERS=$(ls $PK/build/*.o)
+BASE= NEW=
+for F in "$@"; do
+  N=${F%.hip}
+  OTHERS=$(echo "$OTHERS" | grep -v "/$N.o" || true)
+  if git cat-file -e $REV:$PK/csrc/$F 2>/dev/null; then
+    git show $REV:$PK/csrc/$F > $S/base/$F
+    /opt/rocm/bin/hipcc $FL -c $S/base/$F -o $S/base_$N.o
+    BASE="$BASE $S/base_$N.o"
+  fi
+  if [ -f $PK/csrc/$F ]; then
+    /opt/rocm/bin/hipcc $FL -c $PK/csrc/$F -o $S/new_$N.o
+    NEW="$NEW $S/new_$N.o"
+  fi
+done
+/opt/rocm/bin/hipcc $FL -shared -o $PK/build/ab/lib_base.so $BASE $OTHERS
+/opt/rocm/bin/hipcc $FL -shared -o $PK/build/ab/lib_new.so $NEW $OTHERS
 ls -la $PK/build/ab/

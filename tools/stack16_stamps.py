@@ -8,7 +8,8 @@ if 'WN_LIB_PATH' not in os.environ:
     out = os.path.join(PKG, 'build', 'ab', 'lib_stack_stamps.so')
     os.makedirs(os.path.dirname(out), exist_ok=True)
     srcs = [os.path.join(PKG, 'csrc', f) for f in
-            ('wn_layer.hip', 'wn_stack.hip', 'wn_gemm.hip', 'wn_misc.hip', 'wn_fastgen.hip')]
+            ('wn_layer.hip', 'wn_stack.hip', 'wn_gemm.hip', 'wn_misc.hip', 'wn_loss.hip',
+             'wn_optim.hip', 'wn_lc.hip', 'wn_fastgen.hip')]
     subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
                            '-DSTACK_STAMPS', '-shared', '-o', out] + os.environ.get('KB_DEFS', '').split() + srcs)
     os.environ['WN_LIB_PATH'] = out
