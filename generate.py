@@ -39,7 +39,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import local_condition, tf_checkpoint  # noqa: E402
+from wavenet import local_condition, sampling, tf_checkpoint  # noqa: E402
 
 SAMPLES = 16000
 TEMPERATURE = 1.0
@@ -62,6 +62,26 @@ def _ensure_positive_float(f):
     return float(f)
 
 
+def _top_k(v):
+    try:
+        k = int(v)
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise argparse.ArgumentTypeError('Argument must be an integer >= 1')
+    return k
+
+
+def _top_p(v):
+    try:
+        f = float(v)
+    except ValueError:
+        f = float('nan')
+    if not (np.isfinite(f) and 0.0 < f <= 1.0):
+        raise argparse.ArgumentTypeError('Argument must be in (0, 1]')
+    return f
+
+
 def get_arguments(argv=None):
     p = argparse.ArgumentParser(description='WaveNet generation script')
     p.add_argument('checkpoint', type=str,
@@ -69,6 +89,12 @@ def get_arguments(argv=None):
     p.add_argument('--samples', type=int, default=SAMPLES)
     p.add_argument('--temperature', type=_ensure_positive_float,
                    default=TEMPERATURE)
+    p.add_argument('--top_k', type=_top_k, default=None,
+                   help='draw from the K most probable codes only (ties at '
+                   'the cut are kept)')
+    p.add_argument('--top_p', type=_top_p, default=None,
+                   help='draw from the nucleus only: the most probable codes '
+                   'that hold this share of the tempered distribution')
     p.add_argument('--logdir', type=str, default=LOGDIR)
     p.add_argument('--window', type=int, default=WINDOW,
                    help='Past samples taken into account per step (naive '
@@ -334,7 +360,8 @@ def main(argv=None):
         codes = net.generate(n1, seed_samples=waveform,
                              temperature=args.temperature,
                              global_condition=gc, seed=args.seed,
-                             local_condition=rows(0, len(waveform) + n1 - 1))
+                             local_condition=rows(0, len(waveform) + n1 - 1),
+                             top_k=args.top_k, top_p=args.top_p)
         waveform = codes.cpu().numpy().tolist()
         done += min(chunk, args.samples)
         if args.save_every and done < args.samples:
@@ -343,7 +370,8 @@ def main(argv=None):
             n = min(chunk, args.samples - done)
             more = net.continue_generation(
                 n, waveform[-1], args.temperature, gc, args.seed,
-                local_condition=rows(len(waveform) - 1, n))
+                local_condition=rows(len(waveform) - 1, n),
+                top_k=args.top_k, top_p=args.top_p)
             waveform.extend(more.cpu().numpy().tolist())
             done += n
             print('Sample {:3<d}/{:3<d}'.format(done, args.samples), end='\r')
@@ -373,6 +401,11 @@ def main(argv=None):
                     prediction, scaled, atol=1e-5,
                     err_msg='Prediction scaling at temperature=1.0 is not '
                             'working as intended.')
+            if args.top_k is not None or args.top_p is not None:
+                # the draw's truncation (wavenet/sampling.py)
+                scaled = np.where(sampling.kept_mask(
+                    prediction.astype(np.float32), args.temperature,
+                    args.top_k, args.top_p), scaled, 0.0)
             waveform.append(int(rng.choice(np.arange(Q), p=scaled / scaled.sum())))
             if (step + 1) % 100 == 0:
                 print('Sample {:3<d}/{:3<d}'.format(step + 1, args.samples),
@@ -418,7 +451,8 @@ def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None):
     codes = net.generate_batch(done, seeds, seed_samples=waveform,
                                temperature=args.temperature,
                                global_condition=gc,
-                               local_condition=rows(0, len(waveform) + done - 1)
+                               local_condition=rows(0, len(waveform) + done - 1),
+                               top_k=args.top_k, top_p=args.top_p
                                ).cpu().numpy()
     parts = [codes]
     while done < args.samples:
@@ -427,7 +461,8 @@ def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None):
         n = min(chunk, args.samples - done)
         more = net.continue_generation_batch(
             n, parts[-1][:, -1], seeds, args.temperature, gc,
-            local_condition=rows(len(waveform) + done - 1, n))
+            local_condition=rows(len(waveform) + done - 1, n),
+            top_k=args.top_k, top_p=args.top_p)
         parts.append(more.cpu().numpy())
         done += n
         print('Sample {:3<d}/{:3<d}'.format(done, args.samples), end='\r')

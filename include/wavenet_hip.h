@@ -601,7 +601,9 @@ int wn_fastgen_run_wide(const float* params_causal, const float* layer0,
  * (cursors, ctl), so the host captures a few hundred calls into a hipGraph
  * ONCE and replays it for every generate() call.
  * ctl: int32[8] = {base (cursors[0] when the call started), n_given,
- * proba_every, temperature (float bits), seed lo, seed hi, 0, 0}.
+ * proba_every, temperature (float bits), seed lo, seed hi, top_k, top_p
+ * (float bits)}; top_k / top_p: the truncated draw of wn_fastgen_run_trunc
+ * below, 0 = off.
  * pre: float[L][64], maintained by the step kernels; wn_fastgen_pre fills it
  * for the step the queues are at (call once before a sequence of steps). */
 int wn_fastgen_step(const float* params_causal, const float* layer0,
@@ -681,7 +683,9 @@ int wn_fastgen_pack(const float* layer0, long layer_stride, float* img, int L,
  * (cursors[0] - ctl[0] = i); proba_out (optional) float[B][ctl[5]][Q].
  * ctl: int32[8] = {base (cursors[0] when the call started), n_given,
  * proba_every, temperature (float bits), samples row stride, proba rows per
- * stream, 0, 0}.  The draw of stream b takes seeds[b] and the counter rule of
+ * stream, top_k, top_p (float bits)} (the truncated draw of
+ * wn_fastgen_run_trunc, one setting for all streams; 0 = off).
+ * The draw of stream b takes seeds[b] and the counter rule of
  * the single-stream generator.  A step's draw runs at the start of the NEXT
  * step; wn_fastgen_batch_finish draws for the last one (no-op when none is
  * pending).  wn_fastgen_batch_pre fills pre for the step the queues are at
@@ -758,6 +762,55 @@ int wn_fastgen_run_lc(const float* params_causal, const float* layer0,
                       uint64_t seed, float* proba_out, int proba_every,
                       int use_biases, int push, const float* lc_ring, int lc_R,
                       int lc_stride, void* stream);
+
+/* ---- top-k / nucleus (top-p) truncation of the draw.  Between the
+ * temperature and the inverse CDF the draw keeps, of the float32
+ * probabilities p it returns in proba_out (which stay untruncated):
+ *   top_k  the codes with p >= the top_k-th largest p (a tie at the cut keeps
+ *          its whole tie group); 0 or >= Q: every code
+ *   top_p  then, with w the tempered weights of what top_k kept: the smallest
+ *          set {p >= c} whose float64 w-mass is >= (double)top_p * sum(w);
+ *          0 or 1: every code
+ * and gives every other code weight exactly 0, so it is never drawn; the
+ * uniform and its counter rule are unchanged.  0 <= top_k, 0 <= top_p <= 1.
+ * The step, persistent and batched entry points read both from ctl words 6, 7;
+ * the entries with a scalar temperature have the counterparts below: the
+ * arguments of their entry point with top_k, top_p in front of the stream.
+ * top_k = 0, top_p = 0 is the plain entry point, bit for bit. */
+int wn_fastgen_run_trunc(const float* params_causal, const float* layer0,
+                         long layer_stride, const float* skip_w,
+                         const float* skip_bsum, const float* post1_w,
+                         const float* post1_b, const float* post2_w,
+                         const float* post2_b, const float* gc_bias_fg,
+                         const int32_t* dilations_dev, int L, int S, int Q,
+                         float* state, int32_t* cursors, int32_t* samples_io,
+                         int n_given, int n_steps, float temperature,
+                         uint64_t seed, float* proba_out, int proba_every,
+                         int use_biases, int push, int top_k, float top_p,
+                         void* stream);
+int wn_fastgen_run_wide_trunc(const float* params_causal, const float* layer0,
+                              long layer_stride, const float* skip_w,
+                              const float* skip_bsum, const float* post1_w,
+                              const float* post1_b, const float* post2_w,
+                              const float* post2_b, const float* gc_bias_fg,
+                              const int32_t* dilations_dev, int L, int C, int S,
+                              int Q, float* state, int32_t* cursors,
+                              int32_t* samples_io, int n_given, int n_steps,
+                              float temperature, uint64_t seed, float* proba_out,
+                              int proba_every, int use_biases, int push,
+                              void* coop, int top_k, float top_p, void* stream);
+int wn_fastgen_run_lc_trunc(const float* params_causal, const float* layer0,
+                            long layer_stride, const float* skip_w,
+                            const float* skip_bsum, const float* post1_w,
+                            const float* post1_b, const float* post2_w,
+                            const float* post2_b, const float* gc_bias_fg,
+                            const int32_t* dilations_dev, int L, int S, int Q,
+                            float* state, int32_t* cursors, int32_t* samples_io,
+                            int n_given, int n_steps, float temperature,
+                            uint64_t seed, float* proba_out, int proba_every,
+                            int use_biases, int push, const float* lc_ring,
+                            int lc_R, int lc_stride, int top_k, float top_p,
+                            void* stream);
 int wn_fastgen_pre_lc(const float* layer0, long layer_stride,
                       const float* gc_bias_fg, const int32_t* dilations_dev,
                       int L, const float* state, const int32_t* cursors,

@@ -319,6 +319,7 @@ __device__ __forceinline__ void gate_grad(const f32x16& dz, const f32x16& zz,
 // every draw site (tests/draw_ref.py restates it in float64 numpy):
 //   p    = float32(softmax_f64(logits))            the probabilities returned
 //   w_q  = exp(log(p_q) / tau - max)               w = p at tau == 1; 0 at p == 0
+//   w_q  = 0 for the codes top-k / top-p drop      (wave_trunc_cut; off: none)
 //   u    = uniform(seed, counter) * sum(w)         counter-based, no state
 //   code = the inverse CDF of w at u
 // ---------------------------------------------------------------------------
@@ -347,6 +348,57 @@ __device__ __forceinline__ double draw_log_weight(double p, double tau) {
   return p > 0.0 ? log(p) / tau : -INFINITY;
 }
 
+// ---- wave-wide reductions by DPP (row shifts inside the four 16-lane rows,
+// then lane 15 / lane 31 broadcast to the following rows): an inclusive scan in
+// six VALU steps, the total in lane 63 -- no LDS round trip per step as with
+// ds_bpermute shuffles.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_f32(float old, float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL,
+                                                    ROW_MASK, 0xf, false));
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_f64(double old, double x) {
+  const long long o = __double_as_longlong(old), v = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_update_dpp((int)o, (int)v, CTRL, ROW_MASK, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(v >> 32), CTRL, ROW_MASK, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+__device__ __forceinline__ double readlane_f64(double x, int l) {
+  const long long v = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_readlane((int)v, l), hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// max over the wave, the same value in every lane
+__device__ __forceinline__ float wave_max_f32(float x) {
+  x = fmaxf(x, dpp_f32<0x111, 0xf>(x, x));   // row_shr:1
+  x = fmaxf(x, dpp_f32<0x112, 0xf>(x, x));
+  x = fmaxf(x, dpp_f32<0x114, 0xf>(x, x));
+  x = fmaxf(x, dpp_f32<0x118, 0xf>(x, x));
+  x = fmaxf(x, dpp_f32<0x142, 0xa>(x, x));   // row_bcast:15 -> rows 1, 3
+  x = fmaxf(x, dpp_f32<0x143, 0xc>(x, x));   // row_bcast:31 -> rows 2, 3
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+}
+__device__ __forceinline__ double wave_max_f64(double x) {
+  x = fmax(x, dpp_f64<0x111, 0xf>(x, x));
+  x = fmax(x, dpp_f64<0x112, 0xf>(x, x));
+  x = fmax(x, dpp_f64<0x114, 0xf>(x, x));
+  x = fmax(x, dpp_f64<0x118, 0xf>(x, x));
+  x = fmax(x, dpp_f64<0x142, 0xa>(x, x));
+  x = fmax(x, dpp_f64<0x143, 0xc>(x, x));
+  return readlane_f64(x, 63);
+}
+// inclusive prefix sum over the lanes (lane 63: the wave's sum)
+__device__ __forceinline__ double wave_scan_f64(double x) {
+  x += dpp_f64<0x111, 0xf>(0.0, x);
+  x += dpp_f64<0x112, 0xf>(0.0, x);
+  x += dpp_f64<0x114, 0xf>(0.0, x);
+  x += dpp_f64<0x118, 0xf>(0.0, x);
+  x += dpp_f64<0x142, 0xa>(0.0, x);
+  x += dpp_f64<0x143, 0xc>(0.0, x);
+  return x;
+}
+
 // float64 softmax (model.py:620-621) by one wave of the Q logits in pd.
 // Leaves the float32-rounded probabilities, the ones generate.py sees, in pd
 // as doubles and stores them to po unless it is null.  Each exp is evaluated
@@ -369,12 +421,85 @@ __device__ __forceinline__ void wave_softmax_f64(double* pd, int Q, int lane, fl
   }
 }
 
+// ---------------------------------------------------------------------------
+// Top-k / nucleus (top-p) truncation of the draw (tests/trunc_ref.py restates
+// it in float64 numpy; wavenet/sampling.py is the host's copy).  It acts on
+// the tempered weights w, between the temperature and the inverse CDF:
+//   top-k    keep the codes with w >= the top_k-th largest w (a tie at the cut
+//            keeps its whole tie group); 0 or >= Q: off
+//   nucleus  of what top-k kept, with total = sum(w): the smallest set
+//            {w >= c} whose mass is >= (double)top_p * total; 0 or >= 1: off
+// Dropped codes get weight exactly 0, so the inverse CDF never returns them.
+// The rule selects on the float32 probabilities; w is a strictly increasing
+// function of p (equal p give equal w), so the sets are the same.  Both are
+// "the largest cut c with f({w >= c}) >= bound" for a monotone f (a count, a
+// float64 mass added in one fixed order), found by bisection over the weights'
+// bit patterns: non-negative doubles order as unsigned integers.  At tau == 1
+// the weights are float32 values, whose low 29 mantissa bits are 0: the keys
+// are shifted by `sh` = 29 then and the search takes half the probes.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool draw_trunc_on(int top_k, float top_p) {
+  return top_k > 0 || (top_p > 0.f && top_p < 1.f);
+}
+__device__ __forceinline__ int draw_key_shift(float temperature) {
+  return temperature == 1.0f ? 29 : 0;
+}
+__device__ __forceinline__ uint64_t draw_key(double w, int sh) {
+  return (uint64_t)__double_as_longlong(w) >> sh;
+}
+
+// The cut of the Q weights w (LDS, read only) by one whole wave: keep code q
+// iff draw_key(w[q], sh) >= the returned key (the same value in every lane).
+// Lane l adds its weights q = l, l + 64, ... in ascending order, the lanes'
+// sums are added by wave_scan_f64: every probe's mass is summed the same way.
+__device__ __forceinline__ uint64_t wave_trunc_cut(const double* w, int Q, int lane, int top_k,
+                                                   float top_p, int sh) {
+  double mx = 0.0, nmn = -INFINITY;
+  for (int q = lane; q < Q; q += 64) {
+    mx = fmax(mx, w[q]);
+    nmn = fmax(nmn, -w[q]);
+  }
+  uint64_t lo = draw_key(-wave_max_f64(nmn), sh);      // every code is >= lo
+  const uint64_t hi = draw_key(wave_max_f64(mx), sh);
+  if (top_k > 0 && top_k < Q) {
+    uint64_t b = hi;
+    while (lo < b) {                                   // count(key >= lo) >= top_k holds
+      const uint64_t mid = lo + ((b - lo + 1) >> 1);
+      int n = 0;
+      for (int q0 = 0; q0 < Q; q0 += 64) {             // (wave-uniform trip count)
+        const int q = q0 + lane;
+        n += __popcll(__builtin_amdgcn_ballot_w64(q < Q && draw_key(w[q < Q ? q : 0], sh) >= mid));
+      }
+      if (n >= top_k) lo = mid; else b = mid - 1;
+    }
+  }
+  if (top_p > 0.f && top_p < 1.f) {
+    auto mass = [&](uint64_t c) {
+      double s = 0.0;
+      for (int q = lane; q < Q; q += 64) {
+        const double v = w[q];
+        s += draw_key(v, sh) >= c ? v : 0.0;
+      }
+      return readlane_f64(wave_scan_f64(s), 63);
+    };
+    const double bound = (double)top_p * mass(lo);     // of what top-k kept
+    uint64_t b = hi;
+    while (lo < b) {                                   // mass(key >= lo) >= bound holds
+      const uint64_t mid = lo + ((b - lo + 1) >> 1);
+      if (mass(mid) >= bound) lo = mid; else b = mid - 1;
+    }
+  }
+  return lo;
+}
+
 // The draw by one wave from the probabilities wave_softmax_f64 left in pd
-// (overwritten with the weights): temperature, then the inverse CDF over
-// per-lane contiguous segments (segment sums -> prefix sum -> pick) with the
-// uniform of (seed, counter).  Returns the code in every lane.
+// (overwritten with the weights): temperature, the truncation above (top_k =
+// 0, top_p = 0: none), then the inverse CDF over per-lane contiguous segments
+// (segment sums -> prefix sum -> pick) with the uniform of (seed, counter).
+// Returns the code in every lane.
 __device__ __forceinline__ int wave_draw_f64(double* pd, int Q, int lane, float temperature,
-                                             uint64_t seed, uint64_t counter) {
+                                             int top_k, float top_p, uint64_t seed,
+                                             uint64_t counter) {
   if (temperature != 1.0f) {
     const double tau = (double)temperature;
     double mx = -1e300;
@@ -385,6 +510,12 @@ __device__ __forceinline__ int wave_draw_f64(double* pd, int Q, int lane, float 
     }
     for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
     for (int q = lane; q < Q; q += 64) pd[q] = exp(pd[q] - mx);
+  }
+  if (draw_trunc_on(top_k, top_p)) {
+    const int sh = draw_key_shift(temperature);
+    const uint64_t cut = wave_trunc_cut(pd, Q, lane, top_k, top_p, sh);
+    for (int q = lane; q < Q; q += 64)
+      if (draw_key(pd[q], sh) < cut) pd[q] = 0.0;
   }
   __builtin_amdgcn_wave_barrier();
   const int per = (Q + 63) / 64;

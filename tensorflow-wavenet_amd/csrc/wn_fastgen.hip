@@ -50,6 +50,8 @@ struct FastGen {
   int32_t* samples;      // [n_steps + 1]
   int n_given, n_steps;
   float temperature;
+  int top_k;             // top-k / nucleus truncation of the draw (wn_common.h);
+  float top_p;           // 0: off
   uint64_t seed;
   float* proba_out;      // [ceil(n_steps/proba_every)][Q] or null
   int proba_every;
@@ -126,6 +128,8 @@ struct FastGenLc {
 #define FGCTL_PEVERY 2
 #define FGCTL_TEMP 3         // float bits
 #define FGCTL_SEED 4         // 4, 5: uint64 seed (lo, hi)
+#define FGCTL_TOPK 6         // top-k of the draw, 0: off
+#define FGCTL_TOPP 7         // top-p of the draw (float bits), 0: off
 #define FGCTL_WORDS 8
 
 struct FgStep {
@@ -516,6 +520,8 @@ __global__ __launch_bounds__(256) void fg_logits_kernel(FgStep g) {
 struct FgDrawCtl {
   int base, n_given, proba_every;
   float temperature;
+  int top_k;
+  float top_p;
   uint64_t seed;
 };
 __device__ __forceinline__ FgDrawCtl fg_draw_ctl(const FgStep& g) {
@@ -524,6 +530,8 @@ __device__ __forceinline__ FgDrawCtl fg_draw_ctl(const FgStep& g) {
   c.n_given = g.ctl[FGCTL_NGIVEN];
   c.proba_every = g.ctl[FGCTL_PEVERY] > 0 ? g.ctl[FGCTL_PEVERY] : 1;
   c.temperature = __int_as_float(g.ctl[FGCTL_TEMP]);
+  c.top_k = g.ctl[FGCTL_TOPK];
+  c.top_p = __int_as_float(g.ctl[FGCTL_TOPP]);
   c.seed = (uint64_t)(uint32_t)g.ctl[FGCTL_SEED] | ((uint64_t)(uint32_t)g.ctl[FGCTL_SEED + 1] << 32);
   return c;
 }
@@ -539,7 +547,7 @@ __device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lan
   wave_softmax_f64(pd, Q, lane, want_p ? g.proba_out + (long)(local / dc.proba_every) * Q : nullptr);
   int next;
   if (local + 1 >= dc.n_given) {
-    next = wave_draw_f64(pd, Q, lane, dc.temperature, dc.seed, (uint64_t)steps_done);
+    next = wave_draw_f64(pd, Q, lane, dc.temperature, dc.top_k, dc.top_p, dc.seed, (uint64_t)steps_done);
     if (lane == 0) g.samples[local + 1] = next;
   } else {
     next = g.samples[local + 1];           // still inside the given samples
@@ -717,56 +725,8 @@ __device__ __forceinline__ void fgp_get2(float* dst, const fgp_ll_t* src, int k0
   if (h1) dst[d1] = __uint_as_float((unsigned)w1);
 }
 
-// ---- wave-wide reductions by DPP (row shifts inside the four 16-lane rows,
-// then lane 15 / lane 31 broadcast to the following rows): an inclusive scan in
-// six VALU steps, the total in lane 63 -- no LDS round trip per step as with
-// ds_bpermute shuffles.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f32(float old, float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL,
-                                                    ROW_MASK, 0xf, false));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double old, double x) {
-  const long long o = __double_as_longlong(old), v = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_update_dpp((int)o, (int)v, CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(v >> 32), CTRL, ROW_MASK, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double readlane_f64(double x, int l) {
-  const long long v = __double_as_longlong(x);
-  const int lo = __builtin_amdgcn_readlane((int)v, l), hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// max over the wave, the same value in every lane
-__device__ __forceinline__ float wave_max_f32(float x) {
-  x = fmaxf(x, dpp_f32<0x111, 0xf>(x, x));   // row_shr:1
-  x = fmaxf(x, dpp_f32<0x112, 0xf>(x, x));
-  x = fmaxf(x, dpp_f32<0x114, 0xf>(x, x));
-  x = fmaxf(x, dpp_f32<0x118, 0xf>(x, x));
-  x = fmaxf(x, dpp_f32<0x142, 0xa>(x, x));   // row_bcast:15 -> rows 1, 3
-  x = fmaxf(x, dpp_f32<0x143, 0xc>(x, x));   // row_bcast:31 -> rows 2, 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
-__device__ __forceinline__ double wave_max_f64(double x) {
-  x = fmax(x, dpp_f64<0x111, 0xf>(x, x));
-  x = fmax(x, dpp_f64<0x112, 0xf>(x, x));
-  x = fmax(x, dpp_f64<0x114, 0xf>(x, x));
-  x = fmax(x, dpp_f64<0x118, 0xf>(x, x));
-  x = fmax(x, dpp_f64<0x142, 0xa>(x, x));
-  x = fmax(x, dpp_f64<0x143, 0xc>(x, x));
-  return readlane_f64(x, 63);
-}
-// inclusive prefix sum over the lanes (lane 63: the wave's sum)
-__device__ __forceinline__ double wave_scan_f64(double x) {
-  x += dpp_f64<0x111, 0xf>(0.0, x);
-  x += dpp_f64<0x112, 0xf>(0.0, x);
-  x += dpp_f64<0x114, 0xf>(0.0, x);
-  x += dpp_f64<0x118, 0xf>(0.0, x);
-  x += dpp_f64<0x142, 0xa>(0.0, x);
-  x += dpp_f64<0x143, 0xc>(0.0, x);
-  return x;
-}
+// (the wave-wide DPP reductions dpp_f32 / dpp_f64 / wave_max_* / wave_scan_f64:
+// wn_common.h, beside the draw)
 
 // ---- a 32-input mat-vec without an LDS round trip (round 6).  The input
 // vector sits REPLICATED in every 16-lane row of two registers (lo: inputs
@@ -843,9 +803,14 @@ __device__ __forceinline__ void fg_row_halves(float v, float& lo, float& hi) {
 // the reductions as ds_bpermute shuffles of doubles: 2.36 us per draw).  The
 // thread whose interval holds the random number publishes the code itself.
 // part: 16 doubles of LDS; nxt: 2 ints of LDS (the code drawn at step parity).
+// Truncation (dc.top_k / dc.top_p, off: not a barrier more): the tempered
+// weights go to `wts` (Q doubles of LDS) and each of the four waves finds the
+// cut of wave_trunc_cut for itself over all Q of them -- the same additions in
+// every wave, so the same cut, and one barrier instead of one per probe --,
+// then zeroes its threads' dropped weights in their registers.
 template <int PER>   // values per computing thread: 1 (Q <= 256) or 2
 __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& dc, const float* lgs,
-                                              double* part, int* nxt, fgp_ll_t* x0ll,
+                                              double* part, double* wts, int* nxt, fgp_ll_t* x0ll,
                                               const float* ctab, int cur_code,
                                               unsigned step, bool publish, int tid,
                                               int steps_done) {
@@ -922,6 +887,19 @@ __device__ __forceinline__ void fg_draw_wg256(const FgStep& g, const FgDrawCtl& 
 #pragma unroll
     for (int j = 0; j < PER; ++j)
       if (q0 + j < q1) pq[j] = exp(lp[j] - mx);
+  }
+  if (draw_trunc_on(dc.top_k, dc.top_p)) {
+    // (wts is rewritten a step later behind that step's first barrier, which
+    // every wave reaches after its search)
+#pragma unroll
+    for (int j = 0; j < PER; ++j)
+      if (q0 + j < q1) wts[q0 + j] = pq[j];
+    __syncthreads();
+    const int sh = draw_key_shift(dc.temperature);
+    const uint64_t cut = wave_trunc_cut(wts, Q, lane, dc.top_k, dc.top_p, sh);
+#pragma unroll
+    for (int j = 0; j < PER; ++j)
+      if (draw_key(pq[j], sh) < cut) pq[j] = 0.0;
   }
   // prefix sums: inside the wave by DPP, the waves' totals through LDS.  A
   // thread's exclusive bound is its neighbour's inclusive sum and a wave's
@@ -1572,7 +1550,7 @@ __global__ __launch_bounds__(F64 ? 512 : FGW_THREADS, 1) void fastgen_wide_kerne
     __syncthreads();
     if (step + 1 >= g.n_given) {
       if (wave == 0) {
-        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.seed, (uint64_t)tpos);
+        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.top_k, g.top_p, g.seed, (uint64_t)tpos);
         if (lane == 0) {
           g.samples[step + 1] = best;
           s_code = best;
@@ -1641,6 +1619,11 @@ int wn_fastgen_init(float* state, long state_floats, int32_t* cursors, int L,
   return WN_OK;
 }
 
+// top_k >= 0 and 0 <= top_p <= 1 (0: off; top_k >= Q and top_p == 1 keep every code)
+static bool fg_trunc_ok(int top_k, float top_p) {
+  return top_k >= 0 && top_p >= 0.f && top_p <= 1.f;
+}
+
 static int fg_run(bool lc, const float* lc_ring, int lc_R, int lc_stride,
     const float* params_causal, const float* layer0,
                    long layer_stride, const float* skip_w, const float* skip_bsum,
@@ -1649,11 +1632,12 @@ static int fg_run(bool lc, const float* lc_ring, int lc_R, int lc_stride,
                    const float* gc_bias_fg, const int32_t* dilations_dev,
                    int L, int S, int Q, float* state, int32_t* cursors,
                    int32_t* samples_io, int n_given, int n_steps,
-                   float temperature, uint64_t seed, float* proba_out,
+                   float temperature, int top_k, float top_p, uint64_t seed, float* proba_out,
                    int proba_every, int use_biases, int push, void* stream) {
   if (!params_causal || !layer0 || !skip_w || !post1_w || !post2_w ||
       !dilations_dev || !state || !cursors || !samples_io)
     return WN_ERR_NULL;
+  if (!fg_trunc_ok(top_k, top_p)) return WN_ERR_BAD_SHAPE;
   if (lc && !lc_ring) return WN_ERR_NULL;
   if (lc && (lc_R < 1 || (lc_stride != 0 && lc_stride != 64))) return WN_ERR_BAD_SHAPE;
   if (L <= 0 || S <= 0 || Q <= 0 || n_steps <= 0 || n_given < 1)
@@ -1667,6 +1651,7 @@ static int fg_run(bool lc, const float* lc_ring, int lc_R, int lc_stride,
   g.bias_fg = gc_bias_fg; g.dil = dilations_dev; g.L = L; g.S = S; g.Q = Q;
   g.state = state; g.cursors = cursors; g.samples = samples_io;
   g.n_given = n_given; g.n_steps = n_steps; g.temperature = temperature;
+  g.top_k = top_k; g.top_p = top_p;
   g.seed = seed; g.proba_out = proba_out;
   g.proba_every = proba_every > 0 ? proba_every : 1;
   g.use_dense_bias = use_biases;
@@ -1694,8 +1679,26 @@ int wn_fastgen_run(const float* params_causal, const float* layer0,
                    int proba_every, int use_biases, int push, void* stream) {
   return fg_run(false, nullptr, 0, 0, params_causal, layer0, layer_stride, skip_w, skip_bsum,
                 post1_w, post1_b, post2_w, post2_b, gc_bias_fg, dilations_dev, L, S, Q, state,
-                cursors, samples_io, n_given, n_steps, temperature, seed, proba_out,
+                cursors, samples_io, n_given, n_steps, temperature, 0, 0.f, seed, proba_out,
                 proba_every, use_biases, push, stream);
+}
+
+// wn_fastgen_run with the draw truncated to top_k codes and / or the top_p
+// nucleus (wn_common.h; 0: off -- both 0 is wn_fastgen_run)
+int wn_fastgen_run_trunc(const float* params_causal, const float* layer0,
+                         long layer_stride, const float* skip_w, const float* skip_bsum,
+                         const float* post1_w, const float* post1_b,
+                         const float* post2_w, const float* post2_b,
+                         const float* gc_bias_fg, const int32_t* dilations_dev,
+                         int L, int S, int Q, float* state, int32_t* cursors,
+                         int32_t* samples_io, int n_given, int n_steps,
+                         float temperature, uint64_t seed, float* proba_out,
+                         int proba_every, int use_biases, int push, int top_k,
+                         float top_p, void* stream) {
+  return fg_run(false, nullptr, 0, 0, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+                post1_w, post1_b, post2_w, post2_b, gc_bias_fg, dilations_dev, L, S, Q, state,
+                cursors, samples_io, n_given, n_steps, temperature, top_k, top_p, seed,
+                proba_out, proba_every, use_biases, push, stream);
 }
 
 int wn_fastgen_run_lc(const float* params_causal, const float* layer0,
@@ -1710,8 +1713,24 @@ int wn_fastgen_run_lc(const float* params_causal, const float* layer0,
                       int lc_R, int lc_stride, void* stream) {
   return fg_run(true, lc_ring, lc_R, lc_stride, params_causal, layer0, layer_stride, skip_w,
                 skip_bsum, post1_w, post1_b, post2_w, post2_b, gc_bias_fg, dilations_dev, L, S,
-                Q, state, cursors, samples_io, n_given, n_steps, temperature, seed, proba_out,
-                proba_every, use_biases, push, stream);
+                Q, state, cursors, samples_io, n_given, n_steps, temperature, 0, 0.f, seed,
+                proba_out, proba_every, use_biases, push, stream);
+}
+
+int wn_fastgen_run_lc_trunc(const float* params_causal, const float* layer0,
+                            long layer_stride, const float* skip_w, const float* skip_bsum,
+                            const float* post1_w, const float* post1_b,
+                            const float* post2_w, const float* post2_b,
+                            const float* gc_bias_fg, const int32_t* dilations_dev,
+                            int L, int S, int Q, float* state, int32_t* cursors,
+                            int32_t* samples_io, int n_given, int n_steps,
+                            float temperature, uint64_t seed, float* proba_out,
+                            int proba_every, int use_biases, int push, const float* lc_ring,
+                            int lc_R, int lc_stride, int top_k, float top_p, void* stream) {
+  return fg_run(true, lc_ring, lc_R, lc_stride, params_causal, layer0, layer_stride, skip_w,
+                skip_bsum, post1_w, post1_b, post2_w, post2_b, gc_bias_fg, dilations_dev, L, S,
+                Q, state, cursors, samples_io, n_given, n_steps, temperature, top_k, top_p, seed,
+                proba_out, proba_every, use_biases, push, stream);
 }
 
 
@@ -1730,19 +1749,20 @@ long wn_fastgen_wide_coop_bytes(int L, int C, int S, int Q) {
   return (long)FGP_WORDS * 4 + ((long)L * C + 2L * S + Q) * 8;
 }
 
-int wn_fastgen_run_wide(const float* params_causal, const float* layer0,
+static int fg_run_wide(const float* params_causal, const float* layer0,
                         long layer_stride, const float* skip_w,
                         const float* skip_bsum, const float* post1_w,
                         const float* post1_b, const float* post2_w,
                         const float* post2_b, const float* gc_bias_fg,
                         const int32_t* dilations_dev, int L, int C, int S, int Q,
                         float* state, int32_t* cursors, int32_t* samples_io,
-                        int n_given, int n_steps, float temperature,
+                        int n_given, int n_steps, float temperature, int top_k, float top_p,
                         uint64_t seed, float* proba_out, int proba_every,
                         int use_biases, int push, void* coop, void* stream) {
   if (!params_causal || !layer0 || !skip_w || !post1_w || !post2_w ||
       !dilations_dev || !state || !cursors || !samples_io)
     return WN_ERR_NULL;
+  if (!fg_trunc_ok(top_k, top_p)) return WN_ERR_BAD_SHAPE;
   if (L <= 0 || S <= 0 || Q <= 0 || n_steps <= 0 || n_given < 1 || C <= 0 ||
       C % 32 != 0)
     return WN_ERR_BAD_SHAPE;
@@ -1770,6 +1790,7 @@ int wn_fastgen_run_wide(const float* params_causal, const float* layer0,
   g.bias_fg = gc_bias_fg; g.dil = dilations_dev; g.L = L; g.S = S; g.Q = Q;
   g.state = state; g.cursors = cursors; g.samples = samples_io;
   g.n_given = n_given; g.n_steps = n_steps; g.temperature = temperature;
+  g.top_k = top_k; g.top_p = top_p;
   g.seed = seed; g.proba_out = proba_out;
   g.proba_every = proba_every > 0 ? proba_every : 1;
   g.use_dense_bias = use_biases;
@@ -1812,6 +1833,40 @@ int wn_fastgen_run_wide(const float* params_causal, const float* layer0,
   else
     hipLaunchKernelGGL((fastgen_wide_kernel<false, false>), dim3(1), dim3(FGW_THREADS), lds, s, a);
   return wn_check_launch();
+}
+
+int wn_fastgen_run_wide(const float* params_causal, const float* layer0,
+                        long layer_stride, const float* skip_w,
+                        const float* skip_bsum, const float* post1_w,
+                        const float* post1_b, const float* post2_w,
+                        const float* post2_b, const float* gc_bias_fg,
+                        const int32_t* dilations_dev, int L, int C, int S, int Q,
+                        float* state, int32_t* cursors, int32_t* samples_io,
+                        int n_given, int n_steps, float temperature,
+                        uint64_t seed, float* proba_out, int proba_every,
+                        int use_biases, int push, void* coop, void* stream) {
+  return fg_run_wide(params_causal, layer0, layer_stride, skip_w, skip_bsum, post1_w, post1_b,
+                     post2_w, post2_b, gc_bias_fg, dilations_dev, L, C, S, Q, state, cursors,
+                     samples_io, n_given, n_steps, temperature, 0, 0.f, seed, proba_out,
+                     proba_every, use_biases, push, coop, stream);
+}
+
+// wn_fastgen_run_wide with the truncated draw of wn_fastgen_run_trunc
+int wn_fastgen_run_wide_trunc(const float* params_causal, const float* layer0,
+                              long layer_stride, const float* skip_w,
+                              const float* skip_bsum, const float* post1_w,
+                              const float* post1_b, const float* post2_w,
+                              const float* post2_b, const float* gc_bias_fg,
+                              const int32_t* dilations_dev, int L, int C, int S, int Q,
+                              float* state, int32_t* cursors, int32_t* samples_io,
+                              int n_given, int n_steps, float temperature,
+                              uint64_t seed, float* proba_out, int proba_every,
+                              int use_biases, int push, void* coop, int top_k, float top_p,
+                              void* stream) {
+  return fg_run_wide(params_causal, layer0, layer_stride, skip_w, skip_bsum, post1_w, post1_b,
+                     post2_w, post2_b, gc_bias_fg, dilations_dev, L, C, S, Q, state, cursors,
+                     samples_io, n_given, n_steps, temperature, top_k, top_p, seed, proba_out,
+                     proba_every, use_biases, push, coop, stream);
 }
 
 
@@ -1983,7 +2038,8 @@ static int fg_persist(bool lc, const float* lc_ring, int lc_R, int lc_stride,
   size_t chain = (size_t)per * FGP_BLK + 2 * FGP_SEGL + 8;
   size_t skip = (size_t)((L * 32 + 3) & ~3) + (size_t)L * 32 * 16 + 256;
   size_t post = (size_t)((S + 3) & ~3) + (size_t)S * 16 + 256;
-  size_t draw = (size_t)((Q + 3) & ~3) + 48 + (size_t)2 * Q * 32;   // + the causal table
+  // + the causal table + the truncating draw's Q doubles
+  size_t draw = (size_t)((Q + 3) & ~3) + 48 + (size_t)2 * Q * 32 + (size_t)2 * Q;
   size_t fl = chain;
   if (skip > fl) fl = skip;
   if (post > fl) fl = post;

@@ -38,13 +38,15 @@
 // ctl: int32[8] per call (device memory, so that a captured graph serves
 // every call): base (cursors[0] when the call started), n_given, proba_every,
 // temperature (float bits), row stride of samples_io, rows per stream of
-// proba_out, 0, 0
+// proba_out, top-k and top-p (float bits) of the draw (0: off)
 #define FGB_CTL_BASE 0
 #define FGB_CTL_NGIVEN 1
 #define FGB_CTL_PEVERY 2
 #define FGB_CTL_TEMP 3
 #define FGB_CTL_LDS 4
 #define FGB_CTL_LDP 5
+#define FGB_CTL_TOPK 6
+#define FGB_CTL_TOPP 7
 
 struct FgBatch {
   const float* causal;     // [2][Q][32]
@@ -97,8 +99,9 @@ __device__ void fgb_draw_wave(const FgBatch& g, double* pd, int lane, int b, int
                    want_p ? g.proba_out + ((long)b * g.ctl[FGB_CTL_LDP] + local / proba_every) * Q
                           : nullptr);
   if (local + 1 < g.ctl[FGB_CTL_NGIVEN]) return;   // still inside the given samples
-  const int code = wave_draw_f64(pd, Q, lane, __int_as_float(g.ctl[FGB_CTL_TEMP]), g.seeds[b],
-                                 (uint64_t)step);
+  const int code = wave_draw_f64(pd, Q, lane, __int_as_float(g.ctl[FGB_CTL_TEMP]),
+                                 g.ctl[FGB_CTL_TOPK], __int_as_float(g.ctl[FGB_CTL_TOPP]),
+                                 g.seeds[b], (uint64_t)step);
   if (lane == 0) g.samples[(long)b * g.ctl[FGB_CTL_LDS] + local + 1] = code;
 }
 

@@ -231,7 +231,7 @@ __global__ __launch_bounds__(FG_THREADS, 1) void fastgen_kernel(FastGen g) {
     __syncthreads();
     if (step + 1 >= g.n_given) {
       if (wave == 0) {
-        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.seed, (uint64_t)tpos);
+        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.top_k, g.top_p, g.seed, (uint64_t)tpos);
         if (lane == 0) {
           g.samples[step + 1] = best;
           s_code = best;

@@ -256,6 +256,7 @@ __global__ __launch_bounds__(FGP_THREADS) void fg_persist_kernel(FgPersist a) {
   double* dpart = reinterpret_cast<double*>(lds + ((Q + 3) & ~3));  // 16 doubles: per-wave partials
   int* nxt = reinterpret_cast<int*>(dpart + 16);                 // [2] the code drawn at step parity
   float* ctab = reinterpret_cast<float*>(nxt + 8);               // [2][Q][32] the causal layer's filter
+  double* wts = reinterpret_cast<double*>(ctab + 2 * Q * 32);    // [Q] the truncating draw's weights
   for (int i = tid; i < 2 * Q * 32; i += 256) ctab[i] = g.causal[i];
   const FgDrawCtl dc = fg_draw_ctl(g);
   __syncthreads();
@@ -270,8 +271,8 @@ __global__ __launch_bounds__(FGP_THREADS) void fg_persist_kernel(FgPersist a) {
     // (dpart[] is rewritten a step later only after this barrier, which every
     // wave reaches after its last read of the step before)
     // the drawing thread publishes the code of step i + 1 for segment 0
-    if (Q <= 256) fg_draw_wg256<1>(g, dc, lgs, dpart, nxt, x0ll, ctab, cur_code, step, i + 1 < n_steps, tid, base + i);
-    else fg_draw_wg256<2>(g, dc, lgs, dpart, nxt, x0ll, ctab, cur_code, step, i + 1 < n_steps, tid, base + i);
+    if (Q <= 256) fg_draw_wg256<1>(g, dc, lgs, dpart, wts, nxt, x0ll, ctab, cur_code, step, i + 1 < n_steps, tid, base + i);
+    else fg_draw_wg256<2>(g, dc, lgs, dpart, wts, nxt, x0ll, ctab, cur_code, step, i + 1 < n_steps, tid, base + i);
     PSTAMP(i * 16 + 15);
   }
   __syncthreads();

@@ -205,6 +205,10 @@ for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
     # ..., const float* lc_ring, int lc_R, int lc_stride, void* stream
     _res, _args = SIGNATURES[_name]
     SIGNATURES[_name + '_lc'] = (_res, _args[:-1] + [P, c_int, c_int, P])
+for _name in ('wn_fastgen_run', 'wn_fastgen_run_wide', 'wn_fastgen_run_lc'):
+    # ..., int top_k, float top_p, void* stream (the truncated draw; 0: off)
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + '_trunc'] = (_res, _args[:-1] + [c_int, c_float, P])
 
 
 

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import local_condition as lcond
+from . import sampling
 from . import train_pass
 
 CH = 32
@@ -136,6 +137,20 @@ def _check_temperature(temperature):
                          % (temperature,))
 
 
+# Top-k / nucleus truncation of the draw (wavenet/sampling.py has the rule):
+# `trunc` = (top_k, top_p) as sampling.resolve gives them, 0 meaning off.  The
+# step, persistent and batched launches read them from ctl words 6, 7 (as the
+# temperature: captured graphs stay valid); the entry points with a scalar
+# temperature have _trunc counterparts, called only when one of them is on.
+_NO_TRUNC = (0, 0.0)
+
+
+def _trunc_entry(name, trunc):
+    # (entry point, its arguments in front of the stream)
+    return (name + '_trunc', (int(trunc[0]), float(trunc[1]))) \
+        if trunc != _NO_TRUNC else (name, ())
+
+
 def _buf(net, g, name, n, dtype):
     """Persistent buffer of g of at least n elements (grown geometrically;
     growing drops the captured graphs, which hold its address)."""
@@ -168,10 +183,11 @@ def _weights(net, g, gc, B):
 
 
 def _stage(net, g, io, n_given, n_steps, temperature, proba, proba_every,
-           seed=None):
+           seed=None, trunc=_NO_TRUNC):
     # per-call values go to ctl and two persistent buffers (codes io [B, >=
     # n_steps + 1], probabilities), so captured graphs stay valid; ctl words
-    # 4-5: one stream's seed, or B streams' row stride and probability rows
+    # 4-5: one stream's seed, or B streams' row stride and probability rows;
+    # 6-7: top_k and top_p of the draw
     B, ld = io.shape[0], int(n_steps) + 1
     pe = max(1, int(proba_every))
     rows = (int(n_steps) + pe - 1) // pe if proba is not None else 0
@@ -185,6 +201,7 @@ def _stage(net, g, io, n_given, n_steps, temperature, proba, proba_every,
     ctl[3] = np.float32(temperature).view(np.uint32)
     ctl[4], ctl[5] = (ld, rows) if seed is None else \
         (seed & 0xffffffff, seed >> 32)
+    ctl[6], ctl[7] = trunc[0], np.float32(trunc[1]).view(np.uint32)
     g['ctl'].copy_(torch.from_numpy(ctl.view(np.int32)))
     return iob, pb
 
@@ -324,10 +341,12 @@ def reset(net):
 
 
 def run(net, temperature, seed, global_condition, samples_io, n_given,
-        n_steps, proba_out, proba_every, push=True, multi_cu=False, lc=None):
+        n_steps, proba_out, proba_every, push=True, multi_cu=False, lc=None,
+        trunc=_NO_TRUNC):
     """Run `n_steps` generation steps on samples_io int32 [n_steps + 1]
     (the first n_given codes given, the rest drawn) on one device path.
-    lc: an LC model's rows [n_steps, Lc], row i beside samples_io[i]."""
+    lc: an LC model's rows [n_steps, Lc], row i beside samples_io[i].
+    trunc: (top_k, top_p) of sampling.resolve."""
     # (wn_fastgen_step reads both from the device control block and cannot
     # reject them; the reference applies the temperature as log(p) / T,
     # generate.py:229-233)
@@ -346,14 +365,15 @@ def run(net, temperature, seed, global_condition, samples_io, n_given,
     if lc is not None:
         _run_lc(net, g, head, bias, queues, samples_io, int(n_given),
                 int(n_steps), float(temperature), sd, proba_out,
-                max(1, int(proba_every)), ub, push, multi_cu, lc)
+                max(1, int(proba_every)), ub, push, multi_cu, lc, trunc)
     elif net.CB > 1 or net.S > 512 or net.Q > 512 or net.L > 64:
         _run_wide(net, g, samples_io,
-                  head + (net.L, net.CHn, net.S, net.Q) + run_args)
+                  head + (net.L, net.CHn, net.S, net.Q) + run_args, trunc)
     elif not multi_cu or not push:
         # ONE single-workgroup kernel; the peek always runs here, as the
         # multi-CU launches advance the queues with every step they take
-        _lib.call('wn_fastgen_run', *head, net.L, net.S, net.Q, *run_args,
+        name, targs = _trunc_entry('wn_fastgen_run', trunc)
+        _lib.call(name, *head, net.L, net.S, net.Q, *run_args, *targs,
                   _lib.stream())
     else:
         st = _lib.stream()
@@ -367,7 +387,7 @@ def run(net, temperature, seed, global_condition, samples_io, n_given,
                   _lib.ptr(g['dil']), net.L, *queues, _lib.ptr(g['pre']), st)
         io = samples_io.view(1, -1)
         iob, pb = _stage(net, g, io, n_given, n_steps, temperature,
-                         proba_out, proba_every, seed=sd)
+                         proba_out, proba_every, seed=sd, trunc=trunc)
         common = head + (net.L, net.S, net.Q) + queues + (_lib.ptr(iob),)
         tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), ub, _lib.ptr(g['cw_img']),
                 _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
@@ -384,7 +404,8 @@ def run(net, temperature, seed, global_condition, samples_io, n_given,
 
 
 def _run_lc(net, g, head, bias, queues, samples_io, n_given, n_steps,
-            temperature, sd, proba_out, pe, ub, push, multi_cu, lc):
+            temperature, sd, proba_out, pe, ub, push, multi_cu, lc,
+            trunc=_NO_TRUNC):
     # one LC call, chunk by chunk (see _LcRing); the paths of run()
     ring = _LcRing(net, g, _lc_rows_padded(net, lc.reshape(1, n_steps, net.Lc),
                                            n_steps), 1, bias, 0, n_steps, pe)
@@ -393,12 +414,13 @@ def _run_lc(net, g, head, bias, queues, samples_io, n_given, n_steps,
     def prows(a):                  # the probability rows from call step a
         return None if proba_out is None else proba_out.view(-1)[a // pe * Q:]
     if not multi_cu or not push:
+        name, targs = _trunc_entry('wn_fastgen_run_lc', trunc)
         for a, n in ring.plan:
             ring.fill(a, n)
-            _lib.call('wn_fastgen_run_lc', *head, net.L, net.S, net.Q,
+            _lib.call(name, *head, net.L, net.S, net.Q,
                       *queues, _lib.ptr(samples_io[a:]), max(1, n_given - a),
                       n, temperature, sd, _lib.ptr(prows(a)), pe, ub,
-                      1 if push else 0, *ring.args(), _lib.stream())
+                      1 if push else 0, *ring.args(), *targs, _lib.stream())
         return
     st = _lib.stream()
     layer0 = _lib.ptr(net._layer_block(net.params, 0))
@@ -412,7 +434,7 @@ def _run_lc(net, g, head, bias, queues, samples_io, n_given, n_steps,
         g['steps'] = steps0 + a
         pr = prows(a)
         iob, pb = _stage(net, g, io[:, a:], max(1, n_given - a), n_run,
-                         temperature, pr, pe, seed=sd)
+                         temperature, pr, pe, seed=sd, trunc=trunc)
         common = head + (net.L, net.S, net.Q) + queues + (_lib.ptr(iob),)
         tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), ub, _lib.ptr(g['cw_img']),
                 _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
@@ -463,10 +485,11 @@ def _run_lc(net, g, head, bias, queues, samples_io, n_given, n_steps,
     g['steps'] = steps0
 
 
-def _run_wide(net, g, samples_io, args):
+def _run_wide(net, g, samples_io, args, trunc=_NO_TRUNC):
     # more than 32 channels, or more S / Q / L than the tuned kernels hold
     # in LDS: one workgroup, or the cooperative launch (skip sum and post-
     # processing on other CUs) where the library has one for the shape
+    name, targs = _trunc_entry('wn_fastgen_run_wide', trunc)
     coop = None
     if net.fastgen_wide_coop and not net._gen_launch_failed.get('coop'):
         if 'coop' not in g:
@@ -479,10 +502,10 @@ def _run_wide(net, g, samples_io, args):
         # an expired wait: queues, cursors and samples are restored and the
         # single workgroup, which always completes, repeats the run
         snap = [(t, t.clone()) for t in (g['state'], g['cursors'], samples_io)]
-        _lib.call('wn_fastgen_run_wide', *args, _lib.ptr(coop), _lib.stream())
+        _lib.call(name, *args, _lib.ptr(coop), *targs, _lib.stream())
         if not _expired(net, 'coop', coop, snap):
             return
-    _lib.call('wn_fastgen_run_wide', *args, None, _lib.stream())
+    _lib.call(name, *args, None, *targs, _lib.stream())
 
 
 def _run_persistent(net, g, common, tail, io, iob, n_steps, lc=None):
@@ -539,7 +562,8 @@ def predict_proba_incremental(net, waveform, global_condition, push, lc=None):
 
 
 def generate(net, num_samples, seed_samples, temperature, global_condition,
-             seed, return_proba_every, lc=None):
+             seed, return_proba_every, lc=None, top_k=None, top_p=None):
+    trunc = sampling.resolve(top_k, top_p, net.Q)
     net._check_supported()
     if net.filter_width > 2 or net.scalar_input:
         raise NotImplementedError('fast generation needs filter_width 2 '
@@ -561,7 +585,8 @@ def generate(net, num_samples, seed_samples, temperature, global_condition,
                                   None if lc is None else lc[:n_given - 1]),
                     functools.partial(run, net, temperature, seed,
                                       global_condition,
-                                      multi_cu=net.fastgen_multi_cu), lc)
+                                      multi_cu=net.fastgen_multi_cu,
+                                      trunc=trunc), lc)
     return (io, proba) if pe > 0 else io
 
 
@@ -585,13 +610,15 @@ def prime(net, codes, global_condition, lc=None):
 
 
 def continue_generation(net, num_samples, last_sample, temperature,
-                        global_condition, seed, lc=None):
+                        global_condition, seed, lc=None, top_k=None,
+                        top_p=None):
+    trunc = sampling.resolve(top_k, top_p, net.Q)
     net._check_supported()
     n = int(num_samples)
     io = torch.zeros(n + 1, dtype=torch.int32, device=net.device)
     io[0] = int(last_sample)
     run(net, temperature, seed, global_condition, io, 1, n, None, 1,
-        multi_cu=net.fastgen_multi_cu, lc=lc)
+        multi_cu=net.fastgen_multi_cu, lc=lc, trunc=trunc)
     return io[1:]
 
 
@@ -702,7 +729,7 @@ def batch_reset(net, g):
 
 
 def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
-                  proba_every, gc, lc=None):
+                  proba_every, gc, lc=None, trunc=_NO_TRUNC):
     """Everything n_steps batched steps need before the first: the args of
     wn_fastgen_batch_step (no stream) and the buffers batch_complete reads.
     lc (LC models): rows [B or 1, n_steps, Lc]; the result then holds the
@@ -717,7 +744,7 @@ def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
         ring.fill(*ring.plan[0])
     g['seeds'].copy_(torch.from_numpy(seeds))
     iob, pb = _stage(net, g, io, n_given, n_steps, temperature, proba,
-                     proba_every)
+                     proba_every, trunc=trunc)
     # past-tap pre-activations of the first step (every step then leaves
     # the next step's behind)
     pre_args = (_lib.ptr(net._layer_block(net.params, 0)), net.layer_stride,
@@ -752,12 +779,12 @@ def batch_complete(net, g, prep, io, proba, n_steps):
 
 
 def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
-               proba_every, lc=None):
+               proba_every, lc=None, trunc=_NO_TRUNC):
     # n_steps lock-step steps of all B streams on io [B, n_steps + 1]: five
     # kernels per step, captured into a hipGraph once and replayed (LC: in
     # chunks, the ring filled before each)
     prep = batch_prepare(net, g, io, n_given, n_steps, temperature, seeds,
-                         proba, proba_every, gc, lc)
+                         proba, proba_every, gc, lc, trunc)
     args, ring = prep['args'], prep['ring']
     if ring is None:
         _replay_steps(net, g, args, lambda: _lib.call(
@@ -773,7 +800,10 @@ def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
 
 
 def generate_batch(net, num_samples, seeds, seed_samples, temperature,
-                   global_condition, return_proba_every, lc=None):
+                   global_condition, return_proba_every, lc=None, top_k=None,
+                   top_p=None):
+    trunc = sampling.resolve(top_k, top_p, net.Q)
+
     def per_stream(B):
         codes = _batch_codes(net, seed_samples, B)
         if not net.Lc and lc is None:
@@ -812,13 +842,16 @@ def generate_batch(net, num_samples, seeds, seed_samples, temperature,
         g['steps'] = n0
     pe = int(return_proba_every)
     proba = _seeded(net, out, n_given, n, pe, prime, functools.partial(
-        _batch_run, net, g, temperature, sd, gc), lc)
+        _batch_run, net, g, temperature, sd, gc, trunc=trunc), lc)
     return (out, proba) if pe > 0 else out
 
 
 def continue_generation_batch(net, num_samples, last_samples, seeds,
                               temperature, global_condition,
-                              return_proba_every, lc=None):
+                              return_proba_every, lc=None, top_k=None,
+                              top_p=None):
+    trunc = sampling.resolve(top_k, top_p, net.Q)
+
     def per_stream(B):
         last = _batch_last(last_samples, B)
         if not net.Lc and lc is None:
@@ -838,6 +871,6 @@ def continue_generation_batch(net, num_samples, last_samples, seeds,
     io[:, 0] = torch.from_numpy(last).to(net.device)
     pe = int(return_proba_every)
     proba = _seeded(net, io, 1, n, pe, None,
-                    functools.partial(_batch_run, net, g, temperature, sd, gc),
-                    lc)
+                    functools.partial(_batch_run, net, g, temperature, sd, gc,
+                                      trunc=trunc), lc)
     return (io[:, 1:], proba) if pe > 0 else io[:, 1:]

@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from . import fastgen
 from . import local_condition as lcond
+from . import sampling
 from . import train_pass
 from . import workspace
 from .ops import mu_law_encode, mu_law_decode, mu_law_tables
@@ -982,7 +983,7 @@ class WaveNetModel(object):
 
     def generate(self, num_samples, seed_samples=None, temperature=1.0,
                  global_condition=None, seed=0, return_proba_every=0, *,
-                 local_condition=None):
+                 local_condition=None, top_k=None, top_p=None):
         """The whole generate.py:195-241 loop on the device: prime with
         `seed_samples` (int codes; default one random-free seed 128 as in
         test_model.py:63), then draw `num_samples` samples with temperature.
@@ -992,7 +993,14 @@ class WaveNetModel(object):
         local_condition (LC models only, required there): float
         [len(seed) + num_samples - 1, Lc], row i beside code i of the result
         (it conditions the prediction of code i + 1).  The generator is
-        reset internally (reset_generator itself refuses LC models)."""
+        reset internally (reset_generator itself refuses LC models).
+
+        top_k, top_p: truncate every draw to the top_k most probable codes
+        and / or the top_p nucleus of the tempered distribution (the rule:
+        wavenet/sampling.py).  Per call, not remembered; None, top_k >= Q and
+        top_p == 1 draw from all codes.  The returned probabilities stay the
+        untruncated softmax."""
+        sampling.check(top_k, top_p)
         lc = None
         if self.Lc or local_condition is not None:
             lc = lcond.fastgen_rows(self, local_condition, 'generate',
@@ -1000,7 +1008,7 @@ class WaveNetModel(object):
                                     - 1)
         return fastgen.generate(self, num_samples, seed_samples, temperature,
                                 global_condition, seed, return_proba_every,
-                                lc)
+                                lc, top_k, top_p)
 
     def prime_generator(self, codes, global_condition=None, *,
                         local_condition=None):
@@ -1025,7 +1033,7 @@ class WaveNetModel(object):
 
     def continue_generation(self, num_samples, last_sample, temperature=1.0,
                             global_condition=None, seed=0, *,
-                            local_condition=None):
+                            local_condition=None, top_k=None, top_p=None):
         """Draw `num_samples` more samples after `generate` (the queues stay
         on the device; `last_sample` is the last code drawn so far, which has
         not been pushed yet).  Returns the new int32 codes.
@@ -1033,16 +1041,21 @@ class WaveNetModel(object):
         local_condition (LC models only, required there): float
         [num_samples, Lc]; row 0 sits beside `last_sample`, row k beside new
         code k - 1.  generate(a) then continue_generation(b) on consecutive
-        rows is the process of one generate(a + b)."""
+        rows is the process of one generate(a + b).
+
+        top_k, top_p: as generate's, for this call only (a truncated
+        generate does not make its continuation truncated)."""
+        sampling.check(top_k, top_p)
         lc = lcond.fastgen_rows(self, local_condition, 'continue_generation',
                                 int(num_samples))
         return fastgen.continue_generation(self, num_samples, last_sample,
                                            temperature, global_condition, seed,
-                                           lc)
+                                           lc, top_k, top_p)
 
     def generate_batch(self, num_samples, seeds, seed_samples=None,
                        temperature=1.0, global_condition=None,
-                       return_proba_every=0, *, local_condition=None):
+                       return_proba_every=0, *, local_condition=None,
+                       top_k=None, top_p=None):
         """`generate` for B = len(seeds) independent streams stepped in lock
         step (1 <= B <= 256).  Stream b draws with seeds[b] under generate()'s
         counter rule, so it is the same random process as
@@ -1054,18 +1067,23 @@ class WaveNetModel(object):
 
         local_condition (LC models only, required there): float
         [B, n + num_samples - 1, Lc] (n seed codes per stream), or
-        [n + num_samples - 1, Lc] shared by all streams; rows as generate's."""
+        [n + num_samples - 1, Lc] shared by all streams; rows as generate's.
+
+        top_k, top_p: as generate's; one setting for all streams."""
+        sampling.check(top_k, top_p)
         # (the rows are checked in _batch_args's order, beside the seed codes)
         if self.Lc and local_condition is None:
             lcond.refuse_fastgen(self, 'generate_batch')
         return fastgen.generate_batch(self, num_samples, seeds, seed_samples,
                                       temperature, global_condition,
-                                      return_proba_every, local_condition)
+                                      return_proba_every, local_condition,
+                                      top_k, top_p)
 
     def continue_generation_batch(self, num_samples, last_samples, seeds,
                                   temperature=1.0, global_condition=None,
                                   return_proba_every=0, *,
-                                  local_condition=None):
+                                  local_condition=None, top_k=None,
+                                  top_p=None):
         """Draw `num_samples` more samples for every stream of the last
         generate_batch call (the queues stay on the device; last_samples[b]
         is stream b's last code so far, not yet pushed).  Returns int32
@@ -1073,9 +1091,13 @@ class WaveNetModel(object):
 
         local_condition (LC models only, required there): float
         [B, num_samples, Lc] or [num_samples, Lc], rows as
-        continue_generation's."""
+        continue_generation's.
+
+        top_k, top_p: as generate's, for this call only."""
+        sampling.check(top_k, top_p)
         if self.Lc and local_condition is None:
             lcond.refuse_fastgen(self, 'continue_generation_batch')
         return fastgen.continue_generation_batch(
             self, num_samples, last_samples, seeds, temperature,
-            global_condition, return_proba_every, local_condition)
+            global_condition, return_proba_every, local_condition, top_k,
+            top_p)

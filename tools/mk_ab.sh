@@ -18,6 +18,10 @@ mkdir -p $PK/build/ab $S/base
 rm -f $PK/build/ab/lib_*.so
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC"
 git show $REV:$PK/csrc/wn_common.h > $S/base/wn_common.h
+# (.inc: kernel bodies a source includes, as of REV beside the base sources)
+for I in $(git ls-tree --name-only $REV $PK/csrc/ | grep '\.inc$' || true); do
+  git show $REV:$I > $S/base/$(basename $I)
+done
 OTHERS=$(ls $PK/build/*.o)
 BASE= NEW=
 for F in "$@"; do
