@@ -24,6 +24,11 @@ learned network (`upsample_local_condition`) instead of by repetition; the
 flows above then run on those rows.  --lc_context P (a model trained with
 train.py --lc_context P) applies the checkpoint's frame-context convolution in
 front of that upsampler.
+--lc_wav in.wav takes the place of --lc_path (copy synthesis): the features
+are the log-mel front end's (wavenet/features.py) of that wav, computed on the
+device with the checkpoint's 'lc_features' settings (train.py --lc_features)
+or the --lc_features flags; one sample is generated per sample of the wav, or
+--samples of them when that is given and fewer.
 """
 from __future__ import division
 from __future__ import print_function
@@ -39,7 +44,8 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import local_condition, sampling, tf_checkpoint  # noqa: E402
+from wavenet import features, local_condition, sampling  # noqa: E402
+from wavenet import tf_checkpoint  # noqa: E402
 
 SAMPLES = 16000
 TEMPERATURE = 1.0
@@ -86,7 +92,9 @@ def get_arguments(argv=None):
     p = argparse.ArgumentParser(description='WaveNet generation script')
     p.add_argument('checkpoint', type=str,
                    help='Which model checkpoint to generate from')
-    p.add_argument('--samples', type=int, default=SAMPLES)
+    p.add_argument('--samples', type=int, default=None,
+                   help='samples to generate (default %d; with --lc_wav: '
+                   'the length of that wav)' % SAMPLES)
     p.add_argument('--temperature', type=_ensure_positive_float,
                    default=TEMPERATURE)
     p.add_argument('--top_k', type=_top_k, default=None,
@@ -133,7 +141,29 @@ def get_arguments(argv=None):
     p.add_argument('--use_ema', type=_str_to_bool, default=False,
                    help='generate from the checkpoint\'s exponential moving '
                    'average of the weights (train.py --ema_decay)')
+    p.add_argument('--lc_wav', type=str, default=None,
+                   help='local conditioning from a wav: its log-mel '
+                   'features, computed on the device, take the place of '
+                   '--lc_path (not both)')
+    p.add_argument('--lc_channels', type=int, default=None,
+                   help='with --lc_wav: the number of mels (default: the '
+                   'checkpoint\'s)')
+    features.add_cli_flags(
+        p, '  With --lc_wav; default: the checkpoint\'s \'lc_features\' '
+        '(train.py --lc_features), whose settings the other --lc_* flags '
+        'default to.')
     a = p.parse_args(argv)
+    if a.lc_wav is not None and a.lc_path is not None:
+        p.error('give either --lc_wav or --lc_path, not both')
+    if a.lc_wav is None:
+        for flag in ['--lc_features'] * (a.lc_features == 'mel') + \
+                features.cli_flags_given(a):
+            p.error('%s needs --lc_wav' % flag)
+    elif a.lc_features == 'none':
+        p.error('--lc_wav needs a front end, not --lc_features none')
+    a.samples_given = a.samples is not None
+    if a.samples is None:
+        a.samples = SAMPLES
     if a.gc_ids is not None:
         a.gc_ids = [int(v) for v in a.gc_ids.split(',') if v.strip()]
         if not a.gc_ids:
@@ -226,6 +256,16 @@ def open_ema_checkpoint(path):
     return ckpt, None
 
 
+def stored_lc_features(path, ckpt=None):
+    """The 'lc_features' entry train.py --lc_features wrote into the
+    checkpoint at `path` (`ckpt` where the caller holds it), else None."""
+    if ckpt is None:
+        if tf_checkpoint.checkpoint_format(path) or not os.path.isfile(path):
+            return None
+        ckpt = torch.load(path, map_location='cpu')
+    return ckpt.get('lc_features')
+
+
 def restore(net, path, use_ema=False, ckpt=None, check_lc=False):
     """Load the checkpoint at `path` into `net` (evaluate.py shares this):
     the reference's own TensorFlow format, or train.py's torch file `ckpt`
@@ -259,7 +299,28 @@ def main(argv=None):
             print(why)
             return 1
     lc_rows, lc_scales, lc_ctx = None, None, None
-    if args.lc_path is not None:
+    with open(args.wavenet_params, 'r') as f:
+        wavenet_params = json.load(f)
+    n_wav = None
+    if args.lc_wav is not None:
+        # (the hop is the model's: the scales' product, else --lc_hop, whose
+        # default 1 counts as absent, else the checkpoint's)
+        try:
+            hop = local_condition.parse_cli(
+                args.lc_upsample_scales, None if args.lc_hop == 1 else
+                args.lc_hop, args.lc_context)[1]
+            spec = features.spec_from_cli(
+                args, wavenet_params['sample_rate'], args.lc_channels, hop,
+                stored_lc_features(args.checkpoint, ckpt))
+            if spec is None:
+                raise ValueError(
+                    '--lc_wav needs --lc_features mel (the checkpoint names '
+                    'no front end)')
+        except ValueError as e:
+            print(str(e))
+            return 1
+        args.lc_hop = spec.hop
+    if args.lc_path is not None or args.lc_wav is not None:
         if args.fast_generation and not args.lc_fast_generation:
             print('Local conditioning (--lc_path) needs the naive path: '
                   'pass --fast_generation false, or opt in to fast '
@@ -267,7 +328,17 @@ def main(argv=None):
                   '--lc_fast_generation true.')
             return 1
         from wavenet.audio_reader import upsample_lc
-        feats = np.load(args.lc_path)
+        if args.lc_wav is not None:
+            from wavenet.audio_reader import load_wav
+            wav = load_wav(args.lc_wav, wavenet_params['sample_rate'])
+            if wav.shape[0] == 0:
+                print('--lc_wav {} holds no samples'.format(args.lc_wav))
+                return 1
+            n_wav = min(wav.shape[0], args.samples) if args.samples_given \
+                else wav.shape[0]
+            feats = spec(wav[:n_wav]).cpu().numpy()
+        else:
+            feats = np.load(args.lc_path)
         if feats.ndim != 2 or feats.shape[0] == 0 or args.lc_hop <= 0:
             print('--lc_path must hold [frames, channels] features and '
                   '--lc_hop must be positive')
@@ -287,12 +358,12 @@ def main(argv=None):
         else:
             lc_rows = upsample_lc(feats, args.lc_hop,
                                   feats.shape[0] * args.lc_hop)
+        if n_wav is not None:
+            lc_rows = lc_rows[:n_wav]       # (the wav's own length)
         args.samples = lc_rows.shape[0]
     from wavenet import WaveNetModel, mu_law_decode
     started = "{0:%Y-%m-%dT%H-%M-%S}".format(datetime.now())
     logdir = os.path.join(args.logdir, 'generate', started)
-    with open(args.wavenet_params, 'r') as f:
-        wavenet_params = json.load(f)
     net = WaveNetModel(
         batch_size=1,
         dilations=wavenet_params['dilations'],

@@ -918,6 +918,33 @@ int wn_lc_context_wgrad(const float* x, int Fx, const float* dctx, int Fw,
                         int p, int Lc, int B, float* slabs, int num_slabs,
                         long slab_stride, void* stream);
 
+/* ---- log-mel front end (csrc/wn_features.hip): frame-rate local-conditioning
+ * features from the audio, on the LC alignment -- frame f sits beside samples
+ * f * hop .. f * hop + hop - 1 and is centred at c = f * hop + hop / 2:
+ *   frame[j]  = x[c - n_fft / 2 + j] * window[j], j < n_fft; x = 0 outside [0, n[b])
+ *   P[k]      = |DFT(frame)[k]|^2, k < n_bins = n_fft / 2 + 1
+ *   out[f][m] = log(max(sum_k melw[m][k] P[k], floor))        (natural log)
+ * audio float [B][ld] (ld >= T); lengths: device int32 [B] (n[b], clamped to
+ * [0, T] by the kernel, read when it runs) or NULL (n[b] = T); out float
+ * [B][F][n_mels], F = ceil(T / hop); frames f >= ceil(n[b] / hop) are written
+ * as exact zeros.  Nothing at or behind n[b] is read.  The tables (device
+ * float32, built by the host in float64: wavenet/features.py), NC =
+ * ceil(n_bins / 32), MP = n_mels rounded up to 32:
+ *   window [n_fft]
+ *   basis  [NC][n_fft][64]: row j of chunk c holds cos(2 pi j k / n_fft) for
+ *          the bins k = 32 c .. 32 c + 31, then sin(...) for the same bins;
+ *          zeros for k >= n_bins
+ *   melw   [32 NC][MP]: melw[k][m], the filterbank transposed, zero padded
+ * n_fft a multiple of 64 in [64, 2048], 1 <= hop <= n_fft, 1 <= n_mels <= 128,
+ * floor > 0, 1 <= B <= 65535, 1 <= T <= 2^30 (else WN_ERR_BAD_SHAPE); basis,
+ * melw, out 16-byte, the others 4-byte aligned (else WN_ERR_MISALIGNED).  No
+ * atomics, one summation order: a frame's bits depend on its own n_fft
+ * samples and the tables only -- not on B, the other clips or its position. */
+int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths,
+               const float* window, const float* basis, const float* melw,
+               int n_fft, int hop, int n_bins, int n_mels, float floor_,
+               float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

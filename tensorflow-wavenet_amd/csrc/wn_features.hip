@@ -1,0 +1,267 @@
+// Log-mel front end (wavenet/features.py states the rule; tests/mel_ref.py
+// restates it in float64 numpy): frame-rate local-conditioning features from
+// the audio itself, aligned to the LC convention -- frame f sits beside the
+// samples f * hop .. f * hop + hop - 1 and is centred at f * hop + hop / 2.
+//
+//   frame[j]  = x[f * hop + hop / 2 - n_fft / 2 + j] * window[j]   (x = 0 outside [0, n))
+//   P[k]      = |DFT(frame)[k]|^2,  k = 0 .. n_fft / 2
+//   out[f][m] = log(max(sum_k melw[m][k] P[k], floor))
+//
+// One workgroup owns a tile of 32 consecutive frames of one clip.  The
+// 31 * hop + n_fft samples the tile touches are staged into LDS once (zeros
+// outside the clip), the DFT is a fp32 MFMA contraction of the windowed
+// frames with the cos | sin basis, computed transposed as everywhere in this
+// directory (wn_common.h): bins on the M axis, frames on the N axis, so an
+// accumulator [32 bins][32 frames] is, after re^2 + im^2, directly the B
+// operand of the second contraction with that chunk of the mel filterbank.
+// The power spectrum never leaves the registers.
+//
+// The eight waves split the 32-bin chunks (chunk c -> wave c % 8); a wave
+// streams its chunk's basis rows through a wave-private LDS ring in pieces of
+// 16 samples, and keeps a [n_mels][32 frames] accumulator over its chunks.
+// The waves' accumulators are added in wave order through LDS -- no atomics,
+// one summation order per (n_fft, n_mels) -- and the epilogue applies floor
+// and log and writes the tile's rows, contiguous in `out`, with 16-byte
+// stores.  Every MFMA column is one frame: a frame's bits depend on its own
+// samples and the tables only, not on its position in the tile, the batch
+// size or the other clips.
+//
+// LDS banks: lane i of a half-wave reads frame i's sample, hop floats further
+// per lane -- one bank for all 32 lanes at an even hop.  The staged samples are
+// therefore laid out with one pad float after every `hop` samples when hop is
+// even: the lane stride hop + pad is odd and the 32 lanes of a ds_read_b32
+// group hit 32 different banks.  A sample's slot is r + pad * (r / hop); the
+// window table carries that offset for j beside the window value.
+#include "wn_common.h"
+
+#define MEL_TF 32                  // frames per tile
+#define MEL_WAVES 8
+#define MEL_KC 16                  // samples per basis piece
+#define MEL_SLAB (MEL_KC * 64)     // floats of a piece: [16][cos 32 | sin 32]
+#define MEL_RING (MEL_WAVES * 2 * MEL_SLAB)
+#define MEL_STAGE_MAX 16384        // floats of staged samples (64 KiB)
+#define MEL_MAX_FFT 2048
+#define MEL_MAX_MELS 128
+
+struct MelArgs {
+  const float* audio;
+  long ld;
+  const int32_t* lengths;
+  const float* window;
+  const float* basis;
+  const float* melw;
+  float* out;
+  int T, F, n_fft, hop, NC, n_mels, MP, pad;
+  float floor_;
+};
+
+// STAGE: the tile's samples fit the LDS budget (else they are read from
+// memory, the same values); MB = padded mels / 32
+template <bool STAGE, int MB>
+__global__ __launch_bounds__(MEL_WAVES * 64) void melspec_kernel(MelArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float mel_lds[];
+  float* ring = mel_lds;                      // later: the waves' sum [32][MP + 4]
+  float2* tbl = reinterpret_cast<float2*>(mel_lds + MEL_RING);   // [n_fft] {window, slot}
+  float* stage = mel_lds + MEL_RING + 2 * a.n_fft;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = lane & 31, h = lane >> 5;
+  const int b = blockIdx.y, f0 = blockIdx.x * MEL_TF;
+  int n = a.lengths ? a.lengths[b] : a.T;
+  n = n < 0 ? 0 : (n > a.T ? a.T : n);
+  const int nF = (n + a.hop - 1) / a.hop;     // the clip's real frames
+  const int rows = min(MEL_TF, a.F - f0);
+  const int nreal = max(0, min(rows, nF - f0));
+  float* outp = a.out + ((long)b * a.F + f0) * a.n_mels;
+  const int ntot = rows * a.n_mels;
+  if (nreal == 0) {                           // (workgroup-uniform)
+    for (int e = tid; e < ntot; e += MEL_WAVES * 64) outp[e] = 0.f;
+    return;
+  }
+  const float* clip = a.audio + (long)b * a.ld;
+  const long s0 = (long)f0 * a.hop + a.hop / 2 - a.n_fft / 2;   // the tile's first sample
+
+  for (int j = tid; j < a.n_fft; j += MEL_WAVES * 64) {
+    float2 t;
+    t.x = a.window[j];
+    t.y = __int_as_float(STAGE ? j + a.pad * (j / a.hop) : j);
+    tbl[j] = t;
+  }
+  if (STAGE) {
+    const int total = (MEL_TF - 1) * a.hop + a.n_fft;
+    for (int r = tid; r < total; r += MEL_WAVES * 64) {
+      const long g = s0 + r;
+      float v = 0.f;
+      if (g >= 0 && g < n) v = clip[g];
+      stage[r + a.pad * (r / a.hop)] = v;
+    }
+  }
+  __syncthreads();
+
+  f32x16 macc[MB];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) macc[mb] = frag_zero();
+  float* myring = ring + wave * 2 * MEL_SLAB;
+  const int nk = a.n_fft / MEL_KC;
+  const int xoff = i * (a.hop + a.pad);       // frame i's first staged slot
+  const long gi = s0 + (long)i * a.hop;       // ... first sample
+
+  for (int c = wave; c < a.NC; c += MEL_WAVES) {
+    f32x16 re = frag_zero(), im = frag_zero();
+    const f32x4* src = reinterpret_cast<const f32x4*>(a.basis + (long)c * a.n_fft * 64) + lane;
+    f32x4 pf[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) pf[q] = src[q * 64];
+    for (int kc = 0; kc < nk; ++kc) {
+      float* sl = myring + (kc & 1) * MEL_SLAB;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(sl + (q * 64 + lane) * 4) = pf[q];
+      __builtin_amdgcn_wave_barrier();
+      if (kc + 1 < nk) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pf[q] = src[(kc + 1) * 256 + q * 64];
+      }
+      const int j0 = kc * MEL_KC;
+#pragma unroll
+      for (int s = 0; s < MEL_KC / 2; ++s) {
+        const int jj = j0 + 2 * s + h;
+        const float2 t = tbl[jj];
+        float x;
+        if (STAGE) {
+          x = stage[xoff + __float_as_int(t.y)];
+        } else {
+          const long g = gi + jj;
+          x = 0.f;
+          if (g >= 0 && g < n) x = clip[g];
+        }
+        const float xw = x * t.x;
+        const float* row = sl + (2 * s + h) * 64 + i;
+        re = __builtin_amdgcn_mfma_f32_32x32x2f32(row[0], xw, re, 0, 0, 0);
+        im = __builtin_amdgcn_mfma_f32_32x32x2f32(row[32], xw, im, 0, 0, 0);
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+    // P = re^2 + im^2 is the fragment [bin 8(r>>2) + 4h + (r&3)][frame i]:
+    // the B operand of macc[mel][frame] += melw[bin][mel] P[bin][frame]
+    const float* mw = a.melw + (long)(32 * c + 4 * h) * a.MP + i;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float p = __builtin_fmaf(im[r], im[r], re[r] * re[r]);
+      const float* mr = mw + (8 * (r >> 2) + (r & 3)) * a.MP;
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+        macc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(mr[32 * mb], p, macc[mb], 0, 0, 0);
+    }
+  }
+
+  // the waves' sums, added in wave order in place of the ring
+  const int ldr = a.MP + 4;
+  float* red = ring;
+  __syncthreads();
+  for (int w = 0; w < MEL_WAVES; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          f32x4* p = reinterpret_cast<f32x4*>(red + i * ldr + 32 * mb + 8 * q + 4 * h);
+          f32x4 v = {macc[mb][4 * q], macc[mb][4 * q + 1], macc[mb][4 * q + 2],
+                     macc[mb][4 * q + 3]};
+          if (w > 0) v += *p;
+          *p = v;
+        }
+    }
+    __syncthreads();
+  }
+
+  // floor, log; rows at or behind the clip's last frame are exact zeros
+  const float fl = a.floor_;
+  if ((a.n_mels & 3) == 0) {
+    for (int e = tid * 4; e < ntot; e += MEL_WAVES * 64 * 4) {
+      const int f = e / a.n_mels, m = e - f * a.n_mels;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (f < nreal) {
+        v = *reinterpret_cast<const f32x4*>(red + f * ldr + m);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = logf(v[k] < fl ? fl : v[k]);
+      }
+      *reinterpret_cast<f32x4*>(outp + e) = v;
+    }
+  } else {
+    for (int e = tid; e < ntot; e += MEL_WAVES * 64) {
+      const int f = e / a.n_mels, m = e - f * a.n_mels;
+      float v = 0.f;
+      if (f < nreal) {
+        v = red[f * ldr + m];
+        v = logf(v < fl ? fl : v);
+      }
+      outp[e] = v;
+    }
+  }
+}
+
+template <bool STAGE>
+static int mel_launch(const MelArgs& a, int B, size_t lds, hipStream_t s) {
+  const dim3 grid((unsigned)((a.F + MEL_TF - 1) / MEL_TF), (unsigned)B);
+#define LAUNCH(MB)                                                              \
+  {                                                                             \
+    if (hipFuncSetAttribute((const void*)melspec_kernel<STAGE, MB>,             \
+                            hipFuncAttributeMaxDynamicSharedMemorySize,         \
+                            (int)lds) != hipSuccess)                            \
+      return WN_ERR_LAUNCH;                                                     \
+    hipLaunchKernelGGL((melspec_kernel<STAGE, MB>), grid, dim3(MEL_WAVES * 64), \
+                       lds, s, a);                                              \
+  }
+  switch (a.MP / 32) {
+    case 1: LAUNCH(1) break;
+    case 2: LAUNCH(2) break;
+    case 3: LAUNCH(3) break;
+    default: LAUNCH(4) break;
+  }
+#undef LAUNCH
+  return wn_check_launch();
+}
+
+extern "C" {
+
+int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths,
+               const float* window, const float* basis, const float* melw,
+               int n_fft, int hop, int n_bins, int n_mels, float floor_,
+               float* out, void* stream) {
+  if (!audio || !window || !basis || !melw || !out) return WN_ERR_NULL;
+  if (n_fft < 64 || n_fft > MEL_MAX_FFT || n_fft % 64 != 0 || hop < 1 ||
+      hop > n_fft || n_bins != n_fft / 2 + 1 || n_mels < 1 ||
+      n_mels > MEL_MAX_MELS || !(floor_ > 0.f) || !(floor_ < INFINITY) ||
+      B < 1 || B > 65535 || T < 1 || T > (1 << 30) || ld < T)
+    return WN_ERR_BAD_SHAPE;
+  if (!wn_aligned16(basis) || !wn_aligned16(melw) || !wn_aligned16(out) ||
+      (reinterpret_cast<uintptr_t>(audio) & 3u) ||
+      (reinterpret_cast<uintptr_t>(window) & 3u) ||
+      (reinterpret_cast<uintptr_t>(lengths) & 3u))
+    return WN_ERR_MISALIGNED;
+  MelArgs a;
+  a.audio = audio;
+  a.ld = ld;
+  a.lengths = lengths;
+  a.window = window;
+  a.basis = basis;
+  a.melw = melw;
+  a.out = out;
+  a.T = T;
+  a.F = (T + hop - 1) / hop;
+  a.n_fft = n_fft;
+  a.hop = hop;
+  a.NC = (n_bins + 31) / 32;
+  a.n_mels = n_mels;
+  a.MP = (n_mels + 31) / 32 * 32;
+  a.pad = (hop & 1) ? 0 : 1;
+  a.floor_ = floor_;
+  const long total = (long)(MEL_TF - 1) * hop + n_fft;
+  const long nstage = total + a.pad * ((total - 1) / hop) + 1;
+  const bool staged = nstage <= MEL_STAGE_MAX;
+  const size_t lds = sizeof(float) * (size_t)(MEL_RING + 2 * n_fft + (staged ? nstage : 0));
+  return staged ? mel_launch<true>(a, B, lds, (hipStream_t)stream)
+                : mel_launch<false>(a, B, lds, (hipStream_t)stream);
+}
+
+}  // extern "C"

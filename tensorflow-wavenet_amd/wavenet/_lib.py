@@ -198,6 +198,10 @@ SIGNATURES = {
     'wn_lc_context_wgrad_slabs': (c_int, [c_long, c_int]),
     'wn_lc_context_wgrad': (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P,
                                     c_int, c_long, P]),
+    # log-mel front end: audio, ld, B, T, lengths, window, basis, melw, n_fft,
+    # hop, n_bins, n_mels, floor, out, stream
+    'wn_melspec': (c_int, [P, c_long, c_int, c_int, P, P, P, P, c_int, c_int,
+                           c_int, c_int, c_float, P, P]),
 }
 for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
               'wn_fastgen_persist', 'wn_fastgen_batch_pre',

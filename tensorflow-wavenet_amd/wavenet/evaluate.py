@@ -122,6 +122,15 @@ class ValidationSet(object):
             yield audio, lengths, gc, lc
 
 
+def with_features(net, spec, batches):
+    """`batches` of an audio-only ValidationSet with the local conditioning
+    computed on the device from each batch's own audio (features.MelSpec
+    `spec`): frames at offset 0 for an upsampler model, else rows."""
+    for audio, lengths, gc, _ in batches:
+        lc = net.local_condition_from_audio(spec, audio, lengths)
+        yield audio, lengths, gc, ((lc, 0) if net.lc_up else lc)
+
+
 def totals(net, batches, max_batches=None):
     """float64 [4] on the device: (sum of nll, targets, hits, clips) over
     net.score of every batch (at most max_batches of them).  No host wait."""

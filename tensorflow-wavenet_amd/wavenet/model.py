@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from . import fastgen
+from . import features
 from . import local_condition as lcond
 from . import sampling
 from . import train_pass
@@ -60,19 +61,7 @@ def check_lengths(lengths, loss_denominator, B, T, what):
         if loss_denominator is not None:
             raise ValueError('%s: loss_denominator needs lengths' % what)
         return None
-    if isinstance(lengths, torch.Tensor):
-        lengths = lengths.detach().cpu().numpy()
-    n = np.asarray(lengths)
-    if n.dtype == object or n.dtype == np.bool_ or \
-            not np.issubdtype(n.dtype, np.integer):
-        raise ValueError('%s: lengths must be %d integers (dtype %s)'
-                         % (what, B, n.dtype))
-    if n.shape != (B,):
-        raise ValueError('%s: lengths must have shape [%d], got %s'
-                         % (what, B, list(n.shape)))
-    if (n < 1).any() or (n > T).any():
-        raise ValueError('%s: lengths must lie in [1, T] = [1, %d], got %s'
-                         % (what, T, n.tolist()))
+    n = features.check_lengths(lengths, B, T, what)
     den = float(n.astype(np.int64).sum())
     if loss_denominator is not None:
         d = loss_denominator
@@ -82,7 +71,7 @@ def check_lengths(lengths, loss_denominator, B, T, what):
             raise ValueError('%s: loss_denominator must be a positive finite '
                              'number, got %r' % (what, d))
         den = float(d)
-    return n.astype(np.int32), den
+    return n, den
 
 
 def _n_codes(codes):
@@ -668,6 +657,17 @@ class WaveNetModel(object):
         training forward: a row's bits depend on its frame, its slot and the
         weights only.  The rows feed predict_proba and fast generation."""
         return lcond.upsample(self, frames, num_samples, offset)
+
+    def local_condition_from_audio(self, spec, audio, lengths=None):
+        """What this model's LC inputs take, computed from the audio by the
+        log-mel front end `spec` (a features.MelSpec with n_mels = the
+        model's LC channels): audio [B, T] or [T], lengths as for `loss`.
+        A model built with local_condition_upsample_scales gets the frames
+        [B, F, Lc], F = ceil(T / hop) (spec.hop must be the model's hop):
+        pass them as local_condition_batch with local_condition_offset=0.
+        A repetition-row model gets rows [B, T, Lc]: frame t // spec.hop
+        beside sample t.  A device tensor, no host synchronisation."""
+        return features.local_condition_from_audio(self, spec, audio, lengths)
 
     def _layer_block(self, flat, l):
         o, _ = self.segments['layers']

@@ -1,0 +1,90 @@
+"""Write the log-mel features of every wav under DIR beside it, `<clip>.npy`
+[frames, lc_channels], with the device kernel (wavenet/features.py): the
+files train.py --lc_channels, evaluate.py and generate.py --lc_path read.
+
+    python tools/make_lc_features.py DIR --sample_rate 16000 \\
+        --lc_channels 80 --lc_hop 256 [--silence_threshold 0.3]
+        [--lc_n_fft 1024 --lc_win_length 1024 --lc_fmin 0 --lc_fmax 8000]
+
+Every file is loaded and trimmed by AudioReader's own functions.  The
+features are those of the utterance the reader keeps, samples [lo, hi) of the
+file, with zeros around it, stored at the file's frame positions: frame f of
+the .npy sits beside the file's samples f * hop .. f * hop + hop - 1, and
+frames that lie wholly outside the utterance are zeros.  The trimming's start
+is a multiple of 512, so where the hop divides 512 the frames of a whole
+utterance are exactly what train.py --lc_features mel computes for it.  Unlike
+there, a piece cut by --sample_size keeps the context of its file.
+Give --silence_threshold as to train.py (its default is train.py's).
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
+
+import numpy as np  # noqa: E402
+from wavenet import audio_reader as ar, features  # noqa: E402
+
+SILENCE_THRESHOLD = 0.3        # train.py's
+
+
+def get_arguments(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    p.add_argument('directory', metavar='DIR',
+                   help='searched recursively for *.wav')
+    p.add_argument('--sample_rate', type=int, required=True,
+                   help='the model\'s sample rate (wavenet_params.json)')
+    p.add_argument('--lc_channels', type=int, required=True,
+                   help='the number of mels')
+    p.add_argument('--lc_hop', type=int, required=True,
+                   help='audio samples per feature frame')
+    p.add_argument('--silence_threshold', type=float,
+                   default=SILENCE_THRESHOLD)
+    features.add_cli_flags(p, '  (Implied here.)')
+    args = p.parse_args(argv)
+    if args.lc_features == 'none':
+        p.error('--lc_features none: nothing to write')
+    args.lc_features = 'mel'
+    return args
+
+
+def file_features(spec, audio, silence_threshold):
+    """float32 [ceil(len(audio) / hop), n_mels] of one loaded file."""
+    n, hop = audio.shape[0], spec.hop
+    out = np.zeros((spec.num_frames(n), spec.n_mels), np.float32)
+    lo, hi = 0, n
+    if silence_threshold is not None:
+        lo, hi = (int(v) for v in ar.trim_bounds(audio, silence_threshold))
+    hi = min(hi, n)
+    if hi <= lo:
+        return out                      # (only silence: the reader skips it)
+    kept = np.zeros(hi, np.float32)
+    kept[lo:] = audio[lo:hi]
+    f0, f1 = lo // hop, spec.num_frames(hi)
+    out[f0:f1] = spec(kept).cpu().numpy()[f0:]
+    return out
+
+
+def main(argv=None):
+    args = get_arguments(argv)
+    try:
+        spec = features.spec_from_cli(args, args.sample_rate,
+                                      args.lc_channels, args.lc_hop)
+    except ValueError as e:
+        print(str(e))
+        return 1
+    files = ar.find_files(args.directory)
+    if not files:
+        print("No audio files found in '{}'.".format(args.directory))
+        return 1
+    for f in files:
+        feats = file_features(spec, ar.load_wav(f, args.sample_rate),
+                              args.silence_threshold)
+        np.save(ar.lc_path_of(f), feats)
+        print('{}: {} frames'.format(ar.lc_path_of(f), feats.shape[0]))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import local_condition, tf_checkpoint  # noqa: E402
+from wavenet import features, local_condition, tf_checkpoint  # noqa: E402
 
 BATCH_SIZE = 1
 DATA_DIRECTORY = './VCTK-Corpus'
@@ -150,7 +150,23 @@ def get_arguments(argv=None):
     p.add_argument('--validate_ema', type=_str_to_bool, default=False,
                    help='Validate the exponential moving average of the '
                         'weights instead of the weights (needs --ema_decay).')
-    return p.parse_args(argv)
+    features.add_cli_flags(
+        p, '  Needs --lc_channels and --lc_hop or --lc_upsample_scales; '
+        'with --mask_padding true the clips\' lengths go to the front end '
+        'too.  The settings are stored in every checkpoint (\'lc_features\') '
+        'and --validation_dir is scored through the same front end.')
+    args = p.parse_args(argv)
+    if args.lc_features == 'mel':
+        if args.lc_channels is None:
+            p.error('--lc_features mel needs --lc_channels (the number of '
+                    'mels)')
+        if args.lc_hop is None and args.lc_upsample_scales is None:
+            p.error('--lc_features mel needs --lc_hop or '
+                    '--lc_upsample_scales (hop = their product)')
+    elif features.cli_flags_given(args):
+        p.error('%s needs --lc_features mel'
+                % features.cli_flags_given(args)[0])
+    return args
 
 
 def validation_flags(args):
@@ -191,15 +207,18 @@ def checkpoint_path(logdir, step):
     return os.path.join(logdir, 'model.ckpt-{}'.format(step))
 
 
-def save(net, logdir, step, optimizer=None):
+def save(net, logdir, step, optimizer=None, lc_features=None):
     """`optimizer`: its step count, slots and shadow go in as 'optimizer'
     and, with EMA weights, the shadow as 'ema_variables' (the keys of
-    'variables')."""
+    'variables').  `lc_features`: the front end's settings
+    (features.checkpoint_entry), stored under 'lc_features'."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
     path = checkpoint_path(logdir, step)
     ckpt = {'variables': net.state_dict(), 'step': step}
+    if lc_features is not None:
+        ckpt['lc_features'] = lc_features
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
         if optimizer.ema_decay is not None:
@@ -376,10 +395,21 @@ def main(argv=None):
     silence_threshold = args.silence_threshold
     gc_enabled = args.gc_channels is not None
     lc_enabled = args.lc_channels is not None
+    # --lc_features: the readers yield audio only, the features of every
+    # batch are computed on the device from the batch itself
+    spec = None
+    try:
+        spec = features.spec_from_cli(args, wavenet_params['sample_rate'],
+                                      args.lc_channels, lc_hop)
+    except ValueError as e:
+        print(str(e))
+        return 1
+    lc_entry = None if spec is None else features.checkpoint_entry(spec)
+    file_lc = None if spec is not None else args.lc_channels
     if args.synthetic:
         reader = SyntheticReader(args.sample_size,
                                  args.gc_cardinality if gc_enabled else None,
-                                 rank=rank, lc_channels=args.lc_channels,
+                                 rank=rank, lc_channels=file_lc,
                                  lc_hop=lc_hop or 1)
     else:
         if lc_enabled and not lc_hop:
@@ -392,7 +422,7 @@ def main(argv=None):
                              sample_size=args.sample_size,
                              silence_threshold=silence_threshold,
                              rank=rank, world=world, seed=rank,
-                             lc_channels=args.lc_channels,
+                             lc_channels=file_lc,
                              lc_hop=lc_hop, lc_frames=lc_scales is not None)
 
     net = WaveNetModel(
@@ -448,7 +478,7 @@ def main(argv=None):
             sample_size=args.sample_size,
             silence_threshold=silence_threshold, gc_enabled=gc_enabled,
             gc_cardinality=reader.gc_category_cardinality,
-            lc_channels=args.lc_channels, lc_hop=lc_hop,
+            lc_channels=file_lc, lc_hop=lc_hop,
             lc_frames=lc_scales is not None, rank=rank, world=world)
     validate_every = args.validate_every or args.checkpoint_every
 
@@ -517,8 +547,10 @@ def main(argv=None):
         swap = ev.parameters_swapped(net, optimizer.ema_flat(net)) \
             if args.validate_ema else contextlib.nullcontext()
         with swap:
-            tot = ev.totals(net, vset.batches(args.batch_size),
-                            args.validation_batches)
+            batches = vset.batches(args.batch_size)
+            if spec is not None:
+                batches = ev.with_features(net, spec, batches)
+            tot = ev.totals(net, batches, args.validation_batches)
         res = ev.summary(ev.sum_over_ranks(tot, net.device))
         if rank == 0:
             print('step {:d} - validation loss = {:.3f}, bits/sample = {:.3f}'
@@ -580,7 +612,9 @@ def main(argv=None):
                     if args.mask_padding else None
                 gc = reader.dequeue_gc(args.batch_size) if gc_enabled else None
                 lc, lc_off = None, 0
-                if lc_scales is not None:
+                if spec is not None:
+                    pass                  # (from the staged batch, below)
+                elif lc_scales is not None:
                     # frames + offsets: the model upsamples on the device
                     lc, lc_off = reader.dequeue_lc_frames(args.batch_size)
                 elif lc_enabled:
@@ -612,6 +646,10 @@ def main(argv=None):
                 # step's kernels, i.e. the host would wait for the device every
                 # step and prepare the next batch while it idles
                 audio = stage_in(audio.reshape(audio.shape[0], -1), step)
+            if spec is not None:
+                # frames (offset 0) for an upsampler model, else rows
+                lc = net.local_condition_from_audio(
+                    spec, audio.reshape(audio.shape[0], -1), lengths)
             trace_step = args.store_metadata and step % 50 == 0
             trace = trace_step and rank == 0
             if trace:
@@ -654,7 +692,7 @@ def main(argv=None):
                     report(*pending)
                     pending = None
             if rank == 0 and step % args.checkpoint_every == 0:
-                save(net, logdir, step, optimizer)
+                save(net, logdir, step, optimizer, lc_entry)
                 last_saved_step = step
                 if args.histograms:
                     # the reference's histogram summaries (model.py:314-325)
@@ -685,7 +723,7 @@ def main(argv=None):
         print()
     finally:
         if rank == 0 and step is not None and step > last_saved_step:
-            save(net, logdir, step, optimizer)
+            save(net, logdir, step, optimizer, lc_entry)
         coord.request_stop()
         coord.join(threads)
         if events:
