@@ -945,6 +945,57 @@ int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths
                int n_fft, int hop, int n_bins, int n_mels, float floor_,
                float* out, void* stream);
 
+/* ---- device-resident training corpus (csrc/wn_corpus.hip; the rule:
+ * wavenet/corpus.py).  The trimmed utterances lie in one device buffer `flat`
+ * [N] float32; utterance u is flat[utt_off[u] .. + utt_len[u]).  A batch is
+ * cut by the kernel, which derives its plan from device tables and scalars
+ * (the "plan" arguments, the same for both entries):
+ *   utt_off int64 [U], utt_len int32 [U]
+ *   item_utt, item_start int32 [P]: item i is a piece of utterance item_utt[i]
+ *          that begins at item_start[i]
+ *   perm int32 [nE][P]: the item orders of the epochs e0 .. e0 + nE - 1
+ *   g0 = step * B: slot j < B is the global slot g = g0 + j of epoch g / P and
+ *          takes the item perm[g / P - e0][g % P]; the epochs g0 / P ..
+ *          (g0 + B - 1) / P must lie in [e0, e0 + nE) (else WN_ERR_BAD_SHAPE)
+ *   size, random, seed: random == 0: n = utt_len - item_start, cut to `size`
+ *          when size > 0; random != 0 (size >= 1): n = min(size, utt_len) and
+ *          start = draw_bits(seed ^ 0x63726f70, g) % (utt_len - size + 1) when
+ *          utt_len > size, else 0 (draw_bits: splitmix64(seed ^ splitmix64(c)))
+ *   n is cut to T.
+ * wn_corpus_gather: audio [B][T] float32, slot j = flat[utt_off + start .. + n)
+ * and exact zeros behind n, whatever audio held.  Nothing outside
+ * [utt_off + start, utt_off + start + n) is read; a table entry that points
+ * outside its table or outside [0, N) makes its slot all zeros.
+ * wn_corpus_gather_frames: the utterances' frame-rate features fr [NF] float32,
+ * utterance u's frames [fr_len[u]][Lc] from frame fr_off[u] (int64 [U]) on,
+ * frame f beside samples f * hop .. f * hop + hop - 1.  Either output may be
+ * NULL, not both:
+ *   frames [B][Fw][Lc]: row r = frame f_lo + r while that is < f_hi, else
+ *          zeros; f_lo = max(0, start / hop - ctx), f_hi = min(fr_len,
+ *          (start + n - 1) / hop + 1 + ctx).  Fw >= wn_corpus_window_frames
+ *          (T, hop, ctx) = (T + hop - 2) / hop + 1 + 2 ctx covers every start.
+ *   rows [B][T][Lc]: row t = frame (start + t) / hop, zeros for t >= n.
+ * B, T, P, U, nE, N, NF >= 1, hop >= 1, ctx >= 0, Lc >= 1 (else
+ * WN_ERR_BAD_SHAPE); flat, fr and the outputs 16-byte aligned, int64 tables
+ * 8-byte, int32 tables 4-byte (else WN_ERR_MISALIGNED).  All checks come
+ * before any launch; wn_corpus_window_frames needs no device (-1: bad
+ * arguments).  Plain 16-byte stores; 16-byte loads where the source index
+ * allows, scalar loads elsewhere; no atomics. */
+long wn_corpus_window_frames(int T, int hop, int ctx);
+int wn_corpus_gather(const float* flat, long N, const int64_t* utt_off,
+                     const int32_t* utt_len, int U, const int32_t* item_utt,
+                     const int32_t* item_start, int P, const int32_t* perm,
+                     long e0, int nE, long g0, int size, int random,
+                     uint64_t seed, float* audio, int B, int T, void* stream);
+int wn_corpus_gather_frames(const float* fr, long NF, const int64_t* fr_off,
+                            const int32_t* fr_len, const int64_t* utt_off,
+                            const int32_t* utt_len, int U,
+                            const int32_t* item_utt, const int32_t* item_start,
+                            int P, const int32_t* perm, long e0, int nE,
+                            long g0, int size, int random, uint64_t seed,
+                            int hop, int ctx, int Lc, float* frames, int Fw,
+                            float* rows, int B, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

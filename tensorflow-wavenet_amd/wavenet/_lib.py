@@ -202,6 +202,19 @@ SIGNATURES = {
     # hop, n_bins, n_mels, floor, out, stream
     'wn_melspec': (c_int, [P, c_long, c_int, c_int, P, P, P, P, c_int, c_int,
                            c_int, c_int, c_float, P, P]),
+    # device-resident corpus.  The plan (13 arguments): utt_off, utt_len, U,
+    # item_utt, item_start, P, perm, e0, nE, g0, size, random, seed.
+    # gather: flat, N, plan, audio, B, T, stream
+    'wn_corpus_window_frames': (c_long, [c_int, c_int, c_int]),
+    'wn_corpus_gather': (c_int, [P, c_long, P, P, c_int, P, P, c_int, P,
+                                 c_long, c_int, c_long, c_int, c_int, c_u64,
+                                 P, c_int, c_int, P]),
+    # frames, NF, fr_off, fr_len, plan, hop, ctx, Lc, frames, Fw, rows, B, T,
+    # stream
+    'wn_corpus_gather_frames': (c_int, [P, c_long, P, P, P, P, c_int, P, P,
+                                        c_int, P, c_long, c_int, c_long,
+                                        c_int, c_int, c_u64, c_int, c_int,
+                                        c_int, P, c_int, P, c_int, c_int, P]),
 }
 for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
               'wn_fastgen_persist', 'wn_fastgen_batch_pre',

@@ -42,6 +42,7 @@ SAMPLE_SIZE = 100000
 L2_REGULARIZATION_STRENGTH = 0
 SILENCE_THRESHOLD = 0.3
 EPSILON = 0.001
+CORPUS_SEED = 0             # --device_corpus: every rank's index, every run
 MOMENTUM = 0.9
 
 
@@ -55,8 +56,9 @@ def get_arguments(argv=None):
     p = argparse.ArgumentParser(description='WaveNet example network')
     p.add_argument('--batch_size', type=int, default=BATCH_SIZE,
                    help='How many wav files to process at once (per GPU).')
-    p.add_argument('--data_dir', type=str, default=DATA_DIRECTORY,
-                   help='The directory containing the VCTK corpus.')
+    p.add_argument('--data_dir', type=str, default=None,
+                   help='The directory containing the VCTK corpus '
+                        '(default: {}).'.format(DATA_DIRECTORY))
     p.add_argument('--store_metadata', type=bool, default=False,
                    help='Store a kernel trace every 50 steps.')
     p.add_argument('--logdir', type=str, default=None,
@@ -155,7 +157,51 @@ def get_arguments(argv=None):
         'with --mask_padding true the clips\' lengths go to the front end '
         'too.  The settings are stored in every checkpoint (\'lc_features\') '
         'and --validation_dir is scored through the same front end.')
+    p.add_argument('--device_corpus', type=_str_to_bool, default=False,
+                   help='Keep the whole trimmed --data_dir on the device and '
+                        'cut every training batch there with a kernel '
+                        '(wavenet/corpus.py): no reader thread, no copy per '
+                        'step.  The order is a pure function of the step, so '
+                        'a resumed run continues the same sequence.  Needs '
+                        '--data_dir; not with --synthetic, nor with '
+                        '--lc_channels read from <clip>.npy files (use '
+                        '--lc_features mel).  Validation is unchanged.')
+    p.add_argument('--crop', choices=['pieces', 'random'], default=None,
+                   help='--device_corpus: pieces (default) cuts every '
+                        'utterance into --sample_size pieces like the '
+                        'reader; random draws one window of --sample_size '
+                        'samples per utterance afresh every epoch.')
+    p.add_argument('--lc_feature_context', choices=['piece', 'utterance'],
+                   default=None,
+                   help='--lc_features mel: piece (default) computes the '
+                        'features of each batch as cut, a piece\'s edges see '
+                        'zeros; utterance (needs --device_corpus true) '
+                        'computes every utterance\'s frames once at load and '
+                        'gives each piece the frames of its place in the '
+                        'utterance.')
     args = p.parse_args(argv)
+    # (--data_dir's default is filled in here, so that "not given" shows)
+    data_dir_given = args.data_dir is not None
+    if not data_dir_given:
+        args.data_dir = DATA_DIRECTORY
+    if args.device_corpus:
+        if not data_dir_given:
+            p.error('--device_corpus true needs --data_dir')
+        if args.synthetic:
+            p.error('--device_corpus true does not go with --synthetic')
+        if args.lc_channels is not None and args.lc_features != 'mel':
+            p.error('--device_corpus true reads no <clip>.npy features: '
+                    '--lc_channels needs --lc_features mel with it')
+        if args.crop == 'random' and not args.sample_size:
+            p.error('--crop random needs --sample_size')
+    elif args.crop is not None:
+        p.error('--crop needs --device_corpus true')
+    if args.lc_feature_context == 'utterance' and not (
+            args.device_corpus and args.lc_features == 'mel'):
+        p.error('--lc_feature_context utterance needs --device_corpus true '
+                'and --lc_features mel')
+    if args.lc_feature_context is not None and args.lc_features != 'mel':
+        p.error('--lc_feature_context needs --lc_features mel')
     if args.lc_features == 'mel':
         if args.lc_channels is None:
             p.error('--lc_features mel needs --lc_channels (the number of '
@@ -207,11 +253,15 @@ def checkpoint_path(logdir, step):
     return os.path.join(logdir, 'model.ckpt-{}'.format(step))
 
 
-def save(net, logdir, step, optimizer=None, lc_features=None):
+def save(net, logdir, step, optimizer=None, lc_features=None,
+         device_corpus=None):
     """`optimizer`: its step count, slots and shadow go in as 'optimizer'
     and, with EMA weights, the shadow as 'ema_variables' (the keys of
     'variables').  `lc_features`: the front end's settings
-    (features.checkpoint_entry), stored under 'lc_features'."""
+    (features.checkpoint_entry), stored under 'lc_features'.
+    `device_corpus`: the settings of --device_corpus (crop, seed,
+    sample_size, lc_feature_context) and the index of the last batch taken
+    ('batch'), stored under 'device_corpus'."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
@@ -219,6 +269,8 @@ def save(net, logdir, step, optimizer=None, lc_features=None):
     ckpt = {'variables': net.state_dict(), 'step': step}
     if lc_features is not None:
         ckpt['lc_features'] = lc_features
+    if device_corpus is not None:
+        ckpt['device_corpus'] = device_corpus
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
         if optimizer.ema_decay is not None:
@@ -250,10 +302,11 @@ def latest_checkpoint(logdir):
     return max(found, key=found.get) if found else None
 
 
-def load(net, logdir, optimizer=None):
+def load(net, logdir, optimizer=None, entries=None):
     """`optimizer`: restored from the checkpoint's 'optimizer' entry when it
     has one (checkpoints written before it existed, and the reference's own,
-    have none: the optimizer then starts afresh, as it always did)."""
+    have none: the optimizer then starts afresh, as it always did).
+    `entries`: a dict that receives the checkpoint's 'device_corpus' entry."""
     print("Trying to restore saved checkpoints from {} ...".format(logdir),
           end="")
     path = latest_checkpoint(logdir) if os.path.isdir(logdir) else None
@@ -272,8 +325,27 @@ def load(net, logdir, optimizer=None):
         net.load_state_dict(ckpt['variables'])
         if optimizer is not None and 'optimizer' in ckpt:
             optimizer.load_state_dict(ckpt['optimizer'], net)
+        if entries is not None and 'device_corpus' in ckpt:
+            entries['device_corpus'] = ckpt['device_corpus']
     print(" Done.")
     return global_step
+
+
+def corpus_first_batch(stored, entry):
+    """--device_corpus: step k of a run takes batch base + k.  A run continued
+    in its logdir continues its step count (base 0).  A new training restored
+    from a checkpoint starts at step 0: it goes on with the batch after the
+    last one of the checkpoint's 'device_corpus' entry `stored` where that
+    has this run's settings `entry`, else it starts the sequence again."""
+    if stored is None:
+        return 0
+    if {k: stored.get(k) for k in entry} != entry:
+        print("  The checkpoint's corpus settings {} differ: the corpus "
+              "starts again.".format(stored))
+        return 0
+    base = int(stored.get('batch', -1)) + 1
+    print('  Corpus batches continue at {}.'.format(base))
+    return base
 
 
 def get_default_logdir(logdir_root):
@@ -406,7 +478,29 @@ def main(argv=None):
         return 1
     lc_entry = None if spec is None else features.checkpoint_entry(spec)
     file_lc = None if spec is not None else args.lc_channels
-    if args.synthetic:
+    corpus = corpus_entry = corpus_lc = None
+    if args.device_corpus:
+        # the corpus on the device replaces the reader and its threads for
+        # the training batches (wavenet/corpus.py)
+        from wavenet.corpus import DeviceCorpus
+        utt_ctx = args.lc_feature_context == 'utterance'
+        try:
+            corpus = reader = DeviceCorpus(
+                args.data_dir, wavenet_params['sample_rate'], gc_enabled,
+                sample_size=args.sample_size or None,
+                silence_threshold=silence_threshold,
+                crop=args.crop or 'pieces', seed=CORPUS_SEED, rank=rank,
+                world=world, spec=spec if utt_ctx else None)
+        except (ValueError, MemoryError) as e:
+            print(str(e))
+            return 1
+        if utt_ctx:
+            corpus_lc = 'frames' if lc_scales is not None else 'rows'
+        corpus_entry = dict(crop=args.crop or 'pieces', seed=CORPUS_SEED,
+                            sample_size=args.sample_size or None,
+                            lc_feature_context=args.lc_feature_context
+                            or 'piece')
+    elif args.synthetic:
         reader = SyntheticReader(args.sample_size,
                                  args.gc_cardinality if gc_enabled else None,
                                  rank=rank, lc_channels=file_lc,
@@ -453,10 +547,15 @@ def main(argv=None):
         return 1
 
     try:
-        saved_global_step = load(net, restore_from, optimizer)
+        restored = {}
+        saved_global_step = load(net, restore_from, optimizer, restored)
         if is_overwritten_training or saved_global_step is None:
             # the first training step will be saved_global_step + 1
             saved_global_step = -1
+        corpus_base = 0
+        if corpus is not None and is_overwritten_training:
+            corpus_base = corpus_first_batch(restored.get('device_corpus'),
+                                             corpus_entry)
     except Exception:
         print("Something went wrong while restoring checkpoint. "
               "We will terminate training to avoid accidentally overwriting "
@@ -482,7 +581,12 @@ def main(argv=None):
             lc_frames=lc_scales is not None, rank=rank, world=world)
     validate_every = args.validate_every or args.checkpoint_every
 
-    threads = reader.start_threads()
+    threads = [] if corpus is not None else reader.start_threads()
+
+    def corpus_at(k):
+        """The 'device_corpus' entry of a checkpoint after step k."""
+        return None if corpus is None else \
+            dict(corpus_entry, batch=corpus_base + k)
     events = None
     if rank == 0:
         os.makedirs(logdir, exist_ok=True)
@@ -605,24 +709,36 @@ def main(argv=None):
             start_time = time.time()
             # every rank takes the same decision for this step (skip / common
             # clip length / abort) BEFORE any collective of the step is issued
-            err = None
+            err = cplan = None
+            lc, lc_off = None, 0
             try:
-                audio = reader.dequeue(args.batch_size)
-                lengths = reader.dequeue_lengths(args.batch_size).numpy() \
-                    if args.mask_padding else None
-                gc = reader.dequeue_gc(args.batch_size) if gc_enabled else None
-                lc, lc_off = None, 0
-                if spec is not None:
-                    pass                  # (from the staged batch, below)
-                elif lc_scales is not None:
-                    # frames + offsets: the model upsamples on the device
-                    lc, lc_off = reader.dequeue_lc_frames(args.batch_size)
-                elif lc_enabled:
-                    lc = reader.dequeue_lc(args.batch_size)
+                if corpus is not None:
+                    # the host index alone: T, lengths and speaker ids; the
+                    # batch itself is cut on the device, below
+                    cplan = corpus.plan(corpus_base + step, args.batch_size)
+                    audio = None
+                    lengths = cplan.n if args.mask_padding else None
+                    gc = torch.from_numpy(cplan.gc) if gc_enabled else None
+                else:
+                    audio = reader.dequeue(args.batch_size)
+                    lengths = \
+                        reader.dequeue_lengths(args.batch_size).numpy() \
+                        if args.mask_padding else None
+                    gc = reader.dequeue_gc(args.batch_size) \
+                        if gc_enabled else None
+                    if spec is not None:
+                        pass              # (from the staged batch, below)
+                    elif lc_scales is not None:
+                        # frames + offsets: the model upsamples on the device
+                        lc, lc_off = reader.dequeue_lc_frames(args.batch_size)
+                    elif lc_enabled:
+                        lc = reader.dequeue_lc(args.batch_size)
             except Exception as e:        # e.g. a reader-thread failure
                 err, audio, gc, lc, lengths = e, None, None, None, None
             n_t, all_ok = parallel.agree_step(
-                audio.shape[1] if err is None else 0, err is None, net.device)
+                0 if err is not None else
+                cplan.T if cplan is not None else audio.shape[1],
+                err is None, net.device)
             if not all_ok:
                 raise RuntimeError('rank %d: a rank failed to produce a batch '
                                    'at step %d%s' % (rank, step, '' if err is
@@ -637,7 +753,17 @@ def main(argv=None):
                 real = int(round(den * world))
             if (n_t if lengths is None else int(lengths.max())) < 2:
                 continue
-            audio = audio[:, :n_t]
+            if corpus is not None:
+                # (one or two launches on the training stream; no copy)
+                cb = corpus.batch(corpus_base + step, args.batch_size, T=n_t,
+                                  lc=corpus_lc)
+                audio = cb.audio
+                if corpus_lc == 'frames':
+                    lc, lc_off = cb.frames, cb.offsets
+                elif corpus_lc == 'rows':
+                    lc = cb.rows
+            else:
+                audio = audio[:, :n_t]
             if lc is not None and lc_scales is None:
                 lc = lc[:, :n_t]
             if audio.device.type == 'cpu' and net.device.type == 'cuda':
@@ -646,7 +772,7 @@ def main(argv=None):
                 # step's kernels, i.e. the host would wait for the device every
                 # step and prepare the next batch while it idles
                 audio = stage_in(audio.reshape(audio.shape[0], -1), step)
-            if spec is not None:
+            if spec is not None and corpus_lc is None:
                 # frames (offset 0) for an upsampler model, else rows
                 lc = net.local_condition_from_audio(
                     spec, audio.reshape(audio.shape[0], -1), lengths)
@@ -692,7 +818,8 @@ def main(argv=None):
                     report(*pending)
                     pending = None
             if rank == 0 and step % args.checkpoint_every == 0:
-                save(net, logdir, step, optimizer, lc_entry)
+                save(net, logdir, step, optimizer, lc_entry,
+                     corpus_at(step))
                 last_saved_step = step
                 if args.histograms:
                     # the reference's histogram summaries (model.py:314-325)
@@ -723,7 +850,7 @@ def main(argv=None):
         print()
     finally:
         if rank == 0 and step is not None and step > last_saved_step:
-            save(net, logdir, step, optimizer, lc_entry)
+            save(net, logdir, step, optimizer, lc_entry, corpus_at(step))
         coord.request_stop()
         coord.join(threads)
         if events:
