@@ -945,6 +945,44 @@ int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths
                int n_fft, int hop, int n_bins, int n_mels, float floor_,
                float* out, void* stream);
 
+/* ---- feature normalisation (csrc/wn_features.hip; wavenet/features.py:
+ * FeatureStats, Normalizer).  fr / in / out float32 [B][F][C]; nframes: device
+ * int32 [B] (clip b has nframes[b] real frames, clamped to [0, F] by the
+ * kernel, read when it runs) or NULL (all F frames are real).  Frames at or
+ * behind nframes[b] are never read.
+ *
+ * wn_feature_stats ACCUMULATES INTO acc, float64 [2][C], over the real frames:
+ *   acc[0][c] += sum x,   acc[1][c] += sum x * x     (x widened to float64)
+ * partials: scratch of wn_feature_stats_partials_count() * 2 * C doubles (the
+ * count is a constant).  The summation order, fixed: partial k sums the rows
+ * [k per, min(B F, (k + 1) per)) of the B F rows, per = ceil(B F / count) -- a
+ * function of (B, F, count) only.  Inside it the rows are dealt to G = 256 / L
+ * row groups, L = the power of two next at or above ceil(C / V), at most 256,
+ * V = 4 where C % 4 == 0 else 1; group g adds its rows lo + g, lo + g + G, ...
+ * in ascending order, then the groups are added in the order g = 0, 1, ...;
+ * at last the partials are added in the order k = 0, 1, ... starting from
+ * zero, and that sum is added to acc.  No atomics: the result is a function of
+ * the input's bits, (B, F, C), nframes and the previous acc, not of the device
+ * or the launch.  The frame count is the host's sum of nframes.
+ *
+ * wn_feature_normalize: a real frame gets, in float32,
+ *   v = (x - shift[c]) * scale[c]      (one subtraction, one multiplication)
+ *   out = v < lo ? lo : (v > hi ? hi : v)                 (a NaN stays a NaN)
+ * lo = -INFINITY, hi = +INFINITY: no clamp.  Frames f >= nframes[b] are
+ * written as exact zeros whatever `in` held (wn_melspec's padding).  out may
+ * be in.  16-byte loads and stores where C % 4 == 0, else a scalar path.
+ *
+ * 1 <= C <= 512, B, F >= 1, B * F <= 2^31 - 1, lo <= hi (else
+ * WN_ERR_BAD_SHAPE); fr, in, out (and shift, scale) 16-byte aligned when
+ * C % 4 == 0, else 4-byte; nframes 4-byte; acc, partials 8-byte (else
+ * WN_ERR_MISALIGNED).  All checks come before any launch. */
+int wn_feature_stats_partials_count(void);
+int wn_feature_stats(const float* fr, int B, int F, int C, const int32_t* nframes,
+                     double* acc, double* partials, void* stream);
+int wn_feature_normalize(const float* in, float* out, int B, int F, int C,
+                         const int32_t* nframes, const float* shift,
+                         const float* scale, float lo, float hi, void* stream);
+
 /* ---- device-resident training corpus (csrc/wn_corpus.hip; the rule:
  * wavenet/corpus.py).  The trimmed utterances lie in one device buffer `flat`
  * [N] float32; utterance u is flat[utt_off[u] .. + utt_len[u]).  A batch is

@@ -222,6 +222,167 @@ static int mel_launch(const MelArgs& a, int B, size_t lds, hipStream_t s) {
   return wn_check_launch();
 }
 
+// ---------------------------------------------------------------------------
+// Feature normalisation: per-channel statistics of frames and the affine +
+// clamp normaliser (wavenet/features.py: FeatureStats, Normalizer;
+// tests/featnorm_ref.py restates both).
+//
+// feature_stats_partials_kernel: FSTAT_PARTS partial sums of x and x * x per
+// channel, x widened to float64 first.  The B * F rows are cut into
+// FSTAT_PARTS contiguous ranges of per = ceil(B F / FSTAT_PARTS) rows, partial
+// k = rows [k per, min(B F, (k + 1) per)) -- a function of (B, F, FSTAT_PARTS)
+// only; an empty range gives zeros.  Inside a range the workgroup's 256
+// threads form G = 256 / L row groups of L = 2^ceil(log2(ceil(C / V))) lanes
+// (at most 256), V = 4 channels per lane where C % 4 == 0 (one 16-byte load),
+// else 1.  Row group g adds its rows lo + g, lo + g + G, ... in ascending
+// order, the G group sums are added in the order g = 0, 1, ... through LDS.
+// feature_stats_finish_kernel adds the partials k = 0, 1, ... in order, from
+// zero, and adds that sum to acc.  No atomics: the result is a function of
+// the input's bits, (B, F, C), nframes and the previous acc.  Rows at or
+// behind nframes[b] are not read.
+// ---------------------------------------------------------------------------
+#define FSTAT_PARTS 256
+#define FSTAT_THREADS 256
+#define FNORM_THREADS 256
+#define FEAT_MAX_C 512
+
+template <int V>
+__global__ __launch_bounds__(FSTAT_THREADS) void feature_stats_partials_kernel(
+    const float* __restrict__ fr, long R, int F, int C,
+    const int32_t* __restrict__ nframes, long per, int L,
+    double* __restrict__ partials) {
+  __shared__ double red[2 * V * FSTAT_THREADS];
+  const int tid = threadIdx.x;
+  const int G = FSTAT_THREADS / L, g = tid / L, lane = tid - g * L;
+  const long lo = (long)blockIdx.x * per;
+  const long hi = lo + per < R ? lo + per : R;
+  double* outp = partials + (long)blockIdx.x * 2 * C;
+  // (C > 256 V: L = 256, G = 1, and a lane takes several channel groups)
+  // (every thread makes every trip: the barriers below are workgroup-wide)
+  for (int cb = 0; cb < C; cb += L * V) {
+    const int c0 = cb + lane * V;
+    const bool live = c0 < C;
+    double s1[V], s2[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) s1[e] = s2[e] = 0.0;
+    for (long r = lo + g; live && r < hi; r += G) {
+      const long b = r / F;
+      const int f = (int)(r - b * F);
+      int n = F;
+      if (nframes) {
+        n = nframes[b];
+        n = n < 0 ? 0 : (n > F ? F : n);
+      }
+      if (f >= n) continue;
+      const float* row = fr + r * C + c0;
+      if (V == 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          const double x = (double)v[e];
+          s1[e] += x;
+          s2[e] += x * x;
+        }
+      } else {
+        const double x = (double)row[0];
+        s1[0] += x;
+        s2[0] += x * x;
+      }
+    }
+    __syncthreads();                 // (the previous channel group's reads)
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      red[(2 * e) * FSTAT_THREADS + tid] = s1[e];
+      red[(2 * e + 1) * FSTAT_THREADS + tid] = s2[e];
+    }
+    __syncthreads();
+    if (g == 0 && live) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int q = 0; q < G; ++q) {
+          t1 += red[(2 * e) * FSTAT_THREADS + q * L + lane];
+          t2 += red[(2 * e + 1) * FSTAT_THREADS + q * L + lane];
+        }
+        outp[c0 + e] = t1;
+        outp[C + c0 + e] = t2;
+      }
+    }
+  }
+}
+
+__global__ void feature_stats_finish_kernel(const double* __restrict__ partials,
+                                            int C, double* __restrict__ acc) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;   // [2][C] flat
+  if (j >= 2 * C) return;
+  double t = 0.0;
+  for (int k = 0; k < FSTAT_PARTS; ++k) t += partials[(long)k * 2 * C + j];
+  acc[j] += t;
+}
+
+// out = clamp((in - shift[c]) * scale[c]) on the real frames, exact zeros on
+// the others (which are not read).  One subtraction, one multiplication: no
+// FMA can form.  The clamp's comparisons are false for a NaN, which passes.
+template <int V>
+__global__ __launch_bounds__(FNORM_THREADS) void feature_normalize_kernel(
+    const float* in, float* out, long R, int F, int C,
+    const int32_t* __restrict__ nframes, const float* __restrict__ shift,
+    const float* __restrict__ scale, float lo, float hi) {
+#pragma clang fp contract(off)
+  const int CV = C / V;
+  const long total = R * CV;
+  for (long i = (long)blockIdx.x * FNORM_THREADS + threadIdx.x; i < total;
+       i += (long)gridDim.x * FNORM_THREADS) {
+    const long r = i / CV;
+    const int c = (int)(i - r * CV) * V;
+    const long b = r / F;
+    const int f = (int)(r - b * F);
+    int n = F;
+    if (nframes) {
+      n = nframes[b];
+      n = n < 0 ? 0 : (n > F ? F : n);
+    }
+    const long o = r * C + c;
+    if (V == 4) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (f < n) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(in + o);
+        const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + c);
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = x[e] - sh[e];
+          const float w = d * sc[e];
+          v[e] = w < lo ? lo : (w > hi ? hi : w);
+        }
+      }
+      *reinterpret_cast<f32x4*>(out + o) = v;
+    } else {
+      float v = 0.f;
+      if (f < n) {
+        const float d = in[o] - shift[c];
+        const float w = d * scale[c];
+        v = w < lo ? lo : (w > hi ? hi : w);
+      }
+      out[o] = v;
+    }
+  }
+}
+
+// the shape and alignment rules both entries share (`a`, `b`: the float
+// buffers of [B][F][C]; b may be NULL)
+static int feat_check(const void* a, const void* b, int B, int F, int C,
+                      const int32_t* nframes) {
+  if (C < 1 || C > FEAT_MAX_C || B < 1 || F < 1 ||
+      (long)B * (long)F > 2147483647L)
+    return WN_ERR_BAD_SHAPE;
+  const uintptr_t m = (C % 4 == 0) ? 15u : 3u;
+  if ((reinterpret_cast<uintptr_t>(a) & m) || (reinterpret_cast<uintptr_t>(b) & m) ||
+      (reinterpret_cast<uintptr_t>(nframes) & 3u))
+    return WN_ERR_MISALIGNED;
+  return WN_OK;
+}
+
 extern "C" {
 
 int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths,
@@ -262,6 +423,58 @@ int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths
   const size_t lds = sizeof(float) * (size_t)(MEL_RING + 2 * n_fft + (staged ? nstage : 0));
   return staged ? mel_launch<true>(a, B, lds, (hipStream_t)stream)
                 : mel_launch<false>(a, B, lds, (hipStream_t)stream);
+}
+
+int wn_feature_stats_partials_count(void) { return FSTAT_PARTS; }
+
+int wn_feature_stats(const float* fr, int B, int F, int C, const int32_t* nframes,
+                     double* acc, double* partials, void* stream) {
+  if (!fr || !acc || !partials) return WN_ERR_NULL;
+  const int rc = feat_check(fr, nullptr, B, F, C, nframes);
+  if (rc != WN_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(acc) & 7u) || (reinterpret_cast<uintptr_t>(partials) & 7u))
+    return WN_ERR_MISALIGNED;
+  const long R = (long)B * F;
+  const long per = (R + FSTAT_PARTS - 1) / FSTAT_PARTS;
+  const int V = (C % 4 == 0) ? 4 : 1;
+  int L = 1;
+  while (L < (C + V - 1) / V && L < FSTAT_THREADS) L <<= 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (V == 4)
+    hipLaunchKernelGGL(feature_stats_partials_kernel<4>, dim3(FSTAT_PARTS),
+                       dim3(FSTAT_THREADS), 0, s, fr, R, F, C, nframes, per, L, partials);
+  else
+    hipLaunchKernelGGL(feature_stats_partials_kernel<1>, dim3(FSTAT_PARTS),
+                       dim3(FSTAT_THREADS), 0, s, fr, R, F, C, nframes, per, L, partials);
+  if (wn_check_launch() != WN_OK) return WN_ERR_LAUNCH;
+  hipLaunchKernelGGL(feature_stats_finish_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s,
+                     partials, C, acc);
+  return wn_check_launch();
+}
+
+int wn_feature_normalize(const float* in, float* out, int B, int F, int C,
+                         const int32_t* nframes, const float* shift, const float* scale,
+                         float lo, float hi, void* stream) {
+  if (!in || !out || !shift || !scale) return WN_ERR_NULL;
+  int rc = feat_check(in, out, B, F, C, nframes);
+  if (rc != WN_OK) return rc;
+  if (!(lo <= hi)) return WN_ERR_BAD_SHAPE;    // (lo > hi, or a NaN bound)
+  const int V = (C % 4 == 0) ? 4 : 1;
+  const uintptr_t m = V == 4 ? 15u : 3u;
+  if ((reinterpret_cast<uintptr_t>(shift) & m) || (reinterpret_cast<uintptr_t>(scale) & m))
+    return WN_ERR_MISALIGNED;
+  const long R = (long)B * F;
+  const long total = R * (C / V);
+  long blocks = (total + FNORM_THREADS - 1) / FNORM_THREADS;
+  if (blocks > 4096) blocks = 4096;
+  hipStream_t s = (hipStream_t)stream;
+  if (V == 4)
+    hipLaunchKernelGGL(feature_normalize_kernel<4>, dim3((unsigned)blocks), dim3(FNORM_THREADS),
+                       0, s, in, out, R, F, C, nframes, shift, scale, lo, hi);
+  else
+    hipLaunchKernelGGL(feature_normalize_kernel<1>, dim3((unsigned)blocks), dim3(FNORM_THREADS),
+                       0, s, in, out, R, F, C, nframes, shift, scale, lo, hi);
+  return wn_check_launch();
 }
 
 }  // extern "C"

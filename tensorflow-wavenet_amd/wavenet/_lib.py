@@ -202,6 +202,12 @@ SIGNATURES = {
     # hop, n_bins, n_mels, floor, out, stream
     'wn_melspec': (c_int, [P, c_long, c_int, c_int, P, P, P, P, c_int, c_int,
                            c_int, c_int, c_float, P, P]),
+    # feature normalisation.  stats: fr, B, F, C, nframes, acc, partials,
+    # stream; normalize: in, out, B, F, C, nframes, shift, scale, lo, hi, stream
+    'wn_feature_stats_partials_count': (c_int, []),
+    'wn_feature_stats': (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
+    'wn_feature_normalize': (c_int, [P, P, c_int, c_int, c_int, P, P, P,
+                                     c_float, c_float, P]),
     # device-resident corpus.  The plan (13 arguments): utt_off, utt_len, U,
     # item_utt, item_start, P, perm, e0, nE, g0, size, random, seed.
     # gather: flat, N, plan, audio, B, T, stream

@@ -33,6 +33,13 @@ beside samples f * hop .. f * hop + hop - 1, m = WaveNetModel.LC_CONTEXT_MAX):
     offset = start - f_lo * hop
     Fw     = (T + hop - 2) // hop + 1 + 2 m       (window_frames: any start)
 
+Normalised frames (normalize=): 'corpus' sums x and x * x per channel over
+the resident raw frames with one wn_feature_stats launch (features.
+FeatureStats: float64, one fixed order), over all ranks' shards through
+`stats_allreduce`, builds features.Normalizer.from_stats from them and
+normalises the resident frames in place, once; the gathers then copy
+normalised frames.  A features.Normalizer is applied the same way.
+
 loss(..., local_condition_batch=frames, local_condition_offset=offset) then
 selects what it would select from the whole utterance's frames at offset =
 start, the frame-context convolution's neighbours and its zeros at the true
@@ -244,7 +251,8 @@ class DeviceCorpus(object):
 
     def __init__(self, audio_dir, sample_rate, gc_enabled, sample_size=None,
                  silence_threshold=None, crop='pieces', seed=0, rank=0,
-                 world=1, spec=None, device=None, max_bytes=32 << 30):
+                 world=1, spec=None, device=None, max_bytes=32 << 30, *,
+                 normalize=None, normalize_clip=None, stats_allreduce=None):
         from . import audio_reader as ar
         from . import features
         _check_args(sample_size, crop, seed, max_bytes)
@@ -253,6 +261,9 @@ class DeviceCorpus(object):
                              'world %r' % (rank, world))
         if spec is not None and not isinstance(spec, features.MelSpec):
             raise ValueError('spec must be a features.MelSpec or None')
+        norm_kw = _check_normalize(normalize, normalize_clip, stats_allreduce,
+                                   world, None if spec is None else
+                                   spec.n_mels, spec is not None)
         files = ar.find_files(audio_dir)
         if not files:
             raise ValueError("No audio files found in '{}'.".format(audio_dir))
@@ -294,15 +305,28 @@ class DeviceCorpus(object):
         self.files = kept
         self._setup(clips, ids if gc_enabled else None, None, None,
                     dict(sample_size=sample_size, crop=crop, seed=seed),
-                    spec, device, max_bytes)
+                    spec, device, max_bytes, norm_kw)
         self.gc_category_cardinality = card
 
     @classmethod
     def from_arrays(cls, arrays, category_ids=None, frames=None, hop=None,
-                    device=None, max_bytes=32 << 30, **index_kw):
+                    device=None, max_bytes=32 << 30, spec=None,
+                    normalize=None, normalize_clip=None, stats_allreduce=None,
+                    world=1, **index_kw):
         """The same object from float32 arrays in memory (frames: one
-        [F_u, Lc] array per utterance with F_u >= ceil(n_u / hop))."""
+        [F_u, Lc] array per utterance with F_u >= ceil(n_u / hop); or spec:
+        the frames are computed as from files).  normalize...: as the
+        constructor's; world: the number of shards this one belongs to."""
+        from . import features
         self = cls.__new__(cls)
+        if spec is not None and not isinstance(spec, features.MelSpec):
+            raise ValueError('spec must be a features.MelSpec or None')
+        if spec is not None and frames is not None:
+            raise ValueError('from_arrays: spec and frames exclude each '
+                             'other')
+        if not _is_int(world) or world < 1:
+            raise ValueError('from_arrays: world must be a positive int, '
+                             'got %r' % (world,))
         _check_args(index_kw.get('sample_size'), index_kw.get('crop', 'pieces'),
                     index_kw.get('seed', 0), max_bytes)
         clips = []
@@ -333,16 +357,21 @@ class DeviceCorpus(object):
                         'from_arrays: frames must be float32 [F_u, Lc] with '
                         'F_u >= ceil(n_u / hop), got %s %s for %d samples at '
                         'hop %d' % (f.dtype, f.shape, a.shape[0], hop))
+        norm_kw = _check_normalize(
+            normalize, normalize_clip, stats_allreduce, world,
+            spec.n_mels if spec is not None else
+            (frames[0].shape[1] if frames is not None else None),
+            spec is not None or frames is not None)
         self.files = None
-        self._setup(clips, category_ids, frames, hop, index_kw, None, device,
-                    max_bytes)
+        self._setup(clips, category_ids, frames, hop, index_kw, spec, device,
+                    max_bytes, norm_kw)
         self.gc_category_cardinality = None if category_ids is None else \
             int(np.max(category_ids)) + 1
         return self
 
     # ------------------------------------------------------------ internals
     def _setup(self, clips, ids, frames, hop, index_kw, spec, device,
-               max_bytes):
+               max_bytes, norm_kw=None):
         lengths = [int(a.shape[0]) for a in clips]
         self.index = CorpusIndex(lengths, ids, **index_kw)
         Lc = spec.n_mels if spec is not None else \
@@ -360,6 +389,13 @@ class DeviceCorpus(object):
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if device is None else torch.device(device)
         self.hop, self.Lc, self.spec = hop, Lc, spec
+        self.world = norm_kw['world'] if norm_kw else 1
+        self.normalizer = self.feature_stats = None
+        raw = spec
+        if spec is not None and norm_kw and norm_kw['normalize'] is not None:
+            raw = spec.with_normalizer(None)    # (normalised below, once)
+        elif spec is not None:
+            self.normalizer = spec.normalizer
         ix = self.index
 
         def dev(a):
@@ -399,15 +435,66 @@ class DeviceCorpus(object):
                                        fr_off.tolist(), counts.tolist()):
                     if n:
                         self.frames_flat[fo * Lc:(fo + F) * Lc].copy_(
-                            spec(self.flat[o:o + n]).reshape(-1))
+                            raw(self.flat[o:o + n]).reshape(-1))
         elif frames is not None:
             self.frames_flat = filled(list(frames),
                                       [f.shape[0] * Lc for f in frames])
+        if norm_kw and norm_kw['normalize'] is not None:
+            self._normalize_resident(**norm_kw)
         self._perm_dev = None        # device int32 [rows][P]
         self._perm_pin = None        # its pinned staging rows, their events
         self._perm_e0, self._perm_n = 0, 0   # epochs resident: e0 .. e0 + n - 1
         self._bufs = {}              # output kind -> RING flat device buffers
         self._calls = 0              # batch calls so far: call k uses set k % RING
+
+    def _normalize_resident(self, normalize, clip, allreduce, world):
+        """Statistics of the resident raw frames (one launch; all shards'
+        through `allreduce`), the normaliser, and the frames normalised in
+        place, once."""
+        import torch
+        from . import features
+        view = self.frames_flat.view(1, -1, self.Lc)
+        with torch.cuda.device(self.device):
+            if normalize == 'corpus' or world == 1 or allreduce is not None:
+                stats = features.FeatureStats(self.Lc).update(view)
+                if world > 1:
+                    stats = features.FeatureStats.from_vector(
+                        allreduce(stats.vector()))
+                self.feature_stats = stats
+            norm = features.Normalizer.from_stats(stats, clip) \
+                if normalize == 'corpus' else normalize
+            norm(view, out=view)
+        self.normalizer = norm
+        if self.spec is not None:
+            self.spec = self.spec.with_normalizer(norm)
+
+    def compute_feature_stats(self, spec, stats_allreduce=None):
+        """features.FeatureStats of the raw (un-normalised) log-mel frames of
+        every utterance, for a corpus that keeps no frames: each utterance's
+        frames are computed, added to the sums and dropped -- a one-off pass
+        with a device peak of one utterance's frames.  With world > 1 the
+        sums go through `stats_allreduce` (the sum over ranks of a float64
+        vector)."""
+        import torch
+        from . import features
+        if not isinstance(spec, features.MelSpec):
+            raise ValueError('compute_feature_stats: spec must be a '
+                             'features.MelSpec')
+        if self.world > 1 and not callable(stats_allreduce):
+            raise ValueError('compute_feature_stats: world = %d needs '
+                             'stats_allreduce: the statistics of a shard '
+                             'differ between ranks' % self.world)
+        raw = spec.with_normalizer(None)
+        stats = features.FeatureStats(spec.n_mels)
+        with torch.cuda.device(self.device):
+            for o, n in zip(self.index.offsets.tolist(),
+                            self.index.lengths.tolist()):
+                if n:
+                    stats.update(raw(self.flat[o:o + n]))
+        if self.world > 1:
+            stats = features.FeatureStats.from_vector(
+                stats_allreduce(stats.vector()))
+        return stats
 
     @property
     def items(self):
@@ -520,6 +607,39 @@ class DeviceCorpus(object):
                           self.Lc, _lib.ptr(frames), Fw, _lib.ptr(rows), B,
                           p.T, _lib.stream())
         return Batch(audio, p.n.copy(), p.gc, frames, offsets, rows)
+
+
+def _check_normalize(normalize, clip, allreduce, world, channels, has_frames):
+    """The normalisation keywords, checked before any loading: a dict for
+    _setup."""
+    from . import features
+    if normalize is not None and normalize != 'corpus' and \
+            not isinstance(normalize, features.Normalizer):
+        raise ValueError("normalize must be None, 'corpus' or a "
+                         'features.Normalizer, got %r' % (normalize,))
+    if normalize is not None and not has_frames:
+        raise ValueError('normalize needs spec (or frames): the corpus holds '
+                         'no frames to normalise')
+    if clip is not None:
+        if normalize != 'corpus':
+            raise ValueError("normalize_clip needs normalize='corpus'")
+        if isinstance(clip, (bool, np.bool_)) or \
+                not isinstance(clip, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(clip) or not clip > 0:
+            raise ValueError('normalize_clip must be positive, got %r'
+                             % (clip,))
+    if allreduce is not None and not callable(allreduce):
+        raise ValueError('stats_allreduce must be callable or None')
+    if normalize == 'corpus' and world > 1 and allreduce is None:
+        raise ValueError("normalize='corpus' with world = %d needs "
+                         'stats_allreduce: per-shard statistics would '
+                         'silently differ between ranks' % world)
+    if isinstance(normalize, features.Normalizer) and \
+            normalize.n_channels != channels:
+        raise ValueError('the normaliser has %d channels, the frames %r'
+                         % (normalize.n_channels, channels))
+    return dict(normalize=normalize, clip=clip, allreduce=allreduce,
+                world=int(world))
 
 
 def _check_args(sample_size, crop, seed, max_bytes):

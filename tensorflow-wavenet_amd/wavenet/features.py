@@ -17,7 +17,22 @@ frequencies, between n_mels + 2 points equally spaced on the HTK mel scale
 2595 log10(1 + f / 700) from fmin to fmax.  There is no reflection at the
 clip's edges.  The tables are computed once per MelSpec in float64 and rounded
 to float32; `logmel_reference` states the same rule in numpy.
+
+Normalisation.  log(max(M, floor)) spans about -23 .. +7: far outside what a
+Xavier-initialised conditioning projection can take.  `FeatureStats` sums x
+and x * x per channel over a corpus's frames on the device, in float64 and in
+one fixed order (wn_feature_stats); `Normalizer` is the affine + clamp rule
+
+    v   = (x - shift[c]) * scale[c]                    float32, two roundings
+    out = v < lo ? lo : (v > hi ? hi : v)              (a NaN stays a NaN)
+
+applied on the device to the real frames (wn_feature_normalize; padding
+frames stay exact zeros).  A MelSpec with a normaliser applies it to what it
+computes, and its constants travel in the checkpoint's 'lc_features' entry.
 """
+import copy
+import re
+
 import numpy as np
 
 from . import _lib
@@ -70,7 +85,8 @@ class MelSpec(object):
     is touched."""
 
     def __init__(self, sample_rate, n_fft=1024, hop=256, n_mels=80,
-                 win_length=None, fmin=0.0, fmax=None, floor=1e-10):
+                 win_length=None, fmin=0.0, fmax=None, floor=1e-10, *,
+                 normalizer=None):
         if not _is_num(sample_rate) or not sample_rate > 0:
             raise ValueError('sample_rate must be a positive number, got %r'
                              % (sample_rate,))
@@ -96,6 +112,8 @@ class MelSpec(object):
                              % (sample_rate / 2.0, fmin, fmax))
         if not _is_num(floor) or not floor > 0:
             raise ValueError('floor must be positive, got %r' % (floor,))
+        _check_normalizer(normalizer, n_mels)
+        self.normalizer = normalizer
         self.sample_rate = sample_rate
         self.n_fft, self.hop, self.n_mels = int(n_fft), int(hop), int(n_mels)
         self.win_length = int(win_length)
@@ -107,10 +125,21 @@ class MelSpec(object):
     def settings(self):
         """The constructor's keywords (train.py stores them in every
         checkpoint under 'lc_features', beside 'kind': 'mel')."""
-        return dict(sample_rate=self.sample_rate, n_fft=self.n_fft,
-                    hop=self.hop, n_mels=self.n_mels,
-                    win_length=self.win_length, fmin=self.fmin,
-                    fmax=self.fmax, floor=self.floor)
+        d = dict(sample_rate=self.sample_rate, n_fft=self.n_fft,
+                 hop=self.hop, n_mels=self.n_mels,
+                 win_length=self.win_length, fmin=self.fmin,
+                 fmax=self.fmax, floor=self.floor)
+        if self.normalizer is not None:
+            d['normalizer'] = self.normalizer.entry()
+        return d
+
+    def with_normalizer(self, normalizer):
+        """A spec with this normaliser (None: without one) that shares the
+        tables and the device cache with this one."""
+        _check_normalizer(normalizer, self.n_mels)
+        other = copy.copy(self)
+        other.normalizer = normalizer
+        return other
 
     def num_frames(self, n):
         return -(-int(n) // self.hop)
@@ -167,7 +196,8 @@ class MelSpec(object):
         device float32 [B, F, n_mels] or [F, n_mels], F = ceil(T / hop),
         without waiting for the device.  lengths ([B] ints, 1 <= n[b] <= T):
         clip b has n[b] real samples; what lies behind them is not read, and
-        frames f >= ceil(n[b] / hop) are zeros."""
+        frames f >= ceil(n[b] / hop) are zeros.  With a normaliser the real
+        frames are normalised (one more launch), the zeros stay zeros."""
         import torch
         if not isinstance(audio, torch.Tensor):
             audio = np.asarray(audio)
@@ -203,7 +233,357 @@ class MelSpec(object):
                       _lib.ptr(win), _lib.ptr(basis), _lib.ptr(melw),
                       self.n_fft, self.hop, self.n_bins, self.n_mels,
                       self.floor, _lib.ptr(out), _lib.stream())
+            if self.normalizer is not None:
+                self.normalizer._launch(
+                    out, out, None if n is None else -(-n // self.hop))
         return out[0] if one else out
+
+
+def _check_normalizer(normalizer, n_mels):
+    if normalizer is None:
+        return
+    if not isinstance(normalizer, Normalizer):
+        raise ValueError('normalizer must be a features.Normalizer or None')
+    if normalizer.n_channels != n_mels:
+        raise ValueError('the normaliser has %d channels, the front end %r '
+                         'mels' % (normalizer.n_channels, n_mels))
+
+
+def _frames_arg(frames, C, what):
+    """(frames, one, B, F): `frames` as it came, whether it was [F, C], and
+    its shape; float32 [B, F, C] or [F, C] with C channels is required."""
+    if hasattr(frames, 'detach'):
+        ok = str(frames.dtype) == 'torch.float32'
+    else:
+        frames = np.asarray(frames)
+        ok = frames.dtype == np.float32
+    shape = tuple(int(v) for v in frames.shape)
+    if not ok or len(shape) not in (2, 3) or shape[-1] != C or \
+            min(shape) < 1:
+        raise ValueError('%s: frames must be float32 [B, F, %d] or [F, %d], '
+                         'got %s %s' % (what, C, C, frames.dtype, shape))
+    one = len(shape) == 2
+    B, F = (1, shape[0]) if one else shape[:2]
+    if B * F > 2 ** 31 - 1:
+        raise ValueError('%s: B * F = %d exceeds 2^31 - 1' % (what, B * F))
+    return frames, one, B, F
+
+
+def _nframes_arg(nframes, B, F, what):
+    """`nframes` as int32 numpy [B] with 0 <= n[b] <= F (None stays None)."""
+    if nframes is None:
+        return None
+    if hasattr(nframes, 'detach'):
+        nframes = nframes.detach().cpu().numpy()
+    n = np.asarray(nframes)
+    if n.dtype == object or n.dtype == np.bool_ or \
+            not np.issubdtype(n.dtype, np.integer) or n.shape != (B,):
+        raise ValueError('%s: nframes must be %d integers, got %s %s'
+                         % (what, B, n.dtype, list(n.shape)))
+    if (n < 0).any() or (n > F).any():
+        raise ValueError('%s: nframes must lie in [0, F] = [0, %d], got %s'
+                         % (what, F, n.tolist()))
+    return n.astype(np.int32)
+
+
+def _to_device(frames, B, F, C):
+    """float32 device tensor [B, F, C], contiguous (the library is loaded)."""
+    import torch
+    if isinstance(frames, torch.Tensor) and frames.device.type == 'cuda':
+        t = frames
+    else:
+        if not isinstance(frames, torch.Tensor):
+            # (a copy of a read-only array: torch wants a writable one)
+            frames = torch.from_numpy(
+                np.ascontiguousarray(frames) if frames.flags.writeable
+                else np.array(frames))
+        t = frames.to(torch.device('cuda', torch.cuda.current_device()))
+    return t.reshape(B, F, C).contiguous()
+
+
+class FeatureStats(object):
+    """Per-channel sums of x and x * x over frames, in float64: `update` adds
+    a tensor's real frames on the device (wn_feature_stats: one fixed
+    summation order, no atomics) without waiting for it; the sums a host
+    gives (`from_sums`, `merge`, `load`) are kept beside and added in
+    `sums()`.  The frame count is the host's."""
+
+    def __init__(self, n_channels):
+        if not _is_int(n_channels) or not 1 <= n_channels <= 512:
+            raise ValueError('n_channels must be an int in [1, 512], got %r'
+                             % (n_channels,))
+        self.n_channels = int(n_channels)
+        self.count = 0
+        self._s = np.zeros((2, self.n_channels), np.float64)
+        self._acc = None            # device float64 [2, C]
+        self._partials = None
+
+    def update(self, frames, nframes=None):
+        C = self.n_channels
+        frames, one, B, F = _frames_arg(frames, C, 'FeatureStats.update')
+        n = _nframes_arg(nframes, B, F, 'FeatureStats.update')
+        import torch
+        _lib.load()
+        _lib.require_gpu()
+        t = _to_device(frames, B, F, C)
+        if self._acc is not None and self._acc.device != t.device:
+            raise ValueError('FeatureStats.update: frames on %s, the sums so '
+                             'far on %s' % (t.device, self._acc.device))
+        with torch.cuda.device(t.device):
+            if self._acc is None:
+                parts = _lib.load().wn_feature_stats_partials_count()
+                self._acc = torch.zeros((2, C), dtype=torch.float64,
+                                        device=t.device)
+                self._partials = torch.empty(parts * 2 * C,
+                                             dtype=torch.float64,
+                                             device=t.device)
+            nd = None if n is None else torch.from_numpy(n).to(t.device)
+            _lib.call('wn_feature_stats', _lib.ptr(t), B, F, C, _lib.ptr(nd),
+                      _lib.ptr(self._acc), _lib.ptr(self._partials),
+                      _lib.stream())
+        self.count += B * F if n is None else int(n.sum())
+        return self
+
+    def sums(self):
+        """(count, s1 float64 [C], s2 float64 [C]) on the host (waits for
+        the device where `update` ran)."""
+        s = self._s
+        if self._acc is not None:
+            s = s + self._acc.cpu().numpy()
+        return self.count, s[0].copy(), s[1].copy()
+
+    def mean(self):
+        n, s1, _ = self.sums()
+        if n == 0:
+            raise ValueError('FeatureStats.mean: no frames were counted')
+        return s1 / n
+
+    def std(self):
+        """The population value, sqrt(max(s2 / n - mean^2, 0))."""
+        n, s1, s2 = self.sums()
+        if n == 0:
+            raise ValueError('FeatureStats.std: no frames were counted')
+        m = s1 / n
+        return np.sqrt(np.maximum(s2 / n - m * m, 0.0))
+
+    @classmethod
+    def from_sums(cls, count, s1, s2):
+        s1, s2 = np.asarray(s1, np.float64), np.asarray(s2, np.float64)
+        if s1.ndim != 1 or s1.shape != s2.shape or s1.shape[0] < 1:
+            raise ValueError('from_sums: s1 and s2 must both be [C], got %s '
+                             'and %s' % (s1.shape, s2.shape))
+        if isinstance(count, np.ndarray) and count.shape == ():
+            count = count.item()
+        if isinstance(count, (float, np.floating)) and \
+                float(count).is_integer():
+            count = int(count)
+        if not _is_int(count) or count < 0:
+            raise ValueError('from_sums: count must be a non-negative int, '
+                             'got %r' % (count,))
+        self = cls(s1.shape[0])
+        self.count = int(count)
+        self._s = np.stack([s1, s2])
+        return self
+
+    def merge(self, other):
+        """Add another's sums to this one's (host only)."""
+        if not isinstance(other, FeatureStats) or \
+                other.n_channels != self.n_channels:
+            raise ValueError('merge: FeatureStats of %d channels is required'
+                             % self.n_channels)
+        n, s1, s2 = other.sums()
+        self.count += n
+        self._s = self._s + np.stack([s1, s2])
+        return self
+
+    def vector(self):
+        """float64 [1 + 2 C]: count, s1, s2 (what an all-reduce sums)."""
+        n, s1, s2 = self.sums()
+        return np.concatenate([[float(n)], s1, s2])
+
+    @classmethod
+    def from_vector(cls, v):
+        v = np.asarray(v, np.float64).reshape(-1)
+        C = (v.shape[0] - 1) // 2
+        if v.shape[0] != 1 + 2 * C or C < 1:
+            raise ValueError('from_vector: 1 + 2 C values are required')
+        return cls.from_sums(v[0], v[1:1 + C], v[1 + C:])
+
+    def save(self, path):
+        n, s1, s2 = self.sums()
+        with open(path, 'wb') as f:       # (np.savez would append .npz)
+            np.savez(f, count=np.int64(n), s1=s1, s2=s2)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls.from_sums(int(z['count']), z['s1'], z['s2'])
+
+
+class Normalizer(object):
+    """out = clamp((x - shift[c]) * scale[c], lo, hi) per channel (module
+    docstring).  Calling it runs wn_feature_normalize on the device;
+    `reference` is the same rule in numpy float32."""
+
+    def __init__(self, shift, scale, lo=None, hi=None, count=None):
+        shift, scale = np.asarray(shift), np.asarray(scale)
+        for name, v in (('shift', shift), ('scale', scale)):
+            if v.ndim != 1 or v.shape[0] < 1 or v.shape[0] > 512 or \
+                    v.dtype == object or v.dtype == np.bool_ or \
+                    not np.issubdtype(v.dtype, np.number):
+                raise ValueError('Normalizer: %s must be [C] numbers, '
+                                 '1 <= C <= 512, got %s %s'
+                                 % (name, v.dtype, v.shape))
+        if shift.shape != scale.shape:
+            raise ValueError('Normalizer: shift has %d channels, scale %d'
+                             % (shift.shape[0], scale.shape[0]))
+        with np.errstate(over='ignore'):
+            shift, scale = shift.astype(np.float32), scale.astype(np.float32)
+        if not np.isfinite(shift).all() or not np.isfinite(scale).all():
+            raise ValueError('Normalizer: shift and scale must be finite')
+        if (scale == 0).any():
+            raise ValueError('Normalizer: scale must not be zero')
+        for name, v in (('lo', lo), ('hi', hi)):
+            if v is not None and (
+                    not isinstance(v, (int, float, np.integer, np.floating))
+                    or isinstance(v, (bool, np.bool_)) or np.isnan(v)):
+                raise ValueError('Normalizer: %s must be a number or None, '
+                                 'got %r' % (name, v))
+        self.lo = None if lo is None or lo == -np.inf else \
+            float(np.float32(lo))
+        self.hi = None if hi is None or hi == np.inf else \
+            float(np.float32(hi))
+        if self._lo() > self._hi():
+            raise ValueError('Normalizer: lo %r > hi %r' % (lo, hi))
+        if count is not None and (not _is_int(count) or count < 0):
+            raise ValueError('Normalizer: count must be a non-negative int '
+                             'or None, got %r' % (count,))
+        self.shift, self.scale = shift, scale
+        self.count = None if count is None else int(count)
+        self.n_channels = int(shift.shape[0])
+        self._dev = {}
+
+    def _lo(self):
+        return -np.inf if self.lo is None else self.lo
+
+    def _hi(self):
+        return np.inf if self.hi is None else self.hi
+
+    @classmethod
+    def from_stats(cls, stats, clip=None, min_std=1e-5):
+        """shift = float32(mean), scale = float32(1 / max(std, min_std)),
+        clamped to [-clip, clip] with a clip."""
+        if not isinstance(stats, FeatureStats):
+            raise ValueError('from_stats: a FeatureStats is required')
+        if clip is not None and (not _is_num(clip) or not clip > 0):
+            raise ValueError('from_stats: clip must be positive, got %r'
+                             % (clip,))
+        if not _is_num(min_std) or not min_std > 0:
+            raise ValueError('from_stats: min_std must be positive, got %r'
+                             % (min_std,))
+        mean, std = stats.mean(), stats.std()
+        return cls(mean.astype(np.float32),
+                   (1.0 / np.maximum(std, float(min_std))).astype(np.float32),
+                   None if clip is None else -float(clip),
+                   None if clip is None else float(clip), count=stats.count)
+
+    @classmethod
+    def from_range(cls, lo, hi, n_channels):
+        """The dB-range convention: (x - lo) / (hi - lo), clamped to [0, 1].
+        No statistics."""
+        if not _is_num(lo) or not _is_num(hi) or not lo < hi:
+            raise ValueError('from_range: lo < hi is required, got %r, %r'
+                             % (lo, hi))
+        if not _is_int(n_channels) or not 1 <= n_channels <= 512:
+            raise ValueError('from_range: n_channels must be an int in '
+                             '[1, 512], got %r' % (n_channels,))
+        return cls(np.full(n_channels, lo, np.float32),
+                   np.full(n_channels, 1.0 / (float(hi) - float(lo)),
+                           np.float32), 0.0, 1.0)
+
+    def entry(self):
+        """A plain dict for a checkpoint (`from_entry` inverts it bit for
+        bit: a float32 is exactly a Python float)."""
+        return dict(shift=[float(v) for v in self.shift],
+                    scale=[float(v) for v in self.scale],
+                    lo=self.lo, hi=self.hi, count=self.count)
+
+    @classmethod
+    def from_entry(cls, d):
+        if not isinstance(d, dict) or 'shift' not in d or 'scale' not in d:
+            raise ValueError("a normaliser entry needs 'shift' and 'scale', "
+                             'got %r' % (d,))
+        return cls(np.asarray(d['shift'], np.float64),
+                   np.asarray(d['scale'], np.float64), d.get('lo'),
+                   d.get('hi'), count=d.get('count'))
+
+    def with_clip(self, clip):
+        """The same shift and scale, clamped to [-clip, clip]."""
+        if not _is_num(clip) or not clip > 0:
+            raise ValueError('clip must be positive, got %r' % (clip,))
+        return Normalizer(self.shift, self.scale, -float(clip), float(clip),
+                          count=self.count)
+
+    def reference(self, frames, nframes=None):
+        """The rule in numpy float32: [B, F, C] or [F, C]."""
+        x, one, B, F = _frames_arg(np.asarray(frames), self.n_channels,
+                                   'Normalizer.reference')
+        n = _nframes_arg(nframes, B, F, 'Normalizer.reference')
+        x = x.reshape(B, F, self.n_channels)
+        with np.errstate(all='ignore'):
+            v = ((x - self.shift) * self.scale).astype(np.float32)
+            lo, hi = np.float32(self._lo()), np.float32(self._hi())
+            v = np.where(v < lo, lo, np.where(v > hi, hi, v))
+        if n is not None:
+            v = np.where(np.arange(F)[None, :, None] < n[:, None, None], v,
+                         np.float32(0))
+        v = v.astype(np.float32)
+        return v[0] if one else v
+
+    def _launch(self, src, dst, n):
+        """src -> dst, device float32 [B, F, C] contiguous; n: int32 numpy
+        [B] or None.  On src's device, torch's current stream."""
+        import torch
+        key = str(src.device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.shift).to(src.device),
+                              torch.from_numpy(self.scale).to(src.device))
+        shift, scale = self._dev[key]
+        B, F, C = (int(v) for v in src.shape)
+        nd = None if n is None else \
+            torch.from_numpy(np.ascontiguousarray(n, np.int32)).to(src.device)
+        _lib.call('wn_feature_normalize', _lib.ptr(src), _lib.ptr(dst), B, F,
+                  C, _lib.ptr(nd), _lib.ptr(shift), _lib.ptr(scale),
+                  self._lo(), self._hi(), _lib.stream())
+
+    def __call__(self, frames, nframes=None, out=None):
+        """Normalised frames, device float32 of frames' shape, without
+        waiting for the device.  nframes ([B] ints in [0, F]): clip b has
+        that many real frames; the others become zeros and are not read.
+        out: a contiguous device float32 tensor of the same shape to write
+        into (may be `frames` itself)."""
+        C = self.n_channels
+        frames, one, B, F = _frames_arg(frames, C, 'Normalizer')
+        n = _nframes_arg(nframes, B, F, 'Normalizer')
+        if out is not None:
+            if not hasattr(out, 'detach') or \
+                    str(out.dtype) != 'torch.float32' or \
+                    tuple(out.shape) != tuple(frames.shape) or \
+                    out.device.type != 'cuda' or not out.is_contiguous():
+                raise ValueError('Normalizer: out must be a contiguous '
+                                 'float32 device tensor of shape %s'
+                                 % (tuple(frames.shape),))
+        import torch
+        _lib.load()
+        _lib.require_gpu()
+        src = _to_device(frames, B, F, C)
+        if out is not None and out.device != src.device:
+            raise ValueError('Normalizer: out on %s, frames on %s'
+                             % (out.device, src.device))
+        dst = torch.empty_like(src) if out is None else out.view(B, F, C)
+        with torch.cuda.device(src.device):
+            self._launch(src, dst, n)
+        return out if out is not None else (dst[0] if one else dst)
 
 
 def logmel_reference(x, spec, dtype=np.float64):
@@ -223,7 +603,10 @@ def logmel_reference(x, spec, dtype=np.float64):
     re = fr @ cos.astype(dtype)
     im = fr @ sin.astype(dtype)
     m = (re * re + im * im) @ spec.melw64.astype(dtype).T
-    return np.log(np.maximum(m, dtype(spec.floor)))
+    out = np.log(np.maximum(m, dtype(spec.floor)))
+    if spec.normalizer is not None:
+        out = spec.normalizer.reference(out.astype(np.float32)).astype(dtype)
+    return out
 
 
 def local_condition_from_audio(net, spec, audio, lengths=None):
@@ -277,17 +660,116 @@ def add_cli_flags(p, also=''):
                    'sample_rate / 2)')
 
 
+    p.add_argument('--lc_normalize', choices=['none', 'corpus', 'range'],
+                   default=None,
+                   help='--lc_features: normalise the features on the '
+                   'device.  corpus: per channel to zero mean and unit '
+                   'variance with the statistics of the training corpus '
+                   '(--device_corpus true computes them at load, else '
+                   '--lc_stats FILE); range: (x - LO) / (HI - LO) clamped to '
+                   '[0, 1] with --lc_range LO,HI; none: off, whatever the '
+                   'checkpoint says.  The constants are stored in every '
+                   'checkpoint (default: the checkpoint\'s).')
+    p.add_argument('--lc_norm_clip', type=float, default=None,
+                   help='--lc_normalize corpus: clamp the normalised '
+                   'features to [-C, C]')
+    p.add_argument('--lc_range', type=str, default=None,
+                   help='--lc_normalize range: LO,HI in log-mel units, e.g. '
+                   '-23,7')
+    # (argparse takes an argument that starts with '-' for a flag unless it
+    # looks like a negative number; "-23,7" has to look like one too)
+    num = r'(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?'
+    p._negative_number_matcher = re.compile(
+        r'^-%s(,[-+]?%s)?$' % (num, num))
+    p.add_argument('--lc_stats', type=str, default=None,
+                   help='--lc_normalize corpus: an .npz of per-channel sums '
+                   '(tools/make_lc_stats.py, or a run\'s lc_stats.npz)')
+
+
 _CLI_KEYS = ('n_fft', 'win_length', 'fmin', 'fmax')
+_NORM_KEYS = ('normalize', 'norm_clip', 'range', 'stats')
 
 
 def cli_flags_given(args):
     """The --lc_n_fft ... flags that were given, by name."""
-    return ['--lc_' + k for k in _CLI_KEYS
-            if getattr(args, 'lc_' + k) is not None]
+    return ['--lc_' + k for k in _CLI_KEYS + _NORM_KEYS
+            if getattr(args, 'lc_' + k, None) is not None]
 
 
-def spec_from_cli(args, sample_rate, n_mels, hop, stored=None):
-    """The MelSpec the flags ask for, or None without a front end.  `stored`:
+def parse_range(text):
+    """(lo, hi) of --lc_range LO,HI."""
+    try:
+        lo, hi = (float(v) for v in str(text).split(','))
+    except ValueError:
+        raise ValueError('--lc_range must be LO,HI (two numbers), got %r'
+                         % (text,))
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError('--lc_range needs finite LO < HI, got %r' % (text,))
+    return lo, hi
+
+
+def normalize_flags(args, corpus=False):
+    """ValueError where --lc_normalize, --lc_norm_clip, --lc_range and
+    --lc_stats do not fit together.  corpus: a device corpus will compute
+    the statistics."""
+    mode = getattr(args, 'lc_normalize', None)
+    clip = getattr(args, 'lc_norm_clip', None)
+    rng = getattr(args, 'lc_range', None)
+    stats = getattr(args, 'lc_stats', None)
+    if clip is not None and (not np.isfinite(clip) or not clip > 0):
+        raise ValueError('--lc_norm_clip must be positive, got %r' % (clip,))
+    if rng is not None:
+        if mode != 'range':
+            raise ValueError('--lc_range needs --lc_normalize range')
+        parse_range(rng)
+    if mode == 'range' and rng is None:
+        raise ValueError('--lc_normalize range needs --lc_range LO,HI')
+    if stats is not None and mode != 'corpus':
+        raise ValueError('--lc_stats needs --lc_normalize corpus')
+    if clip is not None and mode in ('none', 'range'):
+        raise ValueError('--lc_norm_clip does not go with --lc_normalize %s'
+                         % mode)
+    if mode == 'corpus' and stats is None and not corpus:
+        raise ValueError('--lc_normalize corpus needs --device_corpus true '
+                         'or --lc_stats FILE')
+
+
+def normalizer_from_cli(args, n_mels, stored=None, corpus=False):
+    """The Normalizer the flags ask for, or None.  stored: a checkpoint's
+    normaliser entry, the default without --lc_normalize (--lc_norm_clip
+    then replaces its clamp).  With --lc_normalize corpus and no --lc_stats
+    the corpus supplies it later (corpus=True): None."""
+    normalize_flags(args, corpus)
+    mode = getattr(args, 'lc_normalize', None)
+    clip = getattr(args, 'lc_norm_clip', None)
+    if mode == 'none':
+        return None
+    if mode == 'range':
+        return Normalizer.from_range(*parse_range(args.lc_range),
+                                     n_channels=n_mels)
+    if mode == 'corpus':
+        if args.lc_stats is None:
+            return None
+        try:
+            stats = FeatureStats.load(args.lc_stats)
+        except (OSError, KeyError) as e:
+            raise ValueError('--lc_stats %s: %s' % (args.lc_stats, e))
+        if stats.n_channels != n_mels:
+            raise ValueError('--lc_stats %s holds %d channels, the front end '
+                             'has %d mels' % (args.lc_stats, stats.n_channels,
+                                              n_mels))
+        return Normalizer.from_stats(stats, clip)
+    if stored is None:
+        if clip is not None:
+            raise ValueError('--lc_norm_clip needs --lc_normalize corpus')
+        return None
+    norm = Normalizer.from_entry(stored)
+    return norm if clip is None else norm.with_clip(clip)
+
+
+def spec_from_cli(args, sample_rate, n_mels, hop, stored=None, corpus=False):
+    """The MelSpec the flags ask for, or None without a front end (its
+    normaliser: normalizer_from_cli).  `stored`:
     a checkpoint's 'lc_features' entry -- without --lc_features it switches
     the front end on (--lc_features none: off), and its settings are the
     defaults of the flags that are absent.  ValueError where the flags, the
@@ -323,7 +805,11 @@ def spec_from_cli(args, sample_rate, n_mels, hop, stored=None):
     if hop is None:
         raise ValueError('--lc_features mel needs --lc_hop or '
                          '--lc_upsample_scales (hop = their product)')
-    return MelSpec(sample_rate, hop=hop, n_mels=n_mels, **kw)
+    entry = stored.get('normalizer') if stored is not None and \
+        stored.get('kind') == 'mel' else None
+    return MelSpec(sample_rate, hop=hop, n_mels=n_mels,
+                   normalizer=normalizer_from_cli(args, n_mels, entry, corpus),
+                   **kw)
 
 
 def checkpoint_entry(spec):

@@ -285,3 +285,23 @@ def any_rank(flag, device='cpu'):
     t = torch.tensor([1 if flag else 0], dtype=torch.int64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     return bool(int(t.cpu()[0]))
+
+
+def sum_float64_over_ranks(vec, device='cpu'):
+    """Sum over the ranks of a small host float64 vector (a corpus shard's
+    feature statistics, features.FeatureStats.vector): every rank gathers all
+    ranks' vectors and adds them in rank order, so every rank ends with the
+    same bits, those of a host that merges the shards in rank order -- an
+    all-reduce's order is the backend's.  Returns a float64 numpy array."""
+    import numpy as np
+    v = np.ascontiguousarray(np.asarray(vec, np.float64)).reshape(-1)
+    if not is_distributed():
+        return v.copy()
+    group, device = _ctl(device)
+    t = torch.from_numpy(v.copy()).to(device)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(parts, t, group=group)
+    out = parts[0].cpu().numpy().copy()
+    for q in parts[1:]:
+        out = out + q.cpu().numpy()
+    return out

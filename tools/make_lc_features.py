@@ -15,6 +15,11 @@ is a multiple of 512, so where the hop divides 512 the frames of a whole
 utterance are exactly what train.py --lc_features mel computes for it.  Unlike
 there, a piece cut by --sample_size keeps the context of its file.
 Give --silence_threshold as to train.py (its default is train.py's).
+
+With --lc_normalize corpus --lc_stats FILE [--lc_norm_clip C] (FILE from
+tools/make_lc_stats.py or a run's lc_stats.npz) or --lc_normalize range
+--lc_range LO,HI the frames of the utterance are normalised on the device as
+train.py does; the frames outside it stay zeros.
 """
 import argparse
 import os
@@ -46,6 +51,10 @@ def get_arguments(argv=None):
     if args.lc_features == 'none':
         p.error('--lc_features none: nothing to write')
     args.lc_features = 'mel'
+    try:
+        features.normalize_flags(args)
+    except ValueError as e:
+        p.error(str(e))
     return args
 
 
@@ -71,7 +80,7 @@ def main(argv=None):
     try:
         spec = features.spec_from_cli(args, args.sample_rate,
                                       args.lc_channels, args.lc_hop)
-    except ValueError as e:
+    except (ValueError, OSError) as e:
         print(str(e))
         return 1
     files = ar.find_files(args.directory)

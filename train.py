@@ -209,6 +209,10 @@ def get_arguments(argv=None):
         if args.lc_hop is None and args.lc_upsample_scales is None:
             p.error('--lc_features mel needs --lc_hop or '
                     '--lc_upsample_scales (hop = their product)')
+        try:
+            features.normalize_flags(args, corpus=args.device_corpus)
+        except ValueError as e:
+            p.error(str(e))
     elif features.cli_flags_given(args):
         p.error('%s needs --lc_features mel'
                 % features.cli_flags_given(args)[0])
@@ -329,6 +333,16 @@ def load(net, logdir, optimizer=None, entries=None):
             entries['device_corpus'] = ckpt['device_corpus']
     print(" Done.")
     return global_step
+
+
+def stored_normalizer(logdir):
+    """The normaliser entry in the 'lc_features' of logdir's newest
+    checkpoint, or None (no checkpoint, not one of ours, no normaliser)."""
+    path = latest_checkpoint(logdir) if os.path.isdir(logdir) else None
+    if path is None or tf_checkpoint.checkpoint_format(path):
+        return None
+    entry = torch.load(path, map_location='cpu').get('lc_features') or {}
+    return entry.get('normalizer')
 
 
 def corpus_first_batch(stored, entry):
@@ -472,11 +486,31 @@ def main(argv=None):
     spec = None
     try:
         spec = features.spec_from_cli(args, wavenet_params['sample_rate'],
-                                      args.lc_channels, lc_hop)
-    except ValueError as e:
+                                      args.lc_channels, lc_hop,
+                                      corpus=args.device_corpus)
+    except (ValueError, OSError) as e:
         print(str(e))
         return 1
-    lc_entry = None if spec is None else features.checkpoint_entry(spec)
+    # --lc_normalize corpus without --lc_stats: the corpus supplies the
+    # statistics below.  A run continued in its logdir keeps the normaliser
+    # of its checkpoint instead (--lc_normalize none / range still decide).
+    lc_stats = features.FeatureStats.load(args.lc_stats) \
+        if spec is not None and args.lc_stats is not None else None
+    kept_norm = None
+    if spec is not None and not is_overwritten_training and \
+            args.lc_normalize in (None, 'corpus'):
+        kept = stored_normalizer(restore_from)
+        if kept is not None:
+            kept_norm = features.Normalizer.from_entry(kept)
+            print('  The checkpoint\'s feature normaliser continues.')
+            spec = spec.with_normalizer(kept_norm)
+    from_corpus = spec is not None and args.lc_normalize == 'corpus' and \
+        args.lc_stats is None
+    stats_sum = None
+    if from_corpus and world > 1:
+        def stats_sum(v):
+            return parallel.sum_float64_over_ranks(
+                v, 'cuda' if torch.cuda.is_available() else 'cpu')
     file_lc = None if spec is not None else args.lc_channels
     corpus = corpus_entry = corpus_lc = None
     if args.device_corpus:
@@ -484,16 +518,38 @@ def main(argv=None):
         # the training batches (wavenet/corpus.py)
         from wavenet.corpus import DeviceCorpus
         utt_ctx = args.lc_feature_context == 'utterance'
+        corpus_norm = {}
+        if utt_ctx and from_corpus:
+            # the resident frames: summed and normalised in place at load
+            corpus_norm = dict(normalize=kept_norm, stats_allreduce=stats_sum) \
+                if kept_norm is not None else \
+                dict(normalize='corpus', normalize_clip=args.lc_norm_clip,
+                     stats_allreduce=stats_sum)
         try:
             corpus = reader = DeviceCorpus(
                 args.data_dir, wavenet_params['sample_rate'], gc_enabled,
                 sample_size=args.sample_size or None,
                 silence_threshold=silence_threshold,
                 crop=args.crop or 'pieces', seed=CORPUS_SEED, rank=rank,
-                world=world, spec=spec if utt_ctx else None)
+                world=world, spec=spec if utt_ctx else None, **corpus_norm)
         except (ValueError, MemoryError) as e:
             print(str(e))
             return 1
+        if from_corpus:
+            if utt_ctx:
+                lc_stats, spec = corpus.feature_stats, corpus.spec
+            elif kept_norm is None:
+                # no frames are resident: one pass over the utterances
+                lc_stats = corpus.compute_feature_stats(spec, stats_sum)
+            if kept_norm is None:
+                spec = spec.with_normalizer(features.Normalizer.from_stats(
+                    lc_stats, args.lc_norm_clip))
+            elif lc_stats is not None:
+                fresh = features.Normalizer.from_stats(lc_stats)
+                if not (np.array_equal(fresh.shift, kept_norm.shift) and
+                        np.array_equal(fresh.scale, kept_norm.scale)):
+                    print('  The corpus\'s feature statistics differ from '
+                          'the checkpoint\'s normaliser, which is kept.')
         if utt_ctx:
             corpus_lc = 'frames' if lc_scales is not None else 'rows'
         corpus_entry = dict(crop=args.crop or 'pieces', seed=CORPUS_SEED,
@@ -518,6 +574,11 @@ def main(argv=None):
                              rank=rank, world=world, seed=rank,
                              lc_channels=file_lc,
                              lc_hop=lc_hop, lc_frames=lc_scales is not None)
+
+    lc_entry = None if spec is None else features.checkpoint_entry(spec)
+    if lc_stats is not None and rank == 0:
+        os.makedirs(logdir, exist_ok=True)
+        lc_stats.save(os.path.join(logdir, 'lc_stats.npz'))
 
     net = WaveNetModel(
         batch_size=args.batch_size,
