@@ -9,10 +9,10 @@ prediction).  The clips are prepared as train.py's reader prepares them
 (wavenet/evaluate.py's ValidationSet: sorted files, one pass, pieces per
 file; with --lc_features mel, or a checkpoint that train.py --lc_features
 wrote, the local conditioning is computed on the device from each batch's
-audio and no <clip>.npy is read); the model flags are generate.py's, the checkpoint is loaded through
-generate.py's own function, --use_ema true scores the checkpoint's EMA
-weights.  Without --sample_size whole utterances are scored, batched by
-length.
+audio and no <clip>.npy is read); the model flags are generate.py's, the
+checkpoint is loaded as generate.py loads it (wavenet/checkpoint.py),
+--use_ema true scores the checkpoint's EMA weights.  Without --sample_size
+whole utterances are scored, batched by length.
 """
 from __future__ import print_function
 
@@ -23,13 +23,15 @@ import sys
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
-sys.path.insert(0, ROOT)
 
-import generate  # noqa: E402
 from wavenet import features, local_condition  # noqa: E402
+from wavenet.checkpoint import (  # noqa: E402
+    open_ema_checkpoint, restore, stored_lc_features)
+from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
 BATCH_SIZE = 8
 SILENCE_THRESHOLD = 0.3        # train.py's
+WAVENET_PARAMS = './wavenet_params.json'   # generate.py's
 
 
 def get_arguments(argv=None):
@@ -38,7 +40,7 @@ def get_arguments(argv=None):
                    help='Which model checkpoint to evaluate')
     p.add_argument('--data_dir', type=str, required=True,
                    help='The directory containing the held-out wav files.')
-    p.add_argument('--use_ema', type=generate._str_to_bool, default=False,
+    p.add_argument('--use_ema', type=str_to_bool, default=False,
                    help='score the checkpoint\'s exponential moving average '
                    'of the weights (train.py --ema_decay)')
     p.add_argument('--sample_size', type=int, default=None,
@@ -50,7 +52,7 @@ def get_arguments(argv=None):
     p.add_argument('--silence_threshold', type=float,
                    default=SILENCE_THRESHOLD)
     p.add_argument('--wavenet_params', type=str,
-                   default=generate.WAVENET_PARAMS)
+                   default=WAVENET_PARAMS)
     p.add_argument('--gc_channels', type=int, default=None)
     p.add_argument('--gc_cardinality', type=int, default=None)
     p.add_argument('--lc_channels', type=int, default=None,
@@ -82,7 +84,7 @@ def main(argv=None):
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
     try:
-        stored = generate.stored_lc_features(args.checkpoint)
+        stored = stored_lc_features(args.checkpoint)
         if args.lc_channels is None and args.lc_features != 'none' and \
                 stored is not None:
             # (a checkpoint trained on its own front end names its mels)
@@ -104,11 +106,10 @@ def main(argv=None):
         return 1
     ckpt = None
     if args.use_ema:
-        ckpt, why = generate.open_ema_checkpoint(args.checkpoint)
+        ckpt, why = open_ema_checkpoint(args.checkpoint)
         if why:
             print(why)
             return 1
-    from wavenet import WaveNetModel
     from wavenet import evaluate as ev
     gc_enabled = args.gc_channels is not None
     try:
@@ -122,25 +123,15 @@ def main(argv=None):
     except ValueError as e:
         print(str(e))
         return 1
-    net = WaveNetModel(
-        batch_size=args.batch_size,
-        dilations=wavenet_params['dilations'],
-        filter_width=wavenet_params['filter_width'],
-        residual_channels=wavenet_params['residual_channels'],
-        dilation_channels=wavenet_params['dilation_channels'],
-        quantization_channels=wavenet_params['quantization_channels'],
-        skip_channels=wavenet_params['skip_channels'],
-        use_biases=wavenet_params['use_biases'],
-        scalar_input=wavenet_params['scalar_input'],
-        initial_filter_width=wavenet_params['initial_filter_width'],
+    net = model_from_params(
+        wavenet_params, args.batch_size,
         global_condition_channels=args.gc_channels,
         global_condition_cardinality=args.gc_cardinality,
-        residual_postproc=wavenet_params.get("residual_postproc", False),
         local_condition_channels=args.lc_channels,
         local_condition_upsample_scales=lc_scales,
         local_condition_context=lc_ctx)
-    why = generate.restore(net, args.checkpoint, args.use_ema, ckpt,
-                           check_lc=args.lc_channels is not None)
+    why = restore(net, args.checkpoint, args.use_ema, ckpt,
+                  check_lc=args.lc_channels is not None)
     if why:
         print(why)
         return 1

@@ -43,9 +43,11 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402
 from wavenet import features, local_condition, sampling  # noqa: E402
-from wavenet import tf_checkpoint  # noqa: E402
+from wavenet.checkpoint import (  # noqa: E402,F401
+    context_mismatch, open_ema_checkpoint, restore, stored_lc_features,
+    upsampler_mismatch)
+from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
 SAMPLES = 16000
 TEMPERATURE = 1.0
@@ -54,12 +56,6 @@ WINDOW = 8000
 WAVENET_PARAMS = './wavenet_params.json'
 SAVE_EVERY = None
 SILENCE_THRESHOLD = 0.1
-
-
-def _str_to_bool(s):
-    if s.lower() not in ('true', 'false'):
-        raise ValueError('Argument needs to be a boolean, got {}'.format(s))
-    return s.lower() == 'true'
 
 
 def _ensure_positive_float(f):
@@ -110,7 +106,7 @@ def get_arguments(argv=None):
     p.add_argument('--wavenet_params', type=str, default=WAVENET_PARAMS)
     p.add_argument('--wav_out_path', type=str, default=None)
     p.add_argument('--save_every', type=int, default=SAVE_EVERY)
-    p.add_argument('--fast_generation', type=_str_to_bool, default=True)
+    p.add_argument('--fast_generation', type=str_to_bool, default=True)
     p.add_argument('--wav_seed', type=str, default=None)
     p.add_argument('--gc_channels', type=int, default=None)
     p.add_argument('--gc_cardinality', type=int, default=None)
@@ -124,7 +120,7 @@ def get_arguments(argv=None):
                    help='local conditioning features (.npy, [frames, '
                    'channels]); needs --fast_generation false or '
                    '--lc_fast_generation true')
-    p.add_argument('--lc_fast_generation', type=_str_to_bool, default=False,
+    p.add_argument('--lc_fast_generation', type=str_to_bool, default=False,
                    help='with --lc_path: generate on the fast path '
                    '(default false: --lc_path needs --fast_generation false)')
     p.add_argument('--lc_hop', type=int, default=1,
@@ -138,7 +134,7 @@ def get_arguments(argv=None):
     p.add_argument('--gc_ids', type=str, default=None,
                    help='comma-separated global condition ids, one clip each '
                    '(sets --clips to their number)')
-    p.add_argument('--use_ema', type=_str_to_bool, default=False,
+    p.add_argument('--use_ema', type=str_to_bool, default=False,
                    help='generate from the checkpoint\'s exponential moving '
                    'average of the weights (train.py --ema_decay)')
     p.add_argument('--lc_wav', type=str, default=None,
@@ -209,85 +205,6 @@ def create_seed(filename, sample_rate, quantization_channels,
     return quantized[:min(int(quantized.numel()), window_size)]
 
 
-def upsampler_mismatch(net, sd):
-    """A message when the checkpoint's upsampler variables (state dict `sd`)
-    and the model's (--lc_upsample_scales) differ, else None."""
-    mine = {n: tuple(v.shape) for n, v in net.named_variables()
-            if '/lc_upsample/' in n}
-    theirs = {n: tuple(np.shape(v)) for n, v in sd.items()
-              if '/lc_upsample/' in n}
-    if mine == theirs:
-        return None
-    def desc(d):
-        filt = [d[n][0] for n in sorted(d) if n.endswith('/filter')]
-        return ','.join(str(s) for s in filt) if filt else 'none'
-    return ('the checkpoint\'s learned upsampler (wavenet/lc_upsample/..., '
-            'scales %s) does not match --lc_upsample_scales (scales %s)'
-            % (desc(theirs), desc(mine)))
-
-
-def context_mismatch(net, sd):
-    """A message when the checkpoint's frame-context filter (state dict
-    `sd`) and the model's (--lc_context) differ, else None."""
-    name = 'wavenet/lc_context/filter'
-    mine = dict(net.named_variables()).get(name)
-    mine = None if mine is None else tuple(mine.shape)
-    theirs = tuple(np.shape(sd[name])) if name in sd else None
-    if mine == theirs:
-        return None
-    def desc(shape):
-        return 'none' if shape is None else 'P = %d, shape %s' % (
-            (shape[0] - 1) // 2, 'x'.join(str(n) for n in shape))
-    return ('the checkpoint\'s frame-context filter (%s, %s) does not match '
-            '--lc_context (%s)' % (name, desc(theirs), desc(mine)))
-
-
-def open_ema_checkpoint(path):
-    """--use_ema true: (the checkpoint, None), or (None, why it holds no EMA
-    weights)."""
-    if tf_checkpoint.checkpoint_format(path):
-        return None, ('--use_ema true: a TensorFlow checkpoint holds no EMA '
-                      'weights.')
-    ckpt = torch.load(path, map_location='cpu')
-    if 'ema_variables' not in ckpt:
-        return None, ('--use_ema true: the checkpoint {} holds no EMA weights '
-                      '(`ema_variables`); train with train.py --ema_decay.'
-                      .format(path))
-    return ckpt, None
-
-
-def stored_lc_features(path, ckpt=None):
-    """The 'lc_features' entry train.py --lc_features wrote into the
-    checkpoint at `path` (`ckpt` where the caller holds it), else None."""
-    if ckpt is None:
-        if tf_checkpoint.checkpoint_format(path) or not os.path.isfile(path):
-            return None
-        ckpt = torch.load(path, map_location='cpu')
-    return ckpt.get('lc_features')
-
-
-def restore(net, path, use_ema=False, ckpt=None, check_lc=False):
-    """Load the checkpoint at `path` into `net` (evaluate.py shares this):
-    the reference's own TensorFlow format, or train.py's torch file `ckpt`
-    (read here unless the caller holds it), its `ema_variables` with use_ema.
-    check_lc: compare the learned upsampler's and the context filter's shapes
-    first.  Returns a message when they do not match, else None."""
-    print('Restoring model from {}'.format(path))
-    if tf_checkpoint.checkpoint_format(path):
-        # a checkpoint written by the reference itself (tf.train.Saver)
-        tf_checkpoint.load_into(net, path)
-        return None
-    if ckpt is None:
-        ckpt = torch.load(path, map_location='cpu')
-    sd = ckpt['ema_variables' if use_ema else 'variables']
-    if check_lc:
-        why = upsampler_mismatch(net, sd) or context_mismatch(net, sd)
-        if why:
-            return why
-    net.load_state_dict(sd)
-    return None
-
-
 def main(argv=None):
     args = get_arguments(argv)
     ckpt = None
@@ -302,13 +219,19 @@ def main(argv=None):
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
     n_wav = None
-    if args.lc_wav is not None:
-        # (the hop is the model's: the scales' product, else --lc_hop, whose
-        # default 1 counts as absent, else the checkpoint's)
+    if args.lc_path is not None or args.lc_wav is not None:
         try:
-            hop = local_condition.parse_cli(
+            # (--lc_hop 1, the default, counts as absent)
+            lc_scales, hop, lc_ctx = local_condition.parse_cli(
                 args.lc_upsample_scales, None if args.lc_hop == 1 else
-                args.lc_hop, args.lc_context)[1]
+                args.lc_hop, args.lc_context)
+        except ValueError as e:
+            print(str(e))
+            return 1
+    if args.lc_wav is not None:
+        # (the hop is the model's: the scales' product, else --lc_hop, else
+        # the checkpoint's)
+        try:
             spec = features.spec_from_cli(
                 args, wavenet_params['sample_rate'], args.lc_channels, hop,
                 stored_lc_features(args.checkpoint, ckpt))
@@ -343,14 +266,6 @@ def main(argv=None):
             print('--lc_path must hold [frames, channels] features and '
                   '--lc_hop must be positive')
             return 1
-        try:
-            # (--lc_hop 1, the default, counts as absent)
-            lc_scales, hop, lc_ctx = local_condition.parse_cli(
-                args.lc_upsample_scales, None if args.lc_hop == 1 else
-                args.lc_hop, args.lc_context)
-        except ValueError as e:
-            print(str(e))
-            return 1
         if lc_scales is not None:
             # (the rows come from the model's upsampler once it is loaded)
             lc_rows = np.zeros((feats.shape[0] * hop, feats.shape[1]),
@@ -361,23 +276,12 @@ def main(argv=None):
         if n_wav is not None:
             lc_rows = lc_rows[:n_wav]       # (the wav's own length)
         args.samples = lc_rows.shape[0]
-    from wavenet import WaveNetModel, mu_law_decode
+    from wavenet import mu_law_decode
     started = "{0:%Y-%m-%dT%H-%M-%S}".format(datetime.now())
     logdir = os.path.join(args.logdir, 'generate', started)
-    net = WaveNetModel(
-        batch_size=1,
-        dilations=wavenet_params['dilations'],
-        filter_width=wavenet_params['filter_width'],
-        residual_channels=wavenet_params['residual_channels'],
-        dilation_channels=wavenet_params['dilation_channels'],
-        quantization_channels=wavenet_params['quantization_channels'],
-        skip_channels=wavenet_params['skip_channels'],
-        use_biases=wavenet_params['use_biases'],
-        scalar_input=wavenet_params['scalar_input'],
-        initial_filter_width=wavenet_params['initial_filter_width'],
-        global_condition_channels=args.gc_channels,
+    net = model_from_params(
+        wavenet_params, 1, global_condition_channels=args.gc_channels,
         global_condition_cardinality=args.gc_cardinality,
-        residual_postproc=wavenet_params.get("residual_postproc", False),
         local_condition_channels=None if lc_rows is None else lc_rows.shape[1],
         local_condition_upsample_scales=lc_scales,
         local_condition_context=lc_ctx)

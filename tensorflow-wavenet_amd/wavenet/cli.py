@@ -1,0 +1,28 @@
+"""What train.py, generate.py and evaluate.py share on the command line."""
+
+
+def str_to_bool(s):
+    if s.lower() not in ('true', 'false'):
+        raise ValueError('Argument needs to be a boolean, got {}'.format(s))
+    return s.lower() == 'true'
+
+
+def model_from_params(wavenet_params, batch_size, **conditioning):
+    """The WaveNetModel of a wavenet_params.json dict.  `conditioning`: the
+    keywords the command line decides instead (global_condition_*,
+    local_condition_*, histograms)."""
+    # (looked up at the call: a test may have put a stub in its place)
+    from . import WaveNetModel
+    return WaveNetModel(
+        batch_size=batch_size,
+        dilations=wavenet_params['dilations'],
+        filter_width=wavenet_params['filter_width'],
+        residual_channels=wavenet_params['residual_channels'],
+        dilation_channels=wavenet_params['dilation_channels'],
+        skip_channels=wavenet_params['skip_channels'],
+        quantization_channels=wavenet_params['quantization_channels'],
+        use_biases=wavenet_params['use_biases'],
+        scalar_input=wavenet_params['scalar_input'],
+        initial_filter_width=wavenet_params['initial_filter_width'],
+        residual_postproc=wavenet_params.get('residual_postproc', False),
+        **conditioning)

@@ -135,6 +135,27 @@ def test_train_histogram_summaries(hip_lib, tmp_path, params):
     assert z['layer0_filter/counts'].sum() == 2 * 32 * 32
 
 
+def test_step_log_fetches_survive_a_skipped_step(tmp_path):
+    """A fetch for step 0, then -- step 1 was skipped -- one for step 2, both
+    in flight: each keeps its own pinned slot, for the loss (tag 0) and for
+    the norm (tag 1).  (Slots chosen by the step's parity gave step 2's value
+    twice.)"""
+    from wavenet.training import StepLog
+    log = StepLog(None, str(tmp_path), rank=0)
+    try:
+        for tag in (0, 1):
+            one = torch.full((), 1.0, device='cuda')
+            two = torch.full((), 2.0, device='cuda')
+            first, first_done = log.fetch_later(one, tag=tag)      # step 0
+            second, second_done = log.fetch_later(two, tag=tag)    # step 2
+            first_done.synchronize()
+            second_done.synchronize()
+            assert float(first) == 1.0 and float(second) == 2.0
+            assert first.is_pinned() and second.is_pinned()
+    finally:
+        log.close()
+
+
 def test_bench_line_carries_the_contract(hip_lib, tmp_path):
     """`python bench.py` (small shape): ONE JSON line with the driver's keys,
     the roofline object measured live (NN GEMMs + the TN GEMMs beside them),

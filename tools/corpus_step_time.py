@@ -4,7 +4,8 @@ minimize) fed three ways in one process --
 
     resident  one synthetic batch that stays on the device (bench.py's step)
     reader    AudioReader on a wav tree: its thread, dequeue's numpy padding
-              and train.py's stage_in copy on a side stream
+              and the training loop's copy on a side stream
+              (wavenet/training.py, StageIn)
     corpus    DeviceCorpus.batch: the batch cut on the device by the kernel
 
 The tool writes a VCTK-shaped tree of 16 kHz wavs (p<id>/p<id>_<n>.wav, a few
@@ -73,6 +74,7 @@ def main(argv=None):
     from wavenet import AudioReader, optimizer_factory
     from wavenet.audio_reader import Coordinator
     from wavenet.corpus import DeviceCorpus
+    from wavenet.training import StageIn
     params = json.load(open(os.path.join(ROOT, 'wavenet_params.json')))
     rate, B, T = params['sample_rate'], a.batch, a.samples
     tree = tempfile.mkdtemp(prefix='corpus_step_time_')
@@ -94,15 +96,7 @@ def main(argv=None):
                              sample_size=T,
                              silence_threshold=SILENCE_THRESHOLD, seed=0)
         threads = reader.start_threads()
-        copy_stream = torch.cuda.Stream(device=net.device)
-
-        def stage_in(host):
-            """train.py's stage_in."""
-            with torch.cuda.stream(copy_stream):
-                dev = host.contiguous().to(net.device)
-            torch.cuda.current_stream().wait_stream(copy_stream)
-            dev.record_stream(torch.cuda.current_stream())
-            return dev
+        stage_in = StageIn(net.device)
 
         def from_reader():
             while True:             # (eight short last pieces: next batch)

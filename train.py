@@ -15,10 +15,9 @@ name: tensor}; scalars go to <logdir>/events.jsonl (TensorBoard is TF-only).
 from __future__ import print_function
 
 import argparse
-import glob
+import collections
 import json
 import os
-import re
 import sys
 import time
 from datetime import datetime
@@ -28,7 +27,10 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import features, local_condition, tf_checkpoint  # noqa: E402
+from wavenet import features, local_condition  # noqa: E402
+from wavenet.checkpoint import (  # noqa: E402,F401
+    checkpoint_path, latest_checkpoint, load, open_latest, save)
+from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
 BATCH_SIZE = 1
 DATA_DIRECTORY = './VCTK-Corpus'
@@ -44,12 +46,6 @@ SILENCE_THRESHOLD = 0.3
 EPSILON = 0.001
 CORPUS_SEED = 0             # --device_corpus: every rank's index, every run
 MOMENTUM = 0.9
-
-
-def _str_to_bool(s):
-    if s.lower() not in ('true', 'false'):
-        raise ValueError('Argument needs to be a boolean, got {}'.format(s))
-    return s.lower() == 'true'
 
 
 def get_arguments(argv=None):
@@ -83,10 +79,10 @@ def get_arguments(argv=None):
     p.add_argument('--optimizer', type=str, default='adam',
                    choices=['adam', 'sgd', 'rmsprop'])
     p.add_argument('--momentum', type=float, default=MOMENTUM)
-    p.add_argument('--histograms', type=_str_to_bool, default=False)
+    p.add_argument('--histograms', type=str_to_bool, default=False)
     p.add_argument('--gc_channels', type=int, default=None,
                    help='Number of global condition channels.')
-    p.add_argument('--dp_overlap_allreduce', type=_str_to_bool, default=False,
+    p.add_argument('--dp_overlap_allreduce', type=str_to_bool, default=False,
                    help='Data-parallel runs: all-reduce the skip / '
                         'post-processing gradients on a communication stream '
                         'beside the backward stack (two calls per step) '
@@ -118,7 +114,7 @@ def get_arguments(argv=None):
                         'frames (P frames either side, channels to channels) '
                         'in front of the upsampler, 0 <= P <= 8.  Needs '
                         '--lc_upsample_scales.')
-    p.add_argument('--mask_padding', type=_str_to_bool, default=False,
+    p.add_argument('--mask_padding', type=str_to_bool, default=False,
                    help='Batches of clips of different lengths: pass the '
                         'clips\' real lengths to the loss, so that the zero '
                         'padding behind the shorter ones is neither learned '
@@ -149,7 +145,7 @@ def get_arguments(argv=None):
     p.add_argument('--validation_batches', type=int, default=None,
                    help='Score at most this many batches per rank and '
                         'validation (default: the whole directory).')
-    p.add_argument('--validate_ema', type=_str_to_bool, default=False,
+    p.add_argument('--validate_ema', type=str_to_bool, default=False,
                    help='Validate the exponential moving average of the '
                         'weights instead of the weights (needs --ema_decay).')
     features.add_cli_flags(
@@ -157,7 +153,7 @@ def get_arguments(argv=None):
         'with --mask_padding true the clips\' lengths go to the front end '
         'too.  The settings are stored in every checkpoint (\'lc_features\') '
         'and --validation_dir is scored through the same front end.')
-    p.add_argument('--device_corpus', type=_str_to_bool, default=False,
+    p.add_argument('--device_corpus', type=str_to_bool, default=False,
                    help='Keep the whole trimmed --data_dir on the device and '
                         'cut every training batch there with a kernel '
                         '(wavenet/corpus.py): no reader thread, no copy per '
@@ -251,98 +247,6 @@ def lc_context(args):
         return None
     return local_condition.parse_cli(args.lc_upsample_scales, None,
                                      args.lc_context)[2]
-
-
-def checkpoint_path(logdir, step):
-    return os.path.join(logdir, 'model.ckpt-{}'.format(step))
-
-
-def save(net, logdir, step, optimizer=None, lc_features=None,
-         device_corpus=None):
-    """`optimizer`: its step count, slots and shadow go in as 'optimizer'
-    and, with EMA weights, the shadow as 'ema_variables' (the keys of
-    'variables').  `lc_features`: the front end's settings
-    (features.checkpoint_entry), stored under 'lc_features'.
-    `device_corpus`: the settings of --device_corpus (crop, seed,
-    sample_size, lc_feature_context) and the index of the last batch taken
-    ('batch'), stored under 'device_corpus'."""
-    print('Storing checkpoint to {} ...'.format(logdir), end="")
-    sys.stdout.flush()
-    os.makedirs(logdir, exist_ok=True)
-    path = checkpoint_path(logdir, step)
-    ckpt = {'variables': net.state_dict(), 'step': step}
-    if lc_features is not None:
-        ckpt['lc_features'] = lc_features
-    if device_corpus is not None:
-        ckpt['device_corpus'] = device_corpus
-    if optimizer is not None:
-        ckpt['optimizer'] = optimizer.state_dict()
-        if optimizer.ema_decay is not None:
-            ckpt['ema_variables'] = optimizer.ema_state_dict(net)
-    torch.save(ckpt, path)
-    with open(os.path.join(logdir, 'checkpoint'), 'w') as f:
-        f.write('model_checkpoint_path: "{}"\n'.format(os.path.basename(path)))
-    print(' Done.')
-
-
-def latest_checkpoint(logdir):
-    """Newest `model.ckpt-<step>` in logdir, or None."""
-    marker = os.path.join(logdir, 'checkpoint')
-    if os.path.exists(marker):
-        name = open(marker).read().split('"')[1]
-        path = os.path.join(logdir, name)
-        # (a TensorFlow V2 checkpoint is a prefix: model.ckpt-N.index / .data-*)
-        if os.path.exists(path) or tf_checkpoint.checkpoint_format(path):
-            return path
-    # only `model.ckpt-<step>` itself or a V2 prefix's `.index`: a V2 data
-    # shard (`model.ckpt-N.data-00000-of-00001`) and `.meta` also end in
-    # digits / start with the prefix, and must not be taken for a checkpoint
-    found = {}
-    for f in glob.glob(os.path.join(logdir, 'model.ckpt-*')):
-        base = f[:-len('.index')] if f.endswith('.index') else f
-        m = re.match(r'model\.ckpt-(\d+)$', os.path.basename(base))
-        if m:
-            found[base] = int(m.group(1))
-    return max(found, key=found.get) if found else None
-
-
-def load(net, logdir, optimizer=None, entries=None):
-    """`optimizer`: restored from the checkpoint's 'optimizer' entry when it
-    has one (checkpoints written before it existed, and the reference's own,
-    have none: the optimizer then starts afresh, as it always did).
-    `entries`: a dict that receives the checkpoint's 'device_corpus' entry."""
-    print("Trying to restore saved checkpoints from {} ...".format(logdir),
-          end="")
-    path = latest_checkpoint(logdir) if os.path.isdir(logdir) else None
-    if path is None:
-        print(" No checkpoint found.")
-        return None
-    print("  Checkpoint found: {}".format(path))
-    global_step = int(path.split('/')[-1].split('-')[-1])
-    print("  Global step was: {}".format(global_step))
-    print("  Restoring...", end="")
-    if tf_checkpoint.checkpoint_format(path):
-        # written by the reference's tf.train.Saver (train.py:104-114 there)
-        tf_checkpoint.load_into(net, path)
-    else:
-        ckpt = torch.load(path, map_location='cpu')
-        net.load_state_dict(ckpt['variables'])
-        if optimizer is not None and 'optimizer' in ckpt:
-            optimizer.load_state_dict(ckpt['optimizer'], net)
-        if entries is not None and 'device_corpus' in ckpt:
-            entries['device_corpus'] = ckpt['device_corpus']
-    print(" Done.")
-    return global_step
-
-
-def stored_normalizer(logdir):
-    """The normaliser entry in the 'lc_features' of logdir's newest
-    checkpoint, or None (no checkpoint, not one of ours, no normaliser)."""
-    path = latest_checkpoint(logdir) if os.path.isdir(logdir) else None
-    if path is None or tf_checkpoint.checkpoint_format(path):
-        return None
-    entry = torch.load(path, map_location='cpu').get('lc_features') or {}
-    return entry.get('normalizer')
 
 
 def corpus_first_batch(stored, entry):
@@ -443,6 +347,181 @@ class SyntheticReader(object):
         return []
 
 
+FrontEnd = collections.namedtuple('FrontEnd',
+                                  'spec kept_norm lc_stats from_corpus')
+
+
+def front_end_from_flags(args, sample_rate, lc_hop, continued):
+    """--lc_features, before the corpus exists: FrontEnd(the MelSpec of the
+    flags or None, the normaliser kept from the checkpoint or None, the sums
+    of --lc_stats or None, whether the corpus has to supply the statistics).
+    `continued`: checkpoint.open_latest's result for a run that continues in
+    its logdir, else None.  ValueError / OSError: flags that do not fit.
+
+    The normaliser, by --lc_normalize, --lc_stats, a continued run whose
+    checkpoint stores a normaliser, and --lc_feature_context:
+
+      normalize     stats  continued  context    the spec's normaliser
+      none / range  -      any        any        none / the range; nothing is
+                                                 kept, nothing is summed
+      absent        -      no         any        none
+      absent        -      yes        any        the checkpoint's (*)
+      corpus        FILE   no         any        from FILE
+      corpus        FILE   yes        any        the checkpoint's (*)
+      corpus        -      no         utterance  the corpus sums its resident
+                                                 frames at load and
+                                                 normalises them in place
+      corpus        -      no         piece      from one pass over the
+                                                 utterances
+      corpus        -      yes        utterance  the checkpoint's (*), applied
+                                                 to the resident frames; their
+                                                 sums are compared with it
+                                                 ("... differ ... is kept")
+      corpus        -      yes        piece      the checkpoint's (*); no pass
+
+    (*) prints "The checkpoint's feature normaliser continues."  The last
+    four rows are decided in front_end_from_corpus.  <logdir>/lc_stats.npz
+    is written wherever sums exist: FILE's, or the corpus's (every `corpus -`
+    row but the last)."""
+    spec = features.spec_from_cli(args, sample_rate, args.lc_channels, lc_hop,
+                                  corpus=args.device_corpus)
+    lc_stats = features.FeatureStats.load(args.lc_stats) \
+        if spec is not None and args.lc_stats is not None else None
+    kept_norm = None
+    if spec is not None and continued is not None and \
+            continued.ckpt is not None and \
+            args.lc_normalize in (None, 'corpus'):
+        kept = (continued.ckpt.get('lc_features') or {}).get('normalizer')
+        if kept is not None:
+            kept_norm = features.Normalizer.from_entry(kept)
+            print('  The checkpoint\'s feature normaliser continues.')
+            spec = spec.with_normalizer(kept_norm)
+    from_corpus = spec is not None and args.lc_normalize == 'corpus' and \
+        args.lc_stats is None
+    return FrontEnd(spec, kept_norm, lc_stats, from_corpus)
+
+
+def stats_allreduce(front, world):
+    """How the corpus sums its feature statistics over the ranks, or None."""
+    if not (front.from_corpus and world > 1):
+        return None
+    from wavenet import parallel
+    return lambda v: parallel.sum_float64_over_ranks(
+        v, 'cuda' if torch.cuda.is_available() else 'cpu')
+
+
+def open_corpus(args, wavenet_params, front, rank, world):
+    """--device_corpus: the corpus on the device replaces the reader and its
+    threads for the training batches (wavenet/corpus.py)."""
+    from wavenet.corpus import DeviceCorpus
+    utt_ctx = args.lc_feature_context == 'utterance'
+    corpus_norm = {}
+    if utt_ctx and front.from_corpus:
+        # the resident frames: summed and normalised in place at load
+        stats_sum = stats_allreduce(front, world)
+        corpus_norm = \
+            dict(normalize=front.kept_norm, stats_allreduce=stats_sum) \
+            if front.kept_norm is not None else \
+            dict(normalize='corpus', normalize_clip=args.lc_norm_clip,
+                 stats_allreduce=stats_sum)
+    return DeviceCorpus(
+        args.data_dir, wavenet_params['sample_rate'],
+        args.gc_channels is not None, sample_size=args.sample_size or None,
+        silence_threshold=args.silence_threshold,
+        crop=args.crop or 'pieces', seed=CORPUS_SEED, rank=rank, world=world,
+        spec=front.spec if utt_ctx else None, **corpus_norm)
+
+
+def front_end_from_corpus(args, front, corpus, world):
+    """--lc_features, once the corpus is loaded: (spec, lc_stats) with the
+    corpus's statistics where it has to supply them
+    (front_end_from_flags's table)."""
+    spec, kept_norm, lc_stats, from_corpus = front
+    if not from_corpus:
+        return spec, lc_stats
+    if args.lc_feature_context == 'utterance':
+        lc_stats, spec = corpus.feature_stats, corpus.spec
+    elif kept_norm is None:
+        # no frames are resident: one pass over the utterances
+        lc_stats = corpus.compute_feature_stats(
+            spec, stats_allreduce(front, world))
+    if kept_norm is None:
+        spec = spec.with_normalizer(features.Normalizer.from_stats(
+            lc_stats, args.lc_norm_clip))
+    elif lc_stats is not None:
+        fresh = features.Normalizer.from_stats(lc_stats)
+        if not (np.array_equal(fresh.shift, kept_norm.shift) and
+                np.array_equal(fresh.scale, kept_norm.scale)):
+            print('  The corpus\'s feature statistics differ from '
+                  'the checkpoint\'s normaliser, which is kept.')
+    return spec, lc_stats
+
+
+def corpus_settings(args):
+    """What a checkpoint's 'device_corpus' entry says about the corpus."""
+    return dict(crop=args.crop or 'pieces', seed=CORPUS_SEED,
+                sample_size=args.sample_size or None,
+                lc_feature_context=args.lc_feature_context or 'piece')
+
+
+def build_source(args, wavenet_params, front, file_lc, lc_scales, lc_hop,
+                 rank, world):
+    """The training batches' source (wavenet/training.py) and the front end
+    as it stands once the source exists: (source, spec, lc_stats) -- or None,
+    having printed why not.  file_lc: the channels of <clip>.npy features."""
+    from wavenet import AudioReader, training
+    from wavenet.audio_reader import Coordinator
+    gc_enabled = args.gc_channels is not None
+    # what the source yields beside the audio: the files' features ...
+    lc_mode = None if file_lc is None else \
+        'frames' if lc_scales is not None else 'rows'
+    if args.device_corpus:
+        try:
+            corpus = open_corpus(args, wavenet_params, front, rank, world)
+        except (ValueError, MemoryError) as e:
+            print(str(e))
+            return None
+        spec, lc_stats = front_end_from_corpus(args, front, corpus, world)
+        # ... or the utterances' frames, which the corpus holds
+        if args.lc_feature_context == 'utterance':
+            lc_mode = 'frames' if lc_scales is not None else 'rows'
+        return training.CorpusSource(
+            corpus, corpus_settings(args), args.mask_padding, gc_enabled,
+            lc_mode), spec, lc_stats
+    coord = Coordinator()
+    if args.synthetic:
+        reader = SyntheticReader(
+            args.sample_size, args.gc_cardinality if gc_enabled else None,
+            rank=rank, lc_channels=file_lc, lc_hop=lc_hop or 1)
+    else:
+        if args.lc_channels is not None and not lc_hop:
+            print('--lc_channels needs --lc_hop (audio samples per feature '
+                  'frame)')
+            return None
+        # The reference computes `silence_threshold = None if below EPSILON`
+        # and then passes the RAW flag to the reader (train.py:211-220; SURVEY
+        # Appendix A: "do not fix silently") -- same here:
+        # `--silence_threshold 0` trims with a threshold of 0 (only exactly
+        # silent frames go) instead of skipping the trimming.
+        reader = AudioReader(
+            args.data_dir, coord, sample_rate=wavenet_params['sample_rate'],
+            gc_enabled=gc_enabled, sample_size=args.sample_size,
+            silence_threshold=args.silence_threshold, rank=rank, world=world,
+            seed=rank, lc_channels=file_lc, lc_hop=lc_hop,
+            lc_frames=lc_scales is not None)
+    return training.ReaderSource(reader, coord, args.mask_padding, gc_enabled,
+                                 lc_mode), front.spec, front.lc_stats
+
+
+def save_histograms(net, logdir, step):
+    """The reference's histogram summaries (model.py:314-325) as an .npz next
+    to the checkpoint."""
+    hs = net.histogram_summaries()
+    np.savez(os.path.join(logdir, 'histograms-%d.npz' % step),
+             **{k + '/counts': v[0] for k, v in hs.items()},
+             **{k + '/range': np.asarray(v[1:]) for k, v in hs.items()})
+
+
 def main(argv=None):
     args = get_arguments(argv)
     try:
@@ -463,138 +542,49 @@ def main(argv=None):
     # a restored model written somewhere else counts as a new training
     is_overwritten_training = logdir != restore_from
 
-    from wavenet import WaveNetModel, AudioReader, optimizer_factory, parallel
-    from wavenet.audio_reader import Coordinator
+    from wavenet import optimizer_factory, parallel, training
     rank, world, local = parallel.init_from_env(host_control_plane=True)
     if torch.cuda.is_available():
         torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
 
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
+    sample_rate = wavenet_params['sample_rate']
+    # (read once: the front end below and load() share it)
+    opened = open_latest(restore_from)
 
-    coord = Coordinator()
-    # The reference computes `silence_threshold = None if below EPSILON` and
-    # then passes the RAW flag to the reader (train.py:211-220; SURVEY Appendix
-    # A: "do not fix silently") -- same here: `--silence_threshold 0` trims with
-    # a threshold of 0 (only exactly silent frames go) instead of skipping the
-    # trimming.
-    silence_threshold = args.silence_threshold
     gc_enabled = args.gc_channels is not None
-    lc_enabled = args.lc_channels is not None
-    # --lc_features: the readers yield audio only, the features of every
-    # batch are computed on the device from the batch itself
-    spec = None
+    # --lc_features: the sources yield audio only, the features of every
+    # batch are computed on the device (by the loop from the batch as cut,
+    # by the corpus from the whole utterance).  A run continued in its logdir
+    # keeps the normaliser of its checkpoint.
     try:
-        spec = features.spec_from_cli(args, wavenet_params['sample_rate'],
-                                      args.lc_channels, lc_hop,
-                                      corpus=args.device_corpus)
+        front = front_end_from_flags(
+            args, sample_rate, lc_hop,
+            None if is_overwritten_training else opened)
     except (ValueError, OSError) as e:
         print(str(e))
         return 1
-    # --lc_normalize corpus without --lc_stats: the corpus supplies the
-    # statistics below.  A run continued in its logdir keeps the normaliser
-    # of its checkpoint instead (--lc_normalize none / range still decide).
-    lc_stats = features.FeatureStats.load(args.lc_stats) \
-        if spec is not None and args.lc_stats is not None else None
-    kept_norm = None
-    if spec is not None and not is_overwritten_training and \
-            args.lc_normalize in (None, 'corpus'):
-        kept = stored_normalizer(restore_from)
-        if kept is not None:
-            kept_norm = features.Normalizer.from_entry(kept)
-            print('  The checkpoint\'s feature normaliser continues.')
-            spec = spec.with_normalizer(kept_norm)
-    from_corpus = spec is not None and args.lc_normalize == 'corpus' and \
-        args.lc_stats is None
-    stats_sum = None
-    if from_corpus and world > 1:
-        def stats_sum(v):
-            return parallel.sum_float64_over_ranks(
-                v, 'cuda' if torch.cuda.is_available() else 'cpu')
-    file_lc = None if spec is not None else args.lc_channels
-    corpus = corpus_entry = corpus_lc = None
-    if args.device_corpus:
-        # the corpus on the device replaces the reader and its threads for
-        # the training batches (wavenet/corpus.py)
-        from wavenet.corpus import DeviceCorpus
-        utt_ctx = args.lc_feature_context == 'utterance'
-        corpus_norm = {}
-        if utt_ctx and from_corpus:
-            # the resident frames: summed and normalised in place at load
-            corpus_norm = dict(normalize=kept_norm, stats_allreduce=stats_sum) \
-                if kept_norm is not None else \
-                dict(normalize='corpus', normalize_clip=args.lc_norm_clip,
-                     stats_allreduce=stats_sum)
-        try:
-            corpus = reader = DeviceCorpus(
-                args.data_dir, wavenet_params['sample_rate'], gc_enabled,
-                sample_size=args.sample_size or None,
-                silence_threshold=silence_threshold,
-                crop=args.crop or 'pieces', seed=CORPUS_SEED, rank=rank,
-                world=world, spec=spec if utt_ctx else None, **corpus_norm)
-        except (ValueError, MemoryError) as e:
-            print(str(e))
-            return 1
-        if from_corpus:
-            if utt_ctx:
-                lc_stats, spec = corpus.feature_stats, corpus.spec
-            elif kept_norm is None:
-                # no frames are resident: one pass over the utterances
-                lc_stats = corpus.compute_feature_stats(spec, stats_sum)
-            if kept_norm is None:
-                spec = spec.with_normalizer(features.Normalizer.from_stats(
-                    lc_stats, args.lc_norm_clip))
-            elif lc_stats is not None:
-                fresh = features.Normalizer.from_stats(lc_stats)
-                if not (np.array_equal(fresh.shift, kept_norm.shift) and
-                        np.array_equal(fresh.scale, kept_norm.scale)):
-                    print('  The corpus\'s feature statistics differ from '
-                          'the checkpoint\'s normaliser, which is kept.')
-        if utt_ctx:
-            corpus_lc = 'frames' if lc_scales is not None else 'rows'
-        corpus_entry = dict(crop=args.crop or 'pieces', seed=CORPUS_SEED,
-                            sample_size=args.sample_size or None,
-                            lc_feature_context=args.lc_feature_context
-                            or 'piece')
-    elif args.synthetic:
-        reader = SyntheticReader(args.sample_size,
-                                 args.gc_cardinality if gc_enabled else None,
-                                 rank=rank, lc_channels=file_lc,
-                                 lc_hop=lc_hop or 1)
-    else:
-        if lc_enabled and not lc_hop:
-            print('--lc_channels needs --lc_hop (audio samples per feature '
-                  'frame)')
-            return 1
-        reader = AudioReader(args.data_dir, coord,
-                             sample_rate=wavenet_params['sample_rate'],
-                             gc_enabled=gc_enabled,
-                             sample_size=args.sample_size,
-                             silence_threshold=silence_threshold,
-                             rank=rank, world=world, seed=rank,
-                             lc_channels=file_lc,
-                             lc_hop=lc_hop, lc_frames=lc_scales is not None)
+    # (with a front end the readers yield audio only)
+    file_lc = None if front.spec is not None else args.lc_channels
+    built = build_source(args, wavenet_params, front, file_lc, lc_scales,
+                         lc_hop, rank, world)
+    if built is None:
+        return 1
+    source, spec, lc_stats = built
+    # (the one place that decides what lc is: the source's, or the front
+    # end's of the batch as the source cut it)
+    lc_from_batch = spec is not None and source.lc is None
 
     lc_entry = None if spec is None else features.checkpoint_entry(spec)
     if lc_stats is not None and rank == 0:
         os.makedirs(logdir, exist_ok=True)
         lc_stats.save(os.path.join(logdir, 'lc_stats.npz'))
 
-    net = WaveNetModel(
-        batch_size=args.batch_size,
-        dilations=wavenet_params["dilations"],
-        filter_width=wavenet_params["filter_width"],
-        residual_channels=wavenet_params["residual_channels"],
-        dilation_channels=wavenet_params["dilation_channels"],
-        skip_channels=wavenet_params["skip_channels"],
-        quantization_channels=wavenet_params["quantization_channels"],
-        use_biases=wavenet_params["use_biases"],
-        scalar_input=wavenet_params["scalar_input"],
-        initial_filter_width=wavenet_params["initial_filter_width"],
-        histograms=args.histograms,
+    net = model_from_params(
+        wavenet_params, args.batch_size, histograms=args.histograms,
         global_condition_channels=args.gc_channels,
-        global_condition_cardinality=reader.gc_category_cardinality,
-        residual_postproc=wavenet_params.get("residual_postproc", False),
+        global_condition_cardinality=source.gc_category_cardinality,
         local_condition_channels=args.lc_channels,
         local_condition_upsample_scales=lc_scales,
         local_condition_context=lc_ctx)
@@ -609,19 +599,20 @@ def main(argv=None):
 
     try:
         restored = {}
-        saved_global_step = load(net, restore_from, optimizer, restored)
+        saved_global_step = load(net, restore_from, optimizer, restored,
+                                 opened)
         if is_overwritten_training or saved_global_step is None:
             # the first training step will be saved_global_step + 1
             saved_global_step = -1
-        corpus_base = 0
-        if corpus is not None and is_overwritten_training:
-            corpus_base = corpus_first_batch(restored.get('device_corpus'),
-                                             corpus_entry)
+        if args.device_corpus and is_overwritten_training:
+            source.base = corpus_first_batch(restored.get('device_corpus'),
+                                             source.entry)
     except Exception:
         print("Something went wrong while restoring checkpoint. "
               "We will terminate training to avoid accidentally overwriting "
               "the previous model.")
         raise
+    del opened                  # (the checkpoint's tensors)
     parallel.broadcast_parameters(net)
     # every loss() below is followed by optimizer.minimize(): the skip /
     # post-processing gradients' all-reduce MAY start inside the backward pass
@@ -634,172 +625,30 @@ def main(argv=None):
         # one deterministic pass per validation, this rank's shard of the
         # sorted files, prepared like the training pieces
         vset = ev.ValidationSet(
-            args.validation_dir, wavenet_params['sample_rate'],
-            sample_size=args.sample_size,
-            silence_threshold=silence_threshold, gc_enabled=gc_enabled,
-            gc_cardinality=reader.gc_category_cardinality,
+            args.validation_dir, sample_rate, sample_size=args.sample_size,
+            silence_threshold=args.silence_threshold, gc_enabled=gc_enabled,
+            gc_cardinality=source.gc_category_cardinality,
             lc_channels=file_lc, lc_hop=lc_hop,
             lc_frames=lc_scales is not None, rank=rank, world=world)
     validate_every = args.validate_every or args.checkpoint_every
 
-    threads = [] if corpus is not None else reader.start_threads()
-
-    def corpus_at(k):
-        """The 'device_corpus' entry of a checkpoint after step k."""
-        return None if corpus is None else \
-            dict(corpus_entry, batch=corpus_base + k)
-    events = None
-    if rank == 0:
-        os.makedirs(logdir, exist_ok=True)
-        events = open(os.path.join(logdir, 'events.jsonl'), 'a')
-
+    source.start(net.device)
+    log = training.StepLog(net, logdir, rank)
+    B = args.batch_size
     step = None
     last_saved_step = saved_global_step
-    pending = None            # (step, mean loss tensor, start time) not yet printed
-    last_report = [None]
     last_run = validated = None   # --validation_dir: last step run / validated
-
-    def report(k, mean_loss, started, real=None, norm=None):
-        """Fetch step k's loss (waits for that step), check it, print / log the
-        reference's line (train.py:310-311).  sec/step: from the previous line
-        (the pipeline's cadence), or from the step's start for the first."""
-        # (float(tensor) would wait for EVERYTHING queued on the stream, the
-        # next step included: the loss went to a pinned scalar behind an event)
-        host_scalar, done = mean_loss
-        done.synchronize()
-        loss_value = float(host_scalar)
-        # (--clip_norm: the norm before clipping, copied behind the loss on
-        # the same stream: complete once the loss's event is)
-        norm_value = None if norm is None else float(norm[0])
-        if not np.isfinite(loss_value):
-            # every rank sees the same NaN mean: decide TOGETHER whether a
-            # kernel reported an error, so that no rank is left waiting in
-            # the next step's collectives
-            dev_err = None
-            try:
-                net.check_device_errors()
-            except Exception as e:
-                dev_err = e
-            if parallel.any_rank(dev_err is not None, net.device):
-                raise dev_err or RuntimeError(
-                    'rank %d: another rank reported an expired dependency '
-                    'wait in a persistent stack launch at step %d'
-                    % (rank, k))
-        now = time.time()
-        duration = now - (last_report[0] if last_report[0] is not None and
-                          last_report[0] > started else started)
-        last_report[0] = now
-        if rank == 0:
-            # (--mask_padding: `real` = the step's real samples, all ranks')
-            print('step {:d} - loss = {:.3f}, ({:.3f} sec/step)'
-                  .format(k, loss_value, duration) +
-                  ('' if real is None else ', {:d} real samples'.format(real))
-                  + ('' if norm_value is None else
-                     ', grad norm = {:.3f}'.format(norm_value)))
-            line = {'step': k, 'loss': loss_value, 'sec_per_step': duration}
-            if norm_value is not None:
-                line['grad_norm'] = norm_value
-            if real is not None:
-                line['real_samples'] = real
-            events.write(json.dumps(line) + '\n')
-            events.flush()
-
-    def validate(k):
-        """Score the validation set with the weights after step k's update
-        (the EMA shadow with --validate_ema): every rank its shard, ONE sum
-        over the ranks whatever a shard holds, rank 0 prints and logs."""
-        import contextlib
-        swap = ev.parameters_swapped(net, optimizer.ema_flat(net)) \
-            if args.validate_ema else contextlib.nullcontext()
-        with swap:
-            batches = vset.batches(args.batch_size)
-            if spec is not None:
-                batches = ev.with_features(net, spec, batches)
-            tot = ev.totals(net, batches, args.validation_batches)
-        res = ev.summary(ev.sum_over_ranks(tot, net.device))
-        if rank == 0:
-            print('step {:d} - validation loss = {:.3f}, bits/sample = {:.3f}'
-                  ', accuracy = {:.3f}'.format(
-                      k, res['nll_per_sample'], res['bits_per_sample'],
-                      res['accuracy']))
-            events.write(json.dumps({
-                'step': k, 'validation_loss': res['nll_per_sample'],
-                'validation_bits': res['bits_per_sample'],
-                'validation_accuracy': res['accuracy'],
-                'validation_samples': res['samples']}) + '\n')
-            events.flush()
-
-    fetch_slots = {}
-
-    def fetch_later(t, k, tag=0):
-        """(pinned host scalar, event): the scalar holds t once the event has
-        completed; two slots per `tag` used alternately (a slot is read before
-        the step after next overwrites it)."""
-        k = 2 * tag + (k & 1)
-        if not t.is_cuda:
-            class _Done(object):
-                def synchronize(self):
-                    pass
-            return t.detach().reshape(()).clone(), _Done()
-        if k not in fetch_slots:
-            fetch_slots[k] = (torch.empty((), dtype=torch.float32).pin_memory(),
-                              torch.cuda.Event())
-        host_scalar, ev = fetch_slots[k]
-        host_scalar.copy_(t.detach().reshape(()).float(), non_blocking=True)
-        ev.record()
-        return host_scalar, ev
-
-    copy_stream = [None]
-
-    def stage_in(host, k):
-        """host [B, n] float tensor -> device tensor, copied on a stream of its
-        own: the (pageable, hence host-blocking) copy then does not queue
-        behind the previous step's kernels, and the training stream only
-        waits for the copy.  (Pinned staging buffers measured 33 instead of
-        9.6 ms per step on this platform, tools/h2d_probe.py.)"""
-        if copy_stream[0] is None:
-            copy_stream[0] = torch.cuda.Stream(device=net.device)
-        with torch.cuda.stream(copy_stream[0]):
-            dev = host.contiguous().to(net.device)
-        torch.cuda.current_stream().wait_stream(copy_stream[0])
-        dev.record_stream(torch.cuda.current_stream())
-        return dev
-
     try:
         for step in range(saved_global_step + 1, args.num_steps):
             start_time = time.time()
             # every rank takes the same decision for this step (skip / common
             # clip length / abort) BEFORE any collective of the step is issued
-            err = cplan = None
-            lc, lc_off = None, 0
+            err = None
             try:
-                if corpus is not None:
-                    # the host index alone: T, lengths and speaker ids; the
-                    # batch itself is cut on the device, below
-                    cplan = corpus.plan(corpus_base + step, args.batch_size)
-                    audio = None
-                    lengths = cplan.n if args.mask_padding else None
-                    gc = torch.from_numpy(cplan.gc) if gc_enabled else None
-                else:
-                    audio = reader.dequeue(args.batch_size)
-                    lengths = \
-                        reader.dequeue_lengths(args.batch_size).numpy() \
-                        if args.mask_padding else None
-                    gc = reader.dequeue_gc(args.batch_size) \
-                        if gc_enabled else None
-                    if spec is not None:
-                        pass              # (from the staged batch, below)
-                    elif lc_scales is not None:
-                        # frames + offsets: the model upsamples on the device
-                        lc, lc_off = reader.dequeue_lc_frames(args.batch_size)
-                    elif lc_enabled:
-                        lc = reader.dequeue_lc(args.batch_size)
+                T, lengths, gc = source.plan(step, B)
             except Exception as e:        # e.g. a reader-thread failure
-                err, audio, gc, lc, lengths = e, None, None, None, None
-            n_t, all_ok = parallel.agree_step(
-                0 if err is not None else
-                cplan.T if cplan is not None else audio.shape[1],
-                err is None, net.device)
+                err, T, lengths, gc = e, 0, None, None
+            n_t, all_ok = parallel.agree_step(T, err is None, net.device)
             if not all_ok:
                 raise RuntimeError('rank %d: a rank failed to produce a batch '
                                    'at step %d%s' % (rank, step, '' if err is
@@ -814,26 +663,8 @@ def main(argv=None):
                 real = int(round(den * world))
             if (n_t if lengths is None else int(lengths.max())) < 2:
                 continue
-            if corpus is not None:
-                # (one or two launches on the training stream; no copy)
-                cb = corpus.batch(corpus_base + step, args.batch_size, T=n_t,
-                                  lc=corpus_lc)
-                audio = cb.audio
-                if corpus_lc == 'frames':
-                    lc, lc_off = cb.frames, cb.offsets
-                elif corpus_lc == 'rows':
-                    lc = cb.rows
-            else:
-                audio = audio[:, :n_t]
-            if lc is not None and lc_scales is None:
-                lc = lc[:, :n_t]
-            if audio.device.type == 'cpu' and net.device.type == 'cuda':
-                # pinned staging + asynchronous copy: a pageable host tensor
-                # handed to net.loss is copied synchronously BEHIND the previous
-                # step's kernels, i.e. the host would wait for the device every
-                # step and prepare the next batch while it idles
-                audio = stage_in(audio.reshape(audio.shape[0], -1), step)
-            if spec is not None and corpus_lc is None:
+            audio, lc, lc_off = source.take(step, B, n_t)
+            if lc_from_batch:
                 # frames (offset 0) for an upsampler model, else rows
                 lc = net.local_condition_from_audio(
                     spec, audio.reshape(audio.shape[0], -1), lengths)
@@ -851,71 +682,48 @@ def main(argv=None):
                             local_condition_offset=lc_off,
                             lengths=lengths, loss_denominator=den)
             optimizer.minimize(loss)
-            # The reference fetches the loss inside sess.run and so waits for
-            # every step (train.py:300-311).  Here the step is queued on the
-            # device and its loss is read ONE step later, while the next step
-            # runs (the same lines, one step late; 12.0 -> 9.5 ms per step at
-            # 8 x 16000: bench.py's step time) -- except where the step's own state is needed at
-            # once: a checkpoint step, a traced step, the last step.
-            # (the norm first: the loss's event, recorded behind both copies,
-            # then covers it.  Every rank holds the same norm: no collective)
-            norm = None if optimizer.last_grad_norm is None else \
-                fetch_later(optimizer.last_grad_norm, step, tag=1)
-            mean_loss = fetch_later(parallel.allreduce_mean_scalar(loss), step)
-            if pending is not None:
-                report(*pending)
-            pending = (step, mean_loss, start_time, real, norm)
+            # (prints the step before: StepLog)
+            log.step(step, loss, optimizer.last_grad_norm, start_time, real)
             if trace_step:
-                report(*pending)
-                pending = None
+                log.flush()
             if trace:
                 prof.__exit__(None, None, None)
                 prof.export_chrome_trace(os.path.join(logdir,
                                                       'timeline.trace'))
             if step % args.checkpoint_every == 0:
                 # (every rank resolves the step here, so that the ranks'
-                # collective sequences stay equal on the error path of report)
-                if pending is not None:
-                    report(*pending)
-                    pending = None
+                # collective sequences stay equal on the error path of the
+                # report)
+                log.flush()
             if rank == 0 and step % args.checkpoint_every == 0:
                 save(net, logdir, step, optimizer, lc_entry,
-                     corpus_at(step))
+                     source.checkpoint_entry(step))
                 last_saved_step = step
                 if args.histograms:
-                    # the reference's histogram summaries (model.py:314-325)
-                    # as an .npz next to the checkpoint
-                    hs = net.histogram_summaries()
-                    np.savez(os.path.join(
-                        logdir, 'histograms-%d.npz' % step),
-                        **{k + '/counts': v[0] for k, v in hs.items()},
-                        **{k + '/range': np.asarray(v[1:])
-                           for k, v in hs.items()})
+                    save_histograms(net, logdir, step)
             if vset is not None:
                 last_run = step
                 if step % validate_every == 0:
                     # (the one-step-late training line first: the lines stay
                     # in order)
-                    if pending is not None:
-                        report(*pending)
-                        pending = None
-                    validate(step)
+                    log.flush()
+                    log.validation(step, training.validate(
+                        net, optimizer, vset, spec, args))
                     validated = step
-        if pending is not None:
-            report(*pending)
-            pending = None
+        log.flush()
         if vset is not None and last_run is not None and \
                 validated != last_run:
-            validate(last_run)              # after the last step
+            # after the last step
+            log.validation(last_run, training.validate(
+                net, optimizer, vset, spec, args))
     except KeyboardInterrupt:
         print()
     finally:
         if rank == 0 and step is not None and step > last_saved_step:
-            save(net, logdir, step, optimizer, lc_entry, corpus_at(step))
-        coord.request_stop()
-        coord.join(threads)
-        if events:
-            events.close()
+            save(net, logdir, step, optimizer, lc_entry,
+                 source.checkpoint_entry(step))
+        source.stop()
+        log.close()
     return 0
 
 
