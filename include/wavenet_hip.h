@@ -939,7 +939,15 @@ int wn_lc_context_wgrad(const float* x, int Fx, const float* dctx, int Fw,
  * floor > 0, 1 <= B <= 65535, 1 <= T <= 2^30 (else WN_ERR_BAD_SHAPE); basis,
  * melw, out 16-byte, the others 4-byte aligned (else WN_ERR_MISALIGNED).  No
  * atomics, one summation order: a frame's bits depend on its own n_fft
- * samples and the tables only -- not on B, the other clips or its position. */
+ * samples and the tables only -- not on B, the other clips or its position.
+ * One workgroup computes 32 consecutive frames.  The 31 hop + n_fft samples
+ * they touch are staged on chip -- with one pad float after every `hop` of
+ * them where hop is even -- when
+ *   31 hop + n_fft + (hop even ? (31 hop + n_fft - 1) / hop : 0) + 1 <= 16384
+ * floats; otherwise every sample is read from memory where it is used: the
+ * same arithmetic, the same bits.  The launch asks for 64 KiB + 8 n_fft bytes
+ * + the staged floats of dynamic LDS: 147296 bytes at most (n_fft 2048, hop
+ * 460), 147280 at the largest odd hop (461). */
 int wn_melspec(const float* audio, long ld, int B, int T, const int32_t* lengths,
                const float* window, const float* basis, const float* melw,
                int n_fft, int hop, int n_bins, int n_mels, float floor_,

@@ -138,7 +138,7 @@ def _clips(name):
         yield x[b, :x.shape[1] if lengths is None else lengths[b]]
 
 
-@pytest.mark.parametrize('name', ['a', 'b', 'c'])
+@pytest.mark.parametrize('name', sorted(mel_ref.SHAPES))
 def test_reference_agrees_with_the_oracle(name):
     from wavenet import features
     kw = dict(mel_ref.SHAPES[name])
@@ -165,6 +165,38 @@ def test_float32_restatement_is_within_the_gpu_tolerance():
     print('float32 restatement: max abs error %.3g' % worst)
     assert mel_ref.MEL_TOL == 4.0 * mel_ref.MEL_F32_ERR
     assert worst <= mel_ref.MEL_TOL
+
+
+@pytest.mark.parametrize('name', sorted(mel_ref.MEL_YARDSTICK_BY_SHAPE))
+def test_both_float32_restatements_are_within_the_shape_bound(name):
+    """The sibling for the shapes (d) - (i) and the pairs at the staging
+    limit: each is held to 4 x its OWN yardstick (mel_ref.MEL_F32_MEASURED:
+    the matmul order, the sequential order and one float32 ulp of the largest
+    output, measured once and written down), and on any host both summation
+    orders stay within that bound themselves."""
+    matmul, seq, ulp = mel_ref.yardstick_terms(name)
+    tol = mel_ref.shape_tol(name)
+    print('shape (%s): matmul order %.3g, sequential order %.3g, ulp %.3g '
+          '(recorded %s; bound %.3g)'
+          % (name, matmul, seq, ulp, mel_ref.MEL_F32_MEASURED[name], tol))
+    assert tol == 4.0 * max(mel_ref.MEL_F32_MEASURED[name])
+    assert ulp <= max(mel_ref.MEL_F32_MEASURED[name]) * 1.05  # (the record's digits)
+    assert matmul <= tol and seq <= tol
+
+
+def test_the_new_shapes_leave_the_old_tolerance_alone():
+    assert mel_ref.MEL_F32_ERR == 9.2e-6 and mel_ref.MEL_TOL == 4.0 * 9.2e-6
+    assert sorted(mel_ref.MEL_F32_ERR_BY_SHAPE) == ['a', 'b', 'c']
+    assert set(mel_ref.NEW_SHAPES) <= set(mel_ref.MEL_YARDSTICK_BY_SHAPE)
+    # (a) - (c) keep their signal: the first samples, as they always were
+    x, lengths = mel_ref.make_audio('a')
+    assert x.shape == (3, 100) and lengths == (5, 100, 33)
+    rng = np.random.default_rng(11)
+    want = rng.uniform(-0.1, 0.1, (3, 100))
+    t = np.arange(100) / 8000
+    want += 0.3 * np.sin(2 * np.pi * 0.055 * 8000 * t)[None, :]
+    want += 0.2 * np.sin(2 * np.pi * 0.21 * 8000 * t + 1.0)[None, :]
+    assert np.array_equal(x, want.astype(np.float32))
 
 
 # ------------------------------------------------------------ command line

@@ -15,9 +15,12 @@ pytestmark = pytest.mark.gpu
 NAN = float('nan')
 # (B, F, C): one element; row counts around the partial count (256) that are
 # no multiple of it, scalar path; the same with 80 channels and three clips;
-# the 16-byte path at a small C; the channel cap (a lane takes two groups)
+# the 16-byte path at a small C; the channel cap (128 lanes of 4 channels: one
+# trip of the partials kernel's channel loop); the scalar path above 256
+# channels (256 lanes of 1 channel: two trips, the second with 45 and with 6
+# live lanes)
 SHAPES = [(1, 1, 1), (1, 255, 3), (1, 257, 3), (3, 86, 80), (2, 300, 4),
-          (1, 40, 512)]
+          (1, 40, 512), (1, 40, 301), (2, 300, 262)]
 WN_ERR_BAD_SHAPE, WN_ERR_MISALIGNED = -1, -3
 
 

@@ -152,6 +152,197 @@ def test_frame_bits_do_not_depend_on_the_tile_position(hip_lib):
     assert torch.equal(a[k + lo:-lo], b[lo:a.shape[0] - k - lo])
 
 
+# ---- every kernel shape and edge --------------------------------------------
+# The shapes (d) - (i) of tests/mel_ref.py and the pairs either side of the
+# staging limit.  Each is held to MEL_TOL_FACTOR x its OWN yardstick
+# (mel_ref.MEL_F32_MEASURED: two float32 summation orders and one float32 ulp of
+# the largest output, measured on the CPU against the float64 oracle and
+# written down there); no bound here comes from the kernel's output.
+NEW = list(mel_ref.NEW_SHAPES)
+LIMIT = ['gm', 'gp', 'ks', 'km']
+
+
+def _n(x, lengths, b):
+    return x.shape[1] if lengths is None else lengths[b]
+
+
+def _staged(n_fft, hop):
+    """include/wavenet_hip.h, wn_melspec: a tile's 31 hop + n_fft samples,
+    one pad float after every `hop` of them at an even hop, and one more float,
+    are staged on chip when they fit 16384 floats; else read from memory."""
+    total = 31 * hop + n_fft
+    pads = (total - 1) // hop if hop % 2 == 0 else 0
+    return total + pads + 1 <= 16384
+
+
+def _check_against_oracle(name, got):
+    """Shape, dtype, the (printed) error on the real frames against the shape's
+    own bound, exact zeros behind them."""
+    x, lengths, ref = _case(name)
+    kw = mel_ref.SHAPES[name]
+    for b in range(x.shape[0]):
+        # no compared value sits at the floor
+        assert mel_ref.mel_energy(x[b, :_n(x, lengths, b)], **kw).min() > 1e-6
+    assert got.shape == ref.shape and got.dtype == np.float32
+    err = np.abs(got - ref).max()
+    tol = mel_ref.shape_tol(name)
+    print('shape (%s): max abs error %.3g (bound %.3g = 4 x %.3g)'
+          % (name, err, tol, mel_ref.MEL_YARDSTICK_BY_SHAPE[name]))
+    for b, nf in enumerate(_real_frames(name)):
+        assert not got[b, nf:].view(np.uint32).any(), b
+        assert np.abs(got[b, :nf]).min() > 0
+    assert err <= tol
+
+
+def test_the_new_shapes_take_the_paths_they_are_named_for():
+    paths = {n: _staged(mel_ref.SHAPES[n]['n_fft'], mel_ref.SHAPES[n]['hop'])
+             for n in NEW + LIMIT}
+    assert paths == dict(d=True, e=True, f=True, g=True, h=False, i=True,
+                         gm=False, gp=True, ks=True, km=False)
+    # 64 KiB of basis ring, 8 n_fft bytes of window table and the staged
+    # floats: (g) is the largest launch at an odd hop, 'gp' (one hop less, with
+    # its pad floats) the largest there is -- no allowed setting asks for more
+    # on-chip memory
+    def floats(n_fft, hop):
+        total = 31 * hop + n_fft
+        return total + ((total - 1) // hop if hop % 2 == 0 else 0) + 1
+    most = max((65536 + 8 * n_fft + 4 * floats(n_fft, hop), n_fft, hop)
+               for n_fft in range(64, 2049, 64) for hop in range(1, n_fft + 1)
+               if _staged(n_fft, hop))
+    assert most == (147296, 2048, 460) and floats(2048, 460) == 16344
+    assert 65536 + 8 * 2048 + 4 * floats(2048, 461) == 147280
+    assert floats(2048, 462) == 16406 and floats(1024, 494) == 16372
+
+
+@pytest.mark.parametrize('name', NEW + ['gp'])
+def test_matches_float64_oracle_at_every_kernel_shape(hip_lib, name):
+    x, lengths, _ = _case(name)
+    _check_against_oracle(name, _spec(name)(x, lengths).cpu().numpy())
+
+
+@pytest.mark.parametrize('staged,memory', mel_ref.LIMIT_PAIRS)
+def test_either_side_of_the_staging_limit_is_the_same_rule(hip_lib, staged,
+                                                           memory):
+    """One hop apart on the same audio, the samples staged on chip and read
+    from memory: both meet the float64 oracle within their own bounds."""
+    a, b = mel_ref.SHAPES[staged], mel_ref.SHAPES[memory]
+    assert {k: v for k, v in a.items() if k != 'hop'} == \
+        {k: v for k, v in b.items() if k != 'hop'}
+    assert _staged(a['n_fft'], a['hop']) and not _staged(b['n_fft'], b['hop'])
+    assert np.array_equal(_case(staged)[0], _case(memory)[0])
+    for name in (staged, memory):
+        x, lengths, _ = _case(name)
+        _check_against_oracle(name, _spec(name)(x, lengths).cpu().numpy())
+
+
+@pytest.mark.parametrize('name', ['e', 'f', 'h'])
+def test_clip_in_a_batch_equals_the_clip_alone_at_the_edges(hip_lib, name):
+    """An odd hop with a one-sample clip, a clip that ends on the tile
+    boundary, the memory path."""
+    x, lengths, _ = _case(name)
+    spec = _spec(name)
+    both = spec(x, lengths)
+    for b in range(x.shape[0]):
+        n = lengths[b]
+        alone = spec(x[b], [n])
+        assert torch.equal(alone, both[b]), b
+        short = spec(x[b, :n])
+        assert short.shape[0] == -(-n // spec.hop)
+        assert torch.equal(short, both[b, :short.shape[0]]), b
+
+
+@pytest.mark.parametrize('name', ['e', 'h'])
+def test_garbage_behind_the_length_changes_nothing_on_either_path(hip_lib,
+                                                                  name):
+    x, lengths, _ = _case(name)
+    spec = _spec(name)
+    clean = spec(x, lengths)
+    dirty = x.copy()
+    for b, n in enumerate(lengths):          # (a whole clip has no tail)
+        dirty[b, n::2] = np.nan
+        dirty[b, n + 1::2] = 1e30
+    assert np.isnan(dirty).any() and (dirty == np.float32(1e30)).any()
+    got = spec(dirty, lengths)
+    assert not bool(torch.isnan(got).any())
+    assert torch.equal(got, clean)
+
+
+@pytest.mark.parametrize('name', NEW + LIMIT)
+def test_two_calls_give_identical_bits_at_every_kernel_shape(hip_lib, name):
+    x, lengths, _ = _case(name)
+    spec = _spec(name)
+    assert torch.equal(spec(x, lengths), spec(x, lengths))
+
+
+@pytest.mark.parametrize('name,T', [('e', 25 * 40 + 3), ('h', 462 * 40 + 5)])
+def test_frame_bits_do_not_depend_on_the_tile_position_odd_hop_and_memory(
+        hip_lib, name, T):
+    """As for (b): at an odd hop (no pad slots) and on the memory path.  The
+    clip has 41 frames; shifted by 5 hops, the interior frames 32 .. of the
+    second tile become frames 27 .. of the first."""
+    kw = mel_ref.SHAPES[name]
+    x = mel_ref.signal(31, kw['sample_rate'], 1, T)[0]
+    spec = _spec(name)
+    hop, k = kw['hop'], 5
+    a = spec(x)
+    b = spec(x[k * hop:].copy())
+    lo = -(-kw['n_fft'] // hop)
+    assert a.shape[0] == 41 and b.shape[0] == 36 and k + lo < 32 < 41 - lo
+    assert torch.equal(a[k + lo:-lo], b[lo:a.shape[0] - k - lo])
+    assert not torch.equal(a[:36], b)            # (the frames did move)
+
+
+@pytest.mark.parametrize('name', ['e', 'h'])
+def test_row_stride_and_a_base_off_by_four_bytes(hip_lib, name):
+    """The entry itself with ld = T + 3, NaN in the three gap columns, and an
+    audio base that is 4-byte but not 16-byte aligned: the bits of the
+    contiguous call, on the staged and on the memory path."""
+    from wavenet import _lib
+    x, lengths, _ = _case(name)
+    spec = _spec(name)
+    want = spec(x, lengths)
+    B, T = x.shape
+    ld = T + 3
+    flat = torch.full((B * ld + 1,), float('nan'), dtype=torch.float32,
+                      device='cuda')
+    view = flat[1:].view(B, ld)
+    view[:, :T] = torch.from_numpy(x).cuda()
+    assert view.data_ptr() % 16 == 4 and view.stride() == (ld, 1)
+    assert bool(torch.isnan(view[:, T:]).all()) and bool(torch.isnan(flat[0]))
+    win, basis, melw = spec.device_tables(view.device)
+    nd = torch.tensor(lengths, dtype=torch.int32, device='cuda')
+    F = spec.num_frames(T)
+    out = torch.full((B, F, spec.n_mels), float('nan'), dtype=torch.float32,
+                     device='cuda')
+    _lib.call('wn_melspec', _lib.ptr(view), ld, B, T, _lib.ptr(nd),
+              _lib.ptr(win), _lib.ptr(basis), _lib.ptr(melw), spec.n_fft,
+              spec.hop, spec.n_bins, spec.n_mels, spec.floor, _lib.ptr(out),
+              _lib.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    # whole clips through the stride: the gap columns sit right behind them
+    out.fill_(float('nan'))
+    _lib.call('wn_melspec', _lib.ptr(view), ld, B, T, None,
+              _lib.ptr(win), _lib.ptr(basis), _lib.ptr(melw), spec.n_fft,
+              spec.hop, spec.n_bins, spec.n_mels, spec.floor, _lib.ptr(out),
+              _lib.stream())
+    torch.cuda.synchronize()
+    assert torch.equal(out, spec(x))
+
+
+def test_silence_sits_at_the_floor_on_the_memory_path(hip_lib):
+    """(h): read from memory, four mel fragments, the scalar epilogue."""
+    spec = _spec('h', floor=1e-5)
+    hop, T, lengths = 462, 15251, [15251, 700]
+    got = spec(np.zeros((2, T), np.float32), lengths).cpu().numpy()
+    assert got.shape == (2, 34, 97)
+    want = np.zeros((2, 34, 97), np.float32)
+    want[0, :] = np.log(np.float32(1e-5))
+    want[1, :2] = np.log(np.float32(1e-5))
+    assert np.abs(got - want).max() <= MEL_TOL
+    assert not got[1, 2:].view(np.uint32).any()
+
+
 # ---- the model-level interface ---------------------------------------------
 DIL = [1, 2, 4, 8, 1, 2, 4, 8]
 
