@@ -13,6 +13,19 @@ audio and no <clip>.npy is read); the model flags are generate.py's, the
 checkpoint is loaded as generate.py loads it (wavenet/checkpoint.py),
 --use_ema true scores the checkpoint's EMA weights.  Without --sample_size
 whole utterances are scored, batched by length.
+
+--synthesis true (a model with local conditioning and a checkpoint that names
+a log-mel front end) then copy-synthesises the set's whole utterances --
+conditioning from each utterance's own audio, utterance u of the set drawn
+with --seed + u, --synthesis_batch streams in lock step (wavenet/synthesis.py)
+-- and adds
+
+    "synthesis": {"clips": .., "samples": .., "steps": .., "occupancy": ..,
+                  "log_mel_mae_db": .., "log_mel_lsd_db": ..}
+
+the mean absolute and the root-mean-square (per frame, then averaged)
+difference in dB between the raw log-mel features of what was generated and
+of the original.  --synthesis_out DIR also writes <stem>.wav per utterance.
 """
 from __future__ import print_function
 
@@ -32,6 +45,9 @@ from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 BATCH_SIZE = 8
 SILENCE_THRESHOLD = 0.3        # train.py's
 WAVENET_PARAMS = './wavenet_params.json'   # generate.py's
+SYNTHESIS_BATCH = 32
+SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_out', 'max_clips', 'seed',
+                   'temperature', 'top_k', 'top_p')
 
 
 def get_arguments(argv=None):
@@ -70,7 +86,33 @@ def get_arguments(argv=None):
         p, '  Default: the checkpoint\'s \'lc_features\' (train.py '
         '--lc_features), whose settings the other --lc_* flags default to; '
         '`none` reads <clip>.npy files whatever the checkpoint says.')
-    return p.parse_args(argv)
+    p.add_argument('--synthesis', type=str_to_bool, default=False,
+                   help='after the scoring, copy-synthesise the whole '
+                   'utterances of --data_dir and report the log-mel distance '
+                   'to the originals')
+    p.add_argument('--synthesis_batch', type=int, default=None,
+                   help='--synthesis: streams generated in lock step '
+                   '(default %d)' % SYNTHESIS_BATCH)
+    p.add_argument('--synthesis_out', type=str, default=None,
+                   help='--synthesis: write <stem>.wav of every utterance '
+                   'into this directory')
+    p.add_argument('--max_clips', type=int, default=None,
+                   help='--synthesis: the first N utterances of the set only')
+    p.add_argument('--seed', type=int, default=None,
+                   help='--synthesis: utterance u draws with seed + u '
+                   '(default 0)')
+    p.add_argument('--temperature', type=float, default=None,
+                   help='--synthesis: sampling temperature (default 1)')
+    p.add_argument('--top_k', type=int, default=None,
+                   help='--synthesis: generate.py\'s --top_k')
+    p.add_argument('--top_p', type=float, default=None,
+                   help='--synthesis: generate.py\'s --top_p')
+    a = p.parse_args(argv)
+    if not a.synthesis:
+        for name in SYNTHESIS_FLAGS:
+            if getattr(a, name) is not None:
+                p.error('--%s needs --synthesis true' % name)
+    return a
 
 
 def main(argv=None):
@@ -104,6 +146,11 @@ def main(argv=None):
         print('--lc_channels needs --lc_hop (audio samples per feature '
               'frame)')
         return 1
+    if args.synthesis:
+        why = _synthesis_refused(args, spec)
+        if why:
+            print(why)
+            return 1
     ckpt = None
     if args.use_ema:
         ckpt, why = open_ema_checkpoint(args.checkpoint)
@@ -139,8 +186,63 @@ def main(argv=None):
     if spec is not None:
         batches = ev.with_features(net, spec, batches)
     result = ev.evaluate(net, batches, args.max_batches)
+    if args.synthesis:
+        whole = data
+        if args.sample_size is not None:
+            whole = ev.ValidationSet(
+                args.data_dir, wavenet_params['sample_rate'],
+                silence_threshold=args.silence_threshold,
+                gc_enabled=gc_enabled, gc_cardinality=args.gc_cardinality)
+        try:
+            result['synthesis'] = _synthesis(args, net, spec, whole,
+                                             wavenet_params['sample_rate'])
+        except ValueError as e:
+            print(str(e))
+            return 1
     print(json.dumps(result))
     return 0
+
+
+def _synthesis_refused(args, spec):
+    """One line that names what --synthesis true lacks, or None."""
+    if args.lc_channels is None:
+        return ('--synthesis true needs a model with local conditioning '
+                '(--lc_channels, or a checkpoint of train.py --lc_features '
+                'mel): there is nothing to copy-synthesise from')
+    if spec is None:
+        return ('--synthesis true needs a log-mel front end: the checkpoint '
+                'names none (train.py --lc_features mel) and --lc_features '
+                'mel was not given')
+    if args.synthesis_batch is not None and \
+            not 1 <= args.synthesis_batch <= 256:
+        return '--synthesis_batch must be in [1, 256]'
+    if args.max_clips is not None and args.max_clips < 1:
+        return '--max_clips must be positive'
+    return None
+
+
+def _synthesis(args, net, spec, data, sample_rate):
+    """The "synthesis" entry: the set's whole utterances (in its order; the
+    first --max_clips of them) copy-synthesised and compared."""
+    from wavenet import synthesis
+    pieces = data.pieces[:args.max_clips]
+    audios = [p[0] for p in pieces]
+    seed = args.seed or 0
+    syn, waves = synthesis.copy_synthesize(
+        net, spec, audios, seeds=[seed + u for u in range(len(audios))],
+        batch=args.synthesis_batch or SYNTHESIS_BATCH,
+        global_condition=[p[2] for p in pieces] if data.gc_enabled else None,
+        temperature=1.0 if args.temperature is None else args.temperature,
+        top_k=args.top_k, top_p=args.top_p)
+    mae, lsd = synthesis.log_mel_distance(spec, waves, audios, syn.rounds)
+    if args.synthesis_out:
+        synthesis.write_wavs(
+            waves, [os.path.splitext(os.path.basename(p[1]))[0]
+                    for p in pieces], args.synthesis_out, sample_rate)
+    return {'clips': len(audios),
+            'samples': int(sum(a.shape[0] for a in audios)),
+            'steps': syn.steps, 'occupancy': syn.occupancy,
+            'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}
 
 
 if __name__ == '__main__':

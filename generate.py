@@ -29,6 +29,10 @@ are the log-mel front end's (wavenet/features.py) of that wav, computed on the
 device with the checkpoint's 'lc_features' settings (train.py --lc_features)
 or the --lc_features flags; one sample is generated per sample of the wav, or
 --samples of them when that is given and fewer.
+--lc_wav_dir DIR --wav_out_dir OUT is --lc_wav for every wav of a directory
+(sorted; file i draws with --seed + i): --clips streams (default 32 here) run
+in lock step, the utterances sorted by length (wavenet/synthesis.py), and
+OUT/<stem>.wav holds one generated sample per sample of DIR/<stem>.wav.
 """
 from __future__ import division
 from __future__ import print_function
@@ -56,6 +60,7 @@ WINDOW = 8000
 WAVENET_PARAMS = './wavenet_params.json'
 SAVE_EVERY = None
 SILENCE_THRESHOLD = 0.1
+DIR_CLIPS = 32
 
 
 def _ensure_positive_float(f):
@@ -112,10 +117,11 @@ def get_arguments(argv=None):
     p.add_argument('--gc_cardinality', type=int, default=None)
     p.add_argument('--gc_id', type=int, default=None)
     p.add_argument('--seed', type=int, default=0, help='sampling RNG seed')
-    p.add_argument('--clips', type=int, default=1,
+    p.add_argument('--clips', type=int, default=None,
                    help='independent clips generated together (fast path); '
                    'clip i draws with --seed + i and is written to '
-                   '<stem>_<i><ext>')
+                   '<stem>_<i><ext> (default 1; with --lc_wav_dir: the '
+                   'streams per round, default %d)' % DIR_CLIPS)
     p.add_argument('--lc_path', type=str, default=None,
                    help='local conditioning features (.npy, [frames, '
                    'channels]); needs --fast_generation false or '
@@ -141,6 +147,13 @@ def get_arguments(argv=None):
                    help='local conditioning from a wav: its log-mel '
                    'features, computed on the device, take the place of '
                    '--lc_path (not both)')
+    p.add_argument('--lc_wav_dir', type=str, default=None,
+                   help='--lc_wav for every wav of this directory, --clips '
+                   'at a time; needs --wav_out_dir (not with --lc_wav or '
+                   '--lc_path)')
+    p.add_argument('--wav_out_dir', type=str, default=None,
+                   help='with --lc_wav_dir: the directory of the generated '
+                   '<stem>.wav files')
     p.add_argument('--lc_channels', type=int, default=None,
                    help='with --lc_wav: the number of mels (default: the '
                    'checkpoint\'s)')
@@ -151,12 +164,31 @@ def get_arguments(argv=None):
     a = p.parse_args(argv)
     if a.lc_wav is not None and a.lc_path is not None:
         p.error('give either --lc_wav or --lc_path, not both')
-    if a.lc_wav is None:
+    if a.lc_wav_dir is not None:
+        for other in ('lc_wav', 'lc_path'):
+            if getattr(a, other) is not None:
+                p.error('give either --lc_wav_dir or --%s, not both' % other)
+        if a.wav_out_dir is None:
+            p.error('--lc_wav_dir needs --wav_out_dir')
+        if a.gc_ids is not None:
+            p.error('--gc_ids does not go with --lc_wav_dir (one --gc_id '
+                    'for all files)')
+        if a.clips is None:
+            a.clips = DIR_CLIPS
+        if not 1 <= a.clips <= 256:
+            p.error('--clips must be in [1, 256] with --lc_wav_dir')
+    elif a.wav_out_dir is not None:
+        p.error('--wav_out_dir needs --lc_wav_dir')
+    if a.clips is None:
+        a.clips = 1
+    if a.lc_wav is None and a.lc_wav_dir is None:
         for flag in ['--lc_features'] * (a.lc_features == 'mel') + \
                 features.cli_flags_given(a):
             p.error('%s needs --lc_wav' % flag)
     elif a.lc_features == 'none':
         p.error('--lc_wav needs a front end, not --lc_features none')
+    if a.lc_wav_dir is not None and not a.fast_generation:
+        p.error('--lc_wav_dir runs on the fast path only')
     a.samples_given = a.samples is not None
     if a.samples is None:
         a.samples = SAMPLES
@@ -174,7 +206,7 @@ def get_arguments(argv=None):
             a.gc_id, a.gc_ids = a.gc_ids[0], None
     if a.clips < 1:
         raise ValueError('--clips must be >= 1')
-    if a.clips > 1 and not a.fast_generation:
+    if a.clips > 1 and not a.fast_generation and a.lc_wav_dir is None:
         raise ValueError('--clips > 1 needs --fast_generation true')
     if a.gc_channels is not None:
         if a.gc_cardinality is None:
@@ -219,7 +251,8 @@ def main(argv=None):
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
     n_wav = None
-    if args.lc_path is not None or args.lc_wav is not None:
+    if args.lc_path is not None or args.lc_wav is not None or \
+            args.lc_wav_dir is not None:
         try:
             # (--lc_hop 1, the default, counts as absent)
             lc_scales, hop, lc_ctx = local_condition.parse_cli(
@@ -228,7 +261,7 @@ def main(argv=None):
         except ValueError as e:
             print(str(e))
             return 1
-    if args.lc_wav is not None:
+    if args.lc_wav is not None or args.lc_wav_dir is not None:
         # (the hop is the model's: the scales' product, else --lc_hop, else
         # the checkpoint's)
         try:
@@ -243,6 +276,8 @@ def main(argv=None):
             print(str(e))
             return 1
         args.lc_hop = spec.hop
+    if args.lc_wav_dir is not None:
+        return _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx)
     if args.lc_path is not None or args.lc_wav is not None:
         if args.fast_generation and not args.lc_fast_generation:
             print('Local conditioning (--lc_path) needs the naive path: '
@@ -394,6 +429,52 @@ def main(argv=None):
             np.asarray(waveform, np.int32))
     dump(waveform)
     print('Finished generating. Codes saved under {}.'.format(logdir))
+    return 0
+
+
+def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx):
+    """--lc_wav_dir: copy synthesis of every wav of a directory in
+    length-sorted rounds of --clips streams (wavenet/synthesis.py)."""
+    from wavenet import synthesis
+    from wavenet.audio_reader import find_files, load_wav
+    rate = wavenet_params['sample_rate']
+    files = find_files(args.lc_wav_dir)
+    if not files:
+        print('--lc_wav_dir {} holds no wav files'.format(args.lc_wav_dir))
+        return 1
+    audios = [load_wav(f, rate) for f in files]
+    if args.samples_given:
+        audios = [a[:args.samples] for a in audios]
+    for f, a in zip(files, audios):
+        if a.shape[0] == 0:
+            print('--lc_wav_dir: {} holds no samples'.format(f))
+            return 1
+    net = model_from_params(
+        wavenet_params, 1, global_condition_channels=args.gc_channels,
+        global_condition_cardinality=args.gc_cardinality,
+        local_condition_channels=spec.n_mels,
+        local_condition_upsample_scales=lc_scales,
+        local_condition_context=lc_ctx)
+    why = restore(net, args.checkpoint, args.use_ema, ckpt, check_lc=True)
+    if why:
+        print(why)
+        return 1
+    try:
+        syn, waves = synthesis.copy_synthesize(
+            net, spec, audios,
+            seeds=[args.seed + i for i in range(len(files))],
+            batch=args.clips, global_condition=args.gc_id,
+            temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+    except ValueError as e:
+        print(str(e))
+        return 1
+    synthesis.write_wavs(
+        waves, [os.path.splitext(os.path.basename(f))[0] for f in files],
+        args.wav_out_dir, rate)
+    print('Finished generating {} clips ({} samples in {} lock-step steps, '
+          'occupancy {:.3f}) into {}.'.format(
+              len(files), sum(a.shape[0] for a in audios), syn.steps,
+              syn.occupancy, args.wav_out_dir))
     return 0
 
 

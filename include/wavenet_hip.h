@@ -991,6 +991,35 @@ int wn_feature_normalize(const float* in, float* out, int B, int F, int C,
                          const int32_t* nframes, const float* shift,
                          const float* scale, float lo, float hi, void* stream);
 
+/* ---- distance of two feature tensors (csrc/wn_features.hip; wavenet/
+ * features.py: frame_distance).  a, b float32 [B][F][C]; nframes as above
+ * (frames at or behind nframes[b] are never read).  With d = a - b subtracted
+ * in float32 and widened to float64, outputs float64 [B] each:
+ *   abs_sum[b] = sum_{f,c} |d|
+ *   sq_sum[b]  = sum_{f,c} d * d
+ *   rms_sum[b] = sum_f sqrt((sum_c d * d) / C)          (float64 square root)
+ * partials: scratch of wn_feature_distance_partials(B, F) doubles (3 per clip
+ * and chunk of 64 frames; -1: bad arguments; needs no device).  The summation
+ * order, fixed: the workgroup of chunk k of a clip gives its four waves the
+ * frames 64 k + w, 64 k + w + 4, ... below nframes[b], in ascending order;
+ * lane i of a wave adds the channels V i + 64 V j, j = 0, 1, ... (V = 4 where
+ * C % 4 == 0, one 16-byte load per input, else 1) into its own sums; a
+ * frame's sum over c is the xor butterfly (32, 16, ..., 1) of the lanes' sums
+ * of that frame; the lanes' sums over the wave's frames go through the same
+ * butterfly, the waves are added in the order 0, 1, 2, 3, the chunks in the
+ * order k = 0, 1, ..., from zero.  No atomics: clip b's numbers are a function
+ * of that clip's bits, (F, C) and nframes[b] -- not of B, the clip's position
+ * or the other clips.  Equal inputs give exact zeros.
+ *
+ * 1 <= C <= 512, B, F >= 1, B * F <= 2^31 - 1 (else WN_ERR_BAD_SHAPE); a, b
+ * 16-byte aligned when C % 4 == 0, else 4-byte; nframes 4-byte; the outputs
+ * and partials 8-byte (else WN_ERR_MISALIGNED).  All checks come before any
+ * launch. */
+long wn_feature_distance_partials(int B, int F);
+int wn_feature_distance(const float* a, const float* b, int B, int F, int C,
+                        const int32_t* nframes, double* abs_sum, double* sq_sum,
+                        double* rms_sum, double* partials, void* stream);
+
 /* ---- device-resident training corpus (csrc/wn_corpus.hip; the rule:
  * wavenet/corpus.py).  The trimmed utterances lie in one device buffer `flat`
  * [N] float32; utterance u is flat[utt_off[u] .. + utt_len[u]).  A batch is

@@ -369,7 +369,109 @@ __global__ __launch_bounds__(FNORM_THREADS) void feature_normalize_kernel(
   }
 }
 
-// the shape and alignment rules both entries share (`a`, `b`: the float
+// ---------------------------------------------------------------------------
+// Distance of two feature tensors (wavenet/features.py: frame_distance;
+// tests/synth_ref.py restates it).  With d = a - b subtracted in float32 and
+// widened to float64, per clip over its real frames:
+//   abs = sum |d|,  sq = sum d * d,  rms = sum_f sqrt((sum_c d * d) / C)
+//
+// feature_distance_partials_kernel: workgroup (clip, k) owns the frames
+// [k FDIST_TF, (k + 1) FDIST_TF) of its clip, cut at nframes; its four waves
+// take the frames f0 + w, f0 + w + 4, ... in ascending order, one frame per
+// trip.  Lane i takes the channels V i + 64 V j, j = 0, 1, ... (V = 4 where
+// C % 4 == 0: one 16-byte load per input, else 1) and adds |d| and d * d into
+// lane sums; the frame's sum over c is the xor butterfly (32, 16, ... 1) of
+// the lanes' sums of that frame.  At the end the lane sums go through the
+// same butterfly and the four waves are added in the order 0, 1, 2, 3.
+// feature_distance_finish_kernel adds a clip's partials k = 0, 1, ... in
+// order, from zero.  No atomics: a clip's three numbers are a function of its
+// own bits, (F, C) and nframes[b]; an empty chunk adds exact zeros.  Frames at
+// or behind nframes[b] are not read.
+// ---------------------------------------------------------------------------
+#define FDIST_TF 64
+#define FDIST_THREADS 256
+
+__device__ __forceinline__ double fdist_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <int V>
+__global__ __launch_bounds__(FDIST_THREADS) void feature_distance_partials_kernel(
+    const float* __restrict__ a, const float* __restrict__ b, int F, int C,
+    const int32_t* __restrict__ nframes, int nchunk,
+    double* __restrict__ partials) {
+#pragma clang fp contract(off)
+  __shared__ double red[3 * (FDIST_THREADS / 64)];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long clip = blockIdx.x / nchunk;
+  const int f0 = (int)(blockIdx.x - clip * nchunk) * FDIST_TF;
+  int n = F;
+  if (nframes) {
+    n = nframes[clip];
+    n = n < 0 ? 0 : (n > F ? F : n);
+  }
+  const int f1 = n < f0 + FDIST_TF ? n : f0 + FDIST_TF;
+  double sa = 0.0, ss = 0.0, sr = 0.0;
+  // (wave-uniform trips: every lane takes part in the butterfly)
+  for (int f = f0 + wave; f < f1; f += FDIST_THREADS / 64) {
+    const long o = (clip * F + f) * C;
+    double q = 0.0;
+    for (int c = lane * V; c < C; c += 64 * V) {
+      if (V == 4) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a + o + c);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(b + o + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const double w = (double)(x[e] - y[e]);
+          sa += fabs(w);
+          q += w * w;
+        }
+      } else {
+        const double w = (double)(a[o + c] - b[o + c]);
+        sa += fabs(w);
+        q += w * w;
+      }
+    }
+    ss += q;
+    sr += sqrt(fdist_wave_sum(q) / (double)C);
+  }
+  sa = fdist_wave_sum(sa);
+  ss = fdist_wave_sum(ss);
+  if (lane == 0) {
+    red[3 * wave] = sa;
+    red[3 * wave + 1] = ss;
+    red[3 * wave + 2] = sr;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double t = 0.0;
+    for (int w = 0; w < FDIST_THREADS / 64; ++w) t += red[3 * w + threadIdx.x];
+    partials[(long)blockIdx.x * 3 + threadIdx.x] = t;
+  }
+}
+
+__global__ void feature_distance_finish_kernel(const double* __restrict__ partials,
+                                               int B, int nchunk,
+                                               double* __restrict__ abs_sum,
+                                               double* __restrict__ sq_sum,
+                                               double* __restrict__ rms_sum) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double* p = partials + (long)b * nchunk * 3;
+  double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+  for (int k = 0; k < nchunk; ++k) {
+    t0 += p[3 * k];
+    t1 += p[3 * k + 1];
+    t2 += p[3 * k + 2];
+  }
+  abs_sum[b] = t0;
+  sq_sum[b] = t1;
+  rms_sum[b] = t2;
+}
+
+// the shape and alignment rules the entries share (`a`, `b`: the float
 // buffers of [B][F][C]; b may be NULL)
 static int feat_check(const void* a, const void* b, int B, int F, int C,
                       const int32_t* nframes) {
@@ -474,6 +576,37 @@ int wn_feature_normalize(const float* in, float* out, int B, int F, int C,
   else
     hipLaunchKernelGGL(feature_normalize_kernel<1>, dim3((unsigned)blocks), dim3(FNORM_THREADS),
                        0, s, in, out, R, F, C, nframes, shift, scale, lo, hi);
+  return wn_check_launch();
+}
+
+long wn_feature_distance_partials(int B, int F) {
+  if (B < 1 || F < 1 || (long)B * (long)F > 2147483647L) return -1;
+  return 3L * B * ((F + FDIST_TF - 1) / FDIST_TF);
+}
+
+int wn_feature_distance(const float* a, const float* b, int B, int F, int C,
+                        const int32_t* nframes, double* abs_sum, double* sq_sum,
+                        double* rms_sum, double* partials, void* stream) {
+  if (!a || !b || !abs_sum || !sq_sum || !rms_sum || !partials) return WN_ERR_NULL;
+  const int rc = feat_check(a, b, B, F, C, nframes);
+  if (rc != WN_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(abs_sum) & 7u) ||
+      (reinterpret_cast<uintptr_t>(sq_sum) & 7u) ||
+      (reinterpret_cast<uintptr_t>(rms_sum) & 7u) ||
+      (reinterpret_cast<uintptr_t>(partials) & 7u))
+    return WN_ERR_MISALIGNED;
+  const int nchunk = (F + FDIST_TF - 1) / FDIST_TF;
+  const unsigned grid = (unsigned)((long)B * nchunk);   // (<= B F <= 2^31 - 1)
+  hipStream_t s = (hipStream_t)stream;
+  if (C % 4 == 0)
+    hipLaunchKernelGGL(feature_distance_partials_kernel<4>, dim3(grid),
+                       dim3(FDIST_THREADS), 0, s, a, b, F, C, nframes, nchunk, partials);
+  else
+    hipLaunchKernelGGL(feature_distance_partials_kernel<1>, dim3(grid),
+                       dim3(FDIST_THREADS), 0, s, a, b, F, C, nframes, nchunk, partials);
+  if (wn_check_launch() != WN_OK) return WN_ERR_LAUNCH;
+  hipLaunchKernelGGL(feature_distance_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s,
+                     partials, B, nchunk, abs_sum, sq_sum, rms_sum);
   return wn_check_launch();
 }
 

@@ -208,6 +208,11 @@ SIGNATURES = {
     'wn_feature_stats': (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
     'wn_feature_normalize': (c_int, [P, P, c_int, c_int, c_int, P, P, P,
                                      c_float, c_float, P]),
+    # distance of two feature tensors: a, b, B, F, C, nframes, abs_sum,
+    # sq_sum, rms_sum, partials, stream
+    'wn_feature_distance_partials': (c_long, [c_int, c_int]),
+    'wn_feature_distance': (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P,
+                                    P]),
     # device-resident corpus.  The plan (13 arguments): utt_off, utt_len, U,
     # item_utt, item_start, P, perm, e0, nE, g0, size, random, seed.
     # gather: flat, N, plan, audio, B, T, stream

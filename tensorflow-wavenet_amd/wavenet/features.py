@@ -29,6 +29,11 @@ one fixed order (wn_feature_stats); `Normalizer` is the affine + clamp rule
 applied on the device to the real frames (wn_feature_normalize; padding
 frames stay exact zeros).  A MelSpec with a normaliser applies it to what it
 computes, and its constants travel in the checkpoint's 'lc_features' entry.
+
+Distance.  `frame_distance(a, b, nframes)` sums |a - b|, (a - b)^2 and the
+per-frame root mean square of a - b over each clip's real frames on the device
+(wn_feature_distance: float32 subtraction, float64 sums, one fixed order);
+`FrameDistance.summary` turns the sums of log-mel features into dB.
 """
 import copy
 import re
@@ -584,6 +589,86 @@ class Normalizer(object):
         with torch.cuda.device(src.device):
             self._launch(src, dst, n)
         return out if out is not None else (dst[0] if one else dst)
+
+
+DB_PER_NEPER = 10.0 / np.log(10.0)      # natural log of power -> dB
+
+
+class FrameDistance(object):
+    """What `frame_distance` returns: abs_sum, sq_sum, rms_sum, device
+    float64 [B] each (the rule: `frame_distance`)."""
+
+    def __init__(self, abs_sum, sq_sum, rms_sum):
+        self.abs_sum, self.sq_sum, self.rms_sum = abs_sum, sq_sum, rms_sum
+
+    def __iter__(self):
+        return iter((self.abs_sum, self.sq_sum, self.rms_sum))
+
+    def summary(self, nframes, C):
+        """(log_mel_mae_db, log_mel_lsd_db) over all clips, for features that
+        are natural logs of power (waits for the device):
+            mae = (10 / ln 10) sum abs_sum / (sum nframes * C)
+            lsd = (10 / ln 10) sum rms_sum / sum nframes
+        nframes: the real frames per clip (ints, or one int for all)."""
+        if not _is_int(C) or C < 1:
+            raise ValueError('summary: C must be a positive int, got %r'
+                             % (C,))
+        B = int(self.abs_sum.shape[0])
+        n = np.asarray(nframes)
+        if n.dtype == object or n.dtype == np.bool_ or \
+                not np.issubdtype(n.dtype, np.integer) or \
+                n.shape not in ((), (B,)) or (n < 0).any():
+            raise ValueError('summary: nframes must be %d non-negative '
+                             'integers, got %r' % (B, nframes))
+        total = int(n) * B if n.shape == () else int(n.sum())
+        if total < 1:
+            raise ValueError('summary: no frames were counted')
+        a = float(self.abs_sum.sum().item())
+        r = float(self.rms_sum.sum().item())
+        return DB_PER_NEPER * a / (total * int(C)), DB_PER_NEPER * r / total
+
+
+def frame_distance(a, b, nframes=None):
+    """Distance of two feature tensors, float32 [B, F, C] or [F, C] of the
+    same shape, 1 <= C <= 512, on the device (wn_feature_distance), without
+    waiting for it.  With d = a - b in float32, widened to float64:
+        abs_sum[b] = sum |d|, sq_sum[b] = sum d^2,
+        rms_sum[b] = sum_f sqrt(mean_c d^2)
+    over clip b's real frames (nframes: [B] ints in [0, F]; the others are
+    not read).  One fixed summation order, no atomics: a clip's numbers do
+    not depend on the batch.  Returns a FrameDistance of float64 [B] tensors
+    ([1] for [F, C] inputs)."""
+    what = 'frame_distance'
+    shapes = []
+    for t in (a, b):
+        t = t if hasattr(t, 'detach') else np.asarray(t)
+        shapes.append(tuple(int(v) for v in t.shape))
+    if shapes[0] != shapes[1]:
+        raise ValueError('%s: a and b must have the same shape, got %s and '
+                         '%s' % (what, shapes[0], shapes[1]))
+    if len(shapes[0]) not in (2, 3) or not 1 <= shapes[0][-1] <= 512:
+        raise ValueError('%s: float32 [B, F, C] or [F, C] with 1 <= C <= 512 '
+                         'is required, got %s' % (what, shapes[0]))
+    C = shapes[0][-1]
+    a, _, B, F = _frames_arg(a, C, what)
+    b, _, _, _ = _frames_arg(b, C, what)
+    n = _nframes_arg(nframes, B, F, what)
+    import torch
+    lib = _lib.load()
+    _lib.require_gpu()
+    ta = _to_device(a, B, F, C)
+    tb = _to_device(b, B, F, C)
+    if ta.device != tb.device:
+        raise ValueError('%s: a on %s, b on %s' % (what, ta.device, tb.device))
+    with torch.cuda.device(ta.device):
+        nd = None if n is None else torch.from_numpy(n).to(ta.device)
+        out = torch.empty((3, B), dtype=torch.float64, device=ta.device)
+        parts = torch.empty(lib.wn_feature_distance_partials(B, F),
+                            dtype=torch.float64, device=ta.device)
+        _lib.call('wn_feature_distance', _lib.ptr(ta), _lib.ptr(tb), B, F, C,
+                  _lib.ptr(nd), _lib.ptr(out[0]), _lib.ptr(out[1]),
+                  _lib.ptr(out[2]), _lib.ptr(parts), _lib.stream())
+    return FrameDistance(out[0], out[1], out[2])
 
 
 def logmel_reference(x, spec, dtype=np.float64):
