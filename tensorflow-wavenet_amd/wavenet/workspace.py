@@ -40,6 +40,16 @@ class _Workspace(object):
         self.fwd_skip_ok = bool(lib.wn_stack_fwd_skip_ok(B, T, S,
                                                          self.stack_variant))
 
+        # INVARIANT, "a view fits its owner": every buffer a view (`parent`
+        # given: same B, shorter T, same model switches) asks for here has at
+        # most as many elements as the owner's buffer of that name, so the
+        # reinterpretation below never runs past the owner's memory.  It holds
+        # because each size is either independent of T or non-decreasing in
+        # it -- except the slab count of wn_stack_bwd, for which the owner
+        # asks the library about every shorter shape (_view_stack_slabs).
+        # Guard: the sweep of tests/test_workspace_host.py over model kinds,
+        # variant words, B and T; a new size that can shrink as T grows must
+        # be bounded the same way, never allocated per view.
         def alloc(name, shape, dtype=torch.float32, fill=None):
             n = int(np.prod(shape))
             if parent is not None and getattr(parent, name, None) is not None:
@@ -181,7 +191,11 @@ class _Workspace(object):
                 layers_k=nslab, layers_2=lib.wn_layer_bwd2_slabs(B, T),
                 layers_stack=lib.wn_stack_bwd_slabs(B, T, self.stack_variant)
                 if self.stack_bwd else 0)
-            alloc('lslabs', (L, max(counts.values()), net.LAYER_BLOCK))
+            # (an owner also holds the slabs of its most demanding view, which
+            # may take the backward stack when the owner itself does not)
+            fit = _view_stack_slabs(lib, B, T, self.stack_variant) \
+                if parent is None and net._stack_ok() else 0
+            alloc('lslabs', (L, max(fit, *counts.values()), net.LAYER_BLOCK))
             for key, count in counts.items():
                 self.region[key] = SlabRegion(
                     self.lslabs, count, net.LAYER_BLOCK,
@@ -237,6 +251,17 @@ class _Workspace(object):
             if net.G else None
         alloc('l2_parts', (lib.wn_l2_partials_count(),))
         alloc('l2', (1,), fill=0.0)
+
+
+def _view_stack_slabs(lib, B, T, variant):
+    """The most weight-gradient slabs per layer wn_stack_bwd writes at any
+    (B, T') with T' <= T.  The count is not monotone in T': it drops where
+    the launch goes from 16- to 32-row tiles and where a wave takes one more
+    tile, so a view can need more slabs than its owner's own launch.  It
+    depends on T' through ceil(T' / 16) and ceil(T' / 32) only: one question
+    per 16 rows covers every shorter shape."""
+    return max(lib.wn_stack_bwd_slabs(B, min(16 * k, T), variant)
+               for k in range(1, (T + 15) // 16 + 1))
 
 
 def get(net, B, T, training):
