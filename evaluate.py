@@ -18,7 +18,10 @@ whole utterances are scored, batched by length.
 a log-mel front end) then copy-synthesises the set's whole utterances --
 conditioning from each utterance's own audio, utterance u of the set drawn
 with --seed + u, --synthesis_batch streams in lock step (wavenet/synthesis.py)
--- and adds
+-- runs what was generated through the de-emphasis filter where the model
+was trained with train.py --preemphasis (the checkpoint's 'emphasis' entry, or
+--preemphasis A; the scoring pre-emphasises every batch behind the front end,
+as training does) -- and adds
 
     "synthesis": {"clips": .., "samples": .., "steps": .., "occupancy": ..,
                   "log_mel_mae_db": .., "log_mel_lsd_db": ..}
@@ -37,9 +40,9 @@ import sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
-from wavenet import features, local_condition  # noqa: E402
+from wavenet import emphasis, features, local_condition  # noqa: E402
 from wavenet.checkpoint import (  # noqa: E402
-    open_ema_checkpoint, restore, stored_lc_features)
+    open_ema_checkpoint, restore, stored_emphasis, stored_lc_features)
 from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
 BATCH_SIZE = 8
@@ -107,7 +110,13 @@ def get_arguments(argv=None):
                    help='--synthesis: generate.py\'s --top_k')
     p.add_argument('--top_p', type=float, default=None,
                    help='--synthesis: generate.py\'s --top_p')
+    emphasis.add_cli_flag(p)
     a = p.parse_args(argv)
+    if a.preemphasis is not None:
+        try:
+            emphasis.Emphasis(a.preemphasis)
+        except ValueError as e:
+            p.error('--preemphasis: %s' % e)
     if not a.synthesis:
         for name in SYNTHESIS_FLAGS:
             if getattr(a, name) is not None:
@@ -139,6 +148,8 @@ def main(argv=None):
                                       args.lc_channels, lc_hop, stored)
         if spec is not None:
             lc_hop = spec.hop
+        emph = emphasis.from_cli(args.preemphasis,
+                                 stored_emphasis(args.checkpoint))
     except ValueError as e:
         print(str(e))
         return 1
@@ -185,6 +196,8 @@ def main(argv=None):
     batches = data.batches(args.batch_size)
     if spec is not None:
         batches = ev.with_features(net, spec, batches)
+    if emph is not None:
+        batches = ev.with_emphasis(emph, batches)
     result = ev.evaluate(net, batches, args.max_batches)
     if args.synthesis:
         whole = data
@@ -195,7 +208,8 @@ def main(argv=None):
                 gc_enabled=gc_enabled, gc_cardinality=args.gc_cardinality)
         try:
             result['synthesis'] = _synthesis(args, net, spec, whole,
-                                             wavenet_params['sample_rate'])
+                                             wavenet_params['sample_rate'],
+                                             emph)
         except ValueError as e:
             print(str(e))
             return 1
@@ -221,9 +235,11 @@ def _synthesis_refused(args, spec):
     return None
 
 
-def _synthesis(args, net, spec, data, sample_rate):
+def _synthesis(args, net, spec, data, sample_rate, emph=None):
     """The "synthesis" entry: the set's whole utterances (in its order; the
-    first --max_clips of them) copy-synthesised and compared."""
+    first --max_clips of them) copy-synthesised, de-emphasised where the
+    model generates the emphasised signal (`emph`), and compared with the
+    natural originals."""
     from wavenet import synthesis
     pieces = data.pieces[:args.max_clips]
     audios = [p[0] for p in pieces]
@@ -234,6 +250,8 @@ def _synthesis(args, net, spec, data, sample_rate):
         global_condition=[p[2] for p in pieces] if data.gc_enabled else None,
         temperature=1.0 if args.temperature is None else args.temperature,
         top_k=args.top_k, top_p=args.top_p)
+    if emph is not None:
+        waves = synthesis.deemphasize(emph, waves, syn.rounds)
     mae, lsd = synthesis.log_mel_distance(spec, waves, audios, syn.rounds)
     if args.synthesis_out:
         synthesis.write_wavs(

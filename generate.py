@@ -33,6 +33,11 @@ or the --lc_features flags; one sample is generated per sample of the wav, or
 (sorted; file i draws with --seed + i): --clips streams (default 32 here) run
 in lock step, the utterances sorted by length (wavenet/synthesis.py), and
 OUT/<stem>.wav holds one generated sample per sample of DIR/<stem>.wav.
+Pre-emphasis: a model trained with train.py --preemphasis generates the
+emphasised signal; what is decoded goes through the inverse filter on the
+device before it is written (the checkpoint's 'emphasis' entry, or
+--preemphasis A; 0: off), and a --wav_seed is pre-emphasised before it is
+encoded.  generated_codes.npy holds the model's codes as they are.
 """
 from __future__ import division
 from __future__ import print_function
@@ -47,10 +52,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
-from wavenet import features, local_condition, sampling  # noqa: E402
+from wavenet import emphasis, features, local_condition, sampling  # noqa: E402
 from wavenet.checkpoint import (  # noqa: E402,F401
-    context_mismatch, open_ema_checkpoint, restore, stored_lc_features,
-    upsampler_mismatch)
+    context_mismatch, open_ema_checkpoint, restore, stored_emphasis,
+    stored_lc_features, upsampler_mismatch)
 from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
 SAMPLES = 16000
@@ -161,7 +166,13 @@ def get_arguments(argv=None):
         p, '  With --lc_wav; default: the checkpoint\'s \'lc_features\' '
         '(train.py --lc_features), whose settings the other --lc_* flags '
         'default to.')
+    emphasis.add_cli_flag(p)
     a = p.parse_args(argv)
+    if a.preemphasis is not None:
+        try:
+            emphasis.Emphasis(a.preemphasis)
+        except ValueError as e:
+            p.error('--preemphasis: %s' % e)
     if a.lc_wav is not None and a.lc_path is not None:
         p.error('give either --lc_wav or --lc_path, not both')
     if a.lc_wav_dir is not None:
@@ -228,11 +239,16 @@ def write_wav(waveform, sample_rate, filename):
 
 
 def create_seed(filename, sample_rate, quantization_channels,
-                window_size=WINDOW, silence_threshold=SILENCE_THRESHOLD):
-    """mu-law codes of the (silence-trimmed) seed wav, cut to the window."""
+                window_size=WINDOW, silence_threshold=SILENCE_THRESHOLD,
+                emph=None):
+    """mu-law codes of the (silence-trimmed) seed wav, pre-emphasised where
+    the model was trained so (`emph`), cut to the window."""
     from wavenet import mu_law_encode
     from wavenet.audio_reader import load_wav, trim_silence
     audio = trim_silence(load_wav(filename, sample_rate), silence_threshold)
+    if emph is not None and audio.shape[0]:
+        audio = emph.pre(np.asarray(audio, np.float32).reshape(-1)
+                         ).cpu().numpy()
     quantized = mu_law_encode(audio, quantization_channels)
     return quantized[:min(int(quantized.numel()), window_size)]
 
@@ -248,6 +264,12 @@ def main(argv=None):
             print(why)
             return 1
     lc_rows, lc_scales, lc_ctx = None, None, None
+    try:
+        emph = emphasis.from_cli(args.preemphasis,
+                                 stored_emphasis(args.checkpoint, ckpt))
+    except ValueError as e:
+        print(str(e))
+        return 1
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
     n_wav = None
@@ -277,7 +299,8 @@ def main(argv=None):
             return 1
         args.lc_hop = spec.hop
     if args.lc_wav_dir is not None:
-        return _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx)
+        return _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
+                         emph)
     if args.lc_path is not None or args.lc_wav is not None:
         if args.fast_generation and not args.lc_fast_generation:
             print('Local conditioning (--lc_path) needs the naive path: '
@@ -333,15 +356,21 @@ def main(argv=None):
     rate = wavenet_params['sample_rate']
     gc = None if args.gc_id is None else [args.gc_id]
     if args.wav_seed:
-        waveform = create_seed(args.wav_seed, rate, Q,
-                               args.window).cpu().numpy().tolist()
+        waveform = create_seed(args.wav_seed, rate, Q, args.window,
+                               emph=emph).cpu().numpy().tolist()
     else:
         waveform = np.random.default_rng(args.seed).integers(
             Q, size=(1,)).tolist()
 
+    # (written in pieces with --save_every: what is filtered is kept with
+    # its carry, so the last file is the one written in one go)
+    de = None if emph is None else emphasis.DeStream(emph)
+
     def dump(codes):
         if args.wav_out_path:
             out = mu_law_decode(np.asarray(codes, np.int32), Q).cpu().numpy()
+            if de is not None:
+                out = de.feed(out)
             write_wav(out, rate, args.wav_out_path)
 
     lc_full = None
@@ -357,7 +386,7 @@ def main(argv=None):
         return None if lc_full is None else lc_full[pos:pos + n]
 
     if args.clips > 1:
-        return _main_clips(args, net, waveform, Q, rate, logdir, rows)
+        return _main_clips(args, net, waveform, Q, rate, logdir, rows, emph)
     if args.fast_generation:
         if args.wav_seed:
             print('Priming generation with {} seed samples...'
@@ -432,7 +461,8 @@ def main(argv=None):
     return 0
 
 
-def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx):
+def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
+              emph=None):
     """--lc_wav_dir: copy synthesis of every wav of a directory in
     length-sorted rounds of --clips streams (wavenet/synthesis.py)."""
     from wavenet import synthesis
@@ -468,6 +498,8 @@ def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx):
     except ValueError as e:
         print(str(e))
         return 1
+    if emph is not None:
+        waves = synthesis.deemphasize(emph, waves, syn.rounds)
     synthesis.write_wavs(
         waves, [os.path.splitext(os.path.basename(f))[0] for f in files],
         args.wav_out_dir, rate)
@@ -483,7 +515,8 @@ def _clip_path(path, i):
     return '{}_{}{}'.format(stem, i, ext)
 
 
-def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None):
+def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None,
+                emph=None):
     """--clips N > 1: N streams in lock step (WaveNetModel.generate_batch),
     clip i drawing with --seed + i, all primed by the same seed (and, with
     --lc_path, conditioned on the same rows(position, n))."""
@@ -491,12 +524,15 @@ def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None):
     N = args.clips
     seeds = [args.seed + i for i in range(N)]
     gc = args.gc_ids if args.gc_ids is not None else args.gc_id
+    de = None if emph is None else [emphasis.DeStream(emph) for _ in range(N)]
 
     def dump(codes):
         if args.wav_out_path:
             for i in range(N):
                 out = mu_law_decode(np.asarray(codes[i], np.int32), Q
                                     ).cpu().numpy()
+                if de is not None:
+                    out = de[i].feed(out)
                 write_wav(out, rate, _clip_path(args.wav_out_path, i))
 
     if args.wav_seed:

@@ -1020,6 +1020,40 @@ int wn_feature_distance(const float* a, const float* b, int B, int F, int C,
                         const int32_t* nframes, double* abs_sum, double* sq_sum,
                         double* rms_sum, double* partials, void* stream);
 
+/* ---- pre-emphasis and de-emphasis (csrc/wn_features.hip; wavenet/
+ * emphasis.py).  in / out: float32, clip b at in + b * ld_in / out + b * ld_out,
+ * T samples each; lengths: device int32 [B] (clip b has lengths[b] real
+ * samples, clamped to [0, T] by the kernel, read when it runs) or NULL (all T
+ * are real).  Positions at or behind lengths[b] are never read and are
+ * written as exact zeros.  alpha == 0 copies the real samples bit for bit.
+ *
+ * wn_preemphasis: out[b][t] = in[b][t] - float32(alpha * in[b][t - 1]) with
+ * in[b][-1] = 0: one multiplication, one subtraction, two roundings, no FMA.
+ * out must not overlap in (WN_ERR_UNSUPPORTED).
+ *
+ * wn_deemphasis: y[b][t] = in[b][t] + alpha * y[b][t - 1], y[b][-1] =
+ * initial[b] (NULL: 0), as a blocked scan: one workgroup per clip walks it in
+ * chunks of wn_emphasis_chunk() samples counted from the clip's first sample,
+ * each lane runs 16 samples sequentially, the lanes' runs are joined by a
+ * wave- and workgroup-level scan with the powers of alpha (computed in double,
+ * rounded once) and the chunk's carry is kept in a register.  last (NULL: not
+ * wanted): last[b] = y[b][lengths[b] - 1].  out may be in itself (with ld_out
+ * == ld_in); any other overlap is WN_ERR_UNSUPPORTED.  No atomics: clip b's
+ * output bits are a function of its own real samples, alpha and initial[b] --
+ * not of B, T, the leading dimensions or the other clips.  Cutting a clip at
+ * a multiple of wn_emphasis_chunk() and passing last as the next piece's
+ * initial gives the bits of one call.
+ *
+ * B, T >= 1, ld_in, ld_out >= T, 0 <= alpha < 1 (else WN_ERR_BAD_SHAPE); every
+ * pointer 4-byte aligned (else WN_ERR_MISALIGNED).  All checks come before
+ * any launch; wn_emphasis_chunk needs no device. */
+int wn_emphasis_chunk(void);
+int wn_preemphasis(const float* in, float* out, long ld_in, long ld_out, int B,
+                   int T, const int32_t* lengths, float alpha, void* stream);
+int wn_deemphasis(const float* in, float* out, long ld_in, long ld_out, int B,
+                  int T, const int32_t* lengths, const float* initial,
+                  float* last, float alpha, void* stream);
+
 /* ---- device-resident training corpus (csrc/wn_corpus.hip; the rule:
  * wavenet/corpus.py).  The trimmed utterances lie in one device buffer `flat`
  * [N] float32; utterance u is flat[utt_off[u] .. + utt_len[u]).  A batch is

@@ -471,6 +471,188 @@ __global__ void feature_distance_finish_kernel(const double* __restrict__ partia
   rms_sum[b] = t2;
 }
 
+// ---------------------------------------------------------------------------
+// Pre-emphasis and de-emphasis (wavenet/emphasis.py states both rules;
+// tests/emph_ref.py restates the recurrence in float64).
+//
+// preemphasis_kernel: out[t] = in[t] - float32(alpha * in[t - 1]), two
+// roundings (emph_mul / emph_sub: the FMA contraction is off), in[-1] = 0; exact zeros at t >= n[b], which are not read.
+//
+// deemphasis_kernel: y[t] = in[t] + alpha * y[t - 1] as a blocked scan.  One
+// workgroup of 256 lanes owns a clip and walks it in chunks of EMPH_CHUNK =
+// 256 * EMPH_RUN samples counted from the clip's first sample; `carry`, the y
+// in front of the chunk, is a scalar kept across the loop.  In a chunk:
+//   1. the samples are staged into LDS (coalesced; zeros behind the clip);
+//   2. lane g runs its EMPH_RUN samples sequentially from zero:
+//        l[0] = x[0], l[j] = x[j] + alpha * l[j - 1];  b[g] = l[EMPH_RUN - 1];
+//   3. the lanes' affine maps y -> alpha^RUN y + b[g] are scanned.  Every map
+//      has the same slope, so the scan carries the offsets alone and takes
+//      the slopes' products alpha^(RUN k) from a table: s = inclusive scan of
+//      b inside the wave by DPP (row shifts 1, 2, 4, 8, then lane 15 / lane 31
+//      broadcast to the following rows), the four waves' totals chained in
+//      wave order, G[g] = s[g] + alpha^(RUN (lane + 1)) * (y in front of the
+//      wave): the y at the end of lane g's run;
+//   4. the y in front of lane g's run, X[g] = b[g - 1] + alpha^RUN * G[g - 2]
+//      (X[0] = carry, X[1] = b[0] + alpha^RUN * carry): the neighbouring
+//      run's samples reach it through ONE more addition, not through the
+//      scan's, so that a sample k places back has passed through fewer than
+//      2 k + 3 roundings wherever it sits (tests/emph_ref.py: the bound);
+//   5. the fix-up y[j] = l[j] + alpha^(j + 1) * X[g], back through LDS; the
+//      next chunk's carry is the chunk's last y as it is written, so a clip
+//      cut at a multiple of the chunk, with last -> initial, gives the bits
+//      of one call.
+// The tables alpha^j (j <= RUN) and alpha^(RUN k) (k <= 64) are computed by
+// the host in double and rounded once.  No atomics; the order of every
+// operation is a function of the sample's position in its clip: a clip's
+// bits depend on its samples, alpha and initial[b] alone.  alpha == 0 copies.
+// ---------------------------------------------------------------------------
+#define EMPH_RUN 16
+#define EMPH_THREADS 256
+#define EMPH_CHUNK (EMPH_RUN * EMPH_THREADS)
+#define EMPH_SLOTS (EMPH_CHUNK + EMPH_THREADS)   // one pad float per run
+
+struct EmphTables {
+  float pw[EMPH_RUN + 1];     // alpha^j
+  float pl[65];               // alpha^(RUN k)
+};
+
+// one rounding each: plain operators with the FMA contraction off (the _rn
+// intrinsics inline library code that carries its own contraction flags, and
+// the product and the sum were fused: several ulps off the numpy rule)
+__device__ __forceinline__ float emph_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float emph_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float emph_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+__global__ __launch_bounds__(256) void preemphasis_kernel(
+    const float* __restrict__ in, float* __restrict__ out, long ld_in,
+    long ld_out, int B, int T, const int32_t* __restrict__ lengths,
+    float alpha) {
+#pragma clang fp contract(off)
+  const long total = (long)B * T;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total;
+       i += (long)gridDim.x * 256) {
+    const long b = i / T;
+    const int t = (int)(i - b * T);
+    int n = T;
+    if (lengths) {
+      n = lengths[b];
+      n = n < 0 ? 0 : (n > T ? T : n);
+    }
+    float v = 0.f;
+    if (t < n) {
+      const float* p = in + b * ld_in + t;
+      v = p[0];
+      if (alpha != 0.f)
+        v = emph_sub(v, emph_mul(alpha, t > 0 ? p[-1] : 0.f));
+    }
+    out[b * ld_out + t] = v;
+  }
+}
+
+__global__ __launch_bounds__(EMPH_THREADS) void deemphasis_kernel(
+    const float* in, float* out, long ld_in, long ld_out, int T,
+    const int32_t* __restrict__ lengths, const float* __restrict__ initial,
+    float* __restrict__ last, float alpha, EmphTables tb) {
+#pragma clang fp contract(off)
+  __shared__ float xs[EMPH_SLOTS];
+  __shared__ float cy;                      // the chunk's last y
+  __shared__ float pw[EMPH_RUN + 1];
+  __shared__ float pl[65];
+  __shared__ float Bs[EMPH_THREADS], Gs[EMPH_THREADS], wt[EMPH_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long b = blockIdx.x;
+  int n = T;
+  if (lengths) {
+    n = lengths[b];
+    n = n < 0 ? 0 : (n > T ? T : n);
+  }
+  const float* src = in + b * ld_in;
+  float* dst = out + b * ld_out;
+  float carry = initial ? initial[b] : 0.f;
+
+  if (alpha == 0.f) {                       // the identity, bit for bit
+    for (int t = tid; t < n; t += EMPH_THREADS) dst[t] = src[t];
+    if (last && tid == 0 && n > 0) last[b] = src[n - 1];
+  } else {
+    if (tid <= EMPH_RUN) pw[tid] = tb.pw[tid];
+    if (tid < 65) pl[tid] = tb.pl[tid];
+    for (int c0 = 0; c0 < n; c0 += EMPH_CHUNK) {      // (workgroup-uniform)
+      const int m = min(EMPH_CHUNK, n - c0);
+      __syncthreads();                      // the previous chunk's stores
+#pragma unroll
+      for (int k = 0; k < EMPH_RUN; ++k) {
+        const int s = tid + k * EMPH_THREADS;
+        xs[s + (s >> 4)] = s < m ? src[c0 + s] : 0.f;
+      }
+      __syncthreads();
+      float* mine = xs + tid * (EMPH_RUN + 1);
+      float l[EMPH_RUN];
+      l[0] = mine[0];
+#pragma unroll
+      for (int j = 1; j < EMPH_RUN; ++j)
+        l[j] = emph_add(mine[j], emph_mul(alpha, l[j - 1]));
+      const float bl = l[EMPH_RUN - 1];
+      // inclusive scan of the runs' ends over the wave
+      float s = bl;
+      s = emph_add(s, emph_mul(pl[1], dpp_f32<0x111, 0xf>(0.f, s)));
+      s = emph_add(s, emph_mul(pl[2], dpp_f32<0x112, 0xf>(0.f, s)));
+      s = emph_add(s, emph_mul(pl[4], dpp_f32<0x114, 0xf>(0.f, s)));
+      s = emph_add(s, emph_mul(pl[8], dpp_f32<0x118, 0xf>(0.f, s)));
+      s = emph_add(s, emph_mul(pl[(lane & 15) + 1], dpp_f32<0x142, 0xa>(0.f, s)));
+      s = emph_add(s, emph_mul(pl[(lane & 31) + 1], dpp_f32<0x143, 0xc>(0.f, s)));
+      if (lane == 63) wt[wave] = s;
+      __syncthreads();
+      float v = carry;                      // the y in front of this wave
+      for (int w = 0; w < wave; ++w)
+        v = emph_add(wt[w], emph_mul(pl[64], v));
+      Bs[tid] = bl;
+      Gs[tid] = emph_add(s, emph_mul(pl[lane + 1], v));
+      __syncthreads();
+      float x = carry;                      // the y in front of this run
+      if (tid >= 1)
+        x = emph_add(Bs[tid - 1], emph_mul(pl[1], tid >= 2 ? Gs[tid - 2] : carry));
+#pragma unroll
+      for (int j = 0; j < EMPH_RUN; ++j)
+        mine[j] = emph_add(l[j], emph_mul(pw[j + 1], x));
+      if (tid == EMPH_THREADS - 1) cy = mine[EMPH_RUN - 1];
+      __syncthreads();
+      carry = cy;                           // (the y a next piece starts from)
+#pragma unroll
+      for (int k = 0; k < EMPH_RUN; ++k) {
+        const int s2 = tid + k * EMPH_THREADS;
+        if (s2 < m) {
+          const float y = xs[s2 + (s2 >> 4)];
+          dst[c0 + s2] = y;
+          if (last && c0 + s2 == n - 1) last[b] = y;
+        }
+      }
+    }
+  }
+  if (last && n == 0 && tid == 0) last[b] = carry;
+  for (int t = n + tid; t < T; t += EMPH_THREADS) dst[t] = 0.f;
+}
+
+static int emph_check(const void* in, const void* out, long ld_in, long ld_out,
+                      int B, int T, const int32_t* lengths, float alpha) {
+  if (!in || !out) return WN_ERR_NULL;
+  if (B < 1 || T < 1 || ld_in < T || ld_out < T || !(alpha >= 0.f) ||
+      !(alpha < 1.f))
+    return WN_ERR_BAD_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(in) & 3u) || (reinterpret_cast<uintptr_t>(out) & 3u) ||
+      (reinterpret_cast<uintptr_t>(lengths) & 3u))
+    return WN_ERR_MISALIGNED;
+  return WN_OK;
+}
+
 // the shape and alignment rules the entries share (`a`, `b`: the float
 // buffers of [B][F][C]; b may be NULL)
 static int feat_check(const void* a, const void* b, int B, int F, int C,
@@ -607,6 +789,47 @@ int wn_feature_distance(const float* a, const float* b, int B, int F, int C,
   if (wn_check_launch() != WN_OK) return WN_ERR_LAUNCH;
   hipLaunchKernelGGL(feature_distance_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s,
                      partials, B, nchunk, abs_sum, sq_sum, rms_sum);
+  return wn_check_launch();
+}
+
+int wn_emphasis_chunk(void) { return EMPH_CHUNK; }
+
+int wn_preemphasis(const float* in, float* out, long ld_in, long ld_out, int B,
+                   int T, const int32_t* lengths, float alpha, void* stream) {
+  const int rc = emph_check(in, out, ld_in, ld_out, B, T, lengths, alpha);
+  if (rc != WN_OK) return rc;
+  // a neighbour's input would be overwritten: the buffers must not overlap
+  const float* in_end = in + (long)(B - 1) * ld_in + T;
+  const float* out_end = out + (long)(B - 1) * ld_out + T;
+  if (in < out_end && out < in_end) return WN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(preemphasis_kernel, dim3(grid1d((long)B * T, 256, 4096)),
+                     dim3(256), 0, (hipStream_t)stream, in, out, ld_in, ld_out,
+                     B, T, lengths, alpha);
+  return wn_check_launch();
+}
+
+int wn_deemphasis(const float* in, float* out, long ld_in, long ld_out, int B,
+                  int T, const int32_t* lengths, const float* initial,
+                  float* last, float alpha, void* stream) {
+  const int rc = emph_check(in, out, ld_in, ld_out, B, T, lengths, alpha);
+  if (rc != WN_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(initial) & 3u) || (reinterpret_cast<uintptr_t>(last) & 3u))
+    return WN_ERR_MISALIGNED;
+  // out may be in itself; any other overlap would mix two clips
+  if (in != out) {
+    const float* in_end = in + (long)(B - 1) * ld_in + T;
+    const float* out_end = out + (long)(B - 1) * ld_out + T;
+    if (in < out_end && out < in_end) return WN_ERR_UNSUPPORTED;
+  } else if (ld_in != ld_out) {
+    return WN_ERR_UNSUPPORTED;
+  }
+  EmphTables tb;
+  const double a = (double)alpha;
+  for (int j = 0; j <= EMPH_RUN; ++j) tb.pw[j] = (float)pow(a, (double)j);
+  for (int k = 0; k <= 64; ++k) tb.pl[k] = (float)pow(a, (double)(EMPH_RUN * k));
+  hipLaunchKernelGGL(deemphasis_kernel, dim3((unsigned)B), dim3(EMPH_THREADS), 0,
+                     (hipStream_t)stream, in, out, ld_in, ld_out, T, lengths,
+                     initial, last, alpha, tb);
   return wn_check_launch();
 }
 

@@ -213,6 +213,13 @@ SIGNATURES = {
     'wn_feature_distance_partials': (c_long, [c_int, c_int]),
     'wn_feature_distance': (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P,
                                     P]),
+    # pre- / de-emphasis: in, out, ld_in, ld_out, B, T, lengths, [initial,
+    # last,] alpha, stream
+    'wn_emphasis_chunk': (c_int, []),
+    'wn_preemphasis': (c_int, [P, P, c_long, c_long, c_int, c_int, P, c_float,
+                               P]),
+    'wn_deemphasis': (c_int, [P, P, c_long, c_long, c_int, c_int, P, P, P,
+                              c_float, P]),
     # device-resident corpus.  The plan (13 arguments): utt_off, utt_len, U,
     # item_utt, item_start, P, perm, e0, nE, g0, size, random, seed.
     # gather: flat, N, plan, audio, B, T, stream

@@ -2,7 +2,7 @@
 
 train.py writes torch files holding {'variables': {reference variable name:
 tensor}, 'step'} and, where the run has them, 'optimizer', 'ema_variables',
-'lc_features' and 'device_corpus'; the step is parsed from the file name, as
+'lc_features', 'device_corpus' and 'emphasis'; the step is parsed from the file name, as
 in the reference (train.py:104-134 there).  The reference's own TensorFlow
 checkpoints are read too (tf_checkpoint.py).  train.py, generate.py and
 evaluate.py import their checkpoint functions from here.
@@ -31,14 +31,16 @@ def checkpoint_path(logdir, step):
 
 
 def save(net, logdir, step, optimizer=None, lc_features=None,
-         device_corpus=None):
+         device_corpus=None, emphasis=None):
     """`optimizer`: its step count, slots and shadow go in as 'optimizer'
     and, with EMA weights, the shadow as 'ema_variables' (the keys of
     'variables').  `lc_features`: the front end's settings
     (features.checkpoint_entry), stored under 'lc_features'.
     `device_corpus`: the settings of --device_corpus (crop, seed,
     sample_size, lc_feature_context) and the index of the last batch taken
-    ('batch'), stored under 'device_corpus'."""
+    ('batch'), stored under 'device_corpus'.  `emphasis`: the pre-emphasis
+    the model was trained on (emphasis.Emphasis.entry: {'alpha': ..}),
+    stored under 'emphasis'; a run without it writes no such entry."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
@@ -48,6 +50,8 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
         ckpt['lc_features'] = lc_features
     if device_corpus is not None:
         ckpt['device_corpus'] = device_corpus
+    if emphasis is not None:
+        ckpt['emphasis'] = emphasis
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
         if optimizer.ema_decay is not None:
@@ -177,6 +181,16 @@ def stored_lc_features(path, ckpt=None):
             return None
         ckpt = torch.load(path, map_location='cpu')
     return ckpt.get('lc_features')
+
+
+def stored_emphasis(path, ckpt=None):
+    """The 'emphasis' entry train.py --preemphasis wrote into the checkpoint
+    at `path` (`ckpt` where the caller holds it), else None."""
+    if ckpt is None:
+        if tf_checkpoint.checkpoint_format(path) or not os.path.isfile(path):
+            return None
+        ckpt = torch.load(path, map_location='cpu')
+    return ckpt.get('emphasis')
 
 
 def restore(net, path, use_ema=False, ckpt=None, check_lc=False):

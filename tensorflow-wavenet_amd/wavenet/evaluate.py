@@ -131,6 +131,14 @@ def with_features(net, spec, batches):
         yield audio, lengths, gc, ((lc, 0) if net.lc_up else lc)
 
 
+def with_emphasis(emphasis, batches):
+    """`batches` with the audio pre-emphasised on the device (emphasis.
+    Emphasis), each clip over its own length -- behind with_features, whose
+    features are those of the natural signal."""
+    for audio, lengths, gc, lc in batches:
+        yield emphasis.pre(audio, lengths), lengths, gc, lc
+
+
 def totals(net, batches, max_batches=None):
     """float64 [4] on the device: (sum of nll, targets, hits, clips) over
     net.score of every batch (at most max_batches of them).  No host wait."""

@@ -287,6 +287,19 @@ def copy_synthesize(net, spec, audios, *, seeds, batch=32,
     return syn, [mu_law_decode(c, net.Q) for c in syn.codes]
 
 
+def deemphasize(emphasis, waves, groups):
+    """waves[u] (device float32 [n_u], the decoded output of a model trained
+    on the pre-emphasised signal) through the inverse filter on the device
+    (emphasis.Emphasis.de), one ragged batch with `lengths` per group of
+    utterances (`groups`: lists of indices, e.g. Synthesis.rounds).  Returns
+    the new list; no host wait."""
+    out = list(waves)
+    for items in groups:
+        for u, w in zip(items, emphasis.de_ragged([waves[u] for u in items])):
+            out[u] = w
+    return out
+
+
 def log_mel_distance(spec, generated, original, groups):
     """(log_mel_mae_db, log_mel_lsd_db) between the RAW log-mel features
     (`spec` without its normaliser, the tables shared) of generated[u] and

@@ -7,15 +7,26 @@ batch comes from:
                         the step's batch.  It may raise (a reader thread that
                         failed); the ranks then agree on the step's fate
                         (parallel.agree_step) before any of them goes on.
-    take(step, B, n_t)  the planned batch cut to n_t samples: (audio on the
-                        device, lc, lc_offset).
+    take(step, B, n_t, lengths=None)
+                        the planned batch cut to n_t samples: (audio on the
+                        device, lc, lc_offset).  lengths: the clips' real
+                        lengths as the loss gets them, or None.
     start(device) / stop()   the reader threads; device: the model's.
     checkpoint_entry(step), gc_category_cardinality, lc
 
 `lc` says what the source's local conditioning is: 'frames' (frame-rate
 features and each clip's offset, for a model with a learned upsampler),
-'rows' (one row per sample) or None -- none at all, or computed by the loop
-from the batch as cut (--lc_features mel with piece context).
+'rows' (one row per sample) or None -- none at all, or computed in take by
+`front` (a callable (audio [B, T], lengths) -> lc the loop sets: --lc_features
+mel with piece context) from the batch as cut.
+
+Pre-emphasis (`emphasis`: an emphasis.Emphasis or None, train.py
+--preemphasis): take pre-emphasises the batch's audio AFTER the features have
+been computed from the raw batch -- the model sees the emphasised signal, the
+features are those of the natural one.  The filter is of the piece: a piece's
+first sample sees a zero in front of it, as its mel frames see zeros.  The
+output goes into a buffer of the source's own, two used in turn; the batch
+itself (a view of the corpus's ring) is not rewritten.
 
 StepLog prints and logs the loss lines, one step late; validate scores the
 held-out set.
@@ -53,13 +64,47 @@ class StageIn(object):
         return dev
 
 
-class ReaderSource(object):
+class _EmphasisStep(object):
+    """What the two sources share: `front` and the pre-emphasis of a batch
+    into one of two buffers of the source's own."""
+    front = None
+
+    def _emphasise(self, audio, lengths):
+        """audio: device float32 [B, T], left as it is."""
+        if self.emphasis is None:
+            return audio
+        if not hasattr(self, '_emph'):
+            self._emph, self._emph_calls = [None, None], 0
+        slot = self._emph_calls & 1
+        self._emph_calls += 1
+        buf = self._emph[slot]
+        if buf is None or buf.numel() < audio.numel() or \
+                buf.device != audio.device:
+            buf = self._emph[slot] = torch.empty(
+                audio.numel(), dtype=torch.float32, device=audio.device)
+        out = buf[:audio.numel()].view(audio.shape)
+        return self.emphasis.pre(audio, lengths, out=out)
+
+    def _finish(self, audio, lc, lengths):
+        """(audio, lc) with `front`'s features of the raw batch where the
+        loop set one, then the pre-emphasis."""
+        if self.front is not None:
+            lc = self.front(audio.reshape(audio.shape[0], -1), lengths)
+        if self.emphasis is not None:
+            audio = self._emphasise(audio.reshape(audio.shape[0], -1),
+                                    lengths)
+        return audio, lc
+
+
+class ReaderSource(_EmphasisStep):
     """Batches of an AudioReader or a SyntheticReader: plan dequeues the host
     batch and holds it, take cuts it and copies the audio to the device."""
 
-    def __init__(self, reader, coord, lengths=False, gc=False, lc=None):
+    def __init__(self, reader, coord, lengths=False, gc=False, lc=None,
+                 emphasis=None):
         self.reader, self.coord = reader, coord
         self.lengths, self.gc, self.lc = lengths, gc, lc
+        self.emphasis = emphasis
         self.gc_category_cardinality = reader.gc_category_cardinality
         self.threads, self.held = [], None
 
@@ -86,7 +131,7 @@ class ReaderSource(object):
         self.held = audio, lc, lc_off
         return audio.shape[1], lengths, gc
 
-    def take(self, step, B, n_t):
+    def take(self, step, B, n_t, lengths=None):
         audio, lc, lc_off = self.held
         audio = audio[:, :n_t]
         if self.lc == 'rows':
@@ -97,21 +142,24 @@ class ReaderSource(object):
             # the previous step's kernels, i.e. the host would wait for the
             # device every step and prepare the next batch while it idles
             audio = self.stage_in(audio.reshape(audio.shape[0], -1))
+        audio, lc = self._finish(audio, lc, lengths)
         return audio, lc, lc_off
 
     def checkpoint_entry(self, step):
         return None
 
 
-class CorpusSource(object):
+class CorpusSource(_EmphasisStep):
     """Batches of a corpus.DeviceCorpus: plan reads the host index alone, take
     cuts the batch on the device (one or two launches on the training stream,
     no copy).  Step k takes batch `base` + k; `entry`: the corpus's settings
     as checkpoints store them under 'device_corpus'."""
 
-    def __init__(self, corpus, entry, lengths=False, gc=False, lc=None):
+    def __init__(self, corpus, entry, lengths=False, gc=False, lc=None,
+                 emphasis=None):
         self.corpus, self.entry, self.base = corpus, entry, 0
         self.lengths, self.gc, self.lc = lengths, gc, lc
+        self.emphasis = emphasis
         self.gc_category_cardinality = corpus.gc_category_cardinality
 
     def start(self, device):
@@ -125,11 +173,16 @@ class CorpusSource(object):
         return (p.T, p.n if self.lengths else None,
                 torch.from_numpy(p.gc) if self.gc else None)
 
-    def take(self, step, B, n_t):
+    def take(self, step, B, n_t, lengths=None):
         cb = self.corpus.batch(self.base + step, B, T=n_t, lc=self.lc)
-        if self.lc == 'frames':
-            return cb.audio, cb.frames, cb.offsets
-        return cb.audio, cb.rows, 0
+        # (the front end gets the lengths the loss gets; the filter the
+        # batch's own: its padding is zeros either way)
+        audio, lc = cb.audio, cb.frames if self.lc == 'frames' else cb.rows
+        if self.front is not None:
+            lc = self.front(audio, lengths)
+        # (an empty slot is all zeros: one sample of it gives the same)
+        audio = self._emphasise(audio, np.maximum(cb.lengths, 1))
+        return audio, lc, cb.offsets if self.lc == 'frames' else 0
 
     def checkpoint_entry(self, step):
         """The 'device_corpus' entry of a checkpoint after step `step`."""
@@ -261,10 +314,12 @@ class StepLog(object):
             self.events.close()
 
 
-def validate(net, optimizer, vset, spec, args):
+def validate(net, optimizer, vset, spec, args, emphasis=None):
     """Score the validation set with the weights as they are (the EMA shadow
     with --validate_ema): every rank its shard, ONE sum over the ranks
-    whatever a shard holds.  Returns evaluate.summary's dict."""
+    whatever a shard holds; with `emphasis` the audio is pre-emphasised
+    behind the front end, as the training batches are.  Returns
+    evaluate.summary's dict."""
     from . import evaluate as ev
     swap = ev.parameters_swapped(net, optimizer.ema_flat(net)) \
         if args.validate_ema else contextlib.nullcontext()
@@ -272,5 +327,7 @@ def validate(net, optimizer, vset, spec, args):
         batches = vset.batches(args.batch_size)
         if spec is not None:
             batches = ev.with_features(net, spec, batches)
+        if emphasis is not None:
+            batches = ev.with_emphasis(emphasis, batches)
         tot = ev.totals(net, batches, args.validation_batches)
     return ev.summary(ev.sum_over_ranks(tot, net.device))

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from wavenet import features, local_condition  # noqa: E402
+from wavenet import emphasis, features, local_condition  # noqa: E402
 from wavenet.checkpoint import (  # noqa: E402,F401
     checkpoint_path, latest_checkpoint, load, open_latest, save)
 from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
@@ -175,7 +175,13 @@ def get_arguments(argv=None):
                         'computes every utterance\'s frames once at load and '
                         'gives each piece the frames of its place in the '
                         'utterance.')
+    emphasis.add_cli_flag(p, train=True)
     args = p.parse_args(argv)
+    if args.preemphasis is not None:
+        try:
+            emphasis.Emphasis(args.preemphasis)
+        except ValueError as e:
+            p.error('--preemphasis: %s' % e)
     # (--data_dir's default is filled in here, so that "not given" shows)
     data_dir_given = args.data_dir is not None
     if not data_dir_given:
@@ -264,6 +270,19 @@ def corpus_first_batch(stored, entry):
     base = int(stored.get('batch', -1)) + 1
     print('  Corpus batches continue at {}.'.format(base))
     return base
+
+
+def emphasis_from_flags(args, opened, continued):
+    """The Emphasis of --preemphasis and the restored checkpoint's 'emphasis'
+    entry (`opened`: checkpoint.open_latest's result), or None: the entry is
+    the default, the flag overrides it (0: off) -- but a run `continued` in
+    its logdir keeps its checkpoint's value: ValueError naming both."""
+    stored = None
+    if opened is not None and opened.ckpt is not None:
+        stored = opened.ckpt.get('emphasis')
+    else:
+        continued = False       # (nothing to continue, or not our format)
+    return emphasis.from_cli(args.preemphasis, stored, continued)
 
 
 def get_default_logdir(logdir_root):
@@ -465,10 +484,11 @@ def corpus_settings(args):
 
 
 def build_source(args, wavenet_params, front, file_lc, lc_scales, lc_hop,
-                 rank, world):
+                 rank, world, emph=None):
     """The training batches' source (wavenet/training.py) and the front end
     as it stands once the source exists: (source, spec, lc_stats) -- or None,
-    having printed why not.  file_lc: the channels of <clip>.npy features."""
+    having printed why not.  file_lc: the channels of <clip>.npy features;
+    emph: the Emphasis the source applies to every batch, or None."""
     from wavenet import AudioReader, training
     from wavenet.audio_reader import Coordinator
     gc_enabled = args.gc_channels is not None
@@ -487,7 +507,7 @@ def build_source(args, wavenet_params, front, file_lc, lc_scales, lc_hop,
             lc_mode = 'frames' if lc_scales is not None else 'rows'
         return training.CorpusSource(
             corpus, corpus_settings(args), args.mask_padding, gc_enabled,
-            lc_mode), spec, lc_stats
+            lc_mode, emphasis=emph), spec, lc_stats
     coord = Coordinator()
     if args.synthetic:
         reader = SyntheticReader(
@@ -510,7 +530,8 @@ def build_source(args, wavenet_params, front, file_lc, lc_scales, lc_hop,
             seed=rank, lc_channels=file_lc, lc_hop=lc_hop,
             lc_frames=lc_scales is not None)
     return training.ReaderSource(reader, coord, args.mask_padding, gc_enabled,
-                                 lc_mode), front.spec, front.lc_stats
+                                 lc_mode, emphasis=emph), front.spec, \
+        front.lc_stats
 
 
 def save_histograms(net, logdir, step):
@@ -562,13 +583,14 @@ def main(argv=None):
         front = front_end_from_flags(
             args, sample_rate, lc_hop,
             None if is_overwritten_training else opened)
+        emph = emphasis_from_flags(args, opened, not is_overwritten_training)
     except (ValueError, OSError) as e:
         print(str(e))
         return 1
     # (with a front end the readers yield audio only)
     file_lc = None if front.spec is not None else args.lc_channels
     built = build_source(args, wavenet_params, front, file_lc, lc_scales,
-                         lc_hop, rank, world)
+                         lc_hop, rank, world, emph)
     if built is None:
         return 1
     source, spec, lc_stats = built
@@ -577,6 +599,10 @@ def main(argv=None):
     lc_from_batch = spec is not None and source.lc is None
 
     lc_entry = None if spec is None else features.checkpoint_entry(spec)
+    emph_entry = None if emph is None else emph.entry()
+    if emph is not None:
+        print('  Training on the pre-emphasised signal, alpha = {!r}.'
+              .format(emph.alpha))
     if lc_stats is not None and rank == 0:
         os.makedirs(logdir, exist_ok=True)
         lc_stats.save(os.path.join(logdir, 'lc_stats.npz'))
@@ -632,6 +658,11 @@ def main(argv=None):
             lc_frames=lc_scales is not None, rank=rank, world=world)
     validate_every = args.validate_every or args.checkpoint_every
 
+    if lc_from_batch:
+        # the front end's features of the raw batch as the source cut it:
+        # frames (offset 0) for an upsampler model, else rows
+        source.front = lambda audio, n: net.local_condition_from_audio(
+            spec, audio, n)
     source.start(net.device)
     log = training.StepLog(net, logdir, rank)
     B = args.batch_size
@@ -663,11 +694,7 @@ def main(argv=None):
                 real = int(round(den * world))
             if (n_t if lengths is None else int(lengths.max())) < 2:
                 continue
-            audio, lc, lc_off = source.take(step, B, n_t)
-            if lc_from_batch:
-                # frames (offset 0) for an upsampler model, else rows
-                lc = net.local_condition_from_audio(
-                    spec, audio.reshape(audio.shape[0], -1), lengths)
+            audio, lc, lc_off = source.take(step, B, n_t, lengths)
             trace_step = args.store_metadata and step % 50 == 0
             trace = trace_step and rank == 0
             if trace:
@@ -697,7 +724,7 @@ def main(argv=None):
                 log.flush()
             if rank == 0 and step % args.checkpoint_every == 0:
                 save(net, logdir, step, optimizer, lc_entry,
-                     source.checkpoint_entry(step))
+                     source.checkpoint_entry(step), emph_entry)
                 last_saved_step = step
                 if args.histograms:
                     save_histograms(net, logdir, step)
@@ -708,20 +735,20 @@ def main(argv=None):
                     # in order)
                     log.flush()
                     log.validation(step, training.validate(
-                        net, optimizer, vset, spec, args))
+                        net, optimizer, vset, spec, args, emph))
                     validated = step
         log.flush()
         if vset is not None and last_run is not None and \
                 validated != last_run:
             # after the last step
             log.validation(last_run, training.validate(
-                net, optimizer, vset, spec, args))
+                net, optimizer, vset, spec, args, emph))
     except KeyboardInterrupt:
         print()
     finally:
         if rank == 0 and step is not None and step > last_saved_step:
             save(net, logdir, step, optimizer, lc_entry,
-                 source.checkpoint_entry(step))
+                 source.checkpoint_entry(step), emph_entry)
         source.stop()
         log.close()
     return 0
