@@ -40,10 +40,10 @@ def _flat_grads(net):
     return flat_named(tree_to_numpy(net.gradients))
 
 
-def _log(tag, payload):
+def _log(tag, payload, name='fullsize_errors.json'):
     out = os.path.join(ROOT, 'gpurun_out')
     os.makedirs(out, exist_ok=True)
-    path = os.path.join(out, 'fullsize_errors.json')
+    path = os.path.join(out, name)
     try:
         cur = json.load(open(path))
     except (OSError, ValueError):
