@@ -12,7 +12,10 @@ wrote, the local conditioning is computed on the device from each batch's
 audio and no <clip>.npy is read); the model flags are generate.py's, the
 checkpoint is loaded as generate.py loads it (wavenet/checkpoint.py),
 --use_ema true scores the checkpoint's EMA weights.  Without --sample_size
-whole utterances are scored, batched by length.
+whole utterances are scored, batched by length.  --piece_history N|rf (with
+--sample_size) puts up to N samples (rf: the model's receptive field) of each
+piece's left context in front of it, fed but not scored: the bits/sample are
+then those of samples predicted from their true history.
 
 --synthesis true (a model with local conditioning and a checkpoint that names
 a log-mel front end) then copy-synthesises the set's whole utterances --
@@ -43,7 +46,9 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 from wavenet import emphasis, features, local_condition  # noqa: E402
 from wavenet.checkpoint import (  # noqa: E402
     open_ema_checkpoint, restore, stored_emphasis, stored_lc_features)
-from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
+from wavenet.cli import (  # noqa: E402
+    PIECE_HISTORY_HELP, model_from_params, piece_history, piece_history_arg,
+    str_to_bool)
 
 BATCH_SIZE = 8
 SILENCE_THRESHOLD = 0.3        # train.py's
@@ -65,6 +70,9 @@ def get_arguments(argv=None):
     p.add_argument('--sample_size', type=int, default=None,
                    help='Cut every file into pieces of this many samples '
                    '(default: whole utterances).')
+    p.add_argument('--piece_history', type=piece_history_arg, default=None,
+                   metavar='N|rf',
+                   help='--sample_size: ' + PIECE_HISTORY_HELP)
     p.add_argument('--batch_size', type=int, default=BATCH_SIZE)
     p.add_argument('--max_batches', type=int, default=None,
                    help='Score at most this many batches (default: all).')
@@ -117,6 +125,9 @@ def get_arguments(argv=None):
             emphasis.Emphasis(a.preemphasis)
         except ValueError as e:
             p.error('--preemphasis: %s' % e)
+    if a.piece_history is not None and a.sample_size is None:
+        p.error('--piece_history needs --sample_size (whole utterances have '
+                'no left context to bring)')
     if not a.synthesis:
         for name in SYNTHESIS_FLAGS:
             if getattr(a, name) is not None:
@@ -177,7 +188,8 @@ def main(argv=None):
             silence_threshold=args.silence_threshold, gc_enabled=gc_enabled,
             gc_cardinality=args.gc_cardinality,
             lc_channels=None if spec is not None else args.lc_channels,
-            lc_hop=lc_hop, lc_frames=lc_scales is not None)
+            lc_hop=lc_hop, lc_frames=lc_scales is not None,
+            history=piece_history(args.piece_history, wavenet_params))
     except ValueError as e:
         print(str(e))
         return 1

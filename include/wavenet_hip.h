@@ -419,6 +419,21 @@ int wn_xent_masked(const float* logits, long ld, const int32_t* q,
                    const int32_t* lengths, const float* inv_den,
                    float* dlogits, float* loss_partials, int B, int T, int Q,
                    int tf_quirk, void* stream);
+/* wn_xent_masked for clips with leading history: starts [B] (device int32,
+ * clamped to [0, T] by the kernel; the host checks 0 <= starts[b] <=
+ * lengths[b]) samples at the head of clip b are fed to the network but
+ * predicted by nobody.  Row t has a target iff starts[b] <= t + 1 <
+ * lengths[b]; rows with t + 1 < starts[b] add nothing to the loss and get
+ * dlogits rows of exact zeros, without an exponential being evaluated, like
+ * padding; row lengths[b] - 1 stays the label-less last row.  starts is read
+ * from device memory when the kernel runs, like lengths and inv_den.  Same
+ * partials as wn_xent_masked; starts all zero gives its results bit for bit.
+ * Errors as wn_xent_masked (starts: NULL -5, 4-byte alignment -3), all
+ * before any launch. */
+int wn_xent_window(const float* logits, long ld, const int32_t* q,
+                   const int32_t* starts, const int32_t* lengths,
+                   const float* inv_den, float* dlogits, float* loss_partials,
+                   int B, int T, int Q, int tf_quirk, void* stream);
 /* Scoring of held-out data (WaveNetModel.score): the inputs of wn_xent_masked
  * (lengths may be NULL: every clip has T rows), forward only.
  *   row_nll      float [B*T], may be NULL: logsumexp(logits[b,t,:Q]) -
@@ -443,6 +458,17 @@ int wn_xent_score(const float* logits, long ld, const int32_t* q,
                   const int32_t* lengths, float* row_nll, double* clip_nll,
                   int32_t* clip_count, int32_t* clip_correct, float* scratch,
                   int B, int T, int Q, void* stream);
+/* wn_xent_score with wn_xent_window's starts (may be NULL: no history): rows
+ * with t + 1 < starts[b] have no target either (row_nll 0.0, nothing
+ * evaluated), clip_count[b] = len_b - max(starts[b], 1) for codes in range,
+ * and the per-clip sums run over rows max(starts[b] - 1, 0) .. len_b - 2 in
+ * the same fixed order.  starts NULL or all zero gives wn_xent_score's bits.
+ * starts 4-byte aligned, else WN_ERR_MISALIGNED. */
+int wn_xent_score_window(const float* logits, long ld, const int32_t* q,
+                         const int32_t* starts, const int32_t* lengths,
+                         float* row_nll, double* clip_nll, int32_t* clip_count,
+                         int32_t* clip_correct, float* scratch, int B, int T,
+                         int Q, void* stream);
 int wn_softmax64_row(const float* logits_row, int Q, float* proba,
                      void* stream);
 
@@ -1104,6 +1130,34 @@ int wn_corpus_gather_frames(const float* fr, long NF, const int64_t* fr_off,
                             long g0, int size, int random, uint64_t seed,
                             int hop, int ctx, int Lc, float* frames, int Fw,
                             float* rows, int B, int T, void* stream);
+/* The two gathers with one more plan scalar, history >= 0 (else
+ * WN_ERR_BAD_SHAPE): every slot brings up to `history` samples of its true
+ * left context.  After start and n are derived as above, h = min(history,
+ * start), start' = start - h, n' = n + h, n' is cut to T, and everything
+ * said above holds with (start', n') for (start, n): the audio, the zeros
+ * behind n', f_lo / f_hi / rows, the out-of-table rule.
+ * wn_corpus_gather_hist also writes hist int32 [B] (h, cut to n') and lens
+ * int32 [B] (n'; 0 for an empty slot) to device memory (both required, 4-byte
+ * aligned), for a loss that reads them without a host round trip.
+ * history == 0 gives the existing entries' output bits. */
+int wn_corpus_gather_hist(const float* flat, long N, const int64_t* utt_off,
+                          const int32_t* utt_len, int U,
+                          const int32_t* item_utt, const int32_t* item_start,
+                          int P, const int32_t* perm, long e0, int nE, long g0,
+                          int size, int random, uint64_t seed, int history,
+                          float* audio, int32_t* hist, int32_t* lens, int B,
+                          int T, void* stream);
+int wn_corpus_gather_frames_hist(const float* fr, long NF,
+                                 const int64_t* fr_off, const int32_t* fr_len,
+                                 const int64_t* utt_off,
+                                 const int32_t* utt_len, int U,
+                                 const int32_t* item_utt,
+                                 const int32_t* item_start, int P,
+                                 const int32_t* perm, long e0, int nE, long g0,
+                                 int size, int random, uint64_t seed,
+                                 int history, int hop, int ctx, int Lc,
+                                 float* frames, int Fw, float* rows, int B,
+                                 int T, void* stream);
 
 #ifdef __cplusplus
 }

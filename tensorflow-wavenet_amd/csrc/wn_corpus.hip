@@ -9,6 +9,9 @@
 //   'pieces'  start = item_start, n = min(size, n_u - start)   (size 0: n_u)
 //   'random'  n = min(size, n_u), start = draw_bits(seed ^ 'crop', g) %
 //             (n_u - size + 1) when n_u > size, else 0
+//   history H (the _hist entries; 0 elsewhere): h = min(H, start),
+//             start' = start - h, n' = n + h: the piece with h samples of its
+//             true left context in front; everything below uses (start', n')
 //   n is cut to T.
 //
 // Both kernels are plain copies: a thread owns four consecutive floats of the
@@ -33,16 +36,16 @@ struct CorpusPlan {
   const int32_t* perm;        // [nE][P]: the orders of epochs e0 .. e0 + nE - 1
   long e0, g0;
   uint64_t seed;
-  int U, P, nE, size, random;
+  int U, P, nE, size, random, history;
 };
 
 struct CorpusSlot {
   long off;                   // utt_off[u]
-  int u, start, n, nu;        // n == 0: an empty slot
+  int u, start, n, nu, h;     // n == 0: an empty slot; h: history within n
 };
 
 __device__ __forceinline__ CorpusSlot corpus_slot(const CorpusPlan& p, long j, int T, long N) {
-  CorpusSlot s = {0, -1, 0, 0, 0};
+  CorpusSlot s = {0, -1, 0, 0, 0, 0};
   const long g = p.g0 + j;
   const long e = g / p.P, er = e - p.e0;
   const int r = (int)(g - e * p.P);
@@ -65,11 +68,13 @@ __device__ __forceinline__ CorpusSlot corpus_slot(const CorpusPlan& p, long j, i
     n = nu - start;
     if (p.size > 0) n = min(n, p.size);
   }
+  const int h = min(p.history, start);
   s.off = off;
   s.u = u;
-  s.start = start;
-  s.n = min(n, T);
+  s.start = start - h;
+  s.n = min(n + h, T);
   s.nu = nu;
+  s.h = min(h, s.n);
   return s;
 }
 
@@ -111,6 +116,16 @@ __global__ __launch_bounds__(CORPUS_BLOCK) void corpus_gather_kernel(
     }
     store4(out, idx, total, v);
   }
+}
+
+// hist [B] <- h, lens [B] <- n of every slot (wn_corpus_gather_hist)
+__global__ __launch_bounds__(CORPUS_BLOCK) void corpus_hist_kernel(
+    long N, CorpusPlan p, int32_t* __restrict__ hist, int32_t* __restrict__ lens, int B, int T) {
+  const long j = (long)blockIdx.x * CORPUS_BLOCK + threadIdx.x;
+  if (j >= B) return;
+  const CorpusSlot s = corpus_slot(p, j, T, N);
+  hist[j] = s.h;
+  lens[j] = s.n;
 }
 
 // what a slot reads of its utterance's frames [F][Lc]
@@ -193,9 +208,9 @@ __global__ __launch_bounds__(CORPUS_BLOCK) void corpus_frames_kernel(
 static int corpus_plan(CorpusPlan& p, const int64_t* utt_off, const int32_t* utt_len, int U,
                        const int32_t* item_utt, const int32_t* item_start, int P,
                        const int32_t* perm, long e0, int nE, long g0, int size, int random,
-                       uint64_t seed, int B) {
+                       uint64_t seed, int history, int B) {
   if (!utt_off || !utt_len || !item_utt || !item_start || !perm) return WN_ERR_NULL;
-  if (U <= 0 || P <= 0 || nE <= 0 || e0 < 0 || g0 < 0 || size < 0 || (random && size < 1) ||
+  if (U <= 0 || P <= 0 || nE <= 0 || e0 < 0 || g0 < 0 || size < 0 || (random && size < 1) || history < 0 ||
       g0 / P < e0 || (g0 + B - 1) / P >= e0 + nE)
     return WN_ERR_BAD_SHAPE;
   if ((reinterpret_cast<uintptr_t>(utt_off) & 7u) || (reinterpret_cast<uintptr_t>(utt_len) & 3u) ||
@@ -215,6 +230,7 @@ static int corpus_plan(CorpusPlan& p, const int64_t* utt_off, const int32_t* utt
   p.nE = nE;
   p.size = size;
   p.random = random ? 1 : 0;
+  p.history = history;
   return WN_OK;
 }
 
@@ -225,37 +241,62 @@ long wn_corpus_window_frames(int T, int hop, int ctx) {
   return ((long)T + hop - 2) / hop + 1 + 2L * ctx;
 }
 
-int wn_corpus_gather(const float* flat, long N, const int64_t* utt_off, const int32_t* utt_len,
-                     int U, const int32_t* item_utt, const int32_t* item_start, int P,
-                     const int32_t* perm, long e0, int nE, long g0, int size, int random,
-                     uint64_t seed, float* audio, int B, int T, void* stream) {
+// hist / lens: both or neither (the plain entry passes neither)
+static int corpus_gather(const float* flat, long N, const int64_t* utt_off,
+                         const int32_t* utt_len, int U, const int32_t* item_utt,
+                         const int32_t* item_start, int P, const int32_t* perm, long e0, int nE,
+                         long g0, int size, int random, uint64_t seed, int history, float* audio,
+                         int32_t* hist, int32_t* lens, int B, int T, void* stream) {
   if (!flat || !audio) return WN_ERR_NULL;
   if (B <= 0 || T <= 0 || P <= 0 || N <= 0) return WN_ERR_BAD_SHAPE;
   CorpusPlan p;
   const int rc = corpus_plan(p, utt_off, utt_len, U, item_utt, item_start, P, perm, e0, nE, g0,
-                             size, random, seed, B);
+                             size, random, seed, history, B);
   if (rc != WN_OK) return rc;
-  if (!wn_aligned16(flat) || !wn_aligned16(audio)) return WN_ERR_MISALIGNED;
+  if (!wn_aligned16(flat) || !wn_aligned16(audio) || (reinterpret_cast<uintptr_t>(hist) & 3u) ||
+      (reinterpret_cast<uintptr_t>(lens) & 3u))
+    return WN_ERR_MISALIGNED;
   const long chunks = ((long)B * T + 3) / 4;
   hipLaunchKernelGGL(corpus_gather_kernel, dim3(grid1d(chunks, CORPUS_BLOCK)),
                      dim3(CORPUS_BLOCK), 0, (hipStream_t)stream, flat, N, p, audio, B, T);
+  if (hist)
+    hipLaunchKernelGGL(corpus_hist_kernel, dim3(grid1d(B, CORPUS_BLOCK)), dim3(CORPUS_BLOCK), 0,
+                       (hipStream_t)stream, N, p, hist, lens, B, T);
   return wn_check_launch();
 }
 
-int wn_corpus_gather_frames(const float* fr, long NF, const int64_t* fr_off,
-                            const int32_t* fr_len, const int64_t* utt_off,
-                            const int32_t* utt_len, int U, const int32_t* item_utt,
-                            const int32_t* item_start, int P, const int32_t* perm, long e0,
-                            int nE, long g0, int size, int random, uint64_t seed, int hop,
-                            int ctx, int Lc, float* frames, int Fw, float* rows, int B, int T,
-                            void* stream) {
+int wn_corpus_gather(const float* flat, long N, const int64_t* utt_off, const int32_t* utt_len,
+                     int U, const int32_t* item_utt, const int32_t* item_start, int P,
+                     const int32_t* perm, long e0, int nE, long g0, int size, int random,
+                     uint64_t seed, float* audio, int B, int T, void* stream) {
+  return corpus_gather(flat, N, utt_off, utt_len, U, item_utt, item_start, P, perm, e0, nE, g0,
+                       size, random, seed, 0, audio, nullptr, nullptr, B, T, stream);
+}
+
+int wn_corpus_gather_hist(const float* flat, long N, const int64_t* utt_off,
+                          const int32_t* utt_len, int U, const int32_t* item_utt,
+                          const int32_t* item_start, int P, const int32_t* perm, long e0, int nE,
+                          long g0, int size, int random, uint64_t seed, int history, float* audio,
+                          int32_t* hist, int32_t* lens, int B, int T, void* stream) {
+  if (!hist || !lens) return WN_ERR_NULL;
+  return corpus_gather(flat, N, utt_off, utt_len, U, item_utt, item_start, P, perm, e0, nE, g0,
+                       size, random, seed, history, audio, hist, lens, B, T, stream);
+}
+
+int wn_corpus_gather_frames_hist(const float* fr, long NF, const int64_t* fr_off,
+                                 const int32_t* fr_len, const int64_t* utt_off,
+                                 const int32_t* utt_len, int U, const int32_t* item_utt,
+                                 const int32_t* item_start, int P, const int32_t* perm, long e0,
+                                 int nE, long g0, int size, int random, uint64_t seed,
+                                 int history, int hop, int ctx, int Lc, float* frames, int Fw,
+                                 float* rows, int B, int T, void* stream) {
   if (!fr || !fr_off || !fr_len || (!frames && !rows)) return WN_ERR_NULL;
   if (B <= 0 || T <= 0 || P <= 0 || NF <= 0 || hop < 1 || ctx < 0 || Lc < 1 ||
       (frames && Fw < 1))
     return WN_ERR_BAD_SHAPE;
   CorpusPlan p;
   const int rc = corpus_plan(p, utt_off, utt_len, U, item_utt, item_start, P, perm, e0, nE, g0,
-                             size, random, seed, B);
+                             size, random, seed, history, B);
   if (rc != WN_OK) return rc;
   if (!wn_aligned16(fr) || (frames && !wn_aligned16(frames)) || (rows && !wn_aligned16(rows)) ||
       (reinterpret_cast<uintptr_t>(fr_off) & 7u) || (reinterpret_cast<uintptr_t>(fr_len) & 3u))
@@ -273,6 +314,18 @@ int wn_corpus_gather_frames(const float* fr, long NF, const int64_t* fr_off,
                        ctx, Lc, rows, B, T, T);
   }
   return wn_check_launch();
+}
+
+int wn_corpus_gather_frames(const float* fr, long NF, const int64_t* fr_off,
+                            const int32_t* fr_len, const int64_t* utt_off,
+                            const int32_t* utt_len, int U, const int32_t* item_utt,
+                            const int32_t* item_start, int P, const int32_t* perm, long e0,
+                            int nE, long g0, int size, int random, uint64_t seed, int hop,
+                            int ctx, int Lc, float* frames, int Fw, float* rows, int B, int T,
+                            void* stream) {
+  return wn_corpus_gather_frames_hist(fr, NF, fr_off, fr_len, utt_off, utt_len, U, item_utt,
+                                      item_start, P, perm, e0, nE, g0, size, random, seed, 0, hop,
+                                      ctx, Lc, frames, Fw, rows, B, T, stream);
 }
 
 }  // extern "C"

@@ -21,11 +21,24 @@
 // being evaluated.  1 / denominator arrives in inv_n like 1 / (B*T) does.
 // One body for both kernels: lengths[b] = T takes exactly the unmasked
 // arithmetic, so the two agree bit for bit there.
+//
+// WINDOW (wn_xent_window): clip b also has starts[b] leading samples of
+// history, fed to the network but predicted by nobody: row t has a target iff
+// starts[b] <= t + 1 < lengths[b].  Rows with t + 1 < starts[b] are treated
+// like padding (nothing to the loss, an all-zero dlogits row, no exponential);
+// row lengths[b] - 1 stays the label-less last row.  starts[b] = 0 takes
+// exactly the masked arithmetic.
 // ---------------------------------------------------------------------------
 // clip b's length: lengths[b] clamped to [0, T]
 __device__ __forceinline__ int clip_len(const int32_t* __restrict__ lengths,
                                         long b, int T) {
   return min(max(lengths[b], 0), T);
+}
+
+// clip b's history: starts[b] clamped to [0, T]; 0 without starts
+__device__ __forceinline__ int clip_start(const int32_t* __restrict__ starts,
+                                          long b, int T) {
+  return starts ? min(max(starts[b], 0), T) : 0;
 }
 
 // One row's float32 softmax statistics, by one wave: maximum, sum of
@@ -93,10 +106,11 @@ __device__ __forceinline__ XentRow xent_row(const float* __restrict__ lp, int Q,
   return r;
 }
 
-template <bool MASKED>
+template <bool MASKED, bool WINDOW>
 __device__ __forceinline__ void xent_body(
     const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    const int32_t* __restrict__ lengths, float* __restrict__ dlogits,
+    const int32_t* __restrict__ starts, const int32_t* __restrict__ lengths,
+    float* __restrict__ dlogits,
     float* __restrict__ loss_partials, long rows, int T, int Q, float inv_n,
     int tf_quirk) {
   __shared__ float wsum[4];
@@ -116,7 +130,8 @@ __device__ __forceinline__ void xent_body(
         vn = *reinterpret_cast<const f32x4*>(logits + nrow * ld + lane * 4);
       const int t = (int)(row % T);
       const int len = MASKED ? clip_len(lengths, row / T, T) : T;
-      if (MASKED && t >= len) {              // padding
+      if (MASKED && (t >= len ||             // padding, history
+                     (WINDOW && t + 1 < clip_start(starts, row / T, T)))) {
         if (dlogits)
           *reinterpret_cast<f32x4*>(dlogits + row * ld + lane * 4) =
               f32x4{0.f, 0.f, 0.f, 0.f};
@@ -150,7 +165,8 @@ __device__ __forceinline__ void xent_body(
     const float* lp = logits + row * ld;
     const int t = (int)(row % T);
     const int len = MASKED ? clip_len(lengths, row / T, T) : T;
-    if (MASKED && t >= len) {                // padding
+    if (MASKED && (t >= len ||               // padding, history
+                   (WINDOW && t + 1 < clip_start(starts, row / T, T)))) {
       if (dlogits)
         for (int c = lane * 4; c < Q; c += 256)
           *reinterpret_cast<f32x4*>(dlogits + row * ld + c) =
@@ -188,8 +204,8 @@ __global__ __launch_bounds__(256) void xent_kernel(
     const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
     float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
     int T, int Q, float inv_n, int tf_quirk) {
-  xent_body<false>(logits, ld, q, nullptr, dlogits, loss_partials, rows, T, Q,
-                   inv_n, tf_quirk);
+  xent_body<false, false>(logits, ld, q, nullptr, nullptr, dlogits,
+                          loss_partials, rows, T, Q, inv_n, tf_quirk);
 }
 
 // lengths [B] and 1 / denominator are read from device memory: a recorded
@@ -199,8 +215,18 @@ __global__ __launch_bounds__(256) void xent_masked_kernel(
     const int32_t* __restrict__ lengths, const float* __restrict__ inv_den,
     float* __restrict__ dlogits, float* __restrict__ loss_partials, long rows,
     int T, int Q, int tf_quirk) {
-  xent_body<true>(logits, ld, q, lengths, dlogits, loss_partials, rows, T, Q,
-                  *inv_den, tf_quirk);
+  xent_body<true, false>(logits, ld, q, nullptr, lengths, dlogits,
+                         loss_partials, rows, T, Q, *inv_den, tf_quirk);
+}
+
+// starts [B] is read from device memory like lengths and 1 / denominator
+__global__ __launch_bounds__(256) void xent_window_kernel(
+    const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
+    const int32_t* __restrict__ starts, const int32_t* __restrict__ lengths,
+    const float* __restrict__ inv_den, float* __restrict__ dlogits,
+    float* __restrict__ loss_partials, long rows, int T, int Q, int tf_quirk) {
+  xent_body<true, true>(logits, ld, q, starts, lengths, dlogits, loss_partials,
+                        rows, T, Q, *inv_den, tf_quirk);
 }
 
 // ---------------------------------------------------------------------------
@@ -219,6 +245,10 @@ __global__ __launch_bounds__(256) void xent_masked_kernel(
 // i + 1024, ... below len_b - 1 in float64 (integers for the flags), a fixed
 // LDS tree finishes: a function of the rows' values and len_b alone, whatever
 // order the workgroups of either kernel ran in.  No atomics.
+//
+// starts (wn_xent_score_window, nullable): rows with t + 1 < starts[b] have
+// no target either; the per-clip sums then run over rows max(starts[b] - 1, 0)
+// .. len_b - 2 in the same order.
 // ---------------------------------------------------------------------------
 #define SCORE_CLIP_THREADS 1024
 
@@ -230,8 +260,9 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 
 __global__ __launch_bounds__(256) void xent_score_rows_kernel(
     const float* __restrict__ logits, long ld, const int32_t* __restrict__ q,
-    const int32_t* __restrict__ lengths, float* __restrict__ nll,
-    int32_t* __restrict__ flag, long rows, int T, int Q) {
+    const int32_t* __restrict__ starts, const int32_t* __restrict__ lengths,
+    float* __restrict__ nll, int32_t* __restrict__ flag, long rows, int T,
+    int Q) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long nwaves = (long)gridDim.x * 4;
   if (Q == 256) {
@@ -247,7 +278,8 @@ __global__ __launch_bounds__(256) void xent_score_rows_kernel(
         vn = *reinterpret_cast<const f32x4*>(logits + nrow * ld + lane * 4);
       const int t = (int)(row % T);
       const int len = lengths ? clip_len(lengths, row / T, T) : T;
-      const int label = (t + 1 < len) ? q[row + 1] : -1;
+      const int label =
+          (t + 1 < len && t + 1 >= clip_start(starts, row / T, T)) ? q[row + 1] : -1;
       if (!(label >= 0 && label < Q)) {      // no target: nothing to evaluate
         if (lane == 0) {
           nll[row] = 0.f;
@@ -275,7 +307,8 @@ __global__ __launch_bounds__(256) void xent_score_rows_kernel(
     const float* lp = logits + row * ld;
     const int t = (int)(row % T);
     const int len = lengths ? clip_len(lengths, row / T, T) : T;
-    const int label = (t + 1 < len) ? q[row + 1] : -1;
+    const int label =
+        (t + 1 < len && t + 1 >= clip_start(starts, row / T, T)) ? q[row + 1] : -1;
     if (!(label >= 0 && label < Q)) {
       if (lane == 0) {
         nll[row] = 0.f;
@@ -295,7 +328,8 @@ __global__ __launch_bounds__(256) void xent_score_rows_kernel(
 
 __global__ __launch_bounds__(SCORE_CLIP_THREADS) void xent_score_clips_kernel(
     const float* __restrict__ nll, const int32_t* __restrict__ flag,
-    const int32_t* __restrict__ lengths, double* __restrict__ clip_nll,
+    const int32_t* __restrict__ starts, const int32_t* __restrict__ lengths,
+    double* __restrict__ clip_nll,
     int32_t* __restrict__ clip_count, int32_t* __restrict__ clip_correct,
     int T) {
   __shared__ double rs[SCORE_CLIP_THREADS];
@@ -306,8 +340,10 @@ __global__ __launch_bounds__(SCORE_CLIP_THREADS) void xent_score_clips_kernel(
   const int32_t* pf = flag + (long)b * T;
   double s = 0.0;
   int c = 0, h = 0;
-  // (rows t >= len - 1 have no target: zeros by construction, not read)
-  for (int t = tid; t < len - 1; t += SCORE_CLIP_THREADS) {
+  // (rows t >= len - 1 and rows t + 1 < start have no target: zeros by
+  // construction, not read)
+  const int t0 = max(clip_start(starts, b, T) - 1, 0);
+  for (int t = t0 + tid; t < len - 1; t += SCORE_CLIP_THREADS) {
     const int f = pf[t];
     s += (double)pn[t];
     c += f & 1;
@@ -402,20 +438,41 @@ int wn_xent_masked(const float* logits, long ld, const int32_t* q,
   return wn_check_launch();
 }
 
+int wn_xent_window(const float* logits, long ld, const int32_t* q,
+                   const int32_t* starts, const int32_t* lengths,
+                   const float* inv_den, float* dlogits, float* loss_partials,
+                   int B, int T, int Q, int tf_quirk, void* stream) {
+  if (!logits || !q || !starts || !lengths || !inv_den || !loss_partials)
+    return WN_ERR_NULL;
+  if (B <= 0 || T <= 0 || Q <= 0) return WN_ERR_BAD_SHAPE;
+  if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
+  if (!wn_aligned16(logits) || (dlogits && !wn_aligned16(dlogits)) ||
+      ((uintptr_t)starts & 3) || ((uintptr_t)lengths & 3) ||
+      ((uintptr_t)inv_den & 3))
+    return WN_ERR_MISALIGNED;
+  const long rows = (long)B * T;
+  hipLaunchKernelGGL(xent_window_kernel, dim3(wn_xent_partials(rows)),
+                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, starts,
+                     lengths, inv_den, dlogits, loss_partials, rows, T, Q,
+                     tf_quirk);
+  return wn_check_launch();
+}
+
 long wn_xent_score_scratch_floats(long rows) {
   return rows > 0 ? 2 * rows : 0;          // flags [rows], row values [rows]
 }
 
-int wn_xent_score(const float* logits, long ld, const int32_t* q,
-                  const int32_t* lengths, float* row_nll, double* clip_nll,
-                  int32_t* clip_count, int32_t* clip_correct, float* scratch,
-                  int B, int T, int Q, void* stream) {
+int wn_xent_score_window(const float* logits, long ld, const int32_t* q,
+                         const int32_t* starts, const int32_t* lengths,
+                         float* row_nll, double* clip_nll, int32_t* clip_count,
+                         int32_t* clip_correct, float* scratch, int B, int T,
+                         int Q, void* stream) {
   if (!logits || !q || !clip_nll || !clip_count || !clip_correct || !scratch)
     return WN_ERR_NULL;
   if (B <= 0 || T <= 0 || Q <= 0 || ld < Q) return WN_ERR_BAD_SHAPE;
   if ((Q & 3) || (ld & 3)) return WN_ERR_UNSUPPORTED;
-  if (!wn_aligned16(logits) || ((uintptr_t)lengths & 3) ||
-      ((uintptr_t)row_nll & 3) || ((uintptr_t)clip_nll & 7) ||
+  if (!wn_aligned16(logits) || ((uintptr_t)starts & 3) ||
+      ((uintptr_t)lengths & 3) || ((uintptr_t)row_nll & 3) || ((uintptr_t)clip_nll & 7) ||
       ((uintptr_t)clip_count & 3) || ((uintptr_t)clip_correct & 3) ||
       ((uintptr_t)scratch & 3))
     return WN_ERR_MISALIGNED;
@@ -425,12 +482,22 @@ int wn_xent_score(const float* logits, long ld, const int32_t* q,
   // read the same bits either way)
   float* nll = row_nll ? row_nll : scratch + rows;
   hipLaunchKernelGGL(xent_score_rows_kernel, dim3(wn_xent_partials(rows)),
-                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, lengths,
-                     nll, flag, rows, T, Q);
+                     dim3(256), 0, (hipStream_t)stream, logits, ld, q, starts,
+                     lengths, nll, flag, rows, T, Q);
   hipLaunchKernelGGL(xent_score_clips_kernel, dim3(B),
                      dim3(SCORE_CLIP_THREADS), 0, (hipStream_t)stream, nll,
-                     flag, lengths, clip_nll, clip_count, clip_correct, T);
+                     flag, starts, lengths, clip_nll, clip_count, clip_correct,
+                     T);
   return wn_check_launch();
+}
+
+int wn_xent_score(const float* logits, long ld, const int32_t* q,
+                  const int32_t* lengths, float* row_nll, double* clip_nll,
+                  int32_t* clip_count, int32_t* clip_correct, float* scratch,
+                  int B, int T, int Q, void* stream) {
+  return wn_xent_score_window(logits, ld, q, nullptr, lengths, row_nll,
+                              clip_nll, clip_count, clip_correct, scratch, B,
+                              T, Q, stream);
 }
 
 int wn_softmax64_row(const float* logits_row, int Q, float* proba,

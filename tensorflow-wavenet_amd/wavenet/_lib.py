@@ -101,6 +101,13 @@ SIGNATURES = {
     'wn_xent': (c_int, [P, c_long, P, P, P, c_int, c_int, c_int, c_int, P]),
     'wn_xent_masked': (c_int, [P, c_long, P, P, P, P, P, c_int, c_int, c_int,
                                c_int, P]),
+    # logits, ld, q, starts, lengths, inv_den, dlogits, loss_partials, B, T,
+    # Q, tf_quirk, stream
+    'wn_xent_window': (c_int, [P, c_long, P, P, P, P, P, P, c_int, c_int,
+                               c_int, c_int, P]),
+    # (wn_xent_score's arguments with starts in front of lengths)
+    'wn_xent_score_window': (c_int, [P, c_long, P, P, P, P, P, P, P, P, c_int,
+                                     c_int, c_int, P]),
     # logits, ld, q, lengths, row_nll, clip_nll, clip_count, clip_correct,
     # scratch, B, T, Q, stream
     'wn_xent_score_scratch_floats': (c_long, [c_long]),
@@ -233,6 +240,17 @@ SIGNATURES = {
                                         c_int, P, c_long, c_int, c_long,
                                         c_int, c_int, c_u64, c_int, c_int,
                                         c_int, P, c_int, P, c_int, c_int, P]),
+    # (the two above with `history` behind seed; wn_corpus_gather_hist: and
+    # hist, lens behind audio)
+    'wn_corpus_gather_hist': (c_int, [P, c_long, P, P, c_int, P, P, c_int, P,
+                                      c_long, c_int, c_long, c_int, c_int,
+                                      c_u64, c_int, P, P, P, c_int, c_int,
+                                      P]),
+    'wn_corpus_gather_frames_hist': (c_int, [P, c_long, P, P, P, P, c_int, P,
+                                             P, c_int, P, c_long, c_int,
+                                             c_long, c_int, c_int, c_u64,
+                                             c_int, c_int, c_int, c_int, P,
+                                             c_int, P, c_int, c_int, P]),
 }
 for _name in ('wn_fastgen_run', 'wn_fastgen_pre', 'wn_fastgen_step',
               'wn_fastgen_persist', 'wn_fastgen_batch_pre',

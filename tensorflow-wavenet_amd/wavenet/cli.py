@@ -26,3 +26,39 @@ def model_from_params(wavenet_params, batch_size, **conditioning):
         initial_filter_width=wavenet_params['initial_filter_width'],
         residual_postproc=wavenet_params.get('residual_postproc', False),
         **conditioning)
+
+
+PIECE_HISTORY_HELP = (
+    'Put up to this many samples of a piece\'s true left context in front of '
+    'it: they are fed to the network but not predicted (WaveNetModel.loss, '
+    'history=), so every predicted sample sees the history it sees at '
+    'generation time.  N samples, or rf = the model\'s receptive field.  '
+    'Default: off (a piece\'s first samples see zeros).')
+
+
+def piece_history_arg(s):
+    """argparse type of --piece_history: 'rf' or a non-negative int."""
+    if s == 'rf':
+        return s
+    try:
+        n = int(s)
+    except ValueError:
+        n = -1
+    if n < 0:
+        raise ValueError('--piece_history takes a non-negative int or rf, '
+                         'got {}'.format(s))
+    return n
+
+
+def piece_history(value, wavenet_params):
+    """The samples of --piece_history (None: 0) for a wavenet_params.json
+    dict: 'rf' is WaveNetModel.receptive_field of that model."""
+    if value is None:
+        return 0
+    if value != 'rf':
+        return int(value)
+    from .model import receptive_field
+    return receptive_field(wavenet_params['dilations'],
+                           wavenet_params['filter_width'],
+                           wavenet_params['scalar_input'],
+                           wavenet_params['initial_filter_width'])

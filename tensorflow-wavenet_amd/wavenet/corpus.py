@@ -19,6 +19,11 @@ The rule (tests/corpus_ref.py restates it independently):
     start    'random', n_u > size:
              draw_bits(seed ^ 0x63726f70, g) % (n_u - size + 1)
     draw_bits(seed, c) = splitmix64(seed ^ splitmix64(c))   (csrc/wn_common.h)
+    history  H > 0 (default 0): h = min(H, start), start' = start - h,
+             n' = n + h -- the piece with h samples of its true left context
+             in front, which the loss feeds but does not predict
+             (WaveNetModel.loss, history=).  Everything below uses
+             (start', n').  Items, orders and drawn starts do not depend on H.
 
 The order is a pure function of (seed, step, B): a run resumed at step k
 continues the uninterrupted run's sequence, and a batch may straddle epochs.
@@ -55,9 +60,9 @@ CROP_SALT = 0x63726f70          # 'crop'
 LC_CONTEXT_MAX = 8              # WaveNetModel.LC_CONTEXT_MAX
 _M64 = (1 << 64) - 1
 
-Plan = collections.namedtuple('Plan', 'utt start n gc T')
+Plan = collections.namedtuple('Plan', 'utt start n gc T history')
 Batch = collections.namedtuple('Batch',
-                               'audio lengths gc frames offsets rows')
+                               'audio lengths gc frames offsets rows history')
 
 
 def _is_int(v):
@@ -92,7 +97,7 @@ class CorpusIndex(object):
     library."""
 
     def __init__(self, lengths, category_ids=None, sample_size=None,
-                 crop='pieces', seed=0):
+                 crop='pieces', seed=0, history=0):
         if crop not in ('pieces', 'random'):
             raise ValueError("crop must be 'pieces' or 'random', got %r"
                              % (crop,))
@@ -105,6 +110,10 @@ class CorpusIndex(object):
         if not _is_int(seed) or not 0 <= seed <= _M64:
             raise ValueError('seed must be an int in [0, 2^64), got %r'
                              % (seed,))
+        if not _is_int(history) or not 0 <= history < 1 << 31:
+            raise ValueError('history must be an int in [0, 2^31), got %r'
+                             % (history,))
+        self.history = int(history)
         n = np.asarray(lengths)
         if n.size == 0:
             n = n.astype(np.int64).reshape(-1)
@@ -177,9 +186,12 @@ class CorpusIndex(object):
         return e0, (g0 + int(B) - 1) // self.P - e0 + 1
 
     def plan(self, step, B, T=None):
-        """Batch `step` of B slots: Plan(utt, start, n, gc, T): per slot the
-        utterance, the first sample within it, the sample count, the speaker
-        id (None without category_ids); T = max(n).  A given T cuts n."""
+        """Batch `step` of B slots: Plan(utt, start, n, gc, T, history): per
+        slot the utterance, the first sample within it, the sample count, the
+        speaker id (None without category_ids); T = max(n); the leading
+        samples of the slot that are history (0 for an index without).  A
+        given T cuts n (and history to n).  With history, start and n are
+        start' and n' of the module docstring."""
         if not _is_int(step) or step < 0 or not _is_int(B) or B < 1:
             raise ValueError('plan: step >= 0 and B >= 1 are required, got '
                              '%r, %r' % (step, B))
@@ -202,11 +214,15 @@ class CorpusIndex(object):
             start = self.item_start[item].astype(np.int64)
             n = nu - start if not self.sample_size else \
                 np.minimum(self.sample_size, nu - start)
+        h = np.minimum(self.history, start)
+        start, n = start - h, n + h
         if T is not None:
             n = np.minimum(n, int(T))
+        h = np.minimum(h, n)
         gc = None if self.category_ids is None else self.category_ids[utt]
         return Plan(utt, start, n.astype(np.int64), gc,
-                    int(n.max()) if T is None else int(T))
+                    int(n.max()) if T is None else int(T),
+                    h.astype(np.int64))
 
     def frame_window(self, plan, hop, frame_counts, m=LC_CONTEXT_MAX):
         """(f_lo, f_hi, offsets) int64 [B] of a plan's frames windows
@@ -252,10 +268,11 @@ class DeviceCorpus(object):
     def __init__(self, audio_dir, sample_rate, gc_enabled, sample_size=None,
                  silence_threshold=None, crop='pieces', seed=0, rank=0,
                  world=1, spec=None, device=None, max_bytes=32 << 30, *,
-                 normalize=None, normalize_clip=None, stats_allreduce=None):
+                 normalize=None, normalize_clip=None, stats_allreduce=None,
+                 history=0):
         from . import audio_reader as ar
         from . import features
-        _check_args(sample_size, crop, seed, max_bytes)
+        _check_args(sample_size, crop, seed, max_bytes, history)
         if not _is_int(rank) or not _is_int(world) or not 0 <= rank < world:
             raise ValueError('0 <= rank < world is required, got rank %r, '
                              'world %r' % (rank, world))
@@ -304,7 +321,8 @@ class DeviceCorpus(object):
                              .format(audio_dir))
         self.files = kept
         self._setup(clips, ids if gc_enabled else None, None, None,
-                    dict(sample_size=sample_size, crop=crop, seed=seed),
+                    dict(sample_size=sample_size, crop=crop, seed=seed,
+                         history=history),
                     spec, device, max_bytes, norm_kw)
         self.gc_category_cardinality = card
 
@@ -328,7 +346,8 @@ class DeviceCorpus(object):
             raise ValueError('from_arrays: world must be a positive int, '
                              'got %r' % (world,))
         _check_args(index_kw.get('sample_size'), index_kw.get('crop', 'pieces'),
-                    index_kw.get('seed', 0), max_bytes)
+                    index_kw.get('seed', 0), max_bytes,
+                    index_kw.get('history', 0))
         clips = []
         for a in arrays:
             a = np.asarray(a)
@@ -561,18 +580,35 @@ class DeviceCorpus(object):
                 int(step) * int(B), ix.sample_size or 0,
                 int(ix.crop == 'random'), ix.seed)
 
-    def gather(self, step, B, out, _args=None):
+    def gather(self, step, B, out, _args=None, _slot=0):
         """The audio gather of batch `step` alone, into `out` (device
-        float32 [B, T], contiguous): one launch on the current stream."""
-        _lib.call('wn_corpus_gather', _lib.ptr(self.flat), self.flat.numel(),
-                  *(_args or self.plan_args(step, B)), _lib.ptr(out), B,
-                  int(out.shape[1]), _lib.stream())
+        float32 [B, T], contiguous): one launch on the current stream (with
+        history a second, tiny one: the slots' history and lengths as device
+        int32 [B] each, left in `device_plan`)."""
+        args = _args or self.plan_args(step, B)
+        if not self.index.history:
+            _lib.call('wn_corpus_gather', _lib.ptr(self.flat),
+                      self.flat.numel(), *args, _lib.ptr(out), B,
+                      int(out.shape[1]), _lib.stream())
+            return
+        import torch
+        ring = self._bufs.setdefault('plan', [None] * self.RING)
+        if ring[_slot] is None or ring[_slot].numel() < 2 * B:
+            ring[_slot] = torch.empty(2 * B, dtype=torch.int32,
+                                      device=self.device)
+        hist, lens = ring[_slot][:B], ring[_slot][B:2 * B]
+        _lib.call('wn_corpus_gather_hist', _lib.ptr(self.flat),
+                  self.flat.numel(), *args, self.index.history, _lib.ptr(out),
+                  _lib.ptr(hist), _lib.ptr(lens), B, int(out.shape[1]),
+                  _lib.stream())
+        self.device_plan = (hist, lens)
 
     def batch(self, step, B, T=None, lc='auto'):
         """Batch `step` (module docstring): Batch(audio device float32 [B, T],
         lengths host int64 [B], gc host int32 [B] or None, frames device
         float32 [B, Fw, Lc] + offsets host int64 [B] or rows device float32
-        [B, T, Lc], else None).  T: cut to this many samples (default: the
+        [B, T, Lc], else None; history host int64 [B]: the leading samples of
+        every slot that are its history, all 0 without).  T: cut to this many samples (default: the
         longest item's).  lc: 'frames', 'rows', None, or 'auto' = 'frames'
         where the corpus holds frames."""
         import torch
@@ -589,7 +625,7 @@ class DeviceCorpus(object):
         with torch.cuda.device(self.device):
             args = self.plan_args(step, B)
             audio = self._buffer('audio', slot, (B, p.T))
-            self.gather(step, B, audio, args)
+            self.gather(step, B, audio, args, slot)
             frames = offsets = rows = None
             if lc is not None:
                 m = LC_CONTEXT_MAX
@@ -600,13 +636,16 @@ class DeviceCorpus(object):
                         p, self.hop, self.frame_counts, m)[2]
                 else:
                     rows = self._buffer('rows', slot, (B, p.T, self.Lc))
-                _lib.call('wn_corpus_gather_frames',
+                H = self.index.history
+                _lib.call('wn_corpus_gather_frames_hist' if H else
+                          'wn_corpus_gather_frames',
                           _lib.ptr(self.frames_flat),
                           self.frames_flat.numel(), _lib.ptr(self._fr_off),
-                          _lib.ptr(self._fr_len), *args, self.hop, m,
-                          self.Lc, _lib.ptr(frames), Fw, _lib.ptr(rows), B,
-                          p.T, _lib.stream())
-        return Batch(audio, p.n.copy(), p.gc, frames, offsets, rows)
+                          _lib.ptr(self._fr_len), *args, *([H] if H else []),
+                          self.hop, m, self.Lc, _lib.ptr(frames), Fw,
+                          _lib.ptr(rows), B, p.T, _lib.stream())
+        return Batch(audio, p.n.copy(), p.gc, frames, offsets, rows,
+                     p.history.copy())
 
 
 def _check_normalize(normalize, clip, allreduce, world, channels, has_frames):
@@ -642,9 +681,9 @@ def _check_normalize(normalize, clip, allreduce, world, channels, has_frames):
                 world=int(world))
 
 
-def _check_args(sample_size, crop, seed, max_bytes):
+def _check_args(sample_size, crop, seed, max_bytes, history=0):
     """CorpusIndex's checks of these, and max_bytes (before any loading)."""
-    CorpusIndex([1], None, sample_size, crop, seed)
+    CorpusIndex([1], None, sample_size, crop, seed, history)
     if not _is_int(max_bytes) or max_bytes < 1:
         raise ValueError('max_bytes must be a positive int, got %r'
                          % (max_bytes,))

@@ -27,12 +27,24 @@ class ValidationSet(object):
     next to every wav, upsampled by repetition (lc_hop samples per frame), or
     with lc_frames=True the clip's frames and the piece's offset.  Global
     conditioning: the id of `p<id>_<rec>.wav` (below gc_cardinality where
-    that is given)."""
+    that is given).
+
+    history=H > 0: piece k of a file brings h = min(H, k * sample_size)
+    samples of its left context, [k * sample_size - h, (k + 1) * sample_size)
+    of the file, with the conditioning of those samples; net.score gets
+    history=h and counts only the piece's own rows (`piece_history`: h per
+    piece)."""
 
     def __init__(self, directory, sample_rate, *, sample_size=None,
                  silence_threshold=None, gc_enabled=False, gc_cardinality=None,
                  lc_channels=None, lc_hop=None, lc_frames=False, rank=0,
-                 world=1):
+                 world=1, history=0):
+        if isinstance(history, bool) or \
+                not isinstance(history, (int, np.integer)) or history < 0:
+            raise ValueError('history must be a non-negative int, got %r'
+                             % (history,))
+        self.history = int(history)
+        self.piece_history = []
         self.lc_channels = lc_channels
         self.lc_frames = bool(lc_frames) and lc_channels is not None
         self.gc_enabled = bool(gc_enabled)
@@ -78,13 +90,16 @@ class ValidationSet(object):
                         audio = ar.trim_silence(audio, silence_threshold)
             step = int(sample_size) if sample_size else max(audio.size, 1)
             for k in range(0, audio.size, step):
-                piece = np.ascontiguousarray(audio[k:k + step])
+                h = min(self.history, k)
+                piece = np.ascontiguousarray(audio[k - h:k + step])
                 if self.lc_frames:
-                    cond = (lc, int(lo) + k)
+                    cond = (lc, int(lo) + k - h)
                 else:
-                    cond = None if lc is None else lc[k:k + step]
+                    cond = None if lc is None else lc[k - h:k + step]
                 self.pieces.append((piece, f, gc, cond))
+                self.piece_history.append(h)
         if not sample_size:
+            # (whole utterances: every h above is 0)
             self.pieces.sort(key=lambda p: p[0].shape[0])   # (stable)
 
     def __len__(self):
@@ -94,7 +109,9 @@ class ValidationSet(object):
         """Yields (audio float32 [b, Tmax], lengths int64 [b], gc ids int32
         [b] or None, lc) with b <= B pieces in order, zero padded behind
         each piece; lc: rows float32 [b, Tmax, Lc], or (frames float32
-        [b, Fmax, Lc], offsets int64 [b]) in frames mode, or None."""
+        [b, Fmax, Lc], offsets int64 [b]) in frames mode, or None.  A set
+        built with history > 0 yields a fifth item, the pieces' history
+        int64 [b] (counted in lengths)."""
         B = int(B)
         if B < 1:
             raise ValueError('batch size must be positive, got %d' % B)
@@ -119,38 +136,44 @@ class ValidationSet(object):
                 lc = np.zeros((b, tmax, self.lc_channels), np.float32)
                 for j, p in enumerate(group):
                     lc[j, :lengths[j]] = p[3]
-            yield audio, lengths, gc, lc
+            if self.history > 0:
+                yield audio, lengths, gc, lc, np.array(
+                    self.piece_history[i:i + B], np.int64)
+            else:
+                yield audio, lengths, gc, lc
 
 
 def with_features(net, spec, batches):
     """`batches` of an audio-only ValidationSet with the local conditioning
     computed on the device from each batch's own audio (features.MelSpec
     `spec`): frames at offset 0 for an upsampler model, else rows."""
-    for audio, lengths, gc, _ in batches:
+    for audio, lengths, gc, _, *hist in batches:
         lc = net.local_condition_from_audio(spec, audio, lengths)
-        yield audio, lengths, gc, ((lc, 0) if net.lc_up else lc)
+        yield (audio, lengths, gc, ((lc, 0) if net.lc_up else lc), *hist)
 
 
 def with_emphasis(emphasis, batches):
     """`batches` with the audio pre-emphasised on the device (emphasis.
     Emphasis), each clip over its own length -- behind with_features, whose
     features are those of the natural signal."""
-    for audio, lengths, gc, lc in batches:
-        yield emphasis.pre(audio, lengths), lengths, gc, lc
+    for audio, lengths, gc, lc, *hist in batches:
+        yield (emphasis.pre(audio, lengths), lengths, gc, lc, *hist)
 
 
 def totals(net, batches, max_batches=None):
     """float64 [4] on the device: (sum of nll, targets, hits, clips) over
     net.score of every batch (at most max_batches of them).  No host wait."""
     tot, clips = None, 0
-    for i, (audio, lengths, gc, lc) in enumerate(batches):
+    for i, (audio, lengths, gc, lc, *hist) in enumerate(batches):
         if max_batches is not None and i >= max_batches:
             break
         off = 0
         if isinstance(lc, tuple):
             lc, off = lc
+        # (a fifth item: the pieces' history, ValidationSet(history=...))
+        kw = dict(history=hist[0]) if hist else {}
         s = net.score(audio, gc, local_condition_batch=lc,
-                      local_condition_offset=off, lengths=lengths)
+                      local_condition_offset=off, lengths=lengths, **kw)
         part = torch.stack([s.nll.sum(), s.count.sum().to(torch.float64),
                             s.correct.sum().to(torch.float64)])
         tot = part if tot is None else tot + part

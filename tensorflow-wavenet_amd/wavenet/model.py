@@ -74,6 +74,54 @@ def check_lengths(lengths, loss_denominator, B, T, what):
     return n, den
 
 
+def receptive_field(dilations, filter_width, scalar_input=False,
+                    initial_filter_width=32):
+    """R: logits row t depends on input samples t - R + 1 .. t and on no
+    earlier one.  A filter of K taps at dilation d reaches back s(K) * d
+    samples, s(K) = (K - 1) + (K - 1) // 2 (the tap rule of
+    csrc/wn_layer.hip, tap_shift); the causal layer has initial_filter_width
+    taps with scalar_input, else filter_width.  Host arithmetic only."""
+    def reach(K):
+        return (int(K) - 1) + (int(K) - 1) // 2
+    Kc = initial_filter_width if scalar_input else filter_width
+    return 1 + reach(Kc) + reach(filter_width) * int(sum(dilations))
+
+
+def check_history(history, mask, loss_denominator, B, T, what):
+    """The `history` of a loss / score call, checked on the host: B ints (or
+    one for all clips) with 0 <= history[b] <= n[b], n[b] = lengths[b] or T.
+    Returns (mask, history as int32 numpy [B]); (mask, None) without history.
+    The mask always carries lengths then (T for every clip without them), and
+    its denominator is sum(n - history) unless the caller gave one."""
+    if history is None:
+        return mask, None
+    h = history
+    if hasattr(h, 'detach'):
+        h = h.detach().cpu().numpy()
+    h = np.asarray(h)
+    if h.dtype == object or h.dtype == np.bool_ or \
+            not np.issubdtype(h.dtype, np.integer):
+        raise ValueError('%s: history must be an integer or %d integers '
+                         '(dtype %s)' % (what, B, h.dtype))
+    if h.shape not in ((), (B,)):
+        raise ValueError('%s: history must be one int or have shape [%d], '
+                         'got %s' % (what, B, list(h.shape)))
+    h = np.broadcast_to(h.astype(np.int64), (B,))
+    n = np.full(B, T, np.int64) if mask is None else mask[0].astype(np.int64)
+    if (h < 0).any() or (h > n).any():
+        raise ValueError('%s: history must lie in [0, n[b]], n = %s, got %s'
+                         % (what, n.tolist(), h.tolist()))
+    total = int((n - h).sum())
+    # (a caller that gives the denominator -- a data-parallel rank -- may
+    # hold clips without a target while another rank holds some)
+    if total == 0 and (mask is None or loss_denominator is None):
+        raise ValueError('%s: history leaves no sample to predict: '
+                         'sum(n - history) is 0' % what)
+    den = float(total) if mask is None or loss_denominator is None \
+        else mask[1]
+    return (n.astype(np.int32), den), h.astype(np.int32)
+
+
 def _n_codes(codes):
     """Number of codes of a seed (None: the one default code)."""
     if codes is None:
@@ -291,6 +339,13 @@ class WaveNetModel(object):
     _lc_input = lcond.check
     _lc_frames = lcond.frames
     _lc_forward_ok = lcond.forward_ok
+
+    @property
+    def receptive_field(self):
+        """The model's receptive field in samples (receptive_field above):
+        5117 for the default stack.  Needs no library and no device."""
+        return receptive_field(self.dilations, self.filter_width,
+                               self.scalar_input, self.initial_filter_width)
 
     @property
     def stack_variant(self):
@@ -693,7 +748,8 @@ class WaveNetModel(object):
              local_condition_batch=None,
              local_condition_offset=0,
              lengths=None,
-             loss_denominator=None):
+             loss_denominator=None,
+             history=None):
         '''Creates a WaveNet network and returns the autoencoding loss
         (model.py:628-685).  input_batch: float audio in [-1, 1], anything
         reshapeable to [batch_size, -1].  With backward=True (default) the
@@ -723,7 +779,17 @@ class WaveNetModel(object):
         matter.  loss_denominator (a positive number, only with lengths)
         replaces sum(lengths): data-parallel ranks pass
         parallel.masked_denominator, so that their averaged gradient is the
-        masked mean over the global batch.'''
+        masked mean over the global batch.
+
+        history (batch_size ints or one int, 0 <= history[b] <= n[b] with
+        n[b] = lengths[b], or T without lengths): the first history[b]
+        samples of clip b are fed to the network but predicted by nobody.
+        Clip b is the clip of n[b] samples fed alone, as above; row t has a
+        target iff history[b] <= t + 1 < n[b]; rows with t + 1 < history[b]
+        add nothing to the loss or to any gradient; row n[b] - 1 stays the
+        label-less last row; the mean is taken over sum(n - history) rows
+        (loss_denominator still replaces it).  history = 0 is the call
+        without history, bit for bit.'''
         self._check_supported()
         B = self.batch_size
         a = input_batch
@@ -731,30 +797,36 @@ class WaveNetModel(object):
             a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
         mask = check_lengths(lengths, loss_denominator, B, a.shape[1], 'loss')
+        mask, hist = check_history(history, mask, loss_denominator, B,
+                                   a.shape[1], 'loss')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'loss')
         return self._loss(mu_law_encode(a, self.Q), global_condition_batch,
-                          l2_regularization_strength, backward, a, lc, mask)
+                          l2_regularization_strength, backward, a, lc, mask,
+                          hist)
 
     def loss_from_codes(self, q, global_condition_batch=None,
                         l2_regularization_strength=None, backward=True,
                         audio=None, *, local_condition_batch=None,
                         local_condition_offset=0, lengths=None,
-                        loss_denominator=None):
+                        loss_denominator=None, history=None):
         self._check_supported()
         q = q.reshape(self.batch_size, -1)
         mask = check_lengths(lengths, loss_denominator, self.batch_size,
                              q.shape[1], 'loss')
+        mask, hist = check_history(history, mask, loss_denominator,
+                                   self.batch_size, q.shape[1], 'loss')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          self.batch_size, q.shape[1], 'loss')
         return self._loss(q, global_condition_batch,
                           l2_regularization_strength, backward, audio, lc,
-                          mask)
+                          mask, hist)
 
     def _loss(self, q, global_condition_batch, l2_regularization_strength,
-              backward, audio, lc, mask=None):
+              backward, audio, lc, mask=None, hist=None):
         """loss_from_codes on codes q [B, T] with the LC input checked
-        (local_condition.check) and the lengths (check_lengths)."""
+        (local_condition.check), the lengths (check_lengths) and the history
+        (check_history)."""
         B, T = q.shape
         N = B * T
         ws = self._workspace(B, T, backward)
@@ -795,11 +867,22 @@ class WaveNetModel(object):
             inv = np.float32(1.0) / np.float32(den)
             ws.xent_mask.copy_(torch.from_numpy(np.concatenate(
                 [lengths, np.array([inv], np.float32).view(np.int32)])))
-            _lib.call('wn_xent_masked', _lib.ptr(ws.logits), self.Q,
-                      _lib.ptr(ws.q), _lib.ptr(ws.xent_mask),
-                      _lib.ptr(ws.xent_mask[B:]),
-                      _lib.ptr(ws.logits) if backward else None,
-                      _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk, st)
+            if hist is None:
+                _lib.call('wn_xent_masked', _lib.ptr(ws.logits), self.Q,
+                          _lib.ptr(ws.q), _lib.ptr(ws.xent_mask),
+                          _lib.ptr(ws.xent_mask[B:]),
+                          _lib.ptr(ws.logits) if backward else None,
+                          _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk,
+                          st)
+            else:
+                # staged like the lengths: read by the kernel when it runs
+                ws.xent_hist.copy_(torch.from_numpy(hist))
+                _lib.call('wn_xent_window', _lib.ptr(ws.logits), self.Q,
+                          _lib.ptr(ws.q), _lib.ptr(ws.xent_hist),
+                          _lib.ptr(ws.xent_mask), _lib.ptr(ws.xent_mask[B:]),
+                          _lib.ptr(ws.logits) if backward else None,
+                          _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk,
+                          st)
         _lib.call('wn_reduce_slabs', _lib.ptr(ws.loss_parts), ws.nparts + 2, 1, 1,
                   0, 0, 1, _lib.ptr(ws.loss), 0, 1, 0, st)
         loss = ws.loss[0] / den                         # reduce_mean, :666
@@ -836,7 +919,7 @@ class WaveNetModel(object):
 
     def score(self, input_batch, global_condition_batch=None, *,
               local_condition_batch=None, local_condition_offset=0,
-              lengths=None, per_sample=False):
+              lengths=None, per_sample=False, history=None):
         '''Scores held-out audio: per-clip negative log-likelihood, target
         count and top-1 hits.  Forward only -- the pass predict_proba makes,
         on the forward-only workspace: no gradient is touched, no all-reduce
@@ -861,7 +944,12 @@ class WaveNetModel(object):
         nll.sum() / sum(n) and loss(backward=False) == nll.sum() / (B * T)
         (the reference's mean keeps the label-less rows in its denominator),
         while nll.sum() / count.sum() is the true mean negative
-        log-likelihood per predicted sample, in nats; / ln 2 gives bits.'''
+        log-likelihood per predicted sample, in nats; / ln 2 gives bits.
+
+        history (as for `loss`): rows with t + 1 < history[b] have no target
+        either: count[b] = n[b] - max(history[b], 1), and
+        loss(backward=False, lengths=n, history=h) == nll.sum() /
+        sum(n - h).'''
         self._check_supported()
         a = input_batch
         if not isinstance(a, torch.Tensor):
@@ -870,15 +958,18 @@ class WaveNetModel(object):
             else self.batch_size
         a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
         mask = check_lengths(lengths, None, B, a.shape[1], 'score')
+        mask, hist = check_history(history, mask, None, B, a.shape[1],
+                                   'score')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'score')
         from . import scoring
         return scoring.score(self, mu_law_encode(a, self.Q),
-                             global_condition_batch, a, lc, mask, per_sample)
+                             global_condition_batch, a, lc, mask, per_sample,
+                             hist)
 
     def score_from_codes(self, q, global_condition_batch=None, audio=None, *,
                          local_condition_batch=None, local_condition_offset=0,
-                         lengths=None, per_sample=False):
+                         lengths=None, per_sample=False, history=None):
         """`score` on mu-law codes q (int, [B, T] with any B >= 1, else
         reshaped to [batch_size, -1]); audio: the float audio a scalar_input
         model needs."""
@@ -889,11 +980,13 @@ class WaveNetModel(object):
             else self.batch_size
         q = q.reshape(B, -1)
         mask = check_lengths(lengths, None, B, q.shape[1], 'score')
+        mask, hist = check_history(history, mask, None, B, q.shape[1],
+                                   'score')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, q.shape[1], 'score')
         from . import scoring
         return scoring.score(self, q, global_condition_batch, audio, lc, mask,
-                             per_sample)
+                             per_sample, hist)
 
     def _l2_tmp(self):
         if not hasattr(self, '_l2_parts'):

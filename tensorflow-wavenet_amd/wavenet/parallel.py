@@ -257,7 +257,7 @@ def agree_step(n_samples, ok=True, device='cpu'):
     return int(t[0]), bool(int(t[1]))
 
 
-def masked_denominator(lengths, device='cpu'):
+def masked_denominator(lengths, device='cpu', history=None):
     """The `loss_denominator` of a masked loss step (WaveNetModel.loss with
     `lengths`): (sum of lengths over ALL ranks' clips) / world.  Every rank
     divides its loss and gradients by it, and the optimizer averages the
@@ -265,8 +265,14 @@ def masked_denominator(lengths, device='cpu'):
     over the global batch; the ranks' logged losses average to the global
     masked mean as well.  The lengths are host data known before the step:
     one host collective of one integer that never waits for the device.
-    Call it after agree_step, with the lengths already cut to the common T."""
+    Call it after agree_step, with the lengths already cut to the common T.
+    history (the loss call's, cut to the lengths): the sum runs over
+    lengths - history."""
     total = int(torch.as_tensor(lengths).to(torch.int64).sum())
+    if history is not None:
+        n = torch.as_tensor(lengths).to(torch.int64)
+        h = torch.as_tensor(history).to(torch.int64).expand_as(n)
+        total = int((n - torch.minimum(h, n)).sum())
     if not is_distributed():
         return float(total)
     group, device = _ctl(device)

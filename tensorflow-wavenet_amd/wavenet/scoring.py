@@ -14,10 +14,11 @@ from . import train_pass
 Score = collections.namedtuple('Score', 'nll count correct per_sample')
 
 
-def score(net, q, global_condition_batch, audio, lc, mask, per_sample):
+def score(net, q, global_condition_batch, audio, lc, mask, per_sample,
+          hist=None):
     """Score codes q [B, T] (any B >= 1) with the LC input checked
-    (local_condition.check) and the lengths (model.check_lengths).  Nothing
-    here waits for the device."""
+    (local_condition.check), the lengths (model.check_lengths) and the
+    history (model.check_history).  Nothing here waits for the device."""
     B, T = q.shape
     ws = net._workspace(B, T, False)
     ws.q.copy_(q.reshape(-1))
@@ -45,10 +46,18 @@ def score(net, q, global_condition_batch, audio, lc, mask, per_sample):
         # them from device memory
         lengths = ws.xent_mask[:B]
         lengths.copy_(torch.from_numpy(mask[0]))
-    _lib.call('wn_xent_score', _lib.ptr(ws.logits), net.Q, _lib.ptr(ws.q),
-              _lib.ptr(lengths), _lib.ptr(rows), _lib.ptr(nll),
-              _lib.ptr(count), _lib.ptr(correct), _lib.ptr(ws.score_scratch),
-              B, T, net.Q, _lib.stream())
+    if hist is None:
+        _lib.call('wn_xent_score', _lib.ptr(ws.logits), net.Q,
+                  _lib.ptr(ws.q), _lib.ptr(lengths), _lib.ptr(rows),
+                  _lib.ptr(nll), _lib.ptr(count), _lib.ptr(correct),
+                  _lib.ptr(ws.score_scratch), B, T, net.Q, _lib.stream())
+    else:
+        ws.xent_hist.copy_(torch.from_numpy(hist))
+        _lib.call('wn_xent_score_window', _lib.ptr(ws.logits), net.Q,
+                  _lib.ptr(ws.q), _lib.ptr(ws.xent_hist), _lib.ptr(lengths),
+                  _lib.ptr(rows), _lib.ptr(nll), _lib.ptr(count),
+                  _lib.ptr(correct), _lib.ptr(ws.score_scratch), B, T, net.Q,
+                  _lib.stream())
     # 0, or NaN when a dependency wait of the forward stack launch expired
     # (as predict_proba): a wrong score is never returned silently
     return Score(nll + ws.loss_parts[0], count, correct, rows)

@@ -11,6 +11,9 @@ batch comes from:
                         the planned batch cut to n_t samples: (audio on the
                         device, lc, lc_offset).  lengths: the clips' real
                         lengths as the loss gets them, or None.
+    history(step, B, n_t)    the planned batch's leading history samples per
+                        clip, cut to n_t (host int64 [B]), or None for a
+                        source without history (train.py --piece_history)
     start(device) / stop()   the reader threads; device: the model's.
     checkpoint_entry(step), gc_category_cardinality, lc
 
@@ -68,6 +71,9 @@ class _EmphasisStep(object):
     """What the two sources share: `front` and the pre-emphasis of a batch
     into one of two buffers of the source's own."""
     front = None
+
+    def history(self, step, B, n_t):
+        return None
 
     def _emphasise(self, audio, lengths):
         """audio: device float32 [B, T], left as it is."""
@@ -169,9 +175,17 @@ class CorpusSource(_EmphasisStep):
         pass
 
     def plan(self, step, B):
+        # (with history the loss always gets the lengths: a slot's history
+        # is counted from its own first sample)
         p = self.corpus.plan(self.base + step, B)
-        return (p.T, p.n if self.lengths else None,
+        with_n = self.lengths or self.corpus.index.history > 0
+        return (p.T, p.n if with_n else None,
                 torch.from_numpy(p.gc) if self.gc else None)
+
+    def history(self, step, B, n_t):
+        if not self.corpus.index.history:
+            return None
+        return self.corpus.plan(self.base + step, B, T=n_t).history
 
     def take(self, step, B, n_t, lengths=None):
         cb = self.corpus.batch(self.base + step, B, T=n_t, lc=self.lc)
@@ -317,7 +331,8 @@ class StepLog(object):
 def validate(net, optimizer, vset, spec, args, emphasis=None):
     """Score the validation set with the weights as they are (the EMA shadow
     with --validate_ema): every rank its shard, ONE sum over the ranks
-    whatever a shard holds; with `emphasis` the audio is pre-emphasised
+    whatever a shard holds (a set built with history: each piece behind its
+    left context, which is not scored); with `emphasis` the audio is pre-emphasised
     behind the front end, as the training batches are.  Returns
     evaluate.summary's dict."""
     from . import evaluate as ev

@@ -98,6 +98,8 @@ class _Workspace(object):
         # word, the bits of float32 1 / denominator, staged per call; the
         # kernel reads them from here, so a replayed launch sees this call's
         alloc('xent_mask', (B + 1,), torch.int32, fill=0)
+        # ... and the clips' history (loss(history=...)), staged the same way
+        alloc('xent_hist', (B,), torch.int32, fill=0)
         alloc('proba', (Q,))
         lcond.alloc_workspace(net, self, alloc, None)
         if net.blocked:

@@ -30,7 +30,9 @@ import torch  # noqa: E402
 from wavenet import emphasis, features, local_condition  # noqa: E402
 from wavenet.checkpoint import (  # noqa: E402,F401
     checkpoint_path, latest_checkpoint, load, open_latest, save)
-from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
+from wavenet.cli import (  # noqa: E402
+    PIECE_HISTORY_HELP, model_from_params, piece_history, piece_history_arg,
+    str_to_bool)
 
 BATCH_SIZE = 1
 DATA_DIRECTORY = './VCTK-Corpus'
@@ -175,6 +177,13 @@ def get_arguments(argv=None):
                         'computes every utterance\'s frames once at load and '
                         'gives each piece the frames of its place in the '
                         'utterance.')
+    p.add_argument('--piece_history', type=piece_history_arg, default=None,
+                   metavar='N|rf',
+                   help='--device_corpus true with --sample_size: '
+                        + PIECE_HISTORY_HELP + '  The loss then always gets '
+                        'the clips\' lengths, the step line shows the '
+                        'predicted samples, and --validation_dir is scored '
+                        'with the same history.')
     emphasis.add_cli_flag(p, train=True)
     args = p.parse_args(argv)
     if args.preemphasis is not None:
@@ -198,6 +207,12 @@ def get_arguments(argv=None):
             p.error('--crop random needs --sample_size')
     elif args.crop is not None:
         p.error('--crop needs --device_corpus true')
+    if args.piece_history is not None:
+        missing = [flag for flag, given in (
+            ('--device_corpus true', args.device_corpus),
+            ('--sample_size', bool(args.sample_size))) if not given]
+        if missing:
+            p.error('--piece_history needs %s' % ' and '.join(missing))
     if args.lc_feature_context == 'utterance' and not (
             args.device_corpus and args.lc_features == 'mel'):
         p.error('--lc_feature_context utterance needs --device_corpus true '
@@ -263,7 +278,9 @@ def corpus_first_batch(stored, entry):
     has this run's settings `entry`, else it starts the sequence again."""
     if stored is None:
         return 0
-    if {k: stored.get(k) for k in entry} != entry:
+    # ('history' is not compared: the pieces' sequence does not depend on it)
+    same = [k for k in entry if k != 'history']
+    if {k: stored.get(k) for k in same} != {k: entry[k] for k in same}:
         print("  The checkpoint's corpus settings {} differ: the corpus "
               "starts again.".format(stored))
         return 0
@@ -448,7 +465,9 @@ def open_corpus(args, wavenet_params, front, rank, world):
         args.gc_channels is not None, sample_size=args.sample_size or None,
         silence_threshold=args.silence_threshold,
         crop=args.crop or 'pieces', seed=CORPUS_SEED, rank=rank, world=world,
-        spec=front.spec if utt_ctx else None, **corpus_norm)
+        spec=front.spec if utt_ctx else None,
+        history=piece_history(args.piece_history, wavenet_params),
+        **corpus_norm)
 
 
 def front_end_from_corpus(args, front, corpus, world):
@@ -476,11 +495,16 @@ def front_end_from_corpus(args, front, corpus, world):
     return spec, lc_stats
 
 
-def corpus_settings(args):
-    """What a checkpoint's 'device_corpus' entry says about the corpus."""
-    return dict(crop=args.crop or 'pieces', seed=CORPUS_SEED,
-                sample_size=args.sample_size or None,
-                lc_feature_context=args.lc_feature_context or 'piece')
+def corpus_settings(args, history=0):
+    """What a checkpoint's 'device_corpus' entry says about the corpus
+    ('history': only where there is some; the sequence of pieces does not
+    depend on it)."""
+    entry = dict(crop=args.crop or 'pieces', seed=CORPUS_SEED,
+                 sample_size=args.sample_size or None,
+                 lc_feature_context=args.lc_feature_context or 'piece')
+    if history:
+        entry['history'] = int(history)
+    return entry
 
 
 def build_source(args, wavenet_params, front, file_lc, lc_scales, lc_hop,
@@ -506,7 +530,8 @@ def build_source(args, wavenet_params, front, file_lc, lc_scales, lc_hop,
         if args.lc_feature_context == 'utterance':
             lc_mode = 'frames' if lc_scales is not None else 'rows'
         return training.CorpusSource(
-            corpus, corpus_settings(args), args.mask_padding, gc_enabled,
+            corpus, corpus_settings(args, corpus.index.history),
+            args.mask_padding, gc_enabled,
             lc_mode, emphasis=emph), spec, lc_stats
     coord = Coordinator()
     if args.synthetic:
@@ -655,7 +680,9 @@ def main(argv=None):
             silence_threshold=args.silence_threshold, gc_enabled=gc_enabled,
             gc_cardinality=source.gc_category_cardinality,
             lc_channels=file_lc, lc_hop=lc_hop,
-            lc_frames=lc_scales is not None, rank=rank, world=world)
+            lc_frames=lc_scales is not None, rank=rank, world=world,
+            history=piece_history(args.piece_history, wavenet_params)
+            if args.sample_size else 0)
     validate_every = args.validate_every or args.checkpoint_every
 
     if lc_from_batch:
@@ -684,15 +711,20 @@ def main(argv=None):
                 raise RuntimeError('rank %d: a rank failed to produce a batch '
                                    'at step %d%s' % (rank, step, '' if err is
                                                      None else ': %r' % err))
-            den = real = None
+            den = real = hist = None
             if lengths is not None:
                 # (cut to the common T like the rows; every rank's longest
                 # real clip is then n_t samples, so the guard below looks at
                 # the longest real length and decides the same on every rank)
                 lengths = np.minimum(lengths, n_t)
-                den = parallel.masked_denominator(lengths, net.device)
+                # (--piece_history: a clip cut to its history or less has
+                # no target; the real samples are the predicted ones)
+                hist = source.history(step, B, n_t)
+                den = parallel.masked_denominator(lengths, net.device,
+                                                  history=hist)
                 real = int(round(den * world))
-            if (n_t if lengths is None else int(lengths.max())) < 2:
+            if (n_t if lengths is None else int(lengths.max())) < 2 or \
+                    den == 0:
                 continue
             audio, lc, lc_off = source.take(step, B, n_t, lengths)
             trace_step = args.store_metadata and step % 50 == 0
@@ -707,7 +739,8 @@ def main(argv=None):
                             l2_regularization_strength=l2,
                             local_condition_batch=lc,
                             local_condition_offset=lc_off,
-                            lengths=lengths, loss_denominator=den)
+                            lengths=lengths, loss_denominator=den,
+                            **({} if hist is None else dict(history=hist)))
             optimizer.minimize(loss)
             # (prints the step before: StepLog)
             log.step(step, loss, optimizer.last_grad_norm, start_time, real)
