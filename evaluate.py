@@ -20,7 +20,10 @@ then those of samples predicted from their true history.
 --synthesis true (a model with local conditioning and a checkpoint that names
 a log-mel front end) then copy-synthesises the set's whole utterances --
 conditioning from each utterance's own audio, utterance u of the set drawn
-with --seed + u, --synthesis_batch streams in lock step (wavenet/synthesis.py)
+with --seed + u, --synthesis_batch streams in lock step (wavenet/synthesis.py;
+--synthesis_schedule queue refills a finished stream's slot with the next
+utterance instead of running length-sorted rounds: the same audio, "steps"
+and "occupancy" then report the queue)
 -- runs what was generated through the de-emphasis filter where the model
 was trained with train.py --preemphasis (the checkpoint's 'emphasis' entry, or
 --preemphasis A; the scoring pre-emphasises every batch behind the front end,
@@ -54,8 +57,8 @@ BATCH_SIZE = 8
 SILENCE_THRESHOLD = 0.3        # train.py's
 WAVENET_PARAMS = './wavenet_params.json'   # generate.py's
 SYNTHESIS_BATCH = 32
-SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_out', 'max_clips', 'seed',
-                   'temperature', 'top_k', 'top_p')
+SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_schedule', 'synthesis_out',
+                   'max_clips', 'seed', 'temperature', 'top_k', 'top_p')
 
 
 def get_arguments(argv=None):
@@ -104,6 +107,12 @@ def get_arguments(argv=None):
     p.add_argument('--synthesis_batch', type=int, default=None,
                    help='--synthesis: streams generated in lock step '
                    '(default %d)' % SYNTHESIS_BATCH)
+    p.add_argument('--synthesis_schedule', type=str, default=None,
+                   choices=('rounds', 'queue'),
+                   help='--synthesis: length-sorted rounds (the default), or '
+                   'the restart queue, in which a finished stream\'s slot '
+                   'takes the next utterance at once; the same audio, fewer '
+                   'lock-step steps')
     p.add_argument('--synthesis_out', type=str, default=None,
                    help='--synthesis: write <stem>.wav of every utterance '
                    'into this directory')
@@ -261,7 +270,8 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None):
         batch=args.synthesis_batch or SYNTHESIS_BATCH,
         global_condition=[p[2] for p in pieces] if data.gc_enabled else None,
         temperature=1.0 if args.temperature is None else args.temperature,
-        top_k=args.top_k, top_p=args.top_p)
+        top_k=args.top_k, top_p=args.top_p,
+        schedule=args.synthesis_schedule or 'rounds')
     if emph is not None:
         waves = synthesis.deemphasize(emph, waves, syn.rounds)
     mae, lsd = synthesis.log_mel_distance(spec, waves, audios, syn.rounds)

@@ -33,6 +33,9 @@ or the --lc_features flags; one sample is generated per sample of the wav, or
 (sorted; file i draws with --seed + i): --clips streams (default 32 here) run
 in lock step, the utterances sorted by length (wavenet/synthesis.py), and
 OUT/<stem>.wav holds one generated sample per sample of DIR/<stem>.wav.
+--synthesis_schedule queue refills a finished stream's slot with the next
+utterance at once instead of running length-sorted rounds: the same files in
+fewer lock-step steps.
 Pre-emphasis: a model trained with train.py --preemphasis generates the
 emphasised signal; what is decoded goes through the inverse filter on the
 device before it is written (the checkpoint's 'emphasis' entry, or
@@ -156,6 +159,11 @@ def get_arguments(argv=None):
                    help='--lc_wav for every wav of this directory, --clips '
                    'at a time; needs --wav_out_dir (not with --lc_wav or '
                    '--lc_path)')
+    p.add_argument('--synthesis_schedule', type=str, default=None,
+                   choices=('rounds', 'queue'),
+                   help='with --lc_wav_dir: length-sorted rounds (the '
+                   'default), or the restart queue, in which a finished '
+                   'stream\'s slot takes the next utterance at once')
     p.add_argument('--wav_out_dir', type=str, default=None,
                    help='with --lc_wav_dir: the directory of the generated '
                    '<stem>.wav files')
@@ -190,6 +198,8 @@ def get_arguments(argv=None):
             p.error('--clips must be in [1, 256] with --lc_wav_dir')
     elif a.wav_out_dir is not None:
         p.error('--wav_out_dir needs --lc_wav_dir')
+    elif a.synthesis_schedule is not None:
+        p.error('--synthesis_schedule needs --lc_wav_dir')
     if a.clips is None:
         a.clips = 1
     if a.lc_wav is None and a.lc_wav_dir is None:
@@ -463,8 +473,9 @@ def main(argv=None):
 
 def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
               emph=None):
-    """--lc_wav_dir: copy synthesis of every wav of a directory in
-    length-sorted rounds of --clips streams (wavenet/synthesis.py)."""
+    """--lc_wav_dir: copy synthesis of every wav of a directory on --clips
+    streams, in length-sorted rounds or through the restart queue
+    (--synthesis_schedule; wavenet/synthesis.py)."""
     from wavenet import synthesis
     from wavenet.audio_reader import find_files, load_wav
     rate = wavenet_params['sample_rate']
@@ -494,7 +505,8 @@ def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
             net, spec, audios,
             seeds=[args.seed + i for i in range(len(files))],
             batch=args.clips, global_condition=args.gc_id,
-            temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+            temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+            schedule=args.synthesis_schedule or 'rounds')
     except ValueError as e:
         print(str(e))
         return 1

@@ -755,6 +755,46 @@ int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
 int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
                             const int32_t* ctl, const uint64_t* seeds,
                             float* proba_out, const float* logits, void* stream);
+/* Restarting single streams (bulk synthesis refills the slot of a finished
+ * utterance).  The counter rule above draws with counter = step; the origin
+ * rule: with origins int32[Bp] the counter of stream b is step - origins[b],
+ * so a stream restarted at step T0 draws as a fresh stream does from step 0.
+ * The _q entries are wn_fastgen_batch_step / _step_lc / _finish with the
+ * origin rule (origins in front of the stream; NULL: WN_ERR_NULL); nothing
+ * else in a step knows about origins, the ring position stays cursors[0] % d.
+ * wn_fastgen_batch_restart, one launch: for every stream b < B with
+ * flags[b] != 0 (flags int32[Bp] on the device) the 32 floats of b in every
+ * ring row become zeros, prev[b] = -1 and origins[b] = cursors[0] (read on
+ * the device); no word of another stream is written.  Valid only with no
+ * draw pending (cursors[1] == 0: after wn_fastgen_batch_finish[_q]) and
+ * before the wn_fastgen_batch_pre[_lc] of the next sequence of steps. */
+int wn_fastgen_batch_step_q(const float* params_causal, const float* layer0,
+                            long layer_stride, const float* skip_w,
+                            const float* skip_bsum, const float* post1_w,
+                            const float* post1_b, const float* post2_w,
+                            const float* post2_b, const float* gc_bias_fg,
+                            int bias_stream_stride, const int32_t* dilations_dev,
+                            int L, int S, int Q, int B, float* state,
+                            int32_t* cursors, int32_t* prev, int32_t* samples_io,
+                            const int32_t* ctl, const uint64_t* seeds,
+                            float* proba_out, int use_biases, float* pre,
+                            float* z_all, float* h1, float* h2, float* logits,
+                            const int32_t* origins, void* stream);
+int wn_fastgen_batch_finish_q(int Q, int B, int32_t* cursors, int32_t* samples_io,
+                              const int32_t* ctl, const uint64_t* seeds,
+                              float* proba_out, const float* logits,
+                              const int32_t* origins, void* stream);
+int wn_fastgen_batch_restart(float* state, const int32_t* dilations_dev, int L,
+                             int B, const int32_t* cursors, int32_t* prev,
+                             int32_t* origins, const int32_t* flags,
+                             void* stream);
+/* The LC rows of n lock-step steps from position pos0 for B streams holding
+ * different items: out float[B][n][Lc].  table int64[B][3] on the device:
+ * {address of the item's rows float[m_b][Lc] (0: no item), the stream's
+ * origin, m_b}.  With t = pos0 + j - origin_b: out[b][j] = rows_b[t - 1] for
+ * 1 <= t <= m_b, exact zeros elsewhere; nothing at or behind row m_b is read. */
+int wn_fastgen_batch_lc_rows(const int64_t* table, int B, int n, int Lc,
+                             long pos0, float* out, void* stream);
 
 /* ---- local conditioning in fast generation (csrc/wn_fastgen_lc.hip).
  * The conditioned-bias ring: for positions p = p0 .. p0 + n_rows - 1 and every
@@ -886,6 +926,20 @@ int wn_fastgen_batch_step_lc(const float* params_causal, const float* layer0,
                              float* z_all, float* h1, float* h2, float* logits,
                              const float* lc_ring, int lc_R, int lc_stride,
                              void* stream);
+int wn_fastgen_batch_step_lc_q(const float* params_causal, const float* layer0,
+                               long layer_stride, const float* skip_w,
+                               const float* skip_bsum, const float* post1_w,
+                               const float* post1_b, const float* post2_w,
+                               const float* post2_b, const float* gc_bias_fg,
+                               int bias_stream_stride,
+                               const int32_t* dilations_dev, int L, int S, int Q,
+                               int B, float* state, int32_t* cursors,
+                               int32_t* prev, int32_t* samples_io,
+                               const int32_t* ctl, const uint64_t* seeds,
+                               float* proba_out, int use_biases, float* pre,
+                               float* z_all, float* h1, float* h2, float* logits,
+                               const float* lc_ring, int lc_R, int lc_stride,
+                               const int32_t* origins, void* stream);
 
 /* ---- learned upsampling of frame-rate local-conditioning features
  * (csrc/wn_lc.hip).  scales: host array of m (1..8) ints >= 2, hop = their

@@ -26,6 +26,14 @@
 //
 // State: ring row [sum(d)][Bp][32] (all streams share one cursor), so a
 // layer's past tap is one contiguous read for a whole group.
+//
+// Restarts (bulk synthesis refills a finished stream's slot): the counter
+// rule of the draw is counter = step; the origin rule of the _q entries is
+// counter = step - origin[b].  fgb_restart_kernel zeroes a stream's ring
+// columns, clears its previous code and sets its origin to the current step,
+// after which the stream is bit for bit a fresh one; the ring position stays
+// the shared cursors[0] % d.  fgb_lc_rows_kernel gathers the LC rows of a
+// segment for streams that hold different items.
 #include "wn_common.h"
 
 #define FGB_MAXB 256
@@ -75,6 +83,7 @@ struct FgBatch {
   float* h1;               // [Bp][S]
   float* h2;               // [Bp][S]
   float* logits;           // [Bp][Q]
+  const int32_t* origin;   // [Bp] step at which stream b (re)started, or null (all 0)
 };
 
 // 16 x 16 x 4 f32 MFMA.  Lane l: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15];
@@ -86,7 +95,10 @@ __device__ __forceinline__ f32x4 fgb_mfma(float a, float b, f32x4 c) {
 // ---------------------------------------------------------------- the draw
 // The draw of wn_common.h for stream b: its own rows and seed, counter = the
 // step that produced the logits (the counter rule of tests/draw_ref.py).  One
-// wave; pd: FGB_MAXQ doubles of LDS owned by it.
+// wave; pd: FGB_MAXQ doubles of LDS owned by it.  ORIGIN (the _q entries): the
+// counter is the stream's own step, step - origin[b], so that a stream
+// restarted at step T0 (wn_fastgen_batch_restart) draws as a fresh one does.
+template <bool ORIGIN>
 __device__ void fgb_draw_wave(const FgBatch& g, double* pd, int lane, int b, int step) {
   const int Q = g.Q;
   const float* lg = g.logits + (long)b * Q;
@@ -101,7 +113,8 @@ __device__ void fgb_draw_wave(const FgBatch& g, double* pd, int lane, int b, int
   if (local + 1 < g.ctl[FGB_CTL_NGIVEN]) return;   // still inside the given samples
   const int code = wave_draw_f64(pd, Q, lane, __int_as_float(g.ctl[FGB_CTL_TEMP]),
                                  g.ctl[FGB_CTL_TOPK], __int_as_float(g.ctl[FGB_CTL_TOPP]),
-                                 g.seeds[b], (uint64_t)step);
+                                 g.seeds[b],
+                                 ORIGIN ? (uint64_t)(step - g.origin[b]) : (uint64_t)step);
   if (lane == 0) g.samples[(long)b * g.ctl[FGB_CTL_LDS] + local + 1] = code;
 }
 
@@ -112,7 +125,59 @@ __global__ __launch_bounds__(256) void fgb_draw_kernel(FgBatch g) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + w;
   if (!g.cursors[1] || b >= g.B) return;
-  fgb_draw_wave(g, pd[w], lane, b, g.cursors[0] - 1);
+  fgb_draw_wave<false>(g, pd[w], lane, b, g.cursors[0] - 1);
+}
+
+__global__ __launch_bounds__(256) void fgb_draw_q_kernel(FgBatch g) {
+  __shared__ double pd[4][FGB_MAXQ];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + w;
+  if (!g.cursors[1] || b >= g.B) return;
+  fgb_draw_wave<true>(g, pd[w], lane, b, g.cursors[0] - 1);
+}
+
+// ------------------------------------------------------------- the restart
+// A flagged stream becomes a fresh one: its 32 floats of every ring row are
+// zeroed (a FIFO of zeros is the same wherever its head sits, so the shared
+// ring position needs no reset), prev = -1, origin = the step the queues are
+// at.  Workgroup (x, y): the streams 32 y .. 32 y + 31, ring rows x, x +
+// gridDim.x, ...; a thread: one float4 of one stream.
+__global__ __launch_bounds__(256) void fgb_restart_kernel(
+    float* state, const int32_t* dil, int L, int B, int Bp, const int32_t* cursors,
+    int32_t* prev, int32_t* origin, const int32_t* flags) {
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y * FGB_TILE + (tid >> 3);
+  const bool on = b < B && flags[b] != 0;
+  int rows = 0;
+  for (int l = 0; l < L; ++l) rows += dil[l];
+  if (on) {
+    const float4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int r = blockIdx.x; r < rows; r += gridDim.x)
+      *reinterpret_cast<float4*>(state + ((long)r * Bp + b) * 32 + (tid & 7) * 4) = zero;
+    if (blockIdx.x == 0 && (tid & 7) == 0) {
+      prev[b] = -1;
+      origin[b] = cursors[0];
+    }
+  }
+}
+
+// ------------------------------------------------- a segment's LC rows
+// out[b][j] = row t - 1 of stream b's item for its own step t = pos0 + j -
+// origin_b in [1, m_b], zeros elsewhere.  table [B][3] (int64): the address
+// of the item's rows [m_b][Lc] (0: none), origin_b, m_b.
+__global__ __launch_bounds__(256) void fgb_lc_rows_kernel(const long long* table, int B, int n,
+                                                          int Lc, long pos0, float* out) {
+  const long total = (long)B * n * Lc;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int c = (int)(i % Lc);
+    const long bj = i / Lc;
+    const int j = (int)(bj % n), b = (int)(bj / n);
+    const float* src = reinterpret_cast<const float*>(table[3 * b]);
+    const long t = pos0 + j - table[3 * b + 1];
+    float v = 0.f;
+    if (src && t >= 1 && t <= table[3 * b + 2]) v = src[(t - 1) * Lc + c];
+    out[i] = v;
+  }
 }
 
 // ---------------------------------------------------------------- the chain
@@ -511,7 +576,8 @@ int wn_fastgen_batch_pre_lc(const float* layer0, long layer_stride, const float*
 // Enqueue the stages [first, last) of one step: 0 draw, 1 chain, 2 skip sum +
 // next pre-activations, 3 post1, 4 logits (wn_fastgen_batch_step: all five;
 // single stages let a caller time each launch between its own events).
-static int fgb_stages(const FgbLc* lc, int first, int last, const float* params_causal,
+static int fgb_stages(const FgbLc* lc, const int32_t* origins, int first, int last,
+                      const float* params_causal,
                             const float* layer0, long layer_stride, const float* skip_w,
                             const float* skip_bsum, const float* post1_w,
                             const float* post1_b, const float* post2_w, const float* post2_b,
@@ -542,12 +608,16 @@ static int fgb_stages(const FgbLc* lc, int first, int last, const float* params_
   g.state = state; g.cursors = cursors; g.prev = prev; g.samples = samples_io;
   g.ctl = ctl; g.seeds = seeds; g.proba_out = proba_out; g.use_dense_bias = use_biases;
   g.pre = pre; g.z_all = z_all; g.h1 = h1; g.h2 = h2; g.logits = logits;
+  g.origin = origins;
   hipStream_t s = (hipStream_t)stream;
   const int mt = g.Bp / 16, ng = g.Bp / FGB_TILE;
   for (int stage = first; stage < last; ++stage) {
     switch (stage) {
       case 0:
-        hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
+        if (origins)
+          hipLaunchKernelGGL(fgb_draw_q_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
+        else
+          hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
         break;
       case 1:
         hipLaunchKernelGGL(fgb_chain_kernel, dim3(ng), dim3(256), 0, s, g);
@@ -581,7 +651,7 @@ int wn_fastgen_batch_stages(int first, int last, const float* params_causal,
                             int32_t* samples_io, const int32_t* ctl, const uint64_t* seeds,
                             float* proba_out, int use_biases, float* pre, float* z_all,
                             float* h1, float* h2, float* logits, void* stream) {
-  return fgb_stages(nullptr, first, last, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+  return fgb_stages(nullptr, nullptr, first, last, params_causal, layer0, layer_stride, skip_w, skip_bsum,
                     post1_w, post1_b, post2_w, post2_b, gc_bias_fg, bias_stream_stride,
                     dilations_dev, L, S, Q, B, state, cursors, prev, samples_io, ctl, seeds,
                     proba_out, use_biases, pre, z_all, h1, h2, logits, stream);
@@ -598,7 +668,7 @@ int wn_fastgen_batch_step_lc(const float* params_causal, const float* layer0, lo
                              float* logits, const float* lc_ring, int lc_R, int lc_stride,
                              void* stream) {
   const FgbLc lc = {lc_ring, lc_R, lc_stride};
-  return fgb_stages(&lc, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum, post1_w,
+  return fgb_stages(&lc, nullptr, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum, post1_w,
                     post1_b, post2_w, post2_b, gc_bias_fg, bias_stream_stride, dilations_dev, L,
                     S, Q, B, state, cursors, prev, samples_io, ctl, seeds, proba_out, use_biases,
                     pre, z_all, h1, h2, logits, stream);
@@ -613,16 +683,16 @@ int wn_fastgen_batch_step(const float* params_causal, const float* layer0, long 
                           const int32_t* ctl, const uint64_t* seeds, float* proba_out,
                           int use_biases, float* pre, float* z_all, float* h1, float* h2,
                           float* logits, void* stream) {
-  return fgb_stages(nullptr, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+  return fgb_stages(nullptr, nullptr, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum,
                                  post1_w, post1_b, post2_w, post2_b, gc_bias_fg,
                                  bias_stream_stride, dilations_dev, L, S, Q, B, state, cursors,
                                  prev, samples_io, ctl, seeds, proba_out, use_biases, pre, z_all,
                                  h1, h2, logits, stream);
 }
 
-int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
-                            const int32_t* ctl, const uint64_t* seeds, float* proba_out,
-                            const float* logits, void* stream) {
+static int fgb_finish(const int32_t* origins, int Q, int B, int32_t* cursors,
+                      int32_t* samples_io, const int32_t* ctl, const uint64_t* seeds,
+                      float* proba_out, const float* logits, void* stream) {
   if (!cursors || !samples_io || !ctl || !seeds || !logits) return WN_ERR_NULL;
   if (Q <= 0) return WN_ERR_BAD_SHAPE;
   if (Q > FGB_MAXQ) return WN_ERR_UNSUPPORTED;
@@ -631,12 +701,95 @@ int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
   FgBatch g = {};
   g.Q = Q; g.B = B; g.Bp = fgb_rows(B); g.cursors = cursors; g.samples = samples_io;
   g.ctl = ctl; g.seeds = seeds; g.proba_out = proba_out; g.logits = const_cast<float*>(logits);
+  g.origin = origins;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
+  if (origins)
+    hipLaunchKernelGGL(fgb_draw_q_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
+  else
+    hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
   if (wn_check_launch() != WN_OK) return WN_ERR_LAUNCH;
   if (hipMemsetD32Async((hipDeviceptr_t)(cursors + 1), 0, 1, s) != hipSuccess)
     return WN_ERR_LAUNCH;
   return WN_OK;
+}
+
+int wn_fastgen_batch_finish(int Q, int B, int32_t* cursors, int32_t* samples_io,
+                            const int32_t* ctl, const uint64_t* seeds, float* proba_out,
+                            const float* logits, void* stream) {
+  return fgb_finish(nullptr, Q, B, cursors, samples_io, ctl, seeds, proba_out, logits, stream);
+}
+
+// ---- the _q entries: the same launches with the draw counted from each
+// stream's own origin (streams restarted by wn_fastgen_batch_restart)
+int wn_fastgen_batch_step_q(const float* params_causal, const float* layer0, long layer_stride,
+                            const float* skip_w, const float* skip_bsum, const float* post1_w,
+                            const float* post1_b, const float* post2_w, const float* post2_b,
+                            const float* gc_bias_fg, int bias_stream_stride,
+                            const int32_t* dilations_dev, int L, int S, int Q, int B,
+                            float* state, int32_t* cursors, int32_t* prev, int32_t* samples_io,
+                            const int32_t* ctl, const uint64_t* seeds, float* proba_out,
+                            int use_biases, float* pre, float* z_all, float* h1, float* h2,
+                            float* logits, const int32_t* origins, void* stream) {
+  if (!origins) return WN_ERR_NULL;
+  return fgb_stages(nullptr, origins, 0, 5, params_causal, layer0, layer_stride, skip_w,
+                    skip_bsum, post1_w, post1_b, post2_w, post2_b, gc_bias_fg,
+                    bias_stream_stride, dilations_dev, L, S, Q, B, state, cursors, prev,
+                    samples_io, ctl, seeds, proba_out, use_biases, pre, z_all, h1, h2, logits,
+                    stream);
+}
+
+int wn_fastgen_batch_step_lc_q(const float* params_causal, const float* layer0,
+                               long layer_stride, const float* skip_w, const float* skip_bsum,
+                               const float* post1_w, const float* post1_b, const float* post2_w,
+                               const float* post2_b, const float* gc_bias_fg,
+                               int bias_stream_stride, const int32_t* dilations_dev, int L,
+                               int S, int Q, int B, float* state, int32_t* cursors,
+                               int32_t* prev, int32_t* samples_io, const int32_t* ctl,
+                               const uint64_t* seeds, float* proba_out, int use_biases,
+                               float* pre, float* z_all, float* h1, float* h2, float* logits,
+                               const float* lc_ring, int lc_R, int lc_stride,
+                               const int32_t* origins, void* stream) {
+  if (!origins) return WN_ERR_NULL;
+  const FgbLc lc = {lc_ring, lc_R, lc_stride};
+  return fgb_stages(&lc, origins, 0, 5, params_causal, layer0, layer_stride, skip_w, skip_bsum,
+                    post1_w, post1_b, post2_w, post2_b, gc_bias_fg, bias_stream_stride,
+                    dilations_dev, L, S, Q, B, state, cursors, prev, samples_io, ctl, seeds,
+                    proba_out, use_biases, pre, z_all, h1, h2, logits, stream);
+}
+
+int wn_fastgen_batch_finish_q(int Q, int B, int32_t* cursors, int32_t* samples_io,
+                              const int32_t* ctl, const uint64_t* seeds, float* proba_out,
+                              const float* logits, const int32_t* origins, void* stream) {
+  if (!origins) return WN_ERR_NULL;
+  return fgb_finish(origins, Q, B, cursors, samples_io, ctl, seeds, proba_out, logits, stream);
+}
+
+int wn_fastgen_batch_restart(float* state, const int32_t* dilations_dev, int L, int B,
+                             const int32_t* cursors, int32_t* prev, int32_t* origins,
+                             const int32_t* flags, void* stream) {
+  if (!state || !dilations_dev || !cursors || !prev || !origins || !flags) return WN_ERR_NULL;
+  if (L <= 0) return WN_ERR_BAD_SHAPE;
+  if (L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  const int Bp = fgb_rows(B);
+  hipLaunchKernelGGL(fgb_restart_kernel, dim3(128, Bp / FGB_TILE), dim3(256), 0,
+                     (hipStream_t)stream, state, dilations_dev, L, B, Bp, cursors, prev, origins,
+                     flags);
+  return wn_check_launch();
+}
+
+int wn_fastgen_batch_lc_rows(const int64_t* table, int B, int n, int Lc, long pos0, float* out,
+                             void* stream) {
+  if (!table || !out) return WN_ERR_NULL;
+  if (n <= 0 || Lc <= 0 || pos0 < 0) return WN_ERR_BAD_SHAPE;
+  const int rc = fgb_check_batch(B);
+  if (rc != WN_OK) return rc;
+  const long total = (long)B * n * Lc;
+  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  hipLaunchKernelGGL(fgb_lc_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const long long*>(table), B, n, Lc, pos0, out);
+  return wn_check_launch();
 }
 
 }  // extern "C"

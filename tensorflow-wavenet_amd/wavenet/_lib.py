@@ -262,6 +262,18 @@ for _name in ('wn_fastgen_run', 'wn_fastgen_run_wide', 'wn_fastgen_run_lc'):
     # ..., int top_k, float top_p, void* stream (the truncated draw; 0: off)
     _res, _args = SIGNATURES[_name]
     SIGNATURES[_name + '_trunc'] = (_res, _args[:-1] + [c_int, c_float, P])
+for _name in ('wn_fastgen_batch_step', 'wn_fastgen_batch_step_lc',
+              'wn_fastgen_batch_finish'):
+    # ..., const int32_t* origins, void* stream (restarted streams: the draw
+    # counted from each stream's own origin)
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + '_q'] = (_res, _args[:-1] + [P, P])
+# state, dilations, L, B, cursors, prev, origins, flags, stream
+SIGNATURES['wn_fastgen_batch_restart'] = (c_int, [P, P, c_int, c_int, P, P, P,
+                                                  P, P])
+# table, B, n, Lc, pos0, out, stream
+SIGNATURES['wn_fastgen_batch_lc_rows'] = (c_int, [P, c_int, c_int, c_int,
+                                                  c_long, P, P])
 
 
 

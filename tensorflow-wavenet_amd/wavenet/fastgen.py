@@ -111,7 +111,9 @@ class _LcRing(object):
         self.rstride = 64 if (self.lc_stride or bstride) else 0
         nr = B if self.rstride else 1
         row = net.L * nr * 64
-        self.C = lc_chunk(n_steps, row * 4, net.fastgen_lc_chunk,
+        # (g['reserve']: the longest call of a run whose calls share graphs)
+        self.C = lc_chunk(max(n_steps, g.get('reserve', 0)), row * 4,
+                          net.fastgen_lc_chunk,
                           int(net.fastgen_graph_steps), pe,
                           LC_RING_BYTES if B > 1 else LC_RING_BYTES_ONE)
         self.R = self.C + 1
@@ -191,7 +193,8 @@ def _stage(net, g, io, n_given, n_steps, temperature, proba, proba_every,
     B, ld = io.shape[0], int(n_steps) + 1
     pe = max(1, int(proba_every))
     rows = (int(n_steps) + pe - 1) // pe if proba is not None else 0
-    iob = _buf(net, g, 'io_buf', B * ld, torch.int32)
+    iob = _buf(net, g, 'io_buf', B * max(ld, g.get('reserve', 0) + 1),
+               torch.int32)
     iob[:B * ld].view(B, ld).copy_(io[:, :ld])
     pb = None
     if proba is not None:
@@ -692,6 +695,12 @@ def _batch_codes(net, seed_samples, B):
 
 
 def _batch_last(last, B):
+    if isinstance(last, torch.Tensor) and last.is_cuda:
+        # (stays on the device: nothing waits for the codes of the call before)
+        if last.numel() != B:
+            raise ValueError('last_samples has %d codes for %d streams'
+                             % (last.numel(), B))
+        return last.reshape(-1).to(torch.int32)
     if isinstance(last, torch.Tensor):
         last = last.cpu().numpy()
     last = np.asarray(last, dtype=np.int32).reshape(-1)
@@ -699,6 +708,27 @@ def _batch_last(last, B):
         raise ValueError('last_samples has %d codes for %d streams'
                          % (last.size, B))
     return last
+
+
+def _batch_restart_arg(restart, B):
+    """restart -> None or a sorted list of stream indices: ints in [0, B),
+    no duplicates (ValueError before the library or a device is touched)."""
+    if restart is None:
+        return None
+    if isinstance(restart, torch.Tensor):
+        restart = restart.cpu().numpy()
+    a = np.asarray(restart)
+    if a.ndim == 1 and a.size == 0:
+        return None
+    if a.ndim != 1 or a.dtype == np.bool_ or \
+            not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('restart must be None or a list of stream indices '
+                         '(ints), got %r' % (restart,))
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= B or np.unique(a).size != a.size:
+        raise ValueError('restart must name distinct streams in [0, %d), '
+                         'got %r' % (B, a.tolist()))
+    return sorted(int(v) for v in a)
 
 
 def batch_generator(net, B):
@@ -717,7 +747,12 @@ def batch_generator(net, B):
     net._bgen = _new_state(
         net, dil, nfl, Bp, B, B=B, Bp=Bp,
         seeds=torch.zeros(B, dtype=torch.int64, device=net.device),
-        prev=torch.full((Bp,), -1, dtype=torch.int32, device=net.device))
+        prev=torch.full((Bp,), -1, dtype=torch.int32, device=net.device),
+        # the step at which each stream (re)started; `restarted`: some
+        # origin may differ from 0, the _q entry points run
+        origin=torch.zeros(Bp, dtype=torch.int32, device=net.device),
+        flags=torch.zeros(Bp, dtype=torch.int32, device=net.device),
+        restarted=False, reserve=0)
     return net._bgen
 
 
@@ -726,6 +761,50 @@ def batch_reset(net, g):
               g['state'].numel(), _lib.ptr(g['cursors']),
               _lib.ptr(g['prev']), g['B'], _lib.stream())
     g['steps'] = 0
+    if g['restarted']:
+        g['origin'].zero_()
+        g['restarted'] = False
+
+
+def batch_restart(net, g, streams):
+    """Make the streams `streams` fresh ones at the step the queues are at
+    (wn_fastgen_batch_restart: zero queues, no previous code, the draw
+    counted from here).  Between two calls only: no draw is pending."""
+    flags = np.zeros(g['Bp'], np.int32)
+    flags[streams] = 1
+    g['flags'].copy_(torch.from_numpy(flags))
+    _lib.call('wn_fastgen_batch_restart', _lib.ptr(g['state']),
+              _lib.ptr(g['dil']), net.L, g['B'], _lib.ptr(g['cursors']),
+              _lib.ptr(g['prev']), _lib.ptr(g['origin']),
+              _lib.ptr(g['flags']), _lib.stream())
+    g['restarted'] = True
+
+
+def batch_lc_rows(net, items, pos0, n):
+    """float32 [B, n, Lc] on the device, the LC rows of the n lock-step steps
+    from position pos0 for B streams that hold different items
+    (wn_fastgen_batch_lc_rows).  items[b]: None, or (rows, origin): rows a
+    float32 device tensor [m, Lc] (contiguous), origin the step at which
+    the stream's item started.  The stream's own step t = pos0 + j - origin
+    gets rows[t - 1] for 1 <= t <= m, zeros elsewhere."""
+    B, Lc = len(items), int(net.Lc)
+    table = np.zeros((B, 3), np.int64)
+    for b, it in enumerate(items):
+        if it is None or it[0] is None or int(it[0].shape[0]) == 0:
+            continue
+        rows, origin = it
+        if rows.dtype != torch.float32 or not rows.is_contiguous() or \
+                rows.dim() != 2 or int(rows.shape[1]) != Lc or \
+                not rows.is_cuda:
+            raise ValueError('batch_lc_rows: rows of stream %d must be a '
+                             'contiguous float32 [m, %d] on the device'
+                             % (b, Lc))
+        table[b] = rows.data_ptr(), int(origin), int(rows.shape[0])
+    out = torch.empty((B, int(n), Lc), dtype=torch.float32, device=net.device)
+    tb = torch.from_numpy(table).to(net.device)
+    _lib.call('wn_fastgen_batch_lc_rows', _lib.ptr(tb), B, int(n), Lc,
+              int(pos0), _lib.ptr(out), _lib.stream())
+    return out
 
 
 def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
@@ -762,16 +841,19 @@ def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
                 _lib.ptr(g['seeds']), _lib.ptr(pb), 1 if net.use_biases else 0,
                 _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
                 _lib.ptr(g['h2']), _lib.ptr(g['logits']))
-    return dict(args=args, iob=iob, pb=pb, ring=ring)
+    # restarted streams: the _q entries, the origins in front of the stream
+    q = (_lib.ptr(g['origin']),) if g['restarted'] else ()
+    return dict(args=args, iob=iob, pb=pb, ring=ring, q=q)
 
 
 def batch_complete(net, g, prep, io, proba, n_steps):
     """The last step's draw (every other one runs at the next step's
     start), then the codes / probabilities back into io / proba."""
-    _lib.call('wn_fastgen_batch_finish', net.Q, g['B'],
+    q = prep['q']
+    _lib.call('wn_fastgen_batch_finish' + ('_q' if q else ''), net.Q, g['B'],
               _lib.ptr(g['cursors']), _lib.ptr(prep['iob']),
               _lib.ptr(g['ctl']), _lib.ptr(g['seeds']), _lib.ptr(prep['pb']),
-              _lib.ptr(g['logits']), _lib.stream())
+              _lib.ptr(g['logits']), *q, _lib.stream())
     g['steps'] += int(n_steps)
     io.copy_(prep['iob'][:io.numel()].view(io.shape))
     if proba is not None:
@@ -785,24 +867,36 @@ def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
     # chunks, the ring filled before each)
     prep = batch_prepare(net, g, io, n_given, n_steps, temperature, seeds,
                          proba, proba_every, gc, lc, trunc)
-    args, ring = prep['args'], prep['ring']
+    args, ring, q = prep['args'], prep['ring'], prep['q']
+    sfx = '_q' if q else ''
     if ring is None:
-        _replay_steps(net, g, args, lambda: _lib.call(
-            'wn_fastgen_batch_step', *args, _lib.stream()), n_steps)
+        _replay_steps(net, g, args + q, lambda: _lib.call(
+            'wn_fastgen_batch_step' + sfx, *args, *q, _lib.stream()), n_steps)
     else:
         lcargs = ring.args()
         for i, (a, n) in enumerate(ring.plan):
             if i:
                 ring.fill(a, n)
-            _replay_steps(net, g, (args, lcargs), lambda: _lib.call(
-                'wn_fastgen_batch_step_lc', *args, *lcargs, _lib.stream()), n)
+            _replay_steps(net, g, (args, lcargs) + q, lambda: _lib.call(
+                'wn_fastgen_batch_step_lc' + sfx, *args, *lcargs, *q,
+                _lib.stream()), n)
     batch_complete(net, g, prep, io, proba, n_steps)
+
+
+def _reserve_arg(reserve_steps):
+    r = 0 if reserve_steps is None else reserve_steps
+    if isinstance(r, (bool, np.bool_)) or \
+            not isinstance(r, (int, np.integer)) or r < 0:
+        raise ValueError('reserve_steps must be None or an int >= 0, got %r'
+                         % (reserve_steps,))
+    return int(r)
 
 
 def generate_batch(net, num_samples, seeds, seed_samples, temperature,
                    global_condition, return_proba_every, lc=None, top_k=None,
-                   top_p=None):
+                   top_p=None, reserve_steps=None):
     trunc = sampling.resolve(top_k, top_p, net.Q)
+    reserve = _reserve_arg(reserve_steps)
 
     def per_stream(B):
         codes = _batch_codes(net, seed_samples, B)
@@ -820,6 +914,7 @@ def generate_batch(net, num_samples, seeds, seed_samples, temperature,
     out[:, :n_given] = torch.from_numpy(codes).to(net.device)
     g = batch_generator(net, B)
     batch_reset(net, g)
+    g['reserve'] = reserve
 
     def prime():
         # ONE forward pass per distinct (seed, GC id): a stream's queues are
@@ -849,8 +944,10 @@ def generate_batch(net, num_samples, seeds, seed_samples, temperature,
 def continue_generation_batch(net, num_samples, last_samples, seeds,
                               temperature, global_condition,
                               return_proba_every, lc=None, top_k=None,
-                              top_p=None):
+                              top_p=None, restart=None, reserve_steps=None):
     trunc = sampling.resolve(top_k, top_p, net.Q)
+    reserve = _reserve_arg(reserve_steps)
+    restart = _batch_restart_arg(restart, len(seeds))
 
     def per_stream(B):
         last = _batch_last(last_samples, B)
@@ -868,7 +965,11 @@ def continue_generation_batch(net, num_samples, last_samples, seeds,
                            'continue: call generate_batch first' % B)
     lc = _lc_device(net, lc)
     io = torch.zeros((B, n + 1), dtype=torch.int32, device=net.device)
-    io[:, 0] = torch.from_numpy(last).to(net.device)
+    io[:, 0] = last if isinstance(last, torch.Tensor) else \
+        torch.from_numpy(last).to(net.device)
+    g['reserve'] = reserve
+    if restart:
+        batch_restart(net, g, restart)
     pe = int(return_proba_every)
     proba = _seeded(net, io, 1, n, pe, None,
                     functools.partial(_batch_run, net, g, temperature, sd, gc,

@@ -1148,7 +1148,7 @@ class WaveNetModel(object):
     def generate_batch(self, num_samples, seeds, seed_samples=None,
                        temperature=1.0, global_condition=None,
                        return_proba_every=0, *, local_condition=None,
-                       top_k=None, top_p=None):
+                       top_k=None, top_p=None, reserve_steps=None):
         """`generate` for B = len(seeds) independent streams stepped in lock
         step (1 <= B <= 256).  Stream b draws with seeds[b] under generate()'s
         counter rule, so it is the same random process as
@@ -1162,7 +1162,11 @@ class WaveNetModel(object):
         [B, n + num_samples - 1, Lc] (n seed codes per stream), or
         [n + num_samples - 1, Lc] shared by all streams; rows as generate's.
 
-        top_k, top_p: as generate's; one setting for all streams."""
+        top_k, top_p: as generate's; one setting for all streams.
+
+        reserve_steps: the longest call (in steps) of the run this call
+        starts; buffers are sized for it once, so that this call and its
+        continuations (given the same value) share their captured graphs."""
         sampling.check(top_k, top_p)
         # (the rows are checked in _batch_args's order, beside the seed codes)
         if self.Lc and local_condition is None:
@@ -1170,13 +1174,14 @@ class WaveNetModel(object):
         return fastgen.generate_batch(self, num_samples, seeds, seed_samples,
                                       temperature, global_condition,
                                       return_proba_every, local_condition,
-                                      top_k, top_p)
+                                      top_k, top_p, reserve_steps)
 
     def continue_generation_batch(self, num_samples, last_samples, seeds,
                                   temperature=1.0, global_condition=None,
                                   return_proba_every=0, *,
                                   local_condition=None, top_k=None,
-                                  top_p=None):
+                                  top_p=None, restart=None,
+                                  reserve_steps=None):
         """Draw `num_samples` more samples for every stream of the last
         generate_batch call (the queues stay on the device; last_samples[b]
         is stream b's last code so far, not yet pushed).  Returns int32
@@ -1186,11 +1191,35 @@ class WaveNetModel(object):
         [B, num_samples, Lc] or [num_samples, Lc], rows as
         continue_generation's.
 
-        top_k, top_p: as generate's, for this call only."""
+        top_k, top_p: as generate's, for this call only.
+
+        restart: None, or stream indices (ints in [0, B), no duplicates).
+        Those streams start over with this call: stream b's result is, bit
+        for bit, generate_batch(num_samples, [seeds[b]], seed_samples=
+        [[last_samples[b]]], global_condition=gc[b], local_condition=
+        lc[b:b + 1])[0, 1:] run alone (zero queues, no previous code, the
+        draw counted from this call's first step); later calls without
+        restart continue that process.  The other streams are unaffected.
+
+        reserve_steps: as generate_batch's."""
         sampling.check(top_k, top_p)
         if self.Lc and local_condition is None:
             lcond.refuse_fastgen(self, 'continue_generation_batch')
         return fastgen.continue_generation_batch(
             self, num_samples, last_samples, seeds, temperature,
             global_condition, return_proba_every, local_condition, top_k,
-            top_p)
+            top_p, restart, reserve_steps)
+
+    def batch_local_condition(self, items, position, num_steps):
+        """The local_condition rows [B, num_steps, Lc] (device float32) of a
+        continue_generation_batch call whose first step is lock-step step
+        `position`, for streams that hold different items: items[b] is
+        None (zero rows) or (rows, origin), rows a contiguous float32 device
+        tensor [m, Lc] and origin the step at which stream b (re)started.
+        The stream's own step t = position + j - origin gets rows[t - 1] for
+        1 <= t <= m and zeros elsewhere (step 0 sits beside the given first
+        code).  One launch, no host wait."""
+        if not self.Lc:
+            raise ValueError('batch_local_condition: this model was built '
+                             'without local conditioning')
+        return fastgen.batch_lc_rows(self, items, position, num_steps)

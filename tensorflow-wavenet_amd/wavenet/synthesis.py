@@ -18,6 +18,15 @@ given.  It follows from generate_batch's batch invariance (a stream's codes
 do not depend on B or the other streams) and from causality (a stream's code
 k does not depend on the rows behind position k); tests/test_gpu_synthesis.py
 checks it.  No kernel is launched here but through the model's own methods.
+
+schedule='queue' (`plan_queue`) keeps the contract and drops the rounds: the
+items, in the same order, each take the slot that is free first, so a slot
+whose item has ended does not idle to the end of a round.  The generator
+runs one segment of lock-step steps between consecutive admission times;
+at each of them the admitted slots are restarted inside the running batch
+(continue_generation_batch's `restart`: zero queues, no previous code, the
+draw counted from the stream's own first step), which makes the new item's
+stream bit for bit a fresh one.  tests/test_gpu_synthesis_queue.py.
 """
 import collections
 
@@ -28,6 +37,9 @@ from . import _lib, sampling
 BATCH_MAX = 256
 Plan = collections.namedtuple('Plan', 'rounds steps occupancy')
 Synthesis = collections.namedtuple('Synthesis', 'codes rounds steps occupancy')
+QueuePlan = collections.namedtuple('QueuePlan',
+                                   'slot start segments steps occupancy')
+SCHEDULES = ('rounds', 'queue')
 
 
 def _ints(v, what, lo=None):
@@ -70,6 +82,41 @@ def plan_rounds(lengths, batch):
     rounds = [order[i:i + B] for i in range(0, len(order), B)]
     steps = sum(int(n[r[0]]) for r in rounds)
     return Plan(rounds, steps, float(n.sum()) / (B * steps))
+
+
+def _quantum(quantum):
+    if isinstance(quantum, (bool, np.bool_)) or \
+            not isinstance(quantum, (int, np.integer)) or int(quantum) < 1:
+        raise ValueError('quantum must be an int >= 1, got %r' % (quantum,))
+    return int(quantum)
+
+
+def plan_queue(lengths, batch, quantum=1):
+    """The restart queue of `lengths` at `batch` slots: QueuePlan(slot,
+    start, segments, steps, occupancy).  The items are taken in the order
+    (-n_u, u); every slot is free at step 0; an item takes the slot that is
+    free first (ties: the lowest slot) and starts at start[u] = its free
+    time rounded up to a multiple of `quantum`, which frees the slot at
+    start[u] + n_u.  slot, start: one int per item; steps = max(start + n);
+    segments: the (a, n) pieces between consecutive distinct start times,
+    the last one running to `steps`; occupancy = sum n_u / (batch * steps),
+    counted as plan_rounds counts it.  Host only."""
+    n = _ints(lengths, 'lengths', 1)
+    if n.size < 1:
+        raise ValueError('lengths must name at least one item')
+    B = _batch(batch)
+    q = _quantum(quantum)
+    free = [0] * B
+    slot, start = [0] * n.size, [0] * n.size
+    for u in sorted(range(n.size), key=lambda u: (-int(n[u]), u)):
+        s = min(range(B), key=lambda j: (free[j], j))
+        slot[u], start[u] = s, -(-free[s] // q) * q
+        free[s] = start[u] + int(n[u])
+    steps = max(free)
+    cuts = sorted(set(start)) + [steps]
+    segments = [(a, b - a) for a, b in zip(cuts[:-1], cuts[1:])]
+    return QueuePlan(slot, start, segments, steps,
+                     float(n.sum()) / (B * steps))
 
 
 def _shape_of(t, what):
@@ -176,7 +223,7 @@ def _round_rows(net, kind, cond, items, n, B, steps):
 def synthesize(net, lengths, *, seeds, batch=32, first_samples=None,
                global_condition=None, local_condition=None, frames=None,
                temperature=1.0, top_k=None, top_p=None,
-               max_round_bytes=16 << 30):
+               max_round_bytes=16 << 30, schedule='rounds', quantum=None):
     """Generate item u's n_u = lengths[u] samples behind its first (given)
     code first_samples[u] (default Q // 2), drawing with seeds[u], for every
     item, in the rounds of plan_rounds(lengths, batch).  Returns
@@ -190,6 +237,19 @@ def synthesize(net, lengths, *, seeds, batch=32, first_samples=None,
     ceil(n_u / hop), upsampled by the model.  Exactly one of the two where
     the model has LC, neither where it has none.  A round whose rows
     [B, steps, Lc] exceed max_round_bytes is refused.
+
+    schedule: 'rounds' (above), or 'queue': the restart queue of plan_queue,
+    in which a slot whose item has ended takes the next item at once instead
+    of idling to the end of a round.  The batched generator runs one
+    segment of lock-step steps between consecutive admission times; at each
+    of them the admitted slots are restarted (continue_generation_batch's
+    `restart`).  quantum: admission times are multiples of it; None: max(1,
+    net.fastgen_graph_steps // 10), so that every segment but the last is a
+    whole number of the short captured graph.  The codes are the same bits
+    for either schedule and any quantum (the contract); `rounds` of the
+    result stays plan_rounds(...).rounds (callers group ragged batches by
+    it), `steps` and `occupancy` are those of the schedule that ran, and
+    max_round_bytes applies to the rows of the longest segment.
 
     Every argument is checked before the library or a device is touched;
     nothing waits for the device beyond what generate_batch waits for.  The
@@ -226,7 +286,21 @@ def synthesize(net, lengths, *, seeds, batch=32, first_samples=None,
     if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
         raise ValueError('synthesize: temperature must be a positive finite '
                          'number, got %r' % (temperature,))
+    if schedule not in SCHEDULES:
+        raise ValueError('synthesize: schedule must be one of %s, got %r'
+                         % (', '.join(SCHEDULES), schedule))
+    if quantum is not None:
+        quantum = _quantum(quantum)
     plan = plan_rounds(n, B)
+    if schedule == 'queue':
+        if quantum is None:
+            quantum = max(1, int(net.fastgen_graph_steps) // 10)
+        qplan = plan_queue(n, B, quantum)
+        codes = _run_queue(net, n, qplan, min(B, U), sd, first, gc, kind,
+                           cond, int(max_round_bytes),
+                           dict(temperature=temperature, top_k=top_k,
+                                top_p=top_p))
+        return Synthesis(codes, plan.rounds, qplan.steps, qplan.occupancy)
     # one round: its own size; else every round runs `batch` streams
     Br = B if len(plan.rounds) > 1 else len(plan.rounds[0])
     if kind is not None:
@@ -258,9 +332,86 @@ def synthesize(net, lengths, *, seeds, batch=32, first_samples=None,
     return Synthesis(codes, plan.rounds, plan.steps, plan.occupancy)
 
 
+def _run_queue(net, n, qplan, Bq, sd, first, gc, kind, cond, max_bytes, draw):
+    """The restart queue on Bq = min(batch, items) streams -> codes.  One
+    generate_batch for the first segment (its items start at 0), then one
+    continue_generation_batch(restart=admitted) per segment; every call is
+    given the longest segment as reserve_steps, so that all segments share
+    their buffers and captured graphs.  Nothing here waits for the device:
+    the last codes of a segment go to the next one as a device tensor."""
+    import torch
+    U, Q = n.size, int(net.Q)
+    longest = max(m for _, m in qplan.segments)
+    if kind is not None and Bq * longest * net.Lc * 4 > max_bytes:
+        raise ValueError(
+            'synthesize: the local-conditioning rows of a segment, [%d, %d, '
+            '%d] float32 = %d bytes, exceed max_round_bytes = %d; use a '
+            'smaller batch' % (Bq, longest, net.Lc,
+                               Bq * longest * net.Lc * 4, max_bytes))
+    _lib.load()
+    _lib.require_gpu()
+    by_start = {}
+    for u in range(U):
+        by_start.setdefault(qplan.start[u], []).append(u)
+    cur = [None] * Bq              # the item a slot holds (or held last)
+    rows = [None] * Bq             # its rows [n_u - 1, Lc] while it is live
+    pieces = [[] for _ in range(U)]
+    out = None
+    for a, m in qplan.segments:
+        # the codes of the segment before are taken out of `out` by
+        # slicing only (it is never written), so a finished item keeps its
+        # last code although the next item's first code takes its place
+        # in the generator's sample cell
+        admitted = sorted(by_start.get(a, []), key=lambda u: qplan.slot[u])
+        for s in range(Bq):        # items that have ended hold no rows
+            if cur[s] is not None and \
+                    qplan.start[cur[s]] + int(n[cur[s]]) <= a:
+                rows[s] = None
+        for u in admitted:
+            s = qplan.slot[u]
+            cur[s] = u
+            if kind is not None and n[u] > 1:
+                k = int(n[u]) - 1
+                # (frames: the item alone through the model's upsampler,
+                # the contract's own definition of its rows)
+                r = _device(net, cond[u][:k]) if kind == 'local_condition' \
+                    else net.upsample_local_condition(cond[u], int(n[u]))[:k]
+                rows[s] = r.contiguous()
+        slots = [qplan.slot[u] for u in admitted]
+        kw = dict(draw, reserve_steps=longest)
+        if gc is not None:
+            kw['global_condition'] = gc[cur]
+        if kind is not None:
+            kw['local_condition'] = net.batch_local_condition(
+                [None if rows[s] is None else (rows[s], qplan.start[cur[s]])
+                 for s in range(Bq)], a, m)
+        seeds = [sd[u] for u in cur]
+        if a == 0:
+            out = net.generate_batch(m, seeds,
+                                     seed_samples=first[cur][:, None],
+                                     **kw)[:, 1:]
+        else:
+            last = out[:, -1]
+            if slots:
+                last = last.index_copy(
+                    0, torch.tensor(slots, dtype=torch.int64
+                                    ).to(last.device),
+                    torch.from_numpy(first[admitted].astype(np.int32)
+                                     ).to(last.device))
+            out = net.continue_generation_batch(m, last, seeds,
+                                                restart=slots or None, **kw)
+        for s in range(Bq):
+            u = cur[s]
+            lo = max(a, qplan.start[u]) - a
+            hi = min(a + m, qplan.start[u] + int(n[u])) - a
+            if hi > lo:
+                pieces[u].append(out[s, lo:hi])
+    return [p[0] if len(p) == 1 else torch.cat(p) for p in pieces]
+
+
 def copy_synthesize(net, spec, audios, *, seeds, batch=32,
                     global_condition=None, temperature=1.0, top_k=None,
-                    top_p=None):
+                    top_p=None, schedule='rounds', quantum=None):
     """Copy synthesis of many utterances: every utterance's conditioning is
     computed from its own audio (float [n_u]) by the log-mel front end `spec`
     (net.local_condition_from_audio: frames for an upsampler model, rows for
@@ -283,6 +434,7 @@ def copy_synthesize(net, spec, audios, *, seeds, batch=32,
     syn = synthesize(net, [a.shape[0] for a in audios], seeds=seeds,
                      batch=batch, global_condition=global_condition,
                      temperature=temperature, top_k=top_k, top_p=top_p,
+                     schedule=schedule, quantum=quantum,
                      **{'frames' if net.lc_up else 'local_condition': cond})
     return syn, [mu_law_decode(c, net.Q) for c in syn.codes]
 
