@@ -5,8 +5,11 @@ and prints one JSON line
     {"nll_per_sample": .., "bits_per_sample": .., "accuracy": .., "samples": .., "clips": ..}
 
 (nats and bits per predicted sample, top-1 accuracy of the next-sample
-prediction).  The clips are prepared as train.py's reader prepares them
-(wavenet/evaluate.py's ValidationSet: sorted files, one pass, pieces per
+prediction; with --input_noise P,W also "noisy_input": {"prob", "width",
+"nll_per_sample", "bits_per_sample", "accuracy"}, the same pass scored again
+with the network reading perturbed codes, wavenet/input_noise.py -- clip i of
+the pass draws with key i -- against clean targets).  The clips are prepared
+as train.py's reader prepares them (wavenet/evaluate.py's ValidationSet: sorted files, one pass, pieces per
 file; with --lc_features mel, or a checkpoint that train.py --lc_features
 wrote, the local conditioning is computed on the device from each batch's
 audio and no <clip>.npy is read); the model flags are generate.py's, the
@@ -46,7 +49,8 @@ import sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
-from wavenet import emphasis, features, local_condition  # noqa: E402
+from wavenet import (  # noqa: E402
+    emphasis, features, input_noise, local_condition)
 from wavenet.checkpoint import (  # noqa: E402
     open_ema_checkpoint, restore, stored_emphasis, stored_lc_features)
 from wavenet.cli import (  # noqa: E402
@@ -128,7 +132,10 @@ def get_arguments(argv=None):
     p.add_argument('--top_p', type=float, default=None,
                    help='--synthesis: generate.py\'s --top_p')
     emphasis.add_cli_flag(p)
+    input_noise.add_cli_flags(p)
     a = p.parse_args(argv)
+    # (the InputNoise of --input_noise, or None)
+    a.noise = input_noise.from_cli(p, a)
     if a.preemphasis is not None:
         try:
             emphasis.Emphasis(a.preemphasis)
@@ -154,6 +161,10 @@ def main(argv=None):
         return 1
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
+    if args.noise is not None and wavenet_params.get('scalar_input'):
+        print('--input_noise is not for scalar_input models: their network '
+              'input is the float audio, not the codes')
+        return 1
     try:
         stored = stored_lc_features(args.checkpoint)
         if args.lc_channels is None and args.lc_features != 'none' and \
@@ -214,12 +225,22 @@ def main(argv=None):
     if why:
         print(why)
         return 1
-    batches = data.batches(args.batch_size)
-    if spec is not None:
-        batches = ev.with_features(net, spec, batches)
-    if emph is not None:
-        batches = ev.with_emphasis(emph, batches)
-    result = ev.evaluate(net, batches, args.max_batches)
+    def batches():
+        it = data.batches(args.batch_size)
+        if spec is not None:
+            it = ev.with_features(net, spec, it)
+        if emph is not None:
+            it = ev.with_emphasis(emph, it)
+        return it
+    result = ev.evaluate(net, batches(), args.max_batches)
+    if args.noise is not None:
+        # the same pass again, the network reading perturbed codes
+        noisy = ev.evaluate(net, batches(), args.max_batches,
+                            input_noise=args.noise)
+        result['noisy_input'] = dict(
+            prob=args.noise.prob, width=args.noise.width,
+            **{k: noisy[k] for k in ('nll_per_sample', 'bits_per_sample',
+                                     'accuracy')})
     if args.synthesis:
         whole = data
         if args.sample_size is not None:

@@ -50,6 +50,49 @@ int wn_mu_law_encode(const float* audio, int32_t* codes, long n,
 int wn_mu_law_decode(const int32_t* codes, float* audio, long n,
                      const float* lut_dev, int Q, void* stream);
 
+/* ---- input noise (csrc/wn_misc.hip; wavenet/input_noise.py): perturbed
+ * copies of the codes for the network to read while the loss keeps the clean
+ * codes as targets.  codes / codes_in: int32 [B][T]; keys: device int64 [B],
+ * clip b's key k[b], 0 <= k[b] < 2^40; lengths: device int32 [B] (clamped to
+ * [0, T] by the kernel) or NULL (n[b] = T).  keys and lengths are read when
+ * the kernel runs.  With w = width, for position t < 2^24 of clip b:
+ *
+ *   c    = (k[b] << 24) | t
+ *   bits = draw_bits(seed ^ 0x6e6f697365, c)
+ *        = splitmix64((seed ^ 0x6e6f697365) ^ splitmix64(c))
+ *   hit  = (bits & 0xFFFFFF) < thresh
+ *   d    = ((bits >> 24) & 0xFFFFF) % (w + 1) - ((bits >> 44) & 0xFFFFF) % (w + 1)
+ *   codes_in[b][t] = clamp(codes[b][t] + d, 0, Q - 1)
+ *                        where hit, t < n[b] and 0 <= codes[b][t] < Q,
+ *                    codes[b][t] otherwise (padding, out-of-range codes,
+ *                        thresh == 0)
+ *
+ * (d is triangular on [-w, w]; thresh = int(prob * 2^24), 2^24 hits every
+ * position.)  Integer arithmetic only: a pure function of (seed, k[b], t) and
+ * the code, not of B, T, the clip's place in the batch or the launch.
+ *
+ * wn_code_noise applies the rule to given codes (codes_in may be codes
+ * itself).  wn_mu_law_encode_noisy makes one pass over the audio [B][T] and
+ * writes the clean codes -- the bits of wn_mu_law_encode, by the same
+ * threshold search (thr_dev: its Q - 1 thresholds) -- and the perturbed ones
+ * (codes_in == codes: WN_ERR_UNSUPPORTED).
+ *
+ * One grid row per clip, four consecutive positions per thread, moved with
+ * 16-byte accesses where the clip's rows of every array start 16-byte aligned
+ * (with T % 4 != 0 only clip 0's do) and one by one otherwise; no LDS, no
+ * atomics.  NULL (but lengths): WN_ERR_NULL; B, T <= 0, T > 2^24, Q < 2,
+ * width < 1 or > 4095, thresh < 0 or > 2^24: WN_ERR_BAD_SHAPE; keys not
+ * 8-byte, any other pointer not 4-byte aligned: WN_ERR_MISALIGNED.  All checks
+ * come before any launch. */
+int wn_code_noise(const int32_t* codes, int32_t* codes_in, const int64_t* keys,
+                  const int32_t* lengths, int B, int T, int Q, uint64_t seed,
+                  int thresh, int width, void* stream);
+int wn_mu_law_encode_noisy(const float* audio, int32_t* codes,
+                           int32_t* codes_in, const int64_t* keys,
+                           const int32_t* lengths, int B, int T,
+                           const float* thr_dev, int Q, uint64_t seed,
+                           int thresh, int width, void* stream);
+
 /* ---- causal layer on one-hot input as a gather: wavenet/model.py:227-234
  * (_create_causal_layer) + :518-531 (_one_hot).  Wc is [K][Q][ldw] (the
  * 32 channels of one block start at Wc; ldw = padded channel count, 32 for

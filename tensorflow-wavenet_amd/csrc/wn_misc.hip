@@ -88,6 +88,95 @@ __global__ void mu_law_encode_kernel(const float* __restrict__ audio,
   }
 }
 
+// ---------------------------------------------------------------------------
+// input noise (wavenet/input_noise.py; the rule: include/wavenet_hip.h).
+// Perturbed copies of the codes for the network to READ while the loss keeps
+// the clean ones as targets.  Integer arithmetic on draw_bits only: a pure
+// function of (seed, key of the clip, position).  One grid row per clip, so
+// the key and the length are wave-uniform; a thread owns four consecutive
+// positions and moves them with 16-byte accesses where the clip's rows start
+// 16-byte aligned (rows of a batch with T % 4 != 0 do not from the second
+// clip on: those go one by one).  No LDS: the fused kernel searches the
+// thresholds in global memory (Q - 1 floats, cache resident).
+// ---------------------------------------------------------------------------
+#define NOISE_SEED_TAG 0x6e6f697365ull
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// kc: key << 24; w1: width + 1; n: the clip's real samples
+__device__ __forceinline__ int noisy_code(int q, uint64_t seed, uint64_t kc,
+                                          int t, int n, int Q, int thresh,
+                                          uint32_t w1) {
+  if (t >= n || q < 0 || q >= Q) return q;
+  const uint64_t bits = draw_bits(seed, kc | (uint64_t)t);
+  if ((int)(bits & 0xFFFFFFu) >= thresh) return q;
+  const int d = (int)((uint32_t)((bits >> 24) & 0xFFFFFu) % w1) -
+                (int)((uint32_t)((bits >> 44) & 0xFFFFFu) % w1);
+  return min(max(q + d, 0), Q - 1);
+}
+
+// mu_law_encode_kernel's search, thresholds read where they lie
+__device__ __forceinline__ int mu_code_dev(float x, const float* __restrict__ thr,
+                                           int Q) {
+  if (x >= -1.f && x <= 1.f) {
+    int lo = 0, hi = Q - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (thr[mid] <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  }
+  return mu_chain_dev(x, Q);
+}
+
+// ENCODE: clean codes from audio (written to `codes`), else read from `codes`
+// (codes_in may be codes itself: a position is read and written by one thread)
+template <bool ENCODE>
+__global__ __launch_bounds__(256) void code_noise_kernel(
+    const float* __restrict__ audio, const float* __restrict__ thr,
+    int32_t* codes, int32_t* codes_in, const int64_t* __restrict__ keys,
+    const int32_t* __restrict__ lengths, int B, int T, int Q, uint64_t seed,
+    int thresh, uint32_t w1) {
+  const int t0 = (int)(blockIdx.x * 256 + threadIdx.x) * 4;
+  if (t0 >= T) return;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const long row = (long)b * T;
+    int n = T;
+    if (lengths) n = min(max(lengths[b], 0), T);
+    const uint64_t kc = (uint64_t)keys[b] << 24;
+    uintptr_t al = reinterpret_cast<uintptr_t>(codes + row) |
+                   reinterpret_cast<uintptr_t>(codes_in + row);
+    if (ENCODE) al |= reinterpret_cast<uintptr_t>(audio + row);
+    if ((al & 15u) == 0 && t0 + 4 <= T) {
+      i32x4 q;
+      if (ENCODE) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(audio + row + t0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = mu_code_dev(a[i], thr, Q);
+        *reinterpret_cast<i32x4*>(codes + row + t0) = q;
+      } else {
+        q = *reinterpret_cast<const i32x4*>(codes + row + t0);
+      }
+      i32x4 r;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        r[i] = noisy_code(q[i], seed, kc, t0 + i, n, Q, thresh, w1);
+      *reinterpret_cast<i32x4*>(codes_in + row + t0) = r;
+    } else {
+      const int t1 = min(t0 + 4, T);
+      for (int t = t0; t < t1; ++t) {
+        int q;
+        if (ENCODE) {
+          q = mu_code_dev(audio[row + t], thr, Q);
+          codes[row + t] = q;
+        } else {
+          q = codes[row + t];
+        }
+        codes_in[row + t] = noisy_code(q, seed, kc, t, n, Q, thresh, w1);
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ float mu_decode_dev(int code, int Q) {
   const float mu = (float)(Q - 1);
   const float s = __fsub_rn(__fmul_rn(2.0f, __fdiv_rn((float)code, mu)), 1.0f);
@@ -450,6 +539,62 @@ int wn_mu_law_encode(const float* audio, int32_t* codes, long n,
   hipLaunchKernelGGL(mu_law_encode_kernel, dim3(grid1d(n, 256)), dim3(256),
                      (Q - 1) * sizeof(float), (hipStream_t)stream, audio, codes,
                      n, thr_dev, Q);
+  return wn_check_launch();
+}
+
+static inline bool wn_aligned(const void* p, unsigned bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+
+// the checks the two input-noise entries share
+static inline int code_noise_args(const void* codes, const void* codes_in,
+                                  const void* keys, const void* lengths, int B,
+                                  int T, int Q, int thresh, int width) {
+  if (!codes || !codes_in || !keys) return WN_ERR_NULL;
+  if (B <= 0 || T <= 0 || T > (1 << 24) || Q < 2 || width < 1 ||
+      width > 4095 || thresh < 0 || thresh > (1 << 24))
+    return WN_ERR_BAD_SHAPE;
+  if (!wn_aligned(codes, 4) || !wn_aligned(codes_in, 4) ||
+      !wn_aligned(keys, 8) || !wn_aligned(lengths, 4))
+    return WN_ERR_MISALIGNED;
+  return WN_OK;
+}
+
+static inline dim3 code_noise_grid(int B, int T) {
+  const int groups = (T + 3) / 4;           // four positions per thread
+  return dim3((unsigned)((groups + 255) / 256), (unsigned)(B < 65535 ? B : 65535));
+}
+
+int wn_code_noise(const int32_t* codes, int32_t* codes_in, const int64_t* keys,
+                  const int32_t* lengths, int B, int T, int Q, uint64_t seed,
+                  int thresh, int width, void* stream) {
+  const int bad = code_noise_args(codes, codes_in, keys, lengths, B, T, Q,
+                                  thresh, width);
+  if (bad) return bad;
+  hipLaunchKernelGGL(code_noise_kernel<false>, code_noise_grid(B, T), dim3(256),
+                     0, (hipStream_t)stream, (const float*)nullptr,
+                     (const float*)nullptr, const_cast<int32_t*>(codes),
+                     codes_in, keys, lengths, B, T, Q, seed ^ NOISE_SEED_TAG,
+                     thresh, (uint32_t)(width + 1));
+  return wn_check_launch();
+}
+
+int wn_mu_law_encode_noisy(const float* audio, int32_t* codes,
+                           int32_t* codes_in, const int64_t* keys,
+                           const int32_t* lengths, int B, int T,
+                           const float* thr_dev, int Q, uint64_t seed,
+                           int thresh, int width, void* stream) {
+  if (!audio || !thr_dev) return WN_ERR_NULL;
+  const int bad = code_noise_args(codes, codes_in, keys, lengths, B, T, Q,
+                                  thresh, width);
+  if (bad) return bad;
+  if (!wn_aligned(audio, 4) || !wn_aligned(thr_dev, 4)) return WN_ERR_MISALIGNED;
+  // (the clean and the perturbed codes are both written: two buffers)
+  if (codes == codes_in) return WN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(code_noise_kernel<true>, code_noise_grid(B, T), dim3(256),
+                     0, (hipStream_t)stream, audio, thr_dev, codes, codes_in,
+                     keys, lengths, B, T, Q, seed ^ NOISE_SEED_TAG, thresh,
+                     (uint32_t)(width + 1));
   return wn_check_launch();
 }
 

@@ -22,6 +22,12 @@ SIGNATURES = {
     'wn_mu_law_decode_table_host': (c_int, [c_int, P]),
     'wn_mu_law_encode': (c_int, [P, P, c_long, P, c_int, P]),
     'wn_mu_law_decode': (c_int, [P, P, c_long, P, c_int, P]),
+    # input noise: [audio,] codes, codes_in, keys, lengths, B, T, [thr,] Q,
+    # seed, thresh, width, stream
+    'wn_code_noise': (c_int, [P, P, P, P, c_int, c_int, c_int, c_u64, c_int,
+                              c_int, P]),
+    'wn_mu_law_encode_noisy': (c_int, [P, P, P, P, P, c_int, c_int, P, c_int,
+                                       c_u64, c_int, c_int, P]),
     'wn_causal_gather': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int,
                                  P]),
     'wn_scalar_causal_fwd': (c_int, [P, P, c_int, P, c_int, c_int, c_int, P]),

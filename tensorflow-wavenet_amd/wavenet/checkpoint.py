@@ -2,7 +2,7 @@
 
 train.py writes torch files holding {'variables': {reference variable name:
 tensor}, 'step'} and, where the run has them, 'optimizer', 'ema_variables',
-'lc_features', 'device_corpus' and 'emphasis'; the step is parsed from the file name, as
+'lc_features', 'device_corpus', 'emphasis' and 'input_noise'; the step is parsed from the file name, as
 in the reference (train.py:104-134 there).  The reference's own TensorFlow
 checkpoints are read too (tf_checkpoint.py).  train.py, generate.py and
 evaluate.py import their checkpoint functions from here.
@@ -31,7 +31,7 @@ def checkpoint_path(logdir, step):
 
 
 def save(net, logdir, step, optimizer=None, lc_features=None,
-         device_corpus=None, emphasis=None):
+         device_corpus=None, emphasis=None, input_noise=None):
     """`optimizer`: its step count, slots and shadow go in as 'optimizer'
     and, with EMA weights, the shadow as 'ema_variables' (the keys of
     'variables').  `lc_features`: the front end's settings
@@ -40,7 +40,10 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
     sample_size, lc_feature_context) and the index of the last batch taken
     ('batch'), stored under 'device_corpus'.  `emphasis`: the pre-emphasis
     the model was trained on (emphasis.Emphasis.entry: {'alpha': ..}),
-    stored under 'emphasis'; a run without it writes no such entry."""
+    stored under 'emphasis'; a run without it writes no such entry.
+    `input_noise`: the noise the run's inputs were perturbed with
+    (input_noise.InputNoise.entry: {'prob', 'width', 'seed'}), stored under
+    'input_noise', likewise only where given."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
@@ -52,6 +55,8 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
         ckpt['device_corpus'] = device_corpus
     if emphasis is not None:
         ckpt['emphasis'] = emphasis
+    if input_noise is not None:
+        ckpt['input_noise'] = input_noise
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
         if optimizer.ema_decay is not None:

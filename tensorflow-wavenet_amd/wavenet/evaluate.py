@@ -160,9 +160,13 @@ def with_emphasis(emphasis, batches):
         yield (emphasis.pre(audio, lengths), lengths, gc, lc, *hist)
 
 
-def totals(net, batches, max_batches=None):
+def totals(net, batches, max_batches=None, *, input_noise=None, rank=0,
+           world=1):
     """float64 [4] on the device: (sum of nll, targets, hits, clips) over
-    net.score of every batch (at most max_batches of them).  No host wait."""
+    net.score of every batch (at most max_batches of them).  No host wait.
+    input_noise (input_noise.InputNoise): the network reads perturbed codes,
+    the targets stay clean; the key of a clip is its running index in this
+    pass times `world` plus `rank`."""
     tot, clips = None, 0
     for i, (audio, lengths, gc, lc, *hist) in enumerate(batches):
         if max_batches is not None and i >= max_batches:
@@ -172,6 +176,10 @@ def totals(net, batches, max_batches=None):
             lc, off = lc
         # (a fifth item: the pieces' history, ValidationSet(history=...))
         kw = dict(history=hist[0]) if hist else {}
+        if input_noise is not None:
+            b = int(np.shape(lengths)[0])
+            kw.update(input_noise=input_noise, noise_keys=(
+                clips + np.arange(b, dtype=np.int64)) * world + rank)
         s = net.score(audio, gc, local_condition_batch=lc,
                       local_condition_offset=off, lengths=lengths, **kw)
         part = torch.stack([s.nll.sum(), s.count.sum().to(torch.float64),
@@ -194,12 +202,13 @@ def summary(tot):
             'samples': int(count), 'clips': int(clips)}
 
 
-def evaluate(net, batches, max_batches=None):
+def evaluate(net, batches, max_batches=None, **noise):
     """Score `batches` (ValidationSet.batches items) with net.score, the
     sums kept in float64 on the device and fetched once at the end.  Returns
     nll_per_sample (nats per predicted sample), bits_per_sample (that
-    / ln 2), accuracy (top-1), samples (predicted samples) and clips."""
-    return summary(totals(net, batches, max_batches))
+    / ln 2), accuracy (top-1), samples (predicted samples) and clips.
+    noise: totals' input_noise, rank and world."""
+    return summary(totals(net, batches, max_batches, **noise))
 
 
 @contextlib.contextmanager

@@ -749,7 +749,9 @@ class WaveNetModel(object):
              local_condition_offset=0,
              lengths=None,
              loss_denominator=None,
-             history=None):
+             history=None,
+             input_noise=None,
+             noise_keys=None):
         '''Creates a WaveNet network and returns the autoencoding loss
         (model.py:628-685).  input_batch: float audio in [-1, 1], anything
         reshapeable to [batch_size, -1].  With backward=True (default) the
@@ -789,7 +791,16 @@ class WaveNetModel(object):
         add nothing to the loss or to any gradient; row n[b] - 1 stays the
         label-less last row; the mean is taken over sum(n - history) rows
         (loss_denominator still replaces it).  history = 0 is the call
-        without history, bit for bit.'''
+        without history, bit for bit.
+
+        input_noise (an input_noise.InputNoise) with noise_keys (batch_size
+        ints in [0, 2**40) or a device int64 tensor; both or neither): the
+        network reads perturbed codes -- each of clip b's n[b] input codes,
+        history included, moved as InputNoise states with the key
+        noise_keys[b] -- while every target stays the clean code.  One fused
+        launch encodes the audio and perturbs it.  Not for scalar_input
+        models, whose network input is the float audio.'''
+        self._check_noise(input_noise, noise_keys, 'loss')
         self._check_supported()
         B = self.batch_size
         a = input_batch
@@ -801,17 +812,30 @@ class WaveNetModel(object):
                                    a.shape[1], 'loss')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'loss')
-        return self._loss(mu_law_encode(a, self.Q), global_condition_batch,
+        if input_noise is None:
+            q, q_in = mu_law_encode(a, self.Q), None
+        else:
+            q, q_in = self._encode_noisy(a, input_noise, noise_keys, mask,
+                                         backward)
+        return self._loss(q, global_condition_batch,
                           l2_regularization_strength, backward, a, lc, mask,
-                          hist)
+                          hist, q_in)
 
     def loss_from_codes(self, q, global_condition_batch=None,
                         l2_regularization_strength=None, backward=True,
                         audio=None, *, local_condition_batch=None,
                         local_condition_offset=0, lengths=None,
-                        loss_denominator=None, history=None):
+                        loss_denominator=None, history=None,
+                        input_codes=None):
+        """`loss` on mu-law codes q.  input_codes (device int32
+        [batch_size, T]): what the network reads in place of q, which stays
+        the target of every row (input_noise.InputNoise.codes makes such
+        codes); without it nothing but q is used, as ever."""
+        if input_codes is not None:
+            self._refuse_scalar_noise('loss', 'input_codes')
         self._check_supported()
         q = q.reshape(self.batch_size, -1)
+        q_in = self._check_input_codes(input_codes, q, 'loss')
         mask = check_lengths(lengths, loss_denominator, self.batch_size,
                              q.shape[1], 'loss')
         mask, hist = check_history(history, mask, loss_denominator,
@@ -820,13 +844,57 @@ class WaveNetModel(object):
                          self.batch_size, q.shape[1], 'loss')
         return self._loss(q, global_condition_batch,
                           l2_regularization_strength, backward, audio, lc,
-                          mask, hist)
+                          mask, hist, q_in)
+
+    # ---- inputs that differ from the targets (wavenet/input_noise.py)
+    def _check_noise(self, input_noise, noise_keys, what):
+        if (input_noise is None) != (noise_keys is None):
+            raise ValueError('%s: input_noise and noise_keys go together'
+                             % what)
+        if input_noise is None:
+            return
+        from .input_noise import InputNoise
+        if not isinstance(input_noise, InputNoise):
+            raise ValueError('%s: input_noise must be an InputNoise, got %r'
+                             % (what, input_noise))
+        self._refuse_scalar_noise(what, 'input_noise')
+
+    def _refuse_scalar_noise(self, what, name):
+        if self.scalar_input:
+            raise ValueError(
+                '%s: %s is not for scalar_input models: their network input '
+                'is the float audio, not the codes' % (what, name))
+
+    def _check_input_codes(self, input_codes, q, what):
+        """input_codes as device int32 [B, T] beside codes q [B, T], or
+        None."""
+        if input_codes is None:
+            return None
+        if not isinstance(input_codes, torch.Tensor) or \
+                input_codes.dtype != torch.int32 or \
+                input_codes.device != self.device or \
+                tuple(input_codes.shape) != tuple(q.shape):
+            raise ValueError(
+                '%s: input_codes must be an int32 tensor of shape %s on %s'
+                % (what, tuple(q.shape), self.device))
+        return input_codes
+
+    def _encode_noisy(self, a, noise, keys, mask, training):
+        """(q, q_in) of audio a [B, T] by the fused kernel, written straight
+        into the workspace's q_tgt and q (what _loss and scoring.score would
+        copy them into)."""
+        B, T = a.shape
+        ws = self._workspace(B, T, training)
+        return noise.encode(a, self.Q, keys,
+                            None if mask is None else mask[0],
+                            out=(ws.q_tgt.view(B, T), ws.q.view(B, T)))
 
     def _loss(self, q, global_condition_batch, l2_regularization_strength,
-              backward, audio, lc, mask=None, hist=None):
+              backward, audio, lc, mask=None, hist=None, q_in=None):
         """loss_from_codes on codes q [B, T] with the LC input checked
         (local_condition.check), the lengths (check_lengths) and the history
-        (check_history)."""
+        (check_history).  q_in: what the network reads instead (q stays the
+        target), or None."""
         B, T = q.shape
         N = B * T
         ws = self._workspace(B, T, backward)
@@ -841,7 +909,7 @@ class WaveNetModel(object):
                           'was never joined (no optimizer.minimize followed): '
                           'joined and dropped now')
             parallel.abandon_tail_allreduce(self)
-        ws.q.copy_(q.reshape(-1))
+        q_lab = train_pass.stage_codes(ws, q, q_in)
         if self.scalar_input:
             # network input is the raw float audio (model.py:645-648)
             if audio is None:
@@ -858,7 +926,7 @@ class WaveNetModel(object):
         quirk = 1 if self.tf_xent_zero_label_quirk else 0
         if mask is None:
             den = float(N)
-            _lib.call('wn_xent', _lib.ptr(ws.logits), self.Q, _lib.ptr(ws.q),
+            _lib.call('wn_xent', _lib.ptr(ws.logits), self.Q, _lib.ptr(q_lab),
                       _lib.ptr(ws.logits) if backward else None,
                       _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk, st)
         else:
@@ -869,7 +937,7 @@ class WaveNetModel(object):
                 [lengths, np.array([inv], np.float32).view(np.int32)])))
             if hist is None:
                 _lib.call('wn_xent_masked', _lib.ptr(ws.logits), self.Q,
-                          _lib.ptr(ws.q), _lib.ptr(ws.xent_mask),
+                          _lib.ptr(q_lab), _lib.ptr(ws.xent_mask),
                           _lib.ptr(ws.xent_mask[B:]),
                           _lib.ptr(ws.logits) if backward else None,
                           _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk,
@@ -878,7 +946,7 @@ class WaveNetModel(object):
                 # staged like the lengths: read by the kernel when it runs
                 ws.xent_hist.copy_(torch.from_numpy(hist))
                 _lib.call('wn_xent_window', _lib.ptr(ws.logits), self.Q,
-                          _lib.ptr(ws.q), _lib.ptr(ws.xent_hist),
+                          _lib.ptr(q_lab), _lib.ptr(ws.xent_hist),
                           _lib.ptr(ws.xent_mask), _lib.ptr(ws.xent_mask[B:]),
                           _lib.ptr(ws.logits) if backward else None,
                           _lib.ptr(ws.loss_parts[2:]), B, T, self.Q, quirk,
@@ -919,7 +987,8 @@ class WaveNetModel(object):
 
     def score(self, input_batch, global_condition_batch=None, *,
               local_condition_batch=None, local_condition_offset=0,
-              lengths=None, per_sample=False, history=None):
+              lengths=None, per_sample=False, history=None,
+              input_noise=None, noise_keys=None):
         '''Scores held-out audio: per-clip negative log-likelihood, target
         count and top-1 hits.  Forward only -- the pass predict_proba makes,
         on the forward-only workspace: no gradient is touched, no all-reduce
@@ -949,7 +1018,12 @@ class WaveNetModel(object):
         history (as for `loss`): rows with t + 1 < history[b] have no target
         either: count[b] = n[b] - max(history[b], 1), and
         loss(backward=False, lengths=n, history=h) == nll.sum() /
-        sum(n - h).'''
+        sum(n - h).
+
+        input_noise, noise_keys (as for `loss`, one key per row of the
+        batch): the network reads perturbed codes, the scored targets stay
+        clean.'''
+        self._check_noise(input_noise, noise_keys, 'score')
         self._check_supported()
         a = input_batch
         if not isinstance(a, torch.Tensor):
@@ -963,22 +1037,31 @@ class WaveNetModel(object):
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'score')
         from . import scoring
-        return scoring.score(self, mu_law_encode(a, self.Q),
-                             global_condition_batch, a, lc, mask, per_sample,
-                             hist)
+        if input_noise is None:
+            q, q_in = mu_law_encode(a, self.Q), None
+        else:
+            q, q_in = self._encode_noisy(a, input_noise, noise_keys, mask,
+                                         False)
+        return scoring.score(self, q, global_condition_batch, a, lc, mask,
+                             per_sample, hist, q_in)
 
     def score_from_codes(self, q, global_condition_batch=None, audio=None, *,
                          local_condition_batch=None, local_condition_offset=0,
-                         lengths=None, per_sample=False, history=None):
+                         lengths=None, per_sample=False, history=None,
+                         input_codes=None):
         """`score` on mu-law codes q (int, [B, T] with any B >= 1, else
         reshaped to [batch_size, -1]); audio: the float audio a scalar_input
-        model needs."""
+        model needs; input_codes (device int32, q's shape): what the network
+        reads in place of q, which stays the target."""
+        if input_codes is not None:
+            self._refuse_scalar_noise('score', 'input_codes')
         self._check_supported()
         if not isinstance(q, torch.Tensor):
             q = torch.as_tensor(np.asarray(q))
         B = q.shape[0] if q.dim() == 2 and q.shape[0] >= 1 \
             else self.batch_size
         q = q.reshape(B, -1)
+        q_in = self._check_input_codes(input_codes, q, 'score')
         mask = check_lengths(lengths, None, B, q.shape[1], 'score')
         mask, hist = check_history(history, mask, None, B, q.shape[1],
                                    'score')
@@ -986,7 +1069,7 @@ class WaveNetModel(object):
                          B, q.shape[1], 'score')
         from . import scoring
         return scoring.score(self, q, global_condition_batch, audio, lc, mask,
-                             per_sample, hist)
+                             per_sample, hist, q_in)
 
     def _l2_tmp(self):
         if not hasattr(self, '_l2_parts'):

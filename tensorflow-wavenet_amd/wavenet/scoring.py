@@ -15,13 +15,15 @@ Score = collections.namedtuple('Score', 'nll count correct per_sample')
 
 
 def score(net, q, global_condition_batch, audio, lc, mask, per_sample,
-          hist=None):
+          hist=None, q_in=None):
     """Score codes q [B, T] (any B >= 1) with the LC input checked
     (local_condition.check), the lengths (model.check_lengths) and the
-    history (model.check_history).  Nothing here waits for the device."""
+    history (model.check_history).  q_in: the codes the network reads
+    instead (q stays the target), or None.  Nothing here waits for the
+    device."""
     B, T = q.shape
     ws = net._workspace(B, T, False)
-    ws.q.copy_(q.reshape(-1))
+    q_lab = train_pass.stage_codes(ws, q, q_in)
     if net.scalar_input:
         if audio is None:
             raise ValueError('scalar_input needs the float audio')
@@ -48,13 +50,13 @@ def score(net, q, global_condition_batch, audio, lc, mask, per_sample,
         lengths.copy_(torch.from_numpy(mask[0]))
     if hist is None:
         _lib.call('wn_xent_score', _lib.ptr(ws.logits), net.Q,
-                  _lib.ptr(ws.q), _lib.ptr(lengths), _lib.ptr(rows),
+                  _lib.ptr(q_lab), _lib.ptr(lengths), _lib.ptr(rows),
                   _lib.ptr(nll), _lib.ptr(count), _lib.ptr(correct),
                   _lib.ptr(ws.score_scratch), B, T, net.Q, _lib.stream())
     else:
         ws.xent_hist.copy_(torch.from_numpy(hist))
         _lib.call('wn_xent_score_window', _lib.ptr(ws.logits), net.Q,
-                  _lib.ptr(ws.q), _lib.ptr(ws.xent_hist), _lib.ptr(lengths),
+                  _lib.ptr(q_lab), _lib.ptr(ws.xent_hist), _lib.ptr(lengths),
                   _lib.ptr(rows), _lib.ptr(nll), _lib.ptr(count),
                   _lib.ptr(correct), _lib.ptr(ws.score_scratch), B, T, net.Q,
                   _lib.stream())

@@ -139,6 +139,22 @@ def stage_ids(net, ws, ids):
     return ws.gc_ids
 
 
+def stage_codes(ws, q, q_in=None):
+    """Codes into the workspace: q [B, T] into ws.q, which the network reads
+    and the loss labels with -- or, where the inputs differ from the targets
+    (q_in given), q_in into ws.q and the clean q into ws.q_tgt.  Returns the
+    buffer the cross-entropy / scoring launch gets as its `q`.  (Codes that
+    were written into these buffers in the first place are not copied.)"""
+    if q_in is None:
+        ws.q.copy_(q.reshape(-1))
+        return ws.q
+    if q_in.data_ptr() != ws.q.data_ptr():
+        ws.q.copy_(q_in.reshape(-1))
+    if q.data_ptr() != ws.q_tgt.data_ptr():
+        ws.q_tgt.copy_(q.reshape(-1))
+    return ws.q_tgt
+
+
 def run_pass(net, tag, ws, ids, path):
     """The forward ('fwd') or backward ('bwd') pass through a recorded
     launch plan (see _lib.record), keyed by the call's StepPath."""

@@ -67,6 +67,10 @@ class _Workspace(object):
 
         self.plans = {}
         alloc('q', (N,), torch.int32)
+        # the clean codes of a call whose network input differs from its
+        # targets (loss / score with input_codes): ws.q is what the network
+        # reads, q_tgt what the cross-entropy and scoring launches label with
+        alloc('q_tgt', (N,), torch.int32)
         self.gc_ids = alloc('gc_ids', (B,), torch.int32) \
             if net.card is not None else None
         self.audio = alloc('audio', (N,)) if net.scalar_input else None
