@@ -364,6 +364,29 @@ def test_every_launch_geometry_matches_float64(hip_lib, case):
     _assert_lc_launches(hip_lib, net, B, T, fw, bwd)
 
 
+@pytest.mark.parametrize('var', [None, (32, 2)], ids=['library', 'bw2'])
+@pytest.mark.parametrize('B,T', [(2, 333), (8, 301)])
+def test_unaligned_dilations_match_float64(hip_lib, B, T, var):
+    """DIL_A (tests/util.py; tests/test_dilations_host.py counts what it
+    reaches at T = 333 and 301): taps that straddle two foreign tiles, taps
+    that start inside a later tile, rows t + d cut by the clip's end -- in the
+    LC instantiations of the stack launches, at the library's launch choice
+    and with two backward waves per workgroup."""
+    from util import DIL_A
+    from wavenet import _lib
+    Lc = 80
+    net = _model(B, Lc, DIL_A, seed=B + T)
+    if var is not None:
+        net.stack_variant = _lib.stack_variant(*var)
+    v = net._stack_variant_for_launch()
+    rows, fw, bwd = _launches(hip_lib, B, T, v)
+    assert rows == 32 and (var is None or bwd[0] == var[1])
+    codes, lc = _inputs(B, T, 64, Lc, seed=T)
+    _check_against_ref(net, DIL_A, codes, lc, case='dil_A B%d T%d fw%d bw%dx%d'
+                       % (B, T, fw, bwd[0], bwd[1]))
+    _assert_lc_launches(hip_lib, net, B, T, fw, bwd)
+
+
 def test_default_stack_takes_the_lc_launches_not_stack_skip(hip_lib):
     """wavenet_params.json (L = 50, S = 512, Q = 256) at 2 x 5200: without LC
     the fused-skip forward (which ignores LC) would cover this shape."""

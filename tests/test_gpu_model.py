@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-from util import (O, TINY, MID, DEFAULT, cfg_with, build_pair, flat_named,
-                  tree_to_numpy, model_kwargs, synth_audio,
-                  oracle_grads_at_device_kinks)
+from util import (O, TINY, MID, DEFAULT, DIL_A, DIL_B, DIL_C, cfg_with,
+                  build_pair, flat_named, tree_to_numpy, model_kwargs,
+                  synth_audio, oracle_grads_at_device_kinks)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -165,6 +165,25 @@ CASES = [
                                   global_condition_channels=32,
                                   global_condition_cardinality=377), 5200, True,
      None),
+    # dilations that are not powers of two: taps that straddle two foreign
+    # tiles, taps that start inside a later tile, d >= T
+    # (tests/test_dilations_host.py counts them for these lists and lengths;
+    # the float32 oracle -- tests/golden/make_golden.py, fp32_error -- is
+    # 1.2e-6 / 1.0e-6 / 1.2e-6 / 1.8e-6 from float64 on these four and 5.5e-7 /
+    # 7.1e-7 on the two after them, under a quarter of GRAD_REL: the bound
+    # stands as it is, nothing is added to fp32_oracle_error.npz)
+    ('dil_A', cfg_with(MID, batch_size=2, dilations=DIL_A), 301, False, None),
+    ('dil_B', cfg_with(MID, batch_size=3, dilations=DIL_B), 150, False, None),
+    ('dil_tiny', cfg_with(TINY, batch_size=2,
+                          dilations=[3, 5, 6, 7, 9, 33, 47]), 131, False, None),
+    ('dil_C', cfg_with(DEFAULT, batch_size=2, dilations=DIL_C), 1100, False,
+     None),
+    # ... and the t - d addressing of the block / generic-tap kernels
+    ('r64_k3_odd', cfg_with(TINY, batch_size=1, residual_channels=64,
+                            dilation_channels=48, filter_width=3,
+                            dilations=[3, 5, 33, 7]), 150, False, None),
+    ('k5_odd', cfg_with(TINY, batch_size=2, filter_width=5,
+                        dilations=[3, 9, 17, 6]), 140, False, None),
 ]
 
 
@@ -824,6 +843,19 @@ def test_random_configurations_vs_oracle(hip_lib):
                         '24', '7'], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert '0 of 24 cases failed' in r.stdout
+
+
+def test_random_configurations_any_dilation_vs_oracle(hip_lib):
+    """tools/model_fuzz.py with `any`: the same draws, but every dilation from
+    1 .. 600, half of them within one of a multiple of 16 (12 cases: 2.8 s on
+    an MI355X)."""
+    import subprocess
+    import sys
+    from util import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'model_fuzz.py'),
+                        '12', '7', 'any'], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert '0 of 12 cases failed' in r.stdout
 
 
 @pytest.mark.parametrize('Q', [64, 320, 512])

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import ROOT, TINY, build_pair, cfg_with, synth_audio
+from util import DIL_A, DIL_C, ROOT, TINY, build_pair, cfg_with, synth_audio
 from wavenet import WaveNetModel
 from wavenet._lib import stack_variant
 
@@ -64,6 +64,14 @@ CASES = [
     ('default_B300_T64', lambda: default_cfg(300), 300, 64, None),     # many clips of two tiles
     ('one_layer_B2_T500', lambda: default_cfg(2, dilations=[4]), 2, 500, None),
     ('two_layers_B2_T500', lambda: default_cfg(2, dilations=[64, 1]), 2, 500, None),
+    # dilations that are not powers of two (tests/test_dilations_host.py counts
+    # the tile-layer pairs): a tap that straddles two foreign tiles -- lane 1's
+    # flag wait, forward and backward --, a tap that starts inside a later tile
+    # of a clip that is not the first, rows t + d cut by the clip's end; taps
+    # far behind the clip's start; clips shorter than four of the dilations
+    ('straddle_A_B3_T333', lambda: default_cfg(3, dilations=DIL_A), 3, 333, None),
+    ('straddle_C_B2_T1100', lambda: default_cfg(2, dilations=DIL_C), 2, 1100, None),
+    ('straddle_A_B5_T47', lambda: default_cfg(5, dilations=DIL_A), 5, 47, None),
 ]
 
 
@@ -247,9 +255,14 @@ def test_stack_backward_equals_per_layer(hip_lib, monkeypatch, name, mk, B, T, k
     here; all three models then run the 16-row FORWARD too, so the planes the
     backward paths read are bitwise the same."""
     var = stack_variant(rows=rows, waves=int(waves))
-    monkeypatch.setattr(WaveNetModel, 'DEFAULT_STACK_VARIANT', var)
     assert hip_lib.wn_stack_tile_rows(B, T, var) == rows
-    cfg = mk()
+    _backward_vs_per_layer(monkeypatch, name, mk(), B, T, kind, var)
+
+
+def _backward_vs_per_layer(monkeypatch, name, cfg, B, T, kind, var):
+    """test_stack_backward_equals_per_layer's rule for one configuration under
+    the variant word `var`"""
+    monkeypatch.setattr(WaveNetModel, 'DEFAULT_STACK_VARIANT', var)
     a, _ = build_pair(cfg)
     b, _ = build_pair(cfg)
     c, _ = build_pair(cfg)
@@ -290,6 +303,38 @@ def test_stack_backward_equals_per_layer(hip_lib, monkeypatch, name, mk, B, T, k
         prev = ga.clone()
         ctl = wa.stack_ctl_b.cpu().tolist()
         assert ctl[0] == 0 and ctl[1] == 0 and ctl[3] == 0 and ctl[2] == 2 + rep, ctl
+
+
+def _bwd_launch(lib, B, T, var):
+    """(backward waves, tiles per wave) of the launch, from the library"""
+    import ctypes
+    tpw = ctypes.c_int(0)
+    return lib.wn_stack_bwd_waves(B, T, var, ctypes.byref(tpw)), tpw.value
+
+
+@pytest.mark.parametrize('two_tiles', [False, True], ids=['B2', 'two_tiles_per_wave'])
+@pytest.mark.parametrize('waves', [1, 2])
+def test_stack_backward_few_waves_straddling_taps(hip_lib, monkeypatch, waves, two_tiles):
+    """The 32-row backward with 1 and 2 waves per workgroup on DIL_A, T = 333
+    (taps over two foreign tiles, `hif` cut by the clip's end, a ragged last
+    tile), by test_stack_backward_equals_per_layer's rule.  With two tiles per
+    wave the flags of the NEXT tile are requested during the previous one
+    (`nfv_push`), both lanes' words.  Tiles per wave is ceil(tiles / (waves x
+    CUs)): 2 x 11 tiles give one per wave on any device, so next to B = 2 the
+    same clips run at the smallest B at which the library reports two tiles per
+    wave (24 / 47 clips on 256 CUs); the per-clip tile arithmetic, which is what
+    tests/test_dilations_host.py counts, does not depend on B."""
+    var = stack_variant(32, waves)
+    T, B = 333, 2
+    if two_tiles:
+        B = next((b for b in range(2, 2000)
+                  if _bwd_launch(hip_lib, b, T, var)[1] >= 2), None)
+        assert B is not None and B * T < 2 ** 20, B
+    w, tpw = _bwd_launch(hip_lib, B, T, var)
+    assert hip_lib.wn_stack_tile_rows(B, T, var) == 32 and w == waves
+    assert (tpw >= 2) == two_tiles, (B, w, tpw)
+    _backward_vs_per_layer(monkeypatch, 'A_w%d_B%d' % (waves, B),
+                           default_cfg(B, dilations=DIL_A), B, T, None, var)
 
 
 def test_child_workspace_owns_fresh_backward_control_block(hip_lib):
@@ -352,17 +397,24 @@ def test_bounded_wait_expires_loudly(hip_lib):
     a.check_device_errors()
 
 
-@pytest.mark.parametrize('B,T,gc', [(1, 700, False), (1, 1500, False), (2, 333, True), (3, 40, False),
-                                    (1, 5200, True)])
-def test_forward_with_fused_skip_sum_equals_stack_plus_gemm(hip_lib, monkeypatch, B, T, gc):
+@pytest.mark.parametrize('B,T,gc,dil', [(1, 700, False, None), (1, 1500, False, None),
+                                        (2, 333, True, None), (3, 40, False, None),
+                                        (1, 5200, True, None), (2, 333, False, DIL_A)],
+                         ids=['1-700-False', '1-1500-False', '2-333-True', '3-40-False',
+                              '1-5200-True', '2-333-False-DIL_A'])
+def test_forward_with_fused_skip_sum_equals_stack_plus_gemm(hip_lib, monkeypatch, B, T, gc, dil):
     """wn_stack_fwd_skip (small batches, 512 skip channels: the skip sum by partner
     waves inside the 16-row forward launch) against wn_stack_fwd + the skip GEMM:
     the same X / Z / sigmoid planes bitwise, h1 to rounding (another order of
     the sum), loss and every gradient; forward-only too; ragged last tiles,
-    groups of fewer than four tiles, global conditioning."""
+    groups of fewer than four tiles, global conditioning; dilations whose taps
+    straddle two foreign tiles (the partner waves share the chain waves'
+    tiles)."""
     from util import DEFAULT
     monkeypatch.setattr(WaveNetModel, 'DEFAULT_STACK_VARIANT', 0)   # (the library's choice: 16-row tiles)
     kw = dict(global_condition_channels=32, global_condition_cardinality=377) if gc else {}
+    if dil is not None:
+        kw['dilations'] = dil
     cfg = cfg_with(DEFAULT, batch_size=B, **kw)
     assert hip_lib.wn_stack_fwd_skip_ok(B, T, 512, 0) == 1
     assert hip_lib.wn_stack_fwd_skip_ok(B, T, 256, 0) == 0

@@ -23,6 +23,21 @@ DEFAULT = dict(dilations=[2 ** i for i in range(10)] * 5, filter_width=2,
                residual_channels=32, dilation_channels=32, skip_channels=512,
                quantization_channels=256, use_biases=True)
 
+# Dilation lists that are not powers of two (tests/test_dilations_host.py
+# counts, per list and clip length, the tile-layer pairs of the persistent
+# stack launches whose dilated tap straddles two foreign tiles, or starts
+# inside a later tile):
+#   DIL_A  96 is tile-aligned without being a power of two; 31, 33 and 63 sit
+#          one row off a tile edge            (T = 333 / 301; T = 47: d >= T)
+#   DIL_B  the 16-row geometry                (T = 150)
+#   DIL_C  taps far behind, 513 one off a power of two; receptive field 2605
+#          (T = 1100)
+#   DIL_GEN  the generators' rings: no cursor wraps in phase with another
+DIL_A = [33, 48, 1, 100, 7, 63, 96, 3, 40, 31]
+DIL_B = [17, 24, 5, 40, 15, 50, 9]
+DIL_C = [33, 1000, 48, 1, 100, 7, 63, 96, 3, 700, 513, 40]
+DIL_GEN = [3, 5, 33, 7, 48, 17]
+
 
 def cfg_with(base, **kw):
     c = dict(base)

@@ -2,7 +2,10 @@
 quantization channels, biases, global conditioning, scalar input, residual
 post-processing, L2) against the float64 oracle: loss, every variable's
 gradient, and -- where the reference's generator supports the configuration --
-an incremental-generation trace.   python tools/model_fuzz.py [cases] [seed]
+an incremental-generation trace.
+    python tools/model_fuzz.py [cases] [seed] [any]
+any: every dilation is drawn from 1 .. 600, half of them within +-1 of a
+multiple of 16, instead of a power of two (without it the draws are unchanged).
 KB_BIG=1: 32 channels, filter width 2, dilations up to 512, clips of 200 - 4000
 samples (the persistent stack launches' territory)."""
 import os
@@ -18,6 +21,18 @@ import test_gpu_model as M  # noqa: E402
 O = M.O
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+ANY = len(sys.argv) > 3 and sys.argv[3] == 'any'
+
+
+def any_dilation(rng):
+    """1 .. 600; every second one within +-1 of a multiple of 16 (the tile
+    heights of the stack launches are 16 and 32 rows)"""
+    d = int(rng.integers(1, 601))
+    if rng.random() < 0.5:
+        d = 16 * int(rng.integers(1, 38)) + int(rng.integers(-1, 2))
+    return d
+
+
 bad = 0
 for case in range(n_cases):
     L = int(rng.integers(1, 9))
@@ -53,6 +68,9 @@ for case in range(n_cases):
         cfg.pop('initial_filter_width', None)
         T = int(rng.integers(200, 4000))
         L = len(cfg['dilations'])
+    if ANY:
+        # (extra draws: without `any` the random stream is what it was)
+        cfg['dilations'] = [any_dilation(rng) for _ in range(L)]
     B = cfg['batch_size']
     tag = 'L%d k%d r%d d%d s%d q%d b%d B%d T%d%s%s%s%s' % (
         L, cfg['filter_width'], cfg['residual_channels'], cfg['dilation_channels'],

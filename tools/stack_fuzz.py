@@ -1,7 +1,10 @@
 """Randomised cross-check of the persistent stack launches against the
 per-layer kernels (same model, `stack_fwd` / `stack_bwd` on vs off): random
 dilation lists, clip counts and lengths (ragged tiles, taps longer than the
-clip, single-tile clips).  python tools/stack_fuzz.py [cases] [seed]"""
+clip, single-tile clips).  python tools/stack_fuzz.py [cases] [seed] [any]
+any: every dilation is drawn from 1 .. 600, half of them within +-1 of a
+multiple of 16 (taps that straddle two foreign tiles or start inside a later
+tile), instead of a power of two; without it the draws are unchanged."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,10 +26,20 @@ WaveNetModel.DEFAULT_STACK_VARIANT = stack_variant(
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+ANY = len(sys.argv) > 3 and sys.argv[3] == 'any'
+
+
+def any_dilation(rng):
+    d = int(rng.integers(1, 601))
+    if rng.random() < 0.5:
+        d = 16 * int(rng.integers(1, 38)) + int(rng.integers(-1, 2))
+    return d
+
+
 worst = 0.0
 for case in range(n):
     L = int(rng.integers(1, 12))
-    dil = [int(2 ** rng.integers(0, 10)) for _ in range(L)]
+    dil = [any_dilation(rng) if ANY else int(2 ** rng.integers(0, 10)) for _ in range(L)]
     B = int(rng.integers(1, 6))
     T = int(rng.choice([rng.integers(2, 40), rng.integers(40, 700), rng.integers(700, 4000)]))
     cfg = cfg_with(TINY, batch_size=B, dilations=dil, residual_channels=32, dilation_channels=32,
