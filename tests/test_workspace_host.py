@@ -205,3 +205,61 @@ def test_more_than_64_cached_views_collapse_to_the_owners(hip_lib):
     again = workspace.get(net, 1, 10, False)
     assert again.capacity in (tr.N, fw.N) and again.capacity != again.N
     net._ws = {}
+
+
+# ---- the workspace test's tail enumeration, on models that run nothing ----
+def test_workspace_tails_cover_every_streamed_buffer(hip_lib):
+    """tests/test_gpu_guard_workspace.py on device='cpu' models: every kind
+    takes the path it is there for, every tensor of the owner is either a
+    tail or listed as having none, aliases of one allocation form one tail,
+    and the fills are the ones the buffers' roles ask for."""
+    import test_gpu_guard_workspace as tgw
+    import test_gpu_workspace_sequence as seq
+    from wavenet import WaveNetModel, workspace
+    from util import cfg_with, model_kwargs
+    for name, kind, setup, check in tgw.KINDS:
+        for B in (1, 3):
+            if hasattr(kind, 'cfg'):
+                kw = model_kwargs(cfg_with(kind.cfg, batch_size=B))
+            else:                        # LcUpCtx.model's arguments
+                kw = dict(batch_size=B, dilations=seq.LC_DIL, filter_width=2,
+                          residual_channels=32, dilation_channels=32,
+                          skip_channels=64, quantization_channels=kind.Q,
+                          use_biases=True,
+                          global_condition_channels=kind.gc,
+                          global_condition_cardinality=kind.gc,
+                          local_condition_channels=seq.LC_CH,
+                          local_condition_upsample_scales=seq.LC_SCALES,
+                          local_condition_context=seq.LC_CTX)
+            net = WaveNetModel(device='cpu', **kw)
+            if setup:
+                setup(net)
+            for T in tgw.T_VIEWS:
+                net._ws = {}
+                owner = workspace.get(net, B, 2 * T + 37, True)
+                views = [workspace.get(net, B, T, True),
+                         workspace.get(net, B, T, False)]
+                check(net, views[0], net._step_path(views[0], True))
+                tails, none = tgw._tails(owner, views)
+                seen = set(n for names, _, _ in tails for n in names) | \
+                    set(n for group in none for n in group.split('|'))
+                assert seen == set(tgw._tensors(owner)), (name, B, T)
+                fills = {n: f for names, _, f in tails for n in names}
+                for n in ('X', 'Z', 'h1', 'h2', 'logits', 'loss_parts'):
+                    assert fills[n] == 'float', (name, n)
+                assert fills['q'] == fills['q_tgt'] == 'code'
+                assert fills['stack_flags'] == 'write_only'
+                if name == 'tiny_gc':
+                    assert fills['tilesum'] == fills['tilesum16'] == \
+                        fills['tilesum_buf'] == 'float'
+                    group = [names for names, _, _ in tails
+                             if 'tilesum' in names]
+                    assert group == [('tilesum', 'tilesum16', 'tilesum_buf')]
+                for names, words, _ in tails:
+                    big = max((getattr(owner, n) for n in names),
+                              key=lambda t: t.numel())
+                    used = big.numel() - words.numel()
+                    assert 0 < used < big.numel(), names
+                    for v in views:
+                        t = getattr(v, names[0], None)
+                        assert t is None or t.numel() <= used, names
