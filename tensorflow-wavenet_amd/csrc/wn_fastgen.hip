@@ -19,6 +19,7 @@
 // Reference quirks kept: the generator ignores residual_postproc
 // (model.py:511 vs 436-437); queues start as zeros (net.init_ops).
 #include "wn_common.h"
+#include <type_traits>
 
 #define FG_THREADS 256   // wave 0: chain; waves 1..3: skip / post (192 threads)
 #define FG_SKT 192       // skip threads
@@ -78,20 +79,270 @@ struct FastGen {
 
 // Local conditioning (wn_fastgen_run_lc): the filter|gate bias of step tpos is
 // row tpos of the conditioned-bias ring (wn_fastgen_lc_bias), slot tpos % R,
-// [R][L][64] for the one stream, instead of bias_fg.  A separate
-// instantiation: fastgen_kernel's code is that of the body with LC = false.
+// [R][L][64] for the one stream, instead of bias_fg.  The kernels that have an
+// LC variant (fastgen_kernel, fg_pre_kernel, fg_skip_kernel,
+// fg_persist_kernel) are templates on their argument struct, the plain one or
+// the one that wraps it with the ring: fg_base() gives the plain struct of
+// either, and only `if constexpr (LC)` branches name the ring.  The plain
+// structs keep their layout, and the plain instantiations the machine code
+// they had before LC existed (profiles/fastgen_disasm_templates.txt).
 struct FastGenLc {
   FastGen g;
   const float* ring;
   int R;
 };
+__device__ __forceinline__ const FastGen& fg_base(const FastGen& g) { return g; }
+__device__ __forceinline__ const FastGen& fg_base(const FastGenLc& a) { return a.g; }
 
-#define FG_LC 0
-#include "wn_fastgen_single.inc"
-#undef FG_LC
-#define FG_LC 1
-#include "wn_fastgen_single.inc"
-#undef FG_LC
+template <typename Arg>   // FastGen | FastGenLc
+__global__ __launch_bounds__(FG_THREADS, 1) void fastgen_kernel(Arg arg) {
+  constexpr bool LC = std::is_same<Arg, FastGenLc>::value;
+  // (the LC base by its member, not by fg_base(arg): behind the call the LC
+  // instantiation's scalar code comes out three instructions longer, and the
+  // plain one 43 shorter without it -- neither the machine code they had)
+  const FastGen* gp;
+  if constexpr (LC) gp = &arg.g; else gp = &fg_base(arg);
+  const FastGen& g = *gp;
+  __shared__ __attribute__((aligned(16))) float wring[2][FG_CW];
+  __shared__ float zbuf[2][32];
+  __shared__ float hbuf[FG_MAXS];     // relu(total)
+  __shared__ float h2buf[FG_MAXS];    // relu(conv1)
+  __shared__ float part[FG_MAXS];     // post2 partial sums
+  __shared__ double pd[FG_MAXQ];
+  __shared__ int s_code;
+  __shared__ int pos[FG_MAXL];        // ring cursor of every layer
+  __shared__ int sdil[FG_MAXL], roff[FG_MAXL];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int S = g.S, Q = g.Q, L = g.L;
+  const int st = tid - 64;            // loader-thread index 0..191 (waves 1..3)
+
+  const int steps_done = g.cursors[0];
+  int prev_code = g.cursors[1];
+  if (tid == 0) s_code = g.samples[0];
+  for (int l = tid; l < L; l += FG_THREADS) {
+    sdil[l] = g.dil[l];
+    pos[l] = steps_done % g.dil[l];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int off = 0;
+    for (int l = 0; l < L; ++l) { roff[l] = off; off += sdil[l]; }
+  }
+  __syncthreads();
+
+  for (int step = 0; step < g.n_steps; ++step) {
+    const int code = s_code;
+    const long tpos = (long)steps_done + step;
+    // ---------------- loaders: chain-weight ring + skip columns ------------
+    f32x4 cw[FG_LDR];
+    auto cw_load = [&](int l) {        // global -> registers
+      const f32x4* src = reinterpret_cast<const f32x4*>(
+          g.layer0 + (long)l * g.layer_stride);
+#pragma unroll
+      for (int k = 0; k < FG_LDR; ++k) {
+        const int i4 = st + FG_SKT * k;
+        if (i4 < FG_CW4) cw[k] = src[i4];
+      }
+    };
+    auto cw_store = [&](int buf) {     // registers -> LDS ring
+      f32x4* dst = reinterpret_cast<f32x4*>(wring[buf]);
+#pragma unroll
+      for (int k = 0; k < FG_LDR; ++k) {
+        const int i4 = st + FG_SKT * k;
+        if (i4 < FG_CW4) dst[i4] = cw[k];
+      }
+    };
+    float acc[FG_SKO], sw[FG_SKO][32];
+    bool son[FG_SKO];
+#pragma unroll
+    for (int o = 0; o < FG_SKO; ++o) {
+      acc[o] = 0.f;
+      son[o] = wave >= 1 && st + FG_SKT * o < S;
+    }
+    auto skip_load = [&](int l) {
+      const float* ws = g.skip_w + (long)l * 32 * S + st;
+#pragma unroll
+      for (int o = 0; o < FG_SKO; ++o)
+        if (son[o]) {
+#pragma unroll
+          for (int k = 0; k < 32; ++k) sw[o][k] = ws[(long)k * S + FG_SKT * o];
+        }
+    };
+    auto skip_fma = [&](const float* zl) {
+#pragma unroll
+      for (int o = 0; o < FG_SKO; ++o)
+        if (son[o]) {
+#pragma unroll
+          for (int k = 0; k < 32; ++k) acc[o] = fmaf(zl[k], sw[o][k], acc[o]);
+        }
+    };
+    // ---------------- chain state (wave 0) ---------------------------------
+    float x = 0.f;                     // residual stream on lanes < 32
+    float stv = 0.f, bias = 0.f, bdv = 0.f;  // prefetched for the coming layer
+    auto chain_prefetch = [&](int l) {
+      if constexpr (LC)
+        bias = arg.ring[((tpos % arg.R) * L + l) * 64 + lane];
+      else
+        bias = g.bias_fg ? g.bias_fg[l * 64 + lane] : 0.f;
+      bdv = g.use_dense_bias
+                ? g.layer0[(long)l * g.layer_stride + LAYER_OFF_BD + (lane & 31)]
+                : 0.f;
+      stv = lane < 32 ? g.state[((long)roff[l] + pos[l]) * 32 + lane] : 0.f;
+    };
+    // prologue: layer 0 weights into ring[0]
+    if (wave >= 1) {
+      cw_load(0);
+      cw_store(0);
+      if (L > 1) cw_load(1);
+      skip_load(0);
+    } else {
+      chain_prefetch(0);
+      if (lane < 32) {
+        float v = 0.f;
+        if (prev_code >= 0 && prev_code < Q) v = g.causal[(long)prev_code * 32 + lane];
+        if (code >= 0 && code < Q) v += g.causal[((long)Q + code) * 32 + lane];
+        x = v;
+      }
+    }
+    __syncthreads();
+    for (int l = 0; l <= L; ++l) {
+      if (wave == 0) {
+        if (l < L) {
+          const float* wl = wring[l & 1];
+          const float cur_st = stv, cur_bias = bias, cur_bd = bdv;
+          if (g.push && lane < 32)       // enqueue x_l[t] (after the dequeue)
+            g.state[((long)roff[l] + pos[l]) * 32 + lane] = x;
+          if (l + 1 < L) chain_prefetch(l + 1);
+          const float* wcol = wl + (lane < 32 ? 0 : 2048) + (lane & 31);
+          float a = cur_bias;
+#pragma unroll
+          for (int k = 0; k < 32; ++k) {
+            a = fmaf(readlane_f(cur_st, k), wcol[k * 32], a);      // W[0]
+            a = fmaf(readlane_f(x, k), wcol[1024 + k * 32], a);    // W[1]
+          }
+          const float gate = __shfl(a, (lane & 31) + 32);
+          const float z = wn_tanh(a) * wn_sigmoid(gate);  // valid on lanes < 32
+          if (lane < 32) zbuf[l & 1][lane] = z;
+          if (l + 1 < L) {
+            float dsum = cur_bd;
+            const float* wd = wl + 4096 + (lane & 31);
+#pragma unroll
+            for (int k = 0; k < 32; ++k) dsum = fmaf(readlane_f(z, k), wd[k * 32], dsum);
+            if (lane < 32) x += dsum;
+          }
+        }
+      } else {
+        // ring slot (l+1)&1 was last read in iteration l-1: free to refill
+        if (l + 1 < L) cw_store((l + 1) & 1);
+        if (l + 2 < L) cw_load(l + 2);
+        if (l >= 1) skip_fma(zbuf[(l - 1) & 1]);
+        if (l >= 1 && l < L) skip_load(l);
+      }
+      // raw barrier: only LDS traffic is drained.  __syncthreads() would also
+      // wait vmcnt(0), i.e. for the weight loads just issued for the NEXT
+      // layers -- exposing a full L2 / Infinity-Cache round trip per layer.
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+    // advance the ring cursors (after every wave is done with this step)
+    if (g.push) {
+      for (int l = tid; l < L; l += FG_THREADS) {
+        const int p = pos[l] + 1;
+        pos[l] = p == sdil[l] ? 0 : p;
+      }
+    }
+    // ---------------- post-processing (model.py:505-514) -------------------
+    if (wave >= 1) {
+#pragma unroll
+      for (int o = 0; o < FG_SKO; ++o)
+        if (son[o]) {
+          const int sc = st + FG_SKT * o;
+          hbuf[sc] = fmaxf(acc[o] + (g.skip_bsum ? g.skip_bsum[sc] : 0.f), 0.f);
+        }
+    }
+    __syncthreads();
+    if (wave >= 1) {
+      for (int s = st; s < S; s += FG_SKT) {
+        float c0 = g.post1_b ? g.post1_b[s] : 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
+        const float* w = g.post1_w + s;
+        int k = 0;
+        for (; k + 64 <= S; k += 64) {
+          float wv[64];
+#pragma unroll
+          for (int u = 0; u < 64; ++u) wv[u] = w[(long)(k + u) * S];
+#pragma unroll
+          for (int u = 0; u < 64; u += 4) {
+            c0 = fmaf(hbuf[k + u], wv[u], c0);
+            c1 = fmaf(hbuf[k + u + 1], wv[u + 1], c1);
+            c2 = fmaf(hbuf[k + u + 2], wv[u + 2], c2);
+            c3 = fmaf(hbuf[k + u + 3], wv[u + 3], c3);
+          }
+        }
+        for (; k < S; ++k) c0 = fmaf(hbuf[k], w[(long)k * S], c0);
+        h2buf[s] = fmaxf((c0 + c1) + (c2 + c3), 0.f);
+      }
+    }
+    __syncthreads();
+    // logits: thread (q, part) sums a k-range; parts = 192 / Q
+    {
+      int parts = FG_SKT / Q;
+      if (parts < 1) parts = 1;
+      if (wave >= 1) {
+        for (int o = st; o < Q * parts; o += FG_SKT) {
+          const int q = o % Q, p = o / Q;
+          const int k0 = (int)((long)S * p / parts), k1 = (int)((long)S * (p + 1) / parts);
+          float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
+          const float* w = g.post2_w + q;
+          int k = k0;
+          for (; k + 64 <= k1; k += 64) {
+            float wv[64];
+#pragma unroll
+            for (int u = 0; u < 64; ++u) wv[u] = w[(long)(k + u) * Q];
+#pragma unroll
+            for (int u = 0; u < 64; u += 4) {
+              c0 = fmaf(h2buf[k + u], wv[u], c0);
+              c1 = fmaf(h2buf[k + u + 1], wv[u + 1], c1);
+              c2 = fmaf(h2buf[k + u + 2], wv[u + 2], c2);
+              c3 = fmaf(h2buf[k + u + 3], wv[u + 3], c3);
+            }
+          }
+          for (; k < k1; ++k) c0 = fmaf(h2buf[k], w[(long)k * Q], c0);
+          part[o] = (c0 + c1) + (c2 + c3);
+        }
+      }
+      __syncthreads();
+      for (int q = tid; q < Q; q += FG_THREADS) {
+        float c = g.post2_b ? g.post2_b[q] : 0.f;
+        for (int p = 0; p < parts; ++p) c += part[p * Q + q];
+        pd[q] = (double)c;
+      }
+      __syncthreads();
+    }
+    // softmax in float64, optional temperature, draw (wn_common.h)
+    if (wave == 0) {
+      const bool want_p = g.proba_out && (step % g.proba_every == 0);
+      wave_softmax_f64(pd, Q, lane, want_p ? g.proba_out + (long)(step / g.proba_every) * Q : nullptr);
+    }
+    __syncthreads();
+    if (step + 1 >= g.n_given) {
+      if (wave == 0) {
+        const int best = wave_draw_f64(pd, Q, lane, g.temperature, g.top_k, g.top_p, g.seed, (uint64_t)tpos);
+        if (lane == 0) {
+          g.samples[step + 1] = best;
+          s_code = best;
+        }
+      }
+    } else if (tid == 0) {
+      s_code = g.samples[step + 1];
+    }
+    prev_code = code;
+    __syncthreads();
+  }
+  if (tid == 0 && g.push) {
+    g.cursors[0] = steps_done + g.n_steps;
+    g.cursors[1] = prev_code;
+  }
+}
 
 // ===========================================================================
 // Multi-CU fast generation: one generated sample = four small kernels on the
@@ -189,9 +440,19 @@ __global__ void fg_pack_kernel(const float* __restrict__ layer0, long layer_stri
 // step t' = cursors[0] + ahead: the entry the queue of layer l hands out at
 // that step (model.py:335-338 `state`), which is at least one step old.
 // (LC: the bias is row tpos of the conditioned-bias ring [R][L][64])
-template <bool LC>
-__device__ __forceinline__ void fg_pre_layer(const FgStep& g, const float* ring, int R, int l,
-                                             int ahead, float* lds /* >= 32 + 256 floats */) {
+struct FgStepLc {
+  FgStep g;
+  const float* ring;     // [R][L][64] conditioned filter|gate bias, slot = step % R
+  int R;
+};
+__device__ __forceinline__ const FgStep& fg_base(const FgStep& g) { return g; }
+__device__ __forceinline__ const FgStep& fg_base(const FgStepLc& a) { return a.g; }
+
+// g: the caller's fg_base(arg)
+template <typename Arg>   // FgStep | FgStepLc
+__device__ __forceinline__ void fg_pre_layer(const FgStep& g, const Arg& arg, int l, int ahead,
+                                             float* lds /* >= 32 + 256 floats */) {
+  constexpr bool LC = std::is_same<Arg, FgStepLc>::value;
   const int tid = threadIdx.x;                 // 256 threads
   const int tpos = g.cursors[0] + ahead;
   int roff = 0;
@@ -212,28 +473,18 @@ __device__ __forceinline__ void fg_pre_layer(const FgStep& g, const float* ring,
   __syncthreads();
   if (tid < 64) {
     float bias;
-    if (LC)
-      bias = ring[((long)(tpos % R) * g.L + l) * 64 + tid];
+    if constexpr (LC)
+      bias = arg.ring[((long)(tpos % arg.R) * g.L + l) * 64 + tid];
     else
       bias = g.bias_fg ? g.bias_fg[l * 64 + tid] : 0.f;
     g.pre[l * 64 + tid] = bias + ((red[tid] + red[64 + tid]) + (red[128 + tid] + red[192 + tid]));
   }
 }
 
-struct FgStepLc {
-  FgStep g;
-  const float* ring;     // [R][L][64] conditioned filter|gate bias, slot = step % R
-  int R;
-};
-
-__global__ __launch_bounds__(256) void fg_pre_kernel(FgStep g, int ahead) {
+template <typename Arg>   // FgStep | FgStepLc
+__global__ __launch_bounds__(256) void fg_pre_kernel(Arg arg, int ahead) {
   __shared__ float lds[32 + 256];
-  fg_pre_layer<false>(g, nullptr, 0, blockIdx.x, ahead, lds);
-}
-
-__global__ __launch_bounds__(256) void fg_pre_lc_kernel(FgStepLc a, int ahead) {
-  __shared__ float lds[32 + 256];
-  fg_pre_layer<true>(a.g, a.ring, a.R, blockIdx.x, ahead, lds);
+  fg_pre_layer(fg_base(arg), arg, blockIdx.x, ahead, lds);
 }
 
 __device__ __forceinline__ int fg_draw_wave(const FgStep& g, double* pd, int lane, int steps_done);
@@ -467,14 +718,28 @@ __device__ __forceinline__ float fg_mv_reduce(float (*red)[FGM_OUTS], int o) {
 
 // h1[s] = relu(sum_l z_l . Ws_l[:, s] + sum_l bs_l[s])   (model.py:505-509)
 // (+ g.L more workgroups: the past-tap pre-activations of the NEXT step)
-#define FG_PART 0
-#define FG_LC 0
-#include "wn_fastgen_step.inc"
-#undef FG_LC
-#define FG_LC 1
-#include "wn_fastgen_step.inc"
-#undef FG_LC
-#undef FG_PART
+// (the base struct by value, handed on to fg_pre_layer: read through a
+// reference both instantiations come out two instructions longer)
+template <typename Arg>   // FgStep | FgStepLc
+__global__ __launch_bounds__(256) void fg_skip_kernel(Arg arg) {
+  const FgStep g = fg_base(arg);
+  __shared__ float zs[FG_MAXL * 32];
+  __shared__ float red[FGM_PARTS][FGM_OUTS];
+  const int nskip = (g.S + FGM_OUTS - 1) / FGM_OUTS;
+  if ((int)blockIdx.x >= nskip) {        // workgroup-uniform
+    fg_pre_layer(g, arg, blockIdx.x - nskip, 1, zs);
+    return;
+  }
+  const int tid = threadIdx.x, o = tid & (FGM_OUTS - 1), part = tid / FGM_OUTS;
+  const int s = blockIdx.x * FGM_OUTS + o;
+  const int KK = g.L * 32;
+  for (int i = tid; i < KK; i += 256) zs[i] = g.z_all[i];
+  __syncthreads();
+  red[part][o] = s < g.S ? fg_mv_partial<50>(zs, KK, g.skip_w, g.S, s, part) : 0.f;
+  __syncthreads();
+  if (part == 0 && s < g.S)
+    g.h1[s] = fmaxf((g.skip_bsum ? g.skip_bsum[s] : 0.f) + fg_mv_reduce(red, o), 0.f);
+}
 
 // h2[s] = relu(sum_k h1[k] W1[k][s] + b1[s])
 __global__ __launch_bounds__(256) void fg_post1_kernel(FgStep g) {
@@ -1114,14 +1379,264 @@ struct FgPersistLc {
   int R;
 };
 
-#define FG_PART 1
-#define FG_LC 0
-#include "wn_fastgen_step.inc"
-#undef FG_LC
-#define FG_LC 1
-#include "wn_fastgen_step.inc"
-#undef FG_LC
-#undef FG_PART
+__device__ __forceinline__ const FgPersist& fg_base(const FgPersist& a) { return a; }
+__device__ __forceinline__ const FgPersist& fg_base(const FgPersistLc& a) { return a.a; }
+
+// (LC differs in the filter|gate bias of the helper waves' past-tap
+// pre-activations only)
+template <typename Arg>   // FgPersist | FgPersistLc
+__global__ __launch_bounds__(FGP_THREADS) void fg_persist_kernel(Arg arg) {
+  constexpr bool LC = std::is_same<Arg, FgPersistLc>::value;
+  const FgPersist& a = fg_base(arg);
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const FgStep& g = a.g;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int L = g.L, S = g.S, Q = g.Q, nseg = a.nseg, n_steps = a.n_steps;
+  const int nsk = (S + 15) / 16, nlg = (Q + 15) / 16;
+  const int base = g.ctl[FGCTL_BASE];
+  unsigned* sync = a.sync;
+  // hand-over words: z [L][32] | h1 [S] | h2 [S] | logits [Q] | x [nseg][32] | x0 [32]
+  fgp_ll_t* zll = a.ll;
+  fgp_ll_t* h1ll = zll + L * 32;
+  fgp_ll_t* h2ll = h1ll + S;
+  fgp_ll_t* lgll = h2ll + S;
+  fgp_ll_t* xll = lgll + Q;
+  fgp_ll_t* x0ll = xll + FGP_MAXSEG * 32;            // [32] the causal layer's output for the next step
+  bool dead = false;
+  // Role of this workgroup.  Workgroups go to the eight XCDs round-robin
+  // (blockIdx % 8) and a hand-over word between two workgroups of ONE XCD costs
+  // 0.59 - 0.64 us, between two XCDs 0.76 (tools/ubench/ll_hop.hip): the serial
+  // chain's hand-overs -- draw -> segment 0 -> ... -> last segment -- stay on
+  // one XCD: those nseg + 1 roles take the blocks 0, 8, 16, ..., the mat-vec
+  // roles (skip | post1 | logits) the rest in order.  Roles are numbered
+  // chain segments, skip, post1, logits, draw.
+  int role = fgp_role_of_block((int)blockIdx.x, (int)gridDim.x, nseg);
+#ifdef FGP_STAMPS
+#define PSTAMP(slot) if (a.dbg && (tid & 63) == 0) a.dbg[(size_t)(slot)] = __builtin_amdgcn_s_memrealtime()
+#else
+#define PSTAMP(slot)
+#endif
+
+  if (role < nseg) {
+    // ------------------------------------------------------------ chain segment
+    const int seg = role;
+    const int l0 = __builtin_amdgcn_readfirstlane((int)((long)seg * L / nseg));
+    const int l1 = (int)((long)(seg + 1) * L / nseg);
+    const int nl = __builtin_amdgcn_readfirstlane(l1 - l0);
+    float* wres = lds;                                 // [nl][FGP_BLK]: weights | {pre, row, bd, -}
+    int* meta = reinterpret_cast<int*>(wres + (size_t)nl * FGP_BLK);   // [nl] ring offset (rows), [nl] dilation
+    int* flags = meta + 2 * FGP_SEGL;                  // [0] pre ready for step, [1] chain done with step
+    // resident weights in LANE order: chunk c of the chain lane's row at float4
+    // [c][lane] (filter | gate rows: c < 8; dense rows: [8 + cc][lane], lane =
+    // 32 (c >> 2) + n), so a layer's reads are one lane address plus
+    // immediates and conflict-free (the ring-slot image is [matrix][n][chunk ^ (n & 7)])
+    for (int i = tid; i < nl * FGC_CW / 4; i += FGP_THREADS) {
+      const int ll = i / (FGC_CW / 4), q = i % (FGC_CW / 4);
+      const int m = q >> 8, n = (q >> 3) & 31, c = (q & 7) ^ (n & 7);
+      const int dst = m < 2 ? c * 64 + m * 32 + n : 512 + (c & 3) * 64 + (c >> 2) * 32 + n;
+      reinterpret_cast<f32x4*>(wres)[ll * (FGP_BLK / 4) + dst] =
+          reinterpret_cast<const f32x4*>(g.cw_img + (size_t)l0 * FGC_CW)[i];
+    }
+    if (tid < nl) {
+      int ro = 0;
+      for (int q = 0; q < l0 + tid; ++q) ro += g.dil[q];
+      meta[tid] = ro;
+      meta[FGP_SEGL + tid] = g.dil[l0 + tid];
+    }
+    __syncthreads();
+    for (int i = tid; i < nl * 64; i += FGP_THREADS) {
+      const int ll = i >> 6, ln = i & 63;
+      f32x4 ms;
+      ms[0] = g.pre[(size_t)l0 * 64 + i];
+      ms[1] = __int_as_float((meta[ll] + base % meta[FGP_SEGL + ll]) * 32);
+      ms[2] = g.use_dense_bias
+                  ? g.layer0[(size_t)(l0 + ll) * g.layer_stride + LAYER_OFF_BD + (ln & 31)] : 0.f;
+      ms[3] = 0.f;
+      reinterpret_cast<f32x4*>(wres)[ll * (FGP_BLK / 4) + 768 + ln] = ms;
+    }
+    if (tid == 0) { flags[0] = 1; flags[1] = 0; flags[2] = 0; flags[3] = 0; }
+    __syncthreads();
+    const int nn = lane & 31;
+    if (wave == 0) {
+      // ---- the serial chain of this segment (no workgroup barrier, weights
+      // resident): fgp_chain_layers
+      const int prev_code = g.cursors[1];
+      fgp_ll_t* zrow = zll + l0 * 32 + nn;
+      fgp_ll_t* xo = seg + 1 < nseg ? xll + seg * 32 : nullptr;
+      for (int i = 0; i < n_steps; ++i) {
+        const unsigned step = (unsigned)(i + 1);
+        // this step's past-tap pre-activations are in LDS (helper waves): the
+        // first layer's operands are requested before x is waited for
+        while (!dead && __hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < i + 1)
+          __builtin_amdgcn_s_sleep(1);
+        FgpLW wa;
+        fgp_lw_load(wa, wres, 0, lane);
+        float x = 0.f;
+        if (seg == 0) {
+          // (x lives in EVERY lane: channel lane & 31)
+          if (i > 0) {
+            // the draw workgroup's x0 of this step (fg_draw_wg256)
+            x = fgp_get(x0ll + nn, (unsigned)i, sync, dead);
+          } else {
+            const int code = g.samples[0];
+            float v = 0.f;
+            if (prev_code >= 0 && prev_code < Q) v = g.causal[(long)prev_code * 32 + nn];
+            if (code >= 0 && code < Q) v += g.causal[((long)Q + code) * 32 + nn];
+            x = v;
+          }
+          PSTAMP(i * 16 + 0);
+        } else {
+          x = fgp_get(xll + (seg - 1) * 32 + nn, step, sync, dead);
+        }
+        PSTAMP(i * 16 + 1 + seg);
+        if (nl == 10) x = fgp_chain_layers<10>(x, wres, wa, nl, l0, L, g.state, zrow, xo, step, lane);
+        else x = fgp_chain_layers<0>(x, wres, wa, nl, l0, L, g.state, zrow, xo, step, lane);
+        PSTAMP(i * 16 + 6 + seg);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0)
+          __hip_atomic_store(flags + 1, i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    } else {
+      // ---- helper waves: the NEXT step's past-tap pre-activations of this
+      // segment's layers (model.py:335-338, the `state` half of the conv):
+      // pre[l][n] = bias_fg[l][n] + sum_k x_l[t + 1 - d_l][k] * W[0][k][n],
+      // one wave per layer, lane = output n (filter | gate); the queue entry
+      // is read with device-scope loads after the chain wave's flag (its
+      // write-through stores were acknowledged before it set the flag)
+      const int hw = wave - 1;                          // 0..3
+      for (int i = 0; i + 1 < n_steps; ++i) {
+        while (!dead && __hip_atomic_load(flags + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < i + 1) {
+          __builtin_amdgcn_s_sleep(4);
+          if (__hip_atomic_load(sync + FGP_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) dead = true;
+        }
+        const int tpos = base + i + 1;
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int ll = hw; ll < nl; ll += 4) {
+          const int l = l0 + ll, d = meta[FGP_SEGL + ll];
+          const float xv = lane < 32 ? fgp_ld(g.state + ((long)meta[ll] + tpos % d) * 32 + lane) : 0.f;
+          const float* W = g.layer0 + (long)l * g.layer_stride + (lane < 32 ? 0 : 2 * 1024) + (lane & 31);
+          float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            p0 = fmaf(__shfl(xv, k), W[k * 32], p0);
+            p1 = fmaf(__shfl(xv, 8 + k), W[(8 + k) * 32], p1);
+            p2 = fmaf(__shfl(xv, 16 + k), W[(16 + k) * 32], p2);
+            p3 = fmaf(__shfl(xv, 24 + k), W[(24 + k) * 32], p3);
+          }
+          if constexpr (LC) {
+            const float bias = arg.ring[((long)(tpos % arg.R) * L + l) * 64 + lane];
+            acc[(ll - hw) >> 2] = bias + ((p0 + p1) + (p2 + p3));
+          } else {
+            acc[(ll - hw) >> 2] = (g.bias_fg ? g.bias_fg[l * 64 + lane] : 0.f) + ((p0 + p1) + (p2 + p3));
+          }
+        }
+        // (the chain wave is past this segment's layers of step i: the
+        // {pre, row} words of the layers' blocks are free)
+        for (int ll = hw; ll < nl; ll += 4) {
+          float* ms = wres + (size_t)ll * FGP_BLK + 3072 + lane * 4;
+          ms[0] = acc[(ll - hw) >> 2];
+          ms[1] = __int_as_float((meta[ll] + tpos % meta[FGP_SEGL + ll]) * 32);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // four helper waves: the last one to finish raises the step
+        if (lane == 0) {
+          const int old = __hip_atomic_fetch_add(flags + 2, 1, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (old == 3) {
+            __hip_atomic_store(flags + 2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store(flags, i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+        }
+      }
+    }
+    return;
+  }
+  role -= nseg;
+  if (tid >= 256) return;          // the tail roles are 256-thread workgroups
+  float* in_s = lds;               // staged input vector
+  const int o = tid & 15, part = tid >> 4;
+  if (role < nsk) {
+    // ------------------------------------------------------------------- skip
+    const int KK = L * 32, col0 = role * 16;
+    float* w_s = lds + ((KK + 3) & ~3);               // [KK][16]
+    float* red = w_s + (size_t)KK * 16;               // [16][16]
+    for (int i = tid; i < KK * 16; i += 256) {
+      const int k = i >> 4, c = i & 15;
+      w_s[i] = col0 + c < S ? g.skip_w[(size_t)k * S + col0 + c] : 0.f;
+    }
+    __syncthreads();
+    for (int i = 0; i < n_steps; ++i) {
+      const unsigned step = (unsigned)(i + 1);
+      float accv = 0.f;
+      for (int sg = 0; sg < nseg; ++sg) {
+        const int l0 = (int)((long)sg * L / nseg), l1 = (int)((long)(sg + 1) * L / nseg);
+        const int n = (l1 - l0) * 32;
+        fgp_get2(in_s + l0 * 32, zll + l0 * 32, tid, n, step, sync, dead);
+        __syncthreads();
+        accv += fgp_mv16(in_s + l0 * 32, w_s + (size_t)l0 * 32 * 16, n, o, part, 16);
+      }
+      red[part * 16 + o] = accv;
+      __syncthreads();
+      if (part == 0) {
+        float t = 0.f;
+#pragma unroll
+        for (int p = 0; p < 16; ++p) t += red[p * 16 + o];
+        if (col0 + o < S)
+          fgp_put(h1ll + col0 + o, fmaxf((g.skip_bsum ? g.skip_bsum[col0 + o] : 0.f) + t, 0.f), step);
+      }
+      if (role == 0) { PSTAMP(i * 16 + 11); }
+      __syncthreads();             // (red is rewritten in the next step)
+    }
+    return;
+  }
+  role -= nsk;
+  if (role < nsk + nlg) {
+    // ------------------------------------------------------- post1 / logits
+    const bool lg = role >= nsk;
+    fgp_post_role(lg ? g.post2_w : g.post1_w, lg ? g.post2_b : g.post1_b,
+                  (lg ? role - nsk : role) * 16, lg ? Q : S, S, lg, lg ? h2ll : h1ll,
+                  lg ? lgll : h2ll, n_steps, lds, sync, dead, tid,
+                  a.dbg && role == 0 ? a.dbg + 12 : (a.dbg && role == nsk ? a.dbg + 13 : nullptr));
+    return;
+  }
+  // ---------------------------------------------------------------------- draw
+  // (256 threads: one logit per thread for Q <= 256)
+  float* lgs = lds;                                             // [Q] the step's logits
+  double* dpart = reinterpret_cast<double*>(lds + ((Q + 3) & ~3));  // 16 doubles: per-wave partials
+  int* nxt = reinterpret_cast<int*>(dpart + 16);                 // [2] the code drawn at step parity
+  float* ctab = reinterpret_cast<float*>(nxt + 8);               // [2][Q][32] the causal layer's filter
+  double* wts = reinterpret_cast<double*>(ctab + 2 * Q * 32);    // [Q] the truncating draw's weights
+  for (int i = tid; i < 2 * Q * 32; i += 256) ctab[i] = g.causal[i];
+  const FgDrawCtl dc = fg_draw_ctl(g);
+  __syncthreads();
+  for (int i = 0; i < n_steps; ++i) {
+    const unsigned step = (unsigned)(i + 1);
+    fgp_get2(lgs, lgll, tid, Q, step, sync, dead);
+    PSTAMP(i * 16 + 14);
+    __syncthreads();
+    // the code this step consumes (drawn / given one step ago: written behind
+    // the previous step's last barrier, read behind this one)
+    const int cur_code = i == 0 ? g.samples[0] : nxt[i & 1];
+    // (dpart[] is rewritten a step later only after this barrier, which every
+    // wave reaches after its last read of the step before)
+    // the drawing thread publishes the code of step i + 1 for segment 0
+    if (Q <= 256) fg_draw_wg256<1>(g, dc, lgs, dpart, wts, nxt, x0ll, ctab, cur_code, step, i + 1 < n_steps, tid, base + i);
+    else fg_draw_wg256<2>(g, dc, lgs, dpart, wts, nxt, x0ll, ctab, cur_code, step, i + 1 < n_steps, tid, base + i);
+    PSTAMP(i * 16 + 15);
+  }
+  __syncthreads();
+  // the code the last step consumed (this CU's L1 may hold an older copy of the
+  // samples line: the draws were kept in LDS)
+  const int cur_code = n_steps >= 2 ? nxt[(n_steps - 1) & 1] : g.samples[0];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // cursors as wn_fastgen_finish leaves them: {steps done, the last code consumed, nothing pending}
+  if (tid == 0) {
+    g.cursors[0] = base + n_steps;
+    g.cursors[1] = cur_code;
+    g.cursors[2] = 0;
+  }
+#undef PSTAMP
+}
 
 // ===========================================================================
 // Wide fast generation: the same incremental generator for MORE than 32
@@ -1659,10 +2174,10 @@ static int fg_run(bool lc, const float* lc_ring, int lc_R, int lc_stride,
   if (!push && n_steps != 1) return WN_ERR_BAD_SHAPE;
   if (lc) {
     const FastGenLc a = {g, lc_ring, lc_R};
-    hipLaunchKernelGGL(fastgen_lc_kernel, dim3(1), dim3(FG_THREADS), 0,
+    hipLaunchKernelGGL(fastgen_kernel<FastGenLc>, dim3(1), dim3(FG_THREADS), 0,
                        (hipStream_t)stream, a);
   } else {
-    hipLaunchKernelGGL(fastgen_kernel, dim3(1), dim3(FG_THREADS), 0,
+    hipLaunchKernelGGL(fastgen_kernel<FastGen>, dim3(1), dim3(FG_THREADS), 0,
                        (hipStream_t)stream, g);
   }
   return wn_check_launch();
@@ -1910,9 +2425,9 @@ static int fg_step(bool lc, const float* lc_ring, int lc_R, int lc_stride,
   hipLaunchKernelGGL(fg_chain_kernel, dim3(1), dim3(FGC_THREADS), 0, s, g);
   if (lc) {
     const FgStepLc a = {g, lc_ring, lc_R};
-    hipLaunchKernelGGL(fg_skip_lc_kernel, dim3(wgs + L), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(fg_skip_kernel<FgStepLc>, dim3(wgs + L), dim3(256), 0, s, a);
   } else {
-    hipLaunchKernelGGL(fg_skip_kernel, dim3(wgs + L), dim3(256), 0, s, g);
+    hipLaunchKernelGGL(fg_skip_kernel<FgStep>, dim3(wgs + L), dim3(256), 0, s, g);
   }
   hipLaunchKernelGGL(fg_post1_kernel, dim3(wgs), dim3(256), 0, s, g);
   hipLaunchKernelGGL(fg_logits_kernel, dim3((Q + FGM_OUTS - 1) / FGM_OUTS), dim3(256), 0, s, g);
@@ -2047,7 +2562,8 @@ static int fg_persist(bool lc, const float* lc_ring, int lc_R, int lc_stride,
   const size_t bytes = fl * 4;
   if (bytes > 160 * 1024 - 512) return WN_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  const void* kf = lc ? (const void*)fg_persist_lc_kernel : (const void*)fg_persist_kernel;
+  const void* kf = lc ? (const void*)fg_persist_kernel<FgPersistLc>
+                      : (const void*)fg_persist_kernel<FgPersist>;
   if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
     return WN_ERR_LAUNCH;
   // every workgroup must be resident at once: ask the runtime how many of THIS
@@ -2121,9 +2637,9 @@ static int fg_pre(bool lc, const float* lc_ring, int lc_R, int lc_stride,
   g.cursors = const_cast<int32_t*>(cursors); g.pre = pre;
   if (lc) {
     const FgStepLc a = {g, lc_ring, lc_R};
-    hipLaunchKernelGGL(fg_pre_lc_kernel, dim3(L), dim3(256), 0, (hipStream_t)stream, a, 0);
+    hipLaunchKernelGGL(fg_pre_kernel<FgStepLc>, dim3(L), dim3(256), 0, (hipStream_t)stream, a, 0);
   } else {
-    hipLaunchKernelGGL(fg_pre_kernel, dim3(L), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(fg_pre_kernel<FgStep>, dim3(L), dim3(256), 0, (hipStream_t)stream,
                        g, 0);
   }
   return wn_check_launch();

@@ -118,11 +118,9 @@ class _LcRing(object):
                           LC_RING_BYTES if B > 1 else LC_RING_BYTES_ONE)
         self.R = self.C + 1
         self.ring = _buf(net, g, 'lc_ring', self.R * row, torch.float32)
+        self.args = (_lib.ptr(self.ring), self.R, self.rstride)
         self.p0 = int(g['steps'])
         self.plan = lc_plan(n_steps, self.C)
-
-    def args(self):
-        return (_lib.ptr(self.ring), self.R, self.rstride)
 
     def fill(self, a, n):
         net = self.net
@@ -147,10 +145,14 @@ def _check_temperature(temperature):
 _NO_TRUNC = (0, 0.0)
 
 
-def _trunc_entry(name, trunc):
-    # (entry point, its arguments in front of the stream)
-    return (name + '_trunc', (int(trunc[0]), float(trunc[1]))) \
-        if trunc != _NO_TRUNC else (name, ())
+def _entry(name, lc=(), trunc=_NO_TRUNC, q=()):
+    """(entry point, its arguments in front of the stream): `name` with the
+    ABI's suffix for every argument group that is there (lc: a ring's args,
+    trunc with one of the two on, q: the restarted streams' origins) and the
+    groups in the ABI's order."""
+    t = (int(trunc[0]), float(trunc[1])) if trunc != _NO_TRUNC else ()
+    return (name + '_lc' * bool(lc) + '_trunc' * bool(t) + '_q' * bool(q),
+            tuple(lc) + t + tuple(q))
 
 
 def _buf(net, g, name, n, dtype):
@@ -360,127 +362,105 @@ def run(net, temperature, seed, global_condition, samples_io, n_given,
     w, bias, _ = _weights(net, g, global_condition, 1)
     head = w + (bias, _lib.ptr(g['dil']))
     queues = (_lib.ptr(g['state']), _lib.ptr(g['cursors']))
-    sd = int(seed) & (2**64 - 1)
-    ub = 1 if net.use_biases else 0
-    run_args = queues + (_lib.ptr(samples_io), int(n_given), int(n_steps),
-                         float(temperature), sd, _lib.ptr(proba_out),
-                         int(proba_every), ub, 1 if push else 0)
-    if lc is not None:
-        _run_lc(net, g, head, bias, queues, samples_io, int(n_given),
-                int(n_steps), float(temperature), sd, proba_out,
-                max(1, int(proba_every)), ub, push, multi_cu, lc, trunc)
-    elif net.CB > 1 or net.S > 512 or net.Q > 512 or net.L > 64:
+    n_given, n_steps = int(n_given), int(n_steps)
+    temperature, sd = float(temperature), int(seed) & (2**64 - 1)
+    # (every caller's proba_every is >= 1)
+    pe, ub = max(1, int(proba_every)), 1 if net.use_biases else 0
+    if lc is None and (net.CB > 1 or net.S > 512 or net.Q > 512 or net.L > 64):
         _run_wide(net, g, samples_io,
-                  head + (net.L, net.CHn, net.S, net.Q) + run_args, trunc)
-    elif not multi_cu or not push:
-        # ONE single-workgroup kernel; the peek always runs here, as the
-        # multi-CU launches advance the queues with every step they take
-        name, targs = _trunc_entry('wn_fastgen_run', trunc)
-        _lib.call(name, *head, net.L, net.S, net.Q, *run_args, *targs,
-                  _lib.stream())
+                  head + (net.L, net.CHn, net.S, net.Q) + queues +
+                  (_lib.ptr(samples_io), n_given, n_steps, temperature, sd,
+                   _lib.ptr(proba_out), pe, ub, 1 if push else 0), trunc)
     else:
-        st = _lib.stream()
-        layer0 = _lib.ptr(net._layer_block(net.params, 0))
-        # weights are constant while generating: pack the chain blocks once,
-        # and compute the past-tap pre-activations of the first step (every
-        # step then leaves the next step's behind)
-        _lib.call('wn_fastgen_pack', layer0, net.layer_stride,
-                  _lib.ptr(g['cw_img']), net.L, st)
-        _lib.call('wn_fastgen_pre', layer0, net.layer_stride, bias,
-                  _lib.ptr(g['dil']), net.L, *queues, _lib.ptr(g['pre']), st)
-        io = samples_io.view(1, -1)
-        iob, pb = _stage(net, g, io, n_given, n_steps, temperature,
-                         proba_out, proba_every, seed=sd, trunc=trunc)
-        common = head + (net.L, net.S, net.Q) + queues + (_lib.ptr(iob),)
-        tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), ub, _lib.ptr(g['cw_img']),
-                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
-                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
-        if not (net.fastgen_persistent
-                and not net._gen_launch_failed.get('persist')
-                and _run_persistent(net, g, common, tail, io, iob, n_steps)):
-            _run_steps(net, g, common, tail, iob, pb, n_steps)
-        samples_io[:int(n_steps) + 1].copy_(iob[:int(n_steps) + 1])
-        if proba_out is not None:
-            proba_out.view(-1).copy_(pb[:proba_out.numel()])
+        _run_chunks(net, g, head + (net.L, net.S, net.Q) + queues, bias,
+                    samples_io, n_given, n_steps, temperature, sd, proba_out,
+                    pe, ub, push, multi_cu, lc, trunc)
     if push:
-        g['steps'] += int(n_steps)
+        g['steps'] += n_steps
 
 
-def _run_lc(net, g, head, bias, queues, samples_io, n_given, n_steps,
-            temperature, sd, proba_out, pe, ub, push, multi_cu, lc,
-            trunc=_NO_TRUNC):
-    # one LC call, chunk by chunk (see _LcRing); the paths of run()
-    ring = _LcRing(net, g, _lc_rows_padded(net, lc.reshape(1, n_steps, net.Lc),
-                                           n_steps), 1, bias, 0, n_steps, pe)
-    Q = net.Q
+def _run_chunks(net, g, head, bias, samples_io, n_given, n_steps, temperature,
+                sd, proba_out, pe, ub, push, multi_cu, lc, trunc):
+    # One call of the 32-channel kernels (head: the arguments up to the
+    # queues), chunk by chunk: an LC call has its ring's plan and arguments
+    # (see _LcRing), a plain call is one chunk with neither.
+    plan, lcargs, fill = [(0, n_steps)], (), lambda a, n: None
+    if lc is not None:
+        ring = _LcRing(net, g, _lc_rows_padded(
+            net, lc.reshape(1, n_steps, net.Lc), n_steps), 1, bias, 0,
+            n_steps, pe)
+        plan, lcargs, fill = ring.plan, ring.args, ring.fill
 
     def prows(a):                  # the probability rows from call step a
-        return None if proba_out is None else proba_out.view(-1)[a // pe * Q:]
+        return None if proba_out is None else \
+            proba_out.view(-1)[a // pe * net.Q:]
     if not multi_cu or not push:
-        name, targs = _trunc_entry('wn_fastgen_run_lc', trunc)
-        for a, n in ring.plan:
-            ring.fill(a, n)
-            _lib.call(name, *head, net.L, net.S, net.Q,
-                      *queues, _lib.ptr(samples_io[a:]), max(1, n_given - a),
-                      n, temperature, sd, _lib.ptr(prows(a)), pe, ub,
-                      1 if push else 0, *ring.args(), *targs, _lib.stream())
+        # ONE single-workgroup kernel a chunk; the peek always runs here, as
+        # the multi-CU launches advance the queues with every step they take
+        name, extra = _entry('wn_fastgen_run', lcargs, trunc)
+        for a, n in plan:
+            fill(a, n)
+            _lib.call(name, *head, _lib.ptr(samples_io[a:]),
+                      max(1, n_given - a), n, temperature, sd,
+                      _lib.ptr(prows(a)), pe, ub, 1 if push else 0, *extra,
+                      _lib.stream())
         return
     st = _lib.stream()
     layer0 = _lib.ptr(net._layer_block(net.params, 0))
+    # weights are constant while generating: pack the chain blocks once
     _lib.call('wn_fastgen_pack', layer0, net.layer_stride,
               _lib.ptr(g['cw_img']), net.L, st)
     io = samples_io.view(1, -1)
     steps0 = g['steps']
 
-    def sub(a, n_run):
-        # calls steps a .. a + n_run as a call of their own (ctl, io, proba)
+    def stage(a, n_fill, n_run):
+        # ring rows of n_fill steps from a, the past-tap pre-activations of
+        # step a (every step then leaves the next step's behind), and steps
+        # a .. a + n_run staged as a call of their own (ctl, io, proba)
+        fill(a, n_fill)
+        _lib.call(_entry('wn_fastgen_pre', lcargs)[0], layer0,
+                  net.layer_stride, bias, _lib.ptr(g['dil']), net.L,
+                  _lib.ptr(g['state']), _lib.ptr(g['cursors']),
+                  _lib.ptr(g['pre']), *lcargs, st)
         g['steps'] = steps0 + a
         pr = prows(a)
         iob, pb = _stage(net, g, io[:, a:], max(1, n_given - a), n_run,
                          temperature, pr, pe, seed=sd, trunc=trunc)
-        common = head + (net.L, net.S, net.Q) + queues + (_lib.ptr(iob),)
-        tail = (_lib.ptr(g['ctl']), _lib.ptr(pb), ub, _lib.ptr(g['cw_img']),
-                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
-                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
+        args = head + (
+            _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(pb), ub,
+            _lib.ptr(g['cw_img']), _lib.ptr(g['pre']), _lib.ptr(g['z_all']),
+            _lib.ptr(g['h1']), _lib.ptr(g['h2']), _lib.ptr(g['logits']))
 
         def done():
             samples_io[a:a + n_run + 1].copy_(iob[:n_run + 1])
             if pr is not None:
-                k = (n_run + pe - 1) // pe * Q
+                k = (n_run + pe - 1) // pe * net.Q
                 pr[:k].copy_(pb[:k])
-        return iob, pb, common, tail, done
-
-    def pre():
-        _lib.call('wn_fastgen_pre_lc', layer0, net.layer_stride, bias,
-                  _lib.ptr(g['dil']), net.L, *queues, _lib.ptr(g['pre']),
-                  *ring.args(), st)
-    a_step = n_steps               # where the step kernels take over
+        return iob, pb, args, done
+    a_step, staged = 0, None       # where the step kernels take over
     if net.fastgen_persistent and not net._gen_launch_failed.get('persist'):
-        for a, n in ring.plan:
-            ring.fill(a, n)
-            pre()
-            iob, pb, common, tail, done = sub(a, n)
-            if not _run_persistent(net, g, common, tail, io[:, a:], iob, n,
-                                   lc=ring.args()):
-                a_step = a
+        for a, n in plan:
+            staged = iob, pb, args, done = stage(a, n, n)
+            if not _run_persistent(net, g, args, io[:, a:], iob, n, lcargs):
                 break
             done()
-    else:
-        a_step = 0
+            a_step = a + n
     if a_step < n_steps:
-        # the step kernels from call step a_step (state as the launches left it)
-        plan = [(a, n) for a, n in ring.plan if a >= a_step]
-        ring.fill(*plan[0])
-        pre()
-        iob, pb, common, tail, done = sub(a_step, n_steps - a_step)
-        lcargs = ring.args()
+        # the step kernels from call step a_step (state as the launches left
+        # it), staged as ONE call, an LC call's ring refilled chunk by chunk.
+        # (A plain call's refused launch was staged as just that.)
+        plan = [(a, n) for a, n in plan if a >= a_step]
+        if lcargs or staged is None:
+            staged = stage(a_step, plan[0][1], n_steps - a_step)
+        iob, pb, args, done = staged
+        name = _entry('wn_fastgen_step', lcargs)[0]
         for i, (a, n) in enumerate(plan):
             if i:
-                ring.fill(a, n)
+                fill(a, n)
             # (the stream is looked up inside: a capture runs on its own)
-            _replay_steps(net, g, (common, tail, lcargs), lambda: _lib.call(
-                'wn_fastgen_step_lc', *common, *tail, *lcargs, _lib.stream()),
-                n)
+            _replay_steps(net, g, (args, lcargs), lambda: _lib.call(
+                name, *args, *lcargs, _lib.stream()), n)
+        # the last step's draw (every other one ran inside the next step)
         _lib.call('wn_fastgen_finish', net.Q, _lib.ptr(g['cursors']),
                   _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(pb),
                   _lib.ptr(g['logits']), st)
@@ -492,7 +472,7 @@ def _run_wide(net, g, samples_io, args, trunc=_NO_TRUNC):
     # more than 32 channels, or more S / Q / L than the tuned kernels hold
     # in LDS: one workgroup, or the cooperative launch (skip sum and post-
     # processing on other CUs) where the library has one for the shape
-    name, targs = _trunc_entry('wn_fastgen_run_wide', trunc)
+    name, targs = _entry('wn_fastgen_run_wide', trunc=trunc)
     coop = None
     if net.fastgen_wide_coop and not net._gen_launch_failed.get('coop'):
         if 'coop' not in g:
@@ -511,38 +491,26 @@ def _run_wide(net, g, samples_io, args, trunc=_NO_TRUNC):
     _lib.call(name, *args, None, *targs, _lib.stream())
 
 
-def _run_persistent(net, g, common, tail, io, iob, n_steps, lc=None):
+def _run_persistent(net, g, args, io, iob, n_steps, lcargs):
     # ONE launch for the run; its workgroups must all be resident, which
     # the library checks (WN_ERR_UNSUPPORTED).  False: the step kernels, which
     # always complete, run it (after an expired wait, from restored state)
     lib = _lib.load()
+    name, extra = _entry('wn_fastgen_persist', lcargs)
     sync = _buf(net, g, 'fgp_sync', 16, torch.int32)
     ll = _buf(net, g, 'fgp_ll', int(lib.wn_fastgen_persist_ll_words(
         net.L, net.S, net.Q)), torch.int64)
     snap = [(t, t.clone()) for t in (g['state'], g['cursors'], g['pre'])]
-    if lc is None:
-        code = lib.wn_fastgen_persist(*common, *tail, _lib.ptr(sync),
-                                      _lib.ptr(ll), int(n_steps), _lib.stream())
-    else:
-        code = lib.wn_fastgen_persist_lc(*common, *tail, _lib.ptr(sync),
-                                         _lib.ptr(ll), int(n_steps), *lc,
-                                         _lib.stream())
+    # (the library's attribute as it is now; the error code is read here)
+    code = getattr(lib, name)(*args, _lib.ptr(sync), _lib.ptr(ll),
+                              int(n_steps), *extra, _lib.stream())
     if code == 0:
         n_io = int(n_steps) + 1
         return not _expired(net, 'persist', sync,
                             snap + [(iob[:n_io], io[0, :n_io])])
     if code != -2:                 # WN_ERR_UNSUPPORTED: not resident / shape
-        _lib.check(code, 'wn_fastgen_persist' + ('' if lc is None else '_lc'))
+        _lib.check(code, name)
     return False
-
-
-def _run_steps(net, g, common, tail, iob, pb, n_steps):
-    _replay_steps(net, g, (common, tail), lambda: _lib.call(
-        'wn_fastgen_step', *common, *tail, _lib.stream()), n_steps)
-    # the last step's draw (every other one ran inside the next step)
-    _lib.call('wn_fastgen_finish', net.Q, _lib.ptr(g['cursors']),
-              _lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(pb),
-              _lib.ptr(g['logits']), _lib.stream())
 
 
 def predict_proba_incremental(net, waveform, global_condition, push, lc=None):
@@ -830,11 +798,9 @@ def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
                 bias, bstride, _lib.ptr(g['dil']), net.L, B,
                 _lib.ptr(g['state']), _lib.ptr(g['cursors']),
                 _lib.ptr(g['pre']))
-    if ring is None:
-        _lib.call('wn_fastgen_batch_pre', *pre_args, _lib.stream())
-    else:
-        _lib.call('wn_fastgen_batch_pre_lc', *pre_args, *ring.args(),
-                  _lib.stream())
+    name, lcargs = _entry('wn_fastgen_batch_pre',
+                          () if ring is None else ring.args)
+    _lib.call(name, *pre_args, *lcargs, _lib.stream())
     args = w + (bias, bstride, _lib.ptr(g['dil']), net.L, net.S, net.Q, B,
                 _lib.ptr(g['state']), _lib.ptr(g['cursors']),
                 _lib.ptr(g['prev']), _lib.ptr(iob), _lib.ptr(g['ctl']),
@@ -849,8 +815,8 @@ def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
 def batch_complete(net, g, prep, io, proba, n_steps):
     """The last step's draw (every other one runs at the next step's
     start), then the codes / probabilities back into io / proba."""
-    q = prep['q']
-    _lib.call('wn_fastgen_batch_finish' + ('_q' if q else ''), net.Q, g['B'],
+    name, q = _entry('wn_fastgen_batch_finish', q=prep['q'])
+    _lib.call(name, net.Q, g['B'],
               _lib.ptr(g['cursors']), _lib.ptr(prep['iob']),
               _lib.ptr(g['ctl']), _lib.ptr(g['seeds']), _lib.ptr(prep['pb']),
               _lib.ptr(g['logits']), *q, _lib.stream())
@@ -867,19 +833,15 @@ def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
     # chunks, the ring filled before each)
     prep = batch_prepare(net, g, io, n_given, n_steps, temperature, seeds,
                          proba, proba_every, gc, lc, trunc)
-    args, ring, q = prep['args'], prep['ring'], prep['q']
-    sfx = '_q' if q else ''
-    if ring is None:
-        _replay_steps(net, g, args + q, lambda: _lib.call(
-            'wn_fastgen_batch_step' + sfx, *args, *q, _lib.stream()), n_steps)
-    else:
-        lcargs = ring.args()
-        for i, (a, n) in enumerate(ring.plan):
-            if i:
-                ring.fill(a, n)
-            _replay_steps(net, g, (args, lcargs) + q, lambda: _lib.call(
-                'wn_fastgen_batch_step_lc' + sfx, *args, *lcargs, *q,
-                _lib.stream()), n)
+    args, ring = prep['args'], prep['ring']
+    name, extra = _entry('wn_fastgen_batch_step',
+                         () if ring is None else ring.args, q=prep['q'])
+    for i, (a, n) in enumerate([(0, n_steps)] if ring is None else ring.plan):
+        if i:
+            ring.fill(a, n)
+        # (the stream is looked up inside: a capture runs on its own)
+        _replay_steps(net, g, (args, extra), lambda: _lib.call(
+            name, *args, *extra, _lib.stream()), n)
     batch_complete(net, g, prep, io, proba, n_steps)
 
 

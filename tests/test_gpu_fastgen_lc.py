@@ -402,6 +402,56 @@ def test_cli_lc_fast_generation(hip_lib, tmp_path):
         assert np.array_equal(got, expect), extra
 
 
+def test_lc_call_is_the_plain_call_chunk_by_chunk(hip_lib, monkeypatch):
+    """The library calls of an LC call in ONE chunk are those of the plain
+    call on the same path, in order, plus the ring fills and the _lc suffix;
+    in chunks of 7 the chain weights are still packed once, the step kernels
+    finish once, and every chunk is one persistent launch."""
+    from wavenet import _lib
+    net = _model(80, [1, 2, 4, 8, 1, 2, 4, 8])
+    plain = _twin(net)
+    net.fastgen_graph_steps = plain.fastgen_graph_steps = 4
+    seed, n = [4, 7, 1], 25
+    n_steps = len(seed) - 1 + n
+    lc = _rows(n_steps, 80, 31)
+    lib = _lib.load()
+    names, launches = [], []
+    real_call = _lib.call
+
+    def call(name, *args):
+        names.append(name)
+        return real_call(name, *args)
+    monkeypatch.setattr(_lib, 'call', call)
+    for entry in ('wn_fastgen_persist', 'wn_fastgen_persist_lc'):
+        def launch(*args, entry=entry, real=getattr(lib, entry)):
+            code = real(*args)
+            names.append(entry)
+            launches.append(code)
+            return code
+        monkeypatch.setattr(lib, entry, launch)
+
+    def trace(model, path, **kw):
+        _path(model, path)
+        del names[:], launches[:]
+        model.generate(n, seed_samples=seed, seed=6, **kw)
+        return list(names), list(launches)
+    for path in PATHS:
+        net.fastgen_lc_chunk = n_steps + 13
+        want, ran = trace(plain, path)
+        got, ran_lc = trace(net, path, local_condition=lc)
+        assert ran == ran_lc == ([0] if path == 'persist' else []), path
+        got = [s[:-3] if s.endswith('_lc') else s
+               for s in got if s != 'wn_fastgen_lc_bias']
+        assert got == want, path
+        net.fastgen_lc_chunk = 7
+        got, ran_lc = trace(net, path, local_condition=lc)
+        # (the single-workgroup kernel needs no packed weights)
+        assert got.count('wn_fastgen_pack') == int(path != 'single'), path
+        assert got.count('wn_fastgen_finish') == int(path == 'steps'), path
+        assert ran_lc == ([0] * -(-n_steps // 7) if path == 'persist'
+                          else []), path
+
+
 def test_persistent_lc_launches_run_and_fall_back(hip_lib, monkeypatch):
     """Every chunk of an LC call on the persistent path is one
     wn_fastgen_persist_lc launch that runs; an expired hand-over wait in the

@@ -17,6 +17,8 @@ trap 'rm -rf $S' EXIT
 mkdir -p $PK/build/ab $S/base
 rm -f $PK/build/ab/lib_*.so
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC"
+# per-source flags, as the build gives them
+extra() { [ "$1" = wn_fastgen.hip ] && echo -fno-slp-vectorize || true; }
 git show $REV:$PK/csrc/wn_common.h > $S/base/wn_common.h
 # (.inc: kernel bodies a source includes, as of REV beside the base sources)
 for I in $(git ls-tree --name-only $REV $PK/csrc/ | grep '\.inc$' || true); do
@@ -29,11 +31,11 @@ for F in "$@"; do
   OTHERS=$(echo "$OTHERS" | grep -v "/$N.o" || true)
   if git cat-file -e $REV:$PK/csrc/$F 2>/dev/null; then
     git show $REV:$PK/csrc/$F > $S/base/$F
-    /opt/rocm/bin/hipcc $FL -c $S/base/$F -o $S/base_$N.o
+    /opt/rocm/bin/hipcc $FL $(extra $F) -c $S/base/$F -o $S/base_$N.o
     BASE="$BASE $S/base_$N.o"
   fi
   if [ -f $PK/csrc/$F ]; then
-    /opt/rocm/bin/hipcc $FL -c $PK/csrc/$F -o $S/new_$N.o
+    /opt/rocm/bin/hipcc $FL $(extra $F) -c $PK/csrc/$F -o $S/new_$N.o
     NEW="$NEW $S/new_$N.o"
   fi
 done

@@ -9,10 +9,12 @@ N=${F%.hip}
 mkdir -p $PK/build/ab /tmp/ab_src
 rm -f $PK/build/ab/lib_*.so
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC"
+# per-source flags, as the build gives them
+X=; if [ "$F" = wn_fastgen.hip ]; then X=-fno-slp-vectorize; fi
 OTHERS=$(ls $PK/build/*.o | grep -v "/$N.o")
 for v in "$@"; do
   name=${v%%:*}; defs=${v#*:}
-  /opt/rocm/bin/hipcc $FL $defs -c $PK/csrc/$F -o /tmp/ab_src/$name.o
+  /opt/rocm/bin/hipcc $FL $X $defs -c $PK/csrc/$F -o /tmp/ab_src/$name.o
   /opt/rocm/bin/hipcc $FL -shared -o $PK/build/ab/lib_$name.so /tmp/ab_src/$name.o $OTHERS
 done
 ls -la $PK/build/ab/
