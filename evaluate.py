@@ -38,6 +38,20 @@ as training does) -- and adds
 the mean absolute and the root-mean-square (per frame, then averaged)
 difference in dB between the raw log-mel features of what was generated and
 of the original.  --synthesis_out DIR also writes <stem>.wav per utterance.
+
+--synthesis_pitch true (with --synthesis true) then tracks the pitch of what
+was generated and of the originals on the device (wavenet/pitch.py: the front
+end's hop, a 60 - 500 Hz range unless --pitch_fmin / --pitch_fmax say
+otherwise) and adds the top-level
+
+    "synthesis_pitch": {"f0_rmse_cents": .., "gross_pitch_error": ..,
+                        "vuv_error": .., "voiced_frames": .., "frames": ..,
+                        "fmin": .., "fmax": ..}
+
+the root-mean-square F0 difference in cents over the frames voiced on both
+sides and within 20 % of each other, the share of the frames voiced on both
+sides that are further apart, and the share of all frames voiced on one side
+only (null where there is no such frame to divide by).
 """
 from __future__ import print_function
 
@@ -62,7 +76,9 @@ SILENCE_THRESHOLD = 0.3        # train.py's
 WAVENET_PARAMS = './wavenet_params.json'   # generate.py's
 SYNTHESIS_BATCH = 32
 SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_schedule', 'synthesis_out',
-                   'max_clips', 'seed', 'temperature', 'top_k', 'top_p')
+                   'max_clips', 'seed', 'temperature', 'top_k', 'top_p',
+                   'synthesis_pitch')
+PITCH_FLAGS = ('pitch_fmin', 'pitch_fmax')
 
 
 def get_arguments(argv=None):
@@ -131,6 +147,14 @@ def get_arguments(argv=None):
                    help='--synthesis: generate.py\'s --top_k')
     p.add_argument('--top_p', type=float, default=None,
                    help='--synthesis: generate.py\'s --top_p')
+    p.add_argument('--synthesis_pitch', type=str_to_bool, default=None,
+                   help='--synthesis: also track the pitch of the generated '
+                   'and the original utterances on the device and report the '
+                   'F0 error under "synthesis_pitch"')
+    p.add_argument('--pitch_fmin', type=float, default=None,
+                   help='--synthesis_pitch: lowest F0 in Hz (default 60)')
+    p.add_argument('--pitch_fmax', type=float, default=None,
+                   help='--synthesis_pitch: highest F0 in Hz (default 500)')
     emphasis.add_cli_flag(p)
     input_noise.add_cli_flags(p)
     a = p.parse_args(argv)
@@ -148,6 +172,10 @@ def get_arguments(argv=None):
         for name in SYNTHESIS_FLAGS:
             if getattr(a, name) is not None:
                 p.error('--%s needs --synthesis true' % name)
+    if not a.synthesis_pitch:
+        for name in PITCH_FLAGS:
+            if getattr(a, name) is not None:
+                p.error('--%s needs --synthesis_pitch true' % name)
     return a
 
 
@@ -188,11 +216,18 @@ def main(argv=None):
         print('--lc_channels needs --lc_hop (audio samples per feature '
               'frame)')
         return 1
+    tracker = None
     if args.synthesis:
         why = _synthesis_refused(args, spec)
         if why:
             print(why)
             return 1
+        if args.synthesis_pitch:
+            try:
+                tracker = _pitch_tracker(args, spec)
+            except ValueError as e:
+                print('--synthesis_pitch: %s' % e)
+                return 1
     ckpt = None
     if args.use_ema:
         ckpt, why = open_ema_checkpoint(args.checkpoint)
@@ -249,9 +284,12 @@ def main(argv=None):
                 silence_threshold=args.silence_threshold,
                 gc_enabled=gc_enabled, gc_cardinality=args.gc_cardinality)
         try:
-            result['synthesis'] = _synthesis(args, net, spec, whole,
-                                             wavenet_params['sample_rate'],
-                                             emph)
+            result['synthesis'], pitch_error = _synthesis(
+                args, net, spec, whole, wavenet_params['sample_rate'], emph,
+                tracker)
+            if tracker is not None:
+                result['synthesis_pitch'] = dict(
+                    pitch_error, fmin=tracker.fmin, fmax=tracker.fmax)
         except ValueError as e:
             print(str(e))
             return 1
@@ -277,11 +315,24 @@ def _synthesis_refused(args, spec):
     return None
 
 
-def _synthesis(args, net, spec, data, sample_rate, emph=None):
-    """The "synthesis" entry: the set's whole utterances (in its order; the
-    first --max_clips of them) copy-synthesised, de-emphasised where the
-    model generates the emphasised signal (`emph`), and compared with the
-    natural originals."""
+def _pitch_tracker(args, spec):
+    """The PitchTracker of --synthesis_pitch: the front end's sample rate and
+    hop, --pitch_fmin / --pitch_fmax, defaults otherwise."""
+    from wavenet import pitch
+    kw = {}
+    if args.pitch_fmin is not None:
+        kw['fmin'] = args.pitch_fmin
+    if args.pitch_fmax is not None:
+        kw['fmax'] = args.pitch_fmax
+    return pitch.PitchTracker(spec.sample_rate, hop=spec.hop, **kw)
+
+
+def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
+    """(the "synthesis" entry, the F0 error or None): the set's whole
+    utterances (in its order; the first --max_clips of them)
+    copy-synthesised, de-emphasised where the model generates the emphasised
+    signal (`emph`), and compared with the natural originals -- their raw
+    log-mel features and, with a `tracker`, their pitch."""
     from wavenet import synthesis
     pieces = data.pieces[:args.max_clips]
     audios = [p[0] for p in pieces]
@@ -296,6 +347,8 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None):
     if emph is not None:
         waves = synthesis.deemphasize(emph, waves, syn.rounds)
     mae, lsd = synthesis.log_mel_distance(spec, waves, audios, syn.rounds)
+    pitch_error = None if tracker is None else \
+        synthesis.pitch_distance(tracker, waves, audios, syn.rounds)
     if args.synthesis_out:
         synthesis.write_wavs(
             waves, [os.path.splitext(os.path.basename(p[1]))[0]
@@ -303,7 +356,7 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None):
     return {'clips': len(audios),
             'samples': int(sum(a.shape[0] for a in audios)),
             'steps': syn.steps, 'occupancy': syn.occupancy,
-            'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}
+            'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}, pitch_error
 
 
 if __name__ == '__main__':

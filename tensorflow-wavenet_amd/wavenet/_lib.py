@@ -281,6 +281,18 @@ SIGNATURES['wn_fastgen_batch_restart'] = (c_int, [P, P, c_int, c_int, P, P, P,
 SIGNATURES['wn_fastgen_batch_lc_rows'] = (c_int, [P, c_int, c_int, c_int,
                                                   c_long, P, P])
 
+# name -> (restype, argtypes); mirrors include/wavenet_pitch.h one to one (the
+# pitch tracker's header, bound onto the same library)
+PITCH_SIGNATURES = {
+    'wn_pitch_tau_min': (c_int, [c_float, c_float]),
+    'wn_pitch_tau_max': (c_int, [c_float, c_float]),
+    'wn_pitch_lds_bytes': (c_long, [c_int, c_int, c_int]),
+    # audio, lengths, ld, B, T, hop, window, tau_min, tau_max, threshold,
+    # silence, sample_rate, f0, aper, lag, cmnd, stream
+    'wn_pitch_track': (c_int, [P, P, c_long, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_float, c_float, c_float, P, P, P, P,
+                               P]),
+}
 
 
 _lib = None
@@ -301,10 +313,11 @@ def load():
             '`python __graft_entry__.py build` (hipcc --offload-arch=gfx950). '
             'There is no CPU fallback.' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, PITCH_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is missing
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

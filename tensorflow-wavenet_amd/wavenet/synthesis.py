@@ -452,6 +452,24 @@ def deemphasize(emphasis, waves, groups):
     return out
 
 
+def _padded_groups(generated, original, groups):
+    """Per group of utterances (`groups`: lists of indices): (g, o, n) --
+    generated[u] and original[u], float [n_u] each, as two zero-padded device
+    float32 [len(group), max n_u] batches, and their lengths, int64 numpy."""
+    import torch
+    device = generated[0].device
+    for items in groups:
+        n = np.array([int(generated[u].shape[0]) for u in items], np.int64)
+        T = int(n.max())
+        g = torch.zeros((len(items), T), dtype=torch.float32, device=device)
+        o = torch.zeros_like(g)
+        for j, u in enumerate(items):
+            g[j, :n[j]] = generated[u]
+            o[j, :n[j]] = torch.as_tensor(original[u], dtype=torch.float32
+                                          ).to(device)
+        yield g, o, n
+
+
 def log_mel_distance(spec, generated, original, groups):
     """(log_mel_mae_db, log_mel_lsd_db) between the RAW log-mel features
     (`spec` without its normaliser, the tables shared) of generated[u] and
@@ -463,22 +481,29 @@ def log_mel_distance(spec, generated, original, groups):
     import torch
     from . import features
     raw = spec.with_normalizer(None)
-    device = generated[0].device
     parts, nframes = [], []
-    for items in groups:
-        n = np.array([int(generated[u].shape[0]) for u in items], np.int64)
-        T = int(n.max())
-        g = torch.zeros((len(items), T), dtype=torch.float32, device=device)
-        o = torch.zeros_like(g)
-        for j, u in enumerate(items):
-            g[j, :n[j]] = generated[u]
-            o[j, :n[j]] = torch.as_tensor(original[u], dtype=torch.float32
-                                          ).to(device)
+    for g, o, n in _padded_groups(generated, original, groups):
         nf = -(-n // raw.hop)
         parts.append(features.frame_distance(raw(g, n), raw(o, n), nf))
         nframes.append(nf)
     total = features.FrameDistance(*(torch.cat(t) for t in zip(*parts)))
     return total.summary(np.concatenate(nframes), raw.n_mels)
+
+
+def pitch_distance(tracker, generated, original, groups):
+    """The F0 error of generated[u] against original[u], float [n_u] each,
+    over all utterances: both tracked by `tracker` (pitch.PitchTracker) in
+    the zero-padded groups of log_mel_distance with `lengths` set, compared
+    by pitch.f0_error over each utterance's real frames.  Returns
+    F0Error.summary(): f0_rmse_cents, gross_pitch_error, vuv_error,
+    voiced_frames (of the originals), frames.  One host wait, at the end."""
+    import torch
+    from . import pitch
+    parts = []
+    for g, o, n in _padded_groups(generated, original, groups):
+        parts.append(pitch.f0_error(tracker(g, n), tracker(o, n),
+                                    -(-n // tracker.hop)))
+    return pitch.F0Error(*(torch.cat(t) for t in zip(*parts))).summary()
 
 
 def write_wavs(waves, names, directory, sample_rate):
