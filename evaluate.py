@@ -52,6 +52,12 @@ the root-mean-square F0 difference in cents over the frames voiced on both
 sides and within 20 % of each other, the share of the frames voiced on both
 sides that are further apart, and the share of all frames voiced on one side
 only (null where there is no such frame to divide by).
+
+--pitch_path true (with --synthesis_pitch true) tracks both sides through
+the Viterbi path over the frames (wavenet/pitch.py: PitchPath; --pitch_jump,
+--pitch_octave_bias and --pitch_switch set its weights) instead of frame by
+frame, and "synthesis_pitch" gains "tracker": "path", "jump", "octave_bias"
+and "switch".
 """
 from __future__ import print_function
 
@@ -78,7 +84,8 @@ SYNTHESIS_BATCH = 32
 SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_schedule', 'synthesis_out',
                    'max_clips', 'seed', 'temperature', 'top_k', 'top_p',
                    'synthesis_pitch')
-PITCH_FLAGS = ('pitch_fmin', 'pitch_fmax')
+PITCH_FLAGS = ('pitch_fmin', 'pitch_fmax', 'pitch_path')
+PATH_FLAGS = ('pitch_jump', 'pitch_octave_bias', 'pitch_switch')
 
 
 def get_arguments(argv=None):
@@ -155,6 +162,19 @@ def get_arguments(argv=None):
                    help='--synthesis_pitch: lowest F0 in Hz (default 60)')
     p.add_argument('--pitch_fmax', type=float, default=None,
                    help='--synthesis_pitch: highest F0 in Hz (default 500)')
+    p.add_argument('--pitch_path', type=str_to_bool, default=None,
+                   help='--synthesis_pitch: track both sides through the '
+                   'Viterbi path over the frames (pitch.PitchPath) instead '
+                   'of frame by frame')
+    p.add_argument('--pitch_jump', type=float, default=None,
+                   help='--pitch_path: cost per octave of a lag change '
+                   'between frames (default 0.3)')
+    p.add_argument('--pitch_octave_bias', type=float, default=None,
+                   help='--pitch_path: cost per octave of lag above the '
+                   'shortest (default 0.05)')
+    p.add_argument('--pitch_switch', type=float, default=None,
+                   help='--pitch_path: cost of a voiced / unvoiced change '
+                   '(default 0.2)')
     emphasis.add_cli_flag(p)
     input_noise.add_cli_flags(p)
     a = p.parse_args(argv)
@@ -176,6 +196,10 @@ def get_arguments(argv=None):
         for name in PITCH_FLAGS:
             if getattr(a, name) is not None:
                 p.error('--%s needs --synthesis_pitch true' % name)
+    if not a.pitch_path:
+        for name in PATH_FLAGS:
+            if getattr(a, name) is not None:
+                p.error('--%s needs --pitch_path true' % name)
     return a
 
 
@@ -289,7 +313,7 @@ def main(argv=None):
                 tracker)
             if tracker is not None:
                 result['synthesis_pitch'] = dict(
-                    pitch_error, fmin=tracker.fmin, fmax=tracker.fmax)
+                    pitch_error, **_pitch_entry(tracker))
         except ValueError as e:
             print(str(e))
             return 1
@@ -317,14 +341,35 @@ def _synthesis_refused(args, spec):
 
 def _pitch_tracker(args, spec):
     """The PitchTracker of --synthesis_pitch: the front end's sample rate and
-    hop, --pitch_fmin / --pitch_fmax, defaults otherwise."""
+    hop, --pitch_fmin / --pitch_fmax, defaults otherwise; with --pitch_path
+    true the PitchPath on it, with --pitch_jump, --pitch_octave_bias and
+    --pitch_switch."""
     from wavenet import pitch
     kw = {}
     if args.pitch_fmin is not None:
         kw['fmin'] = args.pitch_fmin
     if args.pitch_fmax is not None:
         kw['fmax'] = args.pitch_fmax
-    return pitch.PitchTracker(spec.sample_rate, hop=spec.hop, **kw)
+    tracker = pitch.PitchTracker(spec.sample_rate, hop=spec.hop, **kw)
+    if not getattr(args, 'pitch_path', None):
+        return tracker
+    kw = {}
+    for flag, name in (('pitch_jump', 'jump'),
+                       ('pitch_octave_bias', 'octave_bias'),
+                       ('pitch_switch', 'switch')):
+        if getattr(args, flag) is not None:
+            kw[name] = getattr(args, flag)
+    return pitch.PitchPath(tracker, **kw)
+
+
+def _pitch_entry(tracker):
+    """What "synthesis_pitch" says about its tracker."""
+    from wavenet import pitch
+    if not isinstance(tracker, pitch.PitchPath):
+        return dict(fmin=tracker.fmin, fmax=tracker.fmax)
+    t = tracker.tracker
+    return dict(fmin=t.fmin, fmax=t.fmax, tracker='path', jump=tracker.jump,
+                octave_bias=tracker.octave_bias, switch=tracker.switch)
 
 
 def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):

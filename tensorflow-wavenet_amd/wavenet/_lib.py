@@ -294,6 +294,16 @@ PITCH_SIGNATURES = {
                                P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_pitch_path.h one to one
+# (the pitch path's header, bound onto the same library)
+PITCH_PATH_SIGNATURES = {
+    'wn_pitch_path_workspace_bytes': (c_long, [c_int, c_int, c_int, c_int]),
+    # cmnd, lag_in, nframes, B, F, tau_min, tau_max, pen, bias, switch_cost,
+    # unvoiced_cost, sample_rate, workspace, f0, aper, lag, cost, stream
+    'wn_pitch_path': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P,
+                              c_float, c_float, c_float, P, P, P, P, P, P]),
+}
+
 
 _lib = None
 
@@ -313,7 +323,7 @@ def load():
             '`python __graft_entry__.py build` (hipcc --offload-arch=gfx950). '
             'There is no CPU fallback.' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, PITCH_SIGNATURES):
+    for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

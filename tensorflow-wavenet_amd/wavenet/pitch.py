@@ -38,6 +38,11 @@ and the settings alone.
 
 `PitchTracker.reference` states the rule in numpy; `PitchTracker.channels`
 and `f0_error` are plain torch ops on whatever device their input lives on.
+
+`PitchPath` is the smoothing across frames, kept apart from the tracker: a
+Viterbi path through the tracker's c' rows on the device (csrc/
+wn_pitch_path.hip, include/wavenet_pitch_path.h), which takes the octave
+slips of weak-fundamental frames out of the track.
 """
 import collections
 import math
@@ -267,6 +272,289 @@ class PitchTracker(object):
         rel = torch.where(voiced, rel.clamp(0.0, 1.0), torch.zeros_like(rel))
         return torch.stack([rel.to(torch.float32),
                             voiced.to(torch.float32)], -1)
+
+
+def _interpolated_f0(c, tau, sr):
+    """Step 5 of the module docstring in float32: f0 of the lag tau on the
+    float32 row c."""
+    f = np.float32
+    a, b, g = c[tau - 1], c[tau], c[tau + 1]
+    den = (a - f(2) * b) + g
+    delta = f(0)
+    if den > 0:
+        delta = min(max(f(0.5) * (a - g) / den, f(-0.5)), f(0.5))
+    return f(sr) / (f(tau) + delta)
+
+
+class PitchPath(object):
+    """A dynamic-programming (Viterbi) path through the tracker's lag
+    candidates over the frames of a clip, on the device (csrc/
+    wn_pitch_path.hip; include/wavenet_pitch_path.h states the rule operation
+    by operation, `reference` restates it in numpy float32).
+
+    Every frame's voiced state s = 0 .. N - 1 (the lag tau_min + s, N =
+    tau_max - tau_min) costs c'[tau] + octave_bias * log2(tau / tau_min), the
+    unvoiced state N costs `unvoiced` (0 on a frame the tracker calls
+    silent); going from lag k to lag s costs jump * |log2 s - log2 k|, into
+    or out of the unvoiced state `switch`.  The cheapest path is returned:
+    Pitch(f0, aper, lag, None) like the tracker's, f0 = 0, lag = 0, aper = 1
+    on its unvoiced frames.  A detour through unvoiced costs 2 * switch +
+    unvoiced (>= jump with the defaults, which are design choices, not tuned
+    on speech), and an isolated frame keeps the tracker's own voiced /
+    unvoiced decision.
+
+    Calling it tracks audio and decodes the path, in groups of clips so that
+    the c' rows plus the predecessor workspace stay under `max_bytes`; clip
+    b's bits do not depend on the grouping.  Every argument is checked here,
+    before any library or device is touched."""
+
+    def __init__(self, tracker, jump=0.3, octave_bias=0.05, switch=0.2,
+                 unvoiced=None, max_bytes=1 << 30):
+        if not isinstance(tracker, PitchTracker):
+            raise ValueError('tracker must be a PitchTracker, got %r'
+                             % (tracker,))
+        if unvoiced is None:
+            unvoiced = tracker.threshold
+        for name, v in (('jump', jump), ('octave_bias', octave_bias),
+                        ('switch', switch), ('unvoiced', unvoiced)):
+            with np.errstate(over='ignore'):
+                if not _is_num(v) or not v >= 0 or \
+                        not np.isfinite(np.float32(v)):
+                    raise ValueError('%s must be a finite non-negative '
+                                     'float32 number, got %r' % (name, v))
+        if not float(np.float32(unvoiced)) > 0:
+            raise ValueError('unvoiced must be positive, got %r'
+                             % (unvoiced,))
+        if not _is_int(max_bytes) or max_bytes < 1:
+            raise ValueError('max_bytes must be a positive int, got %r'
+                             % (max_bytes,))
+        self.tracker = tracker
+        self.jump, self.octave_bias = float(jump), float(octave_bias)
+        self.switch, self.unvoiced = float(switch), float(unvoiced)
+        self.max_bytes = int(max_bytes)
+        self.last_cost = None
+        self._device_tables = {}
+
+    hop = property(lambda self: self.tracker.hop)
+    num_states = property(lambda self: self.tracker.tau_max -
+                          self.tracker.tau_min)
+
+    def settings(self):
+        """The constructor's arguments as a plain dict, the tracker's
+        settings under 'tracker' (`from_settings` inverts it exactly)."""
+        return dict(tracker=self.tracker.settings(), jump=self.jump,
+                    octave_bias=self.octave_bias, switch=self.switch,
+                    unvoiced=self.unvoiced, max_bytes=self.max_bytes)
+
+    @classmethod
+    def from_settings(cls, d):
+        if not isinstance(d, dict) or 'tracker' not in d:
+            raise ValueError("pitch path settings need 'tracker', got %r"
+                             % (d,))
+        d = dict(d)
+        return cls(PitchTracker.from_settings(d.pop('tracker')), **d)
+
+    def tables(self):
+        """(pen, bias): float32 [tau_max + 1], made in float64 and rounded
+        once: pen[k] = jump * log2(max(k, 1)), bias[k] = octave_bias *
+        (log2(max(k, 1)) - log2(tau_min)); bias[tau_min] is 0."""
+        t = self.tracker
+        lg = np.log2(np.maximum(np.arange(t.tau_max + 1), 1)
+                     .astype(np.float64))
+        return ((self.jump * lg).astype(np.float32),
+                (self.octave_bias * (lg - lg[t.tau_min])).astype(np.float32))
+
+    def clip_bytes(self, F):
+        """Device bytes one clip of F frames needs: its c' rows and its
+        predecessor workspace."""
+        t = self.tracker
+        return int(F) * (4 * (t.tau_max + 1) + 2 * (self.num_states + 1))
+
+    def __call__(self, audio, lengths=None):
+        """Track audio [B, T] or [T] with the tracker (return_cmnd=True) and
+        decode the path: Pitch(f0, aper, lag, None) of device tensors [B, F]
+        or [F], without waiting for the device.  `lengths` as the tracker
+        takes them.  A clip that alone needs more than max_bytes is a
+        ValueError naming both sizes, before any launch."""
+        import torch
+        t = self.tracker
+        shape = tuple(getattr(audio, 'shape', None) or np.shape(audio))
+        if len(shape) not in (1, 2) or not all(shape):
+            t(audio, lengths)                   # (raises ValueError)
+            raise ValueError('pitch: audio must have shape [B, T] or [T]')
+        B = 1 if len(shape) == 1 else int(shape[0])
+        F = t.num_frames(shape[-1])
+        need = self.clip_bytes(F)
+        if need > self.max_bytes:
+            raise ValueError(
+                'pitch path: one clip of %d frames needs %d bytes (c\' rows '
+                'and predecessors), max_bytes is %d'
+                % (F, need, self.max_bytes))
+        n = check_lengths(lengths, B, int(shape[-1]), 'pitch')
+        group = max(1, min(B, self.max_bytes // need))
+        if len(shape) == 1 or group >= B:
+            p = t(audio, n, return_cmnd=True)
+            return self.decode(p.cmnd, p.lag,
+                               None if n is None else -(-n // t.hop))
+        parts, costs = [], []
+        for g in range(0, B, group):
+            ng = None if n is None else n[g:g + group]
+            p = t(audio[g:g + group], ng, return_cmnd=True)
+            parts.append(self.decode(p.cmnd, p.lag,
+                                     None if ng is None else -(-ng // t.hop)))
+            costs.append(self.last_cost)
+        self.last_cost = torch.cat(costs)
+        return Pitch(*(torch.cat(v) for v in list(zip(*parts))[:3]), None)
+
+    path = __call__
+
+    def decode(self, cmnd, lag, nframes=None, return_cost=False):
+        """The path alone, on device tensors: cmnd float32 [B, F, tau_max +
+        1] or [F, tau_max + 1] and lag int32 [B, F] or [F] as the tracker
+        returned them; nframes ([B] ints in [0, F], or a device integer
+        tensor, which the kernel clamps): clip b has nframes[b] real frames,
+        the others are zeros in every output.  Returns Pitch(f0, aper, lag,
+        None) (and with return_cost the float64 device tensor [B] of the
+        paths' costs, which `last_cost` holds either way), without waiting
+        for the device."""
+        import torch
+        t = self.tracker
+        R, N = t.tau_max + 1, self.num_states
+        if not isinstance(cmnd, torch.Tensor) or \
+                cmnd.dtype != torch.float32 or cmnd.dim() not in (2, 3) or \
+                int(cmnd.shape[-1]) != R or not all(cmnd.shape):
+            raise ValueError('decode: cmnd must be a float32 tensor [B, F, '
+                             '%d] or [F, %d]' % (R, R))
+        if not isinstance(lag, torch.Tensor) or lag.dtype != torch.int32 or \
+                lag.shape != cmnd.shape[:-1] or lag.device != cmnd.device:
+            raise ValueError('decode: lag must be an int32 tensor %s on '
+                             'cmnd\'s device' % (list(cmnd.shape[:-1]),))
+        one = cmnd.dim() == 2
+        B, F = (1 if one else int(cmnd.shape[0])), int(cmnd.shape[-2])
+        if B > 65535 or F > 1 << 20:
+            raise ValueError('decode: B <= 65535 and F <= 2^20 are required, '
+                             'got [%d, %d]' % (B, F))
+        nd = None
+        if isinstance(nframes, torch.Tensor):
+            if nframes.is_floating_point() or nframes.dtype == torch.bool \
+                    or tuple(nframes.shape) != (B,):
+                raise ValueError('decode: nframes must be %d integers' % B)
+            nd = nframes
+        elif nframes is not None:
+            nf = np.asarray(nframes)
+            if nf.dtype == object or nf.dtype == np.bool_ or \
+                    not np.issubdtype(nf.dtype, np.integer) or \
+                    nf.shape != (B,) or (nf < 0).any() or (nf > F).any():
+                raise ValueError('decode: nframes must be %d integers in '
+                                 '[0, %d], got %r' % (B, F, nframes))
+            nd = torch.from_numpy(nf.astype(np.int32))
+        if cmnd.device.type != 'cuda':
+            raise ValueError('decode: cmnd and lag must be device tensors')
+        _lib.load()
+        _lib.require_gpu()
+        device = cmnd.device
+        with torch.cuda.device(device):
+            if device not in self._device_tables:
+                self._device_tables[device] = tuple(
+                    torch.from_numpy(v).to(device) for v in self.tables())
+            pen, bias = self._device_tables[device]
+            if nd is not None:
+                nd = nd.to(device=device, dtype=torch.int32).contiguous()
+            cmnd, lag = cmnd.contiguous(), lag.contiguous()
+            work = torch.empty(2 * B * F * (N + 1), dtype=torch.uint8,
+                               device=device)
+            f0 = torch.empty((B, F), dtype=torch.float32, device=device)
+            aper = torch.empty_like(f0)
+            out = torch.empty((B, F), dtype=torch.int32, device=device)
+            cost = torch.empty(B, dtype=torch.float64, device=device)
+            _lib.call('wn_pitch_path', _lib.ptr(cmnd), _lib.ptr(lag),
+                      _lib.ptr(nd), B, F, t.tau_min, t.tau_max,
+                      _lib.ptr(pen), _lib.ptr(bias), self.switch,
+                      self.unvoiced, t.sample_rate, _lib.ptr(work),
+                      _lib.ptr(f0), _lib.ptr(aper), _lib.ptr(out),
+                      _lib.ptr(cost), _lib.stream())
+        self.last_cost = cost
+        p = Pitch(f0[0], aper[0], out[0], None) if one else \
+            Pitch(f0, aper, out, None)
+        return (p, cost) if return_cost else p
+
+    def reference(self, cmnd, lag, return_vmax=False):
+        """The rule of wavenet_pitch_path.h in numpy float32 for one clip:
+        cmnd [F, tau_max + 1], lag [F] (the tracker's; 0: a silent frame) ->
+        (Pitch of numpy arrays [F], cost as numpy float64); with return_vmax
+        also the largest magnitude any intermediate took."""
+        f32 = np.float32
+        t = self.tracker
+        tmin, tmax, N = t.tau_min, t.tau_max, self.num_states
+        c = np.ascontiguousarray(cmnd, f32)
+        lag_in = np.asarray(lag).reshape(-1)
+        if c.ndim != 2 or c.shape[1] != tmax + 1 or \
+                lag_in.shape[0] != c.shape[0]:
+            raise ValueError('reference: cmnd [F, %d] and lag [F] are '
+                             'required' % (tmax + 1))
+        F = c.shape[0]
+        pen, bias = self.tables()
+        p, bs = pen[tmin:tmax], bias[tmin:tmax]
+        sw, unv = f32(self.switch), f32(self.unvoiced)
+        ar = np.arange(N)
+        pred = np.zeros((F, N + 1), np.int64)
+        cost, seen = np.float64(0), [0.0]
+
+        def see(*values):
+            with np.errstate(invalid='ignore'):
+                seen[0] = max([seen[0]] + [float(np.max(np.abs(v)))
+                                           for v in values])
+        V = U = None
+        with np.errstate(invalid='ignore', over='ignore'):
+            for f in range(F):
+                loc = c[f, tmin:tmax] + bs
+                lu = f32(0) if lag_in[f] == 0 else unv
+                if f == 0:
+                    nV, nU = loc, lu
+                else:
+                    A, Bk = V - p, V + p
+                    # the smallest index of the running minimum, from below
+                    # and from above (min is exact: any scan gives these)
+                    run = np.minimum.accumulate(A)
+                    new = np.ones(N, bool)
+                    new[1:] = A[1:] < run[:-1]
+                    ia = np.maximum.accumulate(np.where(new, ar, 0))
+                    run = np.minimum.accumulate(Bk[::-1])[::-1]
+                    new = np.ones(N, bool)
+                    new[:-1] = Bk[:-1] <= run[1:]
+                    ib = np.minimum.accumulate(
+                        np.where(new, ar, N)[::-1])[::-1]
+                    L, Rr = A[ia] + p, Bk[ib] - p
+                    left = L <= Rr
+                    vv = np.where(left, L, Rr)
+                    fu = U + sw
+                    voiced = vv <= fu
+                    pred[f, :N] = np.where(voiced, np.where(left, ia, ib), N)
+                    nV = np.where(voiced, vv, fu) + loc
+                    kb = int(np.argmin(V))
+                    fv = V[kb] + sw
+                    stay = U <= fv
+                    pred[f, N] = N if stay else kb
+                    nU = (U if stay else fv) + lu
+                    see(A, Bk, L, Rr, fu, fv)
+                see(loc, nV, nU)
+                m = min(nV.min(), nU)
+                V, U = nV - m, nU - m
+                cost = cost + np.float64(m)
+        f0 = np.zeros(F, f32)
+        aper = np.ones(F, f32)
+        out = np.zeros(F, np.int32)
+        st = N if F == 0 or U <= V.min() else int(np.argmin(V))
+        for f in range(F - 1, -1, -1):
+            if st < N:
+                tau = tmin + st
+                out[f], aper[f] = tau, c[f, tau]
+                with np.errstate(all='ignore'):
+                    f0[f] = _interpolated_f0(c[f], tau,
+                                             f32(t.sample_rate))
+            st = int(pred[f, st])
+        res = (Pitch(f0, aper, out, None), cost)
+        return res + (seen[0],) if return_vmax else res
 
 
 def _real(mask, nframes, what):

@@ -492,7 +492,8 @@ def log_mel_distance(spec, generated, original, groups):
 
 def pitch_distance(tracker, generated, original, groups):
     """The F0 error of generated[u] against original[u], float [n_u] each,
-    over all utterances: both tracked by `tracker` (pitch.PitchTracker) in
+    over all utterances: both tracked by `tracker` (a pitch.PitchTracker, a
+    pitch.PitchPath, or any callable (audio, lengths) -> Pitch with a `hop`) in
     the zero-padded groups of log_mel_distance with `lengths` set, compared
     by pitch.f0_error over each utterance's real frames.  Returns
     F0Error.summary(): f0_rmse_cents, gross_pitch_error, vuv_error,
