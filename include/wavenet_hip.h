@@ -374,7 +374,11 @@ int wn_stack_bwd_lc(const float* X, const float* Z, const float* SG,
  * a_planes planes of [M][32]; C dense [M][ldc] or c_planes planes of [M][32]
  * (c_plane_stride floats apart); an addend passed with ld_add == 0 is in C's
  * plane layout (needs c_planes > 0): the 1x1 residual conv of the
- * channel-block models, x_{l+1} planes = x_l planes + z_l Wd. */
+ * channel-block models, x_{l+1} planes = x_l planes + z_l Wd.  The epilogue
+ * reaches the 32 rows of a wave's half tile through 32-bit byte offsets: ldc
+ * (dense C, or any Cpre), ld_mask and ld_add beyond (31 ld + 64) * 4 < 2^31
+ * (17 318 412 floats at most), a c_plane_stride of 2^29 - 1024 floats or
+ * more, or a negative one of these, is WN_ERR_UNSUPPORTED before any launch. */
 int wn_gemm_nn(const float* A, long lda, int a_planes, long a_plane_stride,
                const float* W, int ldw, const float* bias, const float* mask,
                long ld_mask, const float* addend, long ld_add, float* C,

@@ -1801,6 +1801,18 @@ static int gemm_nn_describe(GemmNN& g, const float* A, long lda, int a_planes,
   // the epilogue addresses a lane's neighbour plane with a 32-bit byte offset)
   if (addend && ld_add == 0 && !c_planes) return WN_ERR_BAD_SHAPE;
   if (c_planes && c_plane_stride * 4 >= (1L << 31)) return WN_ERR_UNSUPPORTED;
+  // The epilogues address C, Cpre, mask and addend through buffer resources
+  // based at a wave's 32-row half: the last 16-byte access of a half lies
+  // (31 ld + 60) * 4 bytes in (plane mode: the neighbour plane + 31 rows of
+  // 128 B + 112), and the resource ends at 2^31 - 1.  Beyond that a store
+  // would be dropped and a load read as zero without any error.
+  const long ep_end = (1L << 31) - 1;
+  auto ep_ld_ok = [&](long ld) { return ld >= 0 && ld <= ep_end && (31 * ld + 64) * 4 <= ep_end; };
+  if (c_planes && (c_plane_stride < 0 || c_plane_stride * 4 + 4096 > ep_end))
+    return WN_ERR_UNSUPPORTED;
+  if ((!c_planes || Cpre) && !ep_ld_ok(ldc)) return WN_ERR_UNSUPPORTED;
+  if (mask && !ep_ld_ok(ld_mask)) return WN_ERR_UNSUPPORTED;
+  if (addend && !ep_ld_ok(ld_add)) return WN_ERR_UNSUPPORTED;
   const void* ptrs[] = {A, W, bias, mask, addend, C, Cpre};
   for (const void* p : ptrs)
     if (p && !wn_aligned16(p)) return WN_ERR_MISALIGNED;
