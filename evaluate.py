@@ -200,6 +200,8 @@ def get_arguments(argv=None):
         for name in PATH_FLAGS:
             if getattr(a, name) is not None:
                 p.error('--%s needs --pitch_path true' % name)
+    if features.f0_flags_refused(a, stored_may_decide=True):
+        p.error(features.f0_flags_refused(a, stored_may_decide=True))
     return a
 
 
@@ -222,7 +224,7 @@ def main(argv=None):
         if args.lc_channels is None and args.lc_features != 'none' and \
                 stored is not None:
             # (a checkpoint trained on its own front end names its mels)
-            args.lc_channels = stored.get('n_mels')
+            args.lc_channels = features.stored_channels(stored)
         if args.lc_upsample_scales is not None and args.lc_channels is None:
             raise ValueError('--lc_upsample_scales needs --lc_channels')
         lc_scales, lc_hop, lc_ctx = local_condition.parse_cli(

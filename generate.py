@@ -203,11 +203,13 @@ def get_arguments(argv=None):
     if a.clips is None:
         a.clips = 1
     if a.lc_wav is None and a.lc_wav_dir is None:
-        for flag in ['--lc_features'] * (a.lc_features == 'mel') + \
-                features.cli_flags_given(a):
+        for flag in ['--lc_features'] * (a.lc_features in features.KINDS) + \
+                features.cli_flags_given(a) + features.f0_flags_given(a):
             p.error('%s needs --lc_wav' % flag)
     elif a.lc_features == 'none':
         p.error('--lc_wav needs a front end, not --lc_features none')
+    if features.f0_flags_refused(a, stored_may_decide=True):
+        p.error(features.f0_flags_refused(a, stored_may_decide=True))
     if a.lc_wav_dir is not None and not a.fast_generation:
         p.error('--lc_wav_dir runs on the fast path only')
     a.samples_given = a.samples is not None
@@ -493,7 +495,7 @@ def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
     net = model_from_params(
         wavenet_params, 1, global_condition_channels=args.gc_channels,
         global_condition_cardinality=args.gc_cardinality,
-        local_condition_channels=spec.n_mels,
+        local_condition_channels=spec.channels,
         local_condition_upsample_scales=lc_scales,
         local_condition_context=lc_ctx)
     why = restore(net, args.checkpoint, args.use_ema, ckpt, check_lc=True)

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('WN_LIB_PATH') or os.path.join(
     os.path.dirname(_HERE), 'libwavenet_hip.so')   # WN_LIB_PATH: A/B builds
 
 c_int, c_long, c_float = ctypes.c_int, ctypes.c_long, ctypes.c_float
+c_double = ctypes.c_double
 c_void_p, c_u64 = ctypes.c_void_p, ctypes.c_uint64
 P = c_void_p  # every device / host pointer crosses as a raw address
 
@@ -304,6 +305,17 @@ PITCH_PATH_SIGNATURES = {
                               c_float, c_float, c_float, P, P, P, P, P, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_lc_frames.h one to one
+# (the conditioning-frame assembler's header, bound onto the same library)
+LC_FRAMES_SIGNATURES = {
+    'wn_lc_frames_chunk': (c_int, []),
+    # mel, ld_mel, M, shift, scale, lo, hi, f0, mode, fmin, span, nframes, B,
+    # F, out, ld_out, c0, stream
+    'wn_lc_frames': (c_int, [P, c_long, c_int, P, P, c_float, c_float, P,
+                             c_int, c_double, c_double, P, c_int, c_int, P,
+                             c_long, c_int, P]),
+}
+
 
 _lib = None
 
@@ -323,7 +335,8 @@ def load():
             '`python __graft_entry__.py build` (hipcc --offload-arch=gfx950). '
             'There is no CPU fallback.' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES):
+    for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
+                  LC_FRAMES_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

@@ -276,8 +276,9 @@ class DeviceCorpus(object):
         if not _is_int(rank) or not _is_int(world) or not 0 <= rank < world:
             raise ValueError('0 <= rank < world is required, got rank %r, '
                              'world %r' % (rank, world))
-        if spec is not None and not isinstance(spec, features.MelSpec):
-            raise ValueError('spec must be a features.MelSpec or None')
+        if spec is not None and not features.is_spec(spec):
+            raise ValueError('spec must be a features.MelSpec, a '
+                             'frontend.MelPitchSpec or None')
         norm_kw = _check_normalize(normalize, normalize_clip, stats_allreduce,
                                    world, None if spec is None else
                                    spec.n_mels, spec is not None)
@@ -310,7 +311,7 @@ class DeviceCorpus(object):
             total += audio.size
             if spec is not None:
                 nframes += spec.num_frames(audio.size)
-            _check_bytes(total, nframes * (spec.n_mels if spec else 0),
+            _check_bytes(total, nframes * (spec.channels if spec else 0),
                          max_bytes, 'at least %%d bytes on the device after '
                          '%d of its %d files' % (len(kept) + 1, len(files)))
             clips.append(audio)
@@ -337,8 +338,9 @@ class DeviceCorpus(object):
         constructor's; world: the number of shards this one belongs to."""
         from . import features
         self = cls.__new__(cls)
-        if spec is not None and not isinstance(spec, features.MelSpec):
-            raise ValueError('spec must be a features.MelSpec or None')
+        if spec is not None and not features.is_spec(spec):
+            raise ValueError('spec must be a features.MelSpec, a '
+                             'frontend.MelPitchSpec or None')
         if spec is not None and frames is not None:
             raise ValueError('from_arrays: spec and frames exclude each '
                              'other')
@@ -393,7 +395,7 @@ class DeviceCorpus(object):
                max_bytes, norm_kw=None):
         lengths = [int(a.shape[0]) for a in clips]
         self.index = CorpusIndex(lengths, ids, **index_kw)
-        Lc = spec.n_mels if spec is not None else \
+        Lc = spec.channels if spec is not None else \
             (frames[0].shape[1] if frames is not None else 0)
         hop = spec.hop if spec is not None else hop
         counts = None if Lc == 0 else np.asarray(
@@ -403,6 +405,7 @@ class DeviceCorpus(object):
                      int(counts.sum()) * Lc, max_bytes)
         # everything above needs neither the library nor a device
         import torch
+        from . import features
         _lib.load()
         _lib.require_gpu()
         self.device = torch.device('cuda', torch.cuda.current_device()) \
@@ -443,46 +446,73 @@ class DeviceCorpus(object):
                 .astype(np.int64)
             self._fr_off, self._fr_len = dev(fr_off), \
                 dev(counts.astype(np.int32))
+        mel_stats = None
         if spec is not None:
             # each utterance's log-mel frames, once (tools/make_lc_features.py
             # does the same for a whole utterance), written to their place
             self.frames_flat = torch.empty(int(counts.sum()) * Lc,
                                            dtype=torch.float32,
                                            device=self.device)
+            composite = not isinstance(spec, features.MelSpec)
+            if composite and raw is not spec and _wants_stats(**norm_kw):
+                mel_stats = features.FeatureStats(spec.n_mels)
             with torch.cuda.device(self.device):
                 for o, n, fo, F in zip(ix.offsets.tolist(), lengths,
                                        fr_off.tolist(), counts.tolist()):
-                    if n:
-                        self.frames_flat[fo * Lc:(fo + F) * Lc].copy_(
-                            raw(self.flat[o:o + n]).reshape(-1))
+                    if not n:
+                        continue
+                    place = self.frames_flat[fo * Lc:(fo + F) * Lc]
+                    if not composite:
+                        place.copy_(raw(self.flat[o:o + n]).reshape(-1))
+                        continue
+                    # mel + F0: the raw mels (summed one utterance at a time,
+                    # as compute_feature_stats sums them), the F0 track, and
+                    # the frames assembled in their place
+                    a = self.flat[o:o + n][None]
+                    mel = raw.mel(a)
+                    if mel_stats is not None:
+                        mel_stats.update(mel)
+                    raw.assemble(mel, (raw.path or raw.tracker)(a).f0,
+                                 out=place.view(1, F, Lc))
         elif frames is not None:
             self.frames_flat = filled(list(frames),
                                       [f.shape[0] * Lc for f in frames])
         if norm_kw and norm_kw['normalize'] is not None:
-            self._normalize_resident(**norm_kw)
+            self._normalize_resident(stats=mel_stats, **norm_kw)
         self._perm_dev = None        # device int32 [rows][P]
         self._perm_pin = None        # its pinned staging rows, their events
         self._perm_e0, self._perm_n = 0, 0   # epochs resident: e0 .. e0 + n - 1
         self._bufs = {}              # output kind -> RING flat device buffers
         self._calls = 0              # batch calls so far: call k uses set k % RING
 
-    def _normalize_resident(self, normalize, clip, allreduce, world):
+    def _normalize_resident(self, normalize, clip, allreduce, world,
+                            stats=None):
         """Statistics of the resident raw frames (one launch; all shards'
         through `allreduce`), the normaliser, and the frames normalised in
-        place, once."""
+        place, once.  With a mel + F0 front end `stats` holds the sums of the
+        raw mel channels already (an n_mels-channel FeatureStats), and the
+        mel channels of the resident frames are normalised in place by one
+        wn_lc_frames launch; the pitch channels stay as they are."""
         import torch
         from . import features
+        composite = self.spec is not None and \
+            not isinstance(self.spec, features.MelSpec)
         view = self.frames_flat.view(1, -1, self.Lc)
         with torch.cuda.device(self.device):
-            if normalize == 'corpus' or world == 1 or allreduce is not None:
-                stats = features.FeatureStats(self.Lc).update(view)
+            if _wants_stats(normalize, clip, allreduce, world):
+                if not composite:
+                    stats = features.FeatureStats(self.Lc).update(view)
                 if world > 1:
                     stats = features.FeatureStats.from_vector(
                         allreduce(stats.vector()))
                 self.feature_stats = stats
             norm = features.Normalizer.from_stats(stats, clip) \
                 if normalize == 'corpus' else normalize
-            norm(view, out=view)
+            if composite:
+                from . import frontend
+                frontend.normalize_resident(view[0], self.spec.n_mels, norm)
+            else:
+                norm(view, out=view)
         self.normalizer = norm
         if self.spec is not None:
             self.spec = self.spec.with_normalizer(norm)
@@ -496,14 +526,17 @@ class DeviceCorpus(object):
         vector)."""
         import torch
         from . import features
-        if not isinstance(spec, features.MelSpec):
+        if not features.is_spec(spec):
             raise ValueError('compute_feature_stats: spec must be a '
-                             'features.MelSpec')
+                             'features.MelSpec or a frontend.MelPitchSpec')
         if self.world > 1 and not callable(stats_allreduce):
             raise ValueError('compute_feature_stats: world = %d needs '
                              'stats_allreduce: the statistics of a shard '
                              'differ between ranks' % self.world)
-        raw = spec.with_normalizer(None)
+        # (of a mel + F0 front end: its mel part's; an n_mels-channel
+        # FeatureStats either way)
+        raw = spec.with_normalizer(None) \
+            if isinstance(spec, features.MelSpec) else spec.mel
         stats = features.FeatureStats(spec.n_mels)
         with torch.cuda.device(self.device):
             for o, n in zip(self.index.offsets.tolist(),
@@ -646,6 +679,11 @@ class DeviceCorpus(object):
                           _lib.ptr(rows), B, p.T, _lib.stream())
         return Batch(audio, p.n.copy(), p.gc, frames, offsets, rows,
                      p.history.copy())
+
+
+def _wants_stats(normalize, clip, allreduce, world):
+    """Whether _normalize_resident sums the resident frames."""
+    return normalize == 'corpus' or world == 1 or allreduce is not None
 
 
 def _check_normalize(normalize, clip, allreduce, world, channels, has_frames):

@@ -149,6 +149,12 @@ class MelSpec(object):
     def num_frames(self, n):
         return -(-int(n) // self.hop)
 
+    @property
+    def channels(self):
+        """The channels of the frames: what the model's
+        local_condition_channels must be."""
+        return self.n_mels
+
     def _tables(self):
         """window [n_fft] and melw [n_mels][n_bins]: float64, and rounded to
         float32 as the device gets them."""
@@ -545,15 +551,20 @@ class Normalizer(object):
         v = v.astype(np.float32)
         return v[0] if one else v
 
+    def device_tables(self, device):
+        """(shift, scale) on `device`, uploaded once."""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.shift).to(device),
+                              torch.from_numpy(self.scale).to(device))
+        return self._dev[key]
+
     def _launch(self, src, dst, n):
         """src -> dst, device float32 [B, F, C] contiguous; n: int32 numpy
         [B] or None.  On src's device, torch's current stream."""
         import torch
-        key = str(src.device)
-        if key not in self._dev:
-            self._dev[key] = (torch.from_numpy(self.shift).to(src.device),
-                              torch.from_numpy(self.scale).to(src.device))
-        shift, scale = self._dev[key]
+        shift, scale = self.device_tables(src.device)
         B, F, C = (int(v) for v in src.shape)
         nd = None if n is None else \
             torch.from_numpy(np.ascontiguousarray(n, np.int32)).to(src.device)
@@ -694,18 +705,31 @@ def logmel_reference(x, spec, dtype=np.float64):
     return out
 
 
+def is_spec(obj):
+    """Whether obj is a front end: a MelSpec, or the mel + F0 composite
+    frontend.MelPitchSpec (which has what the package reads from a MelSpec:
+    hop, sample_rate, num_frames, n_mels, channels, normalizer,
+    with_normalizer, settings; calling it gives [B, F, channels])."""
+    if isinstance(obj, MelSpec):
+        return True
+    from . import frontend           # (frontend imports pitch, pitch this)
+    return isinstance(obj, frontend.MelPitchSpec)
+
+
 def local_condition_from_audio(net, spec, audio, lengths=None):
     """WaveNetModel.local_condition_from_audio (model.py)."""
     import torch
-    if not isinstance(spec, MelSpec):
-        raise ValueError('local_condition_from_audio: spec must be a MelSpec')
+    if not is_spec(spec):
+        raise ValueError('local_condition_from_audio: spec must be a MelSpec '
+                         'or a frontend.MelPitchSpec')
     if not net.Lc:
         raise ValueError('local_condition_from_audio: this model was built '
                          'without local conditioning')
-    if spec.n_mels != net.Lc:
+    if spec.channels != net.Lc:
         raise ValueError('local_condition_from_audio: the front end has %d '
-                         'mels, the model %d local-conditioning channels'
-                         % (spec.n_mels, net.Lc))
+                         '%s, the model %d local-conditioning channels'
+                         % (spec.channels, 'mels' if isinstance(spec, MelSpec)
+                            else 'channels', net.Lc))
     if net.lc_up and spec.hop != net.lc_hop:
         raise ValueError('local_condition_from_audio: the front end has hop '
                          '%d, the model upsamples by %d'
@@ -724,14 +748,32 @@ def local_condition_from_audio(net, spec, audio, lengths=None):
 def add_cli_flags(p, also=''):
     """The front end's flags, shared by train.py, evaluate.py, generate.py
     and tools/make_lc_features.py."""
-    p.add_argument('--lc_features', choices=['mel', 'none'], default=None,
+    p.add_argument('--lc_features', choices=['mel', 'mel+f0', 'none'],
+                   default=None,
                    help='Local conditioning from the audio itself: log-mel '
                    'features computed on the device (wavenet/features.py), '
                    '--lc_channels mels at one frame per hop samples; frame f '
                    'sits beside samples f * hop .. f * hop + hop - 1.  No '
                    '<clip>.npy files are read.  The features are those of '
                    'the piece as dequeued: a piece\'s edges see zeros, not '
-                   'the neighbouring samples of its file.' + also)
+                   'the neighbouring samples of its file.  mel+f0: '
+                   '--lc_channels - 2 mels, then an F0 channel and a voicing '
+                   'flag from the device pitch tracker '
+                   '(wavenet/frontend.py).' + also)
+    p.add_argument('--lc_f0_fmin', type=float, default=None,
+                   help='--lc_features mel+f0: lowest F0 in Hz (default 60)')
+    p.add_argument('--lc_f0_fmax', type=float, default=None,
+                   help='--lc_features mel+f0: highest F0 in Hz (default 500)')
+    p.add_argument('--lc_f0_path', type=_bool_arg, default=None,
+                   metavar='true|false',
+                   help='--lc_features mel+f0: take the F0 track from the '
+                   'Viterbi path over the frames (pitch.PitchPath) instead of '
+                   'frame by frame (default false)')
+    p.add_argument('--lc_f0_interpolate', type=_bool_arg, default=None,
+                   metavar='true|false',
+                   help='--lc_features mel+f0: fill the F0 channel of '
+                   'unvoiced frames by linear interpolation between the '
+                   'nearest voiced frames instead of 0 (default false)')
     p.add_argument('--lc_n_fft', type=int, default=None,
                    help='--lc_features: DFT size, a multiple of 64 in '
                    '[64, %d] (default 1024)' % N_FFT_MAX)
@@ -773,12 +815,55 @@ def add_cli_flags(p, also=''):
 
 _CLI_KEYS = ('n_fft', 'win_length', 'fmin', 'fmax')
 _NORM_KEYS = ('normalize', 'norm_clip', 'range', 'stats')
+_F0_KEYS = ('f0_fmin', 'f0_fmax', 'f0_path', 'f0_interpolate')
+KINDS = ('mel', 'mel+f0')        # the front ends --lc_features switches on
+F0_CHANNELS_ERROR = ('--lc_features mel+f0 needs --lc_channels >= 3: two of '
+                     'the channels are the F0 channel and the voicing flag, '
+                     'the others are mels (got %r)')
+
+
+def _bool_arg(text):
+    if str(text).lower() not in ('true', 'false'):
+        import argparse
+        raise argparse.ArgumentTypeError('true or false is required, got %r'
+                                         % (text,))
+    return str(text).lower() == 'true'
 
 
 def cli_flags_given(args):
     """The --lc_n_fft ... flags that were given, by name."""
     return ['--lc_' + k for k in _CLI_KEYS + _NORM_KEYS
             if getattr(args, 'lc_' + k, None) is not None]
+
+
+def f0_flags_given(args):
+    """The --lc_f0_... flags that were given, by name."""
+    return ['--lc_' + k for k in _F0_KEYS
+            if getattr(args, 'lc_' + k, None) is not None]
+
+
+def f0_flags_refused(args, stored_may_decide=False):
+    """One line where a --lc_f0_... flag was given without --lc_features
+    mel+f0, or --lc_features mel+f0 with fewer than 3 --lc_channels; else
+    None.  stored_may_decide: without --lc_features a checkpoint may still
+    name the front end (evaluate.py, generate.py)."""
+    kind = getattr(args, 'lc_features', None)
+    given = f0_flags_given(args)
+    if given and kind != 'mel+f0' and not (kind is None and stored_may_decide):
+        return '%s needs --lc_features mel+f0' % given[0]
+    ch = getattr(args, 'lc_channels', None)
+    if kind == 'mel+f0' and ch is not None and ch < 3:
+        return F0_CHANNELS_ERROR % (ch,)
+    return None
+
+
+def stored_channels(stored):
+    """The local-conditioning channels of a model trained on the front end
+    of a checkpoint's 'lc_features' entry (None where it names none)."""
+    n = stored.get('n_mels')
+    if n is not None and stored.get('kind') == 'mel+f0':
+        n += 2
+    return n
 
 
 def parse_range(text):
@@ -852,13 +937,20 @@ def normalizer_from_cli(args, n_mels, stored=None, corpus=False):
     return norm if clip is None else norm.with_clip(clip)
 
 
+def same_kind(stored, kind):
+    """Whether a checkpoint's entry names the front end `kind`."""
+    return stored is not None and stored.get('kind') == kind
+
+
 def spec_from_cli(args, sample_rate, n_mels, hop, stored=None, corpus=False):
-    """The MelSpec the flags ask for, or None without a front end (its
-    normaliser: normalizer_from_cli).  `stored`:
+    """The front end the flags ask for -- a MelSpec, or with --lc_features
+    mel+f0 a frontend.MelPitchSpec -- or None without one (its normaliser:
+    normalizer_from_cli).  `stored`:
     a checkpoint's 'lc_features' entry -- without --lc_features it switches
     the front end on (--lc_features none: off), and its settings are the
     defaults of the flags that are absent.  ValueError where the flags, the
-    model (n_mels = --lc_channels, hop) and the entry do not fit."""
+    model (n_mels = --lc_channels: the model's channels, two more than the
+    mels with mel+f0; hop) and the entry do not fit."""
     kind = args.lc_features
     if kind is None and stored is not None:
         kind = stored.get('kind')
@@ -866,12 +958,36 @@ def spec_from_cli(args, sample_rate, n_mels, hop, stored=None, corpus=False):
         given = cli_flags_given(args)
         if given:
             raise ValueError('%s needs --lc_features mel' % given[0])
+        if f0_flags_given(args):
+            raise ValueError('%s needs --lc_features mel+f0'
+                             % f0_flags_given(args)[0])
         return None
-    if kind != 'mel':
+    if kind not in KINDS:
         raise ValueError('unknown front end %r in the checkpoint\'s '
                          "'lc_features'" % (kind,))
+    composite = kind == 'mel+f0'
+    if not composite and f0_flags_given(args):
+        raise ValueError('%s needs --lc_features mel+f0'
+                         % f0_flags_given(args)[0])
+    if stored is not None and stored.get('kind') in KINDS and \
+            stored.get('kind') != kind:
+        raise ValueError("the checkpoint's 'lc_features' are %r, the command "
+                         'line asks for --lc_features %s'
+                         % (stored.get('kind'), kind))
+    if composite and n_mels is not None:
+        if n_mels < 3:
+            raise ValueError(F0_CHANNELS_ERROR % (n_mels,))
+        if same_kind(stored, kind) and 'n_mels' in stored and \
+                stored['n_mels'] + 2 != n_mels:
+            # (in the units of the flag: the model's channels)
+            raise ValueError(
+                "the checkpoint's 'lc_features' have %d channels (%d mels + "
+                'F0 + voicing), the command line asks for --lc_channels %d'
+                % (stored['n_mels'] + 2, stored['n_mels'], n_mels))
+        n_mels -= 2
+    same = same_kind(stored, kind)
     kw = {}
-    if stored is not None and stored.get('kind') == 'mel':
+    if same:
         kw = {k: stored[k] for k in _CLI_KEYS + ('floor',) if k in stored}
         for name, mine in (('n_mels', n_mels), ('hop', hop),
                            ('sample_rate', sample_rate)):
@@ -885,18 +1001,36 @@ def spec_from_cli(args, sample_rate, n_mels, hop, stored=None, corpus=False):
         if getattr(args, 'lc_' + k) is not None:
             kw[k] = getattr(args, 'lc_' + k)
     if n_mels is None:
-        raise ValueError('--lc_features mel needs --lc_channels (the number '
-                         'of mels)')
+        raise ValueError('--lc_features %s needs --lc_channels (the number '
+                         'of mels%s)' % (kind, ' + 2' if composite else ''))
     if hop is None:
-        raise ValueError('--lc_features mel needs --lc_hop or '
-                         '--lc_upsample_scales (hop = their product)')
-    entry = stored.get('normalizer') if stored is not None and \
-        stored.get('kind') == 'mel' else None
-    return MelSpec(sample_rate, hop=hop, n_mels=n_mels,
-                   normalizer=normalizer_from_cli(args, n_mels, entry, corpus),
-                   **kw)
+        raise ValueError('--lc_features %s needs --lc_hop or '
+                         '--lc_upsample_scales (hop = their product)' % kind)
+    entry = stored.get('normalizer') if same else None
+    mel = MelSpec(sample_rate, hop=hop, n_mels=n_mels,
+                  normalizer=normalizer_from_cli(args, n_mels, entry, corpus),
+                  **kw)
+    if not composite:
+        return mel
+    from . import frontend, pitch
+    was = dict(stored.get('pitch') or {}) if same else {}
+    path_kw = was.pop('path', None)
+    interpolate = was.pop('interpolate', False)
+    tkw = {k: v for k, v in was.items() if k not in ('sample_rate', 'hop')}
+    for flag, name in (('lc_f0_fmin', 'fmin'), ('lc_f0_fmax', 'fmax')):
+        if getattr(args, flag, None) is not None:
+            tkw[name] = getattr(args, flag)
+    tracker = pitch.PitchTracker(sample_rate, hop=hop, **tkw)
+    want_path = getattr(args, 'lc_f0_path', None)
+    if want_path is None:
+        want_path = path_kw is not None
+    path = pitch.PitchPath(tracker, **(path_kw or {})) if want_path else None
+    if getattr(args, 'lc_f0_interpolate', None) is not None:
+        interpolate = args.lc_f0_interpolate
+    return frontend.MelPitchSpec(mel, tracker, path, bool(interpolate))
 
 
 def checkpoint_entry(spec):
     """What train.py stores under 'lc_features'."""
-    return dict(kind='mel', **spec.settings())
+    return dict(kind='mel' if isinstance(spec, MelSpec) else 'mel+f0',
+                **spec.settings())

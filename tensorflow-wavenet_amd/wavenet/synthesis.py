@@ -421,8 +421,9 @@ def copy_synthesize(net, spec, audios, *, seeds, batch=32,
     device float32 [n_u].  No host wait beyond synthesize's."""
     from . import features
     from .ops import mu_law_decode
-    if not isinstance(spec, features.MelSpec):
-        raise ValueError('copy_synthesize: spec must be a MelSpec')
+    if not features.is_spec(spec):
+        raise ValueError('copy_synthesize: spec must be a MelSpec or a '
+                         'frontend.MelPitchSpec')
     if not net.Lc:
         raise ValueError('copy_synthesize: this model was built without '
                          'local conditioning')
@@ -480,7 +481,9 @@ def log_mel_distance(spec, generated, original, groups):
     end."""
     import torch
     from . import features
-    raw = spec.with_normalizer(None)
+    # (a mel + F0 front end compares its mel part)
+    raw = spec.with_normalizer(None) if isinstance(spec, features.MelSpec) \
+        else spec.mel
     parts, nframes = [], []
     for g, o, n in _padded_groups(generated, original, groups):
         nf = -(-n // raw.hop)

@@ -41,7 +41,8 @@ def get_arguments(argv=None):
     p.add_argument('--sample_rate', type=int, required=True,
                    help='the model\'s sample rate (wavenet_params.json)')
     p.add_argument('--lc_channels', type=int, required=True,
-                   help='the number of mels')
+                   help='the number of mels (--lc_features mel+f0: the '
+                   'model\'s channels, two more than the mels)')
     p.add_argument('--lc_hop', type=int, required=True,
                    help='audio samples per feature frame')
     p.add_argument('--silence_threshold', type=float,
@@ -50,7 +51,9 @@ def get_arguments(argv=None):
     args = p.parse_args(argv)
     if args.lc_features == 'none':
         p.error('--lc_features none: nothing to write')
-    args.lc_features = 'mel'
+    args.lc_features = args.lc_features or 'mel'
+    if features.f0_flags_refused(args):
+        p.error(features.f0_flags_refused(args))
     try:
         features.normalize_flags(args)
     except ValueError as e:
@@ -59,9 +62,9 @@ def get_arguments(argv=None):
 
 
 def file_features(spec, audio, silence_threshold):
-    """float32 [ceil(len(audio) / hop), n_mels] of one loaded file."""
+    """float32 [ceil(len(audio) / hop), channels] of one loaded file."""
     n, hop = audio.shape[0], spec.hop
-    out = np.zeros((spec.num_frames(n), spec.n_mels), np.float32)
+    out = np.zeros((spec.num_frames(n), spec.channels), np.float32)
     lo, hi = 0, n
     if silence_threshold is not None:
         lo, hi = (int(v) for v in ar.trim_bounds(audio, silence_threshold))

@@ -32,7 +32,9 @@ def get_arguments(argv=None):
     p.add_argument('--sample_rate', type=int, required=True,
                    help='the model\'s sample rate (wavenet_params.json)')
     p.add_argument('--lc_channels', type=int, required=True,
-                   help='the number of mels')
+                   help='the number of mels (--lc_features mel+f0: the '
+                   'model\'s channels, two more than the mels; the '
+                   'statistics are those of the mels)')
     p.add_argument('--lc_hop', type=int, required=True,
                    help='audio samples per feature frame')
     p.add_argument('--silence_threshold', type=float,
@@ -47,7 +49,9 @@ def get_arguments(argv=None):
         if getattr(args, flag) is not None:
             p.error('--%s: the statistics are those of the raw features'
                     % flag)
-    args.lc_features = 'mel'
+    args.lc_features = args.lc_features or 'mel'
+    if features.f0_flags_refused(args):
+        p.error(features.f0_flags_refused(args))
     return args
 
 

@@ -204,9 +204,11 @@ def get_arguments(argv=None):
             p.error('--device_corpus true needs --data_dir')
         if args.synthetic:
             p.error('--device_corpus true does not go with --synthetic')
-        if args.lc_channels is not None and args.lc_features != 'mel':
+        if args.lc_channels is not None and \
+                args.lc_features not in features.KINDS:
             p.error('--device_corpus true reads no <clip>.npy features: '
-                    '--lc_channels needs --lc_features mel with it')
+                    '--lc_channels needs --lc_features mel or mel+f0 with '
+                    'it')
         if args.crop == 'random' and not args.sample_size:
             p.error('--crop random needs --sample_size')
     elif args.crop is not None:
@@ -218,18 +220,23 @@ def get_arguments(argv=None):
         if missing:
             p.error('--piece_history needs %s' % ' and '.join(missing))
     if args.lc_feature_context == 'utterance' and not (
-            args.device_corpus and args.lc_features == 'mel'):
+            args.device_corpus and args.lc_features in features.KINDS):
         p.error('--lc_feature_context utterance needs --device_corpus true '
-                'and --lc_features mel')
-    if args.lc_feature_context is not None and args.lc_features != 'mel':
-        p.error('--lc_feature_context needs --lc_features mel')
-    if args.lc_features == 'mel':
+                'and --lc_features mel or mel+f0')
+    if args.lc_feature_context is not None and \
+            args.lc_features not in features.KINDS:
+        p.error('--lc_feature_context needs --lc_features mel or mel+f0')
+    if features.f0_flags_refused(args):
+        p.error(features.f0_flags_refused(args))
+    if args.lc_features in features.KINDS:
         if args.lc_channels is None:
-            p.error('--lc_features mel needs --lc_channels (the number of '
-                    'mels)')
+            p.error('--lc_features %s needs --lc_channels (the number of '
+                    'mels%s)' % (args.lc_features, ' + 2' if
+                                 args.lc_features == 'mel+f0' else ''))
         if args.lc_hop is None and args.lc_upsample_scales is None:
-            p.error('--lc_features mel needs --lc_hop or '
-                    '--lc_upsample_scales (hop = their product)')
+            p.error('--lc_features %s needs --lc_hop or '
+                    '--lc_upsample_scales (hop = their product)'
+                    % args.lc_features)
         try:
             features.normalize_flags(args, corpus=args.device_corpus)
         except ValueError as e:
