@@ -58,6 +58,27 @@ the Viterbi path over the frames (wavenet/pitch.py: PitchPath; --pitch_jump,
 --pitch_octave_bias and --pitch_switch set its weights) instead of frame by
 frame, and "synthesis_pitch" gains "tracker": "path", "jump", "octave_bias"
 and "switch".
+
+--synthesis_stft true (with --synthesis true) adds the multi-resolution STFT
+distance of the de-emphasised generated utterances to the originals
+(wavenet/spectral.py: StftDistance; --stft_resolutions N:HOP:WIN,... sets the
+n_fft:hop:win_length triples, default 1024:120:600,2048:240:1200,512:50:240)
+
+    "synthesis_stft": {"spectral_convergence": .., "log_stft_magnitude": ..,
+                       "per_resolution": [{"n_fft": .., "hop": ..,
+                                           "win_length": ..,
+                                           "spectral_convergence": ..,
+                                           "log_stft_magnitude": ..}, ..]}
+
+per clip sqrt(sum (|O| - |G|)^2 / sum |O|^2) and the mean of |log |O| -
+log |G||, magnitudes clamped at sqrt(1e-7), averaged over the clips, then over
+the resolutions -- on this project's frame grid (zero padding, frame f centred
+at f * hop + hop / 2), not torch.stft's reflect padding.  --synthesis_mcd true
+adds the MFCC-style mel-cepstral distortion in dB (DCT-II of the raw log-mel
+features, coefficients 1 .. --mcd_order, default 13; not comparable to SPTK /
+WORLD mel-generalised-cepstrum MCDs)
+
+    "synthesis_mcd": {"mcd_db": .., "order": .., "n_mels": .., "frames": ..}
 """
 from __future__ import print_function
 
@@ -81,11 +102,31 @@ BATCH_SIZE = 8
 SILENCE_THRESHOLD = 0.3        # train.py's
 WAVENET_PARAMS = './wavenet_params.json'   # generate.py's
 SYNTHESIS_BATCH = 32
+MCD_ORDER = 13
 SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_schedule', 'synthesis_out',
                    'max_clips', 'seed', 'temperature', 'top_k', 'top_p',
-                   'synthesis_pitch')
+                   'synthesis_pitch', 'synthesis_stft', 'synthesis_mcd')
+STFT_FLAGS = ('stft_resolutions',)
+MCD_FLAGS = ('mcd_order',)
 PITCH_FLAGS = ('pitch_fmin', 'pitch_fmax', 'pitch_path')
 PATH_FLAGS = ('pitch_jump', 'pitch_octave_bias', 'pitch_switch')
+
+
+def stft_resolutions_arg(text):
+    """'1024:120:600,512:50:240' -> ((1024, 120, 600), (512, 50, 240))."""
+    out = []
+    for part in text.split(','):
+        f = part.split(':')
+        try:
+            r = tuple(int(v) for v in f)
+        except ValueError:
+            r = ()
+        if len(f) != 3 or len(r) != 3:
+            raise argparse.ArgumentTypeError(
+                'expected n_fft:hop:win_length triples separated by commas, '
+                'got %r' % text)
+        out.append(r)
+    return tuple(out)
 
 
 def get_arguments(argv=None):
@@ -175,6 +216,22 @@ def get_arguments(argv=None):
     p.add_argument('--pitch_switch', type=float, default=None,
                    help='--pitch_path: cost of a voiced / unvoiced change '
                    '(default 0.2)')
+    p.add_argument('--synthesis_stft', type=str_to_bool, default=None,
+                   help='--synthesis: also report the multi-resolution STFT '
+                   'distance (spectral convergence, log STFT magnitude) of '
+                   'the generated utterances to the originals under '
+                   '"synthesis_stft"')
+    p.add_argument('--stft_resolutions', type=stft_resolutions_arg,
+                   default=None, metavar='N:HOP:WIN,...',
+                   help='--synthesis_stft: the n_fft:hop:win_length triples '
+                   '(default 1024:120:600,2048:240:1200,512:50:240)')
+    p.add_argument('--synthesis_mcd', type=str_to_bool, default=None,
+                   help='--synthesis: also report the MFCC-style mel-cepstral '
+                   'distortion in dB (DCT-II of the raw log-mel features, c0 '
+                   'excluded) under "synthesis_mcd"')
+    p.add_argument('--mcd_order', type=int, default=None,
+                   help='--synthesis_mcd: cepstral coefficients 1 .. N '
+                   '(default 13; at most min(n_mels - 1, 64))')
     emphasis.add_cli_flag(p)
     input_noise.add_cli_flags(p)
     a = p.parse_args(argv)
@@ -200,6 +257,25 @@ def get_arguments(argv=None):
         for name in PATH_FLAGS:
             if getattr(a, name) is not None:
                 p.error('--%s needs --pitch_path true' % name)
+    if not a.synthesis_stft:
+        for name in STFT_FLAGS:
+            if getattr(a, name) is not None:
+                p.error('--%s needs --synthesis_stft true' % name)
+    if not a.synthesis_mcd:
+        for name in MCD_FLAGS:
+            if getattr(a, name) is not None:
+                p.error('--%s needs --synthesis_mcd true' % name)
+    a.stft = None
+    if a.synthesis_stft:
+        from wavenet import spectral
+        try:
+            # (tables in numpy: no library, no device)
+            a.stft = spectral.StftDistance(
+                a.stft_resolutions or spectral.RESOLUTIONS)
+        except ValueError as e:
+            p.error('--stft_resolutions: %s' % e)
+    if a.mcd_order is not None and not 1 <= a.mcd_order <= 64:
+        p.error('--mcd_order must be in [1, 64], got %d' % a.mcd_order)
     if features.f0_flags_refused(a, stored_may_decide=True):
         p.error(features.f0_flags_refused(a, stored_may_decide=True))
     return a
@@ -310,9 +386,10 @@ def main(argv=None):
                 silence_threshold=args.silence_threshold,
                 gc_enabled=gc_enabled, gc_cardinality=args.gc_cardinality)
         try:
-            result['synthesis'], pitch_error = _synthesis(
+            result['synthesis'], pitch_error, more = _synthesis(
                 args, net, spec, whole, wavenet_params['sample_rate'], emph,
                 tracker)
+            result.update(more)
             if tracker is not None:
                 result['synthesis_pitch'] = dict(
                     pitch_error, **_pitch_entry(tracker))
@@ -338,6 +415,12 @@ def _synthesis_refused(args, spec):
         return '--synthesis_batch must be in [1, 256]'
     if args.max_clips is not None and args.max_clips < 1:
         return '--max_clips must be positive'
+    if getattr(args, 'synthesis_mcd', None):
+        raw = spec if isinstance(spec, features.MelSpec) else spec.mel
+        order = args.mcd_order or MCD_ORDER
+        if order > raw.n_mels - 1:
+            return ('--mcd_order %d needs more than %d mel channels (order <= '
+                    'n_mels - 1)' % (order, raw.n_mels))
     return None
 
 
@@ -375,11 +458,13 @@ def _pitch_entry(tracker):
 
 
 def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
-    """(the "synthesis" entry, the F0 error or None): the set's whole
-    utterances (in its order; the first --max_clips of them)
-    copy-synthesised, de-emphasised where the model generates the emphasised
-    signal (`emph`), and compared with the natural originals -- their raw
-    log-mel features and, with a `tracker`, their pitch."""
+    """(the "synthesis" entry, the F0 error or None, the further top-level
+    entries): the set's whole utterances (in its order; the first --max_clips
+    of them) copy-synthesised, de-emphasised where the model generates the
+    emphasised signal (`emph`), and compared with the natural originals --
+    their raw log-mel features and, with a `tracker`, their pitch; with
+    --synthesis_stft "synthesis_stft", the multi-resolution STFT distance,
+    with --synthesis_mcd "synthesis_mcd", the mel-cepstral distortion."""
     from wavenet import synthesis
     pieces = data.pieces[:args.max_clips]
     audios = [p[0] for p in pieces]
@@ -396,6 +481,13 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
     mae, lsd = synthesis.log_mel_distance(spec, waves, audios, syn.rounds)
     pitch_error = None if tracker is None else \
         synthesis.pitch_distance(tracker, waves, audios, syn.rounds)
+    more = {}
+    if getattr(args, 'stft', None) is not None:
+        more['synthesis_stft'] = synthesis.stft_distance(
+            args.stft, waves, audios, syn.rounds)
+    if getattr(args, 'synthesis_mcd', None):
+        more['synthesis_mcd'] = synthesis.mel_cepstral_distortion(
+            spec, waves, audios, syn.rounds, args.mcd_order or MCD_ORDER)
     if args.synthesis_out:
         synthesis.write_wavs(
             waves, [os.path.splitext(os.path.basename(p[1]))[0]
@@ -403,7 +495,7 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
     return {'clips': len(audios),
             'samples': int(sum(a.shape[0] for a in audios)),
             'steps': syn.steps, 'occupancy': syn.occupancy,
-            'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}, pitch_error
+            'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}, pitch_error, more
 
 
 if __name__ == '__main__':

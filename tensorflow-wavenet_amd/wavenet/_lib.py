@@ -316,6 +316,21 @@ LC_FRAMES_SIGNATURES = {
                              c_long, c_int, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_spectral.h one to one
+# (the synthesis metrics' header, bound onto the same library)
+SPECTRAL_SIGNATURES = {
+    'wn_stft_distance_partials': (c_long, [c_int, c_int, c_int]),
+    'wn_stft_distance_staged': (c_int, [c_int, c_int]),
+    # gen, ld_gen, org, ld_org, B, T, lengths, window, basis, n_fft, hop,
+    # n_bins, floor, sc_num, sc_den, log_sum, partials, stream
+    'wn_stft_distance': (c_int, [P, c_long, P, c_long, c_int, c_int, P, P, P,
+                                 c_int, c_int, c_int, c_float, P, P, P, P, P]),
+    'wn_cepstral_distance_partials': (c_long, [c_int, c_int]),
+    # a, b, B, F, C, nframes, dct, K, mcd_sum, partials, stream
+    'wn_cepstral_distance': (c_int, [P, P, c_int, c_int, c_int, P, P, c_int,
+                                     P, P, P]),
+}
+
 
 _lib = None
 
@@ -336,7 +351,7 @@ def load():
             'There is no CPU fallback.' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
-                  LC_FRAMES_SIGNATURES):
+                  LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

@@ -510,6 +510,42 @@ def pitch_distance(tracker, generated, original, groups):
     return pitch.F0Error(*(torch.cat(t) for t in zip(*parts))).summary()
 
 
+def stft_distance(dist, generated, original, groups):
+    """The multi-resolution STFT distance (`dist`: a spectral.StftDistance) of
+    generated[u] against original[u], float [n_u] each, over all utterances,
+    in the zero-padded groups of log_mel_distance with `lengths` set.  A
+    clip's sums do not depend on its group.  Returns StftSums.summary() over
+    the utterances in the order of `groups`.  One host wait, at the end."""
+    from . import spectral
+    parts, lengths = [], []
+    for g, o, n in _padded_groups(generated, original, groups):
+        parts.append(dist(g, o, n))
+        lengths.append(n)
+    return spectral.StftSums.cat(parts).summary(np.concatenate(lengths))
+
+
+def mel_cepstral_distortion(spec, generated, original, groups, order=13):
+    """The mel-cepstral distortion in dB (spectral.mcd_db: DCT-II of the RAW
+    log-mel features, the spec log_mel_distance picks, coefficients 1 ..
+    order) of generated[u] against original[u] over all utterances, in the
+    same groups.  Returns {'mcd_db', 'order', 'n_mels', 'frames'}.  One host
+    wait, at the end."""
+    import torch
+    from . import features, spectral
+    raw = spec.with_normalizer(None) if isinstance(spec, features.MelSpec) \
+        else spec.mel
+    parts, nframes = [], []
+    for g, o, n in _padded_groups(generated, original, groups):
+        nf = -(-n // raw.hop)
+        parts.append(spectral.cepstral_distance(raw(g, n), raw(o, n), nf,
+                                                order))
+        nframes.append(nf)
+    nframes = np.concatenate(nframes)
+    return {'mcd_db': spectral.mcd_db(torch.cat(parts), nframes),
+            'order': int(order), 'n_mels': raw.n_mels,
+            'frames': int(nframes.sum())}
+
+
 def write_wavs(waves, names, directory, sample_rate):
     """waves[u] (device float32 [n_u]) -> directory/<names[u]>.wav, float32
     as generate.py writes them.  Returns the paths."""
