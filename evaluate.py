@@ -79,6 +79,23 @@ features, coefficients 1 .. --mcd_order, default 13; not comparable to SPTK /
 WORLD mel-generalised-cepstrum MCDs)
 
     "synthesis_mcd": {"mcd_db": .., "order": .., "n_mels": .., "frames": ..}
+
+--synthesis_baseline griffin_lim (with --synthesis true) reconstructs every
+evaluated utterance from the raw log-mel features of its NATURAL original by
+Fast Griffin-Lim on the device (wavenet/griffin_lim.py; --gl_iterations,
+default 32, --gl_momentum, default 0.99; no network, no de-emphasis: the
+features are the natural signal's) and adds the number to beat, computed by the
+same helpers against the same originals
+
+    "synthesis_baseline": {"kind": "griffin_lim", "iterations": ..,
+                           "momentum": .., "clips": .., "samples": ..,
+                           "log_mel_mae_db": .., "log_mel_lsd_db": ..}
+
+with "stft", "mcd" and "pitch" sub-entries exactly when --synthesis_stft,
+--synthesis_mcd and --synthesis_pitch are on; --synthesis_out DIR also writes
+<stem>_gl.wav.  Mel inversion by pseudo-inverse and clipping is not a
+non-negative least squares fit, so the baseline's own log-mel error is not
+zero.
 """
 from __future__ import print_function
 
@@ -105,7 +122,11 @@ SYNTHESIS_BATCH = 32
 MCD_ORDER = 13
 SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_schedule', 'synthesis_out',
                    'max_clips', 'seed', 'temperature', 'top_k', 'top_p',
-                   'synthesis_pitch', 'synthesis_stft', 'synthesis_mcd')
+                   'synthesis_pitch', 'synthesis_stft', 'synthesis_mcd',
+                   'synthesis_baseline')
+BASELINE_FLAGS = ('gl_iterations', 'gl_momentum')
+BASELINES = ('griffin_lim',)
+GL_ITERATIONS, GL_MOMENTUM = 32, 0.99
 STFT_FLAGS = ('stft_resolutions',)
 MCD_FLAGS = ('mcd_order',)
 PITCH_FLAGS = ('pitch_fmin', 'pitch_fmax', 'pitch_path')
@@ -232,6 +253,18 @@ def get_arguments(argv=None):
     p.add_argument('--mcd_order', type=int, default=None,
                    help='--synthesis_mcd: cepstral coefficients 1 .. N '
                    '(default 13; at most min(n_mels - 1, 64))')
+    p.add_argument('--synthesis_baseline', type=str, default=None,
+                   choices=BASELINES,
+                   help='--synthesis: also reconstruct every utterance from '
+                   'the raw log-mel features of its natural original by '
+                   'Griffin-Lim on the device and report the same metrics '
+                   'under "synthesis_baseline"')
+    p.add_argument('--gl_iterations', type=int, default=None,
+                   help='--synthesis_baseline: Griffin-Lim iterations in '
+                   '[0, 4096] (default %d)' % GL_ITERATIONS)
+    p.add_argument('--gl_momentum', type=float, default=None,
+                   help='--synthesis_baseline: Fast Griffin-Lim momentum in '
+                   '[0, 1), 0 is plain Griffin-Lim (default %g)' % GL_MOMENTUM)
     emphasis.add_cli_flag(p)
     input_noise.add_cli_flags(p)
     a = p.parse_args(argv)
@@ -265,6 +298,15 @@ def get_arguments(argv=None):
         for name in MCD_FLAGS:
             if getattr(a, name) is not None:
                 p.error('--%s needs --synthesis_mcd true' % name)
+    if not a.synthesis_baseline:
+        for name in BASELINE_FLAGS:
+            if getattr(a, name) is not None:
+                p.error('--%s needs --synthesis_baseline griffin_lim' % name)
+    if a.gl_iterations is not None and not 0 <= a.gl_iterations <= 4096:
+        p.error('--gl_iterations must be in [0, 4096], got %d'
+                % a.gl_iterations)
+    if a.gl_momentum is not None and not 0 <= a.gl_momentum < 1:
+        p.error('--gl_momentum must be in [0, 1), got %r' % a.gl_momentum)
     a.stft = None
     if a.synthesis_stft:
         from wavenet import spectral
@@ -488,14 +530,51 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
     if getattr(args, 'synthesis_mcd', None):
         more['synthesis_mcd'] = synthesis.mel_cepstral_distortion(
             spec, waves, audios, syn.rounds, args.mcd_order or MCD_ORDER)
+    stems = [os.path.splitext(os.path.basename(p[1]))[0] for p in pieces]
     if args.synthesis_out:
-        synthesis.write_wavs(
-            waves, [os.path.splitext(os.path.basename(p[1]))[0]
-                    for p in pieces], args.synthesis_out, sample_rate)
+        synthesis.write_wavs(waves, stems, args.synthesis_out, sample_rate)
+    if getattr(args, 'synthesis_baseline', None):
+        more['synthesis_baseline'] = _baseline(
+            args, spec, audios, syn.rounds, tracker, stems, sample_rate)
     return {'clips': len(audios),
             'samples': int(sum(a.shape[0] for a in audios)),
             'steps': syn.steps, 'occupancy': syn.occupancy,
             'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}, pitch_error, more
+
+
+def _baseline(args, spec, audios, groups, tracker, stems, sample_rate):
+    """The "synthesis_baseline" entry: the utterances reconstructed by
+    Griffin-Lim from the raw log-mel features of the natural originals, in
+    the groups and through the helpers of the generated ones."""
+    from wavenet import griffin_lim, synthesis
+    raw = spec.with_normalizer(None) if isinstance(spec, features.MelSpec) \
+        else spec.mel
+    gl = griffin_lim.GriffinLim(
+        raw,
+        iterations=GL_ITERATIONS if args.gl_iterations is None
+        else args.gl_iterations,
+        momentum=GL_MOMENTUM if args.gl_momentum is None else args.gl_momentum,
+        seed=args.seed or 0)
+    waves = synthesis.griffin_lim_baseline(gl, spec, audios, groups)
+    mae, lsd = synthesis.log_mel_distance(spec, waves, audios, groups)
+    entry = {'kind': args.synthesis_baseline, 'iterations': gl.iterations,
+             'momentum': gl.momentum, 'clips': len(audios),
+             'samples': int(sum(a.shape[0] for a in audios)),
+             'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}
+    if getattr(args, 'stft', None) is not None:
+        entry['stft'] = synthesis.stft_distance(args.stft, waves, audios,
+                                                groups)
+    if getattr(args, 'synthesis_mcd', None):
+        entry['mcd'] = synthesis.mel_cepstral_distortion(
+            spec, waves, audios, groups, args.mcd_order or MCD_ORDER)
+    if tracker is not None:
+        entry['pitch'] = dict(
+            synthesis.pitch_distance(tracker, waves, audios, groups),
+            **_pitch_entry(tracker))
+    if args.synthesis_out:
+        synthesis.write_wavs(waves, [s + '_gl' for s in stems],
+                             args.synthesis_out, sample_rate)
+    return entry
 
 
 if __name__ == '__main__':

@@ -331,6 +331,30 @@ SPECTRAL_SIGNATURES = {
                                      P, P, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_griffin_lim.h one to one
+# (the Griffin-Lim baseline's header, bound onto the same library)
+GRIFFIN_LIM_SIGNATURES = {
+    # x, ld_x, B, T, lengths, window, basis, n_fft, hop, n_bins, out, stream
+    'wn_stft': (c_int, [P, c_long, c_int, c_int, P, P, P, c_int, c_int, c_int,
+                        P, P]),
+    'wn_istft_scratch_bytes': (c_long, [c_int, c_int, c_int, c_int]),
+    # spec, B, T, lengths, window, basis, n_fft, hop, n_bins, scratch, x,
+    # ld_x, stream
+    'wn_istft': (c_int, [P, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P,
+                         c_long, P]),
+    # frames, B, F, n_mels, nframes, pinv, n_bins, out, stream
+    'wn_mel_to_magnitude': (c_int, [P, c_int, c_int, c_int, P, P, c_int, P,
+                                    P]),
+    # A, B, F, n_bins, keys, seed, mode, tab, c0, stream
+    'wn_gl_init': (c_int, [P, c_int, c_int, c_int, P, c_u64, c_int,
+                           P, P, P]),
+    'wn_gl_project_partials': (c_long, [c_int, c_int, c_int]),
+    # x, ld_x, B, T, lengths, window, basis, n_fft, hop, n_bins, A, t_prev,
+    # alpha, t_out, c_out, trace, partials, stream
+    'wn_gl_project': (c_int, [P, c_long, c_int, c_int, P, P, P, c_int, c_int,
+                              c_int, P, P, c_float, P, P, P, P, P]),
+}
+
 
 _lib = None
 
@@ -351,7 +375,8 @@ def load():
             'There is no CPU fallback.' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
-                  LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES):
+                  LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES,
+                  GRIFFIN_LIM_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

@@ -551,6 +551,30 @@ class Normalizer(object):
         v = v.astype(np.float32)
         return v[0] if one else v
 
+    def invert(self, frames, nframes=None):
+        """x = v / scale[c] + shift[c] of normalised frames v, float32
+        [B, F, C] or [F, C] (an array or a tensor): a float32 torch tensor on
+        the frames' device, from torch's elementwise operators (plumbing, no
+        kernel of the library).  Frames at or behind nframes[b] stay zeros.
+        Clamped values do not come back: a v at lo or hi returns the edge of
+        the clamp, not what was there before it."""
+        import torch
+        C = self.n_channels
+        frames, one, B, F = _frames_arg(frames, C, 'Normalizer.invert')
+        n = _nframes_arg(nframes, B, F, 'Normalizer.invert')
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.array(frames))
+        v = frames.reshape(B, F, C)
+        shift = torch.from_numpy(self.shift).to(v.device)
+        scale = torch.from_numpy(self.scale).to(v.device)
+        x = v / scale + shift
+        if n is not None:
+            real = torch.arange(F, device=v.device)[None, :, None] < \
+                torch.from_numpy(n).to(v.device)[:, None, None]
+            x = torch.where(real, x, torch.zeros((), dtype=x.dtype,
+                                                 device=v.device))
+        return x[0] if one else x
+
     def device_tables(self, device):
         """(shift, scale) on `device`, uploaded once."""
         import torch

@@ -546,6 +546,36 @@ def mel_cepstral_distortion(spec, generated, original, groups, order=13):
             'frames': int(nframes.sum())}
 
 
+def griffin_lim_baseline(gl, spec, original, groups):
+    """The Griffin-Lim reconstructions (`gl`: a griffin_lim.GriffinLim over
+    the RAW front end of `spec`, the spec log_mel_distance picks) of
+    original[u], float [n_u] each: per group of utterances (`groups`: lists of
+    indices) the raw log-mel features of the zero-padded originals
+    (wn_melspec, `lengths` set) go through `gl`, utterance u drawing its
+    phases with key u, so that its waveform does not depend on the grouping.
+    Returns the waves, device float32 [n_u] each, in the order of `original`:
+    what the distance helpers take as `generated`.  No host wait."""
+    import torch
+    from . import _lib, features
+    raw = spec.with_normalizer(None) if isinstance(spec, features.MelSpec) \
+        else spec.mel
+    if gl.spec.with_normalizer(None).settings() != raw.settings():
+        raise ValueError('griffin_lim_baseline: gl was built over another '
+                         'front end than the spec\'s')
+    _lib.load()
+    _lib.require_gpu()
+    device = torch.device('cuda', torch.cuda.current_device())
+    dev = [torch.as_tensor(o, dtype=torch.float32).to(device) for o in original]
+    out = [None] * len(original)
+    # (the zero-padded groups of the distance helpers, the originals on both
+    # sides)
+    for items, (o, _, n) in zip(groups, _padded_groups(dev, original, groups)):
+        x = gl(raw(o, n), lengths=n, keys=list(items))
+        for j, u in enumerate(items):
+            out[u] = x[j, :n[j]]
+    return out
+
+
 def write_wavs(waves, names, directory, sample_rate):
     """waves[u] (device float32 [n_u]) -> directory/<names[u]>.wav, float32
     as generate.py writes them.  Returns the paths."""
