@@ -30,7 +30,9 @@ and "occupancy" then report the queue)
 -- runs what was generated through the de-emphasis filter where the model
 was trained with train.py --preemphasis (the checkpoint's 'emphasis' entry, or
 --preemphasis A; the scoring pre-emphasises every batch behind the front end,
-as training does) -- and adds
+as training does), or through the all-pole filter of each utterance's own
+frames where it was trained with train.py --lpc_order (the checkpoint's 'lpc'
+entry, or --lpc_order P; the scoring then scores the excitation) -- and adds
 
     "synthesis": {"clips": .., "samples": .., "steps": .., "occupancy": ..,
                   "log_mel_mae_db": .., "log_mel_lsd_db": ..}
@@ -108,9 +110,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 from wavenet import (  # noqa: E402
-    emphasis, features, input_noise, local_condition)
+    emphasis, features, input_noise, local_condition, lpc)
 from wavenet.checkpoint import (  # noqa: E402
-    open_ema_checkpoint, restore, stored_emphasis, stored_lc_features)
+    open_ema_checkpoint, restore, stored_emphasis, stored_lc_features,
+    stored_lpc)
 from wavenet.cli import (  # noqa: E402
     PIECE_HISTORY_HELP, model_from_params, piece_history, piece_history_arg,
     str_to_bool)
@@ -267,7 +270,10 @@ def get_arguments(argv=None):
                    '[0, 1), 0 is plain Griffin-Lim (default %g)' % GL_MOMENTUM)
     emphasis.add_cli_flag(p)
     input_noise.add_cli_flags(p)
+    lpc.add_cli_flags(p)
     a = p.parse_args(argv)
+    if lpc.flag_error(a, 'evaluate'):
+        p.error(lpc.flag_error(a, 'evaluate'))
     # (the InputNoise of --input_noise, or None)
     a.noise = input_noise.from_cli(p, a)
     if a.preemphasis is not None:
@@ -353,6 +359,11 @@ def main(argv=None):
             lc_hop = spec.hop
         emph = emphasis.from_cli(args.preemphasis,
                                  stored_emphasis(args.checkpoint))
+        lp = lpc.from_cli(args, spec, stored_lpc(args.checkpoint))
+        if lp is not None and emph is not None:
+            raise ValueError('--lpc_order and --preemphasis are two shaping '
+                             'filters (the checkpoint\'s entries count): '
+                             'choose one')
     except ValueError as e:
         print(str(e))
         return 1
@@ -410,6 +421,8 @@ def main(argv=None):
             it = ev.with_features(net, spec, it)
         if emph is not None:
             it = ev.with_emphasis(emph, it)
+        if lp is not None:
+            it = ev.with_lpc(lp, spec, it)
         return it
     result = ev.evaluate(net, batches(), args.max_batches)
     if args.noise is not None:
@@ -430,7 +443,7 @@ def main(argv=None):
         try:
             result['synthesis'], pitch_error, more = _synthesis(
                 args, net, spec, whole, wavenet_params['sample_rate'], emph,
-                tracker)
+                tracker, lp)
             result.update(more)
             if tracker is not None:
                 result['synthesis_pitch'] = dict(
@@ -499,11 +512,13 @@ def _pitch_entry(tracker):
                 octave_bias=tracker.octave_bias, switch=tracker.switch)
 
 
-def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
+def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None,
+               lp=None):
     """(the "synthesis" entry, the F0 error or None, the further top-level
     entries): the set's whole utterances (in its order; the first --max_clips
     of them) copy-synthesised, de-emphasised where the model generates the
-    emphasised signal (`emph`), and compared with the natural originals --
+    emphasised signal (`emph`) or run through the all-pole filter of their
+    originals' frames where it generates the excitation (`lp`), and compared with the natural originals --
     their raw log-mel features and, with a `tracker`, their pitch; with
     --synthesis_stft "synthesis_stft", the multi-resolution STFT distance,
     with --synthesis_mcd "synthesis_mcd", the mel-cepstral distortion."""
@@ -520,6 +535,9 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None):
         schedule=args.synthesis_schedule or 'rounds')
     if emph is not None:
         waves = synthesis.deemphasize(emph, waves, syn.rounds)
+    if lp is not None:
+        waves = synthesis.lpc_synthesize(
+            lp, synthesis.lpc_coefficients(lp, audios), waves, syn.rounds)
     mae, lsd = synthesis.log_mel_distance(spec, waves, audios, syn.rounds)
     pitch_error = None if tracker is None else \
         synthesis.pitch_distance(tracker, waves, audios, syn.rounds)

@@ -41,6 +41,14 @@ emphasised signal; what is decoded goes through the inverse filter on the
 device before it is written (the checkpoint's 'emphasis' entry, or
 --preemphasis A; 0: off), and a --wav_seed is pre-emphasised before it is
 encoded.  generated_codes.npy holds the model's codes as they are.
+Linear prediction: a model trained with train.py --lpc_order generates the
+prediction residual; what is decoded behind the seed goes through the
+all-pole filter of every frame on the device before it is written (the
+checkpoint's 'lpc' entry, or --lpc_order P and its value flags; 0: off).  The
+coefficients come from the raw log-mel frames that condition the run: those
+of --lc_wav / --lc_wav_dir, or --lc_path's with the checkpoint's normaliser
+inverted (what the normaliser clamped stays clamped).  Without frames there
+is no filter: such a run is refused.
 """
 from __future__ import division
 from __future__ import print_function
@@ -55,9 +63,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
-from wavenet import emphasis, features, local_condition, sampling  # noqa: E402
+from wavenet import (  # noqa: E402
+    emphasis, features, local_condition, lpc, sampling)
 from wavenet.checkpoint import (  # noqa: E402,F401
-    context_mismatch, open_ema_checkpoint, restore, stored_emphasis,
+    context_mismatch, open_ema_checkpoint, restore, stored_emphasis, stored_lpc,
     stored_lc_features, upsampler_mismatch)
 from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
@@ -175,7 +184,10 @@ def get_arguments(argv=None):
         '(train.py --lc_features), whose settings the other --lc_* flags '
         'default to.')
     emphasis.add_cli_flag(p)
+    lpc.add_cli_flags(p)
     a = p.parse_args(argv)
+    if lpc.flag_error(a, 'generate'):
+        p.error(lpc.flag_error(a, 'generate'))
     if a.preemphasis is not None:
         try:
             emphasis.Emphasis(a.preemphasis)
@@ -282,6 +294,28 @@ def main(argv=None):
     except ValueError as e:
         print(str(e))
         return 1
+    # linear prediction: on by the flag or by the checkpoint's entry
+    lpc_stored = stored_lpc(args.checkpoint, ckpt)
+    lpc_on = (args.lpc_order if args.lpc_order is not None else
+              (lpc_stored or {}).get('order', 0)) != 0
+    if lpc_on:
+        why = None
+        if emph is not None:
+            why = ('--lpc_order and --preemphasis are two shaping filters '
+                   '(the checkpoint\'s entries count): choose one')
+        elif args.wav_seed:
+            why = ('--lpc_order (or the checkpoint\'s \'lpc\' entry) does '
+                   'not go with --wav_seed: a seed has no frames to take its '
+                   'filter from (--lpc_order 0 switches the filter off)')
+        elif args.lc_path is None and args.lc_wav is None and \
+                args.lc_wav_dir is None:
+            why = ('--lpc_order (or the checkpoint\'s \'lpc\' entry): the '
+                   'all-pole filter needs frames: give --lc_wav, --lc_wav_dir '
+                   'or --lc_path (--lpc_order 0 switches the filter off)')
+        if why:
+            print(why)
+            return 1
+    lp = lp_cf = None
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
     n_wav = None
@@ -310,9 +344,25 @@ def main(argv=None):
             print(str(e))
             return 1
         args.lc_hop = spec.hop
+    elif lpc_on:
+        # (--lc_path: the front end the file's frames came from is the
+        # checkpoint's)
+        try:
+            spec = features.spec_from_cli(
+                args, wavenet_params['sample_rate'], args.lc_channels, hop,
+                stored_lc_features(args.checkpoint, ckpt))
+        except ValueError as e:
+            print(str(e))
+            return 1
+    if lpc_on:
+        try:
+            lp = lpc.from_cli(args, spec, lpc_stored)
+        except ValueError as e:
+            print(str(e))
+            return 1
     if args.lc_wav_dir is not None:
         return _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
-                         emph)
+                         emph, lp)
     if args.lc_path is not None or args.lc_wav is not None:
         if args.fast_generation and not args.lc_fast_generation:
             print('Local conditioning (--lc_path) needs the naive path: '
@@ -330,8 +380,17 @@ def main(argv=None):
             n_wav = min(wav.shape[0], args.samples) if args.samples_given \
                 else wav.shape[0]
             feats = spec(wav[:n_wav]).cpu().numpy()
+            if lp is not None:
+                lp_cf = lp.coefficients_of(wav[:n_wav])
         else:
             feats = np.load(args.lc_path)
+            if lp is not None:
+                lp_cf = _lpc_from_file(lp, feats, spec)
+                if lp_cf is None:
+                    print('--lc_path must hold [frames, channels] features '
+                          'with the {} mels of the checkpoint\'s front end in '
+                          'front'.format(lp.n_mels))
+                    return 1
         if feats.ndim != 2 or feats.shape[0] == 0 or args.lc_hop <= 0:
             print('--lc_path must hold [frames, channels] features and '
                   '--lc_hop must be positive')
@@ -383,8 +442,10 @@ def main(argv=None):
             out = mu_law_decode(np.asarray(codes, np.int32), Q).cpu().numpy()
             if de is not None:
                 out = de.feed(out)
+            out = _lpc_filter(lp, lp_cf, out, n_seed)
             write_wav(out, rate, args.wav_out_path)
 
+    n_seed = len(waveform)
     lc_full = None
     if lc_rows is not None:
         # row of every input position: zeros beside the seed, feature row
@@ -398,7 +459,8 @@ def main(argv=None):
         return None if lc_full is None else lc_full[pos:pos + n]
 
     if args.clips > 1:
-        return _main_clips(args, net, waveform, Q, rate, logdir, rows, emph)
+        return _main_clips(args, net, waveform, Q, rate, logdir, rows, emph,
+                           lp, lp_cf)
     if args.fast_generation:
         if args.wav_seed:
             print('Priming generation with {} seed samples...'
@@ -473,8 +535,30 @@ def main(argv=None):
     return 0
 
 
+def _lpc_from_file(lp, feats, spec):
+    """The coefficients of --lc_path's frames under the checkpoint's front
+    end `spec`: the mel columns (those in front, for a mel+f0 file) with the
+    front end's normaliser inverted (lpc.frames_of_file), or None where the
+    file does not hold them."""
+    raw = lpc.frames_of_file(feats, spec)
+    return None if raw is None else lp.coefficients(raw)
+
+
+def _lpc_filter(lp, cf, out, n_seed):
+    """out (numpy float32 [n], the decoded codes: n_seed seed samples, then
+    what was generated) with the generated part run through the all-pole
+    filter of the frames' coefficients `cf` from a zero state: the whole
+    prefix every time, no state is carried between calls.  The seed in front
+    stays as decoded."""
+    if lp is None or out.shape[0] <= n_seed:
+        return out
+    out = np.asarray(out, np.float32)
+    y = lp.synthesis(out[n_seed:], cf).cpu().numpy()
+    return np.concatenate([out[:n_seed], y])
+
+
 def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
-              emph=None):
+              emph=None, lp=None):
     """--lc_wav_dir: copy synthesis of every wav of a directory on --clips
     streams, in length-sorted rounds or through the restart queue
     (--synthesis_schedule; wavenet/synthesis.py)."""
@@ -514,6 +598,9 @@ def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
         return 1
     if emph is not None:
         waves = synthesis.deemphasize(emph, waves, syn.rounds)
+    if lp is not None:
+        waves = synthesis.lpc_synthesize(
+            lp, synthesis.lpc_coefficients(lp, audios), waves, syn.rounds)
     synthesis.write_wavs(
         waves, [os.path.splitext(os.path.basename(f))[0] for f in files],
         args.wav_out_dir, rate)
@@ -530,7 +617,7 @@ def _clip_path(path, i):
 
 
 def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None,
-                emph=None):
+                emph=None, lp=None, lp_cf=None):
     """--clips N > 1: N streams in lock step (WaveNetModel.generate_batch),
     clip i drawing with --seed + i, all primed by the same seed (and, with
     --lc_path, conditioned on the same rows(position, n))."""
@@ -547,6 +634,7 @@ def _main_clips(args, net, waveform, Q, rate, logdir, rows=lambda p, n: None,
                                     ).cpu().numpy()
                 if de is not None:
                     out = de[i].feed(out)
+                out = _lpc_filter(lp, lp_cf, out, len(waveform))
                 write_wav(out, rate, _clip_path(args.wav_out_path, i))
 
     if args.wav_seed:

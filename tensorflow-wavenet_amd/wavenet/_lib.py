@@ -355,6 +355,22 @@ GRIFFIN_LIM_SIGNATURES = {
                               c_int, P, P, c_float, P, P, P, P, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_lpc.h one to one
+# (linear prediction's header, bound onto the same library)
+LPC_SIGNATURES = {
+    # frames, B, F, n_mels, nframes, pinv, n_bins, ctab, lagwin, order, out,
+    # stream
+    'wn_lpc_from_mel': (c_int, [P, c_int, c_int, c_int, P, P, c_int, P, P,
+                                c_int, P, P]),
+    'wn_lpc_analysis_tile': (c_int, []),
+    # in, ld_in, coeffs, F, order, hop, lengths, B, T, gain (synthesis: its
+    # inverse), out, ld_out, stream
+    'wn_lpc_analysis': (c_int, [P, c_long, P, c_int, c_int, c_int, P, c_int,
+                                c_int, c_float, P, c_long, P]),
+    'wn_lpc_synthesis': (c_int, [P, c_long, P, c_int, c_int, c_int, P, c_int,
+                                 c_int, c_float, P, c_long, P]),
+}
+
 
 _lib = None
 
@@ -376,7 +392,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
                   LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES,
-                  GRIFFIN_LIM_SIGNATURES):
+                  GRIFFIN_LIM_SIGNATURES, LPC_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

@@ -2,7 +2,7 @@
 
 train.py writes torch files holding {'variables': {reference variable name:
 tensor}, 'step'} and, where the run has them, 'optimizer', 'ema_variables',
-'lc_features', 'device_corpus', 'emphasis' and 'input_noise'; the step is parsed from the file name, as
+'lc_features', 'device_corpus', 'emphasis', 'input_noise' and 'lpc'; the step is parsed from the file name, as
 in the reference (train.py:104-134 there).  The reference's own TensorFlow
 checkpoints are read too (tf_checkpoint.py).  train.py, generate.py and
 evaluate.py import their checkpoint functions from here.
@@ -31,7 +31,7 @@ def checkpoint_path(logdir, step):
 
 
 def save(net, logdir, step, optimizer=None, lc_features=None,
-         device_corpus=None, emphasis=None, input_noise=None):
+         device_corpus=None, emphasis=None, input_noise=None, lpc=None):
     """`optimizer`: its step count, slots and shadow go in as 'optimizer'
     and, with EMA weights, the shadow as 'ema_variables' (the keys of
     'variables').  `lc_features`: the front end's settings
@@ -43,7 +43,9 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
     stored under 'emphasis'; a run without it writes no such entry.
     `input_noise`: the noise the run's inputs were perturbed with
     (input_noise.InputNoise.entry: {'prob', 'width', 'seed'}), stored under
-    'input_noise', likewise only where given."""
+    'input_noise', likewise only where given.  `lpc`: the linear prediction
+    whose excitation the model was trained on (lpc.LinearPrediction.entry:
+    {'order', 'noise', 'lag_window', 'gain'}), stored under 'lpc', likewise."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
@@ -57,6 +59,8 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
         ckpt['emphasis'] = emphasis
     if input_noise is not None:
         ckpt['input_noise'] = input_noise
+    if lpc is not None:
+        ckpt['lpc'] = lpc
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
         if optimizer.ema_decay is not None:
@@ -196,6 +200,16 @@ def stored_emphasis(path, ckpt=None):
             return None
         ckpt = torch.load(path, map_location='cpu')
     return ckpt.get('emphasis')
+
+
+def stored_lpc(path, ckpt=None):
+    """The 'lpc' entry train.py --lpc_order wrote into the checkpoint at
+    `path` (`ckpt` where the caller holds it), else None."""
+    if ckpt is None:
+        if tf_checkpoint.checkpoint_format(path) or not os.path.isfile(path):
+            return None
+        ckpt = torch.load(path, map_location='cpu')
+    return ckpt.get('lpc')
 
 
 def restore(net, path, use_ema=False, ckpt=None, check_lc=False):

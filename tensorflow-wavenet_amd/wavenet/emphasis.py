@@ -62,6 +62,58 @@ def _ld(t):
     return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
 
 
+def prepare(audio, lengths, out, what, alias_ok, checked=False):
+    """Checks, then (src [B, T] on the device, dst [B, T], lengths on the
+    device or None, one): what a filter over clips (here and in lpc.py) does
+    with its audio, lengths and out arguments.  checked: `lengths` is
+    check_lengths' result already."""
+    audio, one, B, T = _audio_arg(audio, what)
+    if out is not None:
+        if out is audio and not alias_ok:
+            raise ValueError('%s: out must not be audio itself (a '
+                             'neighbour\'s input would be overwritten)'
+                             % what)
+        if not hasattr(out, 'detach') or \
+                str(out.dtype) != 'torch.float32' or \
+                tuple(out.shape) != tuple(audio.shape) or \
+                out.device.type != 'cuda':
+            raise ValueError('%s: out must be a float32 device tensor of '
+                             'shape %s' % (what, tuple(audio.shape)))
+    n = lengths if checked else check_lengths(lengths, B, T, what)
+    import torch
+    _lib.load()
+    _lib.require_gpu()
+    if isinstance(audio, torch.Tensor) and audio.device.type == 'cuda':
+        device = audio.device
+    else:
+        device = out.device if out is not None else \
+            torch.device('cuda', torch.cuda.current_device())
+        if not isinstance(audio, torch.Tensor):
+            audio = torch.from_numpy(np.ascontiguousarray(audio))
+    src = audio.to(device=device, dtype=torch.float32).reshape(B, T)
+    if not _rows(src):
+        src = src.contiguous()
+    if out is None:
+        dst = torch.empty((B, T), dtype=torch.float32, device=device)
+    else:
+        if out.device != device:
+            raise ValueError('%s: out on %s, audio on %s'
+                             % (what, out.device, device))
+        dst = out.reshape(B, T) if one else out
+        if not _rows(dst) or dst.data_ptr() != out.data_ptr():
+            raise ValueError('%s: out needs unit stride inside a clip '
+                             'and clips at least T apart' % what)
+    if not alias_ok or dst.data_ptr() != src.data_ptr() or \
+            _ld(dst) != _ld(src):
+        lo_s, lo_d = src.data_ptr(), dst.data_ptr()
+        hi_s = lo_s + 4 * ((B - 1) * _ld(src) + T)
+        hi_d = lo_d + 4 * ((B - 1) * _ld(dst) + T)
+        if lo_s < hi_d and lo_d < hi_s:
+            raise ValueError('%s: out overlaps audio' % what)
+    nd = None if n is None else torch.from_numpy(n).to(device)
+    return src, dst, nd, one
+
+
 class Emphasis(object):
     """The filter pair of one alpha, 0 <= alpha < 1 (module docstring).
     Every argument is checked before the library or a device is touched."""
@@ -139,53 +191,7 @@ class Emphasis(object):
 
     # ------------------------------------------------------------ the device
     def _prepare(self, audio, lengths, out, what, alias_ok):
-        """Checks, then (src [B, T] on the device, dst [B, T], lengths on the
-        device or None, one)."""
-        audio, one, B, T = _audio_arg(audio, what)
-        if out is not None:
-            if out is audio and not alias_ok:
-                raise ValueError('%s: out must not be audio itself (a '
-                                 'neighbour\'s input would be overwritten)'
-                                 % what)
-            if not hasattr(out, 'detach') or \
-                    str(out.dtype) != 'torch.float32' or \
-                    tuple(out.shape) != tuple(audio.shape) or \
-                    out.device.type != 'cuda':
-                raise ValueError('%s: out must be a float32 device tensor of '
-                                 'shape %s' % (what, tuple(audio.shape)))
-        n = check_lengths(lengths, B, T, what)
-        import torch
-        _lib.load()
-        _lib.require_gpu()
-        if isinstance(audio, torch.Tensor) and audio.device.type == 'cuda':
-            device = audio.device
-        else:
-            device = out.device if out is not None else \
-                torch.device('cuda', torch.cuda.current_device())
-            if not isinstance(audio, torch.Tensor):
-                audio = torch.from_numpy(np.ascontiguousarray(audio))
-        src = audio.to(device=device, dtype=torch.float32).reshape(B, T)
-        if not _rows(src):
-            src = src.contiguous()
-        if out is None:
-            dst = torch.empty((B, T), dtype=torch.float32, device=device)
-        else:
-            if out.device != device:
-                raise ValueError('%s: out on %s, audio on %s'
-                                 % (what, out.device, device))
-            dst = out.reshape(B, T) if one else out
-            if not _rows(dst) or dst.data_ptr() != out.data_ptr():
-                raise ValueError('%s: out needs unit stride inside a clip '
-                                 'and clips at least T apart' % what)
-        if not alias_ok or dst.data_ptr() != src.data_ptr() or \
-                _ld(dst) != _ld(src):
-            lo_s, lo_d = src.data_ptr(), dst.data_ptr()
-            hi_s = lo_s + 4 * ((B - 1) * _ld(src) + T)
-            hi_d = lo_d + 4 * ((B - 1) * _ld(dst) + T)
-            if lo_s < hi_d and lo_d < hi_s:
-                raise ValueError('%s: out overlaps audio' % what)
-        nd = None if n is None else torch.from_numpy(n).to(device)
-        return src, dst, nd, one
+        return prepare(audio, lengths, out, what, alias_ok)
 
     def pre(self, audio, lengths=None, out=None):
         """Pre-emphasised audio [B, T] or [T] (a float array or a device

@@ -160,6 +160,29 @@ def with_emphasis(emphasis, batches):
         yield (emphasis.pre(audio, lengths), lengths, gc, lc, *hist)
 
 
+def with_lpc(lp, spec, batches):
+    """`batches` with the audio replaced by its linear-prediction excitation
+    on the device (lpc.LinearPrediction `lp`; the coefficients from each
+    clip's own raw log-mel, each clip over its own length) -- behind
+    with_features, whose features are those of the natural signal.  `spec`:
+    the front end those features came from; its raw mel part must be lp's
+    (a ValueError here, before any batch is taken)."""
+    from . import features
+    raw = spec.with_normalizer(None) if isinstance(spec, features.MelSpec) \
+        else spec.mel
+    if raw.settings() != lp.spec.with_normalizer(None).settings():
+        raise ValueError('with_lpc: lp was built over another front end than '
+                         'the features\' (%r, %r)'
+                         % (lp.spec.with_normalizer(None).settings(),
+                            raw.settings()))
+
+    def excited():
+        for audio, lengths, gc, lc, *hist in batches:
+            cf = lp.coefficients_of(audio, lengths)
+            yield (lp.analysis(audio, cf, lengths), lengths, gc, lc, *hist)
+    return excited()
+
+
 def totals(net, batches, max_batches=None, *, input_noise=None, rank=0,
            world=1):
     """float64 [4] on the device: (sum of nll, targets, hits, clips) over

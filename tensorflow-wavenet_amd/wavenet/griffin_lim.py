@@ -73,6 +73,14 @@ def phase_indices(seed, key, F, n_bins, init='random'):
     return p
 
 
+def mel_pinv(spec):
+    """(pinv64, pinv): the float64 pseudo-inverse [n_bins][n_mels] of the
+    spec's own filterbank, and the same rounded to float32 as the device gets
+    it (mel inversion here and in lpc.py)."""
+    pinv64 = np.linalg.pinv(spec.melw64)
+    return pinv64, np.ascontiguousarray(pinv64.astype(np.float32))
+
+
 class GriffinLim(object):
     """The Griffin-Lim baseline of one front-end setting.  Every argument is
     checked here, before any library or device is touched."""
@@ -105,9 +113,7 @@ class GriffinLim(object):
         self.seed, self.init, self.max_bytes = int(seed), init, int(max_bytes)
         self.n_fft, self.hop, self.n_bins = spec.n_fft, spec.hop, spec.n_bins
         self.n_mels = spec.n_mels
-        # float64 pseudo-inverse of the spec's own filterbank, [n_bins][n_mels]
-        self.pinv64 = np.linalg.pinv(spec.melw64)
-        self.pinv = np.ascontiguousarray(self.pinv64.astype(np.float32))
+        self.pinv64, self.pinv = mel_pinv(spec)
         self.tab = phase_table()
         self.last_trace = None
         self._dev = {}

@@ -453,6 +453,31 @@ def deemphasize(emphasis, waves, groups):
     return out
 
 
+def lpc_coefficients(lp, audios):
+    """The predictor coefficients (lpc.LinearPrediction `lp`) of every
+    utterance's natural original audios[u], float [n_u]: device float32
+    [ceil(n_u / hop), order] each, from the raw log-mel frames of the
+    utterance alone -- the frames that also condition it.  No host wait."""
+    return [lp.coefficients_of(np.asarray(a, np.float32).reshape(-1))
+            for a in audios]
+
+
+def lpc_synthesize(lp, coeffs, waves, groups):
+    """waves[u] (device float32 [n_u], the decoded output of a model trained
+    on the linear-prediction excitation) through the all-pole filter of
+    coeffs[u] (float32 [F_u, order], e.g. lpc_coefficients') on the device
+    (lpc.LinearPrediction.synthesis), one ragged batch with `lengths` per
+    group of utterances (`groups`: lists of indices, e.g. Synthesis.rounds).
+    Returns the new list; no host wait."""
+    out = list(waves)
+    for items in groups:
+        done = lp.synthesis_ragged([waves[u] for u in items],
+                                   [coeffs[u] for u in items])
+        for u, w in zip(items, done):
+            out[u] = w
+    return out
+
+
 def _padded_groups(generated, original, groups):
     """Per group of utterances (`groups`: lists of indices): (g, o, n) --
     generated[u] and original[u], float [n_u] each, as two zero-padded device

@@ -31,6 +31,13 @@ first sample sees a zero in front of it, as its mel frames see zeros.  The
 output goes into a buffer of the source's own, two used in turn; the batch
 itself (a view of the corpus's ring) is not rewritten.
 
+Linear prediction (`lpc`: an lpc.LinearPrediction or None, train.py
+--lpc_order) takes the same place: take computes the raw log-mel of the batch
+as cut (a launch of its own beside the front end's), the predictor
+coefficients of every frame and then the excitation into one of the two
+buffers.  The model sees the excitation, the features are those of the
+natural signal.
+
 StepLog prints and logs the loss lines, one step late; validate scores the
 held-out set.
 """
@@ -67,42 +74,52 @@ class StageIn(object):
         return dev
 
 
-class _EmphasisStep(object):
-    """What the two sources share: `front` and the pre-emphasis of a batch
-    into one of two buffers of the source's own."""
+class _ShapedSource(object):
+    """What the two sources share: `front` and the shaping filter of a batch
+    (pre-emphasis, or the linear-prediction excitation) into one of two
+    buffers of the source's own."""
     front = None
+    lpc = None
 
     def history(self, step, B, n_t):
         return None
 
-    def _emphasise(self, audio, lengths):
-        """audio: device float32 [B, T], left as it is."""
-        if self.emphasis is None:
-            return audio
-        if not hasattr(self, '_emph'):
-            self._emph, self._emph_calls = [None, None], 0
-        slot = self._emph_calls & 1
-        self._emph_calls += 1
-        buf = self._emph[slot]
+    def _buffer(self, audio):
+        """One of the source's two buffers, used in turn, as a tensor of
+        audio's shape."""
+        if not hasattr(self, '_shape_bufs'):
+            self._shape_bufs, self._shape_calls = [None, None], 0
+        slot = self._shape_calls & 1
+        self._shape_calls += 1
+        buf = self._shape_bufs[slot]
         if buf is None or buf.numel() < audio.numel() or \
                 buf.device != audio.device:
-            buf = self._emph[slot] = torch.empty(
+            buf = self._shape_bufs[slot] = torch.empty(
                 audio.numel(), dtype=torch.float32, device=audio.device)
-        out = buf[:audio.numel()].view(audio.shape)
-        return self.emphasis.pre(audio, lengths, out=out)
+        return buf[:audio.numel()].view(audio.shape)
+
+    def _shape(self, audio, lengths):
+        """audio: device float32 [B, T], left as it is: its pre-emphasis, or
+        its linear-prediction excitation."""
+        if self.lpc is not None:
+            cf = self.lpc.coefficients_of(audio, lengths)
+            return self.lpc.analysis(audio, cf, lengths,
+                                     out=self._buffer(audio))
+        if self.emphasis is None:
+            return audio
+        return self.emphasis.pre(audio, lengths, out=self._buffer(audio))
 
     def _finish(self, audio, lc, lengths):
         """(audio, lc) with `front`'s features of the raw batch where the
-        loop set one, then the pre-emphasis."""
+        loop set one, then the shaping filter."""
         if self.front is not None:
             lc = self.front(audio.reshape(audio.shape[0], -1), lengths)
-        if self.emphasis is not None:
-            audio = self._emphasise(audio.reshape(audio.shape[0], -1),
-                                    lengths)
+        if self.emphasis is not None or self.lpc is not None:
+            audio = self._shape(audio.reshape(audio.shape[0], -1), lengths)
         return audio, lc
 
 
-class ReaderSource(_EmphasisStep):
+class ReaderSource(_ShapedSource):
     """Batches of an AudioReader or a SyntheticReader: plan dequeues the host
     batch and holds it, take cuts it and copies the audio to the device."""
 
@@ -155,7 +172,7 @@ class ReaderSource(_EmphasisStep):
         return None
 
 
-class CorpusSource(_EmphasisStep):
+class CorpusSource(_ShapedSource):
     """Batches of a corpus.DeviceCorpus: plan reads the host index alone, take
     cuts the batch on the device (one or two launches on the training stream,
     no copy).  Step k takes batch `base` + k; `entry`: the corpus's settings
@@ -195,7 +212,7 @@ class CorpusSource(_EmphasisStep):
         if self.front is not None:
             lc = self.front(audio, lengths)
         # (an empty slot is all zeros: one sample of it gives the same)
-        audio = self._emphasise(audio, np.maximum(cb.lengths, 1))
+        audio = self._shape(audio, np.maximum(cb.lengths, 1))
         return audio, lc, cb.offsets if self.lc == 'frames' else 0
 
     def checkpoint_entry(self, step):
@@ -328,12 +345,13 @@ class StepLog(object):
             self.events.close()
 
 
-def validate(net, optimizer, vset, spec, args, emphasis=None):
+def validate(net, optimizer, vset, spec, args, emphasis=None, lpc=None):
     """Score the validation set with the weights as they are (the EMA shadow
     with --validate_ema): every rank its shard, ONE sum over the ranks
     whatever a shard holds (a set built with history: each piece behind its
     left context, which is not scored); with `emphasis` the audio is pre-emphasised
-    behind the front end, as the training batches are.  Returns
+    behind the front end, as the training batches are (with `lpc` it is
+    replaced by its excitation).  Returns
     evaluate.summary's dict."""
     from . import evaluate as ev
     swap = ev.parameters_swapped(net, optimizer.ema_flat(net)) \
@@ -344,5 +362,7 @@ def validate(net, optimizer, vset, spec, args, emphasis=None):
             batches = ev.with_features(net, spec, batches)
         if emphasis is not None:
             batches = ev.with_emphasis(emphasis, batches)
+        if lpc is not None:
+            batches = ev.with_lpc(lpc, spec, batches)
         tot = ev.totals(net, batches, args.validation_batches)
     return ev.summary(ev.sum_over_ranks(tot, net.device))

@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from wavenet import (  # noqa: E402
-    emphasis, features, input_noise, local_condition)
+    emphasis, features, input_noise, local_condition, lpc)
 from wavenet.checkpoint import (  # noqa: E402,F401
     checkpoint_path, latest_checkpoint, load, open_latest, save)
 from wavenet.cli import (  # noqa: E402
@@ -187,7 +187,10 @@ def get_arguments(argv=None):
                         'with the same history.')
     emphasis.add_cli_flag(p, train=True)
     input_noise.add_cli_flags(p, train=True)
+    lpc.add_cli_flags(p, train=True)
     args = p.parse_args(argv)
+    if lpc.flag_error(args, 'train'):
+        p.error(lpc.flag_error(args, 'train'))
     # (the InputNoise of --input_noise, or None)
     args.noise = input_noise.from_cli(p, args)
     if args.preemphasis is not None:
@@ -311,6 +314,18 @@ def emphasis_from_flags(args, opened, continued):
     else:
         continued = False       # (nothing to continue, or not our format)
     return emphasis.from_cli(args.preemphasis, stored, continued)
+
+
+def lpc_from_flags(args, spec, opened, continued):
+    """The LinearPrediction of the --lpc_* flags and the restored
+    checkpoint's 'lpc' entry over the front end `spec`, or None; as
+    emphasis_from_flags."""
+    stored = None
+    if opened is not None and opened.ckpt is not None:
+        stored = opened.ckpt.get('lpc')
+    else:
+        continued = False
+    return lpc.from_cli(args, spec, stored, continued)
 
 
 def get_default_logdir(logdir_root):
@@ -635,6 +650,12 @@ def main(argv=None):
     if built is None:
         return 1
     source, spec, lc_stats = built
+    try:
+        lp = lpc_from_flags(args, spec, opened, not is_overwritten_training)
+    except ValueError as e:
+        print(str(e))
+        return 1
+    source.lpc = lp
     # (the one place that decides what lc is: the source's, or the front
     # end's of the batch as the source cut it)
     lc_from_batch = spec is not None and source.lc is None
@@ -644,6 +665,10 @@ def main(argv=None):
     if emph is not None:
         print('  Training on the pre-emphasised signal, alpha = {!r}.'
               .format(emph.alpha))
+    lpc_entry = None if lp is None else lp.entry()
+    if lp is not None:
+        print('  Training on the linear-prediction excitation: {!r}.'
+              .format(lp))
     noise_entry = None if noise is None else noise.entry()
     if noise is not None:
         print('  Training on perturbed input codes (clean targets): '
@@ -783,7 +808,7 @@ def main(argv=None):
             if rank == 0 and step % args.checkpoint_every == 0:
                 save(net, logdir, step, optimizer, lc_entry,
                      source.checkpoint_entry(step), emph_entry,
-                     noise_entry)
+                     noise_entry, lpc_entry)
                 last_saved_step = step
                 if args.histograms:
                     save_histograms(net, logdir, step)
@@ -794,21 +819,21 @@ def main(argv=None):
                     # in order)
                     log.flush()
                     log.validation(step, training.validate(
-                        net, optimizer, vset, spec, args, emph))
+                        net, optimizer, vset, spec, args, emph, lp))
                     validated = step
         log.flush()
         if vset is not None and last_run is not None and \
                 validated != last_run:
             # after the last step
             log.validation(last_run, training.validate(
-                net, optimizer, vset, spec, args, emph))
+                net, optimizer, vset, spec, args, emph, lp))
     except KeyboardInterrupt:
         print()
     finally:
         if rank == 0 and step is not None and step > last_saved_step:
             save(net, logdir, step, optimizer, lc_entry,
                  source.checkpoint_entry(step), emph_entry,
-                     noise_entry)
+                 noise_entry, lpc_entry)
         source.stop()
         log.close()
     return 0
