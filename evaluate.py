@@ -98,6 +98,25 @@ with "stft", "mcd" and "pitch" sub-entries exactly when --synthesis_stft,
 <stem>_gl.wav.  Mel inversion by pseudo-inverse and clipping is not a
 non-negative least squares fit, so the baseline's own log-mel error is not
 zero.
+
+--synthesis_stoi true (with --synthesis true) adds short-time objective
+intelligibility (STOI, Taal et al. 2011) and its extended form (ESTOI, Jensen &
+Taal 2016) of the same de-emphasised / LPC-filtered utterances against the
+originals, on the device (wavenet/stoi.py: both sides resampled to 10 kHz,
+frames 40 dB below the original's loudest removed, the envelopes of 15
+third-octave bands correlated over segments of 30 frames)
+
+    "synthesis_stoi": {"stoi": .., "estoi": .., "clips": ..,
+                       "skipped_clips": .., "segments": .., "kept_frames": ..,
+                       "frames": .., "sample_rate": 10000}
+
+a clip's score is the mean over its segments, the entry's the mean over the
+clips that have a segment (30 kept frames, 0.4 s; the others are counted
+under "skipped_clips"); with --synthesis_baseline the baseline gains a "stoi"
+sub-entry.  These are THIS tool's STOI on the rule stated in
+include/wavenet_stoi.h: the resampler is scipy.signal.resample_poly's design,
+not Octave's, and the last full frame is included, so the third decimal need
+not match other implementations.
 """
 from __future__ import print_function
 
@@ -126,7 +145,7 @@ MCD_ORDER = 13
 SYNTHESIS_FLAGS = ('synthesis_batch', 'synthesis_schedule', 'synthesis_out',
                    'max_clips', 'seed', 'temperature', 'top_k', 'top_p',
                    'synthesis_pitch', 'synthesis_stft', 'synthesis_mcd',
-                   'synthesis_baseline')
+                   'synthesis_baseline', 'synthesis_stoi')
 BASELINE_FLAGS = ('gl_iterations', 'gl_momentum')
 BASELINES = ('griffin_lim',)
 GL_ITERATIONS, GL_MOMENTUM = 32, 0.99
@@ -256,6 +275,11 @@ def get_arguments(argv=None):
     p.add_argument('--mcd_order', type=int, default=None,
                    help='--synthesis_mcd: cepstral coefficients 1 .. N '
                    '(default 13; at most min(n_mels - 1, 64))')
+    p.add_argument('--synthesis_stoi', type=str_to_bool, default=None,
+                   help='--synthesis: also report STOI and ESTOI (short-time '
+                   'objective intelligibility at 10 kHz, this tool\'s rule: '
+                   'wavenet/stoi.py) of the generated utterances against the '
+                   'originals under "synthesis_stoi"')
     p.add_argument('--synthesis_baseline', type=str, default=None,
                    choices=BASELINES,
                    help='--synthesis: also reconstruct every utterance from '
@@ -548,6 +572,9 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None,
     if getattr(args, 'synthesis_mcd', None):
         more['synthesis_mcd'] = synthesis.mel_cepstral_distortion(
             spec, waves, audios, syn.rounds, args.mcd_order or MCD_ORDER)
+    if getattr(args, 'synthesis_stoi', None):
+        more['synthesis_stoi'] = synthesis.stoi(
+            _stoi_meter(sample_rate), waves, audios, syn.rounds)
     stems = [os.path.splitext(os.path.basename(p[1]))[0] for p in pieces]
     if args.synthesis_out:
         synthesis.write_wavs(waves, stems, args.synthesis_out, sample_rate)
@@ -558,6 +585,12 @@ def _synthesis(args, net, spec, data, sample_rate, emph=None, tracker=None,
             'samples': int(sum(a.shape[0] for a in audios)),
             'steps': syn.steps, 'occupancy': syn.occupancy,
             'log_mel_mae_db': mae, 'log_mel_lsd_db': lsd}, pitch_error, more
+
+
+def _stoi_meter(sample_rate):
+    """The stoi.Stoi of --synthesis_stoi at the set's sample rate."""
+    from wavenet import stoi
+    return stoi.Stoi(int(sample_rate))
 
 
 def _baseline(args, spec, audios, groups, tracker, stems, sample_rate):
@@ -589,6 +622,9 @@ def _baseline(args, spec, audios, groups, tracker, stems, sample_rate):
         entry['pitch'] = dict(
             synthesis.pitch_distance(tracker, waves, audios, groups),
             **_pitch_entry(tracker))
+    if getattr(args, 'synthesis_stoi', None):
+        entry['stoi'] = synthesis.stoi(_stoi_meter(sample_rate), waves,
+                                       audios, groups)
     if args.synthesis_out:
         synthesis.write_wavs(waves, [s + '_gl' for s in stems],
                              args.synthesis_out, sample_rate)

@@ -371,6 +371,26 @@ LPC_SIGNATURES = {
                                  c_int, c_float, P, c_long, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_resample.h one to one
+# (the sample-rate converter's header, bound onto the same library)
+RESAMPLE_SIGNATURES = {
+    'wn_resample_tile': (c_int, []),
+    # x, ld_x, lengths, B, T, up, down, Hh, tab, out, ld_out, stream
+    'wn_resample': (c_int, [P, c_long, P, c_int, c_int, c_int, c_int, c_int,
+                            P, P, c_long, P]),
+}
+
+# name -> (restype, argtypes); mirrors include/wavenet_stoi.h one to one
+# (STOI / ESTOI's header, bound onto the same library)
+STOI_SIGNATURES = {
+    'wn_stoi_band_edge': (c_int, [c_int]),
+    'wn_stoi_scratch_bytes': (c_long, [c_int, c_int]),
+    # gen, ld_gen, org, ld_org, lengths, B, T, window, basis, scratch,
+    # stoi_sum, estoi_sum, segments, kept, stream
+    'wn_stoi': (c_int, [P, c_long, P, c_long, P, c_int, c_int, P, P, P, P, P,
+                        P, P, P]),
+}
+
 
 _lib = None
 
@@ -392,7 +412,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
                   LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES,
-                  GRIFFIN_LIM_SIGNATURES, LPC_SIGNATURES):
+                  GRIFFIN_LIM_SIGNATURES, LPC_SIGNATURES,
+                  RESAMPLE_SIGNATURES, STOI_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

@@ -549,6 +549,18 @@ def stft_distance(dist, generated, original, groups):
     return spectral.StftSums.cat(parts).summary(np.concatenate(lengths))
 
 
+def stoi(meter, generated, original, groups):
+    """STOI and ESTOI (`meter`: a stoi.Stoi at the utterances' sample rate) of
+    generated[u] against original[u], float [n_u] each, over all utterances,
+    in the zero-padded groups of log_mel_distance with `lengths` set.  A
+    clip's sums do not depend on its group.  Returns StoiSums.summary() over
+    the utterances in the order of `groups`.  One host wait, at the end."""
+    from . import stoi as stoi_
+    return stoi_.StoiSums.cat(
+        [meter(g, o, n) for g, o, n in
+         _padded_groups(generated, original, groups)]).summary()
+
+
 def mel_cepstral_distortion(spec, generated, original, groups, order=13):
     """The mel-cepstral distortion in dB (spectral.mcd_db: DCT-II of the RAW
     log-mel features, the spec log_mel_distance picks, coefficients 1 ..
