@@ -129,10 +129,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 from wavenet import (  # noqa: E402
-    emphasis, features, input_noise, local_condition, lpc)
+    emphasis, features, input_noise, local_condition, lpc, mol)
 from wavenet.checkpoint import (  # noqa: E402
     open_ema_checkpoint, restore, stored_emphasis, stored_lc_features,
-    stored_lpc)
+    stored_lpc, stored_output)
 from wavenet.cli import (  # noqa: E402
     PIECE_HISTORY_HELP, model_from_params, piece_history, piece_history_arg,
     str_to_bool)
@@ -363,6 +363,19 @@ def main(argv=None):
         return 1
     with open(args.wavenet_params, 'r') as f:
         wavenet_params = json.load(f)
+    try:
+        # (K, log_scale_min) of a checkpoint trained with --output_mixture:
+        # scored on the 65536 levels, "accuracy": null
+        head = mol.check_entry(stored_output(args.checkpoint))
+    except ValueError as e:
+        print(str(e))
+        return 1
+    if head is not None and (args.synthesis or args.noise is not None):
+        print('%s: the checkpoint holds a mixture-of-logistics model; %s'
+              % ('--synthesis true' if args.synthesis else '--input_noise',
+                 'its inputs are float audio, not codes' if not args.synthesis
+                 else mol.FOLLOW_UP))
+        return 1
     if args.noise is not None and wavenet_params.get('scalar_input'):
         print('--input_noise is not for scalar_input models: their network '
               'input is the float audio, not the codes')
@@ -433,7 +446,7 @@ def main(argv=None):
         global_condition_cardinality=args.gc_cardinality,
         local_condition_channels=args.lc_channels,
         local_condition_upsample_scales=lc_scales,
-        local_condition_context=lc_ctx)
+        local_condition_context=lc_ctx, **mol.model_keywords(head))
     why = restore(net, args.checkpoint, args.use_ema, ckpt,
                   check_lc=args.lc_channels is not None)
     if why:

@@ -64,9 +64,10 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 
 import numpy as np  # noqa: E402
 from wavenet import (  # noqa: E402
-    emphasis, features, local_condition, lpc, sampling)
+    emphasis, features, local_condition, lpc, mol, sampling)
 from wavenet.checkpoint import (  # noqa: E402,F401
     context_mismatch, open_ema_checkpoint, restore, stored_emphasis, stored_lpc,
+    stored_output,
     stored_lc_features, upsampler_mismatch)
 from wavenet.cli import model_from_params, str_to_bool  # noqa: E402
 
@@ -262,6 +263,36 @@ def write_wav(waveform, sample_rate, filename):
     print('Updated wav file at {}'.format(filename))
 
 
+def write_wav16(waveform, sample_rate, filename):
+    """16-bit PCM: sample x becomes its level (wavenet/mol.py's rule) minus
+    32768, so a waveform of level centres is written without loss."""
+    from scipy.io import wavfile
+    lv, _ = mol.levels_reference(np.asarray(waveform, np.float32))
+    wavfile.write(filename, int(sample_rate),
+                  (lv.astype(np.int32) - 32768).astype(np.int16))
+    print('Updated wav file at {}'.format(filename))
+
+
+def _mixture_seed(args, sample_rate, emph):
+    """A mixture-of-logistics model's seed as float samples on the 16-bit
+    grid: --wav_seed's (silence-trimmed, pre-emphasised where the model was
+    trained so, cut to the window), else one level drawn with --seed."""
+    if args.wav_seed:
+        from wavenet.audio_reader import load_wav, trim_silence
+        audio = trim_silence(load_wav(args.wav_seed, sample_rate),
+                             SILENCE_THRESHOLD)
+        audio = np.asarray(audio, np.float32).reshape(-1)
+        if emph is not None and audio.shape[0]:
+            audio = emph.pre(audio).cpu().numpy()
+        audio = audio[:args.window]
+    else:
+        audio = None
+    if audio is None or audio.shape[0] == 0:
+        lv = np.random.default_rng(args.seed).integers(mol.LEVELS, size=(1,))
+        return mol.centres(lv).tolist()
+    return mol.levels_reference(audio)[1].tolist()
+
+
 def create_seed(filename, sample_rate, quantization_channels,
                 window_size=WINDOW, silence_threshold=SILENCE_THRESHOLD,
                 emph=None):
@@ -291,9 +322,23 @@ def main(argv=None):
     try:
         emph = emphasis.from_cli(args.preemphasis,
                                  stored_emphasis(args.checkpoint, ckpt))
+        # (K, log_scale_min) of a checkpoint trained with --output_mixture
+        head = mol.check_entry(stored_output(args.checkpoint, ckpt))
     except ValueError as e:
         print(str(e))
         return 1
+    if head is not None:
+        why = None
+        if args.fast_generation:
+            why = ('--fast_generation true: the checkpoint holds a mixture-'
+                   'of-logistics model; ' + mol.FOLLOW_UP)
+        elif args.top_k is not None or args.top_p is not None:
+            why = ('--top_k / --top_p truncate a distribution over codes; '
+                   'the checkpoint holds a mixture-of-logistics model, whose '
+                   'draw has none (use --temperature)')
+        if why:
+            print(why)
+            return 1
     # linear prediction: on by the flag or by the checkpoint's entry
     lpc_stored = stored_lpc(args.checkpoint, ckpt)
     lpc_on = (args.lpc_order if args.lpc_order is not None else
@@ -413,7 +458,7 @@ def main(argv=None):
         global_condition_cardinality=args.gc_cardinality,
         local_condition_channels=None if lc_rows is None else lc_rows.shape[1],
         local_condition_upsample_scales=lc_scales,
-        local_condition_context=lc_ctx)
+        local_condition_context=lc_ctx, **mol.model_keywords(head))
     why = restore(net, args.checkpoint, args.use_ema, ckpt,
                   check_lc=lc_rows is not None)
     if why:
@@ -426,7 +471,10 @@ def main(argv=None):
     Q = wavenet_params['quantization_channels']
     rate = wavenet_params['sample_rate']
     gc = None if args.gc_id is None else [args.gc_id]
-    if args.wav_seed:
+    if head is not None:
+        # float samples on the 16-bit grid (the centres of their levels)
+        waveform = _mixture_seed(args, rate, emph)
+    elif args.wav_seed:
         waveform = create_seed(args.wav_seed, rate, Q, args.window,
                                emph=emph).cpu().numpy().tolist()
     else:
@@ -438,7 +486,13 @@ def main(argv=None):
     de = None if emph is None else emphasis.DeStream(emph)
 
     def dump(codes):
-        if args.wav_out_path:
+        if args.wav_out_path and head is not None:
+            out = np.asarray(codes, np.float32)
+            if de is not None:
+                out = de.feed(out)
+            out = _lpc_filter(lp, lp_cf, out, n_seed)
+            write_wav16(out, rate, args.wav_out_path)
+        elif args.wav_out_path:
             out = mu_law_decode(np.asarray(codes, np.int32), Q).cpu().numpy()
             if de is not None:
                 out = de.feed(out)
@@ -461,6 +515,36 @@ def main(argv=None):
     if args.clips > 1:
         return _main_clips(args, net, waveform, Q, rate, logdir, rows, emph,
                            lp, lp_cf)
+    if head is not None:
+        # the naive path: a receptive-field window, predict_mixture, one
+        # wn_mol_sample draw per step with counter = step
+        net.reserve(1, min(args.window, len(waveform) + args.samples))
+        levels = []
+        for step in range(args.samples):
+            window = waveform[-args.window:]
+            lc = None
+            if lc_full is not None:
+                e = len(waveform)
+                lc = lc_full[e - len(window):e][None]
+            params = net.predict_mixture(np.asarray(window, np.float32), gc,
+                                         local_condition=lc)
+            lv, ce = mol.sample(params[None], [args.seed], [step],
+                                args.temperature)
+            levels.append(int(lv[0]))
+            waveform.append(float(ce[0]))
+            if (step + 1) % 100 == 0:
+                print('Sample {:3<d}/{:3<d}'.format(step + 1, args.samples),
+                      end='\r')
+            if (args.wav_out_path and args.save_every and
+                    (step + 1) % args.save_every == 0):
+                dump(waveform)
+        print()
+        os.makedirs(logdir, exist_ok=True)
+        np.save(os.path.join(logdir, 'generated_levels.npy'),
+                np.asarray(levels, np.int32))
+        dump(waveform)
+        print('Finished generating. Levels saved under {}.'.format(logdir))
+        return 0
     if args.fast_generation:
         if args.wav_seed:
             print('Priming generation with {} seed samples...'

@@ -391,6 +391,27 @@ STOI_SIGNATURES = {
                         P, P, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_mol.h one to one
+# (the mixture-of-logistics head's header, bound onto the same library)
+MOL_SIGNATURES = {
+    # audio, lengths, levels_out, centres_out, B, T, stream
+    'wn_mol_quantize': (c_int, [P, P, P, P, c_int, c_int, P]),
+    # logits, ld, levels, starts, lengths, inv_den, dlogits, loss_partials,
+    # B, T, K, log_scale_min, stream
+    'wn_mol_loss': (c_int, [P, c_long, P, P, P, P, P, P, c_int, c_int, c_int,
+                            c_float, P]),
+    'wn_mol_score_scratch_floats': (c_long, [c_long]),
+    # logits, ld, levels, starts, lengths, row_nll, clip_nll, clip_count,
+    # scratch, B, T, K, log_scale_min, stream
+    'wn_mol_score': (c_int, [P, c_long, P, P, P, P, P, P, P, c_int, c_int,
+                             c_int, c_float, P]),
+    # logits_row, K, log_scale_min, out, stream
+    'wn_mol_params_row': (c_int, [P, c_int, c_float, P, P]),
+    # params, seeds, counters, temperature, levels_out, centres_out, R, K,
+    # stream
+    'wn_mol_sample': (c_int, [P, P, P, c_float, P, P, c_int, c_int, P]),
+}
+
 
 _lib = None
 
@@ -413,7 +434,7 @@ def load():
     for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
                   LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES,
                   GRIFFIN_LIM_SIGNATURES, LPC_SIGNATURES,
-                  RESAMPLE_SIGNATURES, STOI_SIGNATURES):
+                  RESAMPLE_SIGNATURES, STOI_SIGNATURES, MOL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

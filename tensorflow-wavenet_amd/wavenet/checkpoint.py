@@ -2,7 +2,8 @@
 
 train.py writes torch files holding {'variables': {reference variable name:
 tensor}, 'step'} and, where the run has them, 'optimizer', 'ema_variables',
-'lc_features', 'device_corpus', 'emphasis', 'input_noise' and 'lpc'; the step is parsed from the file name, as
+'lc_features', 'device_corpus', 'emphasis', 'input_noise', 'lpc' and
+'output'; the step is parsed from the file name, as
 in the reference (train.py:104-134 there).  The reference's own TensorFlow
 checkpoints are read too (tf_checkpoint.py).  train.py, generate.py and
 evaluate.py import their checkpoint functions from here.
@@ -31,7 +32,8 @@ def checkpoint_path(logdir, step):
 
 
 def save(net, logdir, step, optimizer=None, lc_features=None,
-         device_corpus=None, emphasis=None, input_noise=None, lpc=None):
+         device_corpus=None, emphasis=None, input_noise=None, lpc=None,
+         output=None):
     """`optimizer`: its step count, slots and shadow go in as 'optimizer'
     and, with EMA weights, the shadow as 'ema_variables' (the keys of
     'variables').  `lc_features`: the front end's settings
@@ -45,7 +47,10 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
     (input_noise.InputNoise.entry: {'prob', 'width', 'seed'}), stored under
     'input_noise', likewise only where given.  `lpc`: the linear prediction
     whose excitation the model was trained on (lpc.LinearPrediction.entry:
-    {'order', 'noise', 'lag_window', 'gain'}), stored under 'lpc', likewise."""
+    {'order', 'noise', 'lag_window', 'gain'}), stored under 'lpc', likewise.
+    `output`: the head of a model that does not end in the softmax
+    (mol.output_entry: {'kind': 'mol', 'components', 'log_scale_min',
+    'levels'}), stored under 'output', likewise."""
     print('Storing checkpoint to {} ...'.format(logdir), end="")
     sys.stdout.flush()
     os.makedirs(logdir, exist_ok=True)
@@ -61,6 +66,8 @@ def save(net, logdir, step, optimizer=None, lc_features=None,
         ckpt['input_noise'] = input_noise
     if lpc is not None:
         ckpt['lpc'] = lpc
+    if output is not None:
+        ckpt['output'] = output
     if optimizer is not None:
         ckpt['optimizer'] = optimizer.state_dict()
         if optimizer.ema_decay is not None:
@@ -210,6 +217,16 @@ def stored_lpc(path, ckpt=None):
             return None
         ckpt = torch.load(path, map_location='cpu')
     return ckpt.get('lpc')
+
+
+def stored_output(path, ckpt=None):
+    """The 'output' entry train.py --output_mixture wrote into the
+    checkpoint at `path` (`ckpt` where the caller holds it), else None."""
+    if ckpt is None:
+        if tf_checkpoint.checkpoint_format(path) or not os.path.isfile(path):
+            return None
+        ckpt = torch.load(path, map_location='cpu')
+    return ckpt.get('output')
 
 
 def restore(net, path, use_ema=False, ckpt=None, check_lc=False):

@@ -205,8 +205,13 @@ def totals(net, batches, max_batches=None, *, input_noise=None, rank=0,
                 clips + np.arange(b, dtype=np.int64)) * world + rank)
         s = net.score(audio, gc, local_condition_batch=lc,
                       local_condition_offset=off, lengths=lengths, **kw)
+        # (a mixture-of-logistics head has no arg-max: its hits are NaN and
+        # summary reports no accuracy)
+        hits = s.correct.sum().to(torch.float64) if s.correct is not None \
+            else torch.full((), float('nan'), dtype=torch.float64,
+                            device=s.nll.device)
         part = torch.stack([s.nll.sum(), s.count.sum().to(torch.float64),
-                            s.correct.sum().to(torch.float64)])
+                            hits])
         tot = part if tot is None else tot + part
         clips += int(np.shape(lengths)[0])
     if tot is None:
@@ -221,7 +226,8 @@ def summary(tot):
     nats = nll / count if count else float('nan')
     return {'nll_per_sample': nats,
             'bits_per_sample': nats / math.log(2.0),
-            'accuracy': correct / count if count else float('nan'),
+            'accuracy': None if correct != correct else
+            correct / count if count else float('nan'),
             'samples': int(count), 'clips': int(clips)}
 
 

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import local_condition as lcond
+from . import mol
 from . import sampling
 from . import train_pass
 
@@ -513,13 +514,19 @@ def _run_persistent(net, g, args, io, iob, n_steps, lcargs):
     return False
 
 
+def _follow_up(net):
+    """What a refusal of a scalar_input (softmax or mixture head) model
+    adds: fast generation for it is planned, not impossible."""
+    return '; ' + mol.FOLLOW_UP if net.scalar_input else ''
+
+
 def predict_proba_incremental(net, waveform, global_condition, push, lc=None):
     if net.filter_width > 2:
         raise NotImplementedError("Incremental generation does not "
                                   "support filter_width > 2.")
     if net.scalar_input:
         raise NotImplementedError("Scalar input is not supported by "
-                                  "fast generation.")
+                                  "fast generation yet: " + mol.FOLLOW_UP)
     net._check_supported()
     g = generator(net, global_condition)
     w = waveform
@@ -535,10 +542,11 @@ def predict_proba_incremental(net, waveform, global_condition, push, lc=None):
 def generate(net, num_samples, seed_samples, temperature, global_condition,
              seed, return_proba_every, lc=None, top_k=None, top_p=None):
     trunc = sampling.resolve(top_k, top_p, net.Q)
-    net._check_supported()
     if net.filter_width > 2 or net.scalar_input:
         raise NotImplementedError('fast generation needs filter_width 2 '
-                                  'and one-hot input (model.py:597-603)')
+                                  'and one-hot input (model.py:597-603)'
+                                  + _follow_up(net))
+    net._check_supported()
     lc = _lc_device(net, lc)
     if seed_samples is None:
         seed_samples = [net.Q // 2]
@@ -564,7 +572,8 @@ def generate(net, num_samples, seed_samples, temperature, global_condition,
 def prime(net, codes, global_condition, lc=None):
     if net.filter_width > 2 or net.scalar_input:
         raise NotImplementedError('fast generation needs filter_width 2 '
-                                  'and one-hot input (model.py:597-603)')
+                                  'and one-hot input (model.py:597-603)'
+                                  + _follow_up(net))
     net._check_supported()
     g = generator(net, global_condition)
     reset(net)
@@ -607,7 +616,8 @@ def _batch_args(net, seeds, per_stream, global_condition, temperature,
         raise NotImplementedError(
             'generate_batch needs filter_width 2 and one-hot input '
             '(model.py:597-603), as every fast generation path does; use '
-            'predict_proba (generate.py --fast_generation false)')
+            'predict_proba (generate.py --fast_generation false)'
+            + _follow_up(net))
     if net.S > 512 or net.Q > 512 or net.L > 64:
         raise NotImplementedError(
             'generate_batch supports at most 512 skip / quantization '

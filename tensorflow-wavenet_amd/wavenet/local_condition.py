@@ -36,8 +36,11 @@ def configure(net, lc, scales, p):
             why = 'more than 32 residual / dilation channels'
         elif int(net.filter_width) != 2:
             why = 'filter_width %d' % int(net.filter_width)
-        elif net.scalar_input:
-            why = 'scalar_input'
+        elif net.scalar_input and not getattr(net, 'mol_K', 0):
+            # (a mixture-of-logistics model reads scalar input and carries
+            # LC: the LC arithmetic lives in the stack launches, the scalar
+            # causal layer is a launch of its own)
+            why = 'scalar_input without output_mixture'
         if why:
             raise NotImplementedError('%s: %s' % (why, net.LC_SUPPORTED))
         net.Lc = int(lc)

@@ -25,6 +25,7 @@ from . import _lib
 from . import fastgen
 from . import features
 from . import local_condition as lcond
+from . import mol
 from . import sampling
 from . import train_pass
 from . import workspace
@@ -165,7 +166,20 @@ class WaveNetModel(object):
                  *,
                  local_condition_channels=None,
                  local_condition_upsample_scales=None,
-                 local_condition_context=None):
+                 local_condition_context=None,
+                 output_mixture=None,
+                 mixture_log_scale_min=-14.0):
+        # mixture-of-logistics head over 65536 levels (wavenet/mol.py):
+        # output_mixture=K components, 3 Kp output columns [pi | mu | beta_raw]
+        # in the place of the softmax's quantization_channels, which the
+        # network then does not read
+        self.output_mixture = output_mixture
+        self.mixture_log_scale_min = mixture_log_scale_min
+        self.mol_K = self.mol_Kp = 0
+        if output_mixture is not None:
+            self.mol_K, self.mol_log_scale_min = mol.check_config(
+                output_mixture, mixture_log_scale_min, scalar_input)
+            self.mol_Kp = mol.padded(self.mol_K)
         self.batch_size = batch_size
         self.dilations = list(dilations)
         self.filter_width = filter_width
@@ -279,7 +293,7 @@ class WaveNetModel(object):
             # names / shapes / checkpoints); every compute entry point raises.
             self.device = torch.device(device)
         self.L, self.S, self.Q = len(self.dilations), skip_channels, \
-            quantization_channels
+            3 * self.mol_Kp if self.mol_K else quantization_channels
         self.R, self.D = residual_channels, dilation_channels
         self.G = global_condition_channels
         self.card = global_condition_cardinality
@@ -327,9 +341,11 @@ class WaveNetModel(object):
 
     # local conditioning's limits (checked in wavenet/local_condition.py)
     LC_SUPPORTED = ('local conditioning is supported for residual / dilation '
-                    'channels <= 32, filter_width 2 and one-hot input (not '
-                    'scalar_input), on the persistent stack launches '
-                    '(stack_fwd / stack_bwd = True)')
+                    'channels <= 32, filter_width 2 and one-hot input, or '
+                    'scalar_input with a mixture-of-logistics head '
+                    '(output_mixture: training, scoring and predict_mixture, '
+                    'not yet fast generation), on the persistent stack '
+                    'launches (stack_fwd / stack_bwd = True)')
     LC_UPSAMPLE_MAX_LAYERS = 8
     LC_UPSAMPLE_MAX_HOP = 4096
     LC_UPSAMPLE_MAX_CHANNELS = 512     # wn_lc_upsample_* (LCUP_MAX_LC)
@@ -799,7 +815,12 @@ class WaveNetModel(object):
         history included, moved as InputNoise states with the key
         noise_keys[b] -- while every target stays the clean code.  One fused
         launch encodes the audio and perturbs it.  Not for scalar_input
-        models, whose network input is the float audio.'''
+        models, whose network input is the float audio.
+
+        A model built with output_mixture=K (wavenet/mol.py) snaps the audio
+        to 65536 levels on the device, reads their centres and is trained on
+        the discretised mixture-of-logistics likelihood of level j[t + 1] in
+        the place of the cross-entropy; everything above holds unchanged.'''
         self._check_noise(input_noise, noise_keys, 'loss')
         self._check_supported()
         B = self.batch_size
@@ -812,6 +833,13 @@ class WaveNetModel(object):
                                    a.shape[1], 'loss')
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'loss')
+        if self.mol_K:
+            # centres into ws.audio, levels where the labels go
+            ws = self._workspace(B, a.shape[1], backward)
+            mol.stage(self, ws, a, mask)
+            return self._loss(ws.q.view(B, -1), global_condition_batch,
+                              l2_regularization_strength, backward, ws.audio,
+                              lc, mask, hist)
         if input_noise is None:
             q, q_in = mu_law_encode(a, self.Q), None
         else:
@@ -831,6 +859,7 @@ class WaveNetModel(object):
         [batch_size, T]): what the network reads in place of q, which stays
         the target of every row (input_noise.InputNoise.codes makes such
         codes); without it nothing but q is used, as ever."""
+        self._refuse_mixture_codes('loss_from_codes')
         if input_codes is not None:
             self._refuse_scalar_noise('loss', 'input_codes')
         self._check_supported()
@@ -853,6 +882,10 @@ class WaveNetModel(object):
                              % what)
         if input_noise is None:
             return
+        if self.mol_K:
+            raise ValueError('%s: input_noise is not for a mixture-of-'
+                             'logistics model: its inputs are float audio on '
+                             'the 16-bit grid, not codes' % what)
         from .input_noise import InputNoise
         if not isinstance(input_noise, InputNoise):
             raise ValueError('%s: input_noise must be an InputNoise, got %r'
@@ -864,6 +897,14 @@ class WaveNetModel(object):
             raise ValueError(
                 '%s: %s is not for scalar_input models: their network input '
                 'is the float audio, not the codes' % (what, name))
+
+    def _refuse_mixture_codes(self, what):
+        if self.mol_K:
+            raise ValueError(
+                '%s: a mixture-of-logistics model (output_mixture=%d) has no '
+                'mu-law codes: its inputs and targets are the 65536 levels '
+                'of the float audio; use loss / score / predict_mixture'
+                % (what, self.mol_K))
 
     def _check_input_codes(self, input_codes, q, what):
         """input_codes as device int32 [B, T] beside codes q [B, T], or
@@ -909,8 +950,12 @@ class WaveNetModel(object):
                           'was never joined (no optimizer.minimize followed): '
                           'joined and dropped now')
             parallel.abandon_tail_allreduce(self)
-        q_lab = train_pass.stage_codes(ws, q, q_in)
-        if self.scalar_input:
+        if self.mol_K:
+            # (loss() quantised straight into ws.q and ws.audio: mol.stage)
+            q_lab = ws.q
+        else:
+            q_lab = train_pass.stage_codes(ws, q, q_in)
+        if self.scalar_input and not self.mol_K:
             # network input is the raw float audio (model.py:645-648)
             if audio is None:
                 raise ValueError('scalar_input needs the float audio')
@@ -924,7 +969,18 @@ class WaveNetModel(object):
             self, ws, backward, l2=l2_regularization_strength is not None)
         train_pass.run_pass(self, 'fwd', ws, ids, path)
         quirk = 1 if self.tf_xent_zero_label_quirk else 0
-        if mask is None:
+        if self.mol_K:
+            # one entry for plain, masked and windowed (null pointers: plain)
+            den = float(N)
+            if mask is not None:
+                lengths, den = mask
+                inv = np.float32(1.0) / np.float32(den)
+                ws.xent_mask.copy_(torch.from_numpy(np.concatenate(
+                    [lengths, np.array([inv], np.float32).view(np.int32)])))
+                if hist is not None:
+                    ws.xent_hist.copy_(torch.from_numpy(hist))
+            mol.loss(self, ws, mask is not None, hist is not None, backward)
+        elif mask is None:
             den = float(N)
             _lib.call('wn_xent', _lib.ptr(ws.logits), self.Q, _lib.ptr(q_lab),
                       _lib.ptr(ws.logits) if backward else None,
@@ -1022,7 +1078,12 @@ class WaveNetModel(object):
 
         input_noise, noise_keys (as for `loss`, one key per row of the
         batch): the network reads perturbed codes, the scored targets stay
-        clean.'''
+        clean.
+
+        A mixture-of-logistics model (output_mixture=K) is scored on the
+        65536 levels: nll is the sum of -log P(level j[t + 1]) under the
+        mixture, the relations above hold, and correct is None (an arg-max
+        is not defined for this head).'''
         self._check_noise(input_noise, noise_keys, 'score')
         self._check_supported()
         a = input_batch
@@ -1037,6 +1098,12 @@ class WaveNetModel(object):
         lc = lcond.check(self, local_condition_batch, local_condition_offset,
                          B, a.shape[1], 'score')
         from . import scoring
+        if self.mol_K:
+            ws = self._workspace(B, a.shape[1], False)
+            mol.stage(self, ws, a, mask)
+            return scoring.score(self, ws.q.view(B, -1),
+                                 global_condition_batch, ws.audio, lc, mask,
+                                 per_sample, hist)
         if input_noise is None:
             q, q_in = mu_law_encode(a, self.Q), None
         else:
@@ -1053,6 +1120,7 @@ class WaveNetModel(object):
         reshaped to [batch_size, -1]); audio: the float audio a scalar_input
         model needs; input_codes (device int32, q's shape): what the network
         reads in place of q, which stays the target."""
+        self._refuse_mixture_codes('score_from_codes')
         if input_codes is not None:
             self._refuse_scalar_noise('score', 'input_codes')
         self._check_supported()
@@ -1100,6 +1168,10 @@ class WaveNetModel(object):
         (or [T, Lc] with batch_size 1), row t beside waveform sample t.  The
         returned distribution is that of the sample after the last one, so
         the last row conditions it.'''
+        if self.mol_K:
+            raise ValueError('predict_proba: a mixture-of-logistics model '
+                             'has no probability vector over codes; use '
+                             'predict_mixture')
         self._check_supported()
         B = self.batch_size
         w = waveform
@@ -1123,6 +1195,37 @@ class WaveNetModel(object):
         # 0, or NaN when a dependency wait of the forward stack launch
         # expired: wrong probabilities are never returned silently
         return out + ws.loss_parts[0]
+
+    def predict_mixture(self, audio_so_far, global_condition=None, *,
+                        local_condition=None):
+        '''The mixture of the next sample given all samples so far: the
+        counterpart of predict_proba for a model built with
+        output_mixture=K.  audio_so_far: float samples, anything reshapeable
+        to [batch_size, -1]; they are snapped to the 65536 levels and the
+        network reads the centres, as in training.  local_condition: as
+        predict_proba's.  Returns device float32 [3, K] of the last row of
+        the last clip: log_softmax(pi), mu and the clamped beta
+        (wn_mol_params_row), which mol.sample draws from.'''
+        if not self.mol_K:
+            raise ValueError('predict_mixture: this model was built without '
+                             'output_mixture; use predict_proba')
+        self._check_supported()
+        B = self.batch_size
+        a = audio_so_far
+        if not isinstance(a, torch.Tensor):
+            a = torch.as_tensor(np.asarray(a), dtype=torch.float32)
+        a = a.to(device=self.device, dtype=torch.float32).reshape(B, -1)
+        T = a.shape[1]
+        lc = lcond.rows(self, local_condition, B, T, 'predict_mixture')
+        ws = self._workspace(B, T, False)
+        mol.stage(self, ws, a, None)
+        ids = self._gc_ids(global_condition, B)
+        lcond.fill(self, lc, ws)
+        train_pass.run_pass(self, 'fwd', ws, ids,
+                            train_pass.step_path(self, ws, False))
+        # 0, or NaN when a dependency wait of the forward stack launch
+        # expired (as predict_proba)
+        return mol.params_row(self, ws.logits[B * T - 1]) + ws.loss_parts[0]
 
     # ------------------------------------------ fast generation (fastgen.py)
     FASTGEN_MAX_CHANNELS = 1024    # wn_fastgen_run_wide (FGW_MAXC)

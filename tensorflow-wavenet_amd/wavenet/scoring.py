@@ -7,10 +7,12 @@ import torch
 
 from . import _lib
 from . import local_condition as lcond
+from . import mol
 from . import train_pass
 
 # nll float64 [B], count int32 [B], correct int32 [B] (device tensors, one
-# entry per clip), per_sample float32 [B, T] or None
+# entry per clip), per_sample float32 [B, T] or None.  correct is None for a
+# mixture-of-logistics model: an arg-max is not defined for that head
 Score = collections.namedtuple('Score', 'nll count correct per_sample')
 
 
@@ -23,6 +25,10 @@ def score(net, q, global_condition_batch, audio, lc, mask, per_sample,
     device."""
     B, T = q.shape
     ws = net._workspace(B, T, False)
+    if net.mol_K:
+        # (WaveNetModel.score quantised into ws.q and ws.audio: mol.stage)
+        return _score_mixture(net, ws, global_condition_batch, lc, mask,
+                              per_sample, hist)
     q_lab = train_pass.stage_codes(ws, q, q_in)
     if net.scalar_input:
         if audio is None:
@@ -63,3 +69,27 @@ def score(net, q, global_condition_batch, audio, lc, mask, per_sample,
     # 0, or NaN when a dependency wait of the forward stack launch expired
     # (as predict_proba): a wrong score is never returned silently
     return Score(nll + ws.loss_parts[0], count, correct, rows)
+
+
+def _score_mixture(net, ws, global_condition_batch, lc, mask, per_sample,
+                   hist):
+    """score for a model built with output_mixture: the same pass, then
+    wn_mol_score on the levels in ws.q (csrc/wn_mol.hip)."""
+    B, T, dev = ws.B, ws.T, net.device
+    ids = net._gc_ids(global_condition_batch, B)
+    lcond.fill(net, lc, ws)
+    train_pass.run_pass(net, 'fwd', ws, ids,
+                        train_pass.step_path(net, ws, False))
+    nll = torch.empty(B, dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    rows = torch.empty((B, T), dtype=torch.float32, device=dev) \
+        if per_sample else None
+    lengths = None
+    if mask is not None:
+        lengths = ws.xent_mask[:B]
+        lengths.copy_(torch.from_numpy(mask[0]))
+    if hist is not None:
+        ws.xent_hist.copy_(torch.from_numpy(hist))
+    mol.score(net, ws, lengths, None if hist is None else ws.xent_hist, rows,
+              nll, count)
+    return Score(nll + ws.loss_parts[0], count, None, rows)

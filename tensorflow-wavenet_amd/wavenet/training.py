@@ -326,10 +326,11 @@ class StepLog(object):
     def validation(self, k, res):
         """The validation line after step k (res: evaluate.summary's)."""
         if self.rank == 0:
+            # (a mixture-of-logistics head reports no accuracy)
             print('step {:d} - validation loss = {:.3f}, bits/sample = {:.3f}'
-                  ', accuracy = {:.3f}'.format(
-                      k, res['nll_per_sample'], res['bits_per_sample'],
-                      res['accuracy']))
+                  .format(k, res['nll_per_sample'], res['bits_per_sample']) +
+                  ('' if res['accuracy'] is None else
+                   ', accuracy = {:.3f}'.format(res['accuracy'])))
             self._write({
                 'step': k, 'validation_loss': res['nll_per_sample'],
                 'validation_bits': res['bits_per_sample'],

@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tensorflow-wavenet_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from wavenet import (  # noqa: E402
-    emphasis, features, input_noise, local_condition, lpc)
+    emphasis, features, input_noise, local_condition, lpc, mol)
 from wavenet.checkpoint import (  # noqa: E402,F401
     checkpoint_path, latest_checkpoint, load, open_latest, save)
 from wavenet.cli import (  # noqa: E402
@@ -188,7 +188,10 @@ def get_arguments(argv=None):
     emphasis.add_cli_flag(p, train=True)
     input_noise.add_cli_flags(p, train=True)
     lpc.add_cli_flags(p, train=True)
+    mol.add_cli_flags(p)
     args = p.parse_args(argv)
+    # ((K, log_scale_min) of --output_mixture, or None)
+    args.mixture = mol.from_cli(p, args)
     if lpc.flag_error(args, 'train'):
         p.error(lpc.flag_error(args, 'train'))
     # (the InputNoise of --input_noise, or None)
@@ -666,6 +669,20 @@ def main(argv=None):
         print('  Training on the pre-emphasised signal, alpha = {!r}.'
               .format(emph.alpha))
     lpc_entry = None if lp is None else lp.entry()
+    output_entry = None if args.mixture is None else \
+        mol.output_entry(*args.mixture)
+    if opened is not None and opened.ckpt is not None:
+        # (a checkpoint trained with another head holds variables of another
+        # shape)
+        try:
+            mol.same_entry(opened.ckpt.get('output'),
+                           *(args.mixture or (None, None)))
+        except ValueError as e:
+            print(str(e))
+            return 1
+    if args.mixture is not None:
+        print('  Training a mixture of {} logistics over 65536 levels '
+              '(log scale floor {!r}).'.format(*args.mixture))
     if lp is not None:
         print('  Training on the linear-prediction excitation: {!r}.'
               .format(lp))
@@ -684,7 +701,7 @@ def main(argv=None):
         global_condition_cardinality=source.gc_category_cardinality,
         local_condition_channels=args.lc_channels,
         local_condition_upsample_scales=lc_scales,
-        local_condition_context=lc_ctx)
+        local_condition_context=lc_ctx, **mol.model_keywords(args.mixture))
     l2 = args.l2_regularization_strength or None
     try:
         optimizer = optimizer_factory[args.optimizer](
@@ -808,7 +825,7 @@ def main(argv=None):
             if rank == 0 and step % args.checkpoint_every == 0:
                 save(net, logdir, step, optimizer, lc_entry,
                      source.checkpoint_entry(step), emph_entry,
-                     noise_entry, lpc_entry)
+                     noise_entry, lpc_entry, output_entry)
                 last_saved_step = step
                 if args.histograms:
                     save_histograms(net, logdir, step)
@@ -833,7 +850,7 @@ def main(argv=None):
         if rank == 0 and step is not None and step > last_saved_step:
             save(net, logdir, step, optimizer, lc_entry,
                  source.checkpoint_entry(step), emph_entry,
-                 noise_entry, lpc_entry)
+                 noise_entry, lpc_entry, output_entry)
         source.stop()
         log.close()
     return 0
