@@ -178,16 +178,18 @@ def lc_rows(v, lc, B, T, scales=None, offsets=0):
 
 
 def network(var, dilations, x_in, target, den, head, lc=None, scales=None,
-            gc_ids=None, use_biases=False, relu_masks=None, grads=True):
+            gc_ids=None, use_biases=False, relu_masks=None, grads=True,
+            offsets=0):
     """The float64 network on the scalar input x_in [B, T] (what the device
     network reads: the centres).  target int [B, T], -1 for a row without
-    one; den: the mean's denominator; head: (K, log_scale_min).
+    one; den: the mean's denominator; head: (K, log_scale_min); offsets: the
+    timeline position of each clip's first sample (frames through `scales`).
     Returns (loss, gradient tree or None, head outputs [B, T, Q] numpy, row
     nll [B, T] numpy)."""
     v = lc_ref._to_torch(var)
     x = torch.as_tensor(np.asarray(x_in, np.float64))
     B, T = x.shape
-    lct = lc_rows(v, lc, B, T, scales)
+    lct = lc_rows(v, lc, B, T, scales, offsets)
     raw = forward(v, dilations, x, lct, gc_ids, use_biases, relu_masks)
     t = np.asarray(target, np.int64).reshape(-1)
     has = torch.as_tensor(t >= 0)

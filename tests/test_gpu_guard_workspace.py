@@ -80,6 +80,52 @@ def _scalar_check(net, ws, path):
     assert path.causal_wgrad == 'scalar', path
 
 
+class TinyMixture(Plain):
+    """TINY with scalar input and a mixture-of-logistics head (K = 4: 12
+    logit columns), every call with drawn lengths and history: the masked and
+    windowed branches of wn_mol_quantize / wn_mol_loss / wn_mol_score."""
+
+    def model(self, first=False, B=None):
+        from wavenet import WaveNetModel
+        from util import model_kwargs
+        net = WaveNetModel(**model_kwargs(cfg_with(self.cfg,
+                                                   batch_size=B or self.B)))
+        if first:       # (test_gpu_mol_model._model)
+            g = torch.Generator().manual_seed(5)
+            with torch.no_grad():
+                for n, v in net.named_variables():
+                    if 'bias' in n.split('/')[-1]:
+                        v.copy_(0.1 * torch.randn(v.shape, generator=g))
+                Kp, K = net.mol_Kp, net.mol_K
+                net.variables['postprocessing']['postprocess2_bias'][
+                    2 * Kp:2 * Kp + K] -= 2.0
+        return net
+
+    def inputs(self, rng, B, T):
+        inp = Plain.inputs(self, rng, B, T)
+        n = rng.integers(1, T + 1, B)
+        if B > 1:
+            n[-1] = T
+        h = rng.integers(0, n + 1)
+        if (n - h).sum() == 0:
+            h[-1] = 0
+        inp.update(lengths=n.astype(np.int64), history=h.astype(np.int64))
+        return inp
+
+    def kwargs(self, net, inp, host):
+        a, _ = Plain.kwargs(self, net, inp, host)
+        return a, dict(lengths=inp['lengths'], history=inp['history'])
+
+    def proba_args(self, net, inp):
+        """predict_mixture's"""
+        return (inp['audio'], inp.get('ids')), {}
+
+
+def _mixture_check(net, ws, path):
+    _scalar_check(net, ws, path)
+    assert net.mol_K == 4 and net.Q == 12 and ws.logits.shape[1] == 12
+
+
 def _gc_check(net, ws, path):
     assert path.bwd == 'stack', path
     for name in ('tilesum_buf', 'dsum_part', 'gc_part'):
@@ -117,6 +163,10 @@ KINDS = [
     ('tiny_scalar', Plain('tiny_scalar', cfg_with(
         TINY, batch_size=1, scalar_input=True, initial_filter_width=4)),
      None, _scalar_check),
+    ('tiny_mixture', TinyMixture('tiny_mixture', cfg_with(
+        TINY, batch_size=1, scalar_input=True, initial_filter_width=4,
+        output_mixture=4)),
+     None, _mixture_check),
     ('tiny_gc', Plain('tiny_gc', cfg_with(TINY, batch_size=1, **GC)),
      None, _gc_check),
     ('tiny_r64', Plain('tiny_r64', cfg_with(
@@ -233,11 +283,15 @@ def _session(kind, net, B, T, tails, variant, Q, check):
     s = net.score(*a, per_sample=True, **kw)
     torch.cuda.synchronize()
     _check(tails, variant, Q, 'score')
+    # (a mixture head has no arg-max: correct is None there, and only there)
+    assert (s.correct is None) == bool(net.mol_K)
     out += [('score_' + n, _bits(getattr(s, n)))
-            for n in ('nll', 'count', 'correct', 'per_sample')]
+            for n in ('nll', 'count', 'correct', 'per_sample')
+            if getattr(s, n) is not None]
     out.append(('score_logits', _bits(fw.logits)))
     pa, pkw = kind.proba_args(net, inp)
-    p = net.predict_proba(*pa, **pkw)
+    p = net.predict_mixture(*pa, **pkw) if net.mol_K else \
+        net.predict_proba(*pa, **pkw)
     torch.cuda.synchronize()
     _check(tails, variant, Q, 'predict_proba')
     assert bool(torch.isfinite(p).all())

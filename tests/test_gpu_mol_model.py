@@ -57,7 +57,7 @@ def _model(K, ch=16, ifw=2, biases=False, gc=None, lc=None, seed=0, lsm=-14.0):
     return net
 
 
-def _lc_input(lc, seed):
+def _lc_input(lc, seed, B=B, T=T):
     rng = np.random.default_rng(seed)
     if lc == 'rows':
         return rng.standard_normal((B, T, LC)).astype(np.float32)
@@ -68,8 +68,10 @@ def _lc_input(lc, seed):
 
 
 def _reference(net, audio, K, lc, lcin, ids, lengths, history, grads=True):
-    """The float64 network on what the device network read."""
+    """The float64 network on what the device network read (audio [B, T],
+    any B)."""
     from wavenet import mol
+    B, T = np.shape(audio)
     n = np.full(B, T) if lengths is None else np.asarray(lengths)
     h = np.zeros(B, np.int64) if history is None else np.asarray(history)
     den = float(B * T) if lengths is None and history is None else \
@@ -203,3 +205,186 @@ def test_adam_steps_lower_the_loss(hip_lib):
         losses.append(float(loss))
     assert np.isfinite(losses).all()
     assert losses[-1] < losses[0] - 0.05, (losses[0], losses[-1])
+
+
+# ---- launch-plan replay, ragged batches, views --------------------------------
+def _bits(x):
+    x = x.detach().reshape(-1)
+    return x.view(torch.int64 if x.element_size() == 8 else torch.int32)
+
+
+def _replayed(ws, tag):
+    """a recorded launch plan of pass `tag` exists: the next call replays"""
+    return ws is not None and any(k[0] == tag and isinstance(p, list)
+                                  for k, p in ws.plans.items())
+
+
+def _twin(net, *args, **kw):
+    """A second model (_model's arguments) with net's parameters."""
+    other = _model(*args, **kw)
+    with torch.no_grad():
+        other.params.copy_(net.params)
+    return other
+
+
+def _new_inputs(i, gc, Bq=B):
+    """audio, GC ids and LC rows that differ from call to call"""
+    audio = np.roll(synth_audio(Bq, T, seed=30 + i), 37 * i, 1) * \
+        np.float32(1.0 - 0.12 * i)
+    return audio, (np.arange(Bq) + i) % gc, _lc_input('rows', 50 + i, Bq)
+
+
+def _hold_loss_to_float64(what, net, loss, audio, K, lcin, ids, lengths,
+                          history):
+    ref_loss, ref_g, _, _ = _reference(net, audio, K, 'rows', lcin, ids,
+                                       lengths, history)
+    assert abs(loss - ref_loss) <= 1e-5 * max(1.0, abs(ref_loss)), \
+        (what, loss, ref_loss)
+    got = dict(lc_ref.flatten(lc_ref.model_tree(net, grads=True)))
+    ref = dict(lc_ref.flatten(ref_g))
+    assert sorted(got) == sorted(ref)
+    bad, worst = [], 0.0
+    for k in sorted(ref):
+        scale = np.abs(ref[k]).max()
+        err = np.abs(got[k] - ref[k]).max()
+        worst = max(worst, err / max(scale, 1e-30))
+        if not err <= TOL * max(scale, 1e-30):
+            bad.append((k, float(err), float(scale)))
+    print('%s: loss %.7f, float64 %.7f; worst gradient error %.3g of the '
+          'variable\'s largest entry' % (what, loss, ref_loss, worst))
+    assert not bad, (what, bad[:6])
+
+
+def _hold_score_to_float64(what, net, sc, audio, K, lcin, ids, lengths,
+                           history):
+    Bq = audio.shape[0]
+    _, _, _, ref_rows = _reference(net, audio, K, 'rows', lcin, ids, lengths,
+                                   history, grads=False)
+    n = np.full(Bq, T) if lengths is None else np.asarray(lengths)
+    h = np.zeros(Bq, np.int64) if history is None else np.asarray(history)
+    rows = sc.per_sample.cpu().numpy()
+    assert rows.shape == ref_rows.shape == (Bq, T)
+    err = np.abs(rows - ref_rows).max()
+    print('%s: per-row error %.3g of max(1, largest row)'
+          % (what, err / max(1.0, np.abs(ref_rows).max())))
+    assert err <= 2e-5 * max(1.0, np.abs(ref_rows).max()), what
+    assert (rows[ref_rows == 0] == 0).all(), what
+    assert sc.count.cpu().numpy().tolist() == (n - np.maximum(h, 1)).tolist()
+    # (a clip's nll: the float64 sum of its rows, each within the row bound)
+    nll = sc.nll.cpu().numpy()
+    assert (np.abs(nll - ref_rows.sum(1)) <= (n - np.maximum(h, 1)) * 2e-5 *
+            max(1.0, np.abs(ref_rows).max())).all(), what
+    # (... of the float32 rows it returns, in another order: T float64
+    # roundings at the most)
+    assert np.abs(nll - rows.astype(np.float64).sum(1)).max() <= \
+        T * 2.0 ** -52 * max(1.0, np.abs(nll).max()), what
+    assert sc.correct is None
+
+
+def test_replay_tracks_new_inputs(hip_lib):
+    """Five loss calls on one workspace -- eager, recorded, replayed three
+    times -- and three score calls on the forward-only one, every call with
+    new audio, GC ids and LC rows and other lengths and history: each against
+    float64 and, bit for bit, against a model without launch plans.  What a
+    replay could read stale: the levels and centres wn_mol_quantize writes
+    outside the plan, the mask and history words, the ids, the LC rows."""
+    K, gc = 10, 3
+    args = (K, 32, 32, True, gc, 'rows')
+    net = _model(*args, seed=21)
+    plain = _twin(net, *args, seed=21)
+    plain.use_launch_plans = False
+    assert net.use_launch_plans
+    calls = [(None, None), ([200, 131], [0, 17]), (None, [40, 0]),
+             ([77, 200], None), (None, None)]
+    seen = []
+    for i, (lengths, history) in enumerate(calls):
+        audio, ids, lcin = _new_inputs(i, gc)
+        kw = dict(lengths=lengths, history=history,
+                  local_condition_batch=lcin)
+        ws = net._ws.get((B, T, True))
+        for tag in ('fwd', 'bwd'):
+            assert _replayed(ws, tag) == (i >= 2), (i, tag)
+        out = [m.loss(audio, ids, **kw) for m in (net, plain)]
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(out[0]), _bits(out[1])), \
+            (i, float(out[0]), float(out[1]))
+        assert torch.equal(net.grads, plain.grads), i
+        assert ws is None or ws is net._ws[(B, T, True)]
+        assert not plain._ws[(B, T, True)].plans
+        _hold_loss_to_float64('replay, loss call %d' % (i + 1), net,
+                              float(out[0]), audio, K, lcin, ids, lengths,
+                              history)
+        seen.append(float(out[0]))
+    assert len(set(seen)) == len(seen)           # (the inputs did change)
+    for i, (lengths, history) in enumerate([([131, 200], [17, 0]),
+                                            (None, None),
+                                            ([200, 9], [150, 8])]):
+        audio, ids, lcin = _new_inputs(7 + i, gc)
+        kw = dict(lengths=lengths, history=history,
+                  local_condition_batch=lcin, per_sample=True)
+        ws = net._ws.get((B, T, False))
+        assert _replayed(ws, 'fwd') == (i >= 2), i
+        out = [m.score(audio, ids, **kw) for m in (net, plain)]
+        torch.cuda.synchronize()
+        for name in ('nll', 'count', 'per_sample'):
+            assert torch.equal(_bits(getattr(out[0], name)),
+                               _bits(getattr(out[1], name))), (i, name)
+        assert ws is None or ws is net._ws[(B, T, False)]
+        _hold_score_to_float64('replay, score call %d' % (i + 1), net, out[0],
+                               audio, K, lcin, ids, lengths, history)
+    net.check_device_errors()
+
+
+def test_ragged_batches_single_clips_and_predict_on_a_view(hip_lib):
+    """score() of [B', T] with B' = 1 and 3 on a model built for batches of
+    two, with lengths and history: against float64, and bit for bit against
+    the same clips scored one at a time.  Then predict_mixture, on its own
+    workspace and -- after a training step at a longer T -- on a view of the
+    training owner, bit for bit against a fresh model's."""
+    from wavenet import optimizer_factory
+    K, gc = 10, 3
+    args = (K, 16, 32, True, gc, 'rows')
+    net = _model(*args, seed=8)
+    assert net.batch_size == 2
+    for Bq, lengths, history in ((1, [150], [33]),
+                                 (3, [200, 131, 64], [0, 17, 63])):
+        audio, ids, lcin = _new_inputs(Bq, gc, Bq)
+        sc = net.score(audio, ids, lengths=lengths, history=history,
+                       local_condition_batch=lcin, per_sample=True)
+        torch.cuda.synchronize()
+        assert net._ws[(Bq, T, False)].B == Bq
+        assert sc.nll.shape == (Bq,) and sc.per_sample.shape == (Bq, T)
+        _hold_score_to_float64("ragged B' = %d" % Bq, net, sc, audio, K,
+                               lcin, ids, lengths, history)
+        for b in range(Bq):
+            one = net.score(audio[b:b + 1], ids[b:b + 1],
+                            lengths=lengths[b:b + 1],
+                            history=history[b:b + 1],
+                            local_condition_batch=lcin[b:b + 1],
+                            per_sample=True)
+            for name in ('nll', 'count', 'per_sample'):
+                assert torch.equal(_bits(getattr(sc, name)[b]),
+                                   _bits(getattr(one, name))), (Bq, b, name)
+
+    def predict(m, Tp, seed):
+        rng = np.random.default_rng(seed)
+        rows = rng.standard_normal((B, Tp, LC)).astype(np.float32)
+        out = m.predict_mixture(synth_audio(B, Tp, seed=seed), [2, 1],
+                                local_condition=rows)
+        torch.cuda.synchronize()
+        assert out.shape == (3, K) and bool(torch.isfinite(out).all())
+        return out
+
+    got = predict(net, 77, 1)
+    assert torch.equal(_bits(got), _bits(predict(_twin(net, *args), 77, 1)))
+    audio, ids, lcin = _new_inputs(0, gc)
+    audio = np.concatenate([audio, audio[:, :100]], 1)          # T = 300
+    lcin = np.concatenate([lcin, lcin[:, :100]], 1)
+    opt = optimizer_factory['adam'](learning_rate=1e-3, momentum=0.9)
+    opt.minimize(net.loss(audio, ids, local_condition_batch=lcin))
+    got = predict(net, 150, 2)
+    view, owner = net._ws[(B, 150, False)], net._ws[(B, 300, True)]
+    assert view.capacity == owner.N != view.N
+    assert view.logits.data_ptr() == owner.logits.data_ptr()
+    assert torch.equal(_bits(got), _bits(predict(_twin(net, *args), 150, 2)))
+    net.check_device_errors()

@@ -24,6 +24,15 @@ KINDS = {
     'lc_up_ctx': dict(local_condition_channels=8,
                       local_condition_upsample_scales=(4, 4),
                       local_condition_context=2),
+    # mixture-of-logistics heads: Q = 3 * Kp = 12, 36 and 96 logit columns
+    'mol_k1': dict(scalar_input=True, output_mixture=1),
+    'mol_k10_gc': dict(scalar_input=True, initial_filter_width=32,
+                       output_mixture=10, global_condition_channels=4,
+                       global_condition_cardinality=5),
+    'mol_k32_lc_up': dict(scalar_input=True, initial_filter_width=2,
+                          output_mixture=32, local_condition_channels=8,
+                          local_condition_upsample_scales=(4, 4),
+                          local_condition_context=1),
 }
 BATCHES = (1, 2, 3, 4, 8)
 LENGTHS = (1, 17, 33, 500, 4096, 11000, 16000)

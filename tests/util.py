@@ -63,7 +63,7 @@ def model_kwargs(cfg):
             'dilation_channels', 'skip_channels', 'quantization_channels',
             'use_biases', 'scalar_input', 'initial_filter_width',
             'global_condition_channels', 'global_condition_cardinality',
-            'residual_postproc']
+            'residual_postproc', 'output_mixture', 'mixture_log_scale_min']
     return {k: cfg[k] for k in keys if k in cfg}
 
 
