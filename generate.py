@@ -49,6 +49,13 @@ coefficients come from the raw log-mel frames that condition the run: those
 of --lc_wav / --lc_wav_dir, or --lc_path's with the checkpoint's normaliser
 inverted (what the normaliser clamped stays clamped).  Without frames there
 is no filter: such a run is refused.
+Mixture-of-logistics checkpoints (train.py --output_mixture) generate on the
+naive path (--fast_generation false), or with --fast_mixture true on the
+batched generator (`generate_mixture`; --clips N: `generate_mixture_batch`,
+clip i drawing with --seed + i), in --save_every chunks through
+`continue_mixture`.  Both write a 16-bit wav and generated_levels.npy.  The
+draw's counter is the stream's step, the seed's steps included, so the two
+paths draw the same numbers only from a one-sample seed.
 """
 from __future__ import division
 from __future__ import print_function
@@ -130,6 +137,12 @@ def get_arguments(argv=None):
     p.add_argument('--wav_out_path', type=str, default=None)
     p.add_argument('--save_every', type=int, default=SAVE_EVERY)
     p.add_argument('--fast_generation', type=str_to_bool, default=True)
+    p.add_argument('--fast_mixture', type=str_to_bool, default=False,
+                   help='a mixture-of-logistics checkpoint: generate on the '
+                   'batched generator (generate_mixture / '
+                   'generate_mixture_batch) instead of the naive path '
+                   '(default false: such a checkpoint needs '
+                   '--fast_generation false)')
     p.add_argument('--wav_seed', type=str, default=None)
     p.add_argument('--gc_channels', type=int, default=None)
     p.add_argument('--gc_cardinality', type=int, default=None)
@@ -194,6 +207,17 @@ def get_arguments(argv=None):
             emphasis.Emphasis(a.preemphasis)
         except ValueError as e:
             p.error('--preemphasis: %s' % e)
+    if a.fast_mixture:
+        if not a.fast_generation:
+            p.error('--fast_mixture true is a fast path: it does not go with '
+                    '--fast_generation false')
+        if a.top_k is not None or a.top_p is not None:
+            p.error('--fast_mixture true: --top_k / --top_p truncate a '
+                    'distribution over codes; a mixture\'s draw has none '
+                    '(use --temperature)')
+        if a.lc_wav_dir is not None:
+            p.error('--fast_mixture true does not go with --lc_wav_dir: bulk '
+                    'synthesis for mixture checkpoints is a follow-up')
     if a.lc_wav is not None and a.lc_path is not None:
         p.error('give either --lc_wav or --lc_path, not both')
     if a.lc_wav_dir is not None:
@@ -327,9 +351,15 @@ def main(argv=None):
     except ValueError as e:
         print(str(e))
         return 1
+    if head is None and args.fast_mixture:
+        print('--fast_mixture true: the checkpoint holds a softmax model, not '
+              'a mixture-of-logistics one (generate it without the flag)')
+        return 1
     if head is not None:
         why = None
-        if args.fast_generation:
+        if args.fast_generation and args.fast_mixture:
+            pass
+        elif args.fast_generation:
             why = ('--fast_generation true: the checkpoint holds a mixture-'
                    'of-logistics model; ' + mol.FOLLOW_UP)
         elif args.top_k is not None or args.top_p is not None:
@@ -409,7 +439,8 @@ def main(argv=None):
         return _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
                          emph, lp)
     if args.lc_path is not None or args.lc_wav is not None:
-        if args.fast_generation and not args.lc_fast_generation:
+        if args.fast_generation and not args.lc_fast_generation and \
+                not args.fast_mixture:
             print('Local conditioning (--lc_path) needs the naive path: '
                   'pass --fast_generation false, or opt in to fast '
                   'generation with local conditioning with '
@@ -512,6 +543,9 @@ def main(argv=None):
     def rows(pos, n):              # the rows of the n positions from pos
         return None if lc_full is None else lc_full[pos:pos + n]
 
+    if head is not None and args.fast_mixture:
+        return _main_mixture(args, net, waveform, rate, logdir, rows, emph,
+                             lp, lp_cf)
     if args.clips > 1:
         return _main_clips(args, net, waveform, Q, rate, logdir, rows, emph,
                            lp, lp_cf)
@@ -692,6 +726,58 @@ def _main_dir(args, ckpt, wavenet_params, spec, lc_scales, lc_ctx,
           'occupancy {:.3f}) into {}.'.format(
               len(files), sum(a.shape[0] for a in audios), syn.steps,
               syn.occupancy, args.wav_out_dir))
+    return 0
+
+
+def _main_mixture(args, net, waveform, rate, logdir, rows, emph, lp, lp_cf):
+    """--fast_mixture true: --clips N streams (default 1) of a mixture-of-
+    logistics model in lock step (WaveNetModel.generate_mixture_batch /
+    continue_mixture_batch in --save_every chunks), clip i drawing with
+    --seed + i, all primed by the same seed.  waveform: the seed as float
+    samples on the 16-bit grid."""
+    N = args.clips
+    seeds = [args.seed + i for i in range(N)]
+    gc = args.gc_ids if args.gc_ids is not None else args.gc_id
+    seed_lv = mol.levels_reference(np.asarray(waveform, np.float32))[0]
+    n_seed = int(seed_lv.shape[0])
+    de = None if emph is None else [emphasis.DeStream(emph) for _ in range(N)]
+
+    def dump(levels):
+        if args.wav_out_path:
+            for i in range(N):
+                out = mol.centres(levels[i])
+                if de is not None:
+                    out = de[i].feed(out)
+                out = _lpc_filter(lp, lp_cf, out, n_seed)
+                write_wav16(out, rate, args.wav_out_path if N == 1 else
+                            _clip_path(args.wav_out_path, i))
+
+    if args.wav_seed:
+        print('Priming generation of {} clips with {} seed samples...'
+              .format(N, n_seed))
+    chunk = args.save_every or args.samples
+    done = min(chunk, args.samples)
+    parts = [net.generate_mixture_batch(
+        done, seeds, seed_lv, args.temperature, gc,
+        local_condition=rows(0, n_seed + done - 1)).cpu().numpy()]
+    while done < args.samples:
+        if args.save_every:
+            dump(np.concatenate(parts, axis=1))
+        n = min(chunk, args.samples - done)
+        parts.append(net.continue_mixture_batch(
+            n, parts[-1][:, -1], seeds, args.temperature, gc,
+            local_condition=rows(n_seed + done - 1, n)).cpu().numpy())
+        done += n
+        print('Sample {:3<d}/{:3<d}'.format(done, args.samples), end='\r')
+    levels = np.concatenate(parts, axis=1).astype(np.int32)
+    print()
+    os.makedirs(logdir, exist_ok=True)
+    new = levels[:, n_seed:]
+    np.save(os.path.join(logdir, 'generated_levels.npy'),
+            new[0] if N == 1 else new)
+    dump(levels)
+    print('Finished generating {} clips. Levels saved under {}.'
+          .format(N, logdir))
     return 0
 
 

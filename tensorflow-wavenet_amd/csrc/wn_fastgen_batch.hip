@@ -34,57 +34,16 @@
 // after which the stream is bit for bit a fresh one; the ring position stays
 // the shared cursors[0] % d.  fgb_lc_rows_kernel gathers the LC rows of a
 // segment for streams that hold different items.
-#include "wn_common.h"
-
-#define FGB_MAXB 256
-#define FGB_TILE 32      // streams per chain workgroup
-#define FGB_MAXL 64
-#define FGB_MAXS 512
-#define FGB_MAXQ 512
-#define FGB_XLD 33       // LDS row stride of the chain's x / z tiles
-
-// ctl: int32[8] per call (device memory, so that a captured graph serves
-// every call): base (cursors[0] when the call started), n_given, proba_every,
-// temperature (float bits), row stride of samples_io, rows per stream of
-// proba_out, top-k and top-p (float bits) of the draw (0: off)
-#define FGB_CTL_BASE 0
-#define FGB_CTL_NGIVEN 1
-#define FGB_CTL_PEVERY 2
-#define FGB_CTL_TEMP 3
-#define FGB_CTL_LDS 4
-#define FGB_CTL_LDP 5
-#define FGB_CTL_TOPK 6
-#define FGB_CTL_TOPP 7
-
-struct FgBatch {
-  const float* causal;     // [2][Q][32]
-  const float* layer0;     // layer blocks
-  long layer_stride;
-  const float* skip_w;     // [L * 32][S]
-  const float* skip_bsum;  // [S] or null
-  const float* post1_w;    // [S][S]
-  const float* post1_b;    // [S] or null
-  const float* post2_w;    // [S][Q]
-  const float* post2_b;    // [Q] or null
-  const float* bias_fg;    // [L][nb][64] or null; nb = B (stride 64) or 1 (stride 0)
-  int bias_stride;
-  const int32_t* dil;
-  int L, S, Q, B, Bp;
-  float* state;            // [sum(d)][Bp][32]
-  int32_t* cursors;        // [0] steps pushed, [1] draw pending
-  int32_t* prev;           // [Bp] code consumed one step back (-1: none)
-  int32_t* samples;        // [B][ctl[LDS]], indexed by cursors[0] - ctl[BASE]
-  const int32_t* ctl;
-  const uint64_t* seeds;   // [B]
-  float* proba_out;        // [B][ctl[LDP]][Q] or null
-  int use_dense_bias;
-  float* pre;              // [L][Bp][64]
-  float* z_all;            // [Bp][L * 32]
-  float* h1;               // [Bp][S]
-  float* h2;               // [Bp][S]
-  float* logits;           // [Bp][Q]
-  const int32_t* origin;   // [Bp] step at which stream b (re)started, or null (all 0)
-};
+//
+// The two ends are replaceable (wn_fastgen_batch.h): the chain kernel's input
+// stage is a template parameter, one-hot codes (two gathered rows of the
+// causal filter) or levels (a mixture-of-logistics model's scalar input: the
+// K0 taps of the causal filter over a 64-slot history of each stream's
+// levels, staged through LDS), and wn_fastgen_mol.hip puts the mixture draw
+// where fgb_draw_kernel stands.  Everything between them -- rings, past-tap
+// pre-activations, LC ring, skip / post GEMMs -- is the same launch for both.
+#include "wn_fastgen_batch.h"
+#include "wn_mol_draw.h"   // mol_centre, MOL_TOP
 
 // 16 x 16 x 4 f32 MFMA.  Lane l: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15];
 // C/D: column l & 15, rows 4 (l >> 4) + r.
@@ -141,10 +100,11 @@ __global__ __launch_bounds__(256) void fgb_draw_q_kernel(FgBatch g) {
 // zeroed (a FIFO of zeros is the same wherever its head sits, so the shared
 // ring position needs no reset), prev = -1, origin = the step the queues are
 // at.  Workgroup (x, y): the streams 32 y .. 32 y + 31, ring rows x, x +
-// gridDim.x, ...; a thread: one float4 of one stream.
+// gridDim.x, ...; a thread: one float4 of one stream.  prev or hist (levels
+// input: the stream's 64 history slots become -1, eight a thread) is null.
 __global__ __launch_bounds__(256) void fgb_restart_kernel(
     float* state, const int32_t* dil, int L, int B, int Bp, const int32_t* cursors,
-    int32_t* prev, int32_t* origin, const int32_t* flags) {
+    int32_t* prev, int32_t* hist, int32_t* origin, const int32_t* flags) {
   const int tid = threadIdx.x;
   const int b = blockIdx.y * FGB_TILE + (tid >> 3);
   const bool on = b < B && flags[b] != 0;
@@ -154,8 +114,12 @@ __global__ __launch_bounds__(256) void fgb_restart_kernel(
     const float4 zero = {0.f, 0.f, 0.f, 0.f};
     for (int r = blockIdx.x; r < rows; r += gridDim.x)
       *reinterpret_cast<float4*>(state + ((long)r * Bp + b) * 32 + (tid & 7) * 4) = zero;
+    if (blockIdx.x == 0 && hist) {
+#pragma unroll
+      for (int i = 0; i < FGB_HIST / 8; ++i) hist[b * FGB_HIST + (tid & 7) * 8 + i] = -1;
+    }
     if (blockIdx.x == 0 && (tid & 7) == 0) {
-      prev[b] = -1;
+      if (prev) prev[b] = -1;
       origin[b] = cursors[0];
     }
   }
@@ -193,10 +157,27 @@ struct FgbLW {
   float bd;
 };
 
+// LEVELS (the input stage): false, one-hot codes, x = W[0][prev] + W[1][code];
+// true, levels: the rule of scalar_causal_fwd_kernel (wn_misc.hip) on the
+// stream's history ring,
+//   x[col] = sum_k W[k][col] c(hist[(T - s_k) & 63]),
+//   s_k = (K0 - 1 - k) + (K0 - 1) / 2, c = mol_centre,
+// taps k ascending from +0, one fmaf each; a slot that holds no level in
+// 0 .. 65535 is skipped (the zero padding of training).  Slot T & 63 gets the
+// level this step consumes.  The group's 32 x 64 slots, as centres, and the
+// K0 x 32 filter are staged through LDS (rows 65 words apart: the four rows a
+// wave reads fall on different banks).
+#define FGB_HLD (FGB_HIST + 1)
+#define FGB_EMPTY 2.f    // (centres lie in [-1, 1])
+
+template <bool LEVELS>
 __global__ __launch_bounds__(256) void fgb_chain_kernel(FgBatch g) {
   __shared__ float xs[FGB_TILE * FGB_XLD];
   __shared__ float zs[FGB_TILE * FGB_XLD];
   __shared__ int roff_s[FGB_MAXL], pos_s[FGB_MAXL];
+  __shared__ float hs[LEVELS ? FGB_TILE * FGB_HLD : 1];   // centres; FGB_EMPTY: no level
+  __shared__ int cur_s[LEVELS ? FGB_TILE : 1];            // the level this step consumes
+  __shared__ float wcs[LEVELS ? FGB_MAXK0 * 32 : 1];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int rb = w & 1, cb = w >> 1;
   const int ci = lane & 15, kk = lane >> 4;
@@ -245,30 +226,73 @@ __global__ __launch_bounds__(256) void fgb_chain_kernel(FgBatch g) {
       pos_s[lane] = T % dl;
     }
   }
-  // causal layer (filter width 2): x = W[0][prev] + W[1][code]
   float x[4];
   int code[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int b = b0 + row0 + r;
-    int c = -1, p = -1;
-    if (b < g.B) {
-      c = g.samples[b * lds + local];
-      p = g.prev[b];
+  const int slot = T & (FGB_HIST - 1);
+  if constexpr (LEVELS) {
+    // causal layer on levels.  Staging: a stream's 64 slots, the one of this
+    // step already holding the level it consumes; rows past B hold nothing
+    const int K0 = g.K0;
+    for (int i = tid; i < FGB_TILE * FGB_HIST; i += 256) {
+      const int r = i >> 6, sl = i & (FGB_HIST - 1);
+      const int b = b0 + r;
+      int v = -1;
+      if (b < g.B)
+        v = sl == slot ? g.samples[b * lds + local] : g.hist[(long)b * FGB_HIST + sl];
+      // (one conversion a slot here, not one a tap and lane below)
+      hs[r * FGB_HLD + sl] = v >= 0 && v <= MOL_TOP ? mol_centre(v) : FGB_EMPTY;
+      if (sl == slot) cur_s[r] = v;
     }
-    float v = 0.f;
-    if (p >= 0 && p < Q) v = g.causal[(long)p * 32 + col];
-    if (c >= 0 && c < Q) v += g.causal[((long)Q + c) * 32 + col];
-    x[r] = v;
-    code[r] = c;
-    xs[(row0 + r) * FGB_XLD + col] = v;
+    for (int i = tid; i < K0 * 32; i += 256) wcs[i] = g.causal[i];
+    __syncthreads();
+    const int extra = (K0 - 1) / 2;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) x[r] = 0.f;
+    const float* h = hs + row0 * FGB_HLD;
+#pragma unroll 4
+    for (int k = 0; k < K0; ++k) {
+      const int sl = (T - ((K0 - 1 - k) + extra)) & (FGB_HIST - 1);
+      const float wk = wcs[k * 32 + col];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float c = h[r * FGB_HLD + sl];
+        if (c <= 1.f) x[r] = fmaf(wk, c, x[r]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      code[r] = cur_s[row0 + r];
+      xs[(row0 + r) * FGB_XLD + col] = x[r];
+    }
+  } else {
+    // causal layer (filter width 2): x = W[0][prev] + W[1][code]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int b = b0 + row0 + r;
+      int c = -1, p = -1;
+      if (b < g.B) {
+        c = g.samples[b * lds + local];
+        p = g.prev[b];
+      }
+      float v = 0.f;
+      if (p >= 0 && p < Q) v = g.causal[(long)p * 32 + col];
+      if (c >= 0 && c < Q) v += g.causal[((long)Q + c) * 32 + col];
+      x[r] = v;
+      code[r] = c;
+      xs[(row0 + r) * FGB_XLD + col] = v;
+    }
   }
   __syncthreads();
-  // (every wave has read prev[] for its rows)
+  // (every wave has read prev[] / staged hist[] for its rows)
   if (cb == 0 && ci == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (b0 + row0 + r < g.B) g.prev[b0 + row0 + r] = code[r];
+      if (b0 + row0 + r < g.B) {
+        if constexpr (LEVELS)
+          g.hist[(long)(b0 + row0 + r) * FGB_HIST + slot] = code[r];
+        else
+          g.prev[b0 + row0 + r] = code[r];
+      }
   }
   if (blockIdx.x == 0 && tid == 0) g.cursors[1] = 0;   // the draw has run
 
@@ -371,11 +395,6 @@ __device__ __forceinline__ void fgb_gemm_tile(const FgbGemm& p, int nt, int mt,
 // rows 16 (w & 1), filter (w < 2) or gate half, two 16-column tiles.
 // LC: the bias of stream b is row tpos of the conditioned-bias ring
 // [R][L][nb][64] (wn_fastgen_lc_bias; nb = B with stream stride 64, 1 with 0).
-struct FgbLc {
-  const float* ring;
-  int R, stride;
-};
-
 template <bool LC>
 __device__ __forceinline__ void fgb_pre_tile(const FgBatch& g, const FgbLc& lc, int l, int gi,
                                              int ahead) {
@@ -480,20 +499,49 @@ __global__ __launch_bounds__(256) void fgb_logits_kernel(FgBatch g) {
 }
 
 // ------------------------------------------------------------------- C ABI
-static int fgb_rows(int B) { return (B + FGB_TILE - 1) / FGB_TILE * FGB_TILE; }
+int fgb_rows(int B) { return (B + FGB_TILE - 1) / FGB_TILE * FGB_TILE; }
 
-static int fgb_check_batch(int B) {
+int fgb_check_batch(int B) {
   if (B <= 0) return WN_ERR_BAD_SHAPE;
   if (B > FGB_MAXB) return WN_ERR_UNSUPPORTED;
   return WN_OK;
 }
 
 // null: no local conditioning; else the ring must be set and its shape sane
-static int fgb_check_lc(const FgbLc* lc) {
+int fgb_check_lc(const FgbLc* lc) {
   if (!lc) return WN_OK;
   if (!lc->ring) return WN_ERR_NULL;
   if (lc->R < 1 || (lc->stride != 0 && lc->stride != 64)) return WN_ERR_BAD_SHAPE;
   return WN_OK;
+}
+
+void fgb_launch_chain_levels(const FgBatch& g, hipStream_t s) {
+  hipLaunchKernelGGL(fgb_chain_kernel<true>, dim3(g.Bp / FGB_TILE), dim3(256), 0, s, g);
+}
+
+// skip sum + next pre-activations, post1, logits
+void fgb_launch_tail(const FgBatch& g, const FgbLc* lc, FgbStage stage, hipStream_t s) {
+  const int mt = g.Bp / 16, ng = g.Bp / FGB_TILE;
+  if (stage == FGB_STAGE_SKIP) {
+    if (lc)
+      hipLaunchKernelGGL(fgb_skip_lc_kernel, dim3(fgb_ntiles(g.S) * mt + g.L * ng), dim3(256),
+                         0, s, g, *lc);
+    else
+      hipLaunchKernelGGL(fgb_skip_kernel, dim3(fgb_ntiles(g.S) * mt + g.L * ng), dim3(256), 0,
+                         s, g);
+  } else if (stage == FGB_STAGE_POST1) {
+    hipLaunchKernelGGL(fgb_post1_kernel, dim3(fgb_ntiles(g.S) * mt), dim3(256), 0, s, g);
+  } else {
+    hipLaunchKernelGGL(fgb_logits_kernel, dim3(fgb_ntiles(g.Q) * mt), dim3(256), 0, s, g);
+  }
+}
+
+void fgb_launch_restart(float* state, const int32_t* dil, int L, int B,
+                        const int32_t* cursors, int32_t* prev, int32_t* hist,
+                        int32_t* origin, const int32_t* flags, hipStream_t s) {
+  const int Bp = fgb_rows(B);
+  hipLaunchKernelGGL(fgb_restart_kernel, dim3(128, Bp / FGB_TILE), dim3(256), 0, s, state, dil,
+                     L, B, Bp, cursors, prev, hist, origin, flags);
 }
 
 extern "C" {
@@ -531,7 +579,9 @@ int wn_fastgen_batch_init(float* state, long state_floats, int32_t* cursors, int
   return WN_OK;
 }
 
-static int fgb_pre(const FgbLc* lc, const float* layer0, long layer_stride,
+}  // extern "C"
+
+int fgb_pre(const FgbLc* lc, const float* layer0, long layer_stride,
                    const float* gc_bias_fg, int bias_stream_stride,
                    const int32_t* dilations_dev, int L, int B, const float* state,
                    const int32_t* cursors, float* pre, void* stream) {
@@ -555,6 +605,8 @@ static int fgb_pre(const FgbLc* lc, const float* layer0, long layer_stride,
                        (hipStream_t)stream, g, 0);
   return wn_check_launch();
 }
+
+extern "C" {
 
 int wn_fastgen_batch_pre(const float* layer0, long layer_stride, const float* gc_bias_fg,
                          int bias_stream_stride, const int32_t* dilations_dev, int L, int B,
@@ -599,7 +651,7 @@ static int fgb_stages(const FgbLc* lc, const int32_t* origins, int first, int la
   if (S > FGB_MAXS || Q > FGB_MAXQ || L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
   const int rc = fgb_check_batch(B);
   if (rc != WN_OK) return rc;
-  FgBatch g;
+  FgBatch g = {};
   g.causal = params_causal; g.layer0 = layer0; g.layer_stride = layer_stride;
   g.skip_w = skip_w; g.skip_bsum = skip_bsum; g.post1_w = post1_w; g.post1_b = post1_b;
   g.post2_w = post2_w; g.post2_b = post2_b; g.bias_fg = gc_bias_fg;
@@ -610,7 +662,7 @@ static int fgb_stages(const FgbLc* lc, const int32_t* origins, int first, int la
   g.pre = pre; g.z_all = z_all; g.h1 = h1; g.h2 = h2; g.logits = logits;
   g.origin = origins;
   hipStream_t s = (hipStream_t)stream;
-  const int mt = g.Bp / 16, ng = g.Bp / FGB_TILE;
+  const int ng = g.Bp / FGB_TILE;
   for (int stage = first; stage < last; ++stage) {
     switch (stage) {
       case 0:
@@ -620,21 +672,10 @@ static int fgb_stages(const FgbLc* lc, const int32_t* origins, int first, int la
           hipLaunchKernelGGL(fgb_draw_kernel, dim3((B + 3) / 4), dim3(256), 0, s, g);
         break;
       case 1:
-        hipLaunchKernelGGL(fgb_chain_kernel, dim3(ng), dim3(256), 0, s, g);
-        break;
-      case 2:
-        if (lc)
-          hipLaunchKernelGGL(fgb_skip_lc_kernel, dim3(fgb_ntiles(S) * mt + L * ng), dim3(256), 0,
-                             s, g, *lc);
-        else
-          hipLaunchKernelGGL(fgb_skip_kernel, dim3(fgb_ntiles(S) * mt + L * ng), dim3(256), 0, s,
-                             g);
-        break;
-      case 3:
-        hipLaunchKernelGGL(fgb_post1_kernel, dim3(fgb_ntiles(S) * mt), dim3(256), 0, s, g);
+        hipLaunchKernelGGL(fgb_chain_kernel<false>, dim3(ng), dim3(256), 0, s, g);
         break;
       default:
-        hipLaunchKernelGGL(fgb_logits_kernel, dim3(fgb_ntiles(Q) * mt), dim3(256), 0, s, g);
+        fgb_launch_tail(g, lc, (FgbStage)stage, s);
         break;
     }
   }
@@ -772,10 +813,8 @@ int wn_fastgen_batch_restart(float* state, const int32_t* dilations_dev, int L, 
   if (L > FGB_MAXL) return WN_ERR_UNSUPPORTED;
   const int rc = fgb_check_batch(B);
   if (rc != WN_OK) return rc;
-  const int Bp = fgb_rows(B);
-  hipLaunchKernelGGL(fgb_restart_kernel, dim3(128, Bp / FGB_TILE), dim3(256), 0,
-                     (hipStream_t)stream, state, dilations_dev, L, B, Bp, cursors, prev, origins,
-                     flags);
+  fgb_launch_restart(state, dilations_dev, L, B, cursors, prev, nullptr, origins, flags,
+                     (hipStream_t)stream);
   return wn_check_launch();
 }
 

@@ -3,12 +3,11 @@
 // place of wn_xent*, held-out scoring on the same row arithmetic, one row's
 // parameters and the sampling draw.
 #include "wn_common.h"
+#include "wn_mol_draw.h"     // MOL_TOP, MOL_MAXK, mol_centre, the two row rules
 #include <cmath>
 
 #pragma clang fp contract(off)
 
-#define MOL_TOP 65535        // C - 1, the highest level
-#define MOL_MAXK 32
 #define MOL_TILE 64          // rows of a workgroup's tile: four lanes per row
 #define MOL_MAXSTRIDE 100    // floats between a tile's rows in LDS, at most
 #define MOL_CLIP_THREADS 1024
@@ -22,10 +21,6 @@ __device__ __forceinline__ int mol_clip_len(const int32_t* lengths, long b,
 __device__ __forceinline__ int mol_clip_start(const int32_t* starts, long b,
                                               int T) {
   return starts ? min(max(starts[b], 0), T) : 0;
-}
-
-__device__ __forceinline__ float mol_centre(int j) {
-  return (float)(2 * j - MOL_TOP) / 65535.0f;
 }
 
 __device__ __forceinline__ int mol_level(float y) {
@@ -291,53 +286,23 @@ __global__ __launch_bounds__(MOL_CLIP_THREADS) void mol_score_clips_kernel(
   }
 }
 
-// one row's parameters; lane k < K serves component k
+// one row's parameters; lane k < K serves component k (wn_mol_draw.h)
 __global__ __launch_bounds__(64) void mol_params_row_kernel(
     const float* __restrict__ row, int K, float lsm, float* __restrict__ out) {
-  const int k = threadIdx.x, Kp = (K + 3) & ~3;
+  const int k = threadIdx.x;
   if (k >= K) return;
-  double m = -INFINITY;
-  for (int i = 0; i < K; ++i) m = fmax(m, (double)row[i]);
-  double se = 0.0;
-  for (int i = 0; i < K; ++i) se += exp((double)row[i] - m);
-  out[k] = (float)(((double)row[k] - m) - log(se));
-  out[K + k] = row[Kp + k];
-  out[2 * K + k] = fmaxf(row[2 * Kp + k], lsm);
+  mol_params_component(row, K, lsm, k, out);
 }
 
-// the draw, a lane per row, float64
+// the draw, a lane per row, float64 (wn_mol_draw.h)
 __global__ __launch_bounds__(64) void mol_sample_kernel(
     const float* __restrict__ params, const uint64_t* __restrict__ seeds,
     const uint64_t* __restrict__ counters, float temperature,
     int32_t* __restrict__ levels, float* __restrict__ centres, int R, int K) {
   const long r = (long)blockIdx.x * 64 + threadIdx.x;
   if (r >= R) return;
-  const float* p = params + r * 3 * K;
-  const uint64_t seed = seeds[r], ctr = counters[r];
-  const double u1 = draw_uniform(seed, 2 * ctr);
-  const double u2 = draw_uniform(seed, 2 * ctr + 1);
-  double total = 0.0;
-  for (int k = 0; k < K; ++k) total += exp((double)p[k]);
-  const double t = u1 * total;
-  double cum = 0.0;
-  int pick = -1, last = 0;
-  for (int k = 0; k < K; ++k) {
-    const double pk = exp((double)p[k]);
-    cum += pk;
-    if (pk > 0.0) last = k;
-    if (pick < 0 && t < cum) pick = k;
-  }
-  if (pick < 0) pick = last;
-  double x = (double)p[K + pick];
-  if (temperature != 0.f) {
-    const double sc = exp((double)p[2 * K + pick]) * (double)temperature;
-    const double lg = log(u2) - log(1.0 - u2);
-    x = x + sc * lg;
-  }
-  x = fmin(fmax(x, -1.0), 1.0);
-  double q = x + 1.0;
-  q = q * 32767.5;
-  const int j = (int)rint(q);
+  const int j = mol_draw_level(params + r * 3 * K, K, seeds[r], counters[r],
+                               temperature);
   levels[r] = j;
   centres[r] = mol_centre(j);
 }

@@ -412,6 +412,31 @@ MOL_SIGNATURES = {
     'wn_mol_sample': (c_int, [P, P, P, c_float, P, P, c_int, c_int, P]),
 }
 
+# name -> (restype, argtypes); mirrors include/wavenet_fastgen_mol.h one to one
+# (batched fast generation for mixture models, bound onto the same library)
+FASTGEN_MOL_SIGNATURES = {
+    # state, state_floats, cursors, hist, B, stream
+    'wn_fastgen_mol_init': (c_int, [P, c_long, P, P, c_int, P]),
+    # wn_fastgen_batch_pre's arguments, lc_ring, lc_R, lc_stride, stream
+    'wn_fastgen_mol_pre': (c_int, [P, c_long, P, c_int, P, c_int, c_int, P, P,
+                                   P, P, c_int, c_int, P]),
+    # causal, K0, layer0, layer_stride, skip_w, skip_bsum, post1_w, post1_b,
+    # post2_w, post2_b, gc_bias_fg, bias_stream_stride, dilations, L, S, K, B,
+    # state, cursors, hist, samples_io, ctl, seeds, params_out, use_biases,
+    # log_scale_min, pre, z_all, h1, h2, logits, lc_ring, lc_R, lc_stride,
+    # origins, stream
+    'wn_fastgen_mol_step': (c_int, [P, c_int, P, c_long, P, P, P, P, P, P, P,
+                                    c_int, P, c_int, c_int, c_int, c_int, P,
+                                    P, P, P, P, P, P, c_int, c_float, P, P, P,
+                                    P, P, P, c_int, c_int, P, P]),
+    # K, log_scale_min, B, cursors, samples_io, ctl, seeds, params_out,
+    # logits, origins, stream
+    'wn_fastgen_mol_finish': (c_int, [c_int, c_float, c_int, P, P, P, P, P, P,
+                                      P, P]),
+    # state, dilations, L, B, cursors, hist, origins, flags, stream
+    'wn_fastgen_mol_restart': (c_int, [P, P, c_int, c_int, P, P, P, P, P]),
+}
+
 
 _lib = None
 
@@ -434,7 +459,8 @@ def load():
     for table in (SIGNATURES, PITCH_SIGNATURES, PITCH_PATH_SIGNATURES,
                   LC_FRAMES_SIGNATURES, SPECTRAL_SIGNATURES,
                   GRIFFIN_LIM_SIGNATURES, LPC_SIGNATURES,
-                  RESAMPLE_SIGNATURES, STOI_SIGNATURES, MOL_SIGNATURES):
+                  RESAMPLE_SIGNATURES, STOI_SIGNATURES, MOL_SIGNATURES,
+                  FASTGEN_MOL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res

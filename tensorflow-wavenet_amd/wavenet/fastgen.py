@@ -276,7 +276,12 @@ def _prime(net, g, n0, groups, Bp):
     dst = np.concatenate(dst)
     ws = net._workspace(1, n0, False)
     for codes, gc, streams, lc in groups:
-        ws.q.copy_(codes)
+        if net.mol_K:
+            # (levels: the network reads their centres, as in training)
+            mol.stage(net, ws, torch.from_numpy(mol.centres(
+                codes.numpy())).to(net.device).reshape(1, n0), None)
+        else:
+            ws.q.copy_(codes)
         lcond.fill(net, lc, ws)    # the seed's LC rows, as predict_proba
         train_pass.run_pass(net, 'fwd', ws, net._gc_ids(gc, 1),
                             train_pass.step_path(net, ws, False))
@@ -288,10 +293,11 @@ def _prime(net, g, n0, groups, Bp):
             vals.repeat(len(streams), 1))
 
 
-def _seeded(net, io, n_given, n, pe, prime, run, lc=None):
+def _seeded(net, io, n_given, n, pe, prime, run, lc=None, row=None):
     # io [..., n_given + n] starts with the seed codes; returns the
     # probabilities [..., rows, Q] of every pe-th step, or None.  lc: the
-    # call's LC rows [..., n_steps, Lc] (run gets those of its steps)
+    # call's LC rows [..., n_steps, Lc] (run gets those of its steps); row:
+    # the shape of a returned row where it is not (Q,)
     n_steps = n_given - 1 + n
     primed = prime and pe == 0 and \
         n_given - 1 >= net.fastgen_prime_forward_min and n > 0 and \
@@ -301,7 +307,8 @@ def _seeded(net, io, n_given, n, pe, prime, run, lc=None):
                                 else lc)
     proba = None
     if pe > 0:
-        proba = torch.empty(io.shape[:-1] + ((n_steps + pe - 1) // pe, net.Q),
+        proba = torch.empty(io.shape[:-1] + ((n_steps + pe - 1) // pe,) +
+                            tuple(row or (net.Q,)),
                             dtype=torch.float32, device=net.device)
     if primed:
         # the reference's own TODO (generate.py:199-201): fill the queues
@@ -604,15 +611,33 @@ def continue_generation(net, num_samples, last_sample, temperature,
 
 # ---------------------------------------------------------------- B streams
 def _batch_args(net, seeds, per_stream, global_condition, temperature,
-                num_samples):
+                num_samples, mixture=False):
     """The batched entry points' checks, in order, before anything touches
-    a device -> seeds (int64 bit patterns), per_stream(B), GC ids, n."""
+    a device -> seeds (int64 bit patterns), per_stream(B), GC ids, n.
+    mixture: the generate_mixture_batch path, where scalar input is the
+    input (initial_filter_width <= 32) and temperature 0 is legal; its
+    refusals name that call and the naive path, the only other one."""
+    what = 'generate_mixture_batch' if mixture else 'generate_batch'
+    other = 'predict_mixture (generate.py --fast_generation false)' \
+        if mixture else 'generate() per stream'
     if net.CB > 1:
         raise NotImplementedError(
-            'generate_batch supports at most 32 residual / dilation '
-            'channels (this model has %d); use generate() per stream'
-            % max(net.R, net.D))
-    if net.filter_width > 2 or net.scalar_input:
+            '%s supports at most 32 residual / dilation '
+            'channels (this model has %d); use %s'
+            % (what, max(net.R, net.D), other))
+    if mixture:
+        if net.filter_width > 2:
+            raise NotImplementedError(
+                'generate_mixture_batch needs filter_width 2, as every fast '
+                'generation path does; use predict_mixture (generate.py '
+                '--fast_generation false)')
+        if net.initial_filter_width > MOL_MAX_INITIAL_WIDTH:
+            raise NotImplementedError(
+                'generate_mixture_batch supports initial_filter_width 1 to '
+                '%d (the 64-slot level history), this model has %d; use '
+                'predict_mixture (generate.py --fast_generation false)'
+                % (MOL_MAX_INITIAL_WIDTH, net.initial_filter_width))
+    elif net.filter_width > 2 or net.scalar_input:
         raise NotImplementedError(
             'generate_batch needs filter_width 2 and one-hot input '
             '(model.py:597-603), as every fast generation path does; use '
@@ -620,12 +645,13 @@ def _batch_args(net, seeds, per_stream, global_condition, temperature,
             + _follow_up(net))
     if net.S > 512 or net.Q > 512 or net.L > 64:
         raise NotImplementedError(
-            'generate_batch supports at most 512 skip / quantization '
-            'channels and 64 layers; use generate() per stream')
+            '%s supports at most 512 skip / quantization '
+            'channels and 64 layers; use %s' % (what, other))
     s = [int(v) & (2**64 - 1) for v in seeds]
     if not 1 <= len(s) <= net.FASTGEN_BATCH_MAX:
-        raise ValueError('generate_batch takes 1 to %d streams (one seed '
-                         'each), got %d' % (net.FASTGEN_BATCH_MAX, len(s)))
+        raise ValueError('%s takes 1 to %d streams (one seed '
+                         'each), got %d' % (what, net.FASTGEN_BATCH_MAX,
+                                            len(s)))
     B = len(s)
     rows = per_stream(B)
     gc = global_condition
@@ -639,7 +665,13 @@ def _batch_args(net, seeds, per_stream, global_condition, temperature,
             raise ValueError('global_condition has %d ids for %d streams'
                              % (gc.size, B))
         gc = gc.astype(np.int32)
-    _check_temperature(temperature)
+    if mixture:
+        if not (np.isfinite(float(temperature)) and
+                float(temperature) >= 0.0):
+            raise ValueError('temperature must be a finite number >= 0, got '
+                             '%r' % (temperature,))
+    else:
+        _check_temperature(temperature)
     n = int(num_samples)
     if n < 0:
         raise ValueError('num_samples must be >= 0, got %d' % n)
@@ -731,6 +763,10 @@ def batch_generator(net, B):
         origin=torch.zeros(Bp, dtype=torch.int32, device=net.device),
         flags=torch.zeros(Bp, dtype=torch.int32, device=net.device),
         restarted=False, reserve=0)
+    if net.mol_K:
+        # levels input: slot T & 63 holds the level consumed at step T
+        net._bgen['hist'] = torch.full((Bp, MOL_HIST), -1, dtype=torch.int32,
+                                       device=net.device)
     return net._bgen
 
 
@@ -791,8 +827,12 @@ def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
     wn_fastgen_batch_step (no stream) and the buffers batch_complete reads.
     lc (LC models): rows [B or 1, n_steps, Lc]; the result then holds the
     call's ring (`ring`), its first chunk filled, and the pre-activations
-    are those of wn_fastgen_batch_pre_lc."""
-    B = g['B']
+    are those of wn_fastgen_batch_pre_lc.  `step` and `finish` are (entry
+    point, its arguments in front of the stream) for this model: the
+    wn_fastgen_batch_* entries with their _lc / _q suffixes, or, for a
+    mixture model, the wn_fastgen_mol_* entries, whose LC ring and origins
+    are nullable arguments."""
+    B, mixture = g['B'], bool(net.mol_K)
     w, bias, bstride = _weights(net, g, gc, B)
     ring = None
     if lc is not None:
@@ -802,34 +842,48 @@ def batch_prepare(net, g, io, n_given, n_steps, temperature, seeds, proba,
     g['seeds'].copy_(torch.from_numpy(seeds))
     iob, pb = _stage(net, g, io, n_given, n_steps, temperature, proba,
                      proba_every, trunc=trunc)
+    lcargs = () if ring is None else ring.args
+    # restarted streams: the _q entries, the origins in front of the stream
+    q = (_lib.ptr(g['origin']),) if g['restarted'] else ()
     # past-tap pre-activations of the first step (every step then leaves
     # the next step's behind)
     pre_args = (_lib.ptr(net._layer_block(net.params, 0)), net.layer_stride,
                 bias, bstride, _lib.ptr(g['dil']), net.L, B,
                 _lib.ptr(g['state']), _lib.ptr(g['cursors']),
                 _lib.ptr(g['pre']))
-    name, lcargs = _entry('wn_fastgen_batch_pre',
-                          () if ring is None else ring.args)
-    _lib.call(name, *pre_args, *lcargs, _lib.stream())
-    args = w + (bias, bstride, _lib.ptr(g['dil']), net.L, net.S, net.Q, B,
-                _lib.ptr(g['state']), _lib.ptr(g['cursors']),
-                _lib.ptr(g['prev']), _lib.ptr(iob), _lib.ptr(g['ctl']),
-                _lib.ptr(g['seeds']), _lib.ptr(pb), 1 if net.use_biases else 0,
-                _lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
-                _lib.ptr(g['h2']), _lib.ptr(g['logits']))
-    # restarted streams: the _q entries, the origins in front of the stream
-    q = (_lib.ptr(g['origin']),) if g['restarted'] else ()
-    return dict(args=args, iob=iob, pb=pb, ring=ring, q=q)
+    queues = (_lib.ptr(g['state']), _lib.ptr(g['cursors']))
+    io_args = (_lib.ptr(iob), _lib.ptr(g['ctl']), _lib.ptr(g['seeds']),
+               _lib.ptr(pb))
+    scratch = (_lib.ptr(g['pre']), _lib.ptr(g['z_all']), _lib.ptr(g['h1']),
+               _lib.ptr(g['h2']), _lib.ptr(g['logits']))
+    shape = (bias, bstride, _lib.ptr(g['dil']), net.L, net.S)
+    ub = 1 if net.use_biases else 0
+    if mixture:
+        K, lsm = net.mol_K, net.mol_log_scale_min
+        tail = tuple(lcargs or (None, 0, 0)) + (q[0] if q else None,)
+        _lib.call('wn_fastgen_mol_pre', *pre_args, *tail[:3], _lib.stream())
+        args = (w[0], net.initial_filter_width) + w[1:] + shape + (K, B) + \
+            queues + (_lib.ptr(g['hist']),) + io_args + (ub, lsm) + scratch
+        step = ('wn_fastgen_mol_step', tail)
+        finish = ('wn_fastgen_mol_finish', (K, lsm, B, queues[1]) + io_args +
+                  (scratch[4], tail[3]))
+    else:
+        _lib.call(_entry('wn_fastgen_batch_pre', lcargs)[0], *pre_args,
+                  *lcargs, _lib.stream())
+        args = w + shape + (net.Q, B) + queues + (_lib.ptr(g['prev']),) + \
+            io_args + (ub,) + scratch
+        step = _entry('wn_fastgen_batch_step', lcargs, q=q)
+        finish = (_entry('wn_fastgen_batch_finish', q=q)[0],
+                  (net.Q, B, queues[1]) + io_args + (scratch[4],) + q)
+    return dict(args=args, iob=iob, pb=pb, ring=ring, q=q, step=step,
+                finish=finish)
 
 
 def batch_complete(net, g, prep, io, proba, n_steps):
     """The last step's draw (every other one runs at the next step's
     start), then the codes / probabilities back into io / proba."""
-    name, q = _entry('wn_fastgen_batch_finish', q=prep['q'])
-    _lib.call(name, net.Q, g['B'],
-              _lib.ptr(g['cursors']), _lib.ptr(prep['iob']),
-              _lib.ptr(g['ctl']), _lib.ptr(g['seeds']), _lib.ptr(prep['pb']),
-              _lib.ptr(g['logits']), *q, _lib.stream())
+    name, args = prep['finish']
+    _lib.call(name, *args, _lib.stream())
     g['steps'] += int(n_steps)
     io.copy_(prep['iob'][:io.numel()].view(io.shape))
     if proba is not None:
@@ -844,13 +898,12 @@ def _batch_run(net, g, temperature, seeds, gc, io, n_given, n_steps, proba,
     prep = batch_prepare(net, g, io, n_given, n_steps, temperature, seeds,
                          proba, proba_every, gc, lc, trunc)
     args, ring = prep['args'], prep['ring']
-    name, extra = _entry('wn_fastgen_batch_step',
-                         () if ring is None else ring.args, q=prep['q'])
+    name, extra = prep['step']
     for i, (a, n) in enumerate([(0, n_steps)] if ring is None else ring.plan):
         if i:
             ring.fill(a, n)
         # (the stream is looked up inside: a capture runs on its own)
-        _replay_steps(net, g, (args, extra), lambda: _lib.call(
+        _replay_steps(net, g, (name, args, extra), lambda: _lib.call(
             name, *args, *extra, _lib.stream()), n)
     batch_complete(net, g, prep, io, proba, n_steps)
 
@@ -947,3 +1000,157 @@ def continue_generation_batch(net, num_samples, last_samples, seeds,
                     functools.partial(_batch_run, net, g, temperature, sd, gc,
                                       trunc=trunc), lc)
     return (io[:, 1:], proba) if pe > 0 else io[:, 1:]
+
+
+# ------------------------------------------- B streams, mixture of logistics
+# The batched generator with its two ends replaced (csrc/wn_fastgen_mol.hip,
+# include/wavenet_fastgen_mol.h): the causal layer reads a 64-slot history of
+# each stream's levels, the draw is the mixture's.  State, buffers, graphs,
+# the LC ring, priming and restarts are the batched generator's (`net._bgen`).
+MOL_HIST = 64
+MOL_MAX_INITIAL_WIDTH = 32
+
+
+def _mol_need(net, what, other):
+    if not net.mol_K:
+        raise ValueError('%s: this model was built without output_mixture; '
+                         'use %s' % (what, other))
+
+
+def _mol_levels(seed_levels, B):
+    """seed_levels -> int32 [B, n]: None (level 32768 for every stream), one
+    sequence shared by all streams, or one row per stream; levels 0 .. 65535."""
+    if seed_levels is None:
+        return np.full((B, 1), mol.LEVELS // 2, np.int32)
+    if isinstance(seed_levels, torch.Tensor):
+        seed_levels = seed_levels.cpu().numpy()
+    try:
+        a = np.asarray(seed_levels)
+    except ValueError:             # ragged rows
+        a = None
+    if a is None or a.dtype == object or a.ndim not in (1, 2) or \
+            not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+        raise ValueError('seed_levels must be None, one sequence of int '
+                         'levels shared by all streams, or [B, n]: the same '
+                         'number of seed levels for every stream')
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (B, a.shape[0]))
+    if a.shape[0] != B:
+        raise ValueError('seed_levels has %d rows for %d streams'
+                         % (a.shape[0], B))
+    if a.shape[1] < 1:
+        raise ValueError('seed_levels needs at least one level per stream')
+    if a.min() < 0 or a.max() > mol.TOP:
+        raise ValueError('seed_levels must lie in 0 .. %d' % mol.TOP)
+    return np.array(a, dtype=np.int32, order='C')   # (a writable copy)
+
+
+def _mol_last(last, B):
+    last = _batch_last(last, B)
+    if not isinstance(last, torch.Tensor) and last.size and \
+            (last.min() < 0 or last.max() > mol.TOP):
+        raise ValueError('last_levels must lie in 0 .. %d' % mol.TOP)
+    return last
+
+
+def mol_batch_reset(net, g):
+    _lib.call('wn_fastgen_mol_init', _lib.ptr(g['state']), g['state'].numel(),
+              _lib.ptr(g['cursors']), _lib.ptr(g['hist']), g['B'],
+              _lib.stream())
+    g['steps'] = 0
+    if g['restarted']:
+        g['origin'].zero_()
+        g['restarted'] = False
+
+
+def generate_mixture_batch(net, num_samples, seeds, seed_levels, temperature,
+                           global_condition, return_params_every, lc=None,
+                           reserve_steps=None):
+    _mol_need(net, 'generate_mixture_batch', 'generate_batch')
+    reserve = _reserve_arg(reserve_steps)
+
+    def per_stream(B):
+        levels = _mol_levels(seed_levels, B)
+        if not net.Lc and lc is None:
+            return levels, None
+        return levels, lcond.fastgen_rows(
+            net, lc, 'generate_mixture_batch',
+            levels.shape[1] + int(num_samples) - 1, B)
+    sd, (levels, lc), gc, n = _batch_args(net, seeds, per_stream,
+                                          global_condition, temperature,
+                                          num_samples, mixture=True)
+    B, n_given = levels.shape
+    lc = _lc_device(net, lc)
+    out = torch.zeros((B, n_given + n), dtype=torch.int32, device=net.device)
+    out[:, :n_given] = torch.from_numpy(levels).to(net.device)
+    g = batch_generator(net, B)
+    mol_batch_reset(net, g)
+    g['reserve'] = reserve
+
+    def prime():
+        # ONE forward pass per distinct (seed, GC id, LC rows), as
+        # generate_batch; the history gets the seed's last 64 levels
+        mol_batch_reset(net, g)
+        n0, groups = n_given - 1, {}
+        lch = None if lc is None else lc[:, :n0].cpu().numpy()
+        for b in range(B):
+            key = (levels[b, :n0].tobytes(),
+                   None if gc is None else int(gc[b]),
+                   None if lch is None else lch[b % len(lch)].tobytes())
+            groups.setdefault(key, []).append(b)
+        _prime(net, g, n0, [
+            (torch.from_numpy(np.ascontiguousarray(levels[s[0], :n0])),
+             None if gc is None else gc[s[0]:s[0] + 1], s,
+             None if lc is None else lc[s[0] % lc.shape[0], :n0])
+            for s in groups.values()], g['Bp'])
+        g['cursors'][0] = n0
+        t = np.arange(max(0, n0 - MOL_HIST), n0)
+        hist = np.full((g['Bp'], MOL_HIST), -1, np.int32)
+        hist[:B, t % MOL_HIST] = levels[:, t]
+        g['hist'].copy_(torch.from_numpy(hist))
+        g['steps'] = n0
+    pe = int(return_params_every)
+    params = _seeded(net, out, n_given, n, pe, prime, functools.partial(
+        _batch_run, net, g, temperature, sd, gc), lc, (3, net.mol_K))
+    return (out, params) if pe > 0 else out
+
+
+def continue_mixture_batch(net, num_samples, last_levels, seeds, temperature,
+                           global_condition, return_params_every, lc=None,
+                           restart=None, reserve_steps=None):
+    _mol_need(net, 'continue_mixture_batch', 'continue_generation_batch')
+    reserve = _reserve_arg(reserve_steps)
+    restart = _batch_restart_arg(restart, len(seeds))
+
+    def per_stream(B):
+        last = _mol_last(last_levels, B)
+        if not net.Lc and lc is None:
+            return last, None
+        return last, lcond.fastgen_rows(net, lc, 'continue_mixture_batch',
+                                        int(num_samples), B)
+    sd, (last, lc), gc, n = _batch_args(net, seeds, per_stream,
+                                        global_condition, temperature,
+                                        num_samples, mixture=True)
+    B = len(sd)
+    g = net._bgen
+    if g is None or g['B'] != B:
+        raise RuntimeError('no batched generation of %d streams to '
+                           'continue: call generate_mixture_batch first' % B)
+    lc = _lc_device(net, lc)
+    io = torch.zeros((B, n + 1), dtype=torch.int32, device=net.device)
+    io[:, 0] = last if isinstance(last, torch.Tensor) else \
+        torch.from_numpy(last).to(net.device)
+    g['reserve'] = reserve
+    if restart:
+        flags = np.zeros(g['Bp'], np.int32)
+        flags[restart] = 1
+        g['flags'].copy_(torch.from_numpy(flags))
+        _lib.call('wn_fastgen_mol_restart', _lib.ptr(g['state']),
+                  _lib.ptr(g['dil']), net.L, B, _lib.ptr(g['cursors']),
+                  _lib.ptr(g['hist']), _lib.ptr(g['origin']),
+                  _lib.ptr(g['flags']), _lib.stream())
+        g['restarted'] = True
+    pe = int(return_params_every)
+    params = _seeded(net, io, 1, n, pe, None, functools.partial(
+        _batch_run, net, g, temperature, sd, gc), lc, (3, net.mol_K))
+    return (io[:, 1:], params) if pe > 0 else io[:, 1:]

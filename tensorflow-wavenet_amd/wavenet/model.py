@@ -343,8 +343,8 @@ class WaveNetModel(object):
     LC_SUPPORTED = ('local conditioning is supported for residual / dilation '
                     'channels <= 32, filter_width 2 and one-hot input, or '
                     'scalar_input with a mixture-of-logistics head '
-                    '(output_mixture: training, scoring and predict_mixture, '
-                    'not yet fast generation), on the persistent stack '
+                    '(output_mixture: training, scoring, predict_mixture and '
+                    'generate_mixture_batch), on the persistent stack '
                     'launches (stack_fwd / stack_bwd = True)')
     LC_UPSAMPLE_MAX_LAYERS = 8
     LC_UPSAMPLE_MAX_HOP = 4096
@@ -1395,6 +1395,84 @@ class WaveNetModel(object):
             self, num_samples, last_samples, seeds, temperature,
             global_condition, return_proba_every, local_condition, top_k,
             top_p, restart, reserve_steps)
+
+    # ---- mixture-of-logistics models (output_mixture=K): the batched
+    # generator on levels (csrc/wn_fastgen_mol.hip)
+    def generate_mixture_batch(self, num_samples, seeds, seed_levels=None,
+                               temperature=1.0, global_condition=None,
+                               return_params_every=0, *, local_condition=None,
+                               reserve_steps=None):
+        """`generate_batch` for a model built with output_mixture=K: B =
+        len(seeds) independent streams in lock step (1 <= B <= 256), each
+        drawing 16-bit levels from its mixture as mol.sample does, with
+        seeds[b] and counter = the stream's step (the seed's steps count).
+        seed_levels: None (level 32768 for every stream), one sequence of
+        levels (ints in 0 .. 65535) shared by all streams, or [B, n];
+        temperature >= 0 (0: the mean of the drawn component).  Returns int32
+        levels [B, n + num_samples]; with return_params_every = k also
+        float32 [B, ceil(steps / k), 3, K], the format of predict_mixture
+        (log_softmax(pi), mu, clamped beta) of every k-th step.  A stream's
+        levels and parameter bits do not depend on the other streams.
+
+        global_condition, local_condition, reserve_steps: as generate_batch's.
+        Limits: at most 32 residual / dilation channels, filter_width 2,
+        initial_filter_width 1 .. 32, skip_channels <= 512, 64 layers."""
+        if self.Lc and local_condition is None and self.mol_K:
+            lcond.refuse_fastgen(self, 'generate_mixture_batch')
+        return fastgen.generate_mixture_batch(
+            self, num_samples, seeds, seed_levels, temperature,
+            global_condition, return_params_every, local_condition,
+            reserve_steps)
+
+    def continue_mixture_batch(self, num_samples, last_levels, seeds,
+                               temperature=1.0, global_condition=None,
+                               return_params_every=0, *, local_condition=None,
+                               restart=None, reserve_steps=None):
+        """Draw `num_samples` more levels for every stream of the last
+        generate_mixture_batch call, as continue_generation_batch does for
+        codes: last_levels[b] is stream b's last level so far, not yet
+        pushed.  Returns int32 [B, num_samples] (and the parameters, as
+        generate_mixture_batch).  restart: stream indices that start over
+        with this call (empty history, zero queues, the draw counted from
+        this call's first step); bit for bit a fresh stream from there on."""
+        if self.Lc and local_condition is None and self.mol_K:
+            lcond.refuse_fastgen(self, 'continue_mixture_batch')
+        return fastgen.continue_mixture_batch(
+            self, num_samples, last_levels, seeds, temperature,
+            global_condition, return_params_every, local_condition, restart,
+            reserve_steps)
+
+    def generate_mixture(self, num_samples, seed_levels=None, temperature=1.0,
+                         global_condition=None, seed=0,
+                         return_params_every=0, *, local_condition=None,
+                         reserve_steps=None):
+        """generate_mixture_batch with one stream, squeezed: int32 levels
+        [n + num_samples] (and float32 [rows, 3, K]).  It runs on the batched
+        generator's state (there is no single-stream kernel for levels), so a
+        generate_mixture_batch call in between starts that state over."""
+        lc = local_condition
+        if lc is not None and np.ndim(lc) == 2:
+            lc = lc[None]
+        out = self.generate_mixture_batch(
+            num_samples, [seed], seed_levels, temperature, global_condition,
+            return_params_every, local_condition=lc,
+            reserve_steps=reserve_steps)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
+
+    def continue_mixture(self, num_samples, last_level, temperature=1.0,
+                         global_condition=None, seed=0,
+                         return_params_every=0, *, local_condition=None,
+                         reserve_steps=None):
+        """continue_mixture_batch with one stream, squeezed; it continues
+        the batched generator's state that generate_mixture left."""
+        lc = local_condition
+        if lc is not None and np.ndim(lc) == 2:
+            lc = lc[None]
+        out = self.continue_mixture_batch(
+            num_samples, [int(last_level)], [seed], temperature,
+            global_condition, return_params_every, local_condition=lc,
+            reserve_steps=reserve_steps)
+        return (out[0][0], out[1][0]) if isinstance(out, tuple) else out[0]
 
     def batch_local_condition(self, items, position, num_steps):
         """The local_condition rows [B, num_steps, Lc] (device float32) of a

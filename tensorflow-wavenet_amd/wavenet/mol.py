@@ -18,9 +18,12 @@ TOP = LEVELS - 1
 MAX_COMPONENTS = 32
 LOG_SCALE_MIN_RANGE = (-32.0, -1.0)
 # what stays refused for these models, named in every such error
-FOLLOW_UP = ('fast and batched generation for scalar-input and mixture '
-             'models is the follow-up; generate naively (generate.py '
-             '--fast_generation false)')
+FOLLOW_UP = ('a mixture model generates fast through generate_mixture / '
+             'generate_mixture_batch (generate.py --fast_mixture true); the '
+             'single-stream persistent kernels, bulk synthesis and '
+             'evaluate.py --synthesis for mixture models, and scalar-input '
+             'softmax models, are the follow-up; generate naively '
+             '(generate.py --fast_generation false)')
 _M64 = (1 << 64) - 1
 
 
